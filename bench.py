@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - images/sec of one TAM-TR training step (fwd + 12-term RIOU loss + bwd + AdamW) at 640x640, bs 16 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32] [--no-cpu-baseline] [--dump-outputs DIR]
     N > 1: either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py
     --gpus N ...: RANK / WORLD_SIZE in the environment) or plainly as `python bench.py --gpus N`: with no WORLD_SIZE in the environment
     the script starts its own N ranks as a CHILD `torch.distributed.run` (before anything touches the GPU), relays their output and
@@ -26,6 +26,14 @@ figure between two eager passes (`eager_noise_*`: MIOpen's split-K / atomic solv
 `config.static_part_check`: the capture-time check (GraphedPart.verify: token memory and all 552 parameter gradients of a replay
 against eager execution).  `host_cpu_ms_per_step`: process CPU time (user + system, all threads of the rank) per timed step, max and
 per rank - the share of a step the host spends issuing work, which is what N ranks on one host compete for.
+`--dump-outputs DIR`: rank 0 writes what the last timed step computed as DIR/<name>.npy (float32, see dump_outputs).  So that this
+depends on the arguments alone, the last timed step starts again from the state the first warm-up step started from (weights,
+BatchNorm statistics, a fresh AdamW, EMA, random generators: TrainingStart).  The restore runs between two device fences and is left
+out of `ms_per_step` and `host_cpu_ms_per_step`; the extra drain still adds ~0.2 % to the figure.  Without the restore the step's inputs
+would be the end of a trajectory that parts between runs: MIOpen's atomic weight-gradient solvers make one step's gradients differ
+by ~1e-5 (rel. L2) from run to run, and one step later the gradients are uncorrelated.  Measured on MI355X, bf16, two runs of
+--steps 10 --warmup 3: loss and terms bit-identical, gradients 8e-6 (rel. L2), weights 2e-9.  Without the flag every timed step
+continues the training run, as before.
 `config.conv_tuning`: how MIOpen picked the trunk's convolution kernels (tam-tr_amd/tuning.py: its own timed search, looked up in immediate mode from
 the tables shipped in the repo).  `config.static_part`: "hip-graph" when the shape-static part of the step (trunk, VSS blocks, input projection: ~3/4 of the
 launches) is replayed as two HIP graphs (model.capture_static_part), "eager" otherwise (--static-part eager).
@@ -282,6 +290,60 @@ def other_kernels(args, dev):
     return out
 
 
+class TrainingStart:
+    """--dump-outputs: the training state before the first step, put back before the last timed step.  Model state (parameters,
+    BatchNorm statistics and counters) and EMA weights are copied back in place (recorded graphs keep their addresses), the optimizer
+    state is zeroed (exp_avg, exp_avg_sq, step: what a fresh AdamW starts from), the bf16 weight copies are re-derived and the EMA
+    update count and the host and device random generators are reset."""
+
+    def __init__(self, model, ema, opt, stepper):
+        self.opt, self.ema, self.stepper = opt, ema, stepper
+        live = list(model.state_dict().values()) + list(ema.ema.state_dict().values())
+        self.groups = [[t for t in live if t.dtype == dt] for dt in dict.fromkeys(t.dtype for t in live)]   # one multi-tensor copy per dtype
+        self.saved = [[t.clone() for t in g] for g in self.groups]
+        self.updates = ema.updates
+        self.rng = torch.get_rng_state(), torch.cuda.get_rng_state()
+
+    @torch.no_grad()
+    def restore(self):
+        for live, saved in zip(self.groups, self.saved):
+            torch._foreach_copy_(live, saved)
+        state = [t for st in self.opt.state.values() for t in st.values() if torch.is_tensor(t)]
+        if state:
+            torch._foreach_zero_(state)
+        if self.stepper is not None:
+            self.stepper.refresh_shadows()
+        self.ema.updates = self.updates
+        torch.set_rng_state(self.rng[0])
+        torch.cuda.set_rng_state(self.rng[1])
+
+
+DUMP_SAMPLE = 1 << 21   # positions kept of each large output (8 MiB in float32)
+
+
+def dump_outputs(out_dir, model, ema, loss, items):
+    """--dump-outputs: the last timed step's results as float32 .npy files under out_dir (~24 MiB in all).  Whole: `loss`, `loss_items`
+    (giou, class, bbox: what model(batch) returns next to the loss) and `loss_terms` (the 12 summed terms).  Sampled at DUMP_SAMPLE
+    positions drawn with a fixed seed from the concatenation of the tensors in parameter / state_dict order: `grads` (the parameter
+    gradients the optimizer step read, after clipping), `weights` (the model's floating-point state after the step: parameters and
+    BatchNorm statistics) and `ema_weights`."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(tensors, seed):
+        flat = torch.cat([t.detach().float().reshape(-1) for t in tensors])
+        pick = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(seed))[:DUMP_SAMPLE].sort().values
+        return flat[pick.to(flat.device)]
+    params = [p for p in model.parameters() if p.requires_grad]
+    outs = {'loss': loss.detach().float().reshape(()), 'loss_items': items.float(),
+            'loss_terms': torch.stack([v.float().reshape(()) for v in model.last_loss_terms.values()]),
+            'grads': sample([p.grad if p.grad is not None else torch.zeros_like(p) for p in params], 1),
+            'weights': sample([v for v in model.state_dict().values() if v.dtype.is_floating_point], 2),
+            'ema_weights': sample([v for v in ema.ema.state_dict().values() if v.dtype.is_floating_point], 3)}
+    for name, t in outs.items():
+        np.save(os.path.join(out_dir, name + '.npy'), t.cpu().numpy().astype(np.float32))
+
+
 def _brief(chk):
     if not chk:
         return None
@@ -315,7 +377,12 @@ def main():
                     help='clip + AdamW + EMA as the table-driven kernels of csrc/optim.hip (engine.FusedOptimStep) or as the three torch calls')
     ap.add_argument('--no-graph-check', action='store_true', help='skip the graph-vs-eager step and the standalone roofline_other launches after the timed loop (profiling runs: keeps the trace to the timed steps)')
     ap.add_argument('--cpu-baseline-images', type=int, default=8, help='images of the CPU-oracle sample (BASELINE configs[0]: 8)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="write the last timed step's loss, loss terms and a fixed sample of the gradients, weights and EMA weights as "
+                         'DIR/<name>.npy (float32; rank 0); that step starts from the state before the first step (see the docstring)')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
 
     import tamtr_amd  # noqa: F401  (raises if the HIP library is missing; loading it does not touch the GPU)
     from tamtr_amd import dist as tdist
@@ -386,7 +453,7 @@ def main():
             torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.grad is not None], max_norm=0.1)
             opt.step()
             ema.update(model)
-        return loss
+        return loss, items
 
     def fence():
         if grouped:
@@ -433,6 +500,7 @@ def main():
                 model.release_static_part()
                 static_part = 'eager (another rank could not capture its static part)'
                 note(static_part)
+    start = TrainingStart(model, ema, opt, stepper) if args.dump_outputs else None
     note(f'model built on {world} GPU(s), dtype {args.dtype}; warm-up ({args.warmup} steps; the first one includes MIOpen kernel selection)')
     for i in range(args.warmup):
         t1 = time.perf_counter()
@@ -443,11 +511,18 @@ def main():
     timer.enabled = True
     c0 = time.process_time()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    paused = paused_cpu = 0.0
+    for i in range(args.steps):
+        if start is not None and i == args.steps - 1:   # --dump-outputs: the last step from the start state, the restore untimed
+            fence()
+            p0, q0 = time.perf_counter(), time.process_time()
+            start.restore()
+            fence()
+            paused, paused_cpu = time.perf_counter() - p0, time.process_time() - q0
+        loss, items = step()
     fence()
-    dt = time.perf_counter() - t0
-    host_ms = (time.process_time() - c0) / args.steps * 1e3   # CPU time of this rank's process (all threads) per step
+    dt = time.perf_counter() - t0 - paused
+    host_ms = (time.process_time() - c0 - paused_cpu) / args.steps * 1e3   # CPU time of this rank's process (all threads) per step
     timer.enabled = False
     host_all = [host_ms]
     if grouped:
@@ -459,6 +534,9 @@ def main():
         torch.distributed.all_reduce(h)
         host_all = h.tolist()
     note(f'timed {args.steps} steps: {dt / args.steps * 1e3:.1f} ms/step (host CPU {max(host_all):.1f} ms/step)')
+    if args.dump_outputs and rank == 0:   # before the graph check below, which clears the gradients
+        dump_outputs(args.dump_outputs, model, ema, loss, items)
+        note(f'outputs of the last timed step written to {args.dump_outputs}')
     gve = None
     if static_part == 'hip-graph' and not args.no_graph_check:   # the replayed path against kernel-by-kernel execution, at the end of the run (every rank: same work)
         if reducer is None:
