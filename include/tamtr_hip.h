@@ -530,6 +530,25 @@ int tamtr_box_refine_bwd(const float* gout, const float* out, const float* ref, 
  *      (tam-tr_amd/graphs.py: memset nodes do not survive AQL packet capture); TAMTR_EINVAL when the stream is not capturing. */
 int tamtr_graph_capture_census(void* stream, int* counts, int n_types);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Predictor postprocess.  Replaces the per-image loop of RTDETRPredictor.postprocess,
+ * ultralytics/models/rtdetrworld/predict.py:34-78 (xywh2xyxy, utils/ops.py:360-380; class max; `score > conf` and the
+ * optional class filter; torchvision.ops.nms on boxes shifted by cls * max_wh; boxes scaled to the original image):
+ *      preds   (T) [B, nq, nd]  eval output of the model: normalised cx cy w h, then nc = nd - 4 class scores; widened to fp32
+ *      orig_hw i32 [B, 2]       original image (h, w) of every image
+ *      classes i32 [n_classes]  class-id filter; NULL = every class (non-NULL with n_classes == 0 keeps nothing, as the reference)
+ *      out     f32 [B, nq, 6]   kept rows in NMS order: x1 y1 x2 y2 (pixels of the original image), score, cls; zero after counts[b]
+ *      keep    i32 [B, nq]      source query of each kept row, -1 after counts[b]
+ *      counts  i32 [B]          rows kept per image
+ *  Bit-exact with that rule in fp32, every operation rounded on its own; equal scores keep ascending query order (stable sort); the
+ *  IoU is torchvision's (no eps: 0/0 = NaN does not suppress) on the shifted boxes (shift 0 when single_cls), a row is suppressed when
+ *  IoU > iou compared in fp32 (csrc/predict.hip states how the Python op reproduces torchvision's double comparison).  One launch,
+ *  one workgroup per image; nothing is allocated, set or synchronised, so the call can be captured.
+ *  TAMTR_EINVAL: a NULL operand, B < 1, nq < 1, nd < 5, n_classes < 0, dtype not F32 / BF16.  TAMTR_EUNSUP: nq > 512. */
+int tamtr_detect_postprocess(const void* preds, int dtype, int B, int nq, int nd, const int32_t* orig_hw, float conf, float iou,
+                             int single_cls, float max_wh, const int32_t* classes, int n_classes, float* out, int32_t* keep,
+                             int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,236 @@
+// predict.hip - the predictor's postprocess for a whole batch in one launch (tamtr_detect_postprocess).
+//
+// Replaces the per-image loop of RTDETRPredictor.postprocess (ultralytics/models/rtdetrworld/predict.py:34-78): xywh -> xyxy
+// (utils/ops.py:360-380), class max, confidence (and class) filter, class-aware torchvision.ops.nms on boxes shifted by
+// cls * max_wh, scaling to the original image.  The host loop synchronises once per image (engine.nms copies an IoU matrix
+// back); here nothing leaves the device and the output has a fixed shape, so the call can be captured into a graph.
+//
+// Contract: bit-exact with that rule applied in fp32 to the input widened to fp32, every operation rounded on its own (the
+// object is compiled with -ffp-contract=off; the IoU division is the correctly rounded fp32 division):
+//   box     x1 = cx - w/2, x2 = cx + w/2 (same for y)
+//   score   max over the nc class scores, the lowest class index on ties; NaN anywhere in the row -> NaN score (torch.max)
+//   filter  score > conf, and cls in classes[] when a class filter is given
+//   NMS     shifted box = box + cls * (single_cls ? 0 : max_wh); area = (x2-x1)*(y2-y1); for a kept row i and a later row j
+//           (torchvision's nms_kernel.cpp, CPU, operand order included): xx1 = max(x1i, x1j) ... as std::max / std::min,
+//           w = max(0, xx2-xx1), h likewise, inter = w*h, iou = inter / (area_i + area_j - inter), no eps (0/0 = NaN, which
+//           does not suppress); j is suppressed when iou > thr.  Rows are visited in descending score order, stable
+//           (equal scores: ascending query index).
+//   Threshold rule: the comparison is done in fp32 against the float argument `iou`.  torchvision compares the float IoU
+//   with a double threshold; ops.detect_postprocess passes the largest fp32 <= the double threshold, for which
+//   `iou_f32 > thr_f32` and `iou_f32 > thr_f64` agree for every fp32 IoU, so the Python op reproduces torchvision's rule.
+//   output  kept rows in NMS order, unshifted, x *= w_orig, y *= h_orig, then score and float(cls); keep = source query.
+//
+// Design: one workgroup (8 waves) per image, nq <= 512, everything in LDS (about 59 KB):
+//   1. rows -> class max: a group of GW lanes (4, 16 or 64, chosen from nc) shares a row, so the class scores are read as
+//      consecutive elements instead of a 4 * nd byte stride per lane; (value, index) butterfly with the torch.max rule.
+//   2. 64-bit key (~ordered(score) << 32 | query) per row, all ones for rows that fail the filter; a bitonic sort over the
+//      next power of two puts the survivors first in NMS order (no separate compaction: the key already holds the query).
+//      The float -> ordered-integer map handles conf < 0; -0.0 is folded onto +0.0 so the two tie as torch's sort ties them.
+//   3. upper-triangular suppression mask, one 64-bit word per (row, 64-column block), built by whole waves: lane l computes
+//      iou(i, 64 w + l) and a ballot forms the word.
+//   4. greedy pass in wave 0 with no barrier: lane k holds removal word k; every row is tested with a readlane of its word.
+//   5. coalesced write of out / keep (zero / -1 padding after the count) and counts.
+#include "common.h"
+
+#define PP_MAX_Q 512
+#define PP_WORDS (PP_MAX_Q / 64)
+#define PP_THREADS 512
+
+// torch.max over a row: NaN wins (lowest index among NaNs), else the larger value, equal values -> the lower index
+__device__ __forceinline__ bool pp_better(float v, int i, float bv, int bi) {
+  const bool vn = v != v, bn = bv != bv;
+  if (vn || bn) return vn && (!bn || i < bi);
+  return v > bv || (v == bv && i < bi);
+}
+
+// float -> uint32 with the same order (ascending); -0.0 folded onto +0.0
+__device__ __forceinline__ uint32_t pp_ordered(float s) {
+  uint32_t u = s == 0.0f ? 0u : __float_as_uint(s);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// std::max / std::min as torchvision calls them: max(a, b) = a < b ? b : a, min(a, b) = b < a ? b : a
+__device__ __forceinline__ float pp_max(float a, float b) { return a < b ? b : a; }
+__device__ __forceinline__ float pp_min(float a, float b) { return b < a ? b : a; }
+
+struct PpShared {
+  float box[PP_MAX_Q][4];    // unshifted x1 y1 x2 y2 by query
+  float score[PP_MAX_Q];     // by query
+  int cls[PP_MAX_Q];         // by query
+  uint64_t key[PP_MAX_Q];    // sort keys; after the sort, position p holds the p-th row in NMS order
+  float sbox[PP_MAX_Q][4];   // shifted boxes in NMS order
+  float sarea[PP_MAX_Q];
+  uint64_t mask[PP_MAX_Q][PP_WORDS];
+  int kept[PP_MAX_Q];        // NMS positions of the kept rows, in order
+  int n, count;
+};
+
+template <typename T, int GW>
+__global__ __launch_bounds__(PP_THREADS) void detect_postprocess_kernel(const T* __restrict__ preds, int nq, int nd,
+                                                                        const int32_t* __restrict__ orig_hw, float conf, float thr,
+                                                                        int single_cls, float max_wh, const int32_t* __restrict__ classes,
+                                                                        int n_classes, float* __restrict__ out, int32_t* __restrict__ keep,
+                                                                        int32_t* __restrict__ counts) {
+  __shared__ PpShared s;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  const int nc = nd - 4;
+  const T* pb = preds + (size_t)b * nq * nd;
+  if (tid == 0) s.n = 0;
+  __syncthreads();
+
+  // ---- 1. class max, filter, sort key (a group of GW lanes per row)
+  const int sub = tid & (GW - 1);
+  int n_local = 0;
+  for (int q0 = 0; q0 < nq; q0 += PP_THREADS / GW) {
+    const int q = q0 + tid / GW;
+    const bool row = q < nq;  // uniform inside the group
+    float bv = __int_as_float(0xff800000), bx[4] = {0.f, 0.f, 0.f, 0.f};
+    int bi = 0x7fffffff;
+    if (row) {
+      const T* r = pb + (size_t)q * nd;
+      for (int c = sub; c < nc; c += GW) {
+        const float v = Elt<T>::ld(r + 4 + c);
+        if (pp_better(v, c, bv, bi)) { bv = v; bi = c; }
+      }
+      if (sub == 0)
+        for (int k = 0; k < 4; ++k) bx[k] = Elt<T>::ld(r + k);
+    }
+#pragma unroll
+    for (int o = GW / 2; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, WAVE);
+      const int oi = __shfl_xor(bi, o, WAVE);
+      if (pp_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
+    }
+    if (row && sub == 0) {
+      const float dw = bx[2] / 2.0f, dh = bx[3] / 2.0f;
+      s.box[q][0] = bx[0] - dw;
+      s.box[q][1] = bx[1] - dh;
+      s.box[q][2] = bx[0] + dw;
+      s.box[q][3] = bx[1] + dh;
+      s.score[q] = bv;
+      s.cls[q] = bi;
+      bool ok = bv > conf;
+      if (ok && classes) {
+        bool in = false;
+        for (int k = 0; k < n_classes; ++k) in |= classes[k] == bi;
+        ok = in;
+      }
+      s.key[q] = ok ? ((uint64_t)~pp_ordered(bv) << 32) | (uint32_t)q : ~0ull;
+      n_local += ok;
+    }
+  }
+  int P = 1;
+  while (P < nq) P <<= 1;
+  for (int q = nq + tid; q < P; q += PP_THREADS) s.key[q] = ~0ull;
+  if (n_local) atomicAdd(&s.n, n_local);
+  __syncthreads();
+  const int n = s.n;
+
+  // ---- 2. bitonic sort of P <= 512 keys, ascending (= NMS order; failed rows last)
+  for (int k = 2; k <= P; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const int i = tid, l = i ^ j;
+      if (i < P && l > i) {
+        const uint64_t a = s.key[i], c = s.key[l];
+        if ((a > c) == ((i & k) == 0)) { s.key[i] = c; s.key[l] = a; }
+      }
+      __syncthreads();
+    }
+  }
+
+  // shifted boxes and areas in NMS order
+  for (int p = tid; p < n; p += PP_THREADS) {
+    const int q = (int)(s.key[p] & 0xffffffffu);
+    const float sh = (float)s.cls[q] * (single_cls ? 0.0f : max_wh);
+    float bb[4];
+    for (int k = 0; k < 4; ++k) { bb[k] = s.box[q][k] + sh; s.sbox[p][k] = bb[k]; }
+    s.sarea[p] = (bb[2] - bb[0]) * (bb[3] - bb[1]);
+  }
+  __syncthreads();
+
+  // ---- 3. suppression mask: word (i, w) bit l = iou(i, 64 w + l) > thr for 64 w + l > i
+  const int nw = (n + WAVE - 1) / WAVE;
+  for (int t = wave; t < n * nw; t += PP_THREADS / WAVE) {
+    const int i = t / nw, w = t - i * nw, j = w * WAVE + lane;
+    uint64_t word = 0;
+    if (w * WAVE + WAVE - 1 > i) {  // uniform over the wave
+      bool sup = false;
+      if (j > i && j < n) {
+        const float ix1 = s.sbox[i][0], iy1 = s.sbox[i][1], ix2 = s.sbox[i][2], iy2 = s.sbox[i][3];
+        const float xx1 = pp_max(ix1, s.sbox[j][0]), yy1 = pp_max(iy1, s.sbox[j][1]);
+        const float xx2 = pp_min(ix2, s.sbox[j][2]), yy2 = pp_min(iy2, s.sbox[j][3]);
+        const float ww = pp_max(0.0f, xx2 - xx1), hh = pp_max(0.0f, yy2 - yy1);
+        const float inter = ww * hh;
+        const float ovr = inter / ((s.sarea[i] + s.sarea[j]) - inter);
+        sup = ovr > thr;
+      }
+      word = __ballot(sup);
+    }
+    if (lane == 0) s.mask[i][w] = word;
+  }
+  __syncthreads();
+
+  // ---- 4. greedy pass, one wave, no barrier: lane k < nw holds removal word k
+  if (wave == 0) {
+    uint64_t rem = 0;
+    int cnt = 0;
+    for (int i = 0; i < n; ++i) {
+      const int wi = i >> 6;
+      const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)rem, wi), hi = __builtin_amdgcn_readlane((uint32_t)(rem >> 32), wi);
+      const uint64_t rw = ((uint64_t)hi << 32) | lo;
+      if (!((rw >> (i & 63)) & 1ull)) {
+        if (lane == 0) s.kept[cnt] = i;
+        ++cnt;
+        if (lane < nw) rem |= s.mask[i][lane];
+      }
+    }
+    if (lane == 0) s.count = cnt;
+  }
+  __syncthreads();
+
+  // ---- 5. outputs: kept rows, then zero / -1 padding
+  const int cnt = s.count;
+  const float oh = (float)orig_hw[2 * b], ow = (float)orig_hw[2 * b + 1];
+  float* ob = out + (size_t)b * nq * 6;
+  for (int e = tid; e < nq * 6; e += PP_THREADS) {
+    const int r = e / 6, c = e - r * 6;
+    float v = 0.0f;
+    if (r < cnt) {
+      const int q = (int)(s.key[s.kept[r]] & 0xffffffffu);
+      v = c < 4 ? s.box[q][c] * ((c & 1) ? oh : ow) : c == 4 ? s.score[q] : (float)s.cls[q];
+    }
+    ob[e] = v;
+  }
+  for (int r = tid; r < nq; r += PP_THREADS) keep[(size_t)b * nq + r] = r < cnt ? (int)(s.key[s.kept[r]] & 0xffffffffu) : -1;
+  if (tid == 0) counts[b] = cnt;
+}
+
+template <typename T>
+static void pp_launch(const void* preds, int B, int nq, int nd, const int32_t* orig_hw, float conf, float iou, int single_cls, float max_wh,
+                      const int32_t* classes, int n_classes, float* out, int32_t* keep, int32_t* counts, hipStream_t st) {
+  const int nc = nd - 4;
+  const T* p = static_cast<const T*>(preds);
+  if (nc <= 8)
+    hipLaunchKernelGGL((detect_postprocess_kernel<T, 4>), dim3(B), dim3(PP_THREADS), 0, st, p, nq, nd, orig_hw, conf, iou, single_cls,
+                       max_wh, classes, n_classes, out, keep, counts);
+  else if (nc <= 32)
+    hipLaunchKernelGGL((detect_postprocess_kernel<T, 16>), dim3(B), dim3(PP_THREADS), 0, st, p, nq, nd, orig_hw, conf, iou, single_cls,
+                       max_wh, classes, n_classes, out, keep, counts);
+  else
+    hipLaunchKernelGGL((detect_postprocess_kernel<T, 64>), dim3(B), dim3(PP_THREADS), 0, st, p, nq, nd, orig_hw, conf, iou, single_cls,
+                       max_wh, classes, n_classes, out, keep, counts);
+}
+
+extern "C" int tamtr_detect_postprocess(const void* preds, int dtype, int B, int nq, int nd, const int32_t* orig_hw, float conf, float iou,
+                                        int single_cls, float max_wh, const int32_t* classes, int n_classes, float* out, int32_t* keep,
+                                        int32_t* counts, void* stream) {
+  if (!preds || !orig_hw || !out || !keep || !counts || B < 1 || nq < 1 || nd < 5 || n_classes < 0) return TAMTR_EINVAL;
+  if (dtype != TAMTR_F32 && dtype != TAMTR_BF16) return TAMTR_EINVAL;
+  if (nq > PP_MAX_Q) return TAMTR_EUNSUP;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == TAMTR_F32)
+    pp_launch<float>(preds, B, nq, nd, orig_hw, conf, iou, single_cls, max_wh, classes, n_classes, out, keep, counts, st);
+  else
+    pp_launch<bf16_t>(preds, B, nq, nd, orig_hw, conf, iou, single_cls, max_wh, classes, n_classes, out, keep, counts, st);
+  return tamtr_launch_status();
+}

@@ -1774,6 +1774,44 @@ def lsap_assign(cost, gt_groups):
     return out[0], out[1], out[2]
 
 
+def _f32_at_most(x):
+    """Largest float32 <= x: `iou_f32 > it` is then the same test as torchvision's `iou_f32 > x` in double."""
+    import numpy as np
+    f = np.float32(x)
+    return float(np.nextafter(f, np.float32(-np.inf)) if float(f) > x else f)
+
+
+@torch.no_grad()
+def detect_postprocess(y, orig_hw, conf, iou, classes=None, single_cls=False, max_wh=7680.):
+    """RTDETRPredictor.postprocess (models/rtdetrworld/predict.py:34-78) for the whole batch in one launch: class max,
+    `score > conf` (and the class filter), class-aware NMS with torchvision's rule, boxes scaled to the original images.
+    y (f32 / bf16) [B, nq, 4 + nc] eval output on the GPU; orig_hw [B, 2] (h, w) and classes: tensors or lists.
+    Returns device tensors out f32 [B, nq, 6] (x1 y1 x2 y2 score cls, zero after the count), keep i32 [B, nq] (source query,
+    -1 after the count), counts i32 [B].  No synchronisation (orig_hw / classes given as lists cost one small upload)."""
+    require_gpu(y)
+    if y.dim() != 3:
+        raise _lib.TamtrHipError(f'detect_postprocess: expected y [B, nq, 4 + nc], got {tuple(y.shape)}')
+    B, nq, nd = y.shape
+    dev = y.device
+    y = _c(y if y.dtype in (torch.float32, torch.bfloat16) else y.float())
+    hw = torch.as_tensor(orig_hw, dtype=torch.int32)
+    if tuple(hw.shape) != (B, 2):
+        raise _lib.TamtrHipError(f'detect_postprocess: orig_hw must be [B, 2] = [{B}, 2], got {tuple(hw.shape)}')
+    # an empty filter keeps nothing (the reference's `.any(1)` over no classes) and still needs a non-NULL pointer
+    cl = None if classes is None else torch.as_tensor(classes, dtype=torch.int32).reshape(-1)
+    n_cl = 0 if cl is None else cl.numel()
+    parts = [hw.reshape(-1)] + ([] if cl is None else [cl if n_cl else torch.zeros(1, dtype=torch.int32, device=hw.device)])
+    if not all(p.is_cuda for p in parts):   # host operands go up in one copy
+        parts = list(torch.cat([p.cpu() for p in parts]).to(dev, non_blocking=True).split([p.numel() for p in parts]))
+    hw, cl = _c(parts[0]), (_c(parts[1]) if cl is not None else None)
+    out = torch.empty(B, nq, 6, device=dev, dtype=torch.float32)
+    keep = torch.empty(B, nq, device=dev, dtype=torch.int32)
+    counts = torch.empty(B, device=dev, dtype=torch.int32)
+    call('tamtr_detect_postprocess', ptr(y), dtype_code(y), B, nq, nd, ptr(hw), float(conf), _f32_at_most(float(iou)), int(bool(single_cls)),
+         float(max_wh), ptr(cl) if cl is not None else None, n_cl, ptr(out), ptr(keep), ptr(counts), stream_ptr())
+    return out, keep, counts
+
+
 def img_augment(src, inv_affine, luts, flags, out_hw, border=114):
     """The pixel half of the training transforms for a whole batch (affine warp -> HSV look-up -> flips -> CHW float / 255;
     ultralytics/data/augment.py:415-420,590-609,636-666,920-926).  src u8 [B, SH, SW, 3], inv_affine f64 [B, 6]

@@ -1,0 +1,236 @@
+"""Batched image prediction (the reference's predictTAMTR.py / RTDETRPredictor flow): files -> scale-filled batches -> fused
+eval forward -> ops.detect_postprocess (one HIP launch per batch: class max, confidence / class filter, class-aware NMS,
+scaling to the original size) -> one device-to-host copy per batch -> Detections.
+
+    from tamtr_amd.predict import Predictor
+    for det in Predictor(model, names, text_features, conf=0.4, iou=0.6).predict('images/'):
+        det.save_txt(...); det.save(...)
+"""
+import os
+import time
+from concurrent.futures import ThreadPoolExecutor
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from . import data as D, ops
+
+
+# ------------------------------------------------------------------------------------------------ files
+def is_image_file(path):
+    return os.path.isfile(path) and str(path).rsplit('.', 1)[-1].lower() in D.IMG_FORMATS
+
+
+def list_sources(source):
+    """One image file, a directory (recursive) or a list file -> sorted image paths.  An image is recognised by its extension
+    before data.list_images, which reads any other existing file as a list of paths."""
+    if isinstance(source, (str, os.PathLike)) and is_image_file(str(source)):
+        return [str(source)]
+    return D.list_images(source)
+
+
+def increment_path(path, exist_ok=False, sep='', mkdir=False):
+    """runs/predict/TAMTR -> runs/predict/TAMTR2, TAMTR3, ... when it exists (ultralytics/utils/files.py:85-117)."""
+    path = Path(path)
+    if path.exists() and not exist_ok:
+        path, suffix = (path.with_suffix(''), path.suffix) if path.is_file() else (path, '')
+        for n in range(2, 9999):
+            p = f'{path}{sep}{n}{suffix}'
+            if not os.path.exists(p):
+                break
+        path = Path(p)
+    if mkdir:
+        path.mkdir(parents=True, exist_ok=True)
+    return path
+
+
+def allowed_cpus(cap=16):
+    """CPUs this process may run on (not the machine's count), at most `cap`."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except AttributeError:
+        n = os.cpu_count() or 1
+    return max(1, min(cap, n))
+
+
+def letterbox_scalefill(im, imgsz):
+    """LetterBox(imgsz, auto=False, scaleFill=True) (models/rtdetrworld/predict.py:80-92): a plain cv2 INTER_LINEAR resize to
+    imgsz x imgsz, no padding; an image already at that size is returned as it is."""
+    h, w = im.shape[:2]
+    return im if (h, w) == (imgsz, imgsz) else D.resize_linear_u8(im, imgsz, imgsz)
+
+
+def load_image(path, imgsz):
+    """-> (original RGB u8 [h, w, 3], network input u8 [imgsz, imgsz, 3])."""
+    im = D.decode_image(path)
+    return im, letterbox_scalefill(im, imgsz)
+
+
+def to_model_input(ims_u8, device):
+    """u8 [B, S, S, 3] host batch -> f32 [B, 3, S, S] / 255 on the device (engine/predictor.py:111-129: RGB, CHW, float, / 255)."""
+    t = torch.from_numpy(ims_u8)
+    if device.type == 'cuda':
+        t = t.pin_memory().to(device, non_blocking=True)
+    return t.permute(0, 3, 1, 2).contiguous().float() / 255
+
+
+# ------------------------------------------------------------------------------------------------ results
+class Detections:
+    """The boxes of one image (engine/results.py Results + Boxes, detection only): boxes f32 [n, 6] on the host, x1 y1 x2 y2 in
+    pixels of the original image, score, class."""
+
+    def __init__(self, path, orig_shape, names, boxes, orig_img=None):
+        self.path, self.orig_shape, self.names = path, tuple(orig_shape), names
+        self.boxes = boxes
+        self.orig_img = orig_img
+
+    def __len__(self):
+        return len(self.boxes)
+
+    @property
+    def xyxy(self):
+        return self.boxes[:, :4]
+
+    @property
+    def conf(self):
+        return self.boxes[:, 4]
+
+    @property
+    def cls(self):
+        return self.boxes[:, 5]
+
+    @property
+    def xywhn(self):
+        """xyxy2xywh (utils/ops.py:336-356), then / (w, h) of the original image (engine/results.py:436-441)."""
+        x = self.xyxy
+        y = torch.empty_like(x)
+        y[:, 0] = (x[:, 0] + x[:, 2]) / 2
+        y[:, 1] = (x[:, 1] + x[:, 3]) / 2
+        y[:, 2] = x[:, 2] - x[:, 0]
+        y[:, 3] = x[:, 3] - x[:, 1]
+        y[:, [0, 2]] /= self.orig_shape[1]
+        y[:, [1, 3]] /= self.orig_shape[0]
+        return y
+
+    def save_txt(self, txt_file, save_conf=False):
+        """`cls x y w h [conf]` per box, '%g'-formatted, appended; no file when there is no box (engine/results.py:278-311)."""
+        if not len(self):
+            return
+        texts = []
+        for c, xywhn, conf in zip(self.cls.tolist(), self.xywhn.tolist(), self.conf.tolist()):
+            line = (int(c), *xywhn) + (conf,) * save_conf
+            texts.append(('%g ' * len(line)).rstrip() % line)
+        Path(txt_file).parent.mkdir(parents=True, exist_ok=True)
+        with open(txt_file, 'a') as f:
+            f.writelines(t + '\n' for t in texts)
+
+    def save(self, path, line_width=None):
+        """An annotated copy of the original image (boxes and `name score` labels, drawn with PIL)."""
+        from PIL import Image, ImageDraw
+        im = Image.fromarray(self.orig_img if self.orig_img is not None else D.decode_image(self.path))
+        draw = ImageDraw.Draw(im)
+        lw = line_width or max(round(sum(im.size) / 2 * 0.003), 2)
+        for (x1, y1, x2, y2), conf, c in zip(self.xyxy.tolist(), self.conf.tolist(), self.cls.tolist()):
+            color = _COLORS[int(c) % len(_COLORS)]
+            draw.rectangle((x1, y1, x2, y2), outline=color, width=lw)
+            label = f'{self.names.get(int(c), int(c))} {conf:.2f}'
+            l, t, r, b = draw.textbbox((x1, y1), label)
+            top = y1 - (b - t) - 2 if y1 - (b - t) - 2 >= 0 else y1
+            draw.rectangle((x1, top, x1 + (r - l) + 2, top + (b - t) + 2), fill=color)
+            draw.text((x1 + 1, top), label, fill=(255, 255, 255))
+        Path(path).parent.mkdir(parents=True, exist_ok=True)
+        im.save(path)
+
+
+_COLORS = [(255, 56, 56), (255, 157, 151), (255, 112, 31), (255, 178, 29), (207, 210, 49), (72, 249, 10), (146, 204, 23), (61, 219, 134),
+           (26, 147, 52), (0, 212, 187), (44, 153, 168), (0, 194, 255), (52, 69, 147), (100, 115, 255), (0, 24, 236), (132, 56, 255),
+           (82, 0, 133), (203, 56, 255), (255, 149, 200), (255, 55, 199)]
+
+
+# ------------------------------------------------------------------------------------------------ the predictor
+class Predictor:
+    """model: RTDETRDetectionWorldModel on the GPU; names: {id: name} or a list; text_features: data.TextFeatures (encodes the
+    names, first synonym of a 'a/b' entry) or a ready [nc, d] tensor.  Defaults are the reference's (cfg/default.yaml:47-49,68).
+    keep_raw=True keeps the last batch's model input (`last_img`) and raw eval output (`last_y`) for inspection."""
+
+    def __init__(self, model, names, text_features, imgsz=640, conf=0.25, iou=0.7, classes=None, single_cls=False, batch=4, dtype='bf16',
+                 keep_raw=False, workers=None):
+        if dtype not in ('bf16', 'fp32'):
+            raise ValueError(f"dtype must be 'bf16' or 'fp32', got {dtype!r}")
+        self.names = names if isinstance(names, dict) else dict(enumerate(names))
+        self.imgsz, self.conf, self.iou, self.single_cls, self.batch = int(imgsz), float(conf), float(iou), bool(single_cls), int(batch)
+        self.classes = None if classes is None else [int(c) for c in ([classes] if isinstance(classes, int) else classes)]
+        self.autocast_dtype = torch.bfloat16 if dtype == 'bf16' else None
+        self.keep_raw = keep_raw
+        self.workers = workers or allowed_cpus()
+        self.device = next(model.parameters()).device
+        if self.device.type != 'cuda':
+            raise ops._lib.TamtrHipError('Predictor needs the model on an MI355X; there is no CPU path')
+        if isinstance(text_features, D.TextFeatures):
+            tf = text_features.encode([str(v).split('/')[0] for v in self.names.values()])
+        else:
+            tf = torch.as_tensor(text_features, dtype=torch.float32)
+        model.eval()
+        model.fuse()   # what AutoBackend(fuse=True) does; a no-op once fused
+        model.set_text_features(tf.reshape(1, len(self.names), -1).to(self.device))
+        model.autocast_dtype = self.autocast_dtype
+        self.model = model
+        self.times = {'load': 0.0, 'h2d': 0.0, 'forward': 0.0, 'postprocess': 0.0, 'd2h': 0.0}   # ms, summed over batches
+        self.seen = 0
+        self.last_img = self.last_y = None
+
+    @torch.no_grad()
+    def run_batch(self, ims):
+        """Network inputs u8 [B, S, S, 3] (host) + original (h, w) per image -> host (out [B, nq, 6], keep [B, nq], counts [B])."""
+        arr, hw = ims
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+        ev[0].record()
+        img = to_model_input(arr, self.device)
+        ev[1].record()
+        with torch.autocast('cuda', dtype=self.autocast_dtype or torch.bfloat16, enabled=self.autocast_dtype is not None):
+            preds = self.model(img)
+        y = preds[0] if isinstance(preds, (list, tuple)) else preds
+        ev[2].record()
+        out, keep, counts = ops.detect_postprocess(y, hw, self.conf, self.iou, self.classes, self.single_cls)
+        ev[3].record()
+        # one device-to-host copy for the three outputs
+        B, nq = keep.shape
+        packed = torch.cat([out.view(-1), keep.view(torch.float32).view(-1), counts.view(torch.float32)])
+        host = torch.empty(packed.shape, dtype=torch.float32, pin_memory=True)
+        host.copy_(packed, non_blocking=True)
+        ev[4].record()
+        ev[4].synchronize()
+        for k, (a, b) in zip(('h2d', 'forward', 'postprocess', 'd2h'), zip(ev[:-1], ev[1:])):
+            self.times[k] += a.elapsed_time(b)
+        if self.keep_raw:
+            self.last_img, self.last_y = img, y
+        o, kp, c = host.split([B * nq * 6, B * nq, B])
+        return o.view(B, nq, 6), kp.view(torch.int32).view(B, nq), c.view(torch.int32)
+
+    def predict(self, source):
+        """Yields one Detections per image, in the sorted order of list_sources(source)."""
+        files = list_sources(source)
+        with ThreadPoolExecutor(max_workers=self.workers) as pool:
+            chunks = [files[i:i + self.batch] for i in range(0, len(files), self.batch)]
+            pending = [pool.submit(load_image, f, self.imgsz) for f in chunks[0]] if chunks else []
+            for k, chunk in enumerate(chunks):
+                t0 = time.perf_counter()
+                loaded = [f.result() for f in pending]
+                self.times['load'] += (time.perf_counter() - t0) * 1e3
+                # the next batch decodes while this one runs on the GPU
+                pending = [pool.submit(load_image, f, self.imgsz) for f in chunks[k + 1]] if k + 1 < len(chunks) else []
+                origs = [o for o, _ in loaded]
+                hw = [o.shape[:2] for o in origs]
+                out, keep, counts = self.run_batch((np.stack([r for _, r in loaded]), hw))
+                self.seen += len(chunk)
+                for i, path in enumerate(chunk):
+                    n = int(counts[i])
+                    yield Detections(path, hw[i], self.names, out[i, :n].clone(), orig_img=origs[i])
+
+    def __call__(self, source):
+        return list(self.predict(source))
+
+    def speed(self):
+        """ms per image of each phase so far (load = waiting for decoded + resized images; the rest from device events)."""
+        return {k: v / max(self.seen, 1) for k, v in self.times.items()}

@@ -1,0 +1,88 @@
+#!/usr/bin/env python3
+"""Run a checkpoint on images (the reference's predictTAMTR.py flow): boxes per image, optional annotated copies and YOLO-format
+label files under an incremented --project/--name folder; one JSON line at the end.
+
+    python tools/predict.py --weights runs/train/TAMTR/best.pt --text-feats clip_vitb32.npz --data dataset.yaml \
+        --source images/ --conf 0.4 --iou 0.6 --batch 4 --save [--save-txt --save-conf]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description='TAM-TR prediction on images (one HIP postprocess launch per batch)')
+    ap.add_argument('--weights', required=True, help="checkpoint written by training ({'model', 'ema', ...} state_dicts)")
+    ap.add_argument('--raw', action='store_true', help='use the raw weights instead of the EMA copy')
+    ap.add_argument('--text-feats', required=True, help='.npz {texts, feats} or a torch-saved {text: vector}')
+    g = ap.add_mutually_exclusive_group(required=True)
+    g.add_argument('--data', help="dataset yaml whose 'names' are the classes")
+    g.add_argument('--names', help='comma-separated class names')
+    ap.add_argument('--source', required=True, help='an image file, a directory of images, or a list file')
+    ap.add_argument('--imgsz', type=int, default=640)
+    ap.add_argument('--batch', type=int, default=4)
+    ap.add_argument('--conf', type=float, default=0.25)
+    ap.add_argument('--iou', type=float, default=0.7)
+    ap.add_argument('--classes', type=int, nargs='+', default=None, help='keep only these class ids')
+    ap.add_argument('--single-cls', action='store_true', help='class-agnostic NMS')
+    ap.add_argument('--save', action='store_true', help='write annotated images')
+    ap.add_argument('--save-txt', action='store_true', help='write labels/<stem>.txt: cls x y w h (normalised)')
+    ap.add_argument('--save-conf', action='store_true', help='append the score to every label line')
+    ap.add_argument('--project', default='runs/predict')
+    ap.add_argument('--name', default='TAMTR')
+    ap.add_argument('--exist-ok', action='store_true', help='reuse --project/--name instead of incrementing it')
+    ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
+    return ap.parse_args(argv)
+
+
+def load_names(args):
+    if args.names:
+        return dict(enumerate(n.strip() for n in args.names.split(',')))
+    import yaml
+    with open(args.data) as f:
+        names = yaml.safe_load(f)['names']
+    return names if isinstance(names, dict) else dict(enumerate(names))
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import torch
+    import tamtr_amd  # noqa: F401
+    from tamtr_amd import data as D
+    from tamtr_amd.model import RTDETRDetectionWorldModel
+    from tamtr_amd.predict import Predictor, increment_path
+
+    dev = torch.device('cuda', 0)
+    names = load_names(args)
+    model = RTDETRDetectionWorldModel(nc=len(names)).to(dev)
+    ck = torch.load(args.weights, map_location=dev)
+    model.load_state_dict(ck['model' if args.raw else 'ema'])
+    pred = Predictor(model, names, D.TextFeatures.load(args.text_feats), imgsz=args.imgsz, conf=args.conf, iou=args.iou,
+                     classes=args.classes, single_cls=args.single_cls, batch=args.batch, dtype=args.dtype)
+    save_dir = increment_path(os.path.join(args.project, args.name), exist_ok=args.exist_ok)
+    if args.save or args.save_txt:
+        (save_dir / 'labels' if args.save_txt else save_dir).mkdir(parents=True, exist_ok=True)
+    n_img = n_det = 0
+    t0 = time.perf_counter()
+    for det in pred.predict(args.source):
+        n_img += 1
+        n_det += len(det)
+        stem = os.path.splitext(os.path.basename(det.path))[0]
+        if args.save_txt:
+            det.save_txt(save_dir / 'labels' / f'{stem}.txt', save_conf=args.save_conf)
+        if args.save:
+            det.save(save_dir / os.path.basename(det.path))
+    wall = time.perf_counter() - t0
+    sp = pred.speed()
+    print(json.dumps({'images': n_img, 'detections': n_det, 'save_dir': str(save_dir) if (args.save or args.save_txt) else None,
+                      'ms_per_image': {'load': round(sp['load'], 3), 'forward': round(sp['h2d'] + sp['forward'], 3),
+                                       'postprocess': round(sp['postprocess'] + sp['d2h'], 3)},
+                      'wall_s': round(wall, 3), 'dtype': args.dtype, 'imgsz': args.imgsz, 'batch': args.batch}))
+
+
+if __name__ == '__main__':
+    main()

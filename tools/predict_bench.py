@@ -1,0 +1,160 @@
+#!/usr/bin/env python3
+"""Predictor measurements (profiles/r05_predict.txt):
+
+  (a) postprocess of one batch, B = 16, nq = 300, nc = 10 and 80: ops.detect_postprocess (one HIP launch) against the per-image
+      torch path that RTDETRPredictor.postprocess implies (models/rtdetrworld/predict.py:34-78), run on the device with the
+      project's host NMS (engine.nms); device events around a >= 1 s window after warm-up;
+  (b) the predictor end to end at 640 x 640, bf16, batch 4 and 16, from synthetic JPEG files: images/s and ms/image split into
+      load (waiting for decode + resize), H2D, forward, postprocess and D2H (device events).
+
+    python tools/predict_bench.py [--images 64] [--kernel-only]
+--kernel-only runs only the kernel loop of (a), for a `rocprofv3 --kernel-trace --stats` run of its own.
+"""
+import argparse
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def synthetic_preds(B, nq, nc, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    centres = torch.cat([torch.rand(B, 12, 2, generator=g) * 0.8 + 0.1, torch.rand(B, 12, 2, generator=g) * 0.2 + 0.02], -1)
+    pick = torch.gather(centres, 1, torch.randint(0, 12, (B, nq, 1), generator=g).expand(B, nq, 4))
+    xy = pick[..., :2] + torch.randn(B, nq, 2, generator=g) * 0.01               # clustered: NMS has work to do
+    wh = pick[..., 2:] * (0.85 + 0.3 * torch.rand(B, nq, 2, generator=g))
+    scores = torch.sigmoid(torch.randn(B, nq, nc, generator=g) * 2 - 2)
+    return torch.cat([xy, wh, scores], -1)
+
+
+def host_loop(y, hw, conf, iou, max_wh=7680):
+    """The reference's per-image loop on device tensors, NMS through engine.nms (one IoU matrix to the host per image)."""
+    from tamtr_amd.engine import nms, xywh2xyxy
+    nd = y.shape[-1]
+    bboxes, scores = y.split((4, nd - 4), dim=-1)
+    outs = []
+    for i, bbox in enumerate(bboxes):
+        bbox = xywh2xyxy(bbox)
+        score, cls = scores[i].max(-1, keepdim=True)
+        idx = score.squeeze(-1) > conf
+        pred = torch.cat([bbox, score, cls.to(bbox.dtype)], dim=-1)[idx]
+        oi = nms(pred[:, :4] + pred[:, 5:6] * max_wh, pred[:, 4], iou)
+        out = pred[oi]
+        oh, ow = hw[i]
+        out[..., [0, 2]] *= ow
+        out[..., [1, 3]] *= oh
+        outs.append(out.cpu())
+    return outs
+
+
+def timed(fn, min_s=1.0, warmup=5, chunk=20):
+    """Mean ms per call over chunks of `chunk` calls, each chunk bracketed by device events, until >= min_s has passed."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    total_ms, n, t0 = 0.0, 0, time.perf_counter()
+    while time.perf_counter() - t0 < min_s:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(chunk):
+            fn()
+        e1.record()
+        e1.synchronize()
+        total_ms += e0.elapsed_time(e1)
+        n += chunk
+    return total_ms / n, n
+
+
+def bench_postprocess(kernel_only=False):
+    from tamtr_amd import ops
+    rows = []
+    B, nq, conf, iou = 16, 300, 0.25, 0.7
+    for nc in (10, 80):
+        y = synthetic_preds(B, nq, nc).cuda()
+        hw = [(540 + 20 * i, 960 - 10 * i) for i in range(B)]
+        hw_dev = torch.tensor(hw, dtype=torch.int32, device='cuda')
+
+        def kernel():
+            return ops.detect_postprocess(y, hw_dev, conf, iou)
+
+        def kernel_with_copy():   # what the predictor does: the call plus one device-to-host copy of its outputs
+            o, k, c = kernel()
+            return torch.cat([o.view(-1), k.view(torch.float32).view(-1), c.view(torch.float32)]).cpu()
+
+        t_k, n_k = timed(kernel)
+        if kernel_only:
+            rows.append({'nc': nc, 'kernel_ms': t_k, 'iters': n_k})
+            continue
+        t_kc, _ = timed(kernel_with_copy)
+        t_h, n_h = timed(lambda: host_loop(y, hw, conf, iou))
+        _, _, counts = kernel()
+        rows.append({'B': B, 'nq': nq, 'nc': nc, 'conf': conf, 'iou': iou, 'kept_per_image': round(float(counts.float().mean()), 1),
+                     'kernel_ms': round(t_k, 4), 'kernel_plus_d2h_ms': round(t_kc, 4), 'host_loop_ms': round(t_h, 3),
+                     'speedup_vs_host_loop': round(t_h / t_kc, 1), 'iters': [n_k, n_h]})
+    return rows
+
+
+def bench_predictor(n_images, batches, conf=1e-5):
+    """conf: the seeded weights score below 5e-4, so the reference's 0.25 would leave the postprocess nothing to do."""
+    from PIL import Image
+    from tamtr_amd import data as D
+    from tamtr_amd.model import RTDETRDetectionWorldModel
+    from tamtr_amd.predict import Predictor
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests', 'golden'))
+    from weights import fill_state
+    rng = np.random.default_rng(0)
+    names = {i: f'c{i}' for i in range(10)}
+    tf = D.TextFeatures.synthetic(list(names.values()))
+    rows = []
+    with tempfile.TemporaryDirectory() as d:
+        for i in range(n_images):
+            h, w = ((1080, 1920), (540, 960), (1500, 2000), (640, 640))[i % 4]
+            Image.fromarray(rng.integers(0, 256, (h, w, 3), dtype=np.uint8)).save(os.path.join(d, f'{i:04d}.jpg'), quality=90)
+        for batch in batches:
+            torch.manual_seed(0)
+            model = RTDETRDetectionWorldModel(nc=len(names))
+            model.load_state_dict(fill_state(model.state_dict(), 78))
+            pred = Predictor(model.cuda(), names, tf, imgsz=640, conf=conf, iou=0.7, batch=batch, dtype='bf16')
+            for _ in pred.predict(d):   # warm-up pass: kernels, libraries, tail-batch shapes
+                pass
+            pred.times = {k: 0.0 for k in pred.times}
+            pred.seen = 0
+            t0 = time.perf_counter()
+            n_det = sum(len(det) for det in pred.predict(d))
+            wall = time.perf_counter() - t0
+            sp = pred.speed()
+            rows.append({'imgsz': 640, 'dtype': 'bf16', 'batch': batch, 'conf': conf, 'images': pred.seen, 'detections': n_det,
+                         'images_per_s': round(pred.seen / wall, 1), 'ms_per_image': {k: round(v, 3) for k, v in sp.items()},
+                         'workers': pred.workers})
+            del pred, model
+            torch.cuda.empty_cache()
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--images', type=int, default=64)
+    ap.add_argument('--kernel-only', action='store_true')
+    args = ap.parse_args()
+    import tamtr_amd  # noqa: F401
+    assert torch.cuda.is_available(), 'predict_bench needs an MI355X'
+    print(torch.cuda.get_device_name(0), 'torch', torch.__version__)
+    if args.kernel_only:
+        print(json.dumps({'postprocess_kernel_only': bench_postprocess(True)}))
+        return
+    print('(a) postprocess of one batch (device events, >= 1 s window after 5 warm-up calls)')
+    for r in bench_postprocess():
+        print(json.dumps(r))
+    print(f'(b) predictor end to end, {args.images} synthetic JPEGs (1920x1080 / 960x540 / 2000x1500 / 640x640), second pass timed')
+    for r in bench_predictor(args.images, (4, 16)):
+        print(json.dumps(r))
+
+
+if __name__ == '__main__':
+    main()
