@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - images/sec of one TAM-TR training step (fwd + 12-term RIOU loss + bwd + AdamW) at 640x640, bs 16 per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32] [--no-cpu-baseline] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|fp32] [--full [--no-cpu-baseline]] [--dump-outputs DIR]
     N > 1: either under a launcher (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py
     --gpus N ...: RANK / WORLD_SIZE in the environment) or plainly as `python bench.py --gpus N`: with no WORLD_SIZE in the environment
     the script starts its own N ranks as a CHILD `torch.distributed.run` (before anything touches the GPU), relays their output and
@@ -12,6 +12,11 @@ synthetic images rand(B,3,640,640), unit-norm 10x512 text features, 8 GT boxes p
 The step is the reference's training step (engine/trainer.py:328-357,471-479): forward through BaseModel.forward(dict),
 loss, backward, gradient clip 0.1, AdamW(lr 1e-4, wd 1e-4), EMA update of the weights (utils/torch_utils.py:392-419).  Every rank runs bs 16 (weak scaling); gradients are summed
 over ranks with bucketed RCCL all-reduces overlapped with the backward (tam-tr_amd/dist.py).
+
+A plain run does what the headline figure needs: it sets up (model, static-part capture with its replay check), warms up, times the
+steps, writes --dump-outputs and prints the line.  `--full` adds what runs of their own measure or check, about two minutes more on one
+GPU: `config.bf16_vs_fp32`, `config.graph_vs_eager`, `roofline.event_bracket_ms_around_a_2us_kernel`, `roofline_other` and
+`cpu_baseline`; without it these are null or absent.  The timed steps and their inputs are the same either way.
 
 One JSON line on rank 0.  `roofline`: the MEH value-projection GEMM (tamtr_linear_bf16, the dominant dense contraction of
 the head: M = 16*33600, N = K = 512; value_proj x 3 layers + enc_output forward, and the value projections' dX products), timed live with
@@ -359,7 +364,10 @@ def main():
     ap.add_argument('--batch', type=int, default=16, help='images per GPU')
     ap.add_argument('--imgsz', type=int, default=640)
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check what the headline figure does not need: the bf16-vs-fp32 forward, the graph-vs-eager step, '
+                         'the event-bracket offset, roofline_other and the CPU-oracle baseline (see the docstring)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU-oracle baseline')
     ap.add_argument('--rccl-solo', action='store_true',
                     help='--gpus 1 only: run the N > 1 form of the step (gradient buckets, all-reduces from the hooks, barriers, the all-rank agreement) '
                          'on a ONE-rank RCCL process group - every collective goes through the real backend, nothing is exchanged.  A rehearsal of the '
@@ -375,7 +383,7 @@ def main():
                     help='bf16 mode with --optim-step fused: the optimizer kernel maintains the bf16 copies of the weights (engine.FusedOptimStep(shadows=True))')
     ap.add_argument('--optim-step', default='fused', choices=['fused', 'torch'],
                     help='clip + AdamW + EMA as the table-driven kernels of csrc/optim.hip (engine.FusedOptimStep) or as the three torch calls')
-    ap.add_argument('--no-graph-check', action='store_true', help='skip the graph-vs-eager step and the standalone roofline_other launches after the timed loop (profiling runs: keeps the trace to the timed steps)')
+    ap.add_argument('--no-graph-check', action='store_true', help='--full without the graph-vs-eager step and the standalone roofline_other launches after the timed loop (profiling runs: keeps the trace to the timed steps)')
     ap.add_argument('--cpu-baseline-images', type=int, default=8, help='images of the CPU-oracle sample (BASELINE configs[0]: 8)')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help="write the last timed step's loss, loss terms and a fixed sample of the gradients, weights and EMA weights as "
@@ -464,10 +472,10 @@ def main():
         if rank == 0:
             print(f'[bench {time.strftime("%H:%M:%S")}] {msg}', file=sys.stderr, flush=True)
 
-    # bf16 mode against fp32 mode on the same weights and batch (forward only, same denoising seed), before anything is trained
+    # --full: bf16 mode against fp32 mode on the same weights and batch (forward only, same denoising seed), before anything is trained
     mode_err = None
     t_probe = time.perf_counter()
-    if args.dtype == 'bf16':
+    if args.full and args.dtype == 'bf16':
         saved = {k: v.clone() for k, v in model.state_dict().items()}   # BatchNorm statistics move with a training forward
         with torch.no_grad():
             losses = {}
@@ -479,9 +487,10 @@ def main():
         model.autocast_dtype = torch.bfloat16
         mode_err = {'loss_fp32': losses['fp32'], 'loss_bf16': losses['bf16'], 'rel': abs(losses['bf16'] - losses['fp32']) / abs(losses['fp32'])}
         del saved
-        torch.manual_seed(0)
         torch.cuda.synchronize()
         note(f'bf16 against fp32 forward on the same batch: {time.perf_counter() - t_probe:.1f} s (first convolutions: MIOpen handle, tables, code objects)')
+    if args.dtype == 'bf16':
+        torch.manual_seed(0)   # bf16 runs draw the step's random numbers from seed 0 afresh, with the probe or without it
     static_part = 'eager'
     if args.static_part == 'graph':
         try:
@@ -538,7 +547,7 @@ def main():
         dump_outputs(args.dump_outputs, model, ema, loss, items)
         note(f'outputs of the last timed step written to {args.dump_outputs}')
     gve = None
-    if static_part == 'hip-graph' and not args.no_graph_check:   # the replayed path against kernel-by-kernel execution, at the end of the run (every rank: same work)
+    if args.full and static_part == 'hip-graph' and not args.no_graph_check:   # the replayed path against kernel-by-kernel execution, at the end of the run (every rank: same work)
         if reducer is None:
             opt.zero_grad(set_to_none=True)
         try:
@@ -571,17 +580,17 @@ def main():
                 'achieved': ks['tflops'], 'peak': peak, 'unit': 'TFLOP/s', 'frac': ks['tflops'] / peak, 'traffic': gemm_traffic(args),
                 'avg_ms': ks['avg_ms'], 'launches': ks['launches'],
                 # (an event pair around a ~2 us kernel, measured the same way right here: what the bracket itself adds on this runtime)
-                'event_bracket_ms_around_a_2us_kernel': event_bracket_overhead(dev),
+                'event_bracket_ms_around_a_2us_kernel': event_bracket_overhead(dev) if args.full else None,
                 # the same launches priced against the OTHER roof (the shape sits at the chip's balance point: 256 flop/B against 312):
                 # algorithmic bytes (X read once + Y written once) per second over the 8 TB/s HBM peak
                 'hbm_view': _hbm_view(args, ks)},
         }
-        if args.dtype == 'bf16' and not args.no_graph_check:   # (profiling runs keep the trace to the timed steps)
+        if args.full and args.dtype == 'bf16' and not args.no_graph_check:   # (profiling runs keep the trace to the timed steps)
             try:
                 out['roofline_other'] = other_kernels(args, dev)
             except Exception as e:  # noqa: BLE001 - an extra; the line stands without it
                 out['roofline_other'] = {'error': f'{type(e).__name__}: {e}'[:200]}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out['cpu_baseline'] = cpu_baseline(args.cpu_baseline_images, args.imgsz)
         else:
             out['cpu_baseline'] = None
