@@ -549,6 +549,36 @@ int tamtr_detect_postprocess(const void* preds, int dtype, int B, int nq, int nd
                              int single_cls, float max_wh, const int32_t* classes, int n_classes, float* out, int32_t* keep,
                              int32_t* counts, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Validator postprocess and label matching.  Replaces the per-image loop of the validator: RTDETRValidator.postprocess,
+ * ultralytics/models/rtdetrworld/val.py:102-173 (boxes scaled by imgsz, xywh2xyxy, class max, descending-score order, the confidence
+ * mask, torchvision.ops.nms on boxes shifted by cls * max_wh, predictions and labels scaled to the original image), and
+ * match_predictions / _process_batch, ultralytics/engine/validator.py:208-247 (IoU of labels and detections, one detection per label at
+ * each of the ten thresholds 0.5 : 0.05 : 0.95):
+ *      preds   (T) [B, nq, nd]  eval output of the model: normalised cx cy w h, then nc = nd - 4 class scores; widened to fp32
+ *      lab_cls f32 [M]          label classes, grouped by image (file order inside an image)
+ *      lab_box f32 [M, 4]       label boxes, normalised cx cy w h, same order
+ *      lab_off i32 [B + 1]      image b owns labels lab_off[b] .. lab_off[b + 1] - 1 (clamped to 0 .. M); an image may own none
+ *      scale   f32 [B, 4]       per image: fp32(w_orig / imgsz), fp32(h_orig / imgsz) (predictions), fp32(w_orig), fp32(h_orig) (labels)
+ *      predn   f32 [B, nq, 6]   kept rows in NMS order: x1 y1 x2 y2 (pixels of the original image), score, cls; zero after counts[b]
+ *      correct u8  [B, nq, 10]  row d is a true positive at threshold t; zero after counts[b]
+ *      counts  i32 [B]          rows kept per image
+ *  Bit-exact in fp32, every operation rounded on its own, with engine.postprocess + engine.process_batch on CPU fp32 tensors:
+ *  b = xywh * imgsz before the corner conversion; rows in descending score order, stable (equal scores: ascending query; NaN first);
+ *  sorted position p survives iff the score of QUERY p exceeds conf (the reference's unsorted mask on sorted rows, kept on purpose);
+ *  NMS as tamtr_detect_postprocess (IoU > iou in fp32; csrc/valmatch.hip states how the Python op reproduces torchvision's double
+ *  comparison and where engine.nms differs); cls = 0 when single_cls (label classes are not zeroed); matching IoU =
+ *  inter / (((area_label + area_det) - inter) + fp32(1e-7)); detection d takes its same-class label of highest IoU >= 0.5 - among labels
+ *  of EQUAL IoU the LOWER label index (numpy leaves that order unspecified) - and is correct at threshold t when that IoU >= IOUV[t]
+ *  (fp32 values of torch.linspace(0.5, 0.95, 10)) and no earlier row took the same label with an IoU >= IOUV[t].  A NaN IoU and a class
+ *  mismatch never match.  No cap on labels per image.  One launch, one workgroup per image; nothing is allocated, set or synchronised,
+ *  so the call can be captured.
+ *  TAMTR_EINVAL: a NULL operand (lab_cls / lab_box may be NULL only when M == 0), B < 1, nq < 1, nd < 5, M < 0, dtype not F32 / BF16.
+ *  TAMTR_EUNSUP: nq > 512. */
+int tamtr_val_postprocess_match(const void* preds, int dtype, int B, int nq, int nd, float imgsz, float conf, float iou, int single_cls,
+                                float max_wh, const float* lab_cls, const float* lab_box, const int32_t* lab_off, int M, const float* scale,
+                                float* predn, uint8_t* correct, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

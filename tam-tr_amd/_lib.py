@@ -10,7 +10,7 @@ from ctypes import c_float, c_int, c_longlong, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('TAMTR_HIP_LIB') or os.path.join(_HERE, 'csrc', 'libtamtr_hip.so')  # env override: kernel A/B experiments
-ABI_VERSION = 35
+ABI_VERSION = 36
 
 F32, BF16 = 0, 1
 _ERR = {-1: 'TAMTR_EINVAL (bad argument)', -2: 'TAMTR_EUNSUP (shape/dtype outside what the kernels are built for)',
@@ -100,6 +100,7 @@ _SIGS = {
     'tamtr_ln_gate_bwd': [_P, _P, _P, _LL, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _P],
     'tamtr_dwconv_silu_cross_bwd': [_P, _P, _LL, _P, _P, _P, _LL, _P, _I, _I, _I, _I, _I, _I, _P],
     'tamtr_detect_postprocess': [_P, _I, _I, _I, _I, _P, _F, _F, _I, _F, _P, _I, _P, _P, _P, _P],
+    'tamtr_val_postprocess_match': [_P, _I, _I, _I, _I, _F, _F, _F, _I, _F, _P, _P, _P, _I, _P, _P, _P, _P, _P],
 }
 EXPORTS = tuple(_SIGS)
 _lib = None

@@ -30,28 +30,7 @@
 //      iou(i, 64 w + l) and a ballot forms the word.
 //   4. greedy pass in wave 0 with no barrier: lane k holds removal word k; every row is tested with a readlane of its word.
 //   5. coalesced write of out / keep (zero / -1 padding after the count) and counts.
-#include "common.h"
-
-#define PP_MAX_Q 512
-#define PP_WORDS (PP_MAX_Q / 64)
-#define PP_THREADS 512
-
-// torch.max over a row: NaN wins (lowest index among NaNs), else the larger value, equal values -> the lower index
-__device__ __forceinline__ bool pp_better(float v, int i, float bv, int bi) {
-  const bool vn = v != v, bn = bv != bv;
-  if (vn || bn) return vn && (!bn || i < bi);
-  return v > bv || (v == bv && i < bi);
-}
-
-// float -> uint32 with the same order (ascending); -0.0 folded onto +0.0
-__device__ __forceinline__ uint32_t pp_ordered(float s) {
-  uint32_t u = s == 0.0f ? 0u : __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// std::max / std::min as torchvision calls them: max(a, b) = a < b ? b : a, min(a, b) = b < a ? b : a
-__device__ __forceinline__ float pp_max(float a, float b) { return a < b ? b : a; }
-__device__ __forceinline__ float pp_min(float a, float b) { return b < a ? b : a; }
+#include "postproc.h"
 
 struct PpShared {
   float box[PP_MAX_Q][4];    // unshifted x1 y1 x2 y2 by query
@@ -84,23 +63,12 @@ __global__ __launch_bounds__(PP_THREADS) void detect_postprocess_kernel(const T*
   for (int q0 = 0; q0 < nq; q0 += PP_THREADS / GW) {
     const int q = q0 + tid / GW;
     const bool row = q < nq;  // uniform inside the group
-    float bv = __int_as_float(0xff800000), bx[4] = {0.f, 0.f, 0.f, 0.f};
-    int bi = 0x7fffffff;
-    if (row) {
-      const T* r = pb + (size_t)q * nd;
-      for (int c = sub; c < nc; c += GW) {
-        const float v = Elt<T>::ld(r + 4 + c);
-        if (pp_better(v, c, bv, bi)) { bv = v; bi = c; }
-      }
-      if (sub == 0)
-        for (int k = 0; k < 4; ++k) bx[k] = Elt<T>::ld(r + k);
-    }
-#pragma unroll
-    for (int o = GW / 2; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, WAVE);
-      const int oi = __shfl_xor(bi, o, WAVE);
-      if (pp_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }
-    }
+    float bv, bx[4] = {0.f, 0.f, 0.f, 0.f};
+    int bi;
+    const T* r = pb + (size_t)q * nd;
+    pp_row_max<T, GW>(r, nc, sub, row, bv, bi);
+    if (row && sub == 0)
+      for (int k = 0; k < 4; ++k) bx[k] = Elt<T>::ld(r + k);
     if (row && sub == 0) {
       const float dw = bx[2] / 2.0f, dh = bx[3] / 2.0f;
       s.box[q][0] = bx[0] - dw;
@@ -127,16 +95,7 @@ __global__ __launch_bounds__(PP_THREADS) void detect_postprocess_kernel(const T*
   const int n = s.n;
 
   // ---- 2. bitonic sort of P <= 512 keys, ascending (= NMS order; failed rows last)
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const int i = tid, l = i ^ j;
-      if (i < P && l > i) {
-        const uint64_t a = s.key[i], c = s.key[l];
-        if ((a > c) == ((i & k) == 0)) { s.key[i] = c; s.key[l] = a; }
-      }
-      __syncthreads();
-    }
-  }
+  pp_bitonic_sort(s.key, P, tid);
 
   // shifted boxes and areas in NMS order
   for (int p = tid; p < n; p += PP_THREADS) {
@@ -149,41 +108,12 @@ __global__ __launch_bounds__(PP_THREADS) void detect_postprocess_kernel(const T*
   __syncthreads();
 
   // ---- 3. suppression mask: word (i, w) bit l = iou(i, 64 w + l) > thr for 64 w + l > i
-  const int nw = (n + WAVE - 1) / WAVE;
-  for (int t = wave; t < n * nw; t += PP_THREADS / WAVE) {
-    const int i = t / nw, w = t - i * nw, j = w * WAVE + lane;
-    uint64_t word = 0;
-    if (w * WAVE + WAVE - 1 > i) {  // uniform over the wave
-      bool sup = false;
-      if (j > i && j < n) {
-        const float ix1 = s.sbox[i][0], iy1 = s.sbox[i][1], ix2 = s.sbox[i][2], iy2 = s.sbox[i][3];
-        const float xx1 = pp_max(ix1, s.sbox[j][0]), yy1 = pp_max(iy1, s.sbox[j][1]);
-        const float xx2 = pp_min(ix2, s.sbox[j][2]), yy2 = pp_min(iy2, s.sbox[j][3]);
-        const float ww = pp_max(0.0f, xx2 - xx1), hh = pp_max(0.0f, yy2 - yy1);
-        const float inter = ww * hh;
-        const float ovr = inter / ((s.sarea[i] + s.sarea[j]) - inter);
-        sup = ovr > thr;
-      }
-      word = __ballot(sup);
-    }
-    if (lane == 0) s.mask[i][w] = word;
-  }
+  pp_nms_mask(s.sbox, s.sarea, s.mask, n, thr, wave, lane);
   __syncthreads();
 
   // ---- 4. greedy pass, one wave, no barrier: lane k < nw holds removal word k
   if (wave == 0) {
-    uint64_t rem = 0;
-    int cnt = 0;
-    for (int i = 0; i < n; ++i) {
-      const int wi = i >> 6;
-      const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)rem, wi), hi = __builtin_amdgcn_readlane((uint32_t)(rem >> 32), wi);
-      const uint64_t rw = ((uint64_t)hi << 32) | lo;
-      if (!((rw >> (i & 63)) & 1ull)) {
-        if (lane == 0) s.kept[cnt] = i;
-        ++cnt;
-        if (lane < nw) rem |= s.mask[i][lane];
-      }
-    }
+    const int cnt = pp_greedy(s.mask, s.kept, n, lane);
     if (lane == 0) s.count = cnt;
   }
   __syncthreads();

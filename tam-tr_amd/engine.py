@@ -16,6 +16,7 @@
 Host-side PyTorch / numpy by design (the reference's is too).  Batches arrive as tensors (img, txt_feats, cls, bboxes, batch_idx
 [, ori_shape]) - from data.py's loaders or synthetic; the CLIP text encoder stays out of scope (precomputed table, data.py).
 """
+import json
 import math
 import os
 import time
@@ -488,19 +489,133 @@ class Validator:
                 'mAP50-95': float(ap.mean()), 'seen': self.seen}
 
 
+_EMPTY = {'precision': 0.0, 'recall': 0.0, 'mAP50': 0.0, 'mAP50-95': 0.0}
+
+
+class DeviceValidator:
+    """Validator with the per-image work on the device: update() is ops.val_postprocess_match (one launch per batch, csrc/valmatch.hip)
+    plus list appends - no synchronisation; results() does one concatenation and one device-to-host copy for the whole run and feeds
+    the same ap_per_class.  Its dict equals Validator's key for key (on the model output widened to fp32) and adds 'per_class':
+    [{class, images, instances, precision, recall, mAP50, mAP50-95}] for the classes that have labels (the reference's print_results
+    table).  save_json: also collect the reference's pred_to_json records (models/yolo/detect/val.py:231-242; the batch must carry
+    'im_file'); class_map maps a class index to the record's category_id (default: the index)."""
+
+    def __init__(self, imgsz=640, conf=0.001, iou=0.7, single_cls=False, save_json=False, class_map=None, names=None):
+        self.imgsz, self.conf, self.iou, self.single_cls = imgsz, conf, iou, single_cls
+        self.save_json, self.class_map, self.names = save_json, class_map, names
+        self.batches, self.files, self.seen = [], [], 0
+        self.jdict = []
+        self._reduced = None
+
+    @torch.no_grad()
+    def update(self, preds, batch):
+        from . import ops
+        y = preds[0] if isinstance(preds, (list, tuple)) else preds
+        self.batches.append(ops.val_postprocess_match(y, batch['cls'], batch['bboxes'], batch['batch_idx'], batch.get('ori_shape'),
+                                                      self.imgsz, self.conf, self.iou, self.single_cls))
+        self.seen += y.shape[0]
+        if self.save_json:
+            self.files.extend(batch['im_file'])
+        self._reduced = None
+
+    def _reduce(self):
+        """-> (predn [n, 6], correct [n, 10] bool, image [n], target_cls [m], target_image [m]) as numpy, rows in image order."""
+        if self._reduced is None:
+            outs = self.batches
+            dev_parts = []
+            for predn, correct, counts, lab_cls, lab_off in outs:
+                parts = [predn, correct, counts] + ([lab_cls, lab_off] if isinstance(lab_cls, torch.Tensor) else [])
+                dev_parts += [p.reshape(-1).view(torch.uint8) for p in parts]
+            flat = torch.cat(dev_parts).cpu().numpy() if dev_parts else np.zeros(0, np.uint8)   # the run's one device-to-host copy
+            pos, rows, hits, image, tcls, timage, first = 0, [], [], [], [], [], 0
+
+            def take(n, dtype):
+                nonlocal pos
+                a = flat[pos:pos + n * np.dtype(dtype).itemsize].view(dtype)
+                pos += a.nbytes
+                return a
+
+            for predn, _, counts, lab_cls, lab_off in outs:
+                B, nq = predn.shape[:2]
+                pn, co, cn = take(B * nq * 6, np.float32).reshape(B, nq, 6), take(B * nq * 10, np.uint8).reshape(B, nq, 10), take(B, np.int32)
+                if isinstance(lab_cls, torch.Tensor):
+                    lab_cls, lab_off = take(lab_cls.numel(), np.float32), take(B + 1, np.int32)
+                    lab_cls, lab_off = lab_cls[lab_off[0]:lab_off[B]], lab_off - lab_off[0]
+                live = np.arange(nq)[None, :] < cn[:, None]
+                rows.append(pn[live])
+                hits.append(co[live].astype(bool))
+                image.append(first + np.nonzero(live)[0])
+                tcls.append(lab_cls)
+                timage.append(first + np.repeat(np.arange(B), np.diff(lab_off)))
+                first += B
+            cat = lambda xs, shape, dt: np.concatenate(xs) if xs else np.zeros(shape, dt)   # noqa: E731
+            self._reduced = (cat(rows, (0, 6), np.float32), cat(hits, (0, 10), bool), cat(image, (0,), np.int64),
+                             cat(tcls, (0,), np.float32), cat(timage, (0,), np.int64))
+        return self._reduced
+
+    def results(self):
+        predn, correct, image, tcls, timage = self._reduce()
+        if self.save_json:
+            self.jdict = self._records(predn, image)
+        if (len(predn) == 0 and len(tcls) == 0) or not correct.any():
+            return {**_EMPTY, 'seen': self.seen, 'per_class': []}
+        _, _, p, r, _, ap, classes = ap_per_class(correct, predn[:, 4], predn[:, 5], tcls)
+        per_class = []
+        for k, c in enumerate(classes):
+            mine = tcls == c
+            per_class.append({'class': self.names[int(c)] if self.names is not None else int(c), 'images': int(len(np.unique(timage[mine]))),
+                              'instances': int(mine.sum()), 'precision': float(p[k]), 'recall': float(r[k]), 'mAP50': float(ap[k, 0]),
+                              'mAP50-95': float(ap[k].mean())})
+        return {'precision': float(p.mean()), 'recall': float(r.mean()), 'mAP50': float(ap[:, 0].mean()), 'mAP50-95': float(ap.mean()),
+                'seen': self.seen, 'per_class': per_class}
+
+    def _records(self, predn, image):
+        """pred_to_json: image_id = the file stem; bbox = top-left x, y, w, h rounded to 3; score rounded to 5."""
+        box = torch.from_numpy(predn[:, :4]).clone()
+        wh = box[:, 2:] - box[:, :2]
+        box = torch.cat([(box[:, :2] + box[:, 2:]) / 2, wh], 1)    # xyxy2xywh (utils/ops.py:337-357) ...
+        box[:, :2] -= box[:, 2:] / 2                                # ... then centre -> top-left corner
+        out = []
+        for i, p, b in zip(image.tolist(), predn.tolist(), box.tolist()):
+            c = int(p[5])
+            out.append({'image_id': os.path.splitext(os.path.basename(self.files[i]))[0],
+                        'category_id': self.class_map[c] if self.class_map is not None else c,
+                        'bbox': [round(x, 3) for x in b], 'score': round(p[4], 5)})
+        return out
+
+    def write_json(self, path):
+        """Write the collected records as the reference's predictions.json; `path`: the file, or the run folder."""
+        if not self.save_json:
+            raise ValueError('DeviceValidator(save_json=True) collects the records write_json() writes')
+        if self._reduced is None or not self.jdict:
+            predn, _, image, _, _ = self._reduce()
+            self.jdict = self._records(predn, image)
+        path = os.path.join(path, 'predictions.json') if os.path.isdir(path) else path
+        with open(path, 'w') as f:
+            json.dump(self.jdict, f)
+        return path
+
+
 @torch.no_grad()
-def validate(model, batches, imgsz=640, conf=0.001, iou=0.7, autocast_dtype=None):
-    """model in eval mode over an iterable of batches -> metric dict (valTAMTR.py's flow without the dataset plumbing)."""
+def validate(model, batches, imgsz=640, conf=0.001, iou=0.7, autocast_dtype=None, on_device=False, save_json=None, names=None):
+    """model in eval mode over an iterable of batches -> metric dict (valTAMTR.py's flow without the dataset plumbing).
+    on_device: postprocess and label matching in one HIP launch per batch (DeviceValidator; the dict then also carries 'per_class');
+    save_json (a file or folder path, needs on_device): also write the reference's predictions.json there."""
+    if save_json and not on_device:
+        raise ValueError('validate(save_json=...) needs on_device=True: the records come from the device path')
     was_training = model.training
     model.eval()
-    v = Validator(imgsz, conf, iou)
+    v = DeviceValidator(imgsz, conf, iou, save_json=bool(save_json), names=names) if on_device else Validator(imgsz, conf, iou)
     for batch in batches:
         img = batch['img']
         with torch.autocast(img.device.type, dtype=autocast_dtype or torch.bfloat16, enabled=autocast_dtype is not None):
             preds = model(img, txt_feats=batch.get('txt_feats'))
         v.update(preds, batch)
     model.train(was_training)
-    return v.results()
+    res = v.results()
+    if save_json:
+        res['json'] = v.write_json(save_json)
+    return res
 
 
 # ------------------------------------------------------------------------------------------------ the epoch loop
@@ -511,7 +626,7 @@ def fitness(metrics):
 
 def fit(model, train_loader, prepare, epochs, val_loader=None, lr0=1e-4, lrf=1.0, momentum=0.9, weight_decay=1e-4, optimizer='AdamW',
         warmup_iters=2000, warmup_bias_lr=0.1, warmup_momentum=0.8, close_mosaic=0, imgsz=640, reducer=None, rank=0, world=1,
-        save_dir=None, max_steps=None, log=None, resume=None, static_graph=False):
+        save_dir=None, max_steps=None, log=None, resume=None, static_graph=False, val_on_device=False):
     """Train `model` for `epochs` passes over train_loader; defaults are the reference's shipped hyper-parameters
     (cfg/default.yaml:23,84-90; this fork sets nbs = batch, so there is no gradient accumulation and weight decay is unscaled, and
     reads warmup_epochs as an iteration count: trainer.py:263-265,294).
@@ -523,7 +638,8 @@ def fit(model, train_loader, prepare, epochs, val_loader=None, lr0=1e-4, lrf=1.0
     has loaded 'model'): EMA weights and update count, optimizer state, the best fitness so far and the epoch counter continue from it
     (trainer.py:593-615), so the warm-up does not start over, best.pt is only replaced by a better epoch, and a run that resumes inside
     its last `close_mosaic` epochs starts with mosaic already closed.  static_graph: record trunk + VSS blocks + input projection as HIP graphs on the first batch
-    (model.capture_static_part; batches of another shape, and evaluation, run eagerly).  Returns the per-epoch records."""
+    (model.capture_static_part; batches of another shape, and evaluation, run eagerly).  val_on_device: the per-epoch validation runs its
+    postprocess and label matching on the device (validate(on_device=True)); the record then also holds 'per_class'.  Returns the per-epoch records."""
     nb = len(train_loader)
     if nb == 0:   # e.g. drop_last with fewer samples per rank than the batch size: the loop below would 'train' for zero steps without a word
         raise ValueError(f'fit(): the training loader yields no batches ({len(train_loader.dataset)} samples, batch size {train_loader.batch_size}, '
@@ -608,7 +724,7 @@ def fit(model, train_loader, prepare, epochs, val_loader=None, lr0=1e-4, lrf=1.0
         if rank == 0:
             if val_loader is not None:
                 rec.update(validate(ema.ema, (prepare(b, False) for b in val_loader), imgsz=imgsz,
-                                    autocast_dtype=getattr(model, 'autocast_dtype', None)))
+                                    autocast_dtype=getattr(model, 'autocast_dtype', None), on_device=val_on_device))
                 rec['fitness'] = fitness(rec)
             if save_dir is not None:
                 os.makedirs(save_dir, exist_ok=True)

@@ -1812,6 +1812,62 @@ def detect_postprocess(y, orig_hw, conf, iou, classes=None, single_cls=False, ma
     return out, keep, counts
 
 
+@torch.no_grad()
+def val_postprocess_match(y, cls, bboxes, batch_idx, ori_hw, imgsz, conf, iou, single_cls=False, max_wh=7680.):
+    """engine.Validator.update's per-image work (RTDETRValidator.postprocess, models/rtdetrworld/val.py:102-173, and match_predictions,
+    engine/validator.py:208-247) for the whole batch in one launch; the rule is stated in csrc/valmatch.hip and is "the host rule on
+    y.float()".  y (f32 / bf16) [B, nq, 4 + nc] eval output on the GPU; cls [M] or [M, 1], bboxes [M, 4] (normalised xywh) and
+    batch_idx [M] (integer-valued) are the batch's labels, on the host (as data.preprocess_batch leaves them) or on the device;
+    ori_hw: B (h, w) pairs, or None for (imgsz, imgsz).
+    Returns predn f32 [B, nq, 6] (native-space x1 y1 x2 y2, score, cls; zero after the count), correct u8 [B, nq, 10], counts i32 [B]
+    on the device, and the labels grouped by image, where they came from: lab_cls f32 [M'] and lab_off i32 [B + 1] (numpy arrays for
+    host labels, device tensors otherwise).  Host labels go up in ONE non-blocking copy; nothing synchronises."""
+    import numpy as np
+    require_gpu(y)
+    if y.dim() != 3:
+        raise _lib.TamtrHipError(f'val_postprocess_match: expected y [B, nq, 4 + nc], got {tuple(y.shape)}')
+    B, nq, nd = y.shape
+    dev = y.device
+    y = _c(y if y.dtype in (torch.float32, torch.bfloat16) else y.float())
+    hw = np.full((B, 2), imgsz, dtype=np.int64) if ori_hw is None else np.asarray(ori_hw).reshape(-1, 2)
+    if hw.shape[0] != B:
+        raise _lib.TamtrHipError(f'val_postprocess_match: ori_hw must hold {B} (h, w) pairs, got {hw.shape[0]}')
+    # the four fp32 factors per image, rounded as the host rule rounds them (Python double division, then fp32)
+    scale = np.array([[float(w) / imgsz, float(h) / imgsz, float(w), float(h)] for h, w in hw.tolist()], dtype=np.float64).astype(np.float32)
+    M = int(batch_idx.numel())
+    if cls.numel() != M or bboxes.numel() != 4 * M:
+        raise _lib.TamtrHipError(f'val_postprocess_match: {M} batch indices, {cls.numel()} classes, {tuple(bboxes.shape)} boxes')
+    if not (cls.is_cuda or bboxes.is_cuda or batch_idx.is_cuda):
+        bi = batch_idx.reshape(-1).numpy().astype(np.float32)
+        order = np.argsort(bi, kind='stable')          # the host rule's mask keeps file order inside an image
+        off = np.searchsorted(bi[order], np.arange(B + 1, dtype=np.float32)).astype(np.int32)
+        order = order[off[0]:off[B]]                   # (indices outside 0 .. B - 1 belong to no image)
+        lab_cls = cls.reshape(-1).float().numpy()[order]
+        lab_box = bboxes.reshape(-1, 4).float().numpy()[order]
+        off = off - off[0]
+        M = len(order)
+        buf = np.concatenate([off.view(np.float32), scale.reshape(-1), lab_cls, lab_box.reshape(-1)])
+        up = torch.from_numpy(buf).to(dev, non_blocking=True)
+        d_off, d_scale, d_cls, d_box = up.split([B + 1, 4 * B, M, 4 * M])
+        d_off = d_off.view(torch.int32)
+        ret_cls, ret_off = lab_cls, off
+    else:
+        bi = batch_idx.reshape(-1).to(dev).float()
+        sbi, order = torch.sort(bi, stable=True)
+        d_off = torch.searchsorted(sbi, torch.arange(B + 1, device=dev, dtype=torch.float32)).to(torch.int32)
+        d_cls = _c(cls.reshape(-1).to(dev).float()[order])
+        d_box = _c(bboxes.reshape(-1, 4).to(dev).float()[order])
+        d_scale = torch.from_numpy(scale).to(dev, non_blocking=True)
+        ret_cls, ret_off = d_cls, d_off               # (rows outside lab_off[0] .. lab_off[B] belong to no image)
+    predn = torch.empty(B, nq, 6, device=dev, dtype=torch.float32)
+    correct = torch.empty(B, nq, 10, device=dev, dtype=torch.uint8)
+    counts = torch.empty(B, device=dev, dtype=torch.int32)
+    call('tamtr_val_postprocess_match', ptr(y), dtype_code(y), B, nq, nd, float(imgsz), float(conf), _f32_at_most(float(iou)),
+         int(bool(single_cls)), float(max_wh), ptr(d_cls) if M else None, ptr(d_box) if M else None, ptr(d_off), M, ptr(d_scale),
+         ptr(predn), ptr(correct), ptr(counts), stream_ptr())
+    return predn, correct, counts, ret_cls, ret_off
+
+
 def img_augment(src, inv_affine, luts, flags, out_hw, border=114):
     """The pixel half of the training transforms for a whole batch (affine warp -> HSV look-up -> flips -> CHW float / 255;
     ultralytics/data/augment.py:415-420,590-609,636-666,920-926).  src u8 [B, SH, SW, 3], inv_affine f64 [B, 6]

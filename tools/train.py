@@ -62,6 +62,8 @@ def main():
     ap.add_argument('--drop-tail', action='store_true', help="leave out each epoch's incomplete last batch (NOT the reference's behaviour - its "
                                                              'build_dataloader has no drop_last and trains on the tail; the tail is a shape outside the tuned '
                                                              'tables and the recorded graphs: it runs kernel by kernel and its convolutions are searched once per machine)')
+    ap.add_argument('--host-postprocess', action='store_true', help='per-epoch validation with the per-image host loop (engine.Validator) '
+                    'instead of the one-launch device path (engine.DeviceValidator)')
     ap.add_argument('--conv-tuning', default='shipped', choices=['shipped', 'search', 'off'], help='MIOpen solver choice (tam-tr_amd/tuning.py)')
     args = ap.parse_args()
 
@@ -130,7 +132,7 @@ def main():
         print(json.dumps({k: (round(v, 5) if isinstance(v, float) else v) for k, v in rec.items()}), flush=True)
     E.fit(model, tl, prepare, args.epochs, val_loader=vl, lr0=args.lr0, close_mosaic=args.close_mosaic, imgsz=args.imgsz, reducer=reducer,
           rank=rank, world=world, save_dir=args.save_dir if rank == 0 else None, max_steps=args.max_steps, log=log, resume=resume,
-          static_graph=args.static_part == 'graph')
+          static_graph=args.static_part == 'graph', val_on_device=dev.type == 'cuda' and not args.host_postprocess)
     if tmp is not None:
         tmp.cleanup()
 

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Validate a checkpoint on a YOLO-format dataset (the reference's valTAMTR.py flow): mAP50 / mAP50-95 / precision / recall.
 
-    python tools/val.py --data dataset.yaml --text-feats clip_vitb32.npz --weights runs/train/TAMTR/best.pt [--split val]
+    python tools/val.py --data dataset.yaml --text-feats clip_vitb32.npz --weights runs/train/TAMTR/best.pt [--split val] [--save-json]
+
+Postprocess and label matching run on the device (engine.DeviceValidator, one HIP launch per batch); --host-postprocess goes back to the
+per-image host loop.  --save-json writes the reference's predictions.json into the run folder <project>/<name> (name, name2, ...).
 """
 import argparse
 import json
@@ -28,7 +31,13 @@ def main():
     ap.add_argument('--iou', type=float, default=0.7)
     ap.add_argument('--raw', action='store_true', help='use the raw weights instead of the EMA copy')
     ap.add_argument('--no-fuse', action='store_true', help='keep BatchNorm layers separate (valTAMTR.py fuses, nn/autobackend.py:115)')
+    ap.add_argument('--host-postprocess', action='store_true', help='the per-image host loop (engine.Validator); no per-class table, no JSON')
+    ap.add_argument('--save-json', action='store_true', help="write predictions.json (the reference's save_json=True)")
+    ap.add_argument('--project', default='runs/val')
+    ap.add_argument('--name', default='TAMTR')
     args = ap.parse_args()
+    if args.save_json and args.host_postprocess:
+        ap.error('--save-json needs the device path (drop --host-postprocess)')
 
     import tamtr_amd  # noqa: F401
     from tamtr_amd import data as D, engine as E
@@ -49,8 +58,15 @@ def main():
     model.autocast_dtype = torch.bfloat16 if args.dtype == 'bf16' else None    # predict() opens its own autocast region from this
     if not args.no_fuse:
         model.fuse()
+    save_dir = None
+    if args.save_json:
+        from tamtr_amd.predict import increment_path
+        save_dir = str(increment_path(os.path.join(args.project, args.name), mkdir=True))
     res = E.validate(model, (D.preprocess_batch(b, None, dev) for b in loader), imgsz=args.imgsz, conf=args.conf, iou=args.iou,
-                     autocast_dtype=torch.bfloat16 if args.dtype == 'bf16' else None)
+                     autocast_dtype=torch.bfloat16 if args.dtype == 'bf16' else None, on_device=not args.host_postprocess,
+                     save_json=save_dir, names={k: v.split('/')[0] for k, v in names.items()})
+    if save_dir is not None:
+        res['save_dir'] = save_dir
     print(json.dumps(res))
 
 
