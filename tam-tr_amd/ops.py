@@ -1204,6 +1204,24 @@ def _split_row_sums(grow, R):
     return rs[:, 16:16 + R], rs[:, :16], rs[:, 48], rs[:, 49]
 
 
+def _scan_hstate(Bn, KD, L, N, device):
+    """The state at every chunk boundary, which the scan forward leaves for its backward (include/tamtr_hip.h: hstate)."""
+    chunk = _lib.lib().tamtr_selective_scan_chunk()
+    return torch.empty(Bn, KD, (L + chunk - 1) // chunk, N, device=device, dtype=torch.float32)
+
+
+def _scan_bwd_slabs(Bm, Dk):
+    """Workspace of the scan backward's per-workgroup dB/dC slabs."""
+    nslab = _lib.lib().tamtr_selective_scan_bwd_slabs(Dk)
+    return torch.empty(2 * nslab * Bm.numel(), device=Bm.device, dtype=torch.float32)
+
+
+def _fold_directions(gu):
+    """[B, 4*Dk, L] per direction (un-reversed) -> gradient of the two stored copies [B, 2, Dk, L]."""
+    g4 = gu.view(gu.shape[0], 4, -1, gu.shape[2])
+    return g4[:, :2] + g4[:, 2:]
+
+
 class _SelectiveScan(torch.autograd.Function):
     @staticmethod
     def forward(ctx, u, delta, A, Bm, Cm, D, dbias, xmode):
@@ -1211,10 +1229,8 @@ class _SelectiveScan(torch.autograd.Function):
         Bn, KD, L = delta.shape
         K, N = Bm.shape[1], Bm.shape[2]
         u, delta, A, Bm, Cm, D, dbias = (_c(t.float()) for t in (u, delta, A, Bm, Cm, D, dbias))
-        chunk = _lib.lib().tamtr_selective_scan_chunk()
-        nchunk = (L + chunk - 1) // chunk
         y = torch.empty_like(delta)
-        hstate = torch.empty(Bn, KD, nchunk, N, device=u.device, dtype=torch.float32)
+        hstate = _scan_hstate(Bn, KD, L, N, u.device)
         call('tamtr_selective_scan_fwd', ptr(u), ptr(delta), ptr(A), ptr(Bm), ptr(Cm), ptr(D), ptr(dbias), ptr(y), ptr(hstate), Bn, K,
              KD // K, N, L, int(xmode), stream_ptr())
         ctx.save_for_backward(u, delta, A, Bm, Cm, D, dbias, hstate)
@@ -1230,15 +1246,11 @@ class _SelectiveScan(torch.autograd.Function):
         gu, gdelta = torch.empty_like(delta), torch.empty_like(delta)
         gB, gC = torch.empty_like(Bm), torch.empty_like(Cm)
         grow = _scan_row_sums(Bn, KD, u.device)
-        nslab = _lib.lib().tamtr_selective_scan_bwd_slabs(KD // K)
-        ws = torch.empty(2 * nslab * Bm.numel(), device=u.device, dtype=torch.float32)  # per-workgroup dB/dC slabs
+        ws = _scan_bwd_slabs(Bm, KD // K)
         call('tamtr_selective_scan_bwd', ptr(gy), ptr(u), ptr(delta), ptr(A), ptr(Bm), ptr(Cm), ptr(D), ptr(dbias), ptr(hstate), ptr(gu),
              ptr(gdelta), ptr(grow), ptr(gB), ptr(gC), ptr(ws), Bn, K, KD // K, N, L, ctx.xmode, stream_ptr())
         _, gA, gD, gbias = _split_row_sums(grow, 0)
-        if ctx.xmode:  # [B, 4*Dk, L] per direction (un-reversed) -> gradient of the two stored copies [B, 2, Dk, L]
-            g4 = gu.view(Bn, 4, KD // 4, L)
-            gu = g4[:, :2] + g4[:, 2:]
-        return gu, gdelta, gA, gB, gC, gD, gbias, None
+        return (_fold_directions(gu) if ctx.xmode else gu), gdelta, gA, gB, gC, gD, gbias, None
 
 
 def selective_scan(u, delta, A, Bm, Cm, D, delta_bias):
@@ -1251,46 +1263,59 @@ def selective_scan_cross_delta(u2, delta, A, Bm, Cm, D, delta_bias):
     return _SelectiveScan.apply(u2, delta, A, Bm, Cm, D, delta_bias, 1)
 
 
+# The host side of every kernel of the SS2D chain, once: each launcher allocates its kernel's outputs and workspaces, launches and returns
+# the tensors; the chained autograd nodes below and _SS2DCore both go through them.  `pc` = 1: the big time-indexed planes (u2, y, d(y),
+# d(u), d(u2)) are bf16 (include/tamtr_hip.h "bf16 PLANES"), 0: fp32.  A workspace that only the kernel reads dies with its launcher's frame.
+def _plane_dtype(pc):
+    return torch.bfloat16 if pc else torch.float32
+
+
+def _scan_dtproj_fwd(u, dtr, Wdt, A, Bm, Cm, D, dbias, xmode, pc):
+    """Scan with the dt projection inside: y [B, K*Dk, L] (a plane) and the chunk states for the backward."""
+    Bn, K, R, L = dtr.shape
+    KD, N = A.shape
+    y = torch.empty(Bn, KD, L, device=u.device, dtype=_plane_dtype(pc))
+    hstate = _scan_hstate(Bn, KD, L, N, u.device)
+    call('tamtr_selective_scan_dtproj_fwd', ptr(u), ptr(dtr), ptr(Wdt), ptr(A), ptr(Bm), ptr(Cm), ptr(D), ptr(dbias), ptr(y),
+         ptr(hstate), Bn, K, KD // K, N, R, L, xmode, pc, stream_ptr())
+    return y, hstate
+
+
+def _scan_dtproj_bwd(gy, u, dtr, Wdt, A, Bm, Cm, D, dbias, hstate, xmode, ws16, pc):
+    """Backward of _scan_dtproj_fwd.  xmode 1: gy is d(y) [B, K*Dk, L]; 3: the merged gradient in its two flattenings [B, 2, Dk, L].
+    Returns d(u) per direction [B, K*Dk, L] (a plane), d(dtr), dB, dC and the row sums d(Wdt), dA, dD, d(bias) of _split_row_sums."""
+    Bn, K, R, L = dtr.shape
+    KD, N = A.shape
+    gu = torch.empty(Bn, KD, L, device=u.device, dtype=_plane_dtype(pc))
+    # d(delta) is a workspace between the two backward kernels (the operand of d(dtr) = Wdt^T d(delta)); ws16: kept in bf16
+    gdelta = torch.empty(Bn, KD, L, device=u.device, dtype=_plane_dtype(ws16))
+    gdtr = torch.empty_like(dtr)
+    gB, gC = torch.empty_like(Bm), torch.empty_like(Cm)
+    grow = _scan_row_sums(Bn, KD, u.device)
+    ws = _scan_bwd_slabs(Bm, KD // K)
+    call('tamtr_selective_scan_dtproj_bwd', ptr(gy), ptr(u), ptr(dtr), ptr(Wdt), ptr(A), ptr(Bm), ptr(Cm), ptr(D), ptr(dbias),
+         ptr(hstate), ptr(gu), ptr(gdelta), ptr(gdtr), ptr(grow), ptr(gB), ptr(gC), ptr(ws), Bn, K,
+         KD // K, N, R, L, xmode, int(bool(ws16)) | (2 * pc), stream_ptr())
+    return (gu, gdtr, gB, gC) + _split_row_sums(grow, R)
+
+
 class _SelectiveScanDtProj(torch.autograd.Function):
     """Scan with the dt projection fused in: delta = Wdt . dtr is formed inside the kernels (never materialised)."""
 
     @staticmethod
     def forward(ctx, u, dtr, Wdt, A, Bm, Cm, D, dbias, xmode):
         require_gpu(u, dtr, Wdt, A, Bm, Cm, D, dbias)
-        Bn, K, R, L = dtr.shape
-        KD, N = A.shape
         u, dtr, Wdt, A, Bm, Cm, D, dbias = (_c(t.float()) for t in (u, dtr, Wdt, A, Bm, Cm, D, dbias))
-        chunk = _lib.lib().tamtr_selective_scan_chunk()
-        nchunk = (L + chunk - 1) // chunk
-        y = torch.empty(Bn, KD, L, device=u.device, dtype=torch.float32)
-        hstate = torch.empty(Bn, KD, nchunk, N, device=u.device, dtype=torch.float32)
-        call('tamtr_selective_scan_dtproj_fwd', ptr(u), ptr(dtr), ptr(Wdt), ptr(A), ptr(Bm), ptr(Cm), ptr(D), ptr(dbias), ptr(y),
-             ptr(hstate), Bn, K, KD // K, N, R, L, int(xmode), 0, stream_ptr())
+        y, hstate = _scan_dtproj_fwd(u, dtr, Wdt, A, Bm, Cm, D, dbias, int(xmode), 0)
         ctx.save_for_backward(u, dtr, Wdt, A, Bm, Cm, D, dbias, hstate)
         ctx.xmode = int(xmode)
         return y
 
     @staticmethod
     def backward(ctx, gy):
-        u, dtr, Wdt, A, Bm, Cm, D, dbias, hstate = ctx.saved_tensors
-        Bn, K, R, L = dtr.shape
-        KD, N = A.shape
         gy = _c(gy.float())
-        gu = torch.empty(Bn, KD, L, device=u.device, dtype=torch.float32)
-        gdelta = torch.empty(Bn, KD, L, device=u.device, dtype=torch.float32)  # workspace between the two backward kernels
-        gdtr = torch.empty_like(dtr)
-        gB, gC = torch.empty_like(Bm), torch.empty_like(Cm)
-        grow = _scan_row_sums(Bn, KD, dtr.device)
-        nslab = _lib.lib().tamtr_selective_scan_bwd_slabs(KD // K)
-        ws = torch.empty(2 * nslab * Bm.numel(), device=u.device, dtype=torch.float32)
-        call('tamtr_selective_scan_dtproj_bwd', ptr(gy), ptr(u), ptr(dtr), ptr(Wdt), ptr(A), ptr(Bm), ptr(Cm), ptr(D), ptr(dbias),
-             ptr(hstate), ptr(gu), ptr(gdelta), ptr(gdtr), ptr(grow), ptr(gB), ptr(gC), ptr(ws), Bn, K,
-             KD // K, N, R, L, ctx.xmode, 0, stream_ptr())
-        gW, gA, gD, gbias = _split_row_sums(grow, R)
-        if ctx.xmode:
-            g4 = gu.view(Bn, 4, KD // 4, L)
-            gu = g4[:, :2] + g4[:, 2:]
-        return gu, gdtr, gW, gA, gB, gC, gD, gbias, None
+        gu, gdtr, gB, gC, gW, gA, gD, gbias = _scan_dtproj_bwd(gy, *ctx.saved_tensors, ctx.xmode, False, 0)
+        return (_fold_directions(gu) if ctx.xmode else gu), gdtr, gW, gA, gB, gC, gD, gbias, None
 
 
 class _CrossScanInput(torch.autograd.Function):
@@ -1320,6 +1345,29 @@ def cross_scan_input(xc):
     return _CrossScanInput.apply(xc)
 
 
+def _dwconv_silu_cross_fwd(xz, weight, bias, D, pc):
+    """u2 [B, 2, D, H*W] (a plane) from xz [B, H, W, 2*D], and the fp32 forms of the parameters that the kernels read."""
+    B, H, W, C2 = xz.shape
+    w = _c(weight.float().reshape(D, 9))
+    bvec = _c(bias.float()) if bias is not None else None
+    u2 = torch.empty(B, 2, D, H * W, device=xz.device, dtype=_plane_dtype(pc))
+    call('tamtr_dwconv_silu_cross_fwd', ptr(xz), C2, ptr(w), ptr(bvec), ptr(u2), B, D, H, W, dtype_code(xz), pc, stream_ptr())
+    return u2, w, bvec
+
+
+def _dwconv_silu_cross_bwd(g2, xz, w, bvec, gxz, pc, w_shape, w_dt, b_dt):
+    """Writes the xi half of the caller's d(xz) buffer `gxz` (the z half belongs to the gate); returns d(weight), d(bias) in the
+    parameters' shape and dtypes (b_dt None: no bias)."""
+    B, H, W, C2 = xz.shape
+    D = w.shape[0]
+    tiles = _lib.lib().tamtr_dwconv_tiles(H, W)
+    ws = torch.empty(B, tiles, D, 10, device=xz.device, dtype=torch.float32)
+    call('tamtr_dwconv_silu_cross_bwd', ptr(g2), ptr(xz), C2, ptr(w), ptr(bvec if b_dt is not None else None), ptr(gxz), C2,
+         ptr(ws), B, D, H, W, dtype_code(xz), pc, stream_ptr())
+    gwb = slab_sum(ws.view(-1, D, 10))
+    return gwb[:, :9].reshape(w_shape).to(w_dt), (gwb[:, 9].to(b_dt) if b_dt is not None else None)
+
+
 class _DWConvSiluCross(torch.autograd.Function):
     """SS2D front end on the in_proj output as it lies: xz [B, H, W, 2*D] (xi = the first D channels of every pixel) ->
     u2 [B, 2, D, H*W] fp32 = SiLU(dwconv3x3(xi) + bias) in both flattenings (csrc/dwconv.hip)."""
@@ -1328,28 +1376,16 @@ class _DWConvSiluCross(torch.autograd.Function):
     def forward(ctx, xz, weight, bias, D):
         require_gpu(xz, weight)
         xz = _c(xz)
-        B, H, W, C2 = xz.shape
-        w = _c(weight.float().reshape(D, 9))
-        bvec = _c(bias.float()) if bias is not None else None
-        u2 = torch.empty(B, 2, D, H * W, device=xz.device, dtype=torch.float32)
-        call('tamtr_dwconv_silu_cross_fwd', ptr(xz), C2, ptr(w), ptr(bvec), ptr(u2), B, D, H, W, dtype_code(xz), 0, stream_ptr())
+        u2, w, bvec = _dwconv_silu_cross_fwd(xz, weight, bias, D, 0)
         ctx.save_for_backward(xz, w, bvec if bvec is not None else w.new_empty(0))
-        ctx.cfg = (D, weight.shape, weight.dtype, None if bias is None else bias.dtype)
+        ctx.cfg = (weight.shape, weight.dtype, None if bias is None else bias.dtype)
         return u2
 
     @staticmethod
     def backward(ctx, g2):
         xz, w, bvec = ctx.saved_tensors
-        D, w_shape, w_dt, b_dt = ctx.cfg
-        B, H, W, C2 = xz.shape
-        tiles = _lib.lib().tamtr_dwconv_tiles(H, W)
         gxz = torch.zeros_like(xz)  # the second half (z) gets its gradient from the gate path; autograd adds the two
-        ws = torch.empty(B, tiles, D, 10, device=xz.device, dtype=torch.float32)
-        call('tamtr_dwconv_silu_cross_bwd', ptr(_c(g2.float())), ptr(xz), C2, ptr(w), ptr(bvec if b_dt is not None else None), ptr(gxz), C2,
-             ptr(ws), B, D, H, W, dtype_code(xz), 0, stream_ptr())
-        gwb = slab_sum(ws.view(-1, D, 10))
-        gw = gwb[:, :9].reshape(w_shape).to(w_dt)
-        gb = gwb[:, 9].to(b_dt) if b_dt is not None else None
+        gw, gb = _dwconv_silu_cross_bwd(_c(g2.float()), xz, w, bvec, gxz, 0, *ctx.cfg)
         return gxz, gw, gb, None
 
 
@@ -1364,50 +1400,89 @@ def _split_len(L, min_len=1024, max_split=16):
     return S
 
 
+def _xproj_torch_fwd(wx, u2, cdt, R, N):
+    """x_proj as torch ops in the compute dtype `cdt`: wx [4, C, D] (C = R + 2N), u2 [B, 2, D, L] -> (dtr [B,4,R,L], Bs [B,4,N,L],
+    Cs [B,4,N,L]) fp32, contiguous, un-reversed, and what the backward reads: u2 and the two stacked weights [2C, D] in cdt.
+    Directions k and k + 2 share a base copy, so it is two [2C, D] x [D, L] products."""
+    C = R + 2 * N
+    ub = u2.to(cdt)
+    wa, wb = torch.cat([wx[0], wx[2]], 0).to(cdt), torch.cat([wx[1], wx[3]], 0).to(cdt)
+    with torch.autocast('cuda', enabled=False):
+        xa, xb = torch.matmul(wa, ub[:, 0]), torch.matmul(wb, ub[:, 1])  # [B, 2C, L]
+    parts = tuple(torch.stack([xa[:, lo:lo + n], xb[:, lo:lo + n], xa[:, C + lo:C + lo + n], xb[:, C + lo:C + lo + n]], 1).float()
+                  for lo, n in ((0, R), (R, N), (R + N, N)))
+    return parts, ub, wa, wb
+
+
+def _xproj_torch_bwd(gdtr, gBs, gCs, ub, wa, wb, R, N, gu2=None):
+    """Backward of _xproj_torch_fwd: per copy one [D, 2C] x [2C, L] product, d/d(u2) of that copy, and the weight gradient (a
+    reduction over L per image) as a batched GEMM over L slices.  With `gu2` [B, 2, D, L] each product is cast straight into its plane
+    (no stack + cast) as soon as it exists; without, the two products are returned for the caller's fold.  Returns (products, the two
+    stacked weight gradients [2C, D] fp32)."""
+    Bn, _, D, L = ub.shape
+    C = R + 2 * N
+    S = _split_len(L)
+    gws, ms = [], []
+    with torch.autocast('cuda', enabled=False):
+        for i, w in ((0, wa), (1, wb)):
+            gx = torch.cat([gdtr[:, i], gBs[:, i], gCs[:, i], gdtr[:, i + 2], gBs[:, i + 2], gCs[:, i + 2]], 1).to(ub.dtype)  # [B, 2C, L]
+            m = torch.matmul(w.t(), gx)                                                                                      # [B, D, L]
+            if gu2 is None:
+                ms.append(m)
+            else:
+                gu2[:, i].copy_(m)
+            ga = gx.view(Bn, 2 * C, S, L // S).transpose(1, 2).reshape(Bn * S, 2 * C, L // S)
+            ua = ub[:, i].reshape(Bn, D, S, L // S).transpose(1, 2).reshape(Bn * S, D, L // S)
+            gws.append(slab_sum(torch.bmm(ga, ua.transpose(1, 2))))  # [2C, D]
+    return ms, gws
+
+
+def _xproj_unstack_wgrad(gws, C, dt):
+    """The gradients of the two stacked weights [2C, D] (rows [W_i ; W_(i+2)] of copy i) -> d(x_proj_weight) [4, C, D]."""
+    return torch.stack([gws[0][:C], gws[1][:C], gws[0][C:], gws[1][C:]], 0).to(dt)
+
+
 class _XProjCross(torch.autograd.Function):
-    """x_proj of SS2D (vmamba.py:962-970) on the pair layout: wx [4, C, D] (C = R + 2N), u2 [B, 2, D, L] ->
-    dtr [B,4,R,L], Bs [B,4,N,L], Cs [B,4,N,L] (fp32, contiguous, un-reversed).  Directions k and k+2 share a base copy, so it
-    is two [2C, D] x [D, L] products; their weight gradient (a reduction over L per image) runs as a batched GEMM over L
-    slices, and the output assembly has an explicit backward (one concatenation per copy instead of ~30 slice kernels)."""
+    """x_proj of SS2D (vmamba.py:962-970) on the pair layout in autocast's dtype, with an explicit backward of the output assembly
+    (one concatenation per copy instead of ~30 slice kernels): _xproj_torch_fwd / _xproj_torch_bwd."""
 
     @staticmethod
     def forward(ctx, wx, u2, R, N):
         cdt = torch.get_autocast_dtype('cuda') if torch.is_autocast_enabled('cuda') else torch.float32
-        C = R + 2 * N
-        ub = u2.to(cdt)
-        wa, wb = torch.cat([wx[0], wx[2]], 0).to(cdt), torch.cat([wx[1], wx[3]], 0).to(cdt)
-        with torch.autocast('cuda', enabled=False):
-            xa, xb = torch.matmul(wa, ub[:, 0]), torch.matmul(wb, ub[:, 1])  # [B, 2C, L]
-        parts = []
-        for lo, n in ((0, R), (R, N), (R + N, N)):
-            parts.append(torch.stack([xa[:, lo:lo + n], xb[:, lo:lo + n], xa[:, C + lo:C + lo + n], xb[:, C + lo:C + lo + n]], 1).float())
+        parts, ub, wa, wb = _xproj_torch_fwd(wx, u2, cdt, R, N)
         ctx.save_for_backward(ub, wa, wb)
         ctx.cfg = (R, N, wx.dtype, u2.dtype)
-        return tuple(parts)
+        return parts
 
     @staticmethod
     def backward(ctx, gdtr, gBs, gCs):
         ub, wa, wb = ctx.saved_tensors
         R, N, w_dt, u_dt = ctx.cfg
-        cdt = ub.dtype
-        Bn, _, D, L = ub.shape
-        C = R + 2 * N
-        S = _split_len(L)
-        gws = []
-        gu2 = torch.empty(Bn, 2, D, L, device=ub.device, dtype=u_dt)  # each product is cast straight into its plane (no stack + cast)
-        with torch.autocast('cuda', enabled=False):
-            for i, w in ((0, wa), (1, wb)):
-                gx = torch.cat([gdtr[:, i], gBs[:, i], gCs[:, i], gdtr[:, i + 2], gBs[:, i + 2], gCs[:, i + 2]], 1).to(cdt)  # [B, 2C, L]
-                gu2[:, i].copy_(torch.matmul(w.t(), gx))
-                ga = gx.view(Bn, 2 * C, S, L // S).transpose(1, 2).reshape(Bn * S, 2 * C, L // S)
-                ua = ub[:, i].reshape(Bn, D, S, L // S).transpose(1, 2).reshape(Bn * S, D, L // S)
-                gws.append(slab_sum(torch.bmm(ga, ua.transpose(1, 2))))  # [2C, D]
-        gwx = torch.stack([gws[0][:C], gws[1][:C], gws[0][C:], gws[1][C:]], 0).to(w_dt)
-        return gwx, gu2, None, None
+        gu2 = torch.empty(ub.shape, device=ub.device, dtype=u_dt)
+        _, gws = _xproj_torch_bwd(gdtr, gBs, gCs, ub, wa, wb, R, N, gu2)
+        return _xproj_unstack_wgrad(gws, R + 2 * N, w_dt), gu2, None, None
 
 
 def x_proj_cross(wx, u2, R, N):
     return _XProjCross.apply(wx, u2, R, N)
+
+
+def _cross_merge_fwd(y, H, W, pc):
+    """CrossMerge (csms6s.py:26-34) of the scan's planes y [B, 4*Dk, H*W] straight into [B, H*W, Dk] fp32 (what out_norm / out_proj
+    consume): one tiled-transpose kernel."""
+    Bn, Dk = y.shape[0], y.shape[1] // 4
+    ymT = torch.empty(Bn, H * W, Dk, device=y.device, dtype=torch.float32)
+    call('tamtr_cross_merge_fwd', ptr(y), ptr(ymT), Bn, Dk, H, W, pc, stream_ptr())
+    return ymT
+
+
+def _cross_merge_bwd(gm, H, W, pc):
+    """gm [B, H*W, Dk] fp32 -> the merged gradient in its two flattenings [B, 2, Dk, H*W] (a plane), the xmode 3 operand of the scan
+    backward."""
+    Bn, L, Dk = gm.shape
+    g2 = torch.empty(Bn, 2, Dk, L, device=gm.device, dtype=_plane_dtype(pc))
+    call('tamtr_cross_merge_bwd', ptr(gm), ptr(g2), Bn, Dk, H, W, pc, stream_ptr())
+    return g2
 
 
 class _SelectiveScanCrossMerged(torch.autograd.Function):
@@ -1419,56 +1494,60 @@ class _SelectiveScanCrossMerged(torch.autograd.Function):
     def forward(ctx, u2, dtr, Wdt, A, Bm, Cm, D, dbias, H, W, token_major=False):
         require_gpu(u2, dtr, Wdt, A, Bm, Cm, D, dbias)
         u2, dtr, Wdt, A, Bm, Cm, D, dbias = (_c(t.float()) for t in (u2, dtr, Wdt, A, Bm, Cm, D, dbias))
-        Bn, _, Dk, L = u2.shape
-        K, R, N = 4, dtr.shape[2], A.shape[1]
-        chunk = _lib.lib().tamtr_selective_scan_chunk()
-        nchunk = (L + chunk - 1) // chunk
-        y = torch.empty(Bn, K, Dk, L, device=u2.device, dtype=torch.float32)
-        hstate = torch.empty(Bn, K * Dk, nchunk, N, device=u2.device, dtype=torch.float32)
-        call('tamtr_selective_scan_dtproj_fwd', ptr(u2), ptr(dtr), ptr(Wdt), ptr(A), ptr(Bm), ptr(Cm), ptr(D), ptr(dbias), ptr(y),
-             ptr(hstate), Bn, K, Dk, N, R, L, 1, 0, stream_ptr())
+        y, hstate = _scan_dtproj_fwd(u2, dtr, Wdt, A, Bm, Cm, D, dbias, 1, 0)
         ctx.save_for_backward(u2, dtr, Wdt, A, Bm, Cm, D, dbias, hstate)
         ctx.hw = (H, W, token_major)
-        if token_major:  # CrossMerge straight into [B, L, Dk] (what out_norm / out_proj consume): one tiled-transpose kernel
-            ymT = torch.empty(Bn, L, Dk, device=u2.device, dtype=torch.float32)
-            call('tamtr_cross_merge_fwd', ptr(y), ptr(ymT), Bn, Dk, H, W, 0, stream_ptr())
-            return ymT
+        if token_major:
+            return _cross_merge_fwd(y, H, W, 0)
+        Bn, _, Dk, L = u2.shape
+        y = y.view(Bn, 4, Dk, L)
         ym = y[:, 0] + y[:, 2]
         ym += (y[:, 1] + y[:, 3]).view(Bn, Dk, W, H).transpose(2, 3).reshape(Bn, Dk, L)
         return ym
 
     @staticmethod
     def backward(ctx, gm):
-        u2, dtr, Wdt, A, Bm, Cm, D, dbias, hstate = ctx.saved_tensors
         H, W, token_major = ctx.hw
-        Bn, K, R, L = dtr.shape
-        Dk, N = u2.shape[2], A.shape[1]
-        KD = K * Dk
-        g2 = torch.empty(Bn, 2, Dk, L, device=u2.device, dtype=torch.float32)
         if token_major:
-            call('tamtr_cross_merge_bwd', ptr(_c(gm.float())), ptr(g2), Bn, Dk, H, W, 0, stream_ptr())
+            g2 = _cross_merge_bwd(_c(gm.float()), H, W, 0)
         else:
+            Bn, Dk, L = gm.shape
+            g2 = torch.empty(Bn, 2, Dk, L, device=gm.device, dtype=torch.float32)
             g2[:, 0] = gm
             g2[:, 1].view(Bn, Dk, W, H).copy_(gm.view(Bn, Dk, H, W).transpose(2, 3))
-        gu = torch.empty(Bn, KD, L, device=u2.device, dtype=torch.float32)
-        gdelta = torch.empty(Bn, KD, L, device=u2.device, dtype=torch.float32)
-        gdtr = torch.empty_like(dtr)
-        gB, gC = torch.empty_like(Bm), torch.empty_like(Cm)
-        grow = _scan_row_sums(Bn, KD, dtr.device)
-        nslab = _lib.lib().tamtr_selective_scan_bwd_slabs(Dk)
-        ws = torch.empty(2 * nslab * Bm.numel(), device=u2.device, dtype=torch.float32)
-        call('tamtr_selective_scan_dtproj_bwd', ptr(g2), ptr(u2), ptr(dtr), ptr(Wdt), ptr(A), ptr(Bm), ptr(Cm), ptr(D), ptr(dbias),
-             ptr(hstate), ptr(gu), ptr(gdelta), ptr(gdtr), ptr(grow), ptr(gB), ptr(gC), ptr(ws), Bn, K,
-             Dk, N, R, L, 3, 0, stream_ptr())
-        gW, gA, gD, gbias = _split_row_sums(grow, R)
-        g4 = gu.view(Bn, 4, Dk, L)
-        return g4[:, :2] + g4[:, 2:], gdtr, gW, gA, gB, gC, gD, gbias, None, None, None
+        gu, gdtr, gB, gC, gW, gA, gD, gbias = _scan_dtproj_bwd(g2, *ctx.saved_tensors, 3, False, 0)
+        return _fold_directions(gu), gdtr, gW, gA, gB, gC, gD, gbias, None, None, None
 
 
 def selective_scan_cross_merged(u2, dtr, Wdt, A, Bm, Cm, D, delta_bias, H, W, token_major=False):
     """selective_scan_cross followed by the cross-merge: returns [B, Dk, H*W] in row-major pixel order, or with
     token_major=True [B, H*W, Dk] (needs Dk % 32 == 0)."""
     return _SelectiveScanCrossMerged.apply(u2, dtr, Wdt, A, Bm, Cm, D, delta_bias, H, W, token_major)
+
+
+def _ln_gate_fwd(x, xz, gamma, beta, eps):
+    """out = LayerNorm(x; gamma, beta) * SiLU(z) in xz's dtype, the per-token statistics, and the fp32 forms of gamma and beta."""
+    D = x.shape[-1]
+    ntok = x.numel() // D
+    g32, b32 = _c(gamma.float()), _c(beta.float())
+    out = torch.empty(x.shape, device=x.device, dtype=xz.dtype)
+    stats = torch.empty(ntok, 2, device=x.device, dtype=torch.float32)
+    call('tamtr_ln_gate_fwd', ptr(x), ptr(xz), xz.shape[-1], ptr(g32), ptr(b32), ptr(out), ptr(stats), ntok, D, float(eps),
+         dtype_code(xz), stream_ptr())
+    return out, stats, g32, b32
+
+
+def _ln_gate_bwd(gout, x, xz, g32, b32, stats, gxz):
+    """Writes the z half of the caller's d(xz) buffer `gxz` (the xi half belongs to the front end); returns d(x) and the fp32 sums
+    [2, D]: d(gamma), d(beta)."""
+    D = x.shape[-1]
+    ntok = x.numel() // D
+    gx = torch.empty_like(x)
+    nblk = _lib.lib().tamtr_ln_gate_blocks(ntok)
+    part = torch.empty(nblk, 2, D, device=x.device, dtype=torch.float32)
+    call('tamtr_ln_gate_bwd', ptr(gout), ptr(x), ptr(xz), xz.shape[-1], ptr(g32), ptr(b32), ptr(stats), ptr(gx), ptr(gxz), ptr(part),
+         ntok, D, dtype_code(xz), stream_ptr())
+    return gx, slab_sum(part)
 
 
 class _LNGate(torch.autograd.Function):
@@ -1479,13 +1558,7 @@ class _LNGate(torch.autograd.Function):
     def forward(ctx, x, xz, gamma, beta, eps):
         require_gpu(x, xz, gamma, beta)
         x, xz = _c(x.float()), _c(xz)
-        D = x.shape[-1]
-        ntok = x.numel() // D
-        g32, b32 = _c(gamma.float()), _c(beta.float())
-        out = torch.empty(x.shape, device=x.device, dtype=xz.dtype)
-        stats = torch.empty(ntok, 2, device=x.device, dtype=torch.float32)
-        call('tamtr_ln_gate_fwd', ptr(x), ptr(xz), xz.shape[-1], ptr(g32), ptr(b32), ptr(out), ptr(stats), ntok, D, float(eps),
-             dtype_code(xz), stream_ptr())
+        out, stats, g32, b32 = _ln_gate_fwd(x, xz, gamma, beta, eps)
         ctx.save_for_backward(x, xz, g32, b32, stats)
         ctx.cfg = (gamma.dtype, beta.dtype)
         return out
@@ -1493,16 +1566,9 @@ class _LNGate(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         x, xz, g32, b32, stats = ctx.saved_tensors
-        D = x.shape[-1]
-        ntok = x.numel() // D
         gout = _c(gout.to(xz.dtype))
-        gx = torch.empty_like(x)
         gxz = torch.zeros_like(xz)  # the xi half gets its gradient from the conv path; autograd adds the two
-        nblk = _lib.lib().tamtr_ln_gate_blocks(ntok)
-        part = torch.empty(nblk, 2, D, device=x.device, dtype=torch.float32)
-        call('tamtr_ln_gate_bwd', ptr(gout), ptr(x), ptr(xz), xz.shape[-1], ptr(g32), ptr(b32), ptr(stats), ptr(gx), ptr(gxz), ptr(part),
-             ntok, D, dtype_code(xz), stream_ptr())
-        gsum = slab_sum(part)
+        gx, gsum = _ln_gate_bwd(gout, x, xz, g32, b32, stats, gxz)
         return gx, gxz, gsum[0].to(ctx.cfg[0]), gsum[1].to(ctx.cfg[1]), None
 
 
@@ -1602,13 +1668,15 @@ def xproj_pack_weight_t(wcat, C):
 
 class _SS2DCore(torch.autograd.Function):
     """SS2D between in_proj and out_proj as ONE autograd node (vmamba.py:949-1008): depthwise 3x3 + SiLU + cross-scan layout ->
-    x_proj -> selective scan with the dt projection inside -> cross-merge -> out_norm x SiLU(z).  Same kernels and the same
-    arithmetic as dwconv_silu_cross / x_proj_cross / selective_scan_cross_merged / ln_gate chained; what the single node buys is
-    the backward's buffer plan, which autograd otherwise dictates:
+    x_proj -> selective scan with the dt projection inside -> cross-merge -> out_norm x SiLU(z).  It calls the launchers that
+    dwconv_silu_cross / x_proj_cross / selective_scan_cross_merged / ln_gate chained call, so the kernels and the arithmetic are theirs;
+    only the x_proj on own kernels (csrc/xproj.hip) has no chained form.  What the single node buys is the backward's buffer plan,
+    which autograd otherwise dictates:
       * d/d(u2) = fold of the scan's four planes + the two x_proj products in one pass (csrc/fold.hip) instead of a slice add, a cast
         and an accumulation (5 reads + 3 writes of an 839 MB plane pair at level 0 -> 3 + 1);
       * d/d(xz): the gate kernel writes the z half and the depthwise-conv kernel the xi half of ONE buffer (before: two zero-filled
-        [B,H,W,2D] maps and their sum)."""
+        [B,H,W,2D] maps and their sum).
+    The `del` statements are that plan: a plane is released as soon as its last reader has been launched."""
 
     @staticmethod
     def forward(ctx, xz, conv_w, conv_b, wx, Wdt, A, Ds, dbias, gamma, beta, eps, R, N):
@@ -1616,48 +1684,27 @@ class _SS2DCore(torch.autograd.Function):
         xz = _c(xz)
         B, H, W, C2 = xz.shape
         D, L, K = C2 // 2, H * W, 4
-        # front end
-        cw = _c(conv_w.float().reshape(D, 9))
-        cb = _c(conv_b.float()) if conv_b is not None else None
         # bf16 mode: the big time-indexed planes that only cross HBM between kernels (u2, y, and in the backward d(y), d(u), d(u2)) are bf16;
         # the recurrence, its states and every gradient sum stay fp32 (include/tamtr_hip.h "bf16 PLANES")
-        p16 = ss2d_bf16_planes(xz.dtype, D, L, R, N)
-        pdt, pc = (torch.bfloat16, 1) if p16 else (torch.float32, 0)
-        u2 = torch.empty(B, 2, D, L, device=xz.device, dtype=pdt)
-        call('tamtr_dwconv_silu_cross_fwd', ptr(xz), C2, ptr(cw), ptr(cb), ptr(u2), B, D, H, W, dtype_code(xz), pc, stream_ptr())
+        pc = int(ss2d_bf16_planes(xz.dtype, D, L, R, N))
+        u2, cw, cb = _dwconv_silu_cross_fwd(xz, conv_w, conv_b, D, pc)
         # x_proj on the two copies (directions k and k + 2 share one)
         cdt = xz.dtype if xz.dtype == torch.bfloat16 else torch.float32
-        C = R + 2 * N
         own_xp = xproj_ok(cdt, D, L, R, N)
+        ub = wa = wb = wcat = None
         if own_xp:   # csrc/xproj.hip: u2 read once as f32, the three outputs written in the scan's layout
             wcat = xproj_pack_weight(wx)
             dtr, Bs, Cs = (torch.empty(B, K, n, L, device=xz.device, dtype=torch.float32) for n in (R, N, N))
             call('tamtr_xproj_fwd', ptr(u2), ptr(wcat), ptr(dtr), ptr(Bs), ptr(Cs), B, D, L, R, pc, stream_ptr())
-            ub = wa = wb = None
         else:
-            wcat = None
-            ub = u2.to(cdt)
-            wa, wb = torch.cat([wx[0], wx[2]], 0).to(cdt), torch.cat([wx[1], wx[3]], 0).to(cdt)
-            with torch.autocast('cuda', enabled=False):
-                xa, xb = torch.matmul(wa, ub[:, 0]), torch.matmul(wb, ub[:, 1])  # [B, 2C, L]
-            dtr, Bs, Cs = (torch.stack([xa[:, lo:lo + n], xb[:, lo:lo + n], xa[:, C + lo:C + lo + n], xb[:, C + lo:C + lo + n]], 1).float()
-                           for lo, n in ((0, R), (R, N), (R + N, N)))
+            (dtr, Bs, Cs), ub, wa, wb = _xproj_torch_fwd(wx, u2, cdt, R, N)
         # scan + cross-merge, token-major
         Wdt32, A32, D32, db32 = (_c(t.float()) for t in (Wdt, A, Ds, dbias))
-        chunk = _lib.lib().tamtr_selective_scan_chunk()
-        y = torch.empty(B, K, D, L, device=xz.device, dtype=pdt)
-        hstate = torch.empty(B, K * D, (L + chunk - 1) // chunk, N, device=xz.device, dtype=torch.float32)
-        call('tamtr_selective_scan_dtproj_fwd', ptr(u2), ptr(dtr), ptr(Wdt32), ptr(A32), ptr(Bs), ptr(Cs), ptr(D32), ptr(db32), ptr(y),
-             ptr(hstate), B, K, D, N, R, L, 1, pc, stream_ptr())
-        ymT = torch.empty(B, L, D, device=xz.device, dtype=torch.float32)
-        call('tamtr_cross_merge_fwd', ptr(y), ptr(ymT), B, D, H, W, pc, stream_ptr())
+        y, hstate = _scan_dtproj_fwd(u2, dtr, Wdt32, A32, Bs, Cs, D32, db32, 1, pc)
+        ymT = _cross_merge_fwd(y, H, W, pc)
         del y
         # out_norm x SiLU(z)
-        g32, b32 = _c(gamma.float()), _c(beta.float())
-        out = torch.empty(B, L, D, device=xz.device, dtype=xz.dtype)
-        stats = torch.empty(B * L, 2, device=xz.device, dtype=torch.float32)
-        call('tamtr_ln_gate_fwd', ptr(ymT), ptr(xz), C2, ptr(g32), ptr(b32), ptr(out), ptr(stats), B * L, D, float(eps), dtype_code(xz),
-             stream_ptr())
+        out, stats, g32, b32 = _ln_gate_fwd(ymT, xz, gamma, beta, eps)
         none = cw.new_empty(0)
         ctx.save_for_backward(xz, cw, cb if cb is not None else none, u2, ub if ub is not None else none, wa if wa is not None else none,
                               wb if wb is not None else none, wcat if wcat is not None else none, dtr, Bs, Cs, Wdt32, A32, D32, db32, hstate,
@@ -1672,71 +1719,37 @@ class _SS2DCore(torch.autograd.Function):
         (xz, cw, cb, u2, ub, wa, wb, wcat, dtr, Bs, Cs, Wdt32, A32, D32, db32, hstate, ymT, g32, b32, stats) = ctx.saved_tensors
         R, N, H, W, cw_shape, cw_dt, cb_dt, wx_dt, wdt_dt, a_dt, d_dt, db_dt, ga_dt, be_dt = ctx.cfg
         B, _, _, C2 = xz.shape
-        D, L, K, C = C2 // 2, H * W, 4, R + 2 * N
-        dev = xz.device
+        D, L, C = C2 // 2, H * W, R + 2 * N
+        pc = int(u2.dtype == torch.bfloat16)   # the planes' element type (forward's choice)
         # gate: d/d(ymT), the z half of d/d(xz), d(gamma), d(beta)
-        gout = _c(gout.to(xz.dtype))
-        gy = torch.empty_like(ymT)
         gxz = torch.empty_like(xz)   # z half from the gate kernel here, xi half from the depthwise-conv kernel below
-        nblk = _lib.lib().tamtr_ln_gate_blocks(B * L)
-        part = torch.empty(nblk, 2, D, device=dev, dtype=torch.float32)
-        call('tamtr_ln_gate_bwd', ptr(gout), ptr(ymT), ptr(xz), C2, ptr(g32), ptr(b32), ptr(stats), ptr(gy), ptr(gxz), ptr(part), B * L, D,
-             dtype_code(xz), stream_ptr())
-        gsum = slab_sum(part)
+        gout = _c(gout.to(xz.dtype))
+        gy, gsum = _ln_gate_bwd(gout, ymT, xz, g32, b32, stats, gxz)
         # cross-merge and scan
-        pdt = u2.dtype                       # the planes' element type (forward's choice)
-        pc = 1 if pdt == torch.bfloat16 else 0
-        g2 = torch.empty(B, 2, D, L, device=dev, dtype=pdt)
-        call('tamtr_cross_merge_bwd', ptr(gy), ptr(g2), B, D, H, W, pc, stream_ptr())
+        g2 = _cross_merge_bwd(gy, H, W, pc)
         del gy
-        gu = torch.empty(B, K * D, L, device=dev, dtype=pdt)
-        # d(delta) workspace: only the operand of gdtr = Wdt^T d(delta); in bf16 mode (gdtr is rounded to bf16 below anyway) kept in bf16
+        # in bf16 mode d(dtr) is rounded to bf16 below anyway, so the d(delta) workspace is kept in bf16
         ws16 = pc or (xz.dtype == torch.bfloat16 and L % 4 == 0)
-        gdelta = torch.empty(B, K * D, L, device=dev, dtype=torch.bfloat16 if ws16 else torch.float32)
-        gdtr = torch.empty_like(dtr)
-        gB, gC = torch.empty_like(Bs), torch.empty_like(Cs)
-        grow = _scan_row_sums(B, K * D, dev)
-        nslab = _lib.lib().tamtr_selective_scan_bwd_slabs(D)
-        ws = torch.empty(2 * nslab * Bs.numel(), device=dev, dtype=torch.float32)
-        call('tamtr_selective_scan_dtproj_bwd', ptr(g2), ptr(u2), ptr(dtr), ptr(Wdt32), ptr(A32), ptr(Bs), ptr(Cs), ptr(D32), ptr(db32),
-             ptr(hstate), ptr(gu), ptr(gdelta), ptr(gdtr), ptr(grow), ptr(gB), ptr(gC), ptr(ws), B, K, D, N, R, L,
-             3, int(bool(ws16)) | (2 * pc), stream_ptr())
-        gW, gA, gD, gdb = _split_row_sums(grow, R)
-        del gdelta, ws, g2
-        gu2 = torch.empty(B, 2, D, L, device=dev, dtype=pdt)
+        gu, gdtr, gB, gC, gW, gA, gD, gdb = _scan_dtproj_bwd(g2, u2, dtr, Wdt32, A32, Bs, Cs, D32, db32, hstate, 3, ws16, pc)
+        del g2
+        gu2 = torch.empty(B, 2, D, L, device=xz.device, dtype=_plane_dtype(pc))
         if ctx.own_xp:
             # csrc/xproj.hip: d/d(u2) = fold of the scan's four planes + Wcat^T G in one pass; dWcat as per-slice partial tiles + ordered sum
             wT = xproj_pack_weight_t(wcat, C)
             call('tamtr_xproj_bwd_dx', ptr(gu), ptr(gdtr), ptr(gB), ptr(gC), ptr(wT), ptr(gu2), B, D, L, R, pc, stream_ptr())
             del gu
             nsl = _lib.lib().tamtr_xproj_dw_slices(L)
-            part = torch.empty(B * nsl, 2, 2 * C, D, device=dev, dtype=torch.float32)
+            part = torch.empty(B * nsl, 2, 2 * C, D, device=xz.device, dtype=torch.float32)
             call('tamtr_xproj_bwd_dw', ptr(u2), ptr(gdtr), ptr(gB), ptr(gC), ptr(part), B, D, L, R, pc, stream_ptr())
             gws = slab_sum(part)
             del part
         else:
-            # x_proj backward: per copy one [D, 2C] x [2C, L] product and the weight gradient as a batched GEMM over L slices
-            cdt = ub.dtype
-            S = _split_len(L)
-            gws, ms = [], []
-            with torch.autocast('cuda', enabled=False):
-                for i, w in ((0, wa), (1, wb)):
-                    gx = torch.cat([gdtr[:, i], gB[:, i], gC[:, i], gdtr[:, i + 2], gB[:, i + 2], gC[:, i + 2]], 1).to(cdt)  # [B, 2C, L]
-                    ms.append(torch.matmul(w.t(), gx))                                                                         # [B, D, L]
-                    ga = gx.view(B, 2 * C, S, L // S).transpose(1, 2).reshape(B * S, 2 * C, L // S)
-                    ua = ub[:, i].reshape(B, D, S, L // S).transpose(1, 2).reshape(B * S, D, L // S)
-                    gws.append(slab_sum(torch.bmm(ga, ua.transpose(1, 2))))  # [2C, D]
+            ms, gws = _xproj_torch_bwd(gdtr, gB, gC, ub, wa, wb, R, N)
             call('tamtr_fold_add', ptr(gu), ptr(_c(ms[0])), ptr(_c(ms[1])), ptr(gu2), B, D * L, dtype_code(ms[0]), stream_ptr())
             del gu, ms
-        gwx = torch.stack([gws[0][:C], gws[1][:C], gws[0][C:], gws[1][C:]], 0).to(wx_dt)
+        gwx = _xproj_unstack_wgrad(gws, C, wx_dt)
         # front end: the xi half of d/d(xz), d(conv weight), d(conv bias)
-        tiles = _lib.lib().tamtr_dwconv_tiles(H, W)
-        wsd = torch.empty(B, tiles, D, 10, device=dev, dtype=torch.float32)
-        call('tamtr_dwconv_silu_cross_bwd', ptr(gu2), ptr(xz), C2, ptr(cw), ptr(cb if cb_dt is not None else None), ptr(gxz), C2, ptr(wsd), B,
-             D, H, W, dtype_code(xz), pc, stream_ptr())
-        gwb = slab_sum(wsd.view(-1, D, 10))
-        gcw = gwb[:, :9].reshape(cw_shape).to(cw_dt)
-        gcb = gwb[:, 9].to(cb_dt) if cb_dt is not None else None
+        gcw, gcb = _dwconv_silu_cross_bwd(gu2, xz, cw, cb, gxz, pc, cw_shape, cw_dt, cb_dt)
         return (gxz, gcw, gcb, gwx, gW.to(wdt_dt), gA.to(a_dt), gD.to(d_dt), gdb.to(db_dt), gsum[0].to(ga_dt), gsum[1].to(be_dt), None, None,
                 None)
 

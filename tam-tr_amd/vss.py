@@ -15,8 +15,6 @@ import os
 
 from . import ops
 
-_EINSUM_DT = os.environ.get('TAMTR_SS2D_EINSUM') == '1'
-
 
 class TallLinear(nn.Linear):
     """nn.Linear (same parameters / state_dict keys) whose weight gradient on the GPU in bf16 is the split-K batched GEMM of
@@ -47,20 +45,6 @@ class DropPath(nn.Module):
         return x * mask / keep
 
 
-def cross_scan(x):
-    """[B,C,H,W] -> [B,4,C,HW]: row-major, column-major and both reversed (csms6s.py:4-14); autograd handles the merge."""
-    a = x.flatten(2)
-    b = x.transpose(2, 3).flatten(2)
-    return torch.stack([a, b, a.flip(-1), b.flip(-1)], 1)
-
-
-def cross_merge(ys, H, W):
-    """[B,4,D,HW] -> [B,D,HW] (csms6s.py:26-34)."""
-    B, K, D, L = ys.shape
-    y = ys[:, 0:2] + ys[:, 2:4].flip(-1)
-    return y[:, 0] + y[:, 1].view(B, D, W, H).transpose(2, 3).reshape(B, D, L)
-
-
 class SS2D(nn.Module):
     def __init__(self, d_model=96, d_state=16, ssm_ratio=2.0, dt_rank='auto', d_conv=3, conv_bias=True, bias=False,
                  dt_min=0.001, dt_max=0.1, dt_scale=1.0, dt_init_floor=1e-4, **kwargs):
@@ -85,55 +69,42 @@ class SS2D(nn.Module):
         self.A_logs._no_weight_decay = True
         self.Ds._no_weight_decay = True
 
+    def _scan_params(self):
+        """Wdt [4*D, R], A [4*D, N], Ds [4*D], dt bias [4*D] in fp32, as the scan kernels take them."""
+        As = -torch.exp(self.A_logs.float())
+        return self.dt_projs_weight.float().reshape(-1, self.dt_rank), As, self.Ds.float(), self.dt_projs_bias.float().reshape(-1)
+
     def forward(self, x):  # x: [B,H,W,C]
         B, H, W, _ = x.shape
         xz = self.in_proj(x)
-        xi, z = xz.chunk(2, -1)
-        K, R, N, L, D = 4, self.dt_rank, self.d_state, H * W, self.d_inner
-        fused_front = not _EINSUM_DT and D % 32 == 0 and self.conv2d.kernel_size == (3, 3)
-        xc = None if fused_front else self.conv2d(xi.permute(0, 3, 1, 2).contiguous())  # [B,D,H,W]
+        R, N, D = self.dt_rank, self.d_state, self.d_inner
+        fused_front = D % 32 == 0 and self.conv2d.kernel_size == (3, 3)
+        fused_back = D in (64, 128, 256, 512, 1024)
         # Cross-scan WITHOUT materialising the four sequences (csms6s.py:4-14): directions 0/2 walk the row-major flattening
         # forwards/backwards, 1/3 the column-major one; the kernel reads the two stored copies and reverses on the fly, and all
         # per-direction operands are kept in the un-reversed order of their base copy.  The scan runs in fp32 (vmamba.py:980).
-        if fused_front and x.is_cuda and D in (64, 128, 256, 512, 1024) and os.environ.get('TAMTR_SS2D_SPLIT') != '1':
-            # the whole core as one autograd node (ops._SS2DCore): same kernels, planned backward buffers
-            As = -torch.exp(self.A_logs.float())
-            g = ops.ss2d_core(xz, self.conv2d.weight, self.conv2d.bias, self.x_proj_weight, self.dt_projs_weight.float().reshape(K * D, R), As,
-                              self.Ds.float(), self.dt_projs_bias.float().reshape(-1), self.out_norm.weight, self.out_norm.bias,
-                              self.out_norm.eps, R, N)
-            return self.out_proj(g.view(B, H, W, D))
-        if _EINSUM_DT:
-            xi = F.silu(xc).float()
-            u2 = torch.stack([xi.flatten(2), xi.transpose(2, 3).flatten(2)], 1)  # [B,2,D,L]
-            wx = self.x_proj_weight.float()  # [4, R+2N, D]
-            xd_a = torch.matmul(torch.cat([wx[0], wx[2]], 0), u2[:, 0])  # [B, 2C, L]: directions 0 and 2 (same base order)
-            xd_b = torch.matmul(torch.cat([wx[1], wx[3]], 0), u2[:, 1])  # directions 1 and 3
-            C = R + 2 * N
-            x_dbl = torch.stack([xd_a[:, :C], xd_b[:, :C], xd_a[:, C:], xd_b[:, C:]], 1)  # [B,4,C,L]
-            dtr, Bs, Cs = (t.contiguous() for t in torch.split(x_dbl, [R, N, N], 2))
-        else:
-            if fused_front:  # depthwise conv + SiLU + both flattenings in one kernel, read from the channels-last in_proj output
-                u2 = ops.dwconv_silu_cross(xz, self.conv2d.weight, self.conv2d.bias, D)
-            else:
-                u2 = ops.cross_scan_input(xc)                               # SiLU + both flattenings, [B,2,D,L] fp32
-            dtr, Bs, Cs = ops.x_proj_cross(self.x_proj_weight, u2, R, N)    # [B,4,R|N|N,L]
-        # the dt projection (einsum "bkrl,kdr->bkdl", vmamba.py:972) happens INSIDE the scan kernels: the [B, 4*d_inner, L]
+        # The dt projection (einsum "bkrl,kdr->bkdl", vmamba.py:972) happens INSIDE the scan kernels: the [B, 4*d_inner, L]
         # delta tensor is never written, and its skinny K = R <= 32 GEMMs (forward + two backward: ~38 ms per step through
         # rocBLAS at these shapes) disappear
-        As = -torch.exp(self.A_logs.float())
-        if _EINSUM_DT:  # A/B switch (env TAMTR_SS2D_EINSUM=1): reference-shaped einsum + materialised delta
-            dts = torch.einsum('bkrl,kdr->bkdl', dtr, self.dt_projs_weight.float())
-            ys = ops.selective_scan_cross_delta(u2, dts.reshape(B, -1, L), As, Bs, Cs, self.Ds.float(),
-                                                self.dt_projs_bias.float().reshape(-1)).view(B, K, D, L)
-            # cross-merge (csms6s.py:26-34) on un-reversed outputs: no flips left
-            y = ys[:, 0] + ys[:, 2] + (ys[:, 1] + ys[:, 3]).view(B, D, W, H).transpose(2, 3).reshape(B, D, L)
-        else:  # scan + cross-merge as one autograd node (the merged gradient feeds the scan backward directly)
-            fused_back = D in (64, 128, 256, 512, 1024)
-            y = ops.selective_scan_cross_merged(u2, dtr, self.dt_projs_weight.float().reshape(K * D, R), As, Bs, Cs, self.Ds.float(),
-                                                self.dt_projs_bias.float().reshape(-1), H, W, token_major=fused_back)
-            if fused_back:  # y is [B, L, D]: out_norm + SiLU(z) gate in one kernel, z read from xz where it lies
-                g = ops.ln_gate(y, xz, self.out_norm.weight, self.out_norm.bias, self.out_norm.eps)
-                return self.out_proj(g.view(B, H, W, D))
+        if fused_front and fused_back and x.is_cuda and os.environ.get('TAMTR_SS2D_SPLIT') != '1':
+            # the whole core as one autograd node (ops._SS2DCore): the chain's kernels, planned backward buffers
+            Wdt, As, Ds, dt_bias = self._scan_params()
+            g = ops.ss2d_core(xz, self.conv2d.weight, self.conv2d.bias, self.x_proj_weight, Wdt, As, Ds, dt_bias, self.out_norm.weight,
+                              self.out_norm.bias, self.out_norm.eps, R, N)
+            return self.out_proj(g.view(B, H, W, D))
+        # the chain: one autograd node per stage
+        xi, z = xz.chunk(2, -1)
+        if fused_front:  # depthwise conv + SiLU + both flattenings in one kernel, read from the channels-last in_proj output
+            u2 = ops.dwconv_silu_cross(xz, self.conv2d.weight, self.conv2d.bias, D)
+        else:
+            u2 = ops.cross_scan_input(self.conv2d(xi.permute(0, 3, 1, 2).contiguous()))  # SiLU + both flattenings, [B,2,D,L] fp32
+        dtr, Bs, Cs = ops.x_proj_cross(self.x_proj_weight, u2, R, N)    # [B,4,R|N|N,L]
+        # scan + cross-merge as one autograd node (the merged gradient feeds the scan backward directly)
+        Wdt, As, Ds, dt_bias = self._scan_params()
+        y = ops.selective_scan_cross_merged(u2, dtr, Wdt, As, Bs, Cs, Ds, dt_bias, H, W, token_major=fused_back)
+        if fused_back:  # y is [B, L, D]: out_norm + SiLU(z) gate in one kernel, z read from xz where it lies
+            g = ops.ln_gate(y, xz, self.out_norm.weight, self.out_norm.bias, self.out_norm.eps)
+            return self.out_proj(g.view(B, H, W, D))
         y = self.out_norm(y.transpose(1, 2)).view(B, H, W, -1)
         return self.out_proj((y * F.silu(z)).to(x.dtype))
 
