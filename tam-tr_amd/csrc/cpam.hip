@@ -43,6 +43,9 @@ __device__ __forceinline__ void st2<bf16_t>(bf16_t* p, float a, float b) {
 }
 
 __device__ __forceinline__ float sigm(float v) { return 1.f / (1.f + __expf(-v)); }
+// the chunk maximum's update rule: the first maximum wins, and a NaN wins over everything (torch.max: one NaN channel makes the chunk's
+// gate, and with it the chunk's output at that pixel, NaN); the first NaN stays
+__device__ __forceinline__ bool nan_max_gt(float v, float m) { return v > m || (v != v && m == m); }
 
 // geometry of one 2x2 pixel block: pooled rows / columns it taps and the bilinear weights of its first row / column
 struct Taps {
@@ -109,7 +112,7 @@ __global__ __launch_bounds__(CPAM_THREADS) void cpam_fwd_kernel(const T* __restr
         gated(c, keep[c]);
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-          if (keep[c][i] > m[i]) { m[i] = keep[c][i]; am[i] = c; }
+          if (nan_max_gt(keep[c][i], m[i])) { m[i] = keep[c][i]; am[i] = c; }
       }
     }
   } else {
@@ -118,7 +121,7 @@ __global__ __launch_bounds__(CPAM_THREADS) void cpam_fwd_kernel(const T* __restr
       gated(c, cv);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        if (cv[i] > m[i]) { m[i] = cv[i]; am[i] = c; }
+        if (nan_max_gt(cv[i], m[i])) { m[i] = cv[i]; am[i] = c; }
     }
   }
   float s2[4];
@@ -315,12 +318,12 @@ __global__ __launch_bounds__(CPAM_THREADS) void cpam_cl_fwd_kernel(const T* __re
 #pragma unroll
     for (int j = 0; j < V; ++j) {
       u[i][j] = sigm(u[i][j]) * xv[i][j];                      // the channel-gated value c
-      if (u[i][j] > m[i]) { m[i] = u[i][j]; am[i] = (lb % LPC) * V + j; }
+      if (nan_max_gt(u[i][j], m[i])) { m[i] = u[i][j]; am[i] = (lb % LPC) * V + j; }
     }
     for (int o = 1; o < LPC; o <<= 1) {                        // chunk max over its LPC lanes; ties: the lower channel (the NCHW kernel's first maximum)
       const float om = __shfl_xor(m[i], o, WAVE);
       const int oa = __shfl_xor(am[i], o, WAVE);
-      if (om > m[i] || (om == m[i] && oa < am[i])) { m[i] = om; am[i] = oa; }
+      if (nan_max_gt(om, m[i]) || ((om == m[i] || (om != om && m[i] != m[i])) && oa < am[i])) { m[i] = om; am[i] = oa; }
     }
   }
   if (blk >= nblk) return;

@@ -41,7 +41,7 @@ class MaxSigmoidAttnBlock(nn.Module):
         gk = self.gl(guide)  # [B,T,ec]
         pc = self.proj_conv
         if (self.ec is None and not torch.is_grad_enabled() and not isinstance(self.scale, torch.Tensor) and 'bn' in pc._modules
-                and pc.bn.training and pc.bn.affine and isinstance(pc.act, nn.Identity) and ops.gate_cl_ok(x, x.shape[1], self.nh)):
+                and pc.bn.training and pc.bn.affine and isinstance(pc.act, nn.Identity) and ops.gate_cl_ok(x, x.shape[1], self.nh, gk.shape[1])):
             # NHWC trunk, nothing to differentiate (TIAGELAN's discarded evaluation): the BatchNorm of proj_conv is applied
             # inside the gate kernel's load of the raw convolution output - no apply pass, no NCHW repacking (next-3)
             if ops.conv3x3_cl_ok(x, pc.conv) and ops.bn_cl_ok(pc.conv.out_channels, x.dtype):

@@ -276,11 +276,14 @@ class _MaxSigmoidGate(torch.autograd.Function):
         return dx, dgk.to(gk_dt), dbias.to(b_dt), dv, None, None
 
 
-def gate_cl_ok(x, C, nh):
+def gate_cl_ok(x, C, nh, T=None):
     """Shapes / layouts tamtr_maxsigmoid_gate_cl_fwd takes: x a channels-last CUDA map (or a channel slice of one), C = nh * hc with
-    C / 8 and hc / 8 powers of two, C <= 512."""
+    C / 8 and hc / 8 powers of two, C <= 512; with T (the number of text rows) given, also that the fp32 text tile [T, C] fits the
+    kernel's 60 KiB of LDS (T <= 60 at C = 256, 30 at C = 512)."""
     hc = C // nh if nh else 0
     lpr, lph = C // 8, hc // 8
+    if T is not None and T * C * 4 > 60 * 1024:
+        return False
     return (x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) and _cl_pitch(x) and nh * hc == C and C % 8 == 0 and hc % 8 == 0
             and 0 < lpr <= 64 and lpr & (lpr - 1) == 0 and lph & (lph - 1) == 0 and _cl_pitch(x) % (16 // x.element_size()) == 0
             and x.data_ptr() % 16 == 0)

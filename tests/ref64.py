@@ -1,4 +1,5 @@
-"""fp64 references with an error model for the bf16 hot-path kernels (tests/test_gpu_bf16_kernels.py, tests/test_ref64_host.py).
+"""fp64 references with an error model for the bf16 hot-path kernels (tests/test_gpu_bf16_kernels.py, tests/test_ref64_host.py) and for the
+text gate and CPAM kernels in fp32 and bf16 (tests/test_gpu_gates_ref64.py).
 
 Every reference takes the operands exactly as the kernel sees them (bf16 tensors, fp32 side inputs), promotes them to float64 and
 computes on the CPU.  Next to each value it returns a magnitude: the same computation on absolute values.  check() then asserts,
@@ -241,3 +242,242 @@ def ln_gate(x, xz, gamma, beta, gout, eps=1e-5):
         m_dg = (gd.abs() * silu * X).sum(0)
         m_db = (gd.abs() * silu).sum(0)
     return {'out': (out.detach(), m_out), 'dx': (xr.grad, m_dx), 'dz': (zr.grad, m_dz), 'dgamma': (gr.grad, m_dg), 'dbeta': (br.grad, m_db)}
+
+
+# ------------------------------------------------------------------------------------------------ __expf inside the sigmoids
+# Worst |__expf(x) - exp(x)| / exp(x) on gfx950 in units of 2^-24, for |x| below each key: measured by tools/micro/expf_error.hip over
+# 2^24 evenly spaced arguments per range and sign (profiles/r08_gates_ref64.txt keeps the run's output).  The ROCm headers state no bound for
+# __expf (it is the native v_exp_f32 of x log2(e) rounded to fp32, so the error grows with |x|).  expf_b() doubles the measured figure:
+# the measurement samples the range and does not prove a maximum.
+# Measured on an MI355X; the larger of the two signs per range.  (The counted part agrees: the fp32 rounding of x log2(e) moves exp by
+# up to |x| 2^-24, and v_exp_f32 adds about one ulp.)
+EXPF_ULPS = {1: 2.180, 2: 3.032, 4: 4.868, 8: 8.477, 16: 15.911, 32: 30.376, 64: 59.708}
+EXPF_MARGIN = 2.0
+
+
+def expf_b(zmax):
+    """b for one __expf whose argument stays within |x| <= zmax: EXPF_MARGIN times the measured worst relative error of that range."""
+    for hi in sorted(EXPF_ULPS):
+        if zmax < hi:
+            return EXPF_MARGIN * EXPF_ULPS[hi] * U24
+    raise ValueError(f'__expf was not measured for |x| up to {zmax}')
+
+
+def sig_mag(s, m_arg):
+    """Magnitude of s = sigmoid(z), given the magnitude m_arg of z: s (1 + (1 - s) m_arg).  The sigmoid's own roundings are relative to
+    s; an error e in z moves s by s (1 - s) e."""
+    return s * (1 + (1 - s) * m_arg)
+
+
+def ambiguous(gap, mag, b):
+    """Number of argmax decisions that fp32 could legitimately take the other way: the fp64 gap between the two largest values is below
+    twice their forward bound b * mag.  The gradients routed by such an argmax are discontinuous there; test inputs must have none."""
+    return int((gap < 2 * b * mag).sum())
+
+
+# ------------------------------------------------------------------------------------------------ max-sigmoid text gate
+def maxsigmoid_gate(x, gk, bias, v, nh, scale, gout, v_affine=None):
+    """csrc/gate.hip: out = v sigmoid(max_t <x, gk_t> / sqrt(hc) + bias) scale per (image, head, pixel), and dv, dx, dlogit (the
+    derivative by the winning dot product), dgk, dbias for the cotangent gout (None: forward only).
+
+    x, v, gout [B,C,H,W] as the kernel reads them (bf16 or fp32, any layout), gk fp32 [B,T,C], bias fp32 [nh].  With v_affine =
+    (mean_rstd [C,2], gamma [C], beta [C]) it is the forward of gate_cl_fwd_kernel: v is the raw convolution output and the kernel applies
+    v (rstd gamma) + (beta - mean rstd gamma) in its load.  The first maximum over the text rows wins (torch.argmax: first occurrence).
+    Rounding points: none on purpose.  The dot products, the gate a and dlogit are fp32; the backward reads the stored fp32 a and forms
+    1 - a from it.  out, dv, dx are stored in x's dtype (a = 1 for bf16, 0 for fp32); dlogit, dgk, dbias are fp32 (a = 0), dgk and dbias
+    being fp32 reductions over the pixels (b grows by fp32_b of their length).
+    Magnitudes: the same computation on absolute values, with the logit's |dot| / sqrt(hc) + |bias|, the gate's sig_mag(a, that), and
+    1 + (magnitude of a) for 1 - a: the kernel subtracts a rounded a from 1, so a saturated gate keeps no relative accuracy there.
+    Returns {name: (value, magnitude)} for out [B,C,H,W], dv, dx, dlogit [B,nh,HW], dgk [B,T,C], dbias [nh], and 'arg' (the fp64 argmax,
+    [B,nh,HW]), 'gap' (largest minus second largest dot product, inf at T = 1), 'gap_mag' (the larger magnitude of those two dot
+    products), 'zmax' (the largest |logit|: the range of the sigmoid's __expf)."""
+    B, C, H, W = x.shape
+    T, hc, HW = gk.shape[1], C // nh, H * W
+    sc = abs(float(scale))
+    xd = _d(x).reshape(B, nh, hc, HW)
+    g = _d(gk).reshape(B, T, nh, hc)
+    bi = _d(bias).reshape(1, nh, 1)
+    vd = _d(v).reshape(B, nh, hc, HW)
+    m_v = vd.abs()
+    if v_affine is not None:
+        mr, ga, be = (_d(t) for t in v_affine)
+        mean, k, be = mr[:, 0].reshape(1, nh, hc, 1), (mr[:, 1] * ga).reshape(1, nh, hc, 1), be.reshape(1, nh, hc, 1)
+        m_v = vd.abs() * k.abs() + be.abs() + (mean * k).abs()
+        vd = vd * k + (be - mean * k)
+    dots = torch.einsum('bmcp,bnmc->bmpn', xd, g)                 # [B,nh,HW,T]
+    m_dots = torch.einsum('bmcp,bnmc->bmpn', xd.abs(), g.abs())
+    arg = dots.argmax(-1)
+    best, m_best = dots.gather(-1, arg[..., None])[..., 0], m_dots.gather(-1, arg[..., None])[..., 0]
+    if T > 1:
+        top = dots.topk(2, -1)
+        gap, gap_mag = top.values[..., 0] - top.values[..., 1], m_dots.gather(-1, top.indices).amax(-1)
+    else:
+        gap, gap_mag = torch.full_like(best, float('inf')), m_best
+    rs = math.sqrt(hc)
+    z, m_z = best / rs + bi, m_best / rs + bi.abs()
+    a = torch.sigmoid(z)
+    m_a = sig_mag(a, m_z)
+    res = {'out': ((vd * a.unsqueeze(2) * scale).reshape(B, C, H, W), (m_v * m_a.unsqueeze(2) * sc).reshape(B, C, H, W)),
+           'arg': arg, 'gap': gap, 'gap_mag': gap_mag, 'zmax': float(z.abs().max())}
+    if gout is None:
+        return res
+    go = _d(gout).reshape(B, nh, hc, HW)
+    res['dv'] = ((go * a.unsqueeze(2) * scale).reshape(B, C, H, W), (go.abs() * m_a.unsqueeze(2) * sc).reshape(B, C, H, W))
+    daw, m_daw = (go * vd).sum(2), (go.abs() * m_v).sum(2)        # [B,nh,HW]
+    dl, m_dl = daw * scale * a * (1 - a) / rs, m_daw * sc * m_a * (1 + m_a) / rs
+    res['dlogit'] = (dl, m_dl)
+    gsel = g.permute(0, 2, 1, 3).gather(2, arg[..., None].expand(B, nh, HW, hc))      # the winning text row, [B,nh,HW,hc]
+    res['dx'] = ((dl[..., None] * gsel).transpose(2, 3).reshape(B, C, H, W), (m_dl[..., None] * gsel.abs()).transpose(2, 3).reshape(B, C, H, W))
+    hot = torch.nn.functional.one_hot(arg, T).double()            # [B,nh,HW,T]
+    res['dgk'] = (torch.einsum('bmpn,bmp,bmcp->bnmc', hot, dl, xd).reshape(B, T, C),
+                  torch.einsum('bmpn,bmp,bmcp->bnmc', hot, m_dl, xd.abs()).reshape(B, T, C))
+    res['dbias'] = (dl.sum((0, 2)) * rs, m_dl.sum((0, 2)) * rs)
+    return res
+
+
+# ------------------------------------------------------------------------------------------------ CPAM
+def _up2_taps(n):
+    """upsample_bilinear2d(scale 2, align_corners=False) along one axis of n pooled cells: for each of the 2n pixels the two cells and
+    the second one's weight: src = max((o + 0.5) / 2 - 0.5, 0), i0 = floor(src), i1 = min(i0 + 1, n - 1), lam = src - i0."""
+    o = torch.arange(2 * n, dtype=torch.float64)
+    src = ((o + 0.5) / 2 - 0.5).clamp_min(0)
+    i0 = src.floor().long()
+    return i0, (i0 + 1).clamp_max(n - 1), src - i0
+
+
+def _up2(p):
+    """Bilinear x2 of p [..., Hp, Wp].  Pixel row / column 0 sits on cell 0 (lam = 0).  The kernels (make_taps in csrc/cpam.hip) form it as
+    0 * p[0] + 1 * p[0]: their zero-weight tap is the clamped cell 0 itself, where torch's is cell 1.  For finite p all three agree; a
+    non-finite p[0] gives NaN there (0 * inf), and a non-finite p[1] does not reach pixel 0.  This reference does as the kernels do."""
+    Hp, Wp = p.shape[-2:]
+    y0, y1, ly = _up2_taps(Hp)
+    x0, x1, lx = _up2_taps(Wp)
+
+    def mix(a, b, lam):
+        return torch.where(lam == 0, 0 * a + a, (1 - lam) * a + lam * b)
+    rows0, rows1 = p[..., y0, :], p[..., y1, :]
+    top, bot = mix(rows0[..., x0], rows0[..., x1], lx), mix(rows1[..., x0], rows1[..., x1], lx)
+    return mix(top, bot, ly[:, None])
+
+
+def _up2_adjoint(du):
+    """The adjoint of _up2's weights applied to du [..., H, W]: dp[k, l] = sum over the pixels that tap cell (k, l) of wy wx du."""
+    H, W = du.shape[-2:]
+    Hp, Wp = H // 2, W // 2
+    y0, y1, ly = _up2_taps(Hp)
+    x0, x1, lx = _up2_taps(Wp)
+    t = torch.zeros(du.shape[:-2] + (Hp, W), dtype=du.dtype)
+    t.index_add_(-2, y0, du * (1 - ly)[:, None])
+    t.index_add_(-2, y1, du * ly[:, None])
+    dp = torch.zeros(du.shape[:-2] + (Hp, Wp), dtype=du.dtype)
+    dp.index_add_(-1, x0, t * (1 - lx))
+    dp.index_add_(-1, x1, t * lx)
+    return dp
+
+
+def _first_max(t, dim):
+    """max and argmax along dim: the first maximum wins, a NaN wins over everything and the first NaN stays (torch.max's values; the
+    index rule is written out because the kernels depend on it)."""
+    nan = torch.isnan(t)
+    idx = torch.where(nan.any(dim), nan.double().argmax(dim), torch.where(nan, torch.full_like(t, float('-inf')), t).argmax(dim))
+    return t.gather(dim, idx.unsqueeze(dim)).squeeze(dim), idx
+
+
+def cpam(x, gout):
+    """csrc/cpam.hip (both layouts) with its max-pool (csrc/pool.hip, pool3s2_cl_*): p = maxpool 3x3 / stride 2 / padding 1 of x,
+    c = sigmoid(bilinear_x2(p)) x, out = sigmoid(max over the chunk's channels of c) c for each of the 8 channel chunks, and dx for the
+    cotangent gout (None: forward only).
+
+    x, gout [B,C,H,W] as the kernel reads them (bf16 or fp32, any layout), H and W even.  The pool is written out: padding is -inf, the
+    first maximum in row-major window order wins (bf16 maps have many exact ties inside a window, and the backward routes dp to the
+    winner); NaN wins.  The chunk maximum: the first maximum wins, NaN wins.  The bilinear x2 is written out with align_corners=False
+    clamping (_up2).
+    Rounding points for bf16 (cpam_bwd_kernel / cpam_dp_kernel / tamtr_maxpool_bwd and their _cl_ forms): p is exact (a maximum of bf16
+    values is one of them); out is rounded once (a = 1); s2 is kept in fp32 (a = 0).  The backward stores dxd (the direct part of dx), du
+    and dp each in the map's dtype, and dx is the rounded sum of dxd and the up to four dp values routed to the pixel (a = 1).  So for
+    bf16 b of dx is 2^-8 on the stored intermediates plus the fp32 chain, and the magnitude of dx counts the pooled path twice (du and dp
+    are two roundings of it): mag = |dxd| + 2 sum |dp|.  For fp32 b is the fp32 chain alone.
+    This bound of dx is the worst case of its honest roundings (dxd, du, dp, the sum), which one more rounding on the pooled path seldom
+    exceeds: a du rounded twice passes it.  That mistake is caught on the stored du, which is held to a single rounding.
+    Magnitudes: the same computation on absolute values, with sig_mag for both sigmoids and 1 + (magnitude of s) for 1 - s.
+    The stored intermediates are returned too (the C entry points hand them out): dxd and du are rounded once (a = 1), dp is a rounded
+    sum of rounded du (a = 1, b with 2^-8 on its magnitude).
+    Returns {name: (value, magnitude)} for out, dx, dxd, du [B,C,H,W], dp [B,C,H/2,W/2], s2 [B,8,H,W], and 'p' (exact), 'arg' (the fp64 argmax channel inside its
+    chunk, [B,8,H,W]), 'gap' (largest minus second largest c of the chunk, inf for one channel per chunk), 'gap_mag' (the larger magnitude
+    of those two), 'zmax' (the largest argument of either sigmoid)."""
+    import torch.nn.functional as F
+    xd = _d(x)
+    B, C, H, W = xd.shape
+    Hp, Wp, Cg = H // 2, W // 2, C // 8
+    win = F.pad(xd, (1, 1, 1, 1), value=float('-inf')).unfold(2, 3, 2).unfold(3, 3, 2).reshape(B, C, Hp, Wp, 9)
+    p, widx = _first_max(win, -1)                                  # widx = dh * 3 + dw inside the unclipped window
+    u, m_u = _up2(p), _up2(p.abs())
+    s1 = torch.sigmoid(u)
+    m_s1 = sig_mag(s1, torch.where(torch.isfinite(m_u), m_u, torch.zeros_like(m_u)))
+    c, m_c = s1 * xd, m_s1 * xd.abs()
+    cg, m_cg = c.view(B, 8, Cg, H, W), m_c.view(B, 8, Cg, H, W)
+    m, am = _first_max(cg, 2)                                      # [B,8,H,W]
+    m_m = m_cg.gather(2, am.unsqueeze(2)).squeeze(2)
+    if Cg > 1:
+        top = torch.where(torch.isnan(cg), torch.full_like(cg, float('-inf')), cg).topk(2, 2)
+        gap, gap_mag = top.values[:, :, 0] - top.values[:, :, 1], m_cg.gather(2, top.indices).amax(2)
+    else:
+        gap, gap_mag = torch.full_like(m, float('inf')), m_m
+    s2 = torch.sigmoid(m)
+    m_s2 = sig_mag(s2, torch.where(torch.isfinite(m_m), m_m, torch.zeros_like(m_m)))
+    out, m_out = (s2.unsqueeze(2) * cg).reshape(B, C, H, W), (m_s2.unsqueeze(2) * m_cg).reshape(B, C, H, W)
+    fin = torch.cat([u[torch.isfinite(u)].abs().flatten(), m[torch.isfinite(m)].abs().flatten()])
+    res = {'out': (out, m_out), 's2': (s2, m_s2), 'p': p, 'arg': am, 'gap': gap, 'gap_mag': gap_mag, 'zmax': float(fin.max()) if fin.numel() else 0.0}
+    if gout is None:
+        return res
+    go = _d(gout).view(B, 8, Cg, H, W)
+    S, m_S = (go * cg).sum(2), (go.abs() * m_cg).sum(2)
+    dm, m_dm = s2 * (1 - s2) * S, m_s2 * (1 + m_s2) * m_S
+    hot = F.one_hot(am, Cg).permute(0, 1, 4, 2, 3).double()        # [B,8,Cg,H,W]
+    dc = (go * s2.unsqueeze(2) + hot * dm.unsqueeze(2)).reshape(B, C, H, W)
+    m_dc = (go.abs() * m_s2.unsqueeze(2) + hot * m_dm.unsqueeze(2)).reshape(B, C, H, W)
+    dxd, m_dxd = dc * s1, m_dc * m_s1
+    du, m_du = dc * xd * s1 * (1 - s1), m_dc * xd.abs() * m_s1 * (1 + m_s1)
+    dp, m_dp = _up2_adjoint(du), _up2_adjoint(m_du)                # [B,C,Hp,Wp]
+    # the pool's backward: cell (k, l) sends dp to pixel (2k - 1 + dh, 2l - 1 + dw) of its winner
+    k, l = torch.arange(Hp).view(1, 1, Hp, 1), torch.arange(Wp).view(1, 1, 1, Wp)
+    pix = ((2 * k - 1 + widx // 3) * W + (2 * l - 1 + widx % 3)).reshape(B, C, Hp * Wp)
+    pooled, m_pooled = torch.zeros(B, C, H * W, dtype=torch.float64), torch.zeros(B, C, H * W, dtype=torch.float64)
+    pooled.scatter_add_(2, pix, dp.reshape(B, C, Hp * Wp))
+    m_pooled.scatter_add_(2, pix, m_dp.reshape(B, C, Hp * Wp))
+    res.update({'dxd': (dxd, m_dxd), 'du': (du, m_du), 'dp': (dp, m_dp)})
+    res['dx'] = (dxd + pooled.view(B, C, H, W), m_dxd + 2 * m_pooled.view(B, C, H, W))
+    return res
+
+
+# ------------------------------------------------------------------------------------------------ a and b of the gate and CPAM checks
+def gate_bounds(hc, HW, B, zmax, bf16):
+    """{name: (a, b)} for maxsigmoid_gate's outputs; every figure is a count of fp32 roundings along the kernel's chain.
+    The gate a: hc FMAs, / sqrt(hc), + bias (hc + 2), negate-free __expf (expf_b), 1 + e and 1 / (.) (2): hc + 4 and one __expf.
+    out: the gate, a * scale and * v (2); the channels-last kernel adds rsqrtf and the three roundings of the folded affine (4) and sums
+    its dot product in fewer steps: hc + 12 covers both.  dv: the same chain.  dlogit: hc FMAs of gout v, the gate twice (a and 1 - a),
+    the subtraction, three products and the division (6): 3 hc + 18 and two __expf.  dx: one more product.  dgk: dlogit times x summed
+    over the HW pixels; dbias: dlogit summed over B HW pixels, times sqrt(hc)."""
+    e = expf_b(zmax)
+    a = 1 if bf16 else 0
+    b_out, b_dl = fp32_b(hc + 12) + e, fp32_b(3 * hc + 18) + 2 * e
+    return {'out': (a, b_out), 'dv': (a, b_out), 'dlogit': (0, b_dl), 'dx': (a, b_dl + fp32_b(1)),
+            'dgk': (0, b_dl + fp32_b(HW + 1)), 'dbias': (0, b_dl + fp32_b(B * HW + 1))}
+
+
+CPAM_C_N = 10   # roundings of c = sigmoid(u) x besides its __expf: the bilinear taps (2 products + 1 sum, twice: 6), 1 + e, 1 / (.), * x; +1 spare
+
+
+def cpam_bounds(Cg, zmax, bf16):
+    """{name: (a, b)} for cpam's outputs, and 'c': (0, b) of the gated value that the chunk argmax compares.
+    c: CPAM_C_N and one __expf.  s2 = sigmoid(max c): c's chain, 1 + e, 1 / (.), one spare (3) and a second __expf.  out = s2 c: both
+    chains and the product: 24 and three __expf; rounded once to the map's dtype.  dx: S = sum of gout c over the chunk (Cg + c's
+    chain), dm = s2 (1 - s2) S (s2's chain twice + 3), dc (2), dxd = dc s1 (c's chain), du = dc x s1 (1 - s1) (c's chain twice + 4),
+    dp (four weighted taps per row, four rows: 12), the pool's sum of up to four dp (4): Cg + 80 covers it, with eight __expf; in
+    bf16 the stored dxd, du and dp add 2^-8 of the magnitude (ref64.cpam counts the pooled path twice for du and dp).  The stored dxd, du
+    and dp are held to the same chain (dp with 2^-8 for the rounded du it sums)."""
+    e = expf_b(zmax)
+    a = 1 if bf16 else 0
+    chain = fp32_b(Cg + 80) + 8 * e
+    return {'c': (0, fp32_b(CPAM_C_N) + e), 's2': (0, fp32_b(CPAM_C_N + 3) + 2 * e), 'out': (a, fp32_b(24) + 3 * e),
+            'dxd': (a, chain), 'du': (a, chain), 'dp': (a, (U8 if bf16 else 0) + chain), 'dx': (a, (U8 if bf16 else 0) + chain)}

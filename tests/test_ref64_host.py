@@ -241,3 +241,235 @@ def test_ln_gate_emulation_passes_and_mutants_fail():
     dg_m = emu_ln_gate(x, xz, gamma, beta, gout, drop_last_token=True)[3]
     assert R.old_close(dg_m, ref['dgamma'][0], 1e-1, 1e-1 * N ** 0.5)
     rejected('dropped token', dg_m, *ref['dgamma'], *bounds['dgamma'])
+
+
+# ------------------------------------------------------------------------------------------------ max-sigmoid text gate
+import gate_cases as G
+
+BF16 = torch.bfloat16
+
+
+def emu_gate(x, gk, bias, v, nh, scale, gout, drop_row=None, no_rs_head=None, round_before_scale=False, aw_bf16=False):
+    """gate_fwd / gate_bwd_kernel: the T dot products as hc serial fp32 multiply-adds per pixel, the first maximum, 1 / (1 + exp(-z)),
+    v * (a * scale); the backward from the stored fp32 a; out, dv, dx rounded to the maps' dtype; dgk, dbias by fp32 torch reductions."""
+    st = bf if x.dtype == BF16 else (lambda t: t)
+    B, C, H, W = x.shape
+    T, hc, HW = gk.shape[1], C // nh, H * W
+    xf, vf, go = (t.float().reshape(B, nh, hc, HW) for t in (x, v, gout))
+    g = gk.view(B, T, nh, hc).permute(0, 2, 1, 3)                  # [B,nh,T,hc]
+    acc = torch.zeros(B, nh, T, HW)
+    for c in range(hc):
+        acc = acc + g[..., c, None] * xf[:, :, c, None, :]
+    if drop_row is not None:
+        acc[:, :, drop_row] = float('-inf')
+    arg = acc.argmax(2)
+    best = acc.gather(2, arg.unsqueeze(2)).squeeze(2)
+    rs = torch.tensor(float(hc)).sqrt()
+    a = 1 / (1 + torch.exp(-(best / rs + bias.view(1, nh, 1))))
+    if aw_bf16:
+        a = bf(a)
+    s = torch.tensor(scale, dtype=torch.float32)
+    out = st(st(vf * a.unsqueeze(2)) * s) if round_before_scale else st(vf * (a * s).unsqueeze(2))
+    daw = torch.zeros(B, nh, HW)
+    for c in range(hc):
+        daw = daw + go[:, :, c] * vf[:, :, c]
+    dv = st(go * (a * s).unsqueeze(2))
+    dl = daw * s * a * (1 - a) / rs
+    if no_rs_head is not None:
+        dl[:, no_rs_head] = dl[:, no_rs_head] * rs
+    gsel = g.gather(2, arg[..., None].expand(B, nh, HW, hc))       # [B,nh,HW,hc]
+    dx = st(dl[..., None] * gsel).transpose(2, 3)
+    sel = torch.zeros(B, nh, T, HW).scatter_(2, arg.unsqueeze(2), dl.unsqueeze(2))
+    dgk = torch.matmul(sel, xf.transpose(2, 3)).permute(0, 2, 1, 3).reshape(B, T, C)
+    dbias = dl.sum((0, 2)) * math.sqrt(hc)
+    shp = (B, C, H, W)
+    return {'out': out.reshape(shp), 'dv': dv.reshape(shp), 'dx': dx.reshape(shp), 'dlogit': dl, 'dgk': dgk, 'dbias': dbias}
+
+
+def _old_gate_ok(name, got, ref):
+    """The rules these checks replace: out, dv 1e-2 / 1e-2 (test_gate_kernel_bf16, test_gate_bf16_full_size_vs_oracle); the gradients
+    2e-2 relative plus 2e-2 of the largest gradient."""
+    if name in ('out', 'dv'):
+        return R.old_close(got, ref, 1e-2, 1e-2)
+    return R.old_close(got, ref, 2e-2, 2e-2 * float(ref.abs().max()))
+
+
+@pytest.mark.parametrize('dt', [torch.float32, BF16])
+def test_gate_emulation_passes(dt):
+    for case, scale in (('t17', 0.37), ('vec_one_pass', 1.0), ('px1_t37_hc64', 1.0)):
+        B, C, nh, H, W, T = G.GATE_NCHW[case]
+        x, gk, bias, v, gout = G.gate_inputs(G.GATE_NCHW[case], dt)
+        ref = R.maxsigmoid_gate(x, gk, bias, v, nh, scale, gout)
+        ab = R.gate_bounds(C // nh, H * W, B, ref['zmax'], dt == BF16)
+        for n, t in emu_gate(x, gk, bias, v, nh, scale, gout).items():
+            R.check(f'emu gate {case} {n}', t, *ref[n], *ab[n])
+
+
+def test_gate_mutants_fail():
+    shape = G.GATE_NCHW['t17']
+    B, C, nh, H, W, T = shape
+    x, gk, bias, v, gout = G.gate_inputs(shape, BF16)
+    scale = 0.37
+    ref = R.maxsigmoid_gate(x, gk, bias, v, nh, scale, gout)
+    ab = R.gate_bounds(C // nh, H * W, B, ref['zmax'], True)
+    assert int((ref['arg'] == 15).sum()) > 0
+    # the last row of the first TC = 16 chunk dropped from the max: the pixels it wins take the runner-up.  (The old rule sees this one
+    # too at this size: a plain rejection.)
+    m = emu_gate(x, gk, bias, v, nh, scale, gout, drop_row=15)
+    rejected('dropped text row', m['out'], *ref['out'], *ab['out'])
+    rejected('dropped text row', m['dgk'], *ref['dgk'], *ab['dgk'])
+    # dlogit without the 1 / sqrt(hc) on head 1 (the old rule sees it in dx and dgk: a plain rejection)
+    m = emu_gate(x, gk, bias, v, nh, scale, gout, no_rs_head=1)
+    rejected('no 1/sqrt(hc)', m['dlogit'], *ref['dlogit'], *ab['dlogit'])
+    rejected('no 1/sqrt(hc)', m['dx'], *ref['dx'], *ab['dx'])
+    # out rounded to bf16 before the multiply by scale: two roundings
+    m = emu_gate(x, gk, bias, v, nh, scale, gout, round_before_scale=True)
+    assert _old_gate_ok('out', m['out'], ref['out'][0])
+    rejected('rounded before scale', m['out'], *ref['out'], *ab['out'])
+    # the saved gate kept in bf16: 2^-9 relative on out, dv and, through a (1 - a), on every gradient
+    m = emu_gate(x, gk, bias, v, nh, scale, gout, aw_bf16=True)
+    for n in ('out', 'dv', 'dx', 'dgk'):
+        assert _old_gate_ok(n, m[n], ref[n][0]), n
+        rejected('gate in bf16 ' + n, m[n], *ref[n], *ab[n])
+    # the text tile staged in bf16: every dot product off by up to 2^-9 of its magnitude
+    m = emu_gate(x, bf(gk), bias, v, nh, scale, gout)
+    for n in ('dv', 'dx', 'dgk'):
+        assert _old_gate_ok(n, m[n], ref[n][0]), n
+        rejected('text tile in bf16 ' + n, m[n], *ref[n], *ab[n])
+
+
+# ------------------------------------------------------------------------------------------------ CPAM
+def emu_cpam(x, gout, border_075=False, du_twice=False, argmax_x_chunk=None, s2_bf16=False):
+    """cpam_fwd / bwd / dp kernels and the pool: fp32 arithmetic on the map's values; out, dxd, du, dp and dx stored in the map's dtype."""
+    import torch.nn.functional as F
+    st = bf if x.dtype == BF16 else (lambda t: t)
+    B, C, H, W = x.shape
+    Hp, Wp, Cg = H // 2, W // 2, C // 8
+    xf, go = x.float(), gout.float().view(B, 8, Cg, H, W)
+    p, idx = F.max_pool2d(xf, 3, 2, 1, return_indices=True)
+
+    def up(t):
+        return F.interpolate(t, scale_factor=2, mode='bilinear', align_corners=False)
+    s1 = 1 / (1 + torch.exp(-up(p)))
+    c = (s1 * xf).view(B, 8, Cg, H, W)
+    am = c.argmax(2)
+    if argmax_x_chunk is not None:
+        am[:, argmax_x_chunk] = xf.view(B, 8, Cg, H, W)[:, argmax_x_chunk].argmax(1)
+    m = c.gather(2, am.unsqueeze(2)).squeeze(2)
+    s2 = 1 / (1 + torch.exp(-m))
+    if s2_bf16:
+        s2 = bf(s2)
+    out = st(s2.unsqueeze(2) * c).view(B, C, H, W)
+    S = torch.zeros(B, 8, H, W)
+    for ch in range(Cg):
+        S = S + go[:, :, ch] * c[:, :, ch]
+    dm = s2 * (1 - s2) * S
+    hot = F.one_hot(am, Cg).permute(0, 1, 4, 2, 3).float()
+    dc = (go * s2.unsqueeze(2) + hot * dm.unsqueeze(2)).view(B, C, H, W)
+    dxd = st(dc * s1)
+    du = st(st(dc * xf * s1) * (1 - s1)) if du_twice else st(dc * xf * s1 * (1 - s1))
+
+    def adjoint(d):
+        q = torch.zeros(B, C, Hp, Wp, requires_grad=True)
+        return torch.autograd.grad(up(q), q, d)[0]
+    dp = adjoint(du)
+    if border_075:                                                  # the last pixel column into the last pooled column: 0.75, not 1
+        last = torch.zeros_like(du)
+        last[..., W - 1] = du[..., W - 1]
+        dp = dp - 0.25 * adjoint(last)
+    dp = st(dp)
+    pooled = torch.zeros(B, C, H * W).scatter_add_(2, idx.view(B, C, -1), dp.view(B, C, -1)).view(B, C, H, W)
+    return {'out': out, 's2': s2, 'dxd': dxd, 'du': du, 'dp': dp, 'dx': st(dxd + pooled)}
+
+
+def _old_cpam_ok(name, got, ref):
+    """test_cpam_bf16_and_argument_checks / test_cpam_channels_last_kernels: out 1e-2 / 1e-2, dx 3e-2 / 3e-2."""
+    tol = 1e-2 if name == 'out' else 3e-2
+    return R.old_close(got, ref, tol, tol)
+
+
+@pytest.mark.parametrize('dt', [torch.float32, BF16])
+def test_cpam_emulation_passes(dt):
+    for shape in ((2, 64, 12, 16), (1, 128, 2, 2), (1, 256, 6, 6), (2, 64, 4, 6)):
+        x, gout = G.cpam_inputs(shape, dt, G.CPAM_SEED.get((shape, dt), 5))
+        ref = R.cpam(x, gout)
+        ab = R.cpam_bounds(shape[1] // 8, ref['zmax'], dt == BF16)
+        for n, t in emu_cpam(x, gout).items():
+            R.check(f'emu cpam {shape} {n}', t, *ref[n], *ab[n])
+
+
+def test_cpam_mutants_fail():
+    shape = (2, 64, 12, 16)
+    x, gout = G.cpam_inputs(shape, BF16, G.CPAM_SEED.get((shape, BF16), 5))
+    ref = R.cpam(x, gout)
+    ab = R.cpam_bounds(shape[1] // 8, ref['zmax'], True)
+    # the dp gather's last column weighted 0.75 where the clamped tap makes it 1
+    # (at 12 x 16 the old rule sees this one too: a plain rejection)
+    m = emu_cpam(x, gout, border_075=True)
+    rejected('border weight 0.75', m['dx'], *ref['dx'], *ab['dx'])
+    # du rounded twice (once before its last factor)
+    # The bound of dx allows the worst case of its three honest roundings, which a fourth seldom exceeds: the stored du itself shows it.
+    m = emu_cpam(x, gout, du_twice=True)
+    assert _old_cpam_ok('dx', m['dx'], ref['dx'][0])
+    rejected('du rounded twice', m['du'], *ref['du'], *ab['du'])
+    # chunk 3's argmax taken over x, not over sigmoid(u) x
+    m = emu_cpam(x, gout, argmax_x_chunk=3)
+    assert _old_cpam_ok('out', m['out'], ref['out'][0])
+    rejected('argmax over x', m['out'], *ref['out'], *ab['out'])
+    rejected('argmax over x', m['dx'], *ref['dx'], *ab['dx'])
+    # s2 kept in bf16
+    m = emu_cpam(x, gout, s2_bf16=True)
+    assert _old_cpam_ok('out', m['out'], ref['out'][0]) and _old_cpam_ok('dx', m['dx'], ref['dx'][0])
+    rejected('s2 in bf16', m['out'], *ref['out'], *ab['out'])
+    rejected('s2 in bf16', m['s2'], *ref['s2'], *ab['s2'])
+
+
+# ------------------------------------------------------------------------------------------------ inputs of the GPU tests
+def test_gate_and_cpam_gpu_inputs_have_no_ambiguous_argmax():
+    """The argmax-routed gradients (dx, dgk of the gate; dx of CPAM) are discontinuous where the two largest candidates are closer than
+    twice their fp32 bound.  Every seeded input of tests/test_gpu_gates_ref64.py must have none of these, judged from the fp64 reference
+    alone (the GPU tests repeat the assertion before they look at a kernel's output)."""
+    for case, shape in G.GATE_NCHW.items():
+        for dt in (torch.float32, BF16):
+            x, gk, bias, v, gout = G.gate_inputs(shape, dt, G.GATE_SEED.get((case, dt), 1))
+            ref = R.maxsigmoid_gate(x, gk, bias, v, shape[2], 1.0, None)
+            assert R.ambiguous(ref['gap'], ref['gap_mag'], R.fp32_b(shape[1] // shape[2])) == 0, (case, dt)
+    cases = [(s, BF16) for s in G.CPAM_CL_BF16] + [(s, torch.float32) for s in G.CPAM_CL_F32]
+    cases += [(s, dt) for s in G.CPAM_NCHW for dt in (torch.float32, BF16)] + [(G.CPAM_NCHW_GRID_LIMIT, torch.float32)]
+    for shape, dt in cases:
+        x, _ = G.cpam_inputs(shape, dt, G.CPAM_SEED.get((shape, dt), 5))
+        ref = R.cpam(x, None)
+        b = R.cpam_bounds(shape[1] // 8, ref['zmax'], dt == BF16)['c'][1]
+        assert R.ambiguous(ref['gap'], ref['gap_mag'], b) == 0, (shape, dt)
+
+
+# ------------------------------------------------------------------------------------------------ the channels-last gate's LDS limit
+class _ChannelsLastMap:
+    """What ops.gate_cl_ok looks at, for a bf16 channels-last CUDA map [2, C, 12, 12] (no GPU here)."""
+    is_cuda, dtype = True, BF16
+
+    def __init__(self, C):
+        self.shape = (2, C, 12, 12)
+
+    def dim(self):
+        return 4
+
+    def stride(self):
+        B, C, H, W = self.shape
+        return (H * W * C, 1, W * C, C)
+
+    def element_size(self):
+        return 2
+
+    def data_ptr(self):
+        return 0
+
+
+def test_gate_cl_ok_counts_the_text_rows():
+    """tamtr_maxsigmoid_gate_cl_fwd keeps the fp32 text tile [T, C] in 60 KiB of LDS: 80 rows fit at C = 64 and do not at C = 256."""
+    import tamtr_amd.ops as ops
+    assert ops.gate_cl_ok(_ChannelsLastMap(256), 256, 8) and ops.gate_cl_ok(_ChannelsLastMap(256), 256, 8, T=10)
+    assert ops.gate_cl_ok(_ChannelsLastMap(256), 256, 8, T=60) and not ops.gate_cl_ok(_ChannelsLastMap(256), 256, 8, T=61)
+    assert not ops.gate_cl_ok(_ChannelsLastMap(256), 256, 8, T=80)
+    assert ops.gate_cl_ok(_ChannelsLastMap(64), 64, 8, T=80)
+    assert ops.gate_cl_ok(_ChannelsLastMap(512), 512, 8, T=30) and not ops.gate_cl_ok(_ChannelsLastMap(512), 512, 8, T=31)
