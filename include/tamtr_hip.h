@@ -34,7 +34,8 @@ extern "C" {
 #define TAMTR_EUNSUP (-2)
 #define TAMTR_ELAUNCH (-3)
 
-/* ABI version, bumped on any signature change. */
+/* ABI version, bumped on any signature change.  The CLIP text tower's entries at the end of this file (tamtr_text_embed, tamtr_linear_f32,
+ * tamtr_text_pool_project) are new symbols only: no existing signature changed, so the version stayed at 36 when they were added. */
 int tamtr_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -578,6 +579,40 @@ int tamtr_detect_postprocess(const void* preds, int dtype, int B, int nq, int nd
 int tamtr_val_postprocess_match(const void* preds, int dtype, int B, int nq, int nd, float imgsz, float conf, float iou, int single_cls,
                                 float max_wh, const float* lab_cls, const float* lab_box, const int32_t* lab_off, int M, const float* scale,
                                 float* predn, uint8_t* correct, int32_t* counts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * CLIP text tower (frozen ViT-B/32 text encoder), fp32 end to end, forward only.  Replaces `clip.tokenize(...)` followed by
+ * `text_model.encode_text(...)` = clip.model.CLIP.encode_text as the reference calls it for every training batch
+ * (ultralytics/models/rtdetrworld/train.py:148-150), in set_classes (ultralytics/nn/tasks.py:552-571) and for the validator's vocabulary.
+ * The attention of a block runs on tamtr_selfattn_fwd (causal mask_bits, ld = 3 W views into the packed in-projection), its two
+ * LayerNorms on tamtr_layernorm_fwd.
+ *
+ *      tamtr_text_embed: `x = self.token_embedding(text) + self.positional_embedding` (CLIP.encode_text):
+ *          x[(i, l), :] = tok[ids[i, l], :] + pos[l, :]
+ *      ids i32 [n, L]; tok f32 [V, W]; pos f32 [>= L, W]; x f32 [n * L, W].  W % 4 == 0, tok / pos / x 16-byte aligned.  An id outside
+ *      [0, V) is never used as an index: its output row is NaN (the Python wrapper refuses such ids before the launch).
+ */
+int tamtr_text_embed(const int32_t* ids, const float* tok, const float* pos, float* x, long long n, int L, int W, int V, void* stream);
+
+/*      tamtr_linear_f32: the four dense layers of a residual block (nn.MultiheadAttention's packed in-projection and out_proj, mlp.c_fc +
+ *      QuickGELU, mlp.c_proj; CLIP's ResidualAttentionBlock.forward):
+ *          Y[M,N] = epi( X[M,K] @ W[N,K]^T + bias[N] )      fp32 in and out, fp32 accumulation on v_mfma_f32_32x32x2_f32
+ *      epi: 0 none; 1 QuickGELU y * sigmoid(1.702 y); 2 residual add of `residual` f32 [M,N], which may be Y itself (`x = x + ...`).
+ *      X f32 [M,K], W f32 [N,K] (nn.Linear layout), both row-major and 16-byte aligned; bias f32 [N] or NULL; residual NULL unless epi == 2.
+ *      Requires K % 32 == 0, N % 64 == 0 (TAMTR_EUNSUP otherwise); any M >= 1: the row tail of the last tile is masked inside the kernel,
+ *      rows >= M of Y are not touched.  LDS-staged 64 x 64 x 32 tiles, no split-K, no atomics: every element is one ordered sum, the same
+ *      bits on every run.
+ */
+int tamtr_linear_f32(const float* X, const float* W, const float* bias, const float* residual, float* Y, int M, int N, int K, int epi,
+                     void* stream);
+
+/*      tamtr_text_pool_project: `x = self.ln_final(x); x = x[arange(n), text.argmax(dim=-1)] @ self.text_projection` (CLIP.encode_text)
+ *      and, with norm != 0, `txt_feats / txt_feats.norm(p=2, dim=-1, keepdim=True)` (train.py:150), one workgroup per prompt:
+ *          r = first argmax_l ids[i, l];  out[i, :] = LayerNorm(x[(i, r), :]; gamma, beta, eps) @ proj   ( / its L2 norm, no eps )
+ *      x f32 [n * L, W]; ids i32 [n, L]; gamma, beta f32 [W]; proj f32 [W, E]; out f32 [n, E].  W <= 1024, E <= 1024.
+ */
+int tamtr_text_pool_project(const float* x, const int32_t* ids, const float* gamma, const float* beta, const float* proj, float* out, int n,
+                            int L, int W, int E, float eps, int norm, void* stream);
 
 #ifdef __cplusplus
 }

@@ -584,8 +584,9 @@ def reset_workers(loader):
 
 # ------------------------------------------------------------------------------------------------ prompts -> text features
 class TextFeatures:
-    """Prompt -> embedding table standing in for the frozen CLIP ViT-B/32 text tower (computed offline; the encoder is out of
-    scope).  `encode` returns unit-norm rows like the reference's preprocess_batch / set_classes."""
+    """Prompt -> embedding table of the frozen CLIP ViT-B/32 text tower: computed offline (`load`), or filled on demand by the package's
+    own encoder (`from_encoder`).  `encode` returns unit-norm rows like the reference's preprocess_batch / set_classes."""
+    encoder = tokenizer = None
 
     def __init__(self, table):
         self.table = {k: torch.as_tensor(v, dtype=torch.float32) for k, v in table.items()}
@@ -607,7 +608,40 @@ class TextFeatures:
         g = torch.Generator().manual_seed(seed)
         return cls({t: torch.randn(dim, generator=g) for t in texts})
 
+    @classmethod
+    def from_encoder(cls, encoder, tokenizer):
+        """A table that starts empty and grows: `encode` tokenises and encodes (text.ClipTextEncoder.encode_tokens, on the encoder's
+        device) only the prompts it has not seen and keeps their unit-norm rows, so an epoch encodes each distinct prompt once
+        (the reference runs the tower on every batch, models/rtdetrworld/train.py:148-150)."""
+        self = cls.__new__(cls)
+        self.table, self.dim, self.encoder, self.tokenizer = {}, getattr(encoder, 'embed_dim', None), encoder, tokenizer
+        return self
+
+    @classmethod
+    def from_clip_files(cls, weights, vocab, device):
+        """from_encoder for a CLIP checkpoint file (a torch-saved state_dict or the TorchScript archive `clip.load` downloads) and the
+        user's BPE merges file (`bpe_simple_vocab_16e6.txt.gz`)."""
+        from .text import ClipTextEncoder, SimpleTokenizer, load_clip_state_dict
+        enc = ClipTextEncoder.from_state_dict(load_clip_state_dict(weights)).to(device)
+        return cls.from_encoder(enc, SimpleTokenizer(vocab, context_length=enc.context_length))
+
+    @classmethod
+    def from_args(cls, text_feats, clip_weights, clip_vocab, device):
+        """The command-line tools' choice: --text-feats FILE, or --clip-weights FILE --clip-vocab FILE; both or neither is an error."""
+        if (text_feats is None) == (clip_weights is None and clip_vocab is None) or (clip_weights is None) != (clip_vocab is None):
+            raise ValueError('give either --text-feats, or --clip-weights together with --clip-vocab (not both, not neither)')
+        return cls.load(text_feats) if text_feats is not None else cls.from_clip_files(clip_weights, clip_vocab, device)
+
+    def _encode_missing(self, texts):
+        new = list(dict.fromkeys(t for t in texts if t not in self.table))      # distinct, in the order of the request
+        if new:
+            feats = self.encoder.encode_tokens(self.tokenizer(new), normalize=True).detach().to('cpu', torch.float32)
+            self.dim = feats.shape[-1]
+            self.table.update(zip(new, feats))
+
     def encode(self, texts):
+        if self.encoder is not None:
+            self._encode_missing(texts)
         missing = sorted({t for t in texts if t not in self.table})
         if missing:
             raise KeyError(f'no embedding for prompts {missing}')

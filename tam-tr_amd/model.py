@@ -180,9 +180,16 @@ class RTDETRDetectionWorldModel(nn.Module):
         return RTDETRDetectionLoss(nc=self.nc, use_vfl=True)
 
     def set_text_features(self, txt_feats):
-        """Offline vocabulary (stands in for set_classes(), tasks.py:552-571, whose CLIP encoder is out of scope)."""
+        """Vocabulary from features computed elsewhere (what set_classes(), tasks.py:552-571, ends with)."""
         self.txt_feats = txt_feats.reshape(-1, txt_feats.shape[-2], txt_feats.shape[-1])
         self.model[-1].nc = self.txt_feats.shape[1]
+
+    def set_classes(self, names, encoder, tokenizer):
+        """The reference's set_classes (nn/tasks.py:552-571) without its internal clip.load: `encoder` is a text.ClipTextEncoder on the
+        GPU, `tokenizer` a text.SimpleTokenizer.  Of an `a/b` name the first synonym is encoded; rows are unit-norm."""
+        names = list(names.values()) if isinstance(names, dict) else list(names)
+        ids = tokenizer([n.split('/')[0] for n in names])
+        self.set_text_features(encoder.encode_tokens(ids, normalize=True))
 
     def fuse(self, verbose=False):
         """Evaluation graph (nn/tasks.py:121-152, what valTAMTR.py / AutoBackend(fuse=True) run): every RepConvN collapses to one

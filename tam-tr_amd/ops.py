@@ -1145,14 +1145,19 @@ def pack_mask(mask):
     The hit test is object identity + version: an address/shape key could match a NEW mask allocated in a freed one's block."""
     if _mask_cache and _mask_cache[0][0] is mask and _mask_cache[0][1] == mask._version:
         return _mask_cache[0][2]
+    words = mask_words(mask)
+    _mask_cache[:] = [(mask, mask._version, words)]
+    return words
+
+
+def mask_words(mask):
+    """pack_mask without its one-entry cache: for a caller that keeps the words itself (text.ClipTextEncoder's causal mask)."""
     Q = mask.shape[1]
     W = (Q + 31) // 32
     m = torch.zeros(mask.shape[0], W * 32, dtype=torch.int64, device=mask.device)
     m[:, :Q] = mask.to(torch.int64)
     words = (m.view(mask.shape[0], W, 32) << torch.arange(32, device=mask.device)).sum(-1)
-    words = torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32).contiguous()
-    _mask_cache[:] = [(mask, mask._version, words)]
-    return words
+    return torch.where(words >= 2 ** 31, words - 2 ** 32, words).to(torch.int32).contiguous()
 
 
 class _SelfAttention(torch.autograd.Function):
@@ -1192,6 +1197,80 @@ def self_attention(q, k, v, nh, attn_mask=None):
     attn_mask bool [Q,Q], True = blocked (transformer.py:546)."""
     bits = pack_mask(attn_mask) if attn_mask is not None else None
     return _SelfAttention.apply(q, k, v, int(nh), bits)
+
+
+def self_attention_packed(q, k, v, nh, mask_bits):
+    """self_attention with the mask already packed by mask_words (or None)."""
+    return _SelfAttention.apply(q, k, v, int(nh), mask_bits)
+
+
+# ------------------------------------------------------------------------------------------------ CLIP text tower (csrc/text.hip)
+def _f32c(what, *tensors):
+    for t in tensors:
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+            raise _lib.TamtrHipError(f'{what}: operands must be contiguous float32 tensors (got {t.dtype}, strides {tuple(t.stride())})')
+
+
+def text_embed(ids, token_embedding, positional_embedding):
+    """x[n * L, W] = token_embedding[ids] + positional_embedding[:L] in fp32; ids int32 [n, L].  An id outside the vocabulary is refused
+    here, before the launch (one read-back of the ids' range; prompts are encoded once and cached, so it is off the hot path)."""
+    require_gpu(ids, token_embedding, positional_embedding)
+    _f32c('text_embed', token_embedding, positional_embedding)
+    if ids.dtype != torch.int32 or ids.dim() != 2 or not ids.is_contiguous():
+        raise _lib.TamtrHipError('text_embed: ids must be a contiguous int32 [n, L] tensor')
+    n, L = ids.shape
+    V, W = token_embedding.shape
+    if L > positional_embedding.shape[0] or positional_embedding.shape[1] != W:
+        raise _lib.TamtrHipError(f'text_embed: context {L} x {W} does not fit positional_embedding {tuple(positional_embedding.shape)}')
+    lo, hi = (int(v) for v in torch.aminmax(ids))
+    if lo < 0 or hi >= V:
+        raise _lib.TamtrHipError(f'text_embed: token ids span [{lo}, {hi}], outside the vocabulary [0, {V}) (TAMTR_EINVAL)')
+    x = torch.empty(n * L, W, device=ids.device, dtype=torch.float32)
+    call('tamtr_text_embed', ptr(ids), ptr(token_embedding), ptr(positional_embedding), ptr(x), n, L, W, V, stream_ptr())
+    return x
+
+
+_LINEAR_F32_EPI = {None: 0, 'quick_gelu': 1}
+
+
+def linear_f32(x, w, b, act=None, residual=None, out=None):
+    """epi(x @ w^T + b) in fp32 on the fp32 MFMA: x [M, K], w [N, K], b [N] or None; act None | 'quick_gelu'; residual [M, N] is added
+    after the bias (not together with act) and may be `out` itself.  K % 32 == 0, N % 64 == 0, any M."""
+    require_gpu(x, w, b, residual, out)
+    _f32c('linear_f32', x, w, b, residual, out)
+    if act not in _LINEAR_F32_EPI or (act is not None and residual is not None):
+        raise _lib.TamtrHipError(f'linear_f32: act {act!r} with residual={residual is not None} is not an epilogue of the kernel')
+    if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1] or (b is not None and b.shape != (w.shape[0],)):
+        raise _lib.TamtrHipError(f'linear_f32: shapes x {tuple(x.shape)} w {tuple(w.shape)} do not form x @ w^T + b')
+    M, K = x.shape
+    N = w.shape[0]
+    if out is None:
+        out = torch.empty(M, N, device=x.device, dtype=torch.float32)
+    for t in (residual, out):
+        if t is not None and t.shape != (M, N):
+            raise _lib.TamtrHipError(f'linear_f32: residual / out must be [{M}, {N}], got {tuple(t.shape)}')
+    if out.data_ptr() == x.data_ptr():
+        raise _lib.TamtrHipError('linear_f32: out must not be x (only the residual may alias the output)')
+    call('tamtr_linear_f32', ptr(x), ptr(w), ptr(b), ptr(residual), ptr(out), M, N, K, 2 if residual is not None else _LINEAR_F32_EPI[act],
+         stream_ptr())
+    return out
+
+
+def text_pool_project(x, ids, gamma, beta, proj, eps=1e-5, normalize=True):
+    """Per prompt: the row of x [n * L, W] at the first maximum of ids [n, L] -> LayerNorm(gamma, beta, eps) -> @ proj [W, E], divided by
+    its L2 norm when `normalize`; fp32 [n, E]."""
+    require_gpu(x, ids, gamma, beta, proj)
+    _f32c('text_pool_project', x, gamma, beta, proj)
+    if ids.dtype != torch.int32 or ids.dim() != 2 or not ids.is_contiguous():
+        raise _lib.TamtrHipError('text_pool_project: ids must be a contiguous int32 [n, L] tensor')
+    n, L = ids.shape
+    W, E = proj.shape
+    if x.shape != (n * L, W) or gamma.shape != (W,) or beta.shape != (W,):
+        raise _lib.TamtrHipError(f'text_pool_project: x {tuple(x.shape)} does not match ids {tuple(ids.shape)} and proj {tuple(proj.shape)}')
+    out = torch.empty(n, E, device=x.device, dtype=torch.float32)
+    call('tamtr_text_pool_project', ptr(x), ptr(ids), ptr(gamma), ptr(beta), ptr(proj), ptr(out), n, L, W, E, float(eps), int(bool(normalize)),
+         stream_ptr())
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ a-9 selective scan

@@ -4,6 +4,9 @@ label files under an incremented --project/--name folder; one JSON line at the e
 
     python tools/predict.py --weights runs/train/TAMTR/best.pt --text-feats clip_vitb32.npz --data dataset.yaml \
         --source images/ --conf 0.4 --iou 0.6 --batch 4 --save [--save-txt --save-conf]
+
+Instead of --text-feats, --clip-weights ViT-B-32.pt --clip-vocab bpe_simple_vocab_16e6.txt.gz encodes the class names with the package's
+own CLIP text tower (tamtr_amd.text), so any name works, not only those of a table.
 """
 import argparse
 import json
@@ -18,7 +21,9 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='TAM-TR prediction on images (one HIP postprocess launch per batch)')
     ap.add_argument('--weights', required=True, help="checkpoint written by training ({'model', 'ema', ...} state_dicts)")
     ap.add_argument('--raw', action='store_true', help='use the raw weights instead of the EMA copy')
-    ap.add_argument('--text-feats', required=True, help='.npz {texts, feats} or a torch-saved {text: vector}')
+    ap.add_argument('--text-feats', help='.npz {texts, feats} or a torch-saved {text: vector}; or give --clip-weights and --clip-vocab')
+    ap.add_argument('--clip-weights', help='CLIP ViT-B/32 checkpoint (state_dict or TorchScript archive): class names are encoded here')
+    ap.add_argument('--clip-vocab', help="CLIP's BPE merges file (bpe_simple_vocab_16e6.txt.gz), with --clip-weights")
     g = ap.add_mutually_exclusive_group(required=True)
     g.add_argument('--data', help="dataset yaml whose 'names' are the classes")
     g.add_argument('--names', help='comma-separated class names')
@@ -36,7 +41,10 @@ def parse_args(argv=None):
     ap.add_argument('--name', default='TAMTR')
     ap.add_argument('--exist-ok', action='store_true', help='reuse --project/--name instead of incrementing it')
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if (args.text_feats is None) == (args.clip_weights is None and args.clip_vocab is None) or (args.clip_weights is None) != (args.clip_vocab is None):
+        ap.error('give either --text-feats, or --clip-weights together with --clip-vocab (not both, not neither)')
+    return args
 
 
 def load_names(args):
@@ -61,7 +69,7 @@ def main(argv=None):
     model = RTDETRDetectionWorldModel(nc=len(names)).to(dev)
     ck = torch.load(args.weights, map_location=dev)
     model.load_state_dict(ck['model' if args.raw else 'ema'])
-    pred = Predictor(model, names, D.TextFeatures.load(args.text_feats), imgsz=args.imgsz, conf=args.conf, iou=args.iou,
+    pred = Predictor(model, names, D.TextFeatures.from_args(args.text_feats, args.clip_weights, args.clip_vocab, dev), imgsz=args.imgsz, conf=args.conf, iou=args.iou,
                      classes=args.classes, single_cls=args.single_cls, batch=args.batch, dtype=args.dtype)
     save_dir = increment_path(os.path.join(args.project, args.name), exist_ok=args.exist_ok)
     if args.save or args.save_txt:

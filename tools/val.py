@@ -20,7 +20,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--data', required=True)
-    ap.add_argument('--text-feats', required=True)
+    ap.add_argument('--text-feats', help='.npz {texts, feats} or a torch-saved {text: vector}; or give --clip-weights and --clip-vocab')
+    ap.add_argument('--clip-weights', help='CLIP ViT-B/32 checkpoint (state_dict or TorchScript archive): class names are encoded here')
+    ap.add_argument('--clip-vocab', help="CLIP's BPE merges file (bpe_simple_vocab_16e6.txt.gz), with --clip-weights")
     ap.add_argument('--weights', required=True)
     ap.add_argument('--split', default='val')
     ap.add_argument('--batch', type=int, default=16)
@@ -36,6 +38,8 @@ def main():
     ap.add_argument('--project', default='runs/val')
     ap.add_argument('--name', default='TAMTR')
     args = ap.parse_args()
+    if (args.text_feats is None) == (args.clip_weights is None and args.clip_vocab is None) or (args.clip_weights is None) != (args.clip_vocab is None):
+        ap.error('give either --text-feats, or --clip-weights together with --clip-vocab (not both, not neither)')
     if args.save_json and args.host_postprocess:
         ap.error('--save-json needs the device path (drop --host-postprocess)')
 
@@ -47,7 +51,7 @@ def main():
         spec = yaml.safe_load(f)
     root = spec.get('path', os.path.dirname(os.path.abspath(args.data)))
     names = spec['names'] if isinstance(spec['names'], dict) else dict(enumerate(spec['names']))
-    tf = D.TextFeatures.load(args.text_feats)
+    tf = D.TextFeatures.from_args(args.text_feats, args.clip_weights, args.clip_vocab, dev)
     ds = D.PromptDetDataset(os.path.normpath(os.path.join(root, spec[args.split])), names, args.imgsz, augment=False)
     loader = D.build_dataloader(ds, args.batch, args.workers, shuffle=False)
     model = RTDETRDetectionWorldModel(nc=len(names)).to(dev)
