@@ -35,7 +35,8 @@ extern "C" {
 #define TAMTR_ELAUNCH (-3)
 
 /* ABI version, bumped on any signature change.  The CLIP text tower's entries at the end of this file (tamtr_text_embed, tamtr_linear_f32,
- * tamtr_text_pool_project) are new symbols only: no existing signature changed, so the version stayed at 36 when they were added. */
+ * tamtr_text_pool_project) and tamtr_val_confusion are new symbols only: no existing signature changed, so the version stayed at 36 when
+ * they were added. */
 int tamtr_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -579,6 +580,38 @@ int tamtr_detect_postprocess(const void* preds, int dtype, int B, int nq, int nd
 int tamtr_val_postprocess_match(const void* preds, int dtype, int B, int nq, int nd, float imgsz, float conf, float iou, int single_cls,
                                 float max_wh, const float* lab_cls, const float* lab_box, const int32_t* lab_off, int M, const float* scale,
                                 float* predn, uint8_t* correct, int32_t* counts, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Validator confusion matrix.  Replaces the per-image ConfusionMatrix.process_batch (ultralytics/utils/metrics.py:833-877) as
+ * RTDETRValidator.update_metrics calls it (ultralytics/models/rtdetrworld/val.py:141-165).  Reads the outputs of
+ * tamtr_val_postprocess_match on the device and the same grouped labels:
+ *      predn   f32 [B, nq, 6]   as tamtr_val_postprocess_match leaves it: x1 y1 x2 y2 (original-image pixels), score, cls
+ *      counts  i32 [B]          rows of predn that are detections (read on the device; clamped to 0 .. nq)
+ *      lab_cls, lab_box, lab_off, M, scale: as for tamtr_val_postprocess_match (only scale[b][2..3] = fp32(w_orig), fp32(h_orig) are used)
+ *      matrix  i32 [(nc + 1) * (nc + 1)]   row = predicted, column = true, index nc = background.  ADDED TO in place: the caller zeroes
+ *                               it once per run and the accumulation over images, batches and launches stays on the device
+ *  The rule, per image with npr = counts[b] detections and nl labels (exact integer equality with engine.ConfusionMatrix on CPU fp32
+ *  tensors).  Label boxes: xywh -> xyxy on the normalised values, then x *= fp32(w_orig), y *= fp32(h_orig).  Classes are truncated
+ *  towards zero as `.int()` does; a label or a detection whose class is outside [0, nc) (or NaN) is removed first and counted nowhere
+ *  (the reference would index out of range).  Under single_cls the classes of predn are already 0; label classes are left as they are.
+ *   1. npr == 0: every label adds matrix[nc, gc] += 1.
+ *   2. npr > 0 and nl == 0: the matrix is NOT touched - the reference calls process_batch only inside `if nl:`, so detections on an image
+ *      without labels are not counted as false positives (kept on purpose).
+ *   3. otherwise the detections with score > cm_conf (fp32) take part.  IoU = engine.box_iou(labels, dets) =
+ *      inter / (((area_l + area_d) - inter) + fp32(1e-7)), class-agnostic; a pair is a candidate when iou > iou_thres (strict, fp32; a NaN
+ *      IoU never qualifies); L(d) = the candidate label of highest IoU of detection d; D(l) = among the detections with L(d) == l the one
+ *      of highest IoU.  Among equal IoUs the LOWER label index wins in L and the LOWER detection row wins in D (the reference's
+ *      argsort()[::-1] + np.unique passes leave that order unspecified).
+ *   4. a label with a D(l) adds matrix[cls(D(l)), gc(l)] += 1; every other label adds matrix[nc, gc(l)] += 1.
+ *   5. only if the image has at least one matched pair, every confidence-passing detection that is nobody's D(l) adds
+ *      matrix[cls(d), nc] += 1 (the reference's `if n:`): an image whose detections all miss contributes no false positives (kept on
+ *      purpose).
+ *  cm_conf and iou_thres are compared as given, in fp32.  No cap on labels per image.  One launch, one workgroup per image, integer
+ *  atomics only (the result does not depend on order); nothing is allocated, set or synchronised, so the call can be captured.
+ *  TAMTR_EINVAL: a NULL operand (lab_cls / lab_box may be NULL only when M == 0), B < 1, nq < 1, nc < 1, M < 0, iou_thres < 0 or NaN.
+ *  TAMTR_EUNSUP: nq > 512. */
+int tamtr_val_confusion(const float* predn, const int32_t* counts, int B, int nq, int nc, const float* lab_cls, const float* lab_box,
+                        const int32_t* lab_off, int M, const float* scale, float cm_conf, float iou_thres, int32_t* matrix, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * CLIP text tower (frozen ViT-B/32 text encoder), fp32 end to end, forward only.  Replaces `clip.tokenize(...)` followed by

@@ -101,6 +101,7 @@ _SIGS = {
     'tamtr_dwconv_silu_cross_bwd': [_P, _P, _LL, _P, _P, _P, _LL, _P, _I, _I, _I, _I, _I, _I, _P],
     'tamtr_detect_postprocess': [_P, _I, _I, _I, _I, _P, _F, _F, _I, _F, _P, _I, _P, _P, _P, _P],
     'tamtr_val_postprocess_match': [_P, _I, _I, _I, _I, _F, _F, _F, _I, _F, _P, _P, _P, _I, _P, _P, _P, _P, _P],
+    'tamtr_val_confusion': [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _F, _F, _P, _P],
     'tamtr_text_embed': [_P, _P, _P, _P, _LL, _I, _I, _I, _P],
     'tamtr_linear_f32': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     'tamtr_text_pool_project': [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],

@@ -1,4 +1,4 @@
-// capi.hip - ABI version of libtamtr_hip.so (the kernels live in gate/msdeform/contrastive/selfattn/selscan/gemm_bf16/lsap/cpam/dwconv/ss2d_out/bn/conv3x3/imgaug/fold/optim/xproj/detrloss/predict/valmatch/text.hip).
+// capi.hip - ABI version of libtamtr_hip.so (the kernels live in gate/msdeform/contrastive/selfattn/selscan/gemm_bf16/lsap/cpam/dwconv/ss2d_out/bn/conv3x3/imgaug/fold/optim/xproj/detrloss/predict/valmatch/confusion/text.hip).
 #include "common.h"
 #include <stdlib.h>
 

@@ -443,17 +443,99 @@ def ap_per_class(tp, conf, pred_cls, target_cls, eps=1e-16):
     return tpn, fpn, p, r, f1, ap, classes.astype(int)
 
 
-class Validator:
-    """Accumulates (correct, conf, pred_cls, target_cls) over batches and reduces to mp, mr, mAP50, mAP50-95."""
+def cm_conf(conf):
+    """The confusion matrix's confidence threshold from the validator's: 0.25 when that is None or the default 0.001 (metrics.py:818)."""
+    return 0.25 if conf in (None, 0.001) else conf
 
-    def __init__(self, imgsz=640, conf=0.001, iou=0.7, single_cls=False):
+
+def _int_classes(c, nc):
+    """`.int()` of a float class vector with the range check done in float -> (indices int64, in-range mask).  NaN, +-inf and anything
+    that truncates outside [0, nc) is out of range."""
+    t = torch.trunc(c.float())
+    ok = (t >= 0) & (t < nc)
+    return t[ok].long().numpy(), ok
+
+
+class ConfusionMatrix:
+    """The reference's detection ConfusionMatrix (utils/metrics.py:801-888) on CPU tensors, vectorised; the statement of the rule that
+    csrc/confusion.hip implements, its checker, and the host validator's path.  matrix int64 [nc + 1, nc + 1]: row = predicted,
+    column = true, index nc = background.
+    Per image: the detections with score > conf take part; IoU = box_iou(labels, detections), class-agnostic; a pair is a candidate when
+    iou > iou_thres; L(d) = the candidate label of highest IoU of detection d; D(l) = among the detections with L(d) == l the one of
+    highest IoU.  A label with a D(l) counts at [cls(D(l)), gc(l)], every other label at [nc, gc(l)]; a passing detection that is
+    nobody's D(l) counts at [cls(d), nc] - but ONLY IF the image has at least one matched pair (the reference's `if n:`, kept on
+    purpose).  The caller skips images without labels, as the reference does, so their detections are counted nowhere.
+    Where the reference leaves the order of equal IoUs to numpy's argsort, this project defines it: the LOWER label index wins in L, the
+    LOWER detection row wins in D.  A label or detection whose class is outside [0, nc) is removed first and counted nowhere (the
+    reference would index out of range)."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45):
+        if not iou_thres >= 0:
+            raise ValueError('ConfusionMatrix: iou_thres must be >= 0')
+        self.nc, self.conf, self.iou_thres = int(nc), cm_conf(conf), iou_thres
+        self.matrix = np.zeros((self.nc + 1, self.nc + 1), dtype=np.int64)
+
+    def process_batch(self, detections, labels):
+        """detections [N, 6] xyxy conf cls and labels [M, 5] cls xyxy of one image; or detections None and labels [M] classes (an image
+        without detections: every label is a background miss)."""
+        nc = self.nc
+        if detections is None:
+            gc, _ = _int_classes(labels.detach().cpu().reshape(-1), nc)
+            np.add.at(self.matrix[nc], gc, 1)
+            return
+        det, lab = detections.detach().float().cpu(), labels.detach().float().cpu()
+        det = det[det[:, 4] > self.conf]
+        dc, ok = _int_classes(det[:, 5], nc)
+        det = det[ok]
+        gc, ok = _int_classes(lab[:, 0], nc)
+        lab = lab[ok]
+        nl, nd = lab.shape[0], det.shape[0]
+        has, D = np.zeros(nl, bool), np.zeros(nl, np.int64)
+        if nl and nd:
+            iou = box_iou(lab[:, 1:], det[:, :4])
+            v = torch.where(iou > self.iou_thres, iou, torch.full_like(iou, -1.0)).numpy()      # [nl, nd]; NaN fails the comparison
+            L = v.argmax(0)                               # the first maximum: the LOWER label index among equal IoUs
+            best = v[L, np.arange(nd)]
+            claim = np.full((nl, nd), -1.0, np.float32)   # claim[l, d] = iou(l, d) where L(d) == l
+            mine = best > -1.0
+            claim[L[mine], np.nonzero(mine)[0]] = best[mine]
+            D = claim.argmax(1)                           # the first maximum: the LOWER detection row among equal IoUs
+            has = claim[np.arange(nl), D] > -1.0
+        np.add.at(self.matrix, (dc[D[has]], gc[has]), 1)
+        np.add.at(self.matrix[nc], gc[~has], 1)
+        if has.any():
+            free = np.ones(nd, bool)
+            free[D[has]] = False
+            np.add.at(self.matrix[:, nc], dc[free], 1)
+
+    def tp_fp(self):
+        """True and false positives per class (background dropped)."""
+        tp = self.matrix.diagonal()
+        return tp[:-1], (self.matrix.sum(1) - tp)[:-1]
+
+    def normalized(self):
+        """Every column divided by its sum + 1e-9, as the reference's plot normalises."""
+        return self.matrix / (self.matrix.sum(0).reshape(1, -1) + 1e-9)
+
+
+class Validator:
+    """Accumulates (correct, conf, pred_cls, target_cls) over batches and reduces to mp, mr, mAP50, mAP50-95.
+    confusion: also keep the reference's confusion matrix (ConfusionMatrix above, called where RTDETRValidator.update_metrics calls it);
+    results() then carries 'confusion_matrix'.  nc: its class count, taken from the first prediction when None."""
+
+    def __init__(self, imgsz=640, conf=0.001, iou=0.7, single_cls=False, confusion=False, nc=None):
         self.imgsz, self.conf, self.iou, self.single_cls = imgsz, conf, iou, single_cls
         self.stats, self.seen = [], 0
+        self.confusion, self.nc, self.confusion_matrix = confusion, nc, None
 
     @torch.no_grad()
     def update(self, preds, batch):
-        dev = preds[0].device if isinstance(preds, (list, tuple)) else preds.device
+        y = preds[0] if isinstance(preds, (list, tuple)) else preds
+        dev = y.device
         iouv = IOUV.to(dev)
+        if self.confusion and self.confusion_matrix is None:
+            self.nc = y.shape[-1] - 4 if self.nc is None else self.nc
+            self.confusion_matrix = ConfusionMatrix(self.nc, self.conf)
         for si, pred in enumerate(postprocess(preds, self.imgsz, self.conf, self.iou, self.single_cls)):
             idx = batch['batch_idx'].view(-1).to(dev) == si
             cls = batch['cls'].to(dev).view(-1, 1)[idx].float()
@@ -465,6 +547,8 @@ class Validator:
             if npr == 0:
                 if nl:
                     self.stats.append((correct, torch.zeros(0, device=dev), torch.zeros(0, device=dev), cls.squeeze(-1)))
+                    if self.confusion:
+                        self.confusion_matrix.process_batch(None, cls.squeeze(-1))
                 continue
             if self.single_cls:
                 pred[:, 5] = 0
@@ -475,18 +559,24 @@ class Validator:
                 tbox = xywh2xyxy(bbox)
                 tbox[..., [0, 2]] *= shape[1]
                 tbox[..., [1, 3]] *= shape[0]
-                correct = process_batch(predn.float(), torch.cat((cls, tbox), 1), iouv)
+                labelsn = torch.cat((cls, tbox), 1)
+                correct = process_batch(predn.float(), labelsn, iouv)
+                if self.confusion:
+                    self.confusion_matrix.process_batch(predn, labelsn)
             self.stats.append((correct, pred[:, 4], pred[:, 5], cls.squeeze(-1)))
 
     def results(self):
+        extra = {}
+        if self.confusion:
+            extra['confusion_matrix'] = self.confusion_matrix.matrix.tolist() if self.confusion_matrix is not None else []
         if not self.stats:
-            return {'precision': 0.0, 'recall': 0.0, 'mAP50': 0.0, 'mAP50-95': 0.0, 'seen': self.seen}
+            return {'precision': 0.0, 'recall': 0.0, 'mAP50': 0.0, 'mAP50-95': 0.0, 'seen': self.seen, **extra}
         stats = [torch.cat(x, 0).cpu().numpy() for x in zip(*self.stats)]
         if not stats[0].any():
-            return {'precision': 0.0, 'recall': 0.0, 'mAP50': 0.0, 'mAP50-95': 0.0, 'seen': self.seen}
+            return {'precision': 0.0, 'recall': 0.0, 'mAP50': 0.0, 'mAP50-95': 0.0, 'seen': self.seen, **extra}
         _, _, p, r, _, ap, _ = ap_per_class(*stats)
         return {'precision': float(p.mean()), 'recall': float(r.mean()), 'mAP50': float(ap[:, 0].mean()),
-                'mAP50-95': float(ap.mean()), 'seen': self.seen}
+                'mAP50-95': float(ap.mean()), 'seen': self.seen, **extra}
 
 
 _EMPTY = {'precision': 0.0, 'recall': 0.0, 'mAP50': 0.0, 'mAP50-95': 0.0}
@@ -498,21 +588,34 @@ class DeviceValidator:
     the same ap_per_class.  Its dict equals Validator's key for key (on the model output widened to fp32) and adds 'per_class':
     [{class, images, instances, precision, recall, mAP50, mAP50-95}] for the classes that have labels (the reference's print_results
     table).  save_json: also collect the reference's pred_to_json records (models/yolo/detect/val.py:231-242; the batch must carry
-    'im_file'); class_map maps a class index to the record's category_id (default: the index)."""
+    'im_file'); class_map maps a class index to the record's category_id (default: the index).
+    confusion: update() makes one more launch per batch (ops.val_confusion, csrc/confusion.hip) on the outputs and the uploaded labels
+    of the first, adding into one device matrix - still nothing synchronises; results() then carries 'confusion_matrix' (nested lists
+    of ints, equal to Validator's), which rides in the run's one device-to-host copy.  nc: its class count, from the first prediction
+    when None."""
 
-    def __init__(self, imgsz=640, conf=0.001, iou=0.7, single_cls=False, save_json=False, class_map=None, names=None):
+    def __init__(self, imgsz=640, conf=0.001, iou=0.7, single_cls=False, save_json=False, class_map=None, names=None, confusion=False,
+                 nc=None):
         self.imgsz, self.conf, self.iou, self.single_cls = imgsz, conf, iou, single_cls
         self.save_json, self.class_map, self.names = save_json, class_map, names
         self.batches, self.files, self.seen = [], [], 0
         self.jdict = []
         self._reduced = None
+        self.confusion, self.nc = confusion, nc
+        self._matrix, self._matrix_host = None, None   # i32 [nc + 1, nc + 1] on the device; its copy after _reduce()
 
     @torch.no_grad()
     def update(self, preds, batch):
         from . import ops
         y = preds[0] if isinstance(preds, (list, tuple)) else preds
-        self.batches.append(ops.val_postprocess_match(y, batch['cls'], batch['bboxes'], batch['batch_idx'], batch.get('ori_shape'),
-                                                      self.imgsz, self.conf, self.iou, self.single_cls))
+        out = ops.val_postprocess_match(y, batch['cls'], batch['bboxes'], batch['batch_idx'], batch.get('ori_shape'), self.imgsz, self.conf,
+                                        self.iou, self.single_cls, return_device_labels=self.confusion)
+        self.batches.append(out[:5])
+        if self.confusion:
+            if self._matrix is None:
+                self.nc = y.shape[-1] - 4 if self.nc is None else self.nc
+                self._matrix = torch.zeros(self.nc + 1, self.nc + 1, dtype=torch.int32, device=y.device)
+            ops.val_confusion(out[0], out[2], out[5], self.nc, cm_conf(self.conf), 0.45, self._matrix)
         self.seen += y.shape[0]
         if self.save_json:
             self.files.extend(batch['im_file'])
@@ -526,6 +629,8 @@ class DeviceValidator:
             for predn, correct, counts, lab_cls, lab_off in outs:
                 parts = [predn, correct, counts] + ([lab_cls, lab_off] if isinstance(lab_cls, torch.Tensor) else [])
                 dev_parts += [p.reshape(-1).view(torch.uint8) for p in parts]
+            if self._matrix is not None:
+                dev_parts.append(self._matrix.reshape(-1).view(torch.uint8))
             flat = torch.cat(dev_parts).cpu().numpy() if dev_parts else np.zeros(0, np.uint8)   # the run's one device-to-host copy
             pos, rows, hits, image, tcls, timage, first = 0, [], [], [], [], [], 0
 
@@ -548,6 +653,8 @@ class DeviceValidator:
                 tcls.append(lab_cls)
                 timage.append(first + np.repeat(np.arange(B), np.diff(lab_off)))
                 first += B
+            if self._matrix is not None:
+                self._matrix_host = take(self._matrix.numel(), np.int32).reshape(tuple(self._matrix.shape)).copy()
             cat = lambda xs, shape, dt: np.concatenate(xs) if xs else np.zeros(shape, dt)   # noqa: E731
             self._reduced = (cat(rows, (0, 6), np.float32), cat(hits, (0, 10), bool), cat(image, (0,), np.int64),
                              cat(tcls, (0,), np.float32), cat(timage, (0,), np.int64))
@@ -557,8 +664,11 @@ class DeviceValidator:
         predn, correct, image, tcls, timage = self._reduce()
         if self.save_json:
             self.jdict = self._records(predn, image)
+        extra = {}
+        if self.confusion:
+            extra['confusion_matrix'] = self._matrix_host.tolist() if self._matrix_host is not None else []
         if (len(predn) == 0 and len(tcls) == 0) or not correct.any():
-            return {**_EMPTY, 'seen': self.seen, 'per_class': []}
+            return {**_EMPTY, 'seen': self.seen, 'per_class': [], **extra}
         _, _, p, r, _, ap, classes = ap_per_class(correct, predn[:, 4], predn[:, 5], tcls)
         per_class = []
         for k, c in enumerate(classes):
@@ -567,7 +677,7 @@ class DeviceValidator:
                               'instances': int(mine.sum()), 'precision': float(p[k]), 'recall': float(r[k]), 'mAP50': float(ap[k, 0]),
                               'mAP50-95': float(ap[k].mean())})
         return {'precision': float(p.mean()), 'recall': float(r.mean()), 'mAP50': float(ap[:, 0].mean()), 'mAP50-95': float(ap.mean()),
-                'seen': self.seen, 'per_class': per_class}
+                'seen': self.seen, 'per_class': per_class, **extra}
 
     def _records(self, predn, image):
         """pred_to_json: image_id = the file stem; bbox = top-left x, y, w, h rounded to 3; score rounded to 5."""
@@ -597,15 +707,18 @@ class DeviceValidator:
 
 
 @torch.no_grad()
-def validate(model, batches, imgsz=640, conf=0.001, iou=0.7, autocast_dtype=None, on_device=False, save_json=None, names=None):
+def validate(model, batches, imgsz=640, conf=0.001, iou=0.7, autocast_dtype=None, on_device=False, save_json=None, names=None,
+             confusion=False):
     """model in eval mode over an iterable of batches -> metric dict (valTAMTR.py's flow without the dataset plumbing).
     on_device: postprocess and label matching in one HIP launch per batch (DeviceValidator; the dict then also carries 'per_class');
-    save_json (a file or folder path, needs on_device): also write the reference's predictions.json there."""
+    save_json (a file or folder path, needs on_device): also write the reference's predictions.json there.
+    confusion: the dict also carries 'confusion_matrix' ([nc + 1][nc + 1] ints, row = predicted, column = true, last = background)."""
     if save_json and not on_device:
         raise ValueError('validate(save_json=...) needs on_device=True: the records come from the device path')
     was_training = model.training
     model.eval()
-    v = DeviceValidator(imgsz, conf, iou, save_json=bool(save_json), names=names) if on_device else Validator(imgsz, conf, iou)
+    v = (DeviceValidator(imgsz, conf, iou, save_json=bool(save_json), names=names, confusion=confusion) if on_device
+         else Validator(imgsz, conf, iou, confusion=confusion))
     for batch in batches:
         img = batch['img']
         with torch.autocast(img.device.type, dtype=autocast_dtype or torch.bfloat16, enabled=autocast_dtype is not None):

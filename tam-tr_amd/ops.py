@@ -1876,6 +1876,12 @@ def _f32_at_most(x):
     return float(np.nextafter(f, np.float32(-np.inf)) if float(f) > x else f)
 
 
+def _f32_nearest(x):
+    """The float32 nearest to x: what torch turns a Python scalar into before it compares an fp32 tensor with it."""
+    import numpy as np
+    return float(np.float32(x))
+
+
 @torch.no_grad()
 def detect_postprocess(y, orig_hw, conf, iou, classes=None, single_cls=False, max_wh=7680.):
     """RTDETRPredictor.postprocess (models/rtdetrworld/predict.py:34-78) for the whole batch in one launch: class max,
@@ -1908,7 +1914,7 @@ def detect_postprocess(y, orig_hw, conf, iou, classes=None, single_cls=False, ma
 
 
 @torch.no_grad()
-def val_postprocess_match(y, cls, bboxes, batch_idx, ori_hw, imgsz, conf, iou, single_cls=False, max_wh=7680.):
+def val_postprocess_match(y, cls, bboxes, batch_idx, ori_hw, imgsz, conf, iou, single_cls=False, max_wh=7680., return_device_labels=False):
     """engine.Validator.update's per-image work (RTDETRValidator.postprocess, models/rtdetrworld/val.py:102-173, and match_predictions,
     engine/validator.py:208-247) for the whole batch in one launch; the rule is stated in csrc/valmatch.hip and is "the host rule on
     y.float()".  y (f32 / bf16) [B, nq, 4 + nc] eval output on the GPU; cls [M] or [M, 1], bboxes [M, 4] (normalised xywh) and
@@ -1916,7 +1922,9 @@ def val_postprocess_match(y, cls, bboxes, batch_idx, ori_hw, imgsz, conf, iou, s
     ori_hw: B (h, w) pairs, or None for (imgsz, imgsz).
     Returns predn f32 [B, nq, 6] (native-space x1 y1 x2 y2, score, cls; zero after the count), correct u8 [B, nq, 10], counts i32 [B]
     on the device, and the labels grouped by image, where they came from: lab_cls f32 [M'] and lab_off i32 [B + 1] (numpy arrays for
-    host labels, device tensors otherwise).  Host labels go up in ONE non-blocking copy; nothing synchronises."""
+    host labels, device tensors otherwise).  Host labels go up in ONE non-blocking copy; nothing synchronises.
+    return_device_labels: a sixth element, the device-side operands of that upload (lab_cls f32 [M], lab_box f32 [M, 4],
+    lab_off i32 [B + 1], scale f32 [B, 4]) - what val_confusion reads, so the two ops share one copy per batch."""
     import numpy as np
     require_gpu(y)
     if y.dim() != 3:
@@ -1960,7 +1968,35 @@ def val_postprocess_match(y, cls, bboxes, batch_idx, ori_hw, imgsz, conf, iou, s
     call('tamtr_val_postprocess_match', ptr(y), dtype_code(y), B, nq, nd, float(imgsz), float(conf), _f32_at_most(float(iou)),
          int(bool(single_cls)), float(max_wh), ptr(d_cls) if M else None, ptr(d_box) if M else None, ptr(d_off), M, ptr(d_scale),
          ptr(predn), ptr(correct), ptr(counts), stream_ptr())
+    if return_device_labels:
+        return predn, correct, counts, ret_cls, ret_off, (d_cls, d_box, d_off, d_scale)
     return predn, correct, counts, ret_cls, ret_off
+
+
+@torch.no_grad()
+def val_confusion(predn, counts, device_labels, nc, conf, iou_thres, matrix):
+    """engine.ConfusionMatrix.process_batch (the reference's ConfusionMatrix.process_batch, utils/metrics.py:833-877, as the validator
+    calls it per image) for the whole batch in one launch; the rule is stated in csrc/confusion.hip.  predn f32 [B, nq, 6] and counts
+    i32 [B]: the outputs of val_postprocess_match; device_labels: the sixth element it returns with return_device_labels=True.
+    matrix i32 [nc + 1, nc + 1] on the device is ADDED TO in place (row = predicted, column = true, nc = background) and returned.
+    conf and iou_thres are rounded to the nearest fp32, the value torch compares an fp32 tensor with when the other side is a Python
+    scalar.  Nothing is uploaded, allocated or synchronised."""
+    require_gpu(predn, counts, matrix, *device_labels)
+    d_cls, d_box, d_off, d_scale = device_labels
+    nc = int(nc)
+    if predn.dim() != 3 or predn.shape[2] != 6 or predn.dtype != torch.float32 or counts.dtype != torch.int32 or counts.numel() != predn.shape[0]:
+        raise _lib.TamtrHipError(f'val_confusion: expected predn f32 [B, nq, 6] and counts i32 [B], got {tuple(predn.shape)} {predn.dtype}, '
+                                 f'{tuple(counts.shape)} {counts.dtype}')
+    B, nq, _ = predn.shape
+    M = int(d_cls.numel())
+    if (matrix.dtype != torch.int32 or matrix.numel() != (nc + 1) ** 2 or not matrix.is_contiguous() or d_off.dtype != torch.int32
+            or d_off.numel() != B + 1 or d_scale.numel() != 4 * B or d_box.numel() != 4 * M
+            or any(t.dtype != torch.float32 for t in (d_cls, d_box, d_scale))):
+        raise _lib.TamtrHipError(f'val_confusion: matrix must be contiguous i32 [{nc + 1}, {nc + 1}] and the labels those of val_postprocess_match')
+    predn, counts, d_cls, d_box, d_off, d_scale = _c(predn), _c(counts), _c(d_cls), _c(d_box), _c(d_off), _c(d_scale)
+    call('tamtr_val_confusion', ptr(predn), ptr(counts), B, nq, nc, ptr(d_cls) if M else None, ptr(d_box) if M else None, ptr(d_off), M,
+         ptr(d_scale), _f32_nearest(conf), _f32_nearest(iou_thres), ptr(matrix), stream_ptr())
+    return matrix
 
 
 def img_augment(src, inv_affine, luts, flags, out_hw, border=114):

@@ -5,8 +5,12 @@
 
 Postprocess and label matching run on the device (engine.DeviceValidator, one HIP launch per batch); --host-postprocess goes back to the
 per-image host loop.  --save-json writes the reference's predictions.json into the run folder <project>/<name> (name, name2, ...).
+--confusion adds the reference's confusion matrix (one more launch per batch on the device path, engine.ConfusionMatrix on the host path)
+and writes confusion_matrix.csv and confusion_matrix_normalized.csv (columns divided by their sums) into the run folder: row = predicted,
+column = true, header row and first column = the class names and `background`.
 """
 import argparse
+import csv
 import json
 import os
 import sys
@@ -35,6 +39,7 @@ def main():
     ap.add_argument('--no-fuse', action='store_true', help='keep BatchNorm layers separate (valTAMTR.py fuses, nn/autobackend.py:115)')
     ap.add_argument('--host-postprocess', action='store_true', help='the per-image host loop (engine.Validator); no per-class table, no JSON')
     ap.add_argument('--save-json', action='store_true', help="write predictions.json (the reference's save_json=True)")
+    ap.add_argument('--confusion', action='store_true', help='write confusion_matrix.csv and confusion_matrix_normalized.csv')
     ap.add_argument('--project', default='runs/val')
     ap.add_argument('--name', default='TAMTR')
     args = ap.parse_args()
@@ -63,15 +68,34 @@ def main():
     if not args.no_fuse:
         model.fuse()
     save_dir = None
-    if args.save_json:
+    if args.save_json or args.confusion:
         from tamtr_amd.predict import increment_path
         save_dir = str(increment_path(os.path.join(args.project, args.name), mkdir=True))
+    short = {k: v.split('/')[0] for k, v in names.items()}
     res = E.validate(model, (D.preprocess_batch(b, None, dev) for b in loader), imgsz=args.imgsz, conf=args.conf, iou=args.iou,
                      autocast_dtype=torch.bfloat16 if args.dtype == 'bf16' else None, on_device=not args.host_postprocess,
-                     save_json=save_dir, names={k: v.split('/')[0] for k, v in names.items()})
+                     save_json=save_dir if args.save_json else None, names=short, confusion=args.confusion)
     if save_dir is not None:
         res['save_dir'] = save_dir
+    if args.confusion:
+        res['confusion_csv'], res['confusion_normalized_csv'] = write_confusion(res['confusion_matrix'], [short[k] for k in sorted(short)], save_dir)
     print(json.dumps(res))
+
+
+def write_confusion(matrix, names, save_dir):
+    """The two tables of the reference's confusion-matrix plot as CSV: counts, and columns divided by (column sum + 1e-9)."""
+    ticks = list(names) + ['background']
+    total = [sum(col) + 1e-9 for col in zip(*matrix)] if matrix else []
+    tables = {'confusion_matrix.csv': matrix, 'confusion_matrix_normalized.csv': [[v / t for v, t in zip(row, total)] for row in matrix]}
+    paths = []
+    for fname, rows in tables.items():
+        paths.append(os.path.join(save_dir, fname))
+        with open(paths[-1], 'w', newline='') as f:
+            w = csv.writer(f)
+            w.writerow(['predicted / true'] + ticks)
+            for tick, row in zip(ticks, rows):
+                w.writerow([tick] + list(row))
+    return paths
 
 
 if __name__ == '__main__':

@@ -7,8 +7,12 @@
   (b) engine.validate end to end at 640 x 640, batch 16, fp32 and bf16, host against device path, from synthetic JPEG files with
       labels: seconds for the pass (second pass timed) and images/s.
 
-    python tools/val_bench.py [--images 64] [--rounds 3] [--kernel-only]
---kernel-only runs only the device loop of (a), for a `rocprofv3 --kernel-trace --stats` run of its own.
+  (c) --confusion: the shapes of (a); DeviceValidator.update with and without confusion=True, and
+      Validator.update with and without it for scale, ALTERNATING windows as in (a).
+
+    python tools/val_bench.py [--images 64] [--rounds 3] [--kernel-only] [--confusion]
+--kernel-only runs only the device loop of (a) - with --confusion the loop with confusion=True - for a `rocprofv3 --kernel-trace --stats`
+run of its own.
 """
 import argparse
 import json
@@ -43,6 +47,44 @@ def window(fn, min_s=1.0):
     e1.record()
     e1.synchronize()
     return e0.elapsed_time(e1) / n, n
+
+
+def bench_confusion(rounds, kernel_only=False):
+    from tamtr_amd import engine as E
+    rows = []
+    B, nq, conf, iou = 16, 300, 0.001, 0.7
+    for nc in (10, 80):
+        for per_image in (50, 500):
+            y = synthetic_preds(B, nq, nc).cuda()
+            batch = synthetic_labels(B, per_image, nc)
+
+            def run(cls, confusion):
+                v = cls(640, conf, iou, confusion=confusion)
+                v.update(y, batch)
+                return v
+
+            for _ in range(5):
+                run(E.DeviceValidator, True), run(E.DeviceValidator, False)
+            if kernel_only:
+                t, n = window(lambda: run(E.DeviceValidator, True))
+                rows.append({'nc': nc, 'labels_per_image': per_image, 'device_update_confusion_ms': round(t, 4), 'iters': n})
+                continue
+            run(E.Validator, True), run(E.Validator, False)
+            torch.cuda.synchronize()
+            t = {(c, f): [] for c in ('device', 'host') for f in (False, True)}
+            for _ in range(rounds):      # alternating windows
+                for name, cls in (('device', E.DeviceValidator), ('host', E.Validator)):
+                    for flag in (False, True):
+                        t[name, flag].append(window(lambda: run(cls, flag))[0])
+            m = np.array(run(E.DeviceValidator, True).results()['confusion_matrix'])
+            assert m.tolist() == run(E.Validator, True).results()['confusion_matrix']
+            rows.append({'B': B, 'nq': nq, 'nc': nc, 'labels_per_image': per_image, 'conf': conf, 'matched': int(m[:nc, :nc].sum()),
+                         'background_misses': int(m[nc].sum()), 'false_positives': int(m[:nc, nc].sum()),
+                         'device_update_ms': [round(x, 4) for x in t['device', False]],
+                         'device_update_confusion_ms': [round(x, 4) for x in t['device', True]],
+                         'host_update_ms': [round(x, 3) for x in t['host', False]],
+                         'host_update_confusion_ms': [round(x, 3) for x in t['host', True]]})
+    return rows
 
 
 def bench_update(rounds, kernel_only=False):
@@ -133,12 +175,18 @@ def main():
     ap.add_argument('--rounds', type=int, default=3)
     ap.add_argument('--kernel-only', action='store_true')
     ap.add_argument('--skip-validate', action='store_true')
+    ap.add_argument('--confusion', action='store_true', help='measurement (c): update with and without the confusion matrix')
     args = ap.parse_args()
     import tamtr_amd  # noqa: F401
     assert torch.cuda.is_available(), 'val_bench needs an MI355X'
     print(torch.cuda.get_device_name(0), 'torch', torch.__version__)
     if args.kernel_only:
-        print(json.dumps({'device_update_only': bench_update(0, True)}))
+        print(json.dumps({'device_update_only': (bench_confusion if args.confusion else bench_update)(0, True)}))
+        return
+    if args.confusion:
+        print(f'(c) update with and without the confusion matrix on one batch ({args.rounds} alternating windows of >= 1 s each, device events)')
+        for r in bench_confusion(args.rounds):
+            print(json.dumps(r))
         return
     print(f'(a) Validator.update vs DeviceValidator.update on one batch ({args.rounds} alternating windows of >= 1 s each, device events)')
     for r in bench_update(args.rounds):
