@@ -16,10 +16,6 @@ _PROJ_CONV_LIB = _os.environ.get('TAMTR_PROJ_CONV') == 'miopen'   # A/B switch: 
 
 _I, _F = ctypes.c_int, ctypes.c_float
 
-# measurement hook (bench.py): KERNEL_EVENTS['tamtr_linear_bf16'] = [] makes the op bracket the C call itself (not the
-# dtype casts around it) with a pair of events on the launch stream and append (start, end, algorithmic flops)
-KERNEL_EVENTS = {}
-
 
 def _c(t):
     return t if t.is_contiguous() else t.contiguous()
@@ -454,15 +450,7 @@ class _ValueProjMSDA(torch.autograd.Function):
         _, Q, _, nl, P, _ = loc.shape
         x2 = _c(x.reshape(-1, K))
         w16, b32 = _c(bf16_of(weight)), _c(bias.float())
-        value = torch.empty(B, L, M, D, device=x.device, dtype=torch.bfloat16)
-        rec = KERNEL_EVENTS.get('tamtr_linear_bf16')
-        if rec is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        call('tamtr_linear_bf16', ptr(x2), ptr(w16), ptr(b32), ptr(value), B * L, N, K, stream_ptr())
-        if rec is not None:
-            e1.record()
-            rec.append((e0, e1, 2.0 * B * L * N * K))
+        value = _linear_bf16_fwd(x2, w16, b32).view(B, L, M, D)
         loc32, aw32 = _c(loc.float()), _c(aw.float())
         sh = (ctypes.c_int32 * (2 * nl))(*[int(v) for hw in shapes for v in hw])
         out = torch.empty(B, Q, N, device=x.device, dtype=torch.bfloat16)
@@ -485,11 +473,7 @@ class _ValueProjMSDA(torch.autograd.Function):
         gvalue = torch.empty(B * L, N, device=gout.device, dtype=torch.bfloat16)
         call('tamtr_msdeform_attn_bwd_sorted', ptr(gout), ptr(value), ctypes.cast(sh, ctypes.c_void_p), ptr(loc32), ptr(aw32),
              ptr(gvalue), ptr(gloc), ptr(gaw), ptr(colw), B, L, M, D, Q, nl, P, N, dtype_code(value), stream_ptr())
-        gx = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty(B * L, K, device=gout.device, dtype=torch.bfloat16)
-            call('tamtr_linear_bf16', ptr(gvalue), ptr(_c(w16.t())), None, ptr(gx), B * L, K, N, stream_ptr())
-            gx = gx.view(B, L, K)
+        gx = _linear_bf16_dx(gvalue, w16).view(B, L, K) if ctx.needs_input_grad[0] else None
         gw = dw_splitk(gvalue, x2).to(w_dt) if ctx.needs_input_grad[1] else None
         gb = (gout.view(B * Q, M, D).float() * colw.view(B * Q, M, 1)).sum(0).view(N).to(b_dt) if ctx.needs_input_grad[2] else None
         return gx, gw, gb, None, gloc.to(loc_dt), gaw.to(aw_dt), None
@@ -554,7 +538,7 @@ def contrastive_logits(x, w, logit_scale, bias):
     return _ContrastiveLogits.apply(x, w, logit_scale, bias)
 
 
-# ------------------------------------------------------------------------------------------------ a-5 value projection
+# ------------------------------------------------------------------------------------------------ a-5 token-wise linears
 _SPLIT_MAX = int(_os.environ.get('TAMTR_SPLITK_MAX', '64'))   # A/B knob: slices of the row-sliced weight-gradient products
 
 
@@ -593,36 +577,34 @@ def dw_splitk(g2, x2, min_rows=2048):
     return slab_sum(torch.bmm(a, b))
 
 
-class _BoxRefine(torch.autograd.Function):
-    """sigmoid(delta + inverse_sigmoid(ref)) - the decoder's box refinement (transformer.py:881-887) - as one kernel each way."""
-
-    @staticmethod
-    def forward(ctx, delta, ref):
-        require_gpu(delta, ref)
-        d, r = _c(delta.float()), _c(ref.float())
-        out = torch.empty_like(d)
-        call('tamtr_box_refine_fwd', ptr(d), ptr(r), ptr(out), d.numel(), stream_ptr())
-        ctx.save_for_backward(out, r)
-        ctx.cfg = (delta.dtype, ref.dtype)
-        return out
-
-    @staticmethod
-    def backward(ctx, g):
-        out, r = ctx.saved_tensors
-        d_dt, r_dt = ctx.cfg
-        g = _c(g.float())
-        gd = torch.empty_like(out)
-        gr = torch.empty_like(out) if ctx.needs_input_grad[1] else None
-        call('tamtr_box_refine_bwd', ptr(g), ptr(out), ptr(r), ptr(gd), ptr(gr), out.numel(), stream_ptr())
-        return gd.to(d_dt), None if gr is None else gr.to(r_dt)
+def slab_sum(t):
+    """t [R, ...] (f32 | bf16, contiguous) -> f32 [...] = t.sum(0) in a fixed order in ONE kernel (csrc/fold.hip tamtr_slab_sum_rows): the
+    last stage of the two-stage reductions (partial rows written by a kernel's workgroups, per-image rows, split-K slices).  torch's
+    `t.sum(0)` of such a shape is a multi-workgroup reduction behind a memset node (its arrival semaphores), the node kind that breaks
+    HIP-graph replays under AQL packet capture; it also needs `.float()` first for bf16 slices."""
+    R = t.shape[0]
+    C = t.numel() // max(R, 1)
+    if not (t.is_cuda and t.dtype in (torch.float32, torch.bfloat16) and t.is_contiguous() and R > 0 and C % 4 == 0 and t.data_ptr() % 16 == 0):
+        return t.float().sum(0)
+    if R == 1:
+        return t[0].float()
+    out = torch.empty(t.shape[1:], device=t.device, dtype=torch.float32)
+    call('tamtr_slab_sum_rows', ptr(t), ptr(out), R, C, dtype_code(t), stream_ptr())
+    return out
 
 
-def box_refine(delta, ref):
-    """sigmoid(delta + inverse_sigmoid(ref)); delta, ref of the same shape."""
-    if delta.is_cuda and delta.shape == ref.shape and delta.dtype in (torch.float32, torch.bfloat16) and _os.environ.get('TAMTR_BOX_REFINE') != 'torch':
-        return _BoxRefine.apply(delta, ref)
-    x = ref.clamp(min=0, max=1)
-    return torch.sigmoid(delta + torch.log(x.clamp(min=1e-5) / (1 - x).clamp(min=1e-5)))
+def colsum(g2):
+    """Column sums (fp32) of a [M, N] gradient: the bias gradient of a token-wise Linear.  Tall bf16 matrices take the streaming kernel of
+    csrc/fold.hip (torch's generic reduction runs M = 537 600, N = 512 at 2.9 TB/s); everything else torch."""
+    M, N = g2.shape
+    if g2.is_cuda and g2.dtype == torch.bfloat16 and M >= 4096 and N % 8 == 0 and N <= 2048 and 256 % (N // 8) == 0 and g2.is_contiguous():
+        nblk = _lib.lib().tamtr_colsum_blocks(M)
+        part = torch.empty(nblk, N, device=g2.device, dtype=torch.float32)
+        call('tamtr_colsum_bf16', ptr(g2), ptr(part), M, N, stream_ptr())
+        return slab_sum(part)
+    if g2.is_cuda and g2.dtype in (torch.float32, torch.bfloat16) and N % 4 == 0:
+        return slab_sum(_c(g2))   # short or fp32 matrices: the ordered row sum directly (no torch reduction: see slab_sum)
+    return g2.sum(0, dtype=torch.float32)
 
 
 def bf16_shadow(p):
@@ -644,12 +626,71 @@ def bf16_of(p):
     return s if s is not None else p.to(torch.bfloat16)
 
 
+# measurement hook (bench.py): KERNEL_EVENTS['tamtr_linear_bf16'] = [] makes the forward launcher bracket the C call itself (not the
+# dtype casts around it) with a pair of events on the launch stream and append (start, end, algorithmic flops)
+KERNEL_EVENTS = {}
+
+
+def _linear_bf16_fwd(x2, w16, b32):
+    """y [M, N] = x2 [M, K] w16[N, K]^T + b32 (or no bias: None), bf16 in and out, on the MFMA kernel: the forward launch of every node
+    below and of _ValueProjMSDA, and the one launch that the measurement hook brackets."""
+    M, K = x2.shape
+    N = w16.shape[0]
+    y = torch.empty(M, N, device=x2.device, dtype=torch.bfloat16)
+    rec = KERNEL_EVENTS.get('tamtr_linear_bf16')
+    if rec is not None:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+    call('tamtr_linear_bf16', ptr(x2), ptr(w16), ptr(b32), ptr(y), M, N, K, stream_ptr())
+    if rec is not None:
+        e1.record()
+        rec.append((e0, e1, 2.0 * M * N * K))
+    return y
+
+
+def _linear_bf16_dx(g2, w16):
+    """dX [M, K] = g2 [M, N] w16[N, K]: the same "NT" GEMM against W^T (a 0.5 MB transpose) on the same MFMA kernel where its shapes allow,
+    else the library.  Never recorded by the measurement hook: bench.py's roofline.launches counts forward launches."""
+    N, K = w16.shape
+    if K % 128 == 0 and N % 64 == 0:
+        gx = torch.empty(g2.shape[0], K, device=g2.device, dtype=torch.bfloat16)
+        call('tamtr_linear_bf16', ptr(g2), ptr(_c(w16.t())), None, ptr(gx), g2.shape[0], K, N, stream_ptr())
+        return gx
+    return g2 @ w16
+
+
+def _bias_rows(y, idx, b32):
+    """The rows idx (along L) of y [B, L, N] = x W^T + b as if those rows of x had been zero: the bias."""
+    if idx.numel():
+        y[:, idx] = b32.to(torch.bfloat16)
+
+
+def _param_grads(g2, x2, w_dt, b_dt, need_w, need_b, min_rows=2048):
+    """(dW, db) of a token-wise linear from dY [M, N] and X [M, K], in the parameters' dtypes: dW = dY^T X by row slices (dw_splitk), db the
+    ordered column sums of dY (colsum); None for one that is not needed (b_dt None: no bias)."""
+    gw = dw_splitk(g2, x2, min_rows).to(w_dt) if need_w else None
+    gb = colsum(g2).to(b_dt) if (b_dt is not None and need_b) else None
+    return gw, gb
+
+
+def _linear_lib_bwd(needs, gy, x, w16, x_dt, w_dt, b_dt, min_rows=2048):
+    """(dX, dW, db) of y = x w16^T + b run on the library: dX = dY W one library GEMM in x's dtype, cast to x_dt; the rest _param_grads."""
+    N, K = w16.shape
+    g2 = _c(gy.reshape(-1, N).to(x.dtype))
+    x2 = _c(x.reshape(-1, K))
+    gx = (g2 @ w16).view(x.shape).to(x_dt) if needs[0] else None
+    return (gx,) + _param_grads(g2, x2, w_dt, b_dt, needs[1], needs[2], min_rows)
+
+
+_LM_MIN_ROWS = 256   # least rows per slice of _LinearMaster's weight gradient (the measured winner: see its backward)
+
+
 class _LinearMaster(torch.autograd.Function):
     """y = x W^T + b for the SHORT token-wise linears of the decoder side (M = B * Q rows; nn.Linear under bf16 autocast, transformer.py:
     539-558,869-889) with the gradients of W and b produced in fp32 FOR THE fp32 MASTERS: autocast's form casts W and b to bf16 per use, gets
     bf16 gradients for the copies (the bias gradient from a torch reduction behind a memset) and casts each back - per linear and step four
-    cast kernels, a reduction and a memset around three GEMMs.  Here: the optimizer's shadow copies (ops.bf16_of), dW = dY^T X as one GEMM with
-    fp32 output, db by the ordered column-sum kernels."""
+    cast kernels, a reduction and a memset around three GEMMs.  Here: the optimizer's shadow copies (ops.bf16_of), dW = dY^T X by row slices with
+    fp32 output (dw_splitk), db by the ordered column-sum kernels."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, w16=None, b16=None):
@@ -666,70 +707,9 @@ class _LinearMaster(torch.autograd.Function):
     def backward(ctx, gy):
         x16, w16 = ctx.saved_tensors
         x_dt, w_dt, b_dt = ctx.cfg
-        N, K = w16.shape
-        g2 = _c(gy.reshape(-1, N).to(torch.bfloat16))
-        x2 = _c(x16.reshape(-1, K))
-        gx = gw = gb = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.mm(g2, w16).view(x16.shape).to(x_dt)
-        if ctx.needs_input_grad[1]:
-            # M = B * Q = 4 672 rows against N x K <= 1 024 x 1 024 outputs: as ONE product the library runs it on 16 - 64 workgroups (35 us
-            # whatever N and K: profiles/r03_gemm_census.txt); as 16 row slices it is a batched product on 16 x the tiles + the ordered sum (A/B: 77.5 -> 77.1 ms per step)
-            wide = N % 8 == 0 and K % 8 == 0
-            gw = (dw_splitk(g2, x2, _LM_MIN_ROWS) if _LM_MIN_ROWS else (_mm_f32(g2.t(), x2) if wide else torch.mm(g2.t(), x2))).to(w_dt)
-        if b_dt is not None and ctx.needs_input_grad[2]:
-            gb = colsum(g2).to(b_dt)
-        return gx, gw, gb, None, None
-
-
-_MM_F32_OUT = None
-_LM_MIN_ROWS = int(_os.environ.get('TAMTR_LINEAR_MASTER_SLICE_ROWS', '256'))   # A/B knob: 0 = the weight gradient as one product
-
-
-def _mm_f32(a, b):
-    """a @ b for bf16 operands with the fp32 accumulator stored as it is (no rounding to bf16, no cast kernel) where this torch build's
-    mm takes out_dtype; else the bf16 product widened."""
-    global _MM_F32_OUT
-    if _MM_F32_OUT is not False:
-        try:
-            out = torch.mm(a, b, out_dtype=torch.float32)
-            _MM_F32_OUT = True
-            return out
-        except (NotImplementedError, RuntimeError, TypeError):
-            if _MM_F32_OUT:
-                raise
-            _MM_F32_OUT = False
-    return torch.mm(a, b).float()
-
-
-def linear_master_ok(x, lin):
-    return (x.is_cuda and torch.is_grad_enabled() and torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16
-            and isinstance(lin, torch.nn.Linear) and lin.weight.dtype == torch.float32 and x.dtype in (torch.float32, torch.bfloat16)
-            and lin.in_features % 4 == 0 and lin.out_features % 4 == 0 and _os.environ.get('TAMTR_LINEAR_MASTER') != '0')
-
-
-def linear(x, lin):
-    """lin(x) for an nn.Linear of the decoder side: in bf16 training mode on the GPU through _LinearMaster, else the module itself."""
-    if linear_master_ok(x, lin):
-        return _LinearMaster.apply(x, lin.weight, lin.bias)
-    return lin(x)
-
-
-def shared_bf16(x, *lins):
-    """x as the bf16 operand of SEVERAL ops.linear calls (one cast, and one cast of the summed input gradient, instead of one per consumer);
-    x itself where ops.linear would not take the _LinearMaster path."""
-    if x.dtype == torch.float32 and lins and all(linear_master_ok(x, lin) for lin in lins):
-        return x.to(torch.bfloat16)
-    return x
-
-
-def linear_rows(x, weight, bias, lo, hi):
-    """F.linear(x, weight[lo:hi], bias[lo:hi]) - a row block of a packed projection (nn.MultiheadAttention's in_proj) - the same way."""
-    w, b = weight[lo:hi], bias[lo:hi]
-    if (x.is_cuda and torch.is_grad_enabled() and torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16
-            and weight.dtype == torch.float32 and weight.shape[1] % 8 == 0 and (hi - lo) % 8 == 0 and _os.environ.get('TAMTR_LINEAR_MASTER') != '0'):
-        return _LinearMaster.apply(x, w, b, bf16_of(weight)[lo:hi], bf16_of(bias)[lo:hi])
-    return torch.nn.functional.linear(x, w, b)
+        # M = B * Q = 4 672 rows against N x K <= 1 024 x 1 024 outputs: as ONE product the library runs it on 16 - 64 workgroups (35 us
+        # whatever N and K: profiles/r03_gemm_census.txt); as 16 row slices it is a batched product on 16 x the tiles + the ordered sum (A/B: 77.5 -> 77.1 ms per step)
+        return _linear_lib_bwd(ctx.needs_input_grad, gy, x16, w16, x_dt, w_dt, b_dt, _LM_MIN_ROWS) + (None, None)
 
 
 class _LinearSplitK(torch.autograd.Function):
@@ -748,24 +728,20 @@ class _LinearSplitK(torch.autograd.Function):
     def backward(ctx, gy):
         x, w16 = ctx.saved_tensors
         w_dt, b_dt = ctx.cfg
-        g2 = _c(gy.reshape(-1, gy.shape[-1]).to(x.dtype))
-        x2 = _c(x.reshape(-1, x.shape[-1]))
-        gx = (g2 @ w16).view(x.shape) if ctx.needs_input_grad[0] else None
-        gw = dw_splitk(g2, x2).to(w_dt) if ctx.needs_input_grad[1] else None
-        gb = colsum(g2).to(b_dt) if (b_dt is not None and ctx.needs_input_grad[2]) else None
-        return gx, gw, gb
-
-
-def linear_splitk(x, weight, bias=None):
-    return _LinearSplitK.apply(x, weight, bias)
+        return _linear_lib_bwd(ctx.needs_input_grad, gy, x, w16, x.dtype, w_dt, b_dt)
 
 
 class _LinearBF16(torch.autograd.Function):
     """Y = X W^T + b on the hand-written MFMA kernel (bf16 in/out, fp32 accumulate).  Backward: dX = dY W on the same kernel
-    (against W^T); dW = dY^T X (a reduction over the M = B*L rows) is a batched library GEMM over row slices (dw_splitk)."""
+    (against W^T); dW = dY^T X (a reduction over the M = B*L rows) is a batched library GEMM over row slices (dw_splitk).
+
+    With idx (int64 [n] positions along L of x [B, L, K]: the invalid anchors of the MEH token memory, head.py:1210-1213: 1 580 of 33 600
+    at 640 px): y = (x with the rows idx of every image zeroed) W^T + b, without materialising the masked x: the few masked rows of y are
+    set to b.  Backward: dX with those rows zeroed, dW minus the masked rows' contribution (a small GEMM), db = column sums of dY over
+    ALL rows."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias):
+    def forward(ctx, x, weight, bias, idx):
         require_gpu(x, weight, bias)
         K = x.shape[-1]
         N = weight.shape[0]
@@ -774,157 +750,28 @@ class _LinearBF16(torch.autograd.Function):
             raise _lib.TamtrHipError('linear_bf16 needs bf16 activations')
         w16 = _c(bf16_of(weight))
         b32 = _c(bias.float()) if bias is not None else None
-        y = torch.empty(x2.shape[0], N, device=x.device, dtype=torch.bfloat16)
-        rec = KERNEL_EVENTS.get('tamtr_linear_bf16')
-        if rec is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        call('tamtr_linear_bf16', ptr(x2), ptr(w16), ptr(b32), ptr(y), x2.shape[0], N, K, stream_ptr())
-        if rec is not None:
-            e1.record()
-            rec.append((e0, e1, 2.0 * x2.shape[0] * N * K))
-        ctx.save_for_backward(x2, w16)
-        ctx.cfg = (x.shape, weight.dtype, None if bias is None else bias.dtype)
-        return y.view(*x.shape[:-1], N)
-
-    @staticmethod
-    def backward(ctx, gy):
-        x2, w16 = ctx.saved_tensors
-        xshape, w_dt, b_dt = ctx.cfg
-        g2 = _c(gy.reshape(-1, gy.shape[-1]).to(torch.bfloat16))
-        gx = None
-        if ctx.needs_input_grad[0]:
-            N, K = w16.shape
-            if K % 128 == 0 and N % 64 == 0:  # dX = dY W is the same "NT" GEMM against W^T (a 0.5 MB transpose): same MFMA kernel
-                gx = torch.empty(g2.shape[0], K, device=g2.device, dtype=torch.bfloat16)
-                call('tamtr_linear_bf16', ptr(g2), ptr(_c(w16.t())), None, ptr(gx), g2.shape[0], K, N, stream_ptr())
-                gx = gx.view(xshape)
-            else:
-                gx = (g2 @ w16).view(xshape)
-        gw = dw_splitk(g2, x2).to(w_dt) if ctx.needs_input_grad[1] else None
-        gb = colsum(g2).to(b_dt) if (b_dt is not None and ctx.needs_input_grad[2]) else None
-        return gx, gw, gb
-
-
-def colsum(g2):
-    """Column sums (fp32) of a [M, N] gradient: the bias gradient of a token-wise Linear.  Tall bf16 matrices take the streaming kernel of
-    csrc/fold.hip (torch's generic reduction runs M = 537 600, N = 512 at 2.9 TB/s); everything else torch."""
-    M, N = g2.shape
-    if g2.is_cuda and g2.dtype == torch.bfloat16 and M >= 4096 and N % 8 == 0 and N <= 2048 and 256 % (N // 8) == 0 and g2.is_contiguous():
-        nblk = _lib.lib().tamtr_colsum_blocks(M)
-        part = torch.empty(nblk, N, device=g2.device, dtype=torch.float32)
-        call('tamtr_colsum_bf16', ptr(g2), ptr(part), M, N, stream_ptr())
-        return slab_sum(part)
-    if g2.is_cuda and g2.dtype in (torch.float32, torch.bfloat16) and N % 4 == 0:
-        return slab_sum(_c(g2))   # short or fp32 matrices: the ordered row sum directly (no torch reduction: see slab_sum)
-    return g2.sum(0, dtype=torch.float32)
-
-
-def slab_sum(t):
-    """t [R, ...] (f32 | bf16, contiguous) -> f32 [...] = t.sum(0) in a fixed order in ONE kernel (csrc/fold.hip tamtr_slab_sum_rows): the
-    last stage of the two-stage reductions (partial rows written by a kernel's workgroups, per-image rows, split-K slices).  torch's
-    `t.sum(0)` of such a shape is a multi-workgroup reduction behind a memset node (its arrival semaphores), the node kind that breaks
-    HIP-graph replays under AQL packet capture; it also needs `.float()` first for bf16 slices."""
-    R = t.shape[0]
-    C = t.numel() // max(R, 1)
-    if not (t.is_cuda and t.dtype in (torch.float32, torch.bfloat16) and t.is_contiguous() and R > 0 and C % 4 == 0 and t.data_ptr() % 16 == 0):
-        return t.float().sum(0)
-    if R == 1:
-        return t[0].float()
-    out = torch.empty(t.shape[1:], device=t.device, dtype=torch.float32)
-    call('tamtr_slab_sum_rows', ptr(t), ptr(out), R, C, dtype_code(t), stream_ptr())
-    return out
-
-
-class _LinearBF16ZeroRows(torch.autograd.Function):
-    """y = (x with the rows `idx` of every image zeroed) W^T + b, without materialising the masked x: y = x W^T + b on the MFMA
-    kernel, then the few masked rows of y are set to b.  Backward: dX = dY W with those rows zeroed, dW = dY^T X minus the masked
-    rows' contribution (a small GEMM), db = column sums of dY over ALL rows.  x [B, L, K] bf16, idx int64 [n] positions along L
-    (the invalid anchors of the MEH token memory, head.py:1210-1213: 1 580 of 33 600 at 640 px)."""
-
-    @staticmethod
-    def forward(ctx, x, weight, bias, idx):
-        require_gpu(x, weight, bias)
-        B, L, K = x.shape
-        N = weight.shape[0]
-        x2 = _c(x.reshape(-1, K))
-        w16 = _c(bf16_of(weight))
-        b32 = _c(bias.float())
-        y = torch.empty(B, L, N, device=x.device, dtype=torch.bfloat16)
-        rec = KERNEL_EVENTS.get('tamtr_linear_bf16')
-        if rec is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        call('tamtr_linear_bf16', ptr(x2), ptr(w16), ptr(b32), ptr(y), B * L, N, K, stream_ptr())
-        if rec is not None:
-            e1.record()
-            rec.append((e0, e1, 2.0 * B * L * N * K))
-        if idx.numel():
-            y[:, idx] = b32.to(torch.bfloat16)
+        y = _linear_bf16_fwd(x2, w16, b32).view(*x.shape[:-1], N)
+        if idx is not None:
+            _bias_rows(y, idx, b32)
         ctx.save_for_backward(x2, w16, idx)
-        ctx.cfg = (x.shape, weight.dtype, bias.dtype)
+        ctx.cfg = (x.shape, weight.dtype, None if bias is None else bias.dtype)
         return y
 
     @staticmethod
     def backward(ctx, gy):
         x2, w16, idx = ctx.saved_tensors
-        (B, L, K), w_dt, b_dt = ctx.cfg
-        N = w16.shape[0]
-        g3 = _c(gy.to(torch.bfloat16))
-        g2 = g3.view(-1, N)
-        gx = torch.empty(B, L, K, device=g2.device, dtype=torch.bfloat16)
-        if K % 128 == 0 and N % 64 == 0:
-            call('tamtr_linear_bf16', ptr(g2), ptr(_c(w16.t())), None, ptr(gx), B * L, K, N, stream_ptr())
-        else:
-            gx = (g2 @ w16).view(B, L, K)
-        gw = dw_splitk(g2, x2)
-        if idx.numel():
+        xshape, w_dt, b_dt = ctx.cfg
+        N, K = w16.shape
+        g2 = _c(gy.reshape(-1, N).to(torch.bfloat16))
+        gx = _linear_bf16_dx(g2, w16).view(xshape) if ctx.needs_input_grad[0] else None
+        masked = idx is not None and idx.numel() > 0
+        gw, gb = _param_grads(g2, x2, torch.float32 if masked else w_dt, b_dt, *ctx.needs_input_grad[1:3])   # (masked: dW stays fp32 until the rows are off)
+        if masked and gx is not None:
             gx.index_fill_(1, idx, 0)   # (not `gx[:, idx] = 0`: assigning a Python scalar through an index synchronises the host)
-            gi, xi = g3[:, idx].reshape(-1, N), x2.view(B, L, K)[:, idx].reshape(-1, K)
-            gw = gw - (gi.t() @ xi).float()
-        gb = colsum(g2).to(b_dt)
-        return gx, gw.to(w_dt), gb, None
-
-
-def linear_bf16_zero_rows(x, weight, bias, idx):
-    """linear_bf16 of x [B, L, K] with the rows idx (along L) treated as zero; see _LinearBF16ZeroRows."""
-    return _LinearBF16ZeroRows.apply(x, weight, bias, idx)
-
-
-class _Fanout(torch.autograd.Function):
-    """n handles on one tensor for n consumers; the backward adds their n gradients in ONE pass (csrc/fold.hip tamtr_sum_n) instead of
-    autograd's n - 1 pairwise accumulations (three 2-read-1-write passes over the 550 MB token memory gradient per step)."""
-
-    @staticmethod
-    def forward(ctx, x, n):
-        return tuple(x.view_as(x) for _ in range(n))
-
-    @staticmethod
-    def backward(ctx, *gs):
-        live = [g for g in gs if g is not None]
-        if len(live) == 1:
-            return live[0], None
-        return _sum_handles(live, live[0].shape, live[0].dtype, live[0].device), None
-
-
-def _sum_handles(live, shape, dtype, device):
-    """Sum of the gradients of fan-out handles in one pass (tamtr_sum_n) into a buffer of our own; zeros when nobody sent one."""
-    if not live:
-        return torch.zeros(shape, dtype=dtype, device=device)
-    if len(live) == 1:
-        return live[0].clone()
-    g0 = live[0]
-    if (g0.is_cuda and g0.dtype in (torch.float32, torch.bfloat16) and g0.numel() % 4 == 0 and len(live) <= 8
-            and all(g.dtype == g0.dtype and g.shape == g0.shape for g in live)):
-        live = [_c(g) for g in live]
-        out = torch.empty_like(live[0])
-        src = (ctypes.c_void_p * len(live))(*[g.data_ptr() for g in live])
-        call('tamtr_sum_n', ctypes.cast(src, ctypes.c_void_p), len(live), ptr(out), out.numel(), dtype_code(out), stream_ptr())
-        return out
-    acc = live[0].clone()
-    for g in live[1:]:
-        acc += g
-    return acc
+        if masked and gw is not None:
+            gi, xi = g2.view(*xshape[:-1], N)[:, idx].reshape(-1, N), x2.view(xshape)[:, idx].reshape(-1, K)
+            gw = (gw - (gi.t() @ xi).float()).to(w_dt)
+        return gx, gw, gb, None
 
 
 class _EncSelect(torch.autograd.Function):
@@ -951,17 +798,8 @@ class _EncSelect(torch.autograd.Function):
             raise _lib.TamtrHipError('enc_select needs a bf16 token memory')
         x2 = _c(x.reshape(-1, K))
         w16, b32 = _c(bf16_of(w)), _c(b.float())
-        y = torch.empty(B, L, N, device=x.device, dtype=torch.bfloat16)
-        rec = KERNEL_EVENTS.get('tamtr_linear_bf16')
-        if rec is not None:
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-        call('tamtr_linear_bf16', ptr(x2), ptr(w16), ptr(b32), ptr(y), B * L, N, K, stream_ptr())
-        if rec is not None:
-            e1.record()
-            rec.append((e0, e1, 2.0 * B * L * N * K))
-        if invalid.numel():
-            y[:, invalid] = b32.to(torch.bfloat16)
+        y = _linear_bf16_fwd(x2, w16, b32).view(B, L, N)
+        _bias_rows(y, invalid, b32)
         g32, be32 = _c(gamma.float()), _c(beta.float())
         mem = torch.empty_like(y)
         stats = torch.empty(B * L, 2, device=x.device, dtype=torch.float32)
@@ -1009,6 +847,54 @@ class _EncSelect(torch.autograd.Function):
         return (gx, gw.to(w_dt), gb.to(b_dt), ggam.to(ga_dt), gbet.to(be_dt), None, gws.to(ws_dt), gbs.to(bs_dt), None, None, None, None)
 
 
+def _master_mode(x, weight):
+    """bf16-autocast training on the GPU with an fp32 master weight, and _LinearMaster not switched off (TAMTR_LINEAR_MASTER=0: A/B)."""
+    return (x.is_cuda and torch.is_grad_enabled() and torch.is_autocast_enabled('cuda') and torch.get_autocast_dtype('cuda') == torch.bfloat16
+            and weight.dtype == torch.float32 and _os.environ.get('TAMTR_LINEAR_MASTER') != '0')
+
+
+def linear_master_ok(x, lin):
+    return (isinstance(lin, torch.nn.Linear) and _master_mode(x, lin.weight) and x.dtype in (torch.float32, torch.bfloat16)
+            and lin.in_features % 4 == 0 and lin.out_features % 4 == 0)
+
+
+def linear(x, lin):
+    """lin(x) for an nn.Linear of the decoder side: in bf16 training mode on the GPU through _LinearMaster, else the module itself."""
+    if linear_master_ok(x, lin):
+        return _LinearMaster.apply(x, lin.weight, lin.bias)
+    return lin(x)
+
+
+def shared_bf16(x, *lins):
+    """x as the bf16 operand of SEVERAL ops.linear calls (one cast, and one cast of the summed input gradient, instead of one per consumer);
+    x itself where ops.linear would not take the _LinearMaster path."""
+    if x.dtype == torch.float32 and lins and all(linear_master_ok(x, lin) for lin in lins):
+        return x.to(torch.bfloat16)
+    return x
+
+
+def linear_rows(x, weight, bias, lo, hi):
+    """F.linear(x, weight[lo:hi], bias[lo:hi]) - a row block of a packed projection (nn.MultiheadAttention's in_proj) - the same way."""
+    w, b = weight[lo:hi], bias[lo:hi]
+    if _master_mode(x, weight) and weight.shape[1] % 8 == 0 and (hi - lo) % 8 == 0:
+        return _LinearMaster.apply(x, w, b, bf16_of(weight)[lo:hi], bf16_of(bias)[lo:hi])
+    return torch.nn.functional.linear(x, w, b)
+
+
+def linear_splitk(x, weight, bias=None):
+    return _LinearSplitK.apply(x, weight, bias)
+
+
+def linear_bf16(x, weight, bias=None):
+    """x [..., K] bf16, weight [N, K], bias [N] -> [..., N] bf16 (transformer.py:273 value_proj)."""
+    return _LinearBF16.apply(x, weight, bias, None)
+
+
+def linear_bf16_zero_rows(x, weight, bias, idx):
+    """linear_bf16 of x [B, L, K] with the rows idx (along L) treated as zero; see _LinearBF16."""
+    return _LinearBF16.apply(x, weight, bias, idx)
+
+
 def enc_select(x, lin, norm, score_head, invalid, nq, fixed_top=None, n_dec=0):
     """(top_feat [B, nq, hd], enc_scores [B, nq, nc], top [B, nq], n_dec handles on x) - see _EncSelect."""
     out = _EncSelect.apply(x, lin.weight, lin.bias, norm.weight, norm.bias, norm.eps, score_head.weight, score_head.bias, invalid, int(nq),
@@ -1022,6 +908,82 @@ def enc_select_ok(x, lin, norm, score_head):
             and isinstance(lin, torch.nn.Linear) and isinstance(score_head, torch.nn.Linear) and lin.bias is not None and score_head.bias is not None
             and lin.in_features % 64 == 0 and lin.out_features % 128 == 0 and lin.out_features in (32, 64, 128, 256, 512, 1024)
             and _os.environ.get('TAMTR_ENC_SELECT') != 'dense')
+
+
+# ------------------------------------------------------------------------------------------------ box refinement, fan-out sum, embedding rows
+class _BoxRefine(torch.autograd.Function):
+    """sigmoid(delta + inverse_sigmoid(ref)) - the decoder's box refinement (transformer.py:881-887) - as one kernel each way."""
+
+    @staticmethod
+    def forward(ctx, delta, ref):
+        require_gpu(delta, ref)
+        d, r = _c(delta.float()), _c(ref.float())
+        out = torch.empty_like(d)
+        call('tamtr_box_refine_fwd', ptr(d), ptr(r), ptr(out), d.numel(), stream_ptr())
+        ctx.save_for_backward(out, r)
+        ctx.cfg = (delta.dtype, ref.dtype)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        out, r = ctx.saved_tensors
+        d_dt, r_dt = ctx.cfg
+        g = _c(g.float())
+        gd = torch.empty_like(out)
+        gr = torch.empty_like(out) if ctx.needs_input_grad[1] else None
+        call('tamtr_box_refine_bwd', ptr(g), ptr(out), ptr(r), ptr(gd), ptr(gr), out.numel(), stream_ptr())
+        return gd.to(d_dt), None if gr is None else gr.to(r_dt)
+
+
+def box_refine(delta, ref):
+    """sigmoid(delta + inverse_sigmoid(ref)); delta, ref of the same shape."""
+    if delta.is_cuda and delta.shape == ref.shape and delta.dtype in (torch.float32, torch.bfloat16) and _os.environ.get('TAMTR_BOX_REFINE') != 'torch':
+        return _BoxRefine.apply(delta, ref)
+    x = ref.clamp(min=0, max=1)
+    return torch.sigmoid(delta + torch.log(x.clamp(min=1e-5) / (1 - x).clamp(min=1e-5)))
+
+
+class _Fanout(torch.autograd.Function):
+    """n handles on one tensor for n consumers; the backward adds their n gradients in ONE pass (csrc/fold.hip tamtr_sum_n) instead of
+    autograd's n - 1 pairwise accumulations (three 2-read-1-write passes over the 550 MB token memory gradient per step)."""
+
+    @staticmethod
+    def forward(ctx, x, n):
+        return tuple(x.view_as(x) for _ in range(n))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        live = [g for g in gs if g is not None]
+        if len(live) == 1:
+            return live[0], None
+        return _sum_handles(live, live[0].shape, live[0].dtype, live[0].device), None
+
+
+def _sum_handles(live, shape, dtype, device):
+    """Sum of the gradients of fan-out handles in one pass (tamtr_sum_n) into a buffer of our own; zeros when nobody sent one."""
+    if not live:
+        return torch.zeros(shape, dtype=dtype, device=device)
+    if len(live) == 1:
+        return live[0].clone()
+    g0 = live[0]
+    if (g0.is_cuda and g0.dtype in (torch.float32, torch.bfloat16) and g0.numel() % 4 == 0 and len(live) <= 8
+            and all(g.dtype == g0.dtype and g.shape == g0.shape for g in live)):
+        live = [_c(g) for g in live]
+        out = torch.empty_like(live[0])
+        src = (ctypes.c_void_p * len(live))(*[g.data_ptr() for g in live])
+        call('tamtr_sum_n', ctypes.cast(src, ctypes.c_void_p), len(live), ptr(out), out.numel(), dtype_code(out), stream_ptr())
+        return out
+    acc = live[0].clone()
+    for g in live[1:]:
+        acc += g
+    return acc
+
+
+def fanout(x, n):
+    """x -> n tensors with x's values (views), whose gradients are summed in one kernel; for tensors that feed several heavy consumers."""
+    if n <= 1 or not (x.requires_grad and torch.is_grad_enabled()):
+        return (x,) * max(n, 1)
+    return _Fanout.apply(x, int(n))
 
 
 class _EmbedRows(torch.autograd.Function):
@@ -1048,18 +1010,6 @@ def embed_rows(weight, idx):
             and _os.environ.get('TAMTR_EMBED_ROWS') != 'torch'):
         return _EmbedRows.apply(weight, idx)
     return weight[idx]
-
-
-def fanout(x, n):
-    """x -> n tensors with x's values (views), whose gradients are summed in one kernel; for tensors that feed several heavy consumers."""
-    if n <= 1 or not (x.requires_grad and torch.is_grad_enabled()):
-        return (x,) * max(n, 1)
-    return _Fanout.apply(x, int(n))
-
-
-def linear_bf16(x, weight, bias=None):
-    """x [..., K] bf16, weight [N, K], bias [N] -> [..., N] bf16 (transformer.py:273 value_proj)."""
-    return _LinearBF16.apply(x, weight, bias)
 
 
 # ------------------------------------------------------------------------------------------------ trunk: 1x1 convolutions' weight gradient

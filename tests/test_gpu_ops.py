@@ -1410,3 +1410,56 @@ def test_value_proj_msda_pair_gives_the_bias_gradient_from_query_sized_operands(
     scale = float(want.abs().max())
     assert float((b[3].double() - want).abs().max()) <= 1e-5 * scale + 1e-6, 'db from colw'
     assert float((a[3].double() - want).abs().max()) <= 2e-2 * scale, 'the column sums of the bf16 d(value) agree with it to bf16 rounding'
+
+
+def test_linear_bf16_measurement_hook_brackets_every_forward_launch_and_no_backward(ops):
+    """ops.KERNEL_EVENTS['tamtr_linear_bf16'] (what bench.py's roofline figure reads): each of the four nodes that run their forward on the MFMA linear
+    appends exactly one (start, end, 2 M N K) per forward; no backward appends (dX runs on the same kernel: roofline.launches counts forwards only);
+    with the hook popped nothing is recorded.  Shapes: the W-stationary kernel with a ragged last row block (dX on the own kernel), the tile kernel
+    (K = 192: dX on the library), and the smallest cases of the zeroed-rows, enc_select and value_proj_msda tests."""
+    import torch.nn as nn
+    torch.manual_seed(7)
+
+    def leaf(*shape):
+        return torch.randn(*shape, device='cuda').bfloat16().requires_grad_()
+
+    def plain(M, N, K):
+        lin, x = nn.Linear(K, N).cuda(), leaf(M, K)
+        return (lambda: ops.linear_bf16(x, lin.weight, lin.bias)), M, N, K
+
+    def zero_rows(B, L, N, K, idx):
+        lin, x = nn.Linear(K, N).cuda(), leaf(B, L, K)
+        idx = torch.tensor(idx, device='cuda')
+        return (lambda: ops.linear_bf16_zero_rows(x, lin.weight, lin.bias, idx)), B * L, N, K
+
+    def enc_select(B, L, hd, nc, nq, n_dec):
+        lin, norm, head, x = nn.Linear(hd, hd).cuda(), nn.LayerNorm(hd).cuda(), nn.Linear(hd, nc).cuda(), leaf(B, L, hd)
+        invalid = torch.tensor(sorted({0, 3, L // 2, L - 1}), device='cuda')
+        assert ops.enc_select_ok(x, lin, norm, head)
+        return (lambda: sum(t.float().sum() for t in ops.enc_select(x, lin, norm, head, invalid, nq, None, n_dec)[:2])), B * L, hd, hd
+
+    def value_proj_msda(B, Q, M, D, shapes, P):
+        L, N, nl = sum(h * w for h, w in shapes), M * D, len(shapes)
+        lin, x = nn.Linear(N, N).cuda(), leaf(B, L, N)
+        loc = (torch.rand(B, Q, M, nl, P, 2, device='cuda') * 1.3 - 0.15).requires_grad_()
+        aw = torch.softmax(torch.randn(B, Q, M, nl * P, device='cuda'), -1).view(B, Q, M, nl, P).requires_grad_()
+        assert ops.value_proj_msda_ok(x, lin, M, Q, P)
+        return (lambda: ops.value_proj_msda(x, lin, M, shapes, loc, aw)), B * L, N, N
+
+    cases = [plain(100, 256, 128), plain(77, 256, 192), zero_rows(2, 84, 128, 128, [0, 41, 83]), enc_select(1, 84, 256, 4, 8, 0),
+             value_proj_msda(2, 37, 8, 64, [(12, 10), (6, 5), (3, 3)], 4)]
+    assert ops.KERNEL_EVENTS == {}
+    rec = ops.KERNEL_EVENTS['tamtr_linear_bf16'] = []
+    try:
+        for i, (fwd, M, N, K) in enumerate(cases):
+            out = fwd()
+            assert len(rec) == i + 1 and rec[i][2] == 2.0 * M * N * K, (i, len(rec))
+            out.float().sum().backward()
+            assert len(rec) == i + 1, ('a backward recorded', i, len(rec))
+    finally:
+        ops.KERNEL_EVENTS.pop('tamtr_linear_bf16')
+    cases[0][0]()
+    assert len(rec) == len(cases) and ops.KERNEL_EVENTS == {}
+    torch.cuda.synchronize()
+    for e0, e1, _ in rec:
+        assert e0.elapsed_time(e1) > 0
