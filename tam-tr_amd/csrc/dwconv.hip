@@ -92,9 +92,9 @@ __device__ __forceinline__ void stage_tile(const T* __restrict__ x, size_t xs, i
       const int pix = it / GROUPS, gq = it - pix * GROUPS;
       const int py = pix / SIDE, px = pix - py * SIDE;
       const int h = h0 + py - HALO, w = w0 + px - HALO;
-      const float keep = (h >= 0 && h < H && w >= 0 && w < W) ? 1.f : 0.f;
+      const bool keep = h >= 0 && h < H && w >= 0 && w < W;   // a select, not a product with 0: an Inf in a border pixel must not turn the halo into NaN
 #pragma unroll
-      for (int j = 0; j < VN; ++j) s[gq * VN + j][py][px] = v[k][j] * keep;
+      for (int j = 0; j < VN; ++j) s[gq * VN + j][py][px] = keep ? v[k][j] : 0.f;
     }
   }
 }
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv_cross_bwd_kernel(const PT* 
   stage_tile<T, CB, 2, XP>(x, xs, b, d0, h0, w0, H, W, s_x);
 #endif
   // gradient tile = row-major plane (lanes along x) + column-major plane (lanes along y: its contiguous axis).  Loads go out in
-  // batches of 7 with clamped addresses and a 0/1 factor instead of a branch: hipcc ends a conditional block that contains a load with
+  // batches of 7 with clamped addresses and a select on the loaded value instead of a branch: hipcc ends a conditional block that contains a load with
   // s_waitcnt vmcnt(0), which made a thread's 21 loads per plane 21 serial round trips (71 % of the wave cycles were waits, round 2 PMC).
 #ifndef DW_ABL_NOG
   if ((W & 3) == 0 && (H & 3) == 0) {
@@ -177,8 +177,7 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv_cross_bwd_kernel(const PT* 
         const int nfix = plane == 0 ? H : W, nrun = plane == 0 ? W : H;
         const bool ok = fixed >= 0 && fixed < nfix && base >= 0 && base + 3 < nrun;
         const float4 t = plane_ld4(gp + (size_t)c * L + (size_t)min(max(fixed, 0), nfix - 1) * nrun + min(max(base, 0), nrun - 4));
-        const float f = ok ? 1.f : 0.f;
-        v[k] = make_float4(t.x * f, t.y * f, t.z * f, t.w * f);
+        v[k] = ok ? t : make_float4(0.f, 0.f, 0.f, 0.f);
       }
       if (plane == 1) __syncthreads();   // plane 0 is complete in LDS before plane 1 is added onto it
 #pragma unroll
@@ -211,7 +210,8 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv_cross_bwd_kernel(const PT* 
         const int c = it / (GS * GS), r = it - c * (GS * GS), py = r / GS, px = r - py * GS;
         const int h = h0 + py - 1, w = w0 + px - 1;
         const bool ok = h >= 0 && h < H && w >= 0 && w < W;
-        v[k] = plane_ld(gp + (size_t)c * L + (size_t)min(max(h, 0), H - 1) * W + min(max(w, 0), W - 1)) * (ok ? 1.f : 0.f);
+        v[k] = plane_ld(gp + (size_t)c * L + (size_t)min(max(h, 0), H - 1) * W + min(max(w, 0), W - 1));
+        v[k] = ok ? v[k] : 0.f;
       }
 #pragma unroll
       for (int k = 0; k < GB; ++k) {
@@ -236,7 +236,8 @@ __global__ __launch_bounds__(DW_THREADS) void dwconv_cross_bwd_kernel(const PT* 
         const int c = it / (GS * GS), r = it - c * (GS * GS), px = r / GS, py = r - px * GS;
         const int h = h0 + py - 1, w = w0 + px - 1;
         const bool ok = h >= 0 && h < H && w >= 0 && w < W;
-        v[k] = plane_ld(gp + (size_t)c * L + (size_t)min(max(w, 0), W - 1) * H + min(max(h, 0), H - 1)) * (ok ? 1.f : 0.f);
+        v[k] = plane_ld(gp + (size_t)c * L + (size_t)min(max(w, 0), W - 1) * H + min(max(h, 0), H - 1));
+        v[k] = ok ? v[k] : 0.f;
       }
 #pragma unroll
       for (int k = 0; k < GB; ++k) {

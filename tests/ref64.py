@@ -1,5 +1,6 @@
 """fp64 references with an error model for the bf16 hot-path kernels (tests/test_gpu_bf16_kernels.py, tests/test_ref64_host.py) and for the
-text gate and CPAM kernels in fp32 and bf16 (tests/test_gpu_gates_ref64.py).
+text gate and CPAM kernels in fp32 and bf16 (tests/test_gpu_gates_ref64.py), and for the LayerNorm, cross-merge and depthwise SS2D kernels
+(tests/test_gpu_ss2d_ref64.py).
 
 Every reference takes the operands exactly as the kernel sees them (bf16 tensors, fp32 side inputs), promotes them to float64 and
 computes on the CPU.  Next to each value it returns a magnitude: the same computation on absolute values.  check() then asserts,
@@ -481,3 +482,156 @@ def cpam_bounds(Cg, zmax, bf16):
     chain = fp32_b(Cg + 80) + 8 * e
     return {'c': (0, fp32_b(CPAM_C_N) + e), 's2': (0, fp32_b(CPAM_C_N + 3) + 2 * e), 'out': (a, fp32_b(24) + 3 * e),
             'dxd': (a, chain), 'du': (a, chain), 'dp': (a, (U8 if bf16 else 0) + chain), 'dx': (a, (U8 if bf16 else 0) + chain)}
+
+
+# ------------------------------------------------------------------------------------------------ LayerNorm (csrc/ss2d_out.hip)
+def layer_norm(x, gamma, beta, gout, eps=1e-5):
+    """csrc/ss2d_out.hip ln_fwd / ln_bwd (and their narrow forms): out = LayerNorm(x; gamma, beta) over the last axis, and dx, dgamma, dbeta
+    for the cotangent gout.
+
+    x, gout [N, D] in the activation dtype (fp32 or bf16), gamma, beta fp32.  No intermediate rounding: out and dx are stored in x's
+    dtype (a = 1 for bf16, 0 for fp32), dgamma and dbeta in fp32 (a = 0).  Magnitudes as in ln_gate() with the SiLU factor 1: xhat is
+    |xhat| + rstd mean|x| (the fp32 mean is subtracted before the scaling, so its error is absolute).
+    Returns {name: (value, magnitude)} for out, dx, dgamma, dbeta."""
+    import torch.nn.functional as F
+    N, D = x.shape
+    xr, gr, br = _d(x).requires_grad_(), _d(gamma).requires_grad_(), _d(beta).requires_grad_()
+    out = F.layer_norm(xr, (D,), gr, br, eps)
+    gd = _d(gout)
+    (out * gd).sum().backward()
+    with torch.no_grad():
+        xd = xr.detach()
+        mu = xd.mean(-1, keepdim=True)
+        rstd = (((xd - mu) ** 2).mean(-1, keepdim=True) + eps).rsqrt()
+        X = ((xd - mu) * rstd).abs() + rstd * xd.abs().mean(-1, keepdim=True)
+        m_out = gr.detach().abs() * X + br.detach().abs()
+        gxh = gd.abs() * gr.detach().abs()
+        m_dx = rstd * (gxh + gxh.mean(-1, keepdim=True) + X * (gxh * X).mean(-1, keepdim=True))
+        m_dg = (gd.abs() * X).sum(0)
+        m_db = gd.abs().sum(0)
+    return {'out': (out.detach(), m_out), 'dx': (xr.grad, m_dx), 'dgamma': (gr.grad, m_dg), 'dbeta': (br.grad, m_db)}
+
+
+# Roundings of xhat = (x - mean) rstd as every LayerNorm kernel of csrc/ss2d_out.hip forms it (the wave-per-token kernels at D = 1024 are
+# the longest; the narrow kernels sum 8 + log2(D / 8) terms).  D is a power of two, so the products by 1 / D are exact.
+#   mean: a lane's first float4 as (a + b) + (c + d) (2), its three other pieces added on (3), the 64-lane butterfly (6)           = 11
+#   x - mean                                                                                                                    =  1
+#   var = sum c^2 / D + eps: c's rounding counts twice (2), 16 FMAs, the butterfly (6), + eps (1) = 25; the rsqrt halves it        = 13
+#   (a shift of the mean moves var only in second order: sum c = 0); rsqrtf (2); * rstd (1)                                       =  3
+LN_XHAT_N = 28
+LN_OUT_N = LN_XHAT_N + 1                 # the FMA with gamma and beta
+# dx = rstd (gxh - c1 - xhat c2), gxh = g gamma (1): c2 = sum gxh xhat / D is 16 FMAs, the butterfly (6), * (1 / D) (1) on summands that
+# carry gxh (1) and xhat; then xhat c2 (xhat again, 1), the two subtractions (2), * rstd (rstd's 14 + 2 are inside LN_XHAT_N; 1)
+LN_DX_N = 2 * LN_XHAT_N + 23 + 1 + 1 + 2 + 1
+LN_TOK_PER_BLOCK = 64                    # LG_WAVES * LG_TOK_BWD: the tokens of one backward workgroup (one row of the partial sums)
+
+
+def layer_norm_bounds(ntok, bf16):
+    """{name: (a, b)} for layer_norm's outputs.  dgamma: xhat, then 16 tokens per wave as FMAs in registers (16), 4 waves through LDS (4),
+    the ordered slab_sum over ceil(ntok / 64) blocks; dbeta: the same chain of plain sums, without xhat."""
+    a = 1 if bf16 else 0
+    nblk = (ntok + LN_TOK_PER_BLOCK - 1) // LN_TOK_PER_BLOCK
+    return {'out': (a, fp32_b(LN_OUT_N)), 'dx': (a, fp32_b(LN_DX_N)),
+            'dgamma': (0, fp32_b(LN_XHAT_N + 16 + 4 + nblk)), 'dbeta': (0, fp32_b(16 + 4 + nblk))}
+
+
+def ln_gate_f32_bounds(ntok):
+    """{name: (a, b)} for ln_gate() where xz, out and gout are fp32 (ln_gate_fwd / bwd_kernel<float>): the figures
+    tests/test_gpu_bf16_kernels.py uses for the bf16 form, with a = 0 everywhere."""
+    nblk = (ntok + LN_TOK_PER_BLOCK - 1) // LN_TOK_PER_BLOCK
+    return {'out': (0, fp32_b(48)), 'dx': (0, fp32_b(48)), 'dz': (0, fp32_b(48)), 'dgamma': (0, fp32_b(nblk + 80)), 'dbeta': (0, fp32_b(nblk + 80))}
+
+
+# ------------------------------------------------------------------------------------------------ cross-merge (csrc/ss2d_out.hip)
+def cross_merge(y4, H, W):
+    """cross_merge_fwd*: y4 [B, 4, D, L] (directions 0, 2 row-major, 1, 3 column-major flattenings of an H x W map) -> [B, L, D] =
+    y0 + y2 + T(y1 + y3), T the transposition of the column-major planes into row-major order.  Magnitude sum |y_k|.  The kernels add
+    (y0 + y2) + (y1 + y3): three fp32 roundings, the output is fp32 (a = 0, b = fp32_b(3))."""
+    y = _d(y4)
+    B, _, D, L = y.shape
+
+    def T(t):
+        return t.view(B, D, W, H).transpose(2, 3).reshape(B, D, L)
+    val = y[:, 0] + y[:, 2] + T(y[:, 1] + y[:, 3])
+    mag = y[:, 0].abs() + y[:, 2].abs() + T(y[:, 1].abs() + y[:, 3].abs())
+    return val.transpose(1, 2).contiguous(), mag.transpose(1, 2).contiguous()
+
+
+def cross_merge_adjoint(g, H, W):
+    """cross_merge_bwd*: g [B, L, D] -> [B, 2, D, L]: plane 0 the row-major map, plane 1 the column-major map.  Pure data movement: no
+    magnitude; fp32 planes equal it, bf16 planes equal it rounded to nearest-even.  Keeps g's dtype."""
+    B, L, D = g.shape
+    gm = g.detach().cpu().transpose(1, 2)
+    return torch.stack([gm.contiguous(), gm.reshape(B, D, H, W).transpose(2, 3).reshape(B, D, L)], 1)
+
+
+# ------------------------------------------------------------------------------------------------ depthwise front end (csrc/dwconv.hip)
+def dwconv_silu_cross(xz, D, weight, bias, gout2):
+    """csrc/dwconv.hip: u2 [B, 2, D, L] = SiLU(conv3x3_depthwise(xi) + bias) in the row-major (plane 0) and column-major (plane 1)
+    flattening, xi = the first D channels of each pixel's row of xz [B, H, W, >= D]; and d(xi) [B, H, W, D], d(weight) [D, 9],
+    d(bias) [D] for the cotangent pair gout2 [B, 2, D, L] (None: forward only).
+
+    xz and gout2 as the kernel reads them (fp32 or bf16), weight [D, 9] (or [D, 1, 3, 3]) and bias [D] (or None) fp32.  Zero padding.  A
+    non-finite input gives what conv2d + SiLU give (the forward value is computed with torch's own conv2d).  No intermediate rounding.
+    Magnitudes: the conv z is sum |w| |x| + |bias| (m_z); SiLU(z) = z sigmoid(z) is m_z sig_mag(s, m_z); the backward's SiLU'(z) is
+    sig_mag(s, m_z) (1 + |z| (1 - s)) (SiLU' has a zero near z = -1.28; this form has none); the gradients are the same computation on
+    absolute values.  Returns {name: (value, magnitude)} for out, dx, dw, db, and 'zmax' (the largest finite |z|: the range of __expf)."""
+    import torch.nn.functional as F
+    B, H, W = xz.shape[:3]
+    L = H * W
+    xi = _d(xz)[..., :D].permute(0, 3, 1, 2).contiguous()
+    w = _d(weight).reshape(D, 1, 3, 3)
+    bi = _d(bias) if bias is not None else torch.zeros(D, dtype=torch.float64)
+
+    def conv(t, k, b_):
+        return F.conv2d(t, k, b_, padding=1, groups=D)
+
+    def both(t):                                                   # [B, D, H, W] -> [B, 2, D, L]
+        return torch.stack([t.flatten(2), t.transpose(2, 3).flatten(2)], 1)
+    z = conv(xi, w, bi)
+    fin = torch.isfinite(z)
+    m_z = conv(torch.nan_to_num(xi, nan=0.0, posinf=0.0, neginf=0.0).abs(), w.abs(), bi.abs())
+    s = torch.sigmoid(z)
+    m_s = sig_mag(s, m_z)
+    res = {'out': (both(z * s), both(m_z * m_s)), 'zmax': float(z[fin].abs().max()) if bool(fin.any()) else 0.0}
+    if gout2 is None:
+        return res
+    g2 = _d(gout2)
+    g = g2[:, 0].view(B, D, H, W) + g2[:, 1].view(B, D, W, H).transpose(2, 3)
+    m_g = g2[:, 0].view(B, D, H, W).abs() + g2[:, 1].view(B, D, W, H).transpose(2, 3).abs()
+    gz = g * s * (1 + z * (1 - s))
+    m_gz = m_g * m_s * (1 + z.abs() * (1 - s))
+    flip = w.flip(2, 3)                                            # d(input) = the transposed 3 x 3 of d(conv)
+    dx, m_dx = conv(gz, flip, None), conv(m_gz, flip.abs(), None)
+    xp, axp = F.pad(xi, (1, 1, 1, 1)), F.pad(xi.abs(), (1, 1, 1, 1))
+    dw, m_dw = torch.zeros(D, 9, dtype=torch.float64), torch.zeros(D, 9, dtype=torch.float64)
+    for ky in range(3):
+        for kx in range(3):
+            dw[:, ky * 3 + kx] = (gz * xp[:, :, ky:ky + H, kx:kx + W]).sum((0, 2, 3))
+            m_dw[:, ky * 3 + kx] = (m_gz * axp[:, :, ky:ky + H, kx:kx + W]).sum((0, 2, 3))
+    res.update({'dx': (dx.permute(0, 2, 3, 1).contiguous(), m_dx.permute(0, 2, 3, 1).contiguous()), 'dw': (dw, m_dw),
+                'db': (gz.sum((0, 2, 3)), m_gz.sum((0, 2, 3)))})
+    return res
+
+
+DW_TILE = 16          # csrc/dwconv.hip TS: a workgroup owns a 16 x 16 pixel tile; one row of the d(weight) / d(bias) partials per (image, tile)
+
+
+def dwconv_tiles(H, W):
+    return ((H + DW_TILE - 1) // DW_TILE) * ((W + DW_TILE - 1) // DW_TILE)
+
+
+def dwconv_bounds(zmax, B, H, W, bf16_act, bf16_planes):
+    """{name: (a, b)} for dwconv_silu_cross's outputs; every figure is a count of fp32 roundings along the kernel's chain.
+    z: nine FMAs onto the bias (9).  s = 1 / (1 + __expf(-z)): 1 + e and the division (2) and one __expf.  out = z / (1 + e): z's and
+    s's chains and one spare for the product form (12 and one __expf); stored in the plane's dtype.
+    d(conv) gz = (g0 + g1) s (1 + z (1 - s)): the plane sum (1), z (9), s (2 and __expf), 1 - s, z (.), 1 + (.), s (.), g (.) (5); the
+    factor z (1 - s) carries s's absolute error |z| times, so s's chain counts 1 + zmax times.
+    dx: nine FMAs over gz (9); stored in the activation dtype.  dw, db: an FMA per pixel (1), up to 21 of the 18 x 18 halo pixels per thread
+    in sequence (21), the 16-lane group sum (4), the ordered slab_sum over B * tiles partial rows."""
+    e = expf_b(zmax)
+    b_s = fp32_b(2) + e
+    b_gz = fp32_b(1 + 9 + 5) + (1 + math.ceil(zmax)) * b_s
+    b_sum = fp32_b(1 + 21 + 4 + B * dwconv_tiles(H, W))
+    return {'out': (1 if bf16_planes else 0, fp32_b(9 + 1) + b_s), 'dx': (1 if bf16_act else 0, b_gz + fp32_b(9)),
+            'dw': (0, b_gz + b_sum), 'db': (0, b_gz + b_sum)}

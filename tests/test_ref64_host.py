@@ -473,3 +473,302 @@ def test_gate_cl_ok_counts_the_text_rows():
     assert not ops.gate_cl_ok(_ChannelsLastMap(256), 256, 8, T=80)
     assert ops.gate_cl_ok(_ChannelsLastMap(64), 64, 8, T=80)
     assert ops.gate_cl_ok(_ChannelsLastMap(512), 512, 8, T=30) and not ops.gate_cl_ok(_ChannelsLastMap(512), 512, 8, T=31)
+
+
+# ------------------------------------------------------------------------------------------------ LayerNorm, cross-merge, depthwise front end
+import ss2d_cases as S
+
+
+def emu_layer_norm(x, gamma, beta, gout, eps=1e-5, drop_last_token=False, stats_bf16=False, next_stats=False, c2_no_div=False):
+    """ln_fwd / ln_bwd_kernel and their narrow forms: fp32 on the activation's values, the two-pass mean, mean and rstd stored in fp32 and
+    read back by the backward; d(gamma) / d(beta) as 16 tokens per wave in sequence, 4 waves per workgroup, the workgroups in order; out
+    and dx rounded to the activation dtype.  Mutants: the backward's stats rounded to bf16 / taken from the next token, c2 without its
+    1 / D, the last token missing from d(gamma) / d(beta)."""
+    st = bf if x.dtype == BF16 else (lambda t: t)
+    N, D = x.shape
+    xf, g, inv = x.float(), gout.float(), torch.tensor(1.0 / D)
+    mean = xf.sum(-1, keepdim=True) * inv
+    c = xf - mean
+    rstd = torch.rsqrt((c * c).sum(-1, keepdim=True) * inv + eps)
+    if stats_bf16:
+        mean, rstd = bf(mean), bf(rstd)
+    out = st((xf - mean) * rstd * gamma + beta)
+    if next_stats:
+        mean, rstd = torch.cat([mean[1:], mean[-1:]]), torch.cat([rstd[1:], rstd[-1:]])
+    xh = (xf - mean) * rstd
+    gxh = g * gamma
+    c1 = gxh.sum(-1, keepdim=True) * inv
+    c2 = (gxh * xh).sum(-1, keepdim=True) * (1.0 if c2_no_div else inv)
+    dx = st(rstd * (gxh - c1 - xh * c2))
+    gt = g.clone()
+    if drop_last_token:
+        gt[-1] = 0
+
+    def ordered(t):
+        t = torch.cat([t, torch.zeros(-N % 64, D)]).view(-1, 4, 16, D)
+        wave = torch.zeros(t.shape[0], 4, D)
+        for i in range(16):
+            wave = wave + t[:, :, i]
+        blk = wave[:, 0] + wave[:, 1] + wave[:, 2] + wave[:, 3]
+        tot = blk[0]
+        for r in range(1, blk.shape[0]):
+            tot = tot + blk[r]
+        return tot
+    return out, dx, ordered(gt * xh), ordered(gt)
+
+
+def emu_ln_gate_f32(x, xz, gamma, beta, gout, eps=1e-5):
+    """ln_gate_fwd / bwd_kernel<float>: emu_ln_gate without the roundings to bf16."""
+    N, D = x.shape
+    mean = x.mean(-1, keepdim=True)
+    rstd = ((x - mean) ** 2).mean(-1, keepdim=True).add(eps).rsqrt()
+    z = xz[:, D:2 * D]
+    xh = (x - mean) * rstd
+    y = xh * gamma + beta
+    sg = 1 / (1 + torch.exp(-z))
+    gy = gout * (z * sg)
+    gxh = gy * gamma
+    dx = rstd * (gxh - gxh.mean(-1, keepdim=True) - xh * (gxh * xh).mean(-1, keepdim=True))
+    return y * (z * sg), dx, gout * y * (sg * (1 + z * (1 - sg))), (gy * xh).sum(0), gy.sum(0)
+
+
+def _old_ln_ok(got, ref, n):
+    """test_layer_norm_kernel in bf16: out 2e-2 / 2e-2, dx 0.1 / 0.1, dgamma and dbeta 0.1 relative + 0.1 sqrt(n) absolute.  Per output,
+    the fraction of elements that rule accepts."""
+    tol = {'out': (2e-2, 2e-2), 'dx': (0.1, 0.1), 'dgamma': (0.1, 0.1 * n ** 0.5), 'dbeta': (0.1, 0.1 * n ** 0.5)}
+    return {k: float(((t.double() - ref[k][0]).abs() <= tol[k][1] + tol[k][0] * ref[k][0].abs()).double().mean()) for k, t in zip(tol, got)}
+
+
+@pytest.mark.parametrize('dt', list(S.LN_D))
+def test_layer_norm_emulation_passes_every_case(dt):
+    for D in S.LN_D[dt]:
+        for ntok in S.LN_NTOK:
+            for kind in S.LN_KINDS:
+                ins = S.ln_inputs(D, ntok, S.DT[dt], kind)
+                S.ln_assert(f'emu ln[{dt},{D},{ntok},{kind}]', emu_layer_norm(*ins), *ins)
+            for flat in (True, False):
+                ins = S.ln_constant_inputs(D, ntok, S.DT[dt], flat)
+                S.ln_constant_assert(f'emu ln[{dt},{D},{ntok},constant]', emu_layer_norm(*ins), *ins, flat)
+    for D, ntok in (S.LN_GATE_F32 if dt == 'fp32' else []):
+        ins = S.ln_gate_inputs(D, ntok)
+        S.ln_gate_assert(f'emu ln_gate[fp32,{D},{ntok}]', emu_ln_gate_f32(*ins), *ins)
+
+
+def test_layer_norm_mutants_fail():
+    """On the old test's own rows (bf16, 211 tokens, 2 randn + 0.5).  Its tolerances accept bf16 statistics outright, the next token's
+    statistics in dx at D = 1024, and a dropped token in most channels; every mutant misses a counted bound."""
+    D, ntok = 256, 211
+    ins = S.ln_inputs(D, ntok, BF16, 'ordinary')
+    ref = R.layer_norm(*ins)
+    ab = R.layer_norm_bounds(ntok, True)
+    assert set(_old_ln_ok(emu_layer_norm(*ins), ref, ntok).values()) == {1.0}
+    # the last token of the partial last workgroup missing from the partial sums: the old absolute term (1.45) hides it in most channels
+    m = emu_layer_norm(*ins, drop_last_token=True)
+    old = _old_ln_ok(m, ref, ntok)
+    assert old['out'] == old['dx'] == 1 and old['dgamma'] > 0.5 and old['dbeta'] > 0.5
+    rejected('dropped token', m[2], *ref['dgamma'], *ab['dgamma'])
+    rejected('dropped token', m[3], *ref['dbeta'], *ab['dbeta'])
+    # mean and rstd kept in bf16: accepted outright
+    m = emu_layer_norm(*ins, stats_bf16=True)
+    assert set(_old_ln_ok(m, ref, ntok).values()) == {1.0}
+    rejected('bf16 stats', m[1], *ref['dx'], *ab['dx'])
+    rejected('bf16 stats', m[2], *ref['dgamma'], *ab['dgamma'])
+    insf = S.ln_inputs(D, ntok, torch.float32, 'offset')
+    reff = R.layer_norm(*insf)
+    rejected('bf16 stats', emu_layer_norm(*insf, stats_bf16=True)[0], *reff['out'], *R.layer_norm_bounds(ntok, False)['out'])
+    # the backward normalises token t with the statistics of token t + 1: dx passes the old rule at D = 1024
+    ins4 = S.ln_inputs(1024, ntok, BF16, 'ordinary')
+    ref4 = R.layer_norm(*ins4)
+    m = emu_layer_norm(*ins4, next_stats=True)
+    old = _old_ln_ok(m, ref4, ntok)
+    assert old['out'] == old['dx'] == old['dbeta'] == 1 and old['dgamma'] > 0.5
+    rejected('next token\'s stats', m[1], *ref4['dx'], *ab['dx'])
+    rejected('next token\'s stats', m[2], *ref4['dgamma'], *ab['dgamma'])
+    # c2 = sum(gxh xhat) without its 1 / D: the old tolerance sees this one too (a plain rejection)
+    m = emu_layer_norm(*ins, c2_no_div=True)
+    assert _old_ln_ok(m, ref, ntok)['dx'] < 1
+    rejected('c2 without 1 / D', m[1], *ref['dx'], *ab['dx'])
+
+
+# ---- cross-merge
+def emu_cross_merge(y4, g, H, W, pdt, swap_hw=False, drop_dir3_block=False, truncate=False):
+    """cross_merge_fwd* / bwd*: (y0 + y2) + T(y1 + y3) in fp32; the backward copies g into both flattenings, rounded to nearest-even for
+    bf16 planes.  Mutants: the transposed planes read with H and W exchanged, direction 3 left out of the second 16-channel block, the
+    backward planes truncated."""
+    ymT = g2 = None
+    if y4 is not None:
+        y = y4.float()
+        B, _, D, L = y.shape
+        y3 = y[:, 3].clone()
+        if drop_dir3_block:
+            y3[:, 16:32] = 0
+        t = y[:, 1] + y3
+        t = t.view(B, D, H, W).transpose(2, 3).reshape(B, D, L) if swap_hw else t.view(B, D, W, H).transpose(2, 3).reshape(B, D, L)
+        ymT = ((y[:, 0] + y[:, 2]) + t).transpose(1, 2).contiguous()
+    if g is not None:
+        B, L, D = g.shape
+        gm = g.transpose(1, 2)
+        g2 = torch.stack([gm.contiguous(), gm.reshape(B, D, H, W).transpose(2, 3).reshape(B, D, L)], 1)
+        if pdt == BF16:
+            g2 = (g2.view(torch.int32) & -65536).view(torch.float32).bfloat16() if truncate else g2.bfloat16()
+    return ymT, g2
+
+
+def _cm_cases():
+    for dt, shapes in ((torch.float32, S.CM_GENERIC), (BF16, S.CM_FWD_BF16_GENERIC + S.CM_FWD16 + S.CM_BWD16 + S.CM_BWD_BF16_GENERIC)):
+        for H, W in dict.fromkeys(shapes):
+            for D in S.CM_D:
+                yield dt, D, H, W
+    yield BF16, 32, *S.CM_BWD16_D32_ONLY[0]
+
+
+def test_cross_merge_emulation_passes_every_case():
+    for dt, D, H, W in _cm_cases():
+        y4, g = S.cm_inputs(D, H, W, dt)
+        S.cm_assert(f'emu cross_merge[{S.dtn(dt)},{D},{H}x{W}]', *emu_cross_merge(y4, g, H, W, dt), y4, g, H, W)
+
+
+def test_cross_merge_mutants_fail():
+    D = 32
+    # H and W exchanged where the column-major planes are read: the same kernel on a square map, wrong on any other
+    y4, g = S.cm_inputs(D, 16, 16, torch.float32)
+    S.cm_assert('swap at 16 x 16', emu_cross_merge(y4, None, 16, 16, torch.float32, swap_hw=True)[0], None, y4, None, 16, 16)
+    for H, W in ((17, 16), (13, 21), (5, 40)):
+        y4, g = S.cm_inputs(D, H, W, torch.float32)
+        with pytest.raises(AssertionError):
+            S.cm_assert('H and W exchanged', emu_cross_merge(y4, None, H, W, torch.float32, swap_hw=True)[0], None, y4, None, H, W)
+    # direction 3 left out of the second channel block
+    y4, g = S.cm_inputs(D, 34, 30, BF16)
+    with pytest.raises(AssertionError):
+        S.cm_assert('direction 3 dropped', emu_cross_merge(y4, None, 34, 30, BF16, drop_dir3_block=True)[0], None, y4, None, 34, 30)
+    # the backward planes truncated to bf16
+    with pytest.raises(AssertionError):
+        S.cm_assert('truncated', None, emu_cross_merge(None, g, 34, 30, BF16, truncate=True)[1], None, g, 34, 30)
+    S.cm_assert('rounded', None, emu_cross_merge(None, g, 34, 30, BF16)[1], None, g, 34, 30)
+
+
+def test_cross_merge_cases_reach_the_kernels_they_are_listed_for():
+    """The dispatch of tamtr_cross_merge_fwd / _bwd as restated in tests/ss2d_cases.py, on every listed shape."""
+    assert all(S.cm_fwd_kernel(H, W, True) == 'cross_merge_fwd_kernel<bf16_t>' for H, W in S.CM_FWD_BF16_GENERIC)
+    assert all(S.cm_fwd_kernel(H, W, True) == 'cross_merge_fwd16_kernel' for H, W in S.CM_FWD16)
+    assert all(S.cm_bwd_kernel(H, W, True) == 'cross_merge_bwd16_kernel' for H, W in S.CM_BWD16)
+    assert all(S.cm_bwd_kernel(H, W, True) == 'cross_merge_bwd_kernel<bf16_t>' for H, W in S.CM_BWD_BF16_GENERIC + S.CM_BWD16_D32_ONLY)
+    assert S.cm_bwd_kernel(160, 160, True) == 'cross_merge_bwd16_kernel'          # the bench's first level
+    # none of the shapes of test_ss2d_bf16_planes_are_the_f32_kernels_rounded_once reaches the 32 x 32 backward
+    assert all(S.cm_bwd_kernel(H, W, True) == 'cross_merge_bwd_kernel<bf16_t>' for H, W in ((24, 40), (16, 24), (8, 16), (36, 28)))
+    assert S.cm_fwd_kernel(*S.CM_MISALIGNED_FWD, True, aligned=False) == 'cross_merge_fwd_kernel<bf16_t>'
+    assert S.cm_bwd_kernel(*S.CM_MISALIGNED_BWD, True, aligned=False) == 'cross_merge_bwd_kernel<bf16_t>'
+    assert S.ln_kernels(64, True) == ('ln_fwd_narrow_kernel<64>', 'ln_bwd_narrow_kernel<64>') and S.ln_kernels(128, True, aligned=False)[1] == 'ln_bwd_kernel<bf16_t, 128>'
+    vec = [s for s in S.DW_SHAPES if S.dw_vector_path(*s)]
+    assert vec == [(4, 4), (16, 16), (20, 12), (32, 16), (36, 20)] and not any(S.dw_vector_path(*s) for s in S.DW_ROUNDED_ONCE)
+
+
+# ---- depthwise front end
+def emu_dwconv(xz, D, w, bias, gout2, pdt, pad_replicate=False, col_taps_transposed=False, seam_double=False, no_z_term=False, bwd_no_bias=False):
+    """dwconv_cross_fwd / bwd_kernel: nine fp32 multiply-adds onto the bias, v / (1 + exp(-v)), both flattenings stored in the plane's
+    dtype; backward: the sum of the two planes times s (1 + z (1 - s)) with the conv recomputed, the transposed 3 x 3 for d(xi) (stored in
+    the activation dtype), d(weight) / d(bias) as one partial per (image, 16 x 16 tile) added in order.  Mutants: see the arguments."""
+    import torch.nn.functional as F
+    B, H, W = xz.shape[:3]
+    st_a = bf if xz.dtype == BF16 else (lambda t: t)
+    st_p = bf if pdt == BF16 else (lambda t: t)
+    xi = xz[..., :D].float().permute(0, 3, 1, 2)
+    xp = F.pad(xi, (1, 1, 1, 1), mode='replicate') if pad_replicate else F.pad(xi, (1, 1, 1, 1))
+    xp0 = F.pad(xi, (1, 1, 1, 1))
+    wf = w.view(D, 3, 3)
+    bc = bias if bias is not None else torch.zeros(D)
+
+    def conv(src, wk, b_):
+        acc = b_.view(1, D, 1, 1).expand(B, D, H, W).clone()
+        for ky in range(3):
+            for kx in range(3):
+                acc = acc + wk[:, ky, kx].view(1, D, 1, 1) * src[:, :, ky:ky + H, kx:kx + W]
+        return acc
+    z = conv(xp, wf, bc)
+    zc = conv(xp, wf.transpose(1, 2), bc) if col_taps_transposed else z
+    out = torch.stack([st_p(z / (1 + torch.exp(-z))).flatten(2), st_p(zc / (1 + torch.exp(-zc))).transpose(2, 3).flatten(2)], 1)
+    g2 = gout2.float()
+    g = g2[:, 0].view(B, D, H, W) + g2[:, 1].view(B, D, W, H).transpose(2, 3)
+    zb = conv(xp0, wf, torch.zeros(D) if bwd_no_bias else bc)
+    sg = 1 / (1 + torch.exp(-zb))
+    gz = g * (sg * (1 + (0 if no_z_term else zb * (1 - sg))))
+    gp = F.pad(gz, (1, 1, 1, 1))
+    dx = conv(gp, wf.flip(1, 2), torch.zeros(D))
+    part = []
+    for b in range(B):
+        for h0 in range(0, H, 16):
+            for w0 in range(0, W, 16):
+                e = 1 if seam_double else 0
+                hs, ws = slice(max(h0 - e, 0), min(h0 + 16 + e, H)), slice(max(w0 - e, 0), min(w0 + 16 + e, W))
+                gt = gz[b, :, hs, ws]
+                row = [(gt * xp0[b, :, hs.start + ky:hs.stop + ky, ws.start + kx:ws.stop + kx]).sum((1, 2)) for ky in range(3) for kx in range(3)]
+                part.append(torch.stack(row + [gt.sum((1, 2))], 1))
+    tot = part[0]
+    for p in part[1:]:
+        tot = tot + p
+    return out, st_a(dx.permute(0, 2, 3, 1)), tot[:, :9], (tot[:, 9] if bias is not None else None)
+
+
+def _dw_cases():
+    for H, W in S.DW_SHAPES:
+        for form in S.dw_forms(H, W):
+            for D in S.DW_D:
+                for bias in (True, False):
+                    yield H, W, form, D, bias, 0
+    (H, W), D, extra = S.DW_STRIDE_CASE
+    for form in S.DW_FORMS:
+        yield H, W, form, D, True, extra
+
+
+def test_dwconv_emulation_passes_every_case():
+    for H, W, form, D, bias, extra in _dw_cases():
+        xz, w, b, gout2 = S.dw_inputs(D, H, W, form, bias, extra)
+        S.dw_assert(f'emu dwconv[{form},{D},{H}x{W},{bias},{extra}]', emu_dwconv(xz, D, w, b, gout2, S.dw_dtypes(form)[1]), xz, D, w, b, gout2)
+
+
+def _old_dw_ok(got, ref, n):
+    """test_dwconv_silu_cross in bf16: out 1e-2 / 1e-2, dx 0.1 / 0.1, dw and db 0.1 relative + 0.1 sqrt(B H W) absolute."""
+    tol = {'out': (1e-2, 1e-2), 'dx': (0.1, 0.1), 'dw': (0.1, 0.1 * n ** 0.5), 'db': (0.1, 0.1 * n ** 0.5)}
+    return {k: R.old_close(t, ref[k][0], *tol[k]) for k, t in zip(tol, got)}
+
+
+def test_dwconv_mutants_fail():
+    """Every listed mutant misses a counted bound.  The old test's tolerances (bf16: 1e-2 forward, 0.1 backward) reject them as well at
+    this shape and with a unit-variance cotangent: O(1) and O(0.1) mistakes; what they could not see is the accuracy, not these."""
+    D, H, W, form = 32, 36, 20, 'bf16_f32planes'          # a tile seam along both axes, a partial last tile
+    xz, w, b, gout2 = S.dw_inputs(D, H, W, form, True)
+    ref = R.dwconv_silu_cross(xz, D, w, b, gout2)
+    ab = R.dwconv_bounds(ref['zmax'], S.DW_B, H, W, True, False)
+    n = S.DW_B * H * W
+    names = ('out', 'dx', 'dw', 'db')
+
+    def run(**kw):
+        return dict(zip(names, emu_dwconv(xz, D, w, b, gout2, torch.float32, **kw)))
+    assert all(_old_dw_ok(run().values(), ref, n).values())
+    # edge-replicate padding in the forward: O(1) on the border pixels; the old tolerance sees it too
+    m = run(pad_replicate=True)
+    assert not _old_dw_ok(m.values(), ref, n)['out']
+    rejected('replicate padding', m['out'], *ref['out'], *ab['out'])
+    # the taps transposed in the column-major pass only: plane 0 is right, plane 1 is not; the old tolerance sees it too
+    m = run(col_taps_transposed=True)
+    assert not _old_dw_ok(m.values(), ref, n)['out']
+    S_ = R.check('plane 0', m['out'][:, 0], ref['out'][0][:, 0], ref['out'][1][:, 0], *ab['out'], log=False)
+    assert S_ <= 1
+    rejected('taps transposed', m['out'][:, 1], ref['out'][0][:, 1], ref['out'][1][:, 1], *ab['out'])
+    # halo pixels counted into d(weight) / d(bias) on both sides of a tile seam
+    m = run(seam_double=True)
+    old = _old_dw_ok(m.values(), ref, n)
+    assert old['out'] and old['dx'] and not old['dw']          # (no bf16 shape of the old test has a seam; at this one its rule sees it)
+    rejected('seam counted twice', m['dw'], *ref['dw'], *ab['dw'])
+    rejected('seam counted twice', m['db'], *ref['db'], *ab['db'])
+    xs, ws_, bs, gs = S.dw_inputs(D, 16, 16, form, True)            # (no seam: the same kernel)
+    S.dw_assert('seam mutant on one tile', emu_dwconv(xs, D, ws_, bs, gs, torch.float32, seam_double=True), xs, D, ws_, bs, gs)
+    # SiLU' without its z (1 - s) term
+    m = run(no_z_term=True)
+    assert not _old_dw_ok(m.values(), ref, n)['dx']            # (a plain rejection)
+    rejected('SiLU\' without z (1 - s)', m['dx'], *ref['dx'], *ab['dx'])
+    # the bias left out of the backward's recomputed conv
+    m = run(bwd_no_bias=True)
+    assert not _old_dw_ok(m.values(), ref, n)['dx']            # (a plain rejection: the old rule accepts 9 elements in 10)
+    rejected('no bias in the recomputed conv', m['dx'], *ref['dx'], *ab['dx'])
+    rejected('no bias in the recomputed conv', m['dw'], *ref['dw'], *ab['dw'])
