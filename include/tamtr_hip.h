@@ -156,7 +156,8 @@ int tamtr_contrastive_logits_bwd(const float* g, const void* x, const float* w, 
  *      and any other y = x @ W^T + b of the head with N, K multiples of 128/64:
  *          Y[M,N] = X[M,K] @ W[N,K]^T + bias[N]        bf16 in, fp32 MFMA accumulate, bf16 out
  *      X bf16 [M,K] row-major, W bf16 [N,K] row-major (nn.Linear layout), bias f32 [N] or NULL, Y bf16 [M,N].
- *      Requires K % 64 == 0, N % 128 == 0; any M >= 1.
+ *      Requires K % 64 == 0, N % 128 == 0; any M >= 1; X, W, Y and bias 16-byte aligned (4 bytes do for the bias
+ *      where K is 128, 256 or 512 and N / 256 divides 32); TAMTR_EUNSUP otherwise, before any launch.
  */
 int tamtr_linear_bf16(const void* X, const void* W, const float* bias, void* Y, int M, int N, int K, void* stream);
 

@@ -722,6 +722,12 @@ __global__ __launch_bounds__(WS_T, 2) void linear_bf16_wstat_kernel(const bf16_t
 extern "C" int tamtr_linear_bf16(const void* X, const void* W, const float* bias, void* Y, int M, int N, int K, void* stream) {
   if (!X || !W || !Y || M <= 0 || N <= 0 || K <= 0) return TAMTR_EINVAL;
   if (K % BK || N % BN) return TAMTR_EUNSUP;
+  // Alignment: every kernel below reads X and W through 16-byte LDS-DMA requests or 16-byte vector loads and writes Y in 16-byte vector
+  // stores, at offsets that are multiples of 16 bytes from the base (K % 64 == 0, N % 128 == 0): the bases must be 16-byte aligned.
+  // Nothing the project can read promises that a global_load_lds_dwordx4 or a dwordx4 access off its natural alignment is served (the
+  // LDS-DMA form in particular), so such operands are refused here, before any launch; the callers in ops.py copy them to aligned memory.
+  // The bias is read as float4 by the full-row and tile kernels (16 bytes) and one float per lane by the W-stationary kernel (4 bytes).
+  if (((uintptr_t)X | (uintptr_t)W | (uintptr_t)Y) % 16 || (uintptr_t)bias % 4) return TAMTR_EUNSUP;
   // kernel choice (A/B switch TAMTR_GEMM = ws1 | tile), read once when the library is loaded - not per call
   static const int choice = [] { const char* e = getenv("TAMTR_GEMM"); return (e && e[0] == 't') ? 0 : 1; }();
   if (choice >= 1 && (K == 512 || K == 256 || K == 128) && N % WS_COLS == 0 && 32 % (N / WS_COLS) == 0) {
@@ -739,6 +745,7 @@ extern "C" int tamtr_linear_bf16(const void* X, const void* W, const float* bias
 #undef LAUNCH_WS
     return tamtr_launch_status();
   }
+  if ((uintptr_t)bias % 16) return TAMTR_EUNSUP;  // float4 reads of the bias in both kernels below
   if (N % TN == 0 && K % TK == 0) {  // full-row tiles: X read once (the value projection shape)
     const int mbl = (M + TM - 1) / TM, nbl = N / TN;
     if ((long long)mbl * nbl > 0x7fffffffLL) return TAMTR_EUNSUP;

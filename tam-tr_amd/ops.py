@@ -631,12 +631,20 @@ def bf16_of(p):
 KERNEL_EVENTS = {}
 
 
+def _a16(t):
+    """t, or a copy of it where it does not start on a 16-byte boundary (a contiguous view into the middle of a buffer): tamtr_linear_bf16
+    refuses such operands, its kernels move 16 bytes per request.  The caller keeps the result in a name until its launch is issued: a
+    copy dropped before that returns its block to the allocator, and the next copy made on the same stream is written into it first."""
+    return t if t is None or t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _linear_bf16_fwd(x2, w16, b32):
     """y [M, N] = x2 [M, K] w16[N, K]^T + b32 (or no bias: None), bf16 in and out, on the MFMA kernel: the forward launch of every node
     below and of _ValueProjMSDA, and the one launch that the measurement hook brackets."""
     M, K = x2.shape
     N = w16.shape[0]
     y = torch.empty(M, N, device=x2.device, dtype=torch.bfloat16)
+    x2, w16, b32 = _a16(x2), _a16(w16), _a16(b32)
     rec = KERNEL_EVENTS.get('tamtr_linear_bf16')
     if rec is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -654,7 +662,8 @@ def _linear_bf16_dx(g2, w16):
     N, K = w16.shape
     if K % 128 == 0 and N % 64 == 0:
         gx = torch.empty(g2.shape[0], K, device=g2.device, dtype=torch.bfloat16)
-        call('tamtr_linear_bf16', ptr(g2), ptr(_c(w16.t())), None, ptr(gx), g2.shape[0], K, N, stream_ptr())
+        g2, wt = _a16(g2), _a16(_c(w16.t()))
+        call('tamtr_linear_bf16', ptr(g2), ptr(wt), None, ptr(gx), g2.shape[0], K, N, stream_ptr())
         return gx
     return g2 @ w16
 

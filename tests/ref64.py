@@ -1,6 +1,6 @@
 """fp64 references with an error model for the bf16 hot-path kernels (tests/test_gpu_bf16_kernels.py, tests/test_ref64_host.py) and for the
 text gate and CPAM kernels in fp32 and bf16 (tests/test_gpu_gates_ref64.py), and for the LayerNorm, cross-merge and depthwise SS2D kernels
-(tests/test_gpu_ss2d_ref64.py).
+(tests/test_gpu_ss2d_ref64.py), and for the MFMA linear and x_proj kernels (tests/test_gpu_gemm_ref64.py).
 
 Every reference takes the operands exactly as the kernel sees them (bf16 tensors, fp32 side inputs), promotes them to float64 and
 computes on the CPU.  Next to each value it returns a magnitude: the same computation on absolute values.  check() then asserts,
@@ -64,6 +64,14 @@ def report(what, worst, a, b, n):
     if path:
         with open(path, 'a') as f:
             f.write(json.dumps({'check': what, 'worst': worst, 'a': a, 'b': b, 'n': int(n)}) + '\n')
+
+
+def note(text):
+    """With TAMTR_REF64_REPORT=<file> set, append a line of text (a fact about the run, not an assertion) to that file."""
+    path = os.environ.get('TAMTR_REF64_REPORT')
+    if path:
+        with open(path, 'a') as f:
+            f.write(json.dumps({'note': text}) + '\n')
 
 
 def old_close(got, ref, rtol, atol):
@@ -635,3 +643,159 @@ def dwconv_bounds(zmax, B, H, W, bf16_act, bf16_planes):
     b_sum = fp32_b(1 + 21 + 4 + B * dwconv_tiles(H, W))
     return {'out': (1 if bf16_planes else 0, fp32_b(9 + 1) + b_s), 'dx': (1 if bf16_act else 0, b_gz + fp32_b(9)),
             'dw': (0, b_gz + b_sum), 'db': (0, b_gz + b_sum)}
+
+
+# ------------------------------------------------------------------------------------------------ MFMA linear (csrc/gemm_bf16.hip)
+def linear(x, w, bias, gy=None):
+    """csrc/gemm_bf16.hip tamtr_linear_bf16 and the backward of ops.linear_bf16: y = x w^T + bias, and dx = gy w, dw = gy^T x, db = the
+    column sums of gy for the cotangent gy (None: forward only).
+
+    Operands as the kernel reads them: x bf16 [M, K], w bf16 [N, K], bias fp32 [N] or None, gy bf16 [M, N].  Rounding points: none on
+    purpose except the W-stationary kernel's bias split (linear_bounds).  Magnitudes: the same products on absolute values; y's includes
+    |bias|.  A NaN in a row of x makes the row of y NaN (every product of the row's sum is NaN or the sum holds one).
+    Returns {name: (value, magnitude)} for y, dx, dw, db, and 'bias': |bias| broadcast to y's shape (the term that carries the
+    W-stationary kernel's split residual)."""
+    X, W = _d(x), _d(w)
+    M, N = X.shape[0], W.shape[0]
+    b = _d(bias) if bias is not None else torch.zeros(N, dtype=torch.float64)
+    aX, aW = X.abs(), W.abs()
+    res = {'y': (X @ W.t() + b, aX @ aW.t() + b.abs()), 'bias': b.abs().expand(M, N)}
+    if gy is not None:
+        G = _d(gy)
+        aG = G.abs()
+        res.update({'dx': (G @ W, aG @ aW), 'dw': (G.t() @ X, aG.t() @ aX), 'db': (G.sum(0), aG.sum(0))})
+    return res
+
+
+BIAS_SPLIT = 2.0 ** -16   # see linear_bounds: what bf16(b) + bf16(b - bf16(b)) loses of an fp32 b, relative to |b|
+
+
+def linear_bounds(kernel, M, N, K):
+    """(a, b, c) of y for one of tamtr_linear_bf16's kernels ('wstat' | 'n512_k64' | 'tile'): |y - ref| <= a 2^-8 |ref| + b mag + c |bias|.
+
+    Every kernel forms K products of two bf16 values - each exact in fp32: 8 + 8 significant bits - and adds them into an fp32
+    accumulator with v_mfma_f32_32x32x16_bf16, 16 products per instruction.  Whether the instruction rounds each of its internal adds or
+    fewer is not documented where this project can read it; the count takes the worst case, one fp32 rounding per added product, whatever
+    the order: K roundings, each relative to a partial sum that the magnitude bounds.  y is stored in bf16: a = 1.
+      tile      the bias is added to the finished accumulator in fp32: K + 1.
+      n512_k64  the accumulator starts at the bias, which is then one more summand of the same chain: K.
+      wstat     the bias enters by one more MFMA as hi + lo, hi = bf16(b), lo = bf16(b - hi), against two ones: two more products in the
+                chain (the instruction's other 14 are exact zeros): K + 2.  The split itself: |b - hi| <= 2^-8 |b| (round to nearest, 8
+                significant bits), b - hi is exact in fp32 (it is the part of b's significand below hi's last bit), and
+                |(b - hi) - lo| <= 2^-8 |b - hi| <= 2^-16 |b|.  That residual is relative to |bias| alone, not to the products: c = 2^-16.
+    dx on the same kernels (N and K exchanged, no bias) takes the same figures."""
+    n = {'tile': K + 1, 'n512_k64': K, 'wstat': K + 2}[kernel]
+    return 1, fp32_b(n), (BIAS_SPLIT if kernel == 'wstat' else 0.0)
+
+
+def linear_check(what, got, ref, kernel, K):
+    """y (or dx: bias None) of one MFMA kernel against linear()'s result: check() on the combined tensor b mag + c |bias| with b = 1."""
+    a, b, c = linear_bounds(kernel, got.shape[0], got.shape[1], K)
+    return check(what, got, ref['y'][0], b * ref['y'][1] + c * ref['bias'], a, 1.0)
+
+
+def slab_sum_chain(R, C):
+    """The longest chain of fp32 additions behind one output of csrc/fold.hip tamtr_slab_sum_rows over R rows of C columns.  R <= 32: a
+    thread adds its R rows in sequence.  Else 1024 threads = CG column groups x RG row groups (CG = 64, halved while CG / 2 still covers
+    the C / 4 column quads): a thread adds its ceil(R / RG) rows, then the row groups that hold any are added in index order."""
+    if R <= 32:
+        return R
+    CG = 64
+    while CG > 1 and CG // 2 >= C // 4:
+        CG //= 2
+    RG = 1024 // CG
+    return -(-R // RG) + min(RG, R)
+
+
+def colsum_chain(M, N, streams):
+    """The chain behind one element of ops.colsum of a bf16 [M, N] matrix.  Direct (streams False): slab_sum over the M rows.  Streaming
+    (csrc/fold.hip colsum_bf16_kernel): min(ceil(M / 64), 2048) workgroups of ceil(M / workgroups) rows each; 256 / (N / 8) row lanes per
+    column group, a lane adds its ceil(rows / lanes) rows in sequence, the lanes are added in order, slab_sum adds the workgroups' rows."""
+    if not streams:
+        return slab_sum_chain(M, N)
+    nblk = min((M + 63) // 64, 2048)
+    rows = -(-M // nblk)
+    lanes = 256 // (N // 8)
+    return -(-rows // lanes) + lanes + slab_sum_chain(nblk, N)
+
+
+def linear_grad_bounds(M, N, K, S, bmm_f32_out=True, streams=False):
+    """{name: (a, b)} for what ops.linear_bf16's backward leaves to the library and to the ordered sums.
+    dx (library GEMM, where the MFMA kernel does not take the shape): N products in fp32, stored in bf16: (1, N).
+    db: exact bf16 values added in fp32 along the chain that the kernels form, counted in colsum_chain (41 at 8193 x 256 streaming, 79 at
+    1000 x 512 direct): (0, chain).  At these counts one dropped row of gy (an element of about 1 against a magnitude of M) misses the bound.
+    dw, S = 1 slice: one library GEMM with a bf16 result, widened afterwards: (1, M).  S > 1: S batched library products of M / S rows with
+    fp32 results, added in order by slab_sum over S rows of N K columns: (0, M / S + slab_sum_chain(S, N K)); where the build's bmm has no
+    fp32 output the partials are bf16 and each carries 2^-8 of its magnitude.  The order inside the library's product is not this
+    project's to read, so its M / S products count as M / S roundings, the bound of any order; with the worst-case magnitude that is too
+    wide to see ONE dropped row of dw at M / S = 2050 (it sees a dropped slice: tests/test_ref64_host.py) - single rows of dw are held
+    by the S = 1 cases (a = 1 on |ref|) and by test_linear_bf16_kernel."""
+    dw = (1, fp32_b(M)) if S == 1 else (0, fp32_b(M // S + slab_sum_chain(S, N * K)) + (0 if bmm_f32_out else U8))
+    return {'dx': (1, fp32_b(N)), 'db': (0, fp32_b(colsum_chain(M, N, streams))), 'dw': dw}
+
+
+# ------------------------------------------------------------------------------------------------ x_proj of SS2D (csrc/xproj.hip)
+XP_N = 16            # d_state
+XP_SLICE = 1024      # pixels per partial tile of the weight gradient
+
+
+def xproj_wcat(wx):
+    """x_proj_weight [4, C, D] -> [2, 2C, D] fp64: the rows [W_i ; W_(i+2)] of stored copy i, rounded to bf16 as ops.xproj_pack_weight does."""
+    w = wx.detach().cpu()
+    return torch.stack([torch.cat([w[0], w[2]], 0), torch.cat([w[1], w[3]], 0)]).bfloat16().double()
+
+
+def xproj_rows(dtr, Bs, Cs):
+    """[B, 4, R | 16 | 16, L] x 3 -> [B, 2, 2C, L]: copy i's rows [dtr_i ; B_i ; C_i ; dtr_(i+2) ; B_(i+2) ; C_(i+2)] (xp_row's order)."""
+    return torch.stack([torch.cat([dtr[:, i], Bs[:, i], Cs[:, i], dtr[:, i + 2], Bs[:, i + 2], Cs[:, i + 2]], 1) for i in range(2)], 1)
+
+
+def xproj(u2, wx, R, gdtr, gB, gC, gu, plane_bf16=None):
+    """csrc/xproj.hip: per image and stored copy i, OUT_i [2C, L] = Wcat_i [2C, D] U_i [D, L] split into dtr / Bs / Cs of directions i and
+    i + 2; d/d(u2)[b, i] = gu[b, i] + gu[b, i + 2] + Wcat_i^T G_i; dWcat_i = sum over images and pixels of G_i U_i^T.
+
+    u2 [B, 2, D, L] and gu [B, 4, D, L] in the plane dtype (fp32 or bf16), wx fp32 [4, C, D], gdtr [B, 4, R, L], gB, gC [B, 4, 16, L] fp32.
+    Rounding points, from the source, each applied here exactly (round to nearest even, what v_cvt_pk_bf16_f32 does), so that they cost
+    no term of the bound: W is bf16 (the packed weight); u is rounded to bf16 in registers (exact for bf16 planes); G is rounded to bf16
+    in registers.  What remains:
+      forward   D exact products in an fp32 chain, the result rounded to bf16 and stored as fp32: a = 1, b = fp32_b(D + 1); every stored
+                value is a bf16 value.
+      d/d(u2)   2C products in an fp32 chain (fp32_b(2C) on the product's magnitude m), the product p rounded to bf16 (2^-8 of the fp32
+                product, which is within fp32_b(2C) m of |p|: 2^-8 |p| and one more count on m), then gu_i + gu_(i+2) + p in fp32: two
+                roundings on |gu_i| + |gu_(i+2)| + m.  The returned magnitude is that whole sum,
+                2^-8 |p| + fp32_b(2C + 1) m + fp32_b(2) (|gu_i| + |gu_(i+2)| + m), to be used with b = 1; bf16 planes round the sum once
+                more: a = 1, fp32 planes a = 0.
+      dWcat     fp32 partial tiles per (image, 1 024-pixel slice): min(L, 1024) products in a chain; the ordered slab_sum over
+                B * ceil(L / 1024) rows: a = 0, b = fp32_b(min(L, 1024) + B * slices), as dwconv_bounds counts its partials.
+    Returns {name: (value, magnitude)} for dtr, Bs, Cs ([B, 4, R | 16 | 16, L]), gu2 [B, 2, D, L], dw [2, 2C, D]."""
+    assert plane_bf16 is None or (u2.dtype == gu.dtype == (torch.bfloat16 if plane_bf16 else torch.float32)), 'u2 and gu are in the plane dtype'
+    B, _, D, L = u2.shape
+    C = R + 2 * XP_N
+    Wc = xproj_wcat(wx)                                             # [2, 2C, D]
+    U = u2.detach().cpu().bfloat16().double()                       # the register rounding (exact for bf16 planes)
+    out, m_out = torch.einsum('imd,bidl->biml', Wc, U), torch.einsum('imd,bidl->biml', Wc.abs(), U.abs())
+
+    def split(t):                                                   # [B, 2, 2C, L] -> dtr, Bs, Cs
+        h = t.view(B, 2, 2, C, L)                                   # [b, i, half (direction i | i + 2), c, l]
+        d4 = h.permute(0, 2, 1, 3, 4).reshape(B, 4, C, L)           # direction = 2 half + i
+        return d4[:, :, :R], d4[:, :, R:R + XP_N], d4[:, :, R + XP_N:]
+    res = {n: (v.contiguous(), m.contiguous()) for n, v, m in zip(('dtr', 'Bs', 'Cs'), split(out), split(m_out))}
+    G = xproj_rows(gdtr.detach().cpu(), gB.detach().cpu(), gC.detach().cpu()).bfloat16().double()      # [B, 2, 2C, L]
+    g = _d(gu)
+    prod, m_prod = torch.einsum('imd,biml->bidl', Wc, G), torch.einsum('imd,biml->bidl', Wc.abs(), G.abs())
+    val = g[:, :2] + g[:, 2:] + prod
+    m_sum = g[:, :2].abs() + g[:, 2:].abs() + m_prod
+    res['gu2'] = (val, U8 * prod.abs() + fp32_b(2 * C + 1) * m_prod + fp32_b(2) * m_sum)
+    res['prod'] = prod
+    res['dw'] = (torch.einsum('biml,bidl->imd', G, U), torch.einsum('biml,bidl->imd', G.abs(), U.abs()))
+    return res
+
+
+def xproj_slices(L):
+    return (L + XP_SLICE - 1) // XP_SLICE
+
+
+def xproj_bounds(B, D, L, plane_bf16):
+    """{name: (a, b)} for xproj()'s outputs; the counts are written out in xproj()'s docstring."""
+    fwd = (1, fp32_b(D + 1))
+    return {'dtr': fwd, 'Bs': fwd, 'Cs': fwd, 'gu2': (1 if plane_bf16 else 0, 1.0), 'dw': (0, fp32_b(min(L, XP_SLICE) + B * xproj_slices(L)))}

@@ -772,3 +772,282 @@ def test_dwconv_mutants_fail():
     assert not _old_dw_ok(m.values(), ref, n)['dx']            # (a plain rejection: the old rule accepts 9 elements in 10)
     rejected('no bias in the recomputed conv', m['dx'], *ref['dx'], *ab['dx'])
     rejected('no bias in the recomputed conv', m['dw'], *ref['dw'], *ab['dw'])
+
+
+# ================================================================================================ MFMA linear and x_proj (tests/gemm_cases.py)
+import gemm_cases as GM
+
+MUTANT_TABLE = []      # (family, mutant, passes the old rule, passes the new rule)
+
+
+def _report_mutants(family):
+    """The per-mutant old-rule / new-rule table (profiles/r11_gemm_ref64.txt), written where TAMTR_REF64_REPORT is set."""
+    for fam, name, old, new in MUTANT_TABLE:
+        if fam == family:
+            R.note(f'mutant [{fam}] {name}: old rule {"passes" if old else "fails"}, new rule {"passes" if new else "fails"}')
+
+
+def _new_rule(fn):
+    try:
+        fn()
+        return True
+    except AssertionError:
+        return False
+
+
+def emu_linear(x, w, b, kernel, drop_last_k=False, double_round=False, lose_lo=False, tail_from_m2=False, transpose_tile=False):
+    """tamtr_linear_bf16: exact products of bf16 values added in fp32 (torch's order: any order is within the bound), the bias as the
+    kernel adds it - in fp32 (tile, n512_k64) or as bf16(b) + bf16(b - bf16(b)) (wstat) - and one rounding to bf16.  Mutants: the last
+    k-step of 64 left out; the accumulator rounded to bf16 before the bias is added and again after; the bias's lo half lost; the last
+    row computed from row M - 2; the first 32 x 32 tile transposed."""
+    xf, wf = x.float(), w.float()
+    M = xf.shape[0]
+    acc = (xf[:, :-64] @ wf[:, :-64].t()) if drop_last_k else xf @ wf.t()
+    if tail_from_m2:
+        acc[M - 1] = acc[M - 2]
+    if b is None:
+        bv = torch.zeros(wf.shape[0])
+    elif kernel == 'wstat':
+        hi = bf(b)
+        bv = hi if lose_lo else hi + bf(b - hi)
+    else:
+        bv = b
+    y = (bf(acc) + bv if double_round else acc + bv).bfloat16()
+    if transpose_tile:
+        y[:32, :32] = y[:32, :32].t().clone()
+    return y
+
+
+def test_linear_cases_reach_the_kernels_they_are_listed_for():
+    """The dispatch of tamtr_linear_bf16 and of ops.linear_bf16's backward as restated in tests/gemm_cases.py."""
+    for kernel, M, N, K, _, _ in GM.LINEAR_CASES:
+        assert GM.linear_kernel(N, K) == kernel
+    assert {k for k, *_ in GM.LINEAR_CASES} == {'wstat', 'n512_k64', 'tile'}
+    assert all(sum(1 for k, *_r in GM.LINEAR_CASES if k == kn and not _r[3]) == 1 for kn in ('wstat', 'n512_k64', 'tile'))     # one without bias each
+    for M, N, K, kdx, streams, S in GM.GRAD_CASES:
+        assert (GM.dx_kernel(N, K), GM.colsum_streams(M, N), GM.split_count(M)) == (kdx, streams, S)
+    assert {c[3] for c in GM.GRAD_CASES} == {'wstat', 'n512_k64', 'tile', 'lib'}
+    assert {c[4] for c in GM.GRAD_CASES} == {True, False} and {c[5] > 1 for c in GM.GRAD_CASES} == {True, False}
+    # the six shapes of test_linear_bf16_kernel: four on wstat, two on the tile kernel, none on the full-row kernel
+    old = [(1000, 512, 512), (2048, 128, 64), (77, 256, 192), (8193, 256, 256), (33, 1024, 128), (4999, 2048, 512)]
+    assert sorted(GM.linear_kernel(N, K) for _, N, K in old) == ['tile', 'tile'] + ['wstat'] * 4
+    assert GM.linear_kernel(1536, 256) == 'n512_k64' and GM.linear_kernel(1536, 512) == 'n512_k64' and GM.linear_kernel(512, 512) == 'wstat'
+    B, L, N, K = GM.ZERO_ROWS_CASE
+    assert GM.linear_kernel(N, K) == 'n512_k64'
+    assert [GM.xproj_ks_mb(c[3]) for c in GM.XPROJ_CASES] == GM.XPROJ_KS_MB
+
+
+@pytest.mark.parametrize('kernel,M,N,K,bias,what', GM.LINEAR_CASES, ids=GM.LINEAR_IDS)
+def test_linear_emulation_passes(kernel, M, N, K, bias, what):
+    x, w, b, _ = GM.linear_inputs(M, N, K, bias)
+    GM.linear_assert(f'emu linear[{kernel},{M}x{N}x{K}]', emu_linear(x, w, b, kernel), kernel, M, N, K, bias)
+
+
+def test_linear_emulation_passes_the_poison_and_gradient_assertions():
+    for kernel, M, N, K, inf_row in GM.POISON_CASES:
+        x, w, b = GM.poison_inputs(M, N, K, inf_row)
+        GM.poison_assert(f'emu linear[{kernel}]', emu_linear(x, w, b, kernel), kernel, M, N, K, inf_row)
+        leak = emu_linear(x, w, b, kernel)
+        leak[inf_row - 1] = float('nan')                      # the poison in a third row
+        with pytest.raises(AssertionError):
+            GM.poison_assert('leak', leak, kernel, M, N, K, inf_row)
+        leak = emu_linear(x, w, b, kernel)
+        col = int(torch.isinf(leak[inf_row].float()).nonzero()[0])
+        leak[inf_row, col] = float('nan')                     # the last row's NaN in one column of the Inf's row
+        with pytest.raises(AssertionError, match='pattern of row'):
+            GM.poison_assert('NaN inside the Inf row', leak, kernel, M, N, K, inf_row)
+        leak = emu_linear(x, w, b, kernel)
+        leak[inf_row, col] = -leak[inf_row, col]              # an Inf of the wrong sign
+        with pytest.raises(AssertionError, match='pattern of row'):
+            GM.poison_assert('sign flipped inside the Inf row', leak, kernel, M, N, K, inf_row)
+    for M, N, K, kdx, _, S in GM.GRAD_CASES[:4]:
+        x, w, b, gy = GM.linear_inputs(M, N, K, True, True)
+        g, xf, wf = gy.float(), x.float(), w.float()
+        dw = (g.t() @ xf).bfloat16().float()                   # S = 1: the library's bf16 result, widened
+        GM.grads_assert(f'emu linear_bf16[{M}x{N}x{K}]', (g @ wf).bfloat16(), dw, g.sum(0), M, N, K, True)
+    # zero_rows: y and dx of the masked input, dw as the difference of two rounded products
+    B, L, N, K = GM.ZERO_ROWS_CASE
+    x, w, b, gy, idx, xz = GM.zero_rows_inputs()
+    y = emu_linear(xz.reshape(B * L, K), w, b, 'n512_k64').view(B, L, N)
+    g, wf = gy.float(), w.float()
+    dx = (g @ wf).bfloat16()
+    dx[:, idx] = 0
+    dw = bf(g.reshape(B * L, N).t() @ x.float().reshape(B * L, K)) - bf(g[:, idx].reshape(-1, N).t() @ x.float()[:, idx].reshape(-1, K))
+    GM.zero_rows_assert('emu zero_rows', y, dx, dw, g.sum((0, 1)), 'n512_k64', True)
+    with pytest.raises(AssertionError):                       # the masked rows left in dw
+        GM.zero_rows_assert('mutant zero_rows, masked rows left in dw:', y, dx, bf(g.reshape(B * L, N).t() @ x.float().reshape(B * L, K)), g.sum((0, 1)), 'n512_k64', True)
+
+
+def test_linear_emulation_is_exact_where_no_addition_rounds_and_mutants_are_not():
+    for kernel, M, N, K in GM.EXACT_CASES:
+        if M > 2000:
+            continue                                           # (the same kernels at the smaller shapes: the host run stays short)
+        x, w, b = GM.exact_inputs(M, N, K)
+        n_tie = GM.exact_assert(f'emu linear[{kernel},exact]', emu_linear(x, w, b, kernel), kernel, M, N, K)
+        for kw in ({'drop_last_k': True}, {'transpose_tile': True}) + (({'lose_lo': True},) if kernel == 'wstat' else ()):
+            with pytest.raises(AssertionError):
+                GM.exact_assert('mutant', emu_linear(x, w, b, kernel, **kw), kernel, M, N, K)
+        if kernel == 'wstat':                                  # the lost lo half changes exactly the ties
+            assert int((emu_linear(x, w, b, kernel, lose_lo=True) != GM.exact_want(M, N, K)).sum()) == n_tie
+
+
+def test_linear_sums_emulation_passes_and_dropped_rows_fail():
+    """db on the streaming kernel's chain and dw in slices: the emulations pass; a column sum that leaves out the one-row tail block and
+    a dw that leaves out its last slice miss the counted bounds."""
+    M, N, K = 8193, 256, 256                                   # db: 129 workgroups of 64 rows, the last one holds one row
+    assert GM.colsum_streams(M, N) and R.colsum_chain(M, N, True) == 8 + 8 + 9 + 16
+    g = GM.linear_inputs(M, N, K, True, True)[3].float()
+    ref, ab = GM.linear_ref(M, N, K, True, True), R.linear_grad_bounds(M, N, K, 1, True, True)
+    R.check('emu db (streaming chain)', g.sum(0), *ref['db'], *ab['db'])
+    rejected('db without the one-row tail block', g[:-1].sum(0), *ref['db'], *ab['db'])
+    M, N, K = 1000, 512, 512
+    assert R.colsum_chain(M, N, False) == 63 + 16
+    g = GM.linear_inputs(M, N, K, True, True)[3].float()
+    rejected('db without the last row (direct slab_sum)', g[:-1].sum(0), *GM.linear_ref(M, N, K, True, True)['db'], *R.linear_grad_bounds(M, N, K, 1)['db'])
+    M, N, K = 8200, 2048, 64                                   # dw in 4 slices of 2050 rows, fp32 partials added in order
+    S = GM.split_count(M)
+    x, _, _, gy = GM.linear_inputs(M, N, K, True, True)
+    parts = [gy.float()[i * (M // S):(i + 1) * (M // S)].t() @ x.float()[i * (M // S):(i + 1) * (M // S)] for i in range(S)]
+    ref, ab = GM.linear_ref(M, N, K, True, True), R.linear_grad_bounds(M, N, K, S)
+    R.check('emu dw (S = 4)', parts[0] + parts[1] + parts[2] + parts[3], *ref['dw'], *ab['dw'])
+    rejected('dw without its last slice', parts[0] + parts[1] + parts[2], *ref['dw'], *ab['dw'])
+
+
+def _old_linear(y, ref):
+    """test_linear_bf16_kernel's forward rule: rtol 2^-8, atol 1e-3."""
+    return R.old_close(y.float(), ref['y'][0], 2 ** -8, 1e-3)
+
+
+def test_linear_mutants_fail():
+    """Each mutant misses the counted bound; the old rule (2^-8 relative + 1e-3) accepts the dropped k-step of small products and the
+    lost lo half of the bias."""
+    # the last k-step dropped, its products small: the last 64 columns of x scaled by 2^-12 (exact in bf16)
+    kernel, M, N, K = 'n512_k64', 130, 512, 192
+    x, w, b, _ = GM.linear_inputs(M, N, K)
+    xs = x.clone()
+    xs[:, -64:] = (xs[:, -64:].float() * 2.0 ** -12).bfloat16()
+    ref = R.linear(xs, w, b)
+    R.linear_check('emu, small last k-step', emu_linear(xs, w, b, kernel).float(), ref, kernel, K)
+    m = emu_linear(xs, w, b, kernel, drop_last_k=True)
+    old, new = _old_linear(m, ref), _new_rule(lambda: R.linear_check('dropped k-step', m.float(), ref, kernel, K))
+    MUTANT_TABLE.append(('linear', 'last k-step of 64 dropped (products of 2^-12)', old, new))
+    assert old and not new
+    # the bias rounded to bf16 once on the W-stationary model; |b| < 0.5, where bf16(b) is within 2^-10 < 1e-3 of b
+    kernel, M, N, K = 'wstat', 33, 2048, 128
+    x, w, _, _ = GM.linear_inputs(M, N, K)
+    b = urnd((N,), 5, -0.49, 0.49)
+    ref = R.linear(x, w, b)
+    R.linear_check('emu, |b| < 0.5', emu_linear(x, w, b, kernel).float(), ref, kernel, K)
+    m = emu_linear(x, w, b, kernel, lose_lo=True)
+    old, new = _old_linear(m, ref), _new_rule(lambda: R.linear_check('lo lost', m.float(), ref, kernel, K))
+    MUTANT_TABLE.append(('linear', 'wstat bias rounded to bf16 once (lo lost), |b| < 0.5', old, new))
+    assert old and not new
+    b1 = GM.linear_inputs(M, N, K)[2]                          # the cases' own bias, |b| of about 1: the old rule may see some elements
+    ref1 = GM.linear_ref(M, N, K)
+    m = emu_linear(x, w, b1, kernel, lose_lo=True)
+    new = _new_rule(lambda: R.linear_check('lo lost', m.float(), ref1, kernel, K))
+    MUTANT_TABLE.append(('linear', 'wstat bias rounded to bf16 once (lo lost), |b| ~ 1', _old_linear(m, ref1), new))
+    assert not new
+    # the other three, on the tile model
+    kernel, M, N, K = 'tile', 77, 256, 192
+    x, w, b, _ = GM.linear_inputs(M, N, K)
+    ref = GM.linear_ref(M, N, K)
+    for name, kw in (('accumulator rounded to bf16, bias added, rounded again', {'double_round': True}),
+                     ('tail row taken from row M - 2', {'tail_from_m2': True}), ('one 32 x 32 tile transposed', {'transpose_tile': True})):
+        m = emu_linear(x, w, b, kernel, **kw)
+        new = _new_rule(lambda: R.linear_check(name, m.float(), ref, kernel, K))
+        MUTANT_TABLE.append(('linear', name, _old_linear(m, ref), new))
+        assert not new, name
+    _report_mutants('linear')
+
+
+# ---- x_proj
+def emu_xproj(i, R_, plane_bf16, no_round=False, pad_row=False, swap_B_dirs=False, drop_second_slice=False):
+    """csrc/xproj.hip in fp32 on the CPU with the kernels' rounding points and padding: the packed weights zero-padded to MB * 32 rows /
+    KS * 16 columns, u and the gradient rows rounded to bf16, the forward and the d/d(u2) product rounded to bf16, the fold in fp32, the
+    weight gradient as per-(image, 1 024-pixel slice) partial tiles of MB * 32 rows added in order.  Mutants: the forward not rounded; a
+    padding column of wT non-zero (2^-10), met by a padding row of G that re-reads a real row instead of being zero (the clamp the dW
+    kernel uses for its loads, without its zeroing); the B rows of directions i and i + 2 exchanged; the second dW slice left out."""
+    u2, wx, gdtr, gB, gC, gu = (i[k] for k in ('u2', 'wx', 'gdtr', 'gB', 'gC', 'gu'))
+    B, _, D, L = u2.shape
+    C = R_ + 2 * R.XP_N
+    KS, MB = GM.xproj_ks_mb(R_)
+    wc = torch.stack([torch.cat([wx[0], wx[2]], 0), torch.cat([wx[1], wx[3]], 0)]).bfloat16().float()       # [2, 2C, D]
+    wcat = torch.nn.functional.pad(wc, (0, 0, 0, MB * 32 - 2 * C))
+    wT = torch.nn.functional.pad(wc.transpose(1, 2), (0, KS * 16 - 2 * C))                                   # [2, D, KP]
+    U = bf(u2.float())
+    out = torch.einsum('imd,bidl->biml', wcat, U)[:, :, :2 * C]
+    if not no_round:
+        out = bf(out)
+    h = out.view(B, 2, 2, C, L).permute(0, 2, 1, 3, 4).reshape(B, 4, C, L)
+    got = {'dtr': h[:, :, :R_].contiguous(), 'Bs': h[:, :, R_:R_ + R.XP_N].contiguous(), 'Cs': h[:, :, R_ + R.XP_N:].contiguous()}
+    if swap_B_dirs:
+        got['Bs'] = got['Bs'][:, [2, 3, 0, 1]].contiguous()
+    G = bf(R.xproj_rows(gdtr, gB, gC))                                                                        # [B, 2, 2C, L]
+    Gk = torch.nn.functional.pad(G, (0, 0, 0, KS * 16 - 2 * C))
+    if pad_row:
+        assert KS * 16 > 2 * C
+        wT = wT.clone()
+        wT[:, :, 2 * C] = 2.0 ** -10
+        Gk[:, :, 2 * C] = G[:, :, 0]
+    g = gu.float()
+    s = g[:, :2] + g[:, 2:] + bf(torch.einsum('idm,biml->bidl', wT, Gk))
+    got['gu2'] = s.bfloat16() if plane_bf16 else s
+    Gm = torch.nn.functional.pad(G, (0, 0, 0, MB * 32 - 2 * C))
+    nsl = R.xproj_slices(L)
+    part = torch.zeros(B * nsl, 2, MB * 32, D)
+    for b in range(B):
+        for sl in range(nsl):
+            if drop_second_slice and sl == 1:
+                continue
+            px = slice(sl * R.XP_SLICE, min((sl + 1) * R.XP_SLICE, L))
+            part[b * nsl + sl] = torch.einsum('iml,idl->imd', Gm[b, :, :, px], U[b, :, :, px])
+    assert float(part[:, :, 2 * C:].abs().max() if MB * 32 > 2 * C else 0) == 0, 'the accumulator rows beyond 2C are exact zeros'
+    got['part'] = part[:, :, :2 * C].contiguous()
+    tot = got['part'][0]
+    for r in got['part'][1:]:
+        tot = tot + r
+    got['dw'] = tot
+    return got
+
+
+@pytest.mark.parametrize('planes', ['fp32', 'bf16'])
+@pytest.mark.parametrize('B,D,L,R_,what', GM.XPROJ_CASES, ids=[f'{c[0]}x{c[1]}x{c[2]}-R{c[3]}' for c in GM.XPROJ_CASES])
+def test_xproj_emulation_passes(B, D, L, R_, what, planes):
+    pb = planes == 'bf16'
+    GM.xproj_assert(f'emu xproj[{planes},{B}x{D}x{L},R={R_}]', emu_xproj(GM.xproj_inputs(B, D, L, R_, pb), R_, pb), B, D, L, R_, pb)
+
+
+def _old_xproj(got, ref, i):
+    """test_xproj_kernels_vs_fp32_products_of_the_same_bf16_operands: per stored copy, forward 8e-3 relative + 8e-3 max|ref|; d/d(u2) 1e-6
+    relative + 8e-3 max|product|; dWcat 1e-4 relative + 1e-4 max|ref|."""
+    ok = {'fwd': True, 'gu2': True, 'dw': True}
+    rows_g = R.xproj_rows(got['dtr'], got['Bs'], got['Cs'])
+    rows_r = R.xproj_rows(ref['dtr'][0], ref['Bs'][0], ref['Cs'][0])
+    for c in range(2):
+        ok['fwd'] &= R.old_close(rows_g[:, c], rows_r[:, c], 8e-3, 8e-3 * float(rows_r[:, c].abs().max()))
+        ok['gu2'] &= R.old_close(got['gu2'][:, c].float(), ref['gu2'][0][:, c], 1e-6, 8e-3 * float(ref['prod'][:, c].abs().max()))
+        ok['dw'] &= R.old_close(got['dw'][c], ref['dw'][0][c], 1e-4, 1e-4 * float(ref['dw'][0][c].abs().max()))
+    return ok
+
+
+def test_xproj_mutants_fail():
+    """Each mutant misses its assertion; the old rule accepts the unrounded forward and the non-zero padding column."""
+    def run(case, key, name, **kw):
+        B, D, L, R_ = case
+        i, ref = GM.xproj_inputs(B, D, L, R_, False), GM.xproj_ref(B, D, L, R_, False)
+        m = emu_xproj(i, R_, False, **kw)
+        assert all(_old_xproj(emu_xproj(i, R_, False), ref, i).values())
+        old = _old_xproj(m, ref, i)[key]
+        new = _new_rule(lambda: GM.xproj_assert(name, m, B, D, L, R_, False))
+        MUTANT_TABLE.append(('xproj', name, old, new))
+        return old, new
+    old, new = run((2, 256, 40, 8), 'fwd', 'forward not rounded to bf16', no_round=True)
+    assert old and not new
+    old, new = run((2, 256, 8, 5), 'gu2', 'a padding column of wT non-zero (2^-10) against a padding row of G that re-reads row 0', pad_row=True)
+    assert old and not new
+    old, new = run((2, 256, 40, 8), 'fwd', 'B rows of directions i and i + 2 exchanged', swap_B_dirs=True)
+    assert not new
+    old, new = run((2, 256, 1032, 16), 'dw', 'second dW slice (8 pixels) dropped', drop_second_slice=True)
+    assert not new
+    _report_mutants('xproj')
