@@ -35,8 +35,8 @@ extern "C" {
 #define TAMTR_ELAUNCH (-3)
 
 /* ABI version, bumped on any signature change.  The CLIP text tower's entries at the end of this file (tamtr_text_embed, tamtr_linear_f32,
- * tamtr_text_pool_project) and tamtr_val_confusion are new symbols only: no existing signature changed, so the version stayed at 36 when
- * they were added. */
+ * tamtr_text_pool_project), tamtr_val_confusion and tamtr_val_ap_curves / tamtr_val_ap_tile are new symbols only: no existing signature
+ * changed, so the version stayed at 36 when they were added. */
 int tamtr_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -613,6 +613,38 @@ int tamtr_val_postprocess_match(const void* preds, int dtype, int B, int nq, int
  *  TAMTR_EUNSUP: nq > 512. */
 int tamtr_val_confusion(const float* predn, const int32_t* counts, int B, int nq, int nc, const float* lab_cls, const float* lab_box,
                         const int32_t* lab_off, int M, const float* scale, float cm_conf, float iou_thres, int32_t* matrix, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * The validator's AP per class and IoU threshold and its precision / recall / PR curves in one launch.  Replaces compute_ap and the
+ * per-class loop of ap_per_class (ultralytics/utils/metrics.py:999-1029,1073-1127) on rows that never leave the device.
+ *      conf     f32 [N]        scores of all rows of the run, SORTED by class ascending, then score descending, then original order
+ *      correct  u8  [N, 10]    the rows' hits per IoU threshold, in the same order
+ *      seg_off  i32 [nc + 1]   rows seg_off[c] .. seg_off[c + 1] are class c's (read on the device, clamped to 0 .. N); rows before
+ *                              seg_off[0] and after seg_off[nc] (dead rows) belong to no class
+ *      lab_cls  f32 [M]        the run's label classes, in any order (NULL only when M == 0)
+ *      px f64 [1000], grid f64 [101]   numpy's linspace(0, 1, 1000) and linspace(0, 1, 101), uploaded (not recomputed: i / 999.0 has
+ *                              other bits)
+ *      tpc_scratch i32 [10, N], env_scratch f64 [10, N]    scratch, contents undefined before and after
+ *      ap f64 [nc, 10]; p_curve, r_curve, pr_curve f64 [nc, 1000]; n_gt, n_pred i32 [nc]    dense over [0, nc), fully written
+ *  The rule is engine.ap_per_class(stable=True, curves=True), all in fp64, one rounding per operation.  n_gt[c] = the labels with
+ *  float(c) == class (labels outside [0, nc) are counted nowhere; the host rule would give them a zero row of their own);
+ *  n_pred[c] = k = seg_off[c + 1] - seg_off[c].  With n = n_gt[c], rows i = 0 .. k - 1 and threshold t: tpc[i] = inclusive count of
+ *  correct[., t]; recall = tpc / (n + 1e-16); precision = tpc / (i + 1).  A class with n == 0 or k == 0 keeps all-zero rows.
+ *   ap        knots (0, 1), the curve, (1, 0); envelope = suffix maximum of precision; y = interp(grid, knot recall, envelope);
+ *             ap = h * (sum y - 0.5 * (y[0] + y[100])), h = grid[1] - grid[0], the sum serial over g = 0 .. 100.
+ *   r_curve   interp(-px, -conf, recall[:, 0], left = 0); p_curve interp(-px, -conf, precision[:, 0], left = 1); right = the last value.
+ *   pr_curve  interp(px, knot recall of threshold 0, its envelope).
+ *   interp    numpy's: j = largest index with xp[j] <= x; `left` below xp[0]; fp[last] at or beyond xp[last]; fp[j] when x == xp[j];
+ *             else ((fp[j+1] - fp[j]) / (xp[j+1] - xp[j])) * (x - xp[j]) + fp[j] as separate operations; repeated xp use the last of the run.
+ *  tpc <= n is assumed (a label is matched at most once per threshold).  One workgroup per (class, threshold), tiles of
+ *  tamtr_val_ap_tile() rows with a carry, no cap on a segment's length, no atomics: two runs give the same bits.  Nothing is allocated
+ *  or synchronised.
+ *  TAMTR_EINVAL: a NULL operand (lab_cls may be NULL only when M == 0), an f64 operand not 8-byte or an f32 / i32 operand not 4-byte
+ *  aligned, N < 1, nc < 1, M < 0.  TAMTR_EUNSUP: nc > 2^20 or N > 2^30.  The checks come before any GPU call. */
+int tamtr_val_ap_curves(const float* conf, const uint8_t* correct, const int32_t* seg_off, int N, int nc, const float* lab_cls, int M,
+                        const double* px, const double* grid, int32_t* tpc_scratch, double* env_scratch, double* ap, double* p_curve,
+                        double* r_curve, double* pr_curve, int32_t* n_gt, int32_t* n_pred, void* stream);
+int tamtr_val_ap_tile(void); /* rows per tile of the scans above (ops.VAL_AP_TILE) */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * CLIP text tower (frozen ViT-B/32 text encoder), fp32 end to end, forward only.  Replaces `clip.tokenize(...)` followed by

@@ -102,6 +102,8 @@ _SIGS = {
     'tamtr_detect_postprocess': [_P, _I, _I, _I, _I, _P, _F, _F, _I, _F, _P, _I, _P, _P, _P, _P],
     'tamtr_val_postprocess_match': [_P, _I, _I, _I, _I, _F, _F, _F, _I, _F, _P, _P, _P, _I, _P, _P, _P, _P, _P],
     'tamtr_val_confusion': [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _F, _F, _P, _P],
+    'tamtr_val_ap_tile': [],
+    'tamtr_val_ap_curves': [_P, _P, _P, _I, _I, _P, _I] + [_P] * 10 + [_P],
     'tamtr_text_embed': [_P, _P, _P, _P, _LL, _I, _I, _I, _P],
     'tamtr_linear_f32': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     'tamtr_text_pool_project': [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],

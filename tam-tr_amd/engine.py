@@ -410,37 +410,62 @@ def compute_ap(recall, precision):
 
 def _curves_of_class(hit, score, n_gt, grid, eps):
     """hit [n, T] bool (descending score), score [n]: recall / precision of the first IoU threshold resampled on `grid` (confidence
-    axis) and the AP of every threshold."""
+    axis), the AP of every threshold, and the first threshold's precision envelope resampled on `grid` (recall axis)."""
     tp_run = hit.cumsum(0)
     fp_run = (1 - hit).cumsum(0)
     recall = tp_run / (n_gt + eps)
     precision = tp_run / (tp_run + fp_run)
     r_grid = np.interp(-grid, -score, recall[:, 0], left=0)          # confidence decreases along the arrays: negate to interpolate
     p_grid = np.interp(-grid, -score, precision[:, 0], left=1)
-    ap = np.array([compute_ap(recall[:, t], precision[:, t])[0] for t in range(hit.shape[1])])
-    return r_grid, p_grid, ap
+    per_t = [compute_ap(recall[:, t], precision[:, t]) for t in range(hit.shape[1])]
+    ap = np.array([a for a, _, _ in per_t])
+    _, envelope, knots_r = per_t[0]
+    return r_grid, p_grid, ap, np.interp(grid, knots_r, envelope)
 
 
-def ap_per_class(tp, conf, pred_cls, target_cls, eps=1e-16):
-    """-> tp, fp, p, r, f1 (at the max-F1 confidence), ap [nc, 10], unique_classes   (metrics.py:1032-1128, plots dropped).
-    Classes are the ones that have ground truth; a class nobody predicted keeps zero curves."""
-    order = np.argsort(-conf)
-    tp, conf, pred_cls = tp[order], conf[order], pred_cls[order]
-    classes, n_gt = np.unique(target_cls, return_counts=True)
-    grid = np.linspace(0, 1, 1000)
-    ap = np.zeros((len(classes), tp.shape[1]))
-    p_curve, r_curve = np.zeros((len(classes), grid.size)), np.zeros((len(classes), grid.size))
-    for row, (c, n) in enumerate(zip(classes, n_gt)):
-        mine = pred_cls == c
-        if n == 0 or not mine.any():
-            continue
-        r_curve[row], p_curve[row], ap[row] = _curves_of_class(tp[mine], conf[mine], n, grid, eps)
+def operating_point(p_curve, r_curve, n_gt, eps=1e-16):
+    """-> tp, fp, p, r, f1 at the one confidence that maximises the smoothed mean F1 over classes, and f1_curve (metrics.py:1113-1126).
+    p_curve, r_curve [classes, 1000] over confidence, n_gt [classes]: shared by ap_per_class and the device path of DeviceValidator."""
     f1_curve = 2 * p_curve * r_curve / (p_curve + r_curve + eps)
     best = smooth(f1_curve.mean(0), 0.1).argmax()                       # one operating confidence for all classes
     p, r, f1 = p_curve[:, best], r_curve[:, best], f1_curve[:, best]
     tpn = (r * n_gt).round()
     fpn = (tpn / (p + eps) - tpn).round()
-    return tpn, fpn, p, r, f1, ap, classes.astype(int)
+    return tpn, fpn, p, r, f1, f1_curve
+
+
+def ap_per_class(tp, conf, pred_cls, target_cls, eps=1e-16, curves=False, stable=False):
+    """-> tp, fp, p, r, f1 (at the max-F1 confidence), ap [nc, 10], unique_classes   (metrics.py:1032-1128; its plots are the curves below).
+    Classes are the ones that have ground truth; a class nobody predicted keeps zero curves.
+    curves: an eighth element, a dict of float64 arrays whose rows follow the returned classes: 'px' = linspace(0, 1, 1000); 'p', 'r',
+    'f1' [classes, 1000] over confidence (the reference's P_curve, R_curve, F1_curve); 'pr' [classes, 1000], the precision envelope of the
+    first IoU threshold over recall px (its PR_curve, `prec_values`); 'valid' bool [classes]: the class has labels and predictions.  The
+    reference appends prec_values for valid classes only, so its rows lose their class; here the rows are dense, zero where not valid.
+    stable: predictions of equal confidence keep their input order (image order, then row order) instead of the order numpy's default
+    argsort happens to give them.  The two agree when no two confidences are equal; csrc/metrics.hip implements the stable order."""
+    order = np.argsort(-conf, kind='stable') if stable else np.argsort(-conf)
+    tp, conf, pred_cls = tp[order], conf[order], pred_cls[order]
+    classes, n_gt = np.unique(target_cls, return_counts=True)
+    grid = np.linspace(0, 1, 1000)
+    ap = np.zeros((len(classes), tp.shape[1]))
+    p_curve, r_curve = np.zeros((len(classes), grid.size)), np.zeros((len(classes), grid.size))
+    pr_curve, valid = np.zeros((len(classes), grid.size)), np.zeros(len(classes), bool)
+    for row, (c, n) in enumerate(zip(classes, n_gt)):
+        mine = pred_cls == c
+        if n == 0 or not mine.any():
+            continue
+        r_curve[row], p_curve[row], ap[row], pr_curve[row] = _curves_of_class(tp[mine], conf[mine], n, grid, eps)
+        valid[row] = True
+    tpn, fpn, p, r, f1, f1_curve = operating_point(p_curve, r_curve, n_gt, eps)
+    out = (tpn, fpn, p, r, f1, ap, classes.astype(int))
+    if curves:
+        out += ({'px': grid, 'p': p_curve, 'r': r_curve, 'f1': f1_curve, 'pr': pr_curve, 'valid': valid},)
+    return out
+
+
+def curves_as_lists(curves, classes):
+    """The curves dict of ap_per_class as nested lists plus 'classes': what results(curves=True) carries under 'curves'."""
+    return {**{k: np.asarray(v).tolist() for k, v in curves.items()}, 'classes': [int(c) for c in classes]}
 
 
 def cm_conf(conf):
@@ -565,16 +590,21 @@ class Validator:
                     self.confusion_matrix.process_batch(predn, labelsn)
             self.stats.append((correct, pred[:, 4], pred[:, 5], cls.squeeze(-1)))
 
-    def results(self):
+    def results(self, curves=False):
+        """curves: the dict also carries 'curves' (ap_per_class's curves as nested lists, plus 'classes'; {} when there is nothing to reduce)."""
         extra = {}
         if self.confusion:
             extra['confusion_matrix'] = self.confusion_matrix.matrix.tolist() if self.confusion_matrix is not None else []
+        if curves:
+            extra['curves'] = {}
         if not self.stats:
             return {'precision': 0.0, 'recall': 0.0, 'mAP50': 0.0, 'mAP50-95': 0.0, 'seen': self.seen, **extra}
         stats = [torch.cat(x, 0).cpu().numpy() for x in zip(*self.stats)]
         if not stats[0].any():
             return {'precision': 0.0, 'recall': 0.0, 'mAP50': 0.0, 'mAP50-95': 0.0, 'seen': self.seen, **extra}
-        _, _, p, r, _, ap, _ = ap_per_class(*stats)
+        _, _, p, r, _, ap, classes, *cv = ap_per_class(*stats, curves=curves)
+        if curves:
+            extra['curves'] = curves_as_lists(cv[0], classes)
         return {'precision': float(p.mean()), 'recall': float(r.mean()), 'mAP50': float(ap[:, 0].mean()),
                 'mAP50-95': float(ap.mean()), 'seen': self.seen, **extra}
 
@@ -592,10 +622,15 @@ class DeviceValidator:
     confusion: update() makes one more launch per batch (ops.val_confusion, csrc/confusion.hip) on the outputs and the uploaded labels
     of the first, adding into one device matrix - still nothing synchronises; results() then carries 'confusion_matrix' (nested lists
     of ints, equal to Validator's), which rides in the run's one device-to-host copy.  nc: its class count, from the first prediction
-    when None."""
+    when None.
+    device_metrics: results() reduces on the device as well: ops.val_ap_curves (two stable sorts and one launch, csrc/metrics.hip) leaves
+    AP per class and threshold and the P / R / PR curves in one packed buffer, and the run's one device-to-host copy carries that buffer
+    (plus the confusion matrix and device-side labels) instead of every row: 8 * (3010 * nc) + 8 * nc bytes, whatever the number of
+    rows.  The order of equal confidences is then the defined one (ap_per_class(stable=True)); F1, the operating confidence and the
+    dict come from the same host lines.  Classes are the label classes inside [0, nc).  save_json keeps the row copy for its records."""
 
     def __init__(self, imgsz=640, conf=0.001, iou=0.7, single_cls=False, save_json=False, class_map=None, names=None, confusion=False,
-                 nc=None):
+                 nc=None, device_metrics=False):
         self.imgsz, self.conf, self.iou, self.single_cls = imgsz, conf, iou, single_cls
         self.save_json, self.class_map, self.names = save_json, class_map, names
         self.batches, self.files, self.seen = [], [], 0
@@ -603,6 +638,7 @@ class DeviceValidator:
         self._reduced = None
         self.confusion, self.nc = confusion, nc
         self._matrix, self._matrix_host = None, None   # i32 [nc + 1, nc + 1] on the device; its copy after _reduce()
+        self.device_metrics, self._ncls, self._reduced_dev = device_metrics, nc, None
 
     @torch.no_grad()
     def update(self, preds, batch):
@@ -619,7 +655,9 @@ class DeviceValidator:
         self.seen += y.shape[0]
         if self.save_json:
             self.files.extend(batch['im_file'])
-        self._reduced = None
+        if self._ncls is None:
+            self._ncls = y.shape[-1] - 4
+        self._reduced = self._reduced_dev = None
 
     def _reduce(self):
         """-> (predn [n, 6], correct [n, 10] bool, image [n], target_cls [m], target_image [m]) as numpy, rows in image order."""
@@ -660,24 +698,88 @@ class DeviceValidator:
                              cat(tcls, (0,), np.float32), cat(timage, (0,), np.int64))
         return self._reduced
 
-    def results(self):
-        predn, correct, image, tcls, timage = self._reduce()
-        if self.save_json:
-            self.jdict = self._records(predn, image)
-        extra = {}
-        if self.confusion:
-            extra['confusion_matrix'] = self._matrix_host.tolist() if self._matrix_host is not None else []
-        if (len(predn) == 0 and len(tcls) == 0) or not correct.any():
-            return {**_EMPTY, 'seen': self.seen, 'per_class': [], **extra}
-        _, _, p, r, _, ap, classes = ap_per_class(correct, predn[:, 4], predn[:, 5], tcls)
+    def _reduce_device(self):
+        """device_metrics: -> (the six outputs of ops.val_ap_curves as numpy, target_cls [m], target_image [m]).  One device-to-host
+        copy: the packed result, the confusion matrix, and the labels of the batches whose labels live on the device."""
+        if self._reduced_dev is None:
+            from . import ops
+            nc, labs, dev_labs = self._ncls, [], []
+            for _, _, _, lab_cls, lab_off in self.batches:
+                if isinstance(lab_cls, torch.Tensor):     # rows outside lab_off[0] .. lab_off[B] belong to no image: class -1, counted nowhere
+                    i = torch.arange(lab_cls.numel(), device=lab_cls.device)
+                    labs.append(torch.where((i >= lab_off[0]) & (i < lab_off[-1]), lab_cls, -1.0))
+                    dev_labs += [lab_cls, lab_off]
+                else:
+                    labs.append(lab_cls)
+            packed = ops.val_ap_curves([b[:3] for b in self.batches], labs, nc, return_packed=True)[-1]
+            parts = [packed] + (dev_labs if not self.save_json else []) + ([self._matrix] if self._matrix is not None and not self.save_json else [])
+            flat = torch.cat([p.reshape(-1).view(torch.uint8) for p in parts]).cpu().numpy()   # the run's one device-to-host copy
+            out = ops.val_ap_split(flat[:packed.numel() * 8].view(np.float64), nc)
+            if self.save_json:                            # the records need the rows: today's copy, which also brings labels and matrix
+                tcls, timage = self._reduce()[3:]
+            else:
+                pos, tcls, timage, first = packed.numel() * 8, [], [], 0
+                for predn, _, _, lab_cls, lab_off in self.batches:
+                    B = predn.shape[0]
+                    if isinstance(lab_cls, torch.Tensor):
+                        n = lab_cls.numel()
+                        lab_cls, lab_off = flat[pos:pos + 4 * n].view(np.float32), flat[pos + 4 * n:pos + 4 * (n + B + 1)].view(np.int32)
+                        pos += 4 * (n + B + 1)
+                        lab_cls, lab_off = lab_cls[lab_off[0]:lab_off[B]], lab_off - lab_off[0]
+                    tcls.append(lab_cls)
+                    timage.append(first + np.repeat(np.arange(B), np.diff(lab_off)))
+                    first += B
+                if self._matrix is not None:
+                    self._matrix_host = flat[pos:pos + 4 * self._matrix.numel()].view(np.int32).reshape(tuple(self._matrix.shape)).copy()
+                tcls, timage = np.concatenate(tcls), np.concatenate(timage)
+            self._reduced_dev = (*out, tcls, timage)
+        return self._reduced_dev
+
+    def _table(self, classes, p, r, ap, tcls, timage):
+        """The reference's print_results table: one record per class that has labels."""
         per_class = []
         for k, c in enumerate(classes):
             mine = tcls == c
             per_class.append({'class': self.names[int(c)] if self.names is not None else int(c), 'images': int(len(np.unique(timage[mine]))),
                               'instances': int(mine.sum()), 'precision': float(p[k]), 'recall': float(r[k]), 'mAP50': float(ap[k, 0]),
                               'mAP50-95': float(ap[k].mean())})
+        return per_class
+
+    def results(self, curves=False):
+        """curves: the dict also carries 'curves' (ap_per_class's curves as nested lists, plus 'classes'; {} when there is nothing to reduce)."""
+        extra = {'curves': {}} if curves else {}
+        if self.device_metrics:
+            if not self.batches:
+                return {**_EMPTY, 'seen': self.seen, 'per_class': [], **({'confusion_matrix': []} if self.confusion else {}), **extra}
+            ap, p_curve, r_curve, pr_curve, n_gt, n_pred, tcls, timage = self._reduce_device()
+            if self.save_json:
+                predn, _, image = self._reduce()[:3]
+                self.jdict = self._records(predn, image)
+            if self.confusion:
+                extra['confusion_matrix'] = self._matrix_host.tolist() if self._matrix_host is not None else []
+            # `no row and no label, or no hit at all` of the host path: a hit makes the precision envelope positive at recall 0, and with
+            # it the class's AP; without a hit every AP is zero
+            if not ap.any():
+                return {**_EMPTY, 'seen': self.seen, 'per_class': [], **extra}
+            has = n_gt > 0
+            classes, ap = np.nonzero(has)[0], ap[has]
+            _, _, p, r, _, f1_curve = operating_point(p_curve[has], r_curve[has], n_gt[has])
+            if curves:
+                extra['curves'] = curves_as_lists({'px': np.linspace(0, 1, 1000), 'p': p_curve[has], 'r': r_curve[has], 'f1': f1_curve,
+                                                   'pr': pr_curve[has], 'valid': n_pred[has] > 0}, classes)
+        else:
+            predn, correct, image, tcls, timage = self._reduce()
+            if self.save_json:
+                self.jdict = self._records(predn, image)
+            if self.confusion:
+                extra['confusion_matrix'] = self._matrix_host.tolist() if self._matrix_host is not None else []
+            if (len(predn) == 0 and len(tcls) == 0) or not correct.any():
+                return {**_EMPTY, 'seen': self.seen, 'per_class': [], **extra}
+            _, _, p, r, _, ap, classes, *cv = ap_per_class(correct, predn[:, 4], predn[:, 5], tcls, curves=curves)
+            if curves:
+                extra['curves'] = curves_as_lists(cv[0], classes)
         return {'precision': float(p.mean()), 'recall': float(r.mean()), 'mAP50': float(ap[:, 0].mean()), 'mAP50-95': float(ap.mean()),
-                'seen': self.seen, 'per_class': per_class, **extra}
+                'seen': self.seen, 'per_class': self._table(classes, p, r, ap, tcls, timage), **extra}
 
     def _records(self, predn, image):
         """pred_to_json: image_id = the file stem; bbox = top-left x, y, w, h rounded to 3; score rounded to 5."""
@@ -708,16 +810,20 @@ class DeviceValidator:
 
 @torch.no_grad()
 def validate(model, batches, imgsz=640, conf=0.001, iou=0.7, autocast_dtype=None, on_device=False, save_json=None, names=None,
-             confusion=False):
+             confusion=False, device_metrics=False, curves=False):
     """model in eval mode over an iterable of batches -> metric dict (valTAMTR.py's flow without the dataset plumbing).
     on_device: postprocess and label matching in one HIP launch per batch (DeviceValidator; the dict then also carries 'per_class');
     save_json (a file or folder path, needs on_device): also write the reference's predictions.json there.
-    confusion: the dict also carries 'confusion_matrix' ([nc + 1][nc + 1] ints, row = predicted, column = true, last = background)."""
+    confusion: the dict also carries 'confusion_matrix' ([nc + 1][nc + 1] ints, row = predicted, column = true, last = background).
+    device_metrics (needs on_device): AP and the curves are reduced on the device too (DeviceValidator(device_metrics=True)).
+    curves: the dict also carries 'curves' (the reference's P / R / F1 / PR curves; see ap_per_class)."""
     if save_json and not on_device:
         raise ValueError('validate(save_json=...) needs on_device=True: the records come from the device path')
+    if device_metrics and not on_device:
+        raise ValueError('validate(device_metrics=True) needs on_device=True: the reduction reads what the device path keeps')
     was_training = model.training
     model.eval()
-    v = (DeviceValidator(imgsz, conf, iou, save_json=bool(save_json), names=names, confusion=confusion) if on_device
+    v = (DeviceValidator(imgsz, conf, iou, save_json=bool(save_json), names=names, confusion=confusion, device_metrics=device_metrics) if on_device
          else Validator(imgsz, conf, iou, confusion=confusion))
     for batch in batches:
         img = batch['img']
@@ -725,7 +831,7 @@ def validate(model, batches, imgsz=640, conf=0.001, iou=0.7, autocast_dtype=None
             preds = model(img, txt_feats=batch.get('txt_feats'))
         v.update(preds, batch)
     model.train(was_training)
-    res = v.results()
+    res = v.results(curves=True) if curves else v.results()
     if save_json:
         res['json'] = v.write_json(save_json)
     return res
@@ -739,7 +845,7 @@ def fitness(metrics):
 
 def fit(model, train_loader, prepare, epochs, val_loader=None, lr0=1e-4, lrf=1.0, momentum=0.9, weight_decay=1e-4, optimizer='AdamW',
         warmup_iters=2000, warmup_bias_lr=0.1, warmup_momentum=0.8, close_mosaic=0, imgsz=640, reducer=None, rank=0, world=1,
-        save_dir=None, max_steps=None, log=None, resume=None, static_graph=False, val_on_device=False):
+        save_dir=None, max_steps=None, log=None, resume=None, static_graph=False, val_on_device=False, val_device_metrics=False):
     """Train `model` for `epochs` passes over train_loader; defaults are the reference's shipped hyper-parameters
     (cfg/default.yaml:23,84-90; this fork sets nbs = batch, so there is no gradient accumulation and weight decay is unscaled, and
     reads warmup_epochs as an iteration count: trainer.py:263-265,294).
@@ -752,7 +858,8 @@ def fit(model, train_loader, prepare, epochs, val_loader=None, lr0=1e-4, lrf=1.0
     (trainer.py:593-615), so the warm-up does not start over, best.pt is only replaced by a better epoch, and a run that resumes inside
     its last `close_mosaic` epochs starts with mosaic already closed.  static_graph: record trunk + VSS blocks + input projection as HIP graphs on the first batch
     (model.capture_static_part; batches of another shape, and evaluation, run eagerly).  val_on_device: the per-epoch validation runs its
-    postprocess and label matching on the device (validate(on_device=True)); the record then also holds 'per_class'.  Returns the per-epoch records."""
+    postprocess and label matching on the device (validate(on_device=True)); the record then also holds 'per_class'.  val_device_metrics (with val_on_device): its AP reduction
+    runs on the device too (validate(device_metrics=True)).  Returns the per-epoch records."""
     nb = len(train_loader)
     if nb == 0:   # e.g. drop_last with fewer samples per rank than the batch size: the loop below would 'train' for zero steps without a word
         raise ValueError(f'fit(): the training loader yields no batches ({len(train_loader.dataset)} samples, batch size {train_loader.batch_size}, '
@@ -837,7 +944,8 @@ def fit(model, train_loader, prepare, epochs, val_loader=None, lr0=1e-4, lrf=1.0
         if rank == 0:
             if val_loader is not None:
                 rec.update(validate(ema.ema, (prepare(b, False) for b in val_loader), imgsz=imgsz,
-                                    autocast_dtype=getattr(model, 'autocast_dtype', None), on_device=val_on_device))
+                                    autocast_dtype=getattr(model, 'autocast_dtype', None), on_device=val_on_device,
+                                    device_metrics=val_device_metrics))
                 rec['fitness'] = fitness(rec)
             if save_dir is not None:
                 os.makedirs(save_dir, exist_ok=True)

@@ -23,6 +23,7 @@ counts the memset nodes of both graphs (hipGraphGetNodes on the capturing stream
 verify() replays three times (the corruption only shows from the second replay on).  DEBUG_CLR_GRAPH_PACKET_CAPTURE=0, exported before
 the HIP runtime starts, restores node-by-node launches, under which memset nodes are harmless.
 """
+import gc
 import os
 
 import torch
@@ -91,14 +92,27 @@ class GraphedPart:
         torch.cuda.current_stream().wait_stream(self.stream)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        with torch.cuda.graph(self.fwd, pool=pool, stream=self.stream):
-            self.static_out = run()
-            census_f = capture_census(self.stream)
-        self.static_gout = torch.zeros_like(self.static_out)
-        leaves = [alias[n] for n in self.names if alias[n].requires_grad]
-        with torch.cuda.graph(self.bwd, pool=pool, stream=self.stream):
-            grads = torch.autograd.grad(self.static_out, leaves, self.static_gout, allow_unused=True)
-            census_b = capture_census(self.stream)
+        # No cyclic garbage collection while a capture is open.  A released GraphedPart is a reference cycle (its _Replay class holds it), so
+        # only the collector frees it - and if that happens inside a later capture, the destructors of its two CUDAGraphs and the return of
+        # its pool's blocks are HIP calls that a capture in global mode forbids: the exception leaves a destructor and the process aborts
+        # ("Fatal Python error: Aborted ... Garbage-collecting" under torch.func.functional_call in the forward capture).  torch.cuda.graph
+        # used to collect before every capture and since 2.9 only does so with torch.compiler.config.force_cudagraph_gc; so collect here,
+        # before the captures, and keep the collector off until both are closed.
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(self.fwd, pool=pool, stream=self.stream):
+                self.static_out = run()
+                census_f = capture_census(self.stream)
+            self.static_gout = torch.zeros_like(self.static_out)
+            leaves = [alias[n] for n in self.names if alias[n].requires_grad]
+            with torch.cuda.graph(self.bwd, pool=pool, stream=self.stream):
+                grads = torch.autograd.grad(self.static_out, leaves, self.static_gout, allow_unused=True)
+                census_b = capture_census(self.stream)
+        finally:
+            if gc_was_on:
+                gc.enable()
         self.census = {'forward': census_f, 'backward': census_b}
         self.memset_nodes = (census_f['memset'], census_b['memset'])
         self.packet_capture = packet_capture_on()

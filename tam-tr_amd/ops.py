@@ -1958,6 +1958,77 @@ def val_confusion(predn, counts, device_labels, nc, conf, iou_thres, matrix):
     return matrix
 
 
+VAL_AP_TILE = 256      # rows per tile of the scans of csrc/metrics.hip (= tamtr_val_ap_tile(); a host test holds the two together)
+_VAL_AP_GRIDS = {}     # device -> f64 [1000 + 101]: numpy's own linspace(0, 1, 1000) and linspace(0, 1, 101), uploaded once
+
+
+def val_ap_split(packed, nc):
+    """The packed f64 buffer of val_ap_curves (a device tensor, or its copy as a numpy array) -> ap [nc, 10], p_curve, r_curve,
+    pr_curve [nc, 1000] (f64), n_gt, n_pred [nc] (i32), all views."""
+    import numpy as np
+    i32 = torch.int32 if isinstance(packed, torch.Tensor) else np.int32
+    cut = [0, 10 * nc, 1010 * nc, 2010 * nc, 3010 * nc]
+    ap, p, r, pr = (packed[a:b].reshape(nc, -1) for a, b in zip(cut[:-1], cut[1:]))
+    counts = packed[3010 * nc:3011 * nc].view(i32)
+    return ap, p, r, pr, counts[:nc], counts[nc:]
+
+
+@torch.no_grad()
+def val_ap_curves(batches, lab_cls, nc, return_packed=False):
+    """The reduction of a validation run, engine.ap_per_class(stable=True, curves=True), on the device: AP per class and IoU threshold and
+    the precision / recall / PR curves of every class in [0, nc) from the rows val_postprocess_match left there; the rule is stated in
+    csrc/metrics.hip.  batches: a list of (predn f32 [B, nq, 6], correct u8 [B, nq, 10], counts i32 [B]) device tensors, in run order.
+    lab_cls: the run's label classes - a numpy array or device tensor, or a list of them (host arrays go up in ONE non-blocking copy).
+    The rows are concatenated, dead rows (row >= counts[b]) get the class key nc, two stable torch.sort calls order them by class, then
+    score descending, then original order, torch.searchsorted finds the class segments, and one launch does the rest.
+    Returns ap f64 [nc, 10], p_curve, r_curve, pr_curve f64 [nc, 1000], n_gt, n_pred i32 [nc]: views of one packed device buffer
+    (return_packed: a seventh element, that buffer, f64 [3011 * nc]; val_ap_split undoes it).  Nothing synchronises."""
+    import numpy as np
+    nc = int(nc)
+    if not batches or nc < 1:
+        raise _lib.TamtrHipError('val_ap_curves: needs at least one batch and nc >= 1')
+    for predn, correct, counts in batches:
+        require_gpu(predn, correct, counts)
+        if (predn.dim() != 3 or predn.shape[2] != 6 or predn.dtype != torch.float32 or correct.dtype != torch.uint8
+                or tuple(correct.shape) != (*predn.shape[:2], 10) or counts.dtype != torch.int32 or counts.numel() != predn.shape[0]):
+            raise _lib.TamtrHipError(f'val_ap_curves: expected predn f32 [B, nq, 6], correct u8 [B, nq, 10], counts i32 [B], got '
+                                     f'{tuple(predn.shape)} {predn.dtype}, {tuple(correct.shape)} {correct.dtype}, {tuple(counts.shape)} {counts.dtype}')
+    dev = batches[0][0].device
+    labs = list(lab_cls) if isinstance(lab_cls, (list, tuple)) else [lab_cls]
+    on_dev = [t.reshape(-1).float() for t in labs if isinstance(t, torch.Tensor)]
+    require_gpu(*on_dev)
+    host = [np.asarray(a, dtype=np.float32).reshape(-1) for a in labs if not isinstance(a, torch.Tensor)]
+    if sum(len(a) for a in host):
+        on_dev.append(torch.from_numpy(np.concatenate(host)).to(dev, non_blocking=True))
+    lab = _c(torch.cat(on_dev)) if on_dev else None
+    M = int(lab.numel()) if lab is not None else 0
+    grids = _VAL_AP_GRIDS.get(dev)
+    if grids is None:
+        grids = _VAL_AP_GRIDS[dev] = torch.from_numpy(np.concatenate([np.linspace(0, 1, 1000), np.linspace(0, 1, 101)])).to(dev, non_blocking=True)
+
+    conf = torch.cat([b[0][..., 4].reshape(-1) for b in batches])
+    cls = torch.cat([b[0][..., 5].reshape(-1) for b in batches])
+    hits = torch.cat([b[1].reshape(-1, 10) for b in batches])
+    if len({b[0].shape[1] for b in batches}) == 1:            # the usual run, one nq: one comparison for all batches
+        live = (torch.arange(batches[0][0].shape[1], device=dev)[None, :] < torch.cat([b[2] for b in batches])[:, None]).reshape(-1)
+    else:
+        live = torch.cat([(torch.arange(b[0].shape[1], device=dev)[None, :] < b[2][:, None]).reshape(-1) for b in batches])
+    key = torch.where(live, cls, float(nc))
+    _, by_conf = torch.sort(-conf, stable=True)              # the host rule's np.argsort(-conf, kind='stable') ...
+    key, by_cls = torch.sort(key[by_conf], stable=True)      # ... and its per-class masks, which keep that order
+    order = by_conf[by_cls]
+    conf, hits = _c(conf[order]), _c(hits[order])
+    seg = _c(torch.searchsorted(key, torch.arange(nc + 1, device=dev, dtype=torch.float32)).to(torch.int32))
+    N = int(conf.numel())
+    tpc = torch.empty(10 * N, device=dev, dtype=torch.int32)
+    env = torch.empty(10 * N, device=dev, dtype=torch.float64)
+    packed = torch.empty(3011 * nc, device=dev, dtype=torch.float64)
+    ap, p, r, pr, n_gt, n_pred = val_ap_split(packed, nc)
+    call('tamtr_val_ap_curves', ptr(conf), ptr(hits), ptr(seg), N, nc, ptr(lab) if M else None, M, ptr(grids), ctypes.c_void_p(grids.data_ptr() + 8000),
+         ptr(tpc), ptr(env), ptr(ap), ptr(p), ptr(r), ptr(pr), ptr(n_gt), ptr(n_pred), stream_ptr())
+    return (ap, p, r, pr, n_gt, n_pred) + ((packed,) if return_packed else ())
+
+
 def img_augment(src, inv_affine, luts, flags, out_hw, border=114):
     """The pixel half of the training transforms for a whole batch (affine warp -> HSV look-up -> flips -> CHW float / 255;
     ultralytics/data/augment.py:415-420,590-609,636-666,920-926).  src u8 [B, SH, SW, 3], inv_affine f64 [B, 6]

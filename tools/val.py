@@ -8,6 +8,10 @@ per-image host loop.  --save-json writes the reference's predictions.json into t
 --confusion adds the reference's confusion matrix (one more launch per batch on the device path, engine.ConfusionMatrix on the host path)
 and writes confusion_matrix.csv and confusion_matrix_normalized.csv (columns divided by their sums) into the run folder: row = predicted,
 column = true, header row and first column = the class names and `background`.
+--curves writes the reference's four curve plots as tables, PR_curve.csv (precision over recall at IoU 0.5), P_curve.csv, R_curve.csv and
+F1_curve.csv (over confidence), into the run folder: first column = the 1000-point grid, then one column per class that has labels, last
+column `all classes` = their mean.  --device-metrics also reduces AP and the curves on the device (engine.DeviceValidator(device_metrics=True):
+the rows of the run never come to the host).
 """
 import argparse
 import csv
@@ -40,6 +44,8 @@ def main():
     ap.add_argument('--host-postprocess', action='store_true', help='the per-image host loop (engine.Validator); no per-class table, no JSON')
     ap.add_argument('--save-json', action='store_true', help="write predictions.json (the reference's save_json=True)")
     ap.add_argument('--confusion', action='store_true', help='write confusion_matrix.csv and confusion_matrix_normalized.csv')
+    ap.add_argument('--curves', action='store_true', help='write PR_curve.csv, P_curve.csv, R_curve.csv and F1_curve.csv')
+    ap.add_argument('--device-metrics', action='store_true', help='reduce AP and the curves on the device too (not with --host-postprocess)')
     ap.add_argument('--project', default='runs/val')
     ap.add_argument('--name', default='TAMTR')
     args = ap.parse_args()
@@ -47,6 +53,8 @@ def main():
         ap.error('give either --text-feats, or --clip-weights together with --clip-vocab (not both, not neither)')
     if args.save_json and args.host_postprocess:
         ap.error('--save-json needs the device path (drop --host-postprocess)')
+    if args.device_metrics and args.host_postprocess:
+        ap.error('--device-metrics needs the device path (drop --host-postprocess)')
 
     import tamtr_amd  # noqa: F401
     from tamtr_amd import data as D, engine as E
@@ -68,18 +76,46 @@ def main():
     if not args.no_fuse:
         model.fuse()
     save_dir = None
-    if args.save_json or args.confusion:
+    if args.save_json or args.confusion or args.curves:
         from tamtr_amd.predict import increment_path
         save_dir = str(increment_path(os.path.join(args.project, args.name), mkdir=True))
     short = {k: v.split('/')[0] for k, v in names.items()}
     res = E.validate(model, (D.preprocess_batch(b, None, dev) for b in loader), imgsz=args.imgsz, conf=args.conf, iou=args.iou,
                      autocast_dtype=torch.bfloat16 if args.dtype == 'bf16' else None, on_device=not args.host_postprocess,
-                     save_json=save_dir if args.save_json else None, names=short, confusion=args.confusion)
+                     save_json=save_dir if args.save_json else None, names=short, confusion=args.confusion,
+                     device_metrics=args.device_metrics, curves=args.curves)
     if save_dir is not None:
         res['save_dir'] = save_dir
     if args.confusion:
         res['confusion_csv'], res['confusion_normalized_csv'] = write_confusion(res['confusion_matrix'], [short[k] for k in sorted(short)], save_dir)
+    if args.curves:
+        res['curves_csv'] = write_curves(res.pop('curves'), short, save_dir)
     print(json.dumps(res))
+
+
+CURVE_FILES = {'PR_curve.csv': ('pr', 'recall'), 'P_curve.csv': ('p', 'confidence'), 'R_curve.csv': ('r', 'confidence'),
+               'F1_curve.csv': ('f1', 'confidence')}
+
+
+def write_curves(curves, names, save_dir):
+    """The reference's PR / P / R / F1 plots (utils/metrics.py:894-996) as CSV: the grid, one column per class that has labels (named by
+    `names[class]`), and their mean as `all classes` (PR_curve: the mean of the classes that also have predictions).  curves: the 'curves' dict of results(curves=True); {} writes the headers only."""
+    classes = curves.get('classes', [])
+    px = curves.get('px', [])
+    paths = []
+    for fname, (key, axis) in CURVE_FILES.items():
+        rows = curves.get(key, [])
+        paths.append(os.path.join(save_dir, fname))
+        with open(paths[-1], 'w', newline='') as f:
+            w = csv.writer(f)
+            w.writerow([axis] + [names[c] for c in classes] + ['all classes'])
+            # the reference's PR plot averages the classes that have predictions too (its prec_values has no other rows)
+            mean_of = [k for k, ok in enumerate(curves.get('valid', [])) if ok or key != 'pr']
+            for g, x in enumerate(px):
+                col = [row[g] for row in rows]
+                mean = sum(col[k] for k in mean_of) / len(mean_of) if mean_of else float('nan')    # the mean of no class, as numpy names it
+                w.writerow([repr(float(x))] + [repr(float(v)) for v in col] + [repr(mean)])
+    return paths
 
 
 def write_confusion(matrix, names, save_dir):

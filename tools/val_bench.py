@@ -10,9 +10,13 @@
   (c) --confusion: the shapes of (a); DeviceValidator.update with and without confusion=True, and
       Validator.update with and without it for scale, ALTERNATING windows as in (a).
 
-    python tools/val_bench.py [--images 64] [--rounds 3] [--kernel-only] [--confusion]
---kernel-only runs only the device loop of (a) - with --confusion the loop with confusion=True - for a `rocprofv3 --kernel-trace --stats`
-run of its own.
+  (d) --metrics: DeviceValidator.results() at VisDrone-val scale on synthetic rows (548 images x 300 live rows, 70 labels per image,
+      nc = 10 and 80, about a tenth of the rows hit at IoU 0.5): the host reduction (every row to the host, engine.ap_per_class) against
+      device_metrics=True (ops.val_ap_curves, one packed copy), ALTERNATING windows as in (a); and the bytes each path copies.
+
+    python tools/val_bench.py [--images 64] [--rounds 3] [--kernel-only] [--confusion | --metrics]
+--kernel-only runs only the device loop of (a) - with --confusion the loop with confusion=True, with --metrics the device reduction of
+(d) - for a `rocprofv3 --kernel-trace --stats` run of its own.
 """
 import argparse
 import json
@@ -84,6 +88,60 @@ def bench_confusion(rounds, kernel_only=False):
                          'device_update_confusion_ms': [round(x, 4) for x in t['device', True]],
                          'host_update_ms': [round(x, 3) for x in t['host', False]],
                          'host_update_confusion_ms': [round(x, 3) for x in t['host', True]]})
+    return rows
+
+
+def synthetic_run(nc, images=548, nq=300, per_image=70, batch=16, seed=3):
+    """What DeviceValidator.update leaves behind for a run of `images` images, made directly: every row live, distinct-ish scores,
+    hits rarer at higher IoU thresholds (about 10 % at 0.5, so hits stay below the labels of a class), host-side labels."""
+    g = torch.Generator().manual_seed(seed)
+    rng = np.random.default_rng(seed)
+    out = []
+    for first in range(0, images, batch):
+        B = min(batch, images - first)
+        predn = torch.rand(B, nq, 6, generator=g)
+        predn[..., 5] = torch.randint(0, nc, (B, nq), generator=g).float()
+        hit = torch.rand(B, nq, 1, generator=g) < torch.linspace(0.1, 0.02, 10) * (0.5 + predn[..., 4:5])
+        out.append((predn.cuda(), hit.to(torch.uint8).cuda(), torch.full((B,), nq, dtype=torch.int32).cuda(),
+                    rng.integers(0, nc, B * per_image).astype(np.float32), (np.arange(B + 1) * per_image).astype(np.int32)))
+    return out
+
+
+def bench_metrics(rounds, kernel_only=False):
+    from tamtr_amd import engine as E
+    rows = []
+    for nc in (10, 80):
+        run = synthetic_run(nc)
+
+        def validator(device_metrics):
+            v = E.DeviceValidator(640, 0.001, 0.7, nc=nc, device_metrics=device_metrics)
+            v.batches, v.seen = list(run), sum(b[0].shape[0] for b in run)
+            return v
+
+        host, device = validator(False), validator(True)
+
+        def results(v):
+            v._reduced = v._reduced_dev = None       # results() keeps its reduction: time it afresh
+            return v.results()
+
+        for _ in range(3):
+            results(device)
+        if kernel_only:
+            t, n = window(lambda: results(device))
+            rows.append({'nc': nc, 'device_results_ms': round(t, 3), 'iters': n})
+            continue
+        results(host)
+        th, td = [], []
+        for _ in range(rounds):      # alternating windows
+            th.append(window(lambda: results(host))[0])
+            td.append(window(lambda: results(device))[0])
+        a, b = results(host), results(device)
+        n_rows = sum(int(b_[2].sum()) for b_ in run)
+        rows.append({'images': host.seen, 'rows': n_rows, 'labels': sum(len(b_[3]) for b_ in run), 'nc': nc,
+                     'mAP50_host': a['mAP50'], 'mAP50_device': b['mAP50'], 'mAP50-95_host': a['mAP50-95'], 'mAP50-95_device': b['mAP50-95'],
+                     'host_results_ms': [round(t, 3) for t in th], 'device_results_ms': [round(t, 3) for t in td],
+                     'host_copy_bytes': sum(b_[0].numel() * 4 + b_[1].numel() + b_[2].numel() * 4 for b_ in run),
+                     'device_copy_bytes': 8 * 3011 * nc})
     return rows
 
 
@@ -176,10 +234,19 @@ def main():
     ap.add_argument('--kernel-only', action='store_true')
     ap.add_argument('--skip-validate', action='store_true')
     ap.add_argument('--confusion', action='store_true', help='measurement (c): update with and without the confusion matrix')
+    ap.add_argument('--metrics', action='store_true', help='measurement (d): results() on the host path and with device_metrics=True')
     args = ap.parse_args()
     import tamtr_amd  # noqa: F401
     assert torch.cuda.is_available(), 'val_bench needs an MI355X'
     print(torch.cuda.get_device_name(0), 'torch', torch.__version__)
+    if args.metrics:
+        if args.kernel_only:
+            print(json.dumps({'device_results_only': bench_metrics(0, True)}))
+            return
+        print(f'(d) DeviceValidator.results(): host reduction vs device_metrics=True ({args.rounds} alternating windows of >= 1 s each, device events)')
+        for r in bench_metrics(args.rounds):
+            print(json.dumps(r))
+        return
     if args.kernel_only:
         print(json.dumps({'device_update_only': (bench_confusion if args.confusion else bench_update)(0, True)}))
         return
