@@ -35,7 +35,8 @@ extern "C" {
 #define TAMTR_ELAUNCH (-3)
 
 /* ABI version, bumped on any signature change.  The CLIP text tower's entries at the end of this file (tamtr_text_embed, tamtr_linear_f32,
- * tamtr_text_pool_project), tamtr_val_confusion and tamtr_val_ap_curves / tamtr_val_ap_tile are new symbols only: no existing signature
+ * tamtr_text_pool_project), tamtr_val_confusion, tamtr_val_ap_curves / tamtr_val_ap_tile and tamtr_bytetrack_update /
+ * tamtr_bytetrack_workspace_bytes are new symbols only: no existing signature
  * changed, so the version stayed at 36 when they were added. */
 int tamtr_abi_version(void);
 
@@ -679,6 +680,36 @@ int tamtr_linear_f32(const float* X, const float* W, const float* bias, const fl
  */
 int tamtr_text_pool_project(const float* x, const int32_t* ids, const float* gamma, const float* beta, const float* proj, float* out, int n,
                             int L, int W, int E, float eps, int norm, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * ByteTrack multi-object tracking.  Replaces BYTETracker.update, ultralytics/trackers/byte_tracker.py:238-351, with its Kalman filter
+ * (trackers/utils/kalman_filter.py:33-180: initiate, multi_predict, project, update) and its association (trackers/utils/matching.py:20-126:
+ * linear_assignment over lap.lapjv(extend_cost=True, cost_limit=thresh), iou_distance, fuse_score), as trackers/track.py:40-53 calls it
+ * once per frame on the host.  (New symbols only; the ABI version stays 36.)
+ *
+ *  out f32 [B, nq, 6], counts i32 [B]: the output of tamtr_detect_postprocess; the B frames are consumed in order inside one launch.
+ *  tracks f32 [B, nq, 8]: x1 y1 x2 y2 id score cls idx per activated track in state Tracked, the box from the filter mean, idx the row
+ *  of `out` the track was last matched to; rows after tcounts[b] are zero.  A frame with counts[b] <= 0 does not reach the tracker:
+ *  the frame counter does not advance and nothing ages (track.py:46-47).
+ *  The tracker's state is a table of T slots that the caller owns and the kernel updates in place:
+ *      mean f64 [T, 8], cov f64 [T, 8, 8], sc f32 [T, 2] (score, cls), hdr i32 [8] (frame_id, next_id, live slots, overflow, 0...),
+ *      meta i32 [T, 8] (state, is_activated, track_id, frame_id, start_frame, tracklet_len, idx, flags)
+ *  with state 0 free / 1 Tracked / 2 Lost / 3 Removed but still listed for one update, and flags 1 = mean is the untouched fp32
+ *  measurement, 2 = id is in the reference's removed list (csrc/track.hip states both).  A fresh table is all zero except
+ *  hdr[1] = 1 (ids start at 1).  A new track that finds no free slot is not created and is counted in hdr[3]; nothing is written
+ *  outside the T slots.
+ *  Arithmetic: the filter in fp64 as numpy, the costs in fp32 in the reference's operation order (the object is compiled with
+ *  -ffp-contract=off), scores compared in fp32; each assignment is the optimum lap.lapjv returns (the partial matching minimising
+ *  sum(c_ij - thresh)), found by lsap.hip's solver with one shared `unmatched` column - the reference's matching wherever it is unique.
+ *  workspace: tamtr_bytetrack_workspace_bytes(T, nq) bytes of device memory, 16-byte aligned, contents irrelevant (0 = unsupported).
+ *  One launch, one workgroup; nothing is allocated, set or synchronised, so the call can be captured.
+ *  TAMTR_EINVAL: a NULL operand, B < 1, nq < 1, T < 1, a workspace that is too small.  TAMTR_EUNSUP: T and nq whose solver state
+ *  (about 12 T + 30 nq bytes) exceeds 64 KiB of LDS.  The checks come before any GPU call. */
+int tamtr_bytetrack_update(const float* out, const int32_t* counts, int B, int nq, double* mean, double* cov, int32_t* meta, float* sc,
+                           int32_t* hdr, int T, float track_high_thresh, float track_low_thresh, float new_track_thresh,
+                           double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts, void* workspace, int workspace_bytes,
+                           void* stream);
+int tamtr_bytetrack_workspace_bytes(int T, int nq);
 
 #ifdef __cplusplus
 }

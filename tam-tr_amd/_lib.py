@@ -21,7 +21,7 @@ class TamtrHipError(RuntimeError):
     pass
 
 
-_P, _I, _F, _LL = c_void_p, c_int, c_float, c_longlong
+_P, _I, _F, _LL, _D = c_void_p, c_int, c_float, c_longlong, ctypes.c_double
 _SIGS = {
     'tamtr_abi_version': [],
     'tamtr_maxsigmoid_gate_fwd': [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _I, _P],
@@ -107,6 +107,8 @@ _SIGS = {
     'tamtr_text_embed': [_P, _P, _P, _P, _LL, _I, _I, _I, _P],
     'tamtr_linear_f32': [_P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     'tamtr_text_pool_project': [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P],
+    'tamtr_bytetrack_update': [_P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _F, _F, _F, _D, _I, _P, _P, _P, _I, _P],
+    'tamtr_bytetrack_workspace_bytes': [_I, _I],
 }
 EXPORTS = tuple(_SIGS)
 _lib = None

@@ -1,0 +1,543 @@
+// track.hip - ByteTrack on the device: BYTETracker.update (ultralytics/trackers/byte_tracker.py:238-351, with
+// utils/kalman_filter.py:33-180 and utils/matching.py:20-126) for the B frames of a predictor batch, in order, inside ONE launch
+// (tamtr_bytetrack_update).
+//
+// Replaces the reference's per-frame host loop (trackers/track.py:40-53): copy the frame's boxes to the host, numpy Kalman filters,
+// bbox_ioa and lap.lapjv three times.  Here the kernel reads what tamtr_detect_postprocess left on the device (out [B, nq, 6],
+// counts [B]) and writes tracks [B, nq, 8] (x1 y1 x2 y2 id score cls idx; zero after the count) and tcounts [B]; the tracker's state
+// lives in a slot table on the device, so nothing synchronises.
+//
+// The table (capacity T, owned by the caller; the numpy twin tests/bytetrack_np.py keeps the same one):
+//   mean f64 [T, 8], cov f64 [T, 8, 8]
+//   meta i32 [T, 8]   state, is_activated, track_id, frame_id, start_frame, tracklet_len, idx, flags
+//   sc   f32 [T, 2]   score, cls
+//   hdr  i32 [8]      frame_id, next_id, live slots, overflow count, 0...
+// state: 0 free, 1 Tracked, 2 Lost, 3 Removed but still listed: the reference drops a lost track that aged out from its lost list only
+// one update later (it filters with the removed list as it stood before the frame's removals, byte_tracker.py:344-346); until then the
+// track still takes part in the first association, where a match revives it, and in the duplicate removal.
+// flags: 1 = the mean still is the fp32 measurement it was initiated with (numpy then derives the first predict's process noise and
+// the first projection's std in fp32, because `0.05 * np.float32` is fp32), 2 = the id is in the reference's removed list (such a
+// track, revived and lost again, leaves the lost list at once).  New tracks take the lowest free slots; when there are more of them
+// than free slots the excess is counted in hdr[3] and not created - nothing is written past the table.
+//
+// Arithmetic (the object is compiled with -ffp-contract=off):
+//   filter   fp64 as numpy: initiate / predict / project / update.  F = [[I, I], [0, I]], so F P F^T is block additions in numpy's
+//            order ((A + C) + (B + D), B + D, C + D, D); the gain is one 4x4 Cholesky solve; P - K (S K^T) as multi_dot orders it.
+//   costs    fp32 in the reference's operation order: tlbr cast to fp32 (a detection's is x1 y1 (x2-x1)+x1 (y2-y1)+y1, as an STrack
+//            without a mean reports it), bbox_ioa(iou=True) with eps = fp32(1e-7), d = 1 - iou, fused = 1 - (1 - d) * score.
+//   scores   compared in fp32 with the fp32 thresholds, `>` and `<` as the reference (a score equal to track_high_thresh is in
+//            neither set).
+// Assignment: lap.lapjv(cost, extend_cost=True, cost_limit=L) returns the partial matching that minimises sum(c_ij - L).  The same
+// optimum comes from lsap.hip's shortest-augmenting-path solver (float64 duals) when every row may also take one shared `unmatched`
+// column of cost L with unlimited capacity: a path that reaches that column ends there, its dual stays 0, and the problem is
+// n x (m + 1).  Where the optimum is unique the matching is the reference's.
+//
+// Design: one workgroup of one wavefront per tracker (the grid dimension is kept for several trackers); the frames are a loop with
+// a barrier between the steps.  Lists (pool, unconfirmed, high / low detections ...) are built in index order with ballots, the cost
+// matrices and lists live in a workspace in global memory (L2-resident), the solver's duals and paths in LDS.  One lane runs one
+// track's filter.  The work is tiny and latency-bound.
+#include "common.h"
+
+#define TRK_FREE 0
+#define TRK_TRACKED 1
+#define TRK_LOST 2
+#define TRK_LIMBO 3
+#define TRK_RAW 1
+#define TRK_EVER_REMOVED 2
+enum { M_STATE, M_ACT, M_ID, M_FRAME, M_START, M_LEN, M_IDX, M_FLAGS };
+
+// ---------------------------------------------------------------------------------------------------------------- small helpers
+// the i in [0, n) with pred(i), in index order -> list; called by the whole wave; returns their number
+template <typename F>
+__device__ __forceinline__ int trk_compact(int n, int* list, int lane, F pred) {
+  int cnt = 0;
+  for (int i0 = 0; i0 < n; i0 += WAVE) {
+    const int i = i0 + lane;
+    const bool p = i < n && pred(i);
+    const unsigned long long b = __ballot(p);
+    if (p) list[cnt + __popcll(b & ((1ull << lane) - 1ull))] = i;
+    cnt += __popcll(b);
+  }
+  return cnt;
+}
+
+// bbox_ioa(a, b, iou=True), utils/metrics.py:17-46, fp32 op by op
+__device__ __forceinline__ float trk_iou(const float* a, const float* b) {
+  float iw = fminf(a[2], b[2]) - fmaxf(a[0], b[0]);
+  float ih = fminf(a[3], b[3]) - fmaxf(a[1], b[1]);
+  iw = iw < 0.0f ? 0.0f : iw;
+  ih = ih < 0.0f ? 0.0f : ih;
+  const float inter = iw * ih;
+  float area = (b[2] - b[0]) * (b[3] - b[1]);
+  area = (area + (a[2] - a[0]) * (a[3] - a[1])) - inter;
+  return inter / (area + (float)1e-7);
+}
+
+// STrack.tlbr from the filter mean (byte_tracker.py:151-166), fp64, then the cast to fp32
+__device__ __forceinline__ void trk_tlbr(const double* m, float* o) {
+  const double w = m[2] * m[3];
+  const double x1 = m[0] - w / 2, y1 = m[1] - m[3] / 2;
+  o[0] = (float)x1;
+  o[1] = (float)y1;
+  o[2] = (float)(w + x1);
+  o[3] = (float)(m[3] + y1);
+}
+
+// convert_coords of a detection (tlbr_to_tlwh, tlwh_to_xyah): fp32 throughout
+__device__ __forceinline__ void trk_xyah(const float* d, float* z) {
+  const float w = d[2] - d[0], h = d[3] - d[1];
+  z[0] = d[0] + w / 2.0f;
+  z[1] = d[1] + h / 2.0f;
+  z[2] = w / h;
+  z[3] = h;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- Kalman filter
+__device__ void kf_initiate(double* m, double* P, const float* z) {
+  const float sp32 = (float)0.1 * z[3], sv32 = (float)0.0625 * z[3];   // 2 * (1 / 20) and 10 * (1 / 160), times an fp32 height
+  const double sp = sp32, sv = sv32;
+  const double dg[8] = {sp * sp, sp * sp, 1e-2 * 1e-2, sp * sp, sv * sv, sv * sv, 1e-5 * 1e-5, sv * sv};
+  for (int i = 0; i < 8; ++i) {
+    m[i] = i < 4 ? (double)z[i] : 0.0;
+    for (int j = 0; j < 8; ++j) P[i * 8 + j] = i == j ? dg[i] : 0.0;
+  }
+}
+
+__device__ void kf_predict(double* m, double* P, bool raw, bool not_tracked) {
+  if (not_tracked) m[7] = 0.0;
+  double q[8];
+  if (raw) {
+    const float h = (float)m[3];
+    const float sp = (float)(1.0 / 20) * h, sv = (float)(1.0 / 160) * h;
+    const float cp = (float)1e-2, cv = (float)1e-5;
+    const float qf[8] = {sp * sp, sp * sp, cp * cp, sp * sp, sv * sv, sv * sv, cv * cv, sv * sv};
+    for (int i = 0; i < 8; ++i) q[i] = qf[i];
+  } else {
+    const double sp = 1.0 / 20 * m[3], sv = 1.0 / 160 * m[3];
+    const double qd[8] = {sp * sp, sp * sp, 1e-2 * 1e-2, sp * sp, sv * sv, sv * sv, 1e-5 * 1e-5, sv * sv};
+    for (int i = 0; i < 8; ++i) q[i] = qd[i];
+  }
+  for (int i = 0; i < 4; ++i) m[i] = m[i] + m[i + 4];
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) {
+      const double A = P[i * 8 + j], Bq = P[i * 8 + j + 4], C = P[(i + 4) * 8 + j], D = P[(i + 4) * 8 + j + 4];
+      P[i * 8 + j] = (A + C) + (Bq + D);
+      P[i * 8 + j + 4] = Bq + D;
+      P[(i + 4) * 8 + j] = C + D;
+    }
+  for (int i = 0; i < 8; ++i) P[i * 9] += q[i];
+}
+
+__device__ void kf_update(double* mg, double* Pg, const float* z, bool raw) {
+  double m[8], P[64];
+  for (int i = 0; i < 8; ++i) m[i] = mg[i];
+  for (int i = 0; i < 64; ++i) P[i] = Pg[i];
+  const double sp = raw ? (double)((float)(1.0 / 20) * (float)m[3]) : 1.0 / 20 * m[3];
+  const double dg[4] = {sp * sp, sp * sp, 1e-1 * 1e-1, sp * sp};
+  double S[4][4], L[4][4];
+  for (int i = 0; i < 4; ++i)
+    for (int j = 0; j < 4; ++j) { S[i][j] = P[i * 8 + j] + (i == j ? dg[i] : 0.0); L[i][j] = 0.0; }
+  for (int j = 0; j < 4; ++j) {
+    double s = S[j][j];
+    for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
+    L[j][j] = sqrt(s);
+    for (int i = j + 1; i < 4; ++i) {
+      double t = S[i][j];
+      for (int k = 0; k < j; ++k) t -= L[i][k] * L[j][k];
+      L[i][j] = t / L[j][j];
+    }
+  }
+  double K[8][4];   // K^T = S^-1 (P H^T)^T, column by column
+  for (int i = 0; i < 8; ++i) {
+    double y[4];
+    for (int k = 0; k < 4; ++k) {
+      double t = P[i * 8 + k];
+      for (int l = 0; l < k; ++l) t -= L[k][l] * y[l];
+      y[k] = t / L[k][k];
+    }
+    for (int k = 3; k >= 0; --k) {
+      double t = y[k];
+      for (int l = k + 1; l < 4; ++l) t -= L[l][k] * K[i][l];
+      K[i][k] = t / L[k][k];
+    }
+  }
+  double inn[4], SKt[4][8];
+  for (int k = 0; k < 4; ++k) inn[k] = (double)z[k] - m[k];
+  for (int k = 0; k < 4; ++k)
+    for (int j = 0; j < 8; ++j) {
+      double t = 0.0;
+      for (int l = 0; l < 4; ++l) t += S[k][l] * K[j][l];
+      SKt[k][j] = t;
+    }
+  for (int i = 0; i < 8; ++i) {
+    double t = 0.0;
+    for (int k = 0; k < 4; ++k) t += K[i][k] * inn[k];
+    mg[i] = m[i] + t;
+    for (int j = 0; j < 8; ++j) {
+      double c = 0.0;
+      for (int k = 0; k < 4; ++k) c += K[i][k] * SKt[k][j];
+      Pg[i * 8 + j] = P[i * 8 + j] - c;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- assignment
+struct TrkCand {
+  double val;
+  int it;   // position in `remaining`
+  int un;   // 1 = column can end the path (not assigned yet, or the shared `unmatched` column)
+};
+
+__device__ __forceinline__ bool trk_cand_wins(const TrkCand& a, const TrkCand& b) {
+  if (a.val != b.val) return a.val < b.val;
+  if (a.un != b.un) return a.un > b.un;
+  return a.un ? a.it > b.it : a.it < b.it;
+}
+
+struct TrkLsap {   // LDS, sized for R <= T rows and Cn <= nq + 1 columns
+  double *u, *v, *sp;
+  int *path, *row4col, *remaining, *col4row;
+  unsigned char *SR, *SC;
+};
+
+// The partial matching of n rows and m columns that minimises sum(c_ij - L): lsap.hip's solver with the extra column m of cost L that
+// any number of rows may take.  cost is [n, m] row-major; x[i] receives the column of row i, or -1.  Called by the whole wave.
+__device__ void trk_assign(const float* cost, int n, int m, double L, const TrkLsap& w, int* x, int lane) {
+  const int Cn = m + 1;
+  for (int i = lane; i < n; i += WAVE) { w.u[i] = 0.0; w.col4row[i] = -1; }
+  for (int j = lane; j < Cn; j += WAVE) { w.v[j] = 0.0; w.row4col[j] = -1; w.path[j] = -1; }
+  __syncthreads();
+  const double INF = __longlong_as_double(0x7ff0000000000000ll);
+  bool failed = false;
+  for (int cur = 0; cur < n && !failed; ++cur) {
+    for (int i = lane; i < n; i += WAVE) w.SR[i] = 0;
+    for (int j = lane; j < Cn; j += WAVE) { w.SC[j] = 0; w.sp[j] = INF; w.remaining[j] = Cn - j - 1; }
+    __syncthreads();
+    int num_remaining = Cn, i = cur, sink = -1;
+    double minVal = 0.0;
+    while (sink == -1 && num_remaining > 0) {
+      if (lane == 0) w.SR[i] = 1;
+      const double ui = w.u[i];
+      TrkCand best{INF, 0x7fffffff, 0};
+      for (int it = lane; it < num_remaining; it += WAVE) {
+        const int j = w.remaining[it];
+        const double c = j == m ? L : (double)cost[(size_t)i * m + j];
+        const double r = ((minVal + c) - ui) - w.v[j];
+        double s = w.sp[j];
+        if (r < s) { w.path[j] = i; w.sp[j] = r; s = r; }
+        TrkCand cnd{s, it, (j == m || w.row4col[j] == -1) ? 1 : 0};
+        if (trk_cand_wins(cnd, best)) best = cnd;
+      }
+#pragma unroll
+      for (int o = WAVE / 2; o > 0; o >>= 1) {
+        TrkCand other{__shfl_xor(best.val, o, WAVE), __shfl_xor(best.it, o, WAVE), __shfl_xor(best.un, o, WAVE)};
+        if (trk_cand_wins(other, best)) best = other;
+      }
+      if (!(best.val < INF) || best.it >= num_remaining) { failed = true; break; }   // NaN costs
+      minVal = best.val;
+      const int j = w.remaining[best.it];
+      const int r4c = j == m ? -1 : w.row4col[j];
+      if (r4c == -1) sink = j; else i = r4c;
+      __syncthreads();   // every lane has read remaining[] before it is edited
+      --num_remaining;
+      if (lane == 0) { w.SC[j] = 1; w.remaining[best.it] = w.remaining[num_remaining]; }
+      __syncthreads();
+    }
+    if (failed || sink == -1) { failed = true; break; }
+    for (int r = lane; r < n; r += WAVE) {
+      if (r == cur) w.u[r] += minVal;
+      else if (w.SR[r]) w.u[r] += minVal - w.sp[w.col4row[r]];
+    }
+    for (int j = lane; j < Cn; j += WAVE)
+      if (w.SC[j]) w.v[j] -= minVal - w.sp[j];
+    __syncthreads();
+    if (lane == 0) {
+      int j = sink;
+      for (int guard = 0; guard <= n; ++guard) {
+        const int r = w.path[j];
+        if (j != m) w.row4col[j] = r;
+        const int t = w.col4row[r];
+        w.col4row[r] = j;
+        j = t;
+        if (r == cur) break;
+      }
+    }
+    __syncthreads();
+  }
+  for (int i = lane; i < n; i += WAVE) {
+    const int j = w.col4row[i];
+    x[i] = (failed || j < 0 || j >= m) ? -1 : j;
+  }
+  __syncthreads();
+}
+
+// ---------------------------------------------------------------------------------------------------------------- the tracker
+struct TrkParams {
+  const float* out;
+  const int32_t* counts;
+  int B, nq, T;
+  double* mean;
+  double* cov;
+  int32_t* meta;
+  float* sc;
+  int32_t* hdr;
+  float high, low, newt;
+  double match;
+  int max_time_lost;
+  float* tracks;
+  int32_t* tcounts;
+  unsigned char* ws;
+};
+
+static size_t trk_ws_bytes(int T, int nq) { return 4 * ((size_t)T * nq + 4 * (size_t)T + 4 * (size_t)nq + 7 * (size_t)T + 5 * (size_t)nq); }
+static size_t trk_lds_bytes(int T, int nq) {
+  const size_t R = T, Cn = (size_t)nq + 1;
+  return 8 * (R + 2 * Cn) + 4 * (3 * Cn + R) + R + Cn + 16;
+}
+
+// a matched track: STrack.update / re_activate (byte_tracker.py:112-145)
+__device__ __forceinline__ void trk_matched(const TrkParams& p, int s, const float* d, int dj, int fid, bool keep_len) {
+  int32_t* mt = p.meta + (size_t)s * 8;
+  float z[4];
+  trk_xyah(d + (size_t)dj * 6, z);
+  kf_update(p.mean + (size_t)s * 8, p.cov + (size_t)s * 64, z, mt[M_FLAGS] & TRK_RAW);
+  mt[M_FLAGS] &= ~TRK_RAW;
+  mt[M_LEN] = keep_len ? mt[M_LEN] + 1 : 0;
+  mt[M_STATE] = TRK_TRACKED;
+  mt[M_ACT] = 1;
+  mt[M_FRAME] = fid;
+  mt[M_IDX] = dj;
+  p.sc[2 * s] = d[(size_t)dj * 6 + 4];
+  p.sc[2 * s + 1] = d[(size_t)dj * 6 + 5];
+}
+
+__global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  const int lane = threadIdx.x, T = p.T, nq = p.nq;
+  TrkLsap w;
+  {
+    const int R = T, Cn = nq + 1;
+    w.u = reinterpret_cast<double*>(lds);
+    w.v = w.u + R;
+    w.sp = w.v + Cn;
+    w.path = reinterpret_cast<int*>(w.sp + Cn);
+    w.row4col = w.path + Cn;
+    w.remaining = w.row4col + Cn;
+    w.col4row = w.remaining + Cn;
+    w.SR = reinterpret_cast<unsigned char*>(w.col4row + R);
+    w.SC = w.SR + R;
+  }
+  float* cost = reinterpret_cast<float*>(p.ws);   // [T, nq]
+  float* tb = cost + (size_t)T * nq;              // tlbr of a slot's track [T, 4]
+  float* db = tb + 4 * (size_t)T;                 // tlbr of a detection [nq, 4]
+  int* pool = reinterpret_cast<int*>(db + 4 * (size_t)nq);
+  int *unconf = pool + T, *rest = unconf + T, *freel = rest + T, *xs = freel + T, *newly_lost = xs + T, *dup = newly_lost + T;
+  int *hi = dup + T, *lo = hi + nq, *left = lo + nq, *newd = left + nq, *used = newd + nq;
+
+  int fid = p.hdr[0], next_id = p.hdr[1], over = p.hdr[3];
+  for (int b = 0; b < p.B; ++b) {
+    const int nd = min(max(p.counts[b], 0), nq);
+    const float* d = p.out + (size_t)b * nq * 6;
+    float* trow = p.tracks + (size_t)b * nq * 8;
+    if (nd == 0) {   // trackers/track.py:46-47: the tracker is not called, nothing ages
+      for (int e = lane; e < nq * 8; e += WAVE) trow[e] = 0.0f;
+      if (lane == 0) p.tcounts[b] = 0;
+      continue;
+    }
+    ++fid;
+    // ---- 1. detections: their tlbr, the high and the low set
+    for (int j = lane; j < nd; j += WAVE) {
+      const float* r = d + (size_t)j * 6;
+      db[4 * j] = r[0];
+      db[4 * j + 1] = r[1];
+      db[4 * j + 2] = (r[2] - r[0]) + r[0];
+      db[4 * j + 3] = (r[3] - r[1]) + r[1];
+      used[j] = 0;
+    }
+    const int nhi = trk_compact(nd, hi, lane, [&](int j) { return d[(size_t)j * 6 + 4] > p.high; });
+    const int nlo = trk_compact(nd, lo, lane, [&](int j) { const float s = d[(size_t)j * 6 + 4]; return s > p.low && s < p.high; });
+    // ---- 2. unconfirmed tracks and the pool (activated tracked + lost), in slot order
+    const int nun = trk_compact(T, unconf, lane, [&](int s) { return p.meta[s * 8 + M_STATE] == TRK_TRACKED && !p.meta[s * 8 + M_ACT]; });
+    const int npool = trk_compact(T, pool, lane, [&](int s) {
+      const int st = p.meta[s * 8 + M_STATE];
+      return (st == TRK_TRACKED && p.meta[s * 8 + M_ACT]) || st == TRK_LOST || st == TRK_LIMBO;
+    });
+    for (int s = lane; s < T; s += WAVE) { newly_lost[s] = 0; dup[s] = 0; }
+    __syncthreads();
+    // ---- 3. predict the pool (not the unconfirmed tracks)
+    for (int i = lane; i < npool; i += WAVE) {
+      const int s = pool[i];
+      int32_t* mt = p.meta + (size_t)s * 8;
+      kf_predict(p.mean + (size_t)s * 8, p.cov + (size_t)s * 64, mt[M_FLAGS] & TRK_RAW, mt[M_STATE] != TRK_TRACKED);
+      mt[M_FLAGS] &= ~TRK_RAW;
+      trk_tlbr(p.mean + (size_t)s * 8, tb + 4 * s);
+    }
+    for (int i = lane; i < nun; i += WAVE) trk_tlbr(p.mean + (size_t)unconf[i] * 8, tb + 4 * unconf[i]);
+    __syncthreads();
+    // ---- 4. first association: pool x high detections, fused distance, match_thresh
+    if (npool > 0 && nhi > 0) {
+      for (int e = lane; e < npool * nhi; e += WAVE) {
+        const int i = e / nhi, j = e - i * nhi, dj = hi[j];
+        const float dist = 1.0f - trk_iou(tb + 4 * pool[i], db + 4 * dj);
+        cost[e] = 1.0f - (1.0f - dist) * d[(size_t)dj * 6 + 4];
+      }
+      __syncthreads();
+      trk_assign(cost, npool, nhi, p.match, w, xs, lane);
+    } else {
+      for (int i = lane; i < npool; i += WAVE) xs[i] = -1;
+      __syncthreads();
+    }
+    for (int i = lane; i < npool; i += WAVE) {
+      const int j = xs[i];
+      if (j >= 0) {
+        const int s = pool[i];
+        trk_matched(p, s, d, hi[j], fid, p.meta[s * 8 + M_STATE] == TRK_TRACKED);
+        used[hi[j]] = 1;
+      }
+    }
+    __syncthreads();
+    // ---- 5. second association: the unmatched pool tracks in state Tracked x low detections, plain IoU distance, 0.5
+    const int nrest = trk_compact(npool, rest, lane, [&](int i) { return xs[i] < 0 && p.meta[pool[i] * 8 + M_STATE] == TRK_TRACKED; });
+    __syncthreads();
+    if (nrest > 0 && nlo > 0) {
+      for (int e = lane; e < nrest * nlo; e += WAVE) {
+        const int i = e / nlo, j = e - i * nlo;
+        cost[e] = 1.0f - trk_iou(tb + 4 * pool[rest[i]], db + 4 * lo[j]);
+      }
+      __syncthreads();
+      trk_assign(cost, nrest, nlo, 0.5, w, xs, lane);
+    } else {
+      for (int i = lane; i < nrest; i += WAVE) xs[i] = -1;
+      __syncthreads();
+    }
+    for (int i = lane; i < nrest; i += WAVE) {
+      const int s = pool[rest[i]], j = xs[i];
+      if (j >= 0) {
+        trk_matched(p, s, d, lo[j], fid, true);
+      } else if (p.meta[s * 8 + M_FLAGS] & TRK_EVER_REMOVED) {
+        p.meta[s * 8 + M_STATE] = TRK_FREE;
+      } else {
+        p.meta[s * 8 + M_STATE] = TRK_LOST;
+        newly_lost[s] = 1;
+      }
+    }
+    __syncthreads();
+    // ---- 6. unconfirmed tracks x the high detections still free, fused distance, 0.7; the unmatched ones are removed
+    const int nleft = trk_compact(nhi, left, lane, [&](int k) { return !used[hi[k]]; });
+    __syncthreads();
+    if (nun > 0 && nleft > 0) {
+      for (int e = lane; e < nun * nleft; e += WAVE) {
+        const int i = e / nleft, j = e - i * nleft, dj = hi[left[j]];
+        const float dist = 1.0f - trk_iou(tb + 4 * unconf[i], db + 4 * dj);
+        cost[e] = 1.0f - (1.0f - dist) * d[(size_t)dj * 6 + 4];
+      }
+      __syncthreads();
+      trk_assign(cost, nun, nleft, 0.7, w, xs, lane);
+    } else {
+      for (int i = lane; i < nun; i += WAVE) xs[i] = -1;
+      __syncthreads();
+    }
+    for (int i = lane; i < nun; i += WAVE) {
+      const int s = unconf[i], j = xs[i];
+      if (j >= 0) {
+        trk_matched(p, s, d, hi[left[j]], fid, true);
+        used[hi[left[j]]] = 1;
+      } else {
+        p.meta[s * 8 + M_STATE] = TRK_FREE;
+      }
+    }
+    __syncthreads();
+    // ---- 7. new tracks from what is left, score >= new_track_thresh, into the lowest free slots
+    const int nnew = trk_compact(nleft, newd, lane, [&](int k) { const int dj = hi[left[k]]; return !used[dj] && !(d[(size_t)dj * 6 + 4] < p.newt); });
+    const int nfree = trk_compact(T, freel, lane, [&](int s) { return p.meta[s * 8 + M_STATE] == TRK_FREE; });
+    __syncthreads();
+    const int ncreate = min(nnew, nfree);
+    over += nnew - ncreate;
+    for (int k = lane; k < ncreate; k += WAVE) {
+      const int s = freel[k], dj = hi[left[newd[k]]];
+      float z[4];
+      trk_xyah(d + (size_t)dj * 6, z);
+      kf_initiate(p.mean + (size_t)s * 8, p.cov + (size_t)s * 64, z);
+      int32_t* mt = p.meta + (size_t)s * 8;
+      mt[M_STATE] = TRK_TRACKED;
+      mt[M_ACT] = fid == 1;
+      mt[M_ID] = next_id + k;
+      mt[M_FRAME] = fid;
+      mt[M_START] = fid;
+      mt[M_LEN] = 0;
+      mt[M_IDX] = dj;
+      mt[M_FLAGS] = TRK_RAW;
+      p.sc[2 * s] = d[(size_t)dj * 6 + 4];
+      p.sc[2 * s + 1] = d[(size_t)dj * 6 + 5];
+    }
+    next_id += ncreate;
+    __syncthreads();
+    // ---- 8. lost tracks age out; one removed a frame ago leaves now
+    for (int s = lane; s < T; s += WAVE) {
+      int32_t* mt = p.meta + (size_t)s * 8;
+      if (mt[M_STATE] == TRK_LIMBO) {
+        mt[M_STATE] = TRK_FREE;
+      } else if (mt[M_STATE] == TRK_LOST && !newly_lost[s] && fid - mt[M_FRAME] > p.max_time_lost) {
+        mt[M_STATE] = TRK_LIMBO;
+        mt[M_FLAGS] |= TRK_EVER_REMOVED;
+      }
+    }
+    __syncthreads();
+    // ---- 9. duplicates: tracked x lost with distance < 0.15; the younger side goes, the tracked side on equal age
+    const int nA = trk_compact(T, pool, lane, [&](int s) { return p.meta[s * 8 + M_STATE] == TRK_TRACKED; });
+    const int nB = trk_compact(T, unconf, lane, [&](int s) { const int st = p.meta[s * 8 + M_STATE]; return st == TRK_LOST || st == TRK_LIMBO; });
+    for (int s = lane; s < T; s += WAVE)
+      if (p.meta[s * 8 + M_STATE] != TRK_FREE) trk_tlbr(p.mean + (size_t)s * 8, tb + 4 * s);
+    __syncthreads();
+    for (int e = lane; e < nA * nB; e += WAVE) {
+      const int i = e / nB, sa = pool[i], sb = unconf[e - i * nB];
+      if (1.0f - trk_iou(tb + 4 * sa, tb + 4 * sb) < (float)0.15) {
+        const int tp = p.meta[sa * 8 + M_FRAME] - p.meta[sa * 8 + M_START], tq = p.meta[sb * 8 + M_FRAME] - p.meta[sb * 8 + M_START];
+        dup[tp > tq ? sb : sa] = 1;
+      }
+    }
+    __syncthreads();
+    for (int s = lane; s < T; s += WAVE)
+      if (dup[s]) p.meta[s * 8 + M_STATE] = TRK_FREE;
+    __syncthreads();
+    // ---- 10. rows: the activated tracks in state Tracked, in slot order; zero after the count
+    int cnt = trk_compact(T, rest, lane, [&](int s) { return p.meta[s * 8 + M_STATE] == TRK_TRACKED && p.meta[s * 8 + M_ACT]; });
+    cnt = min(cnt, nq);
+    __syncthreads();
+    for (int k = lane; k < cnt; k += WAVE) {
+      const int s = rest[k];
+      float* r = trow + (size_t)k * 8;
+      r[0] = tb[4 * s]; r[1] = tb[4 * s + 1]; r[2] = tb[4 * s + 2]; r[3] = tb[4 * s + 3];
+      r[4] = (float)p.meta[s * 8 + M_ID];
+      r[5] = p.sc[2 * s];
+      r[6] = p.sc[2 * s + 1];
+      r[7] = (float)p.meta[s * 8 + M_IDX];
+    }
+    for (int e = cnt * 8 + lane; e < nq * 8; e += WAVE) trow[e] = 0.0f;
+    if (lane == 0) p.tcounts[b] = cnt;
+    __syncthreads();
+  }
+  int live = 0;
+  for (int s0 = 0; s0 < T; s0 += WAVE) live += __popcll(__ballot(s0 + lane < T && p.meta[(s0 + lane) * 8 + M_STATE] != TRK_FREE));
+  if (lane == 0) { p.hdr[0] = fid; p.hdr[1] = next_id; p.hdr[2] = live; p.hdr[3] = over; }
+}
+
+extern "C" int tamtr_bytetrack_workspace_bytes(int T, int nq) {
+  if (T < 1 || nq < 1) return 0;
+  const size_t n = trk_ws_bytes(T, nq);
+  return n > 0x7fffffff ? 0 : (int)n;
+}
+
+extern "C" int tamtr_bytetrack_update(const float* out, const int32_t* counts, int B, int nq, double* mean, double* cov, int32_t* meta,
+                                      float* sc, int32_t* hdr, int T, float track_high_thresh, float track_low_thresh,
+                                      float new_track_thresh, double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts,
+                                      void* workspace, int workspace_bytes, void* stream) {
+  if (!out || !counts || !mean || !cov || !meta || !sc || !hdr || !tracks || !tcounts || !workspace || B < 1 || nq < 1 || T < 1)
+    return TAMTR_EINVAL;
+  if (tamtr_bytetrack_workspace_bytes(T, nq) == 0 || trk_lds_bytes(T, nq) > 64 * 1024) return TAMTR_EUNSUP;
+  if (workspace_bytes < tamtr_bytetrack_workspace_bytes(T, nq)) return TAMTR_EINVAL;
+  TrkParams p{out, counts, B, nq, T, mean, cov, meta, sc, hdr, track_high_thresh, track_low_thresh, new_track_thresh, match_thresh,
+              max_time_lost, tracks, tcounts, static_cast<unsigned char*>(workspace)};
+  hipLaunchKernelGGL(bytetrack_kernel, dim3(1), dim3(WAVE), trk_lds_bytes(T, nq), (hipStream_t)stream, p);
+  return tamtr_launch_status();
+}

@@ -1872,6 +1872,56 @@ def detect_postprocess(y, orig_hw, conf, iou, classes=None, single_cls=False, ma
     return out, keep, counts
 
 
+TRACK_STATE_SPEC = (('mean', torch.float64, (8,)), ('cov', torch.float64, (8, 8)), ('meta', torch.int32, (8,)), ('sc', torch.float32, (2,)))
+
+
+def bytetrack_workspace_bytes(capacity, nq):
+    """Bytes of device workspace tamtr_bytetrack_update needs for a table of `capacity` slots and nq rows per frame (no GPU call)."""
+    n = _lib.lib().tamtr_bytetrack_workspace_bytes(int(capacity), int(nq))
+    if n <= 0:
+        raise _lib.TamtrHipError(f'bytetrack: capacity {capacity} with nq {nq} is outside what the kernel is built for')
+    return n
+
+
+def bytetrack_update(out, counts, state, capacity, track_high_thresh=0.5, track_low_thresh=0.1, new_track_thresh=0.6, match_thresh=0.8,
+                     max_time_lost=30, workspace=None):
+    """BYTETracker.update (trackers/byte_tracker.py:238-351) for the B frames of a batch, in order, in one launch; the rule is stated
+    in csrc/track.hip.  out f32 [B, nq, 6] and counts i32 [B] are detect_postprocess's outputs on the GPU; state: the tracker's table,
+    a dict of device tensors mean f64 [T, 8], cov f64 [T, 8, 8], meta i32 [T, 8], sc f32 [T, 2], hdr i32 [8] with T = capacity,
+    updated in place.  Returns device tensors tracks f32 [B, nq, 8] (x1 y1 x2 y2 id score cls idx, zero after the count) and
+    tcounts i32 [B].  hdr[3] counts the new tracks that found no free slot.  Every check comes before the launch; no synchronisation."""
+    if out.dim() != 3 or out.shape[-1] != 6 or out.shape[0] < 1 or out.shape[1] < 1:
+        raise _lib.TamtrHipError(f'bytetrack_update: expected out [B, nq, 6], got {tuple(out.shape)}')
+    B, nq, _ = out.shape
+    if tuple(counts.shape) != (B,):
+        raise _lib.TamtrHipError(f'bytetrack_update: counts must be [B] = [{B}], got {tuple(counts.shape)}')
+    if out.dtype != torch.float32 or counts.dtype != torch.int32:
+        raise _lib.TamtrHipError(f'bytetrack_update: out must be float32 and counts int32, got {out.dtype} and {counts.dtype}')
+    T = int(capacity)
+    if T < 1:
+        raise _lib.TamtrHipError(f'bytetrack_update: capacity must be positive, got {capacity}')
+    for k, dt, tail in TRACK_STATE_SPEC + (('hdr', torch.int32, None),):
+        t = state.get(k) if isinstance(state, dict) else None
+        want = (8,) if tail is None else (T,) + tail
+        if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
+            got = None if t is None else (t.dtype, tuple(t.shape))
+            raise _lib.TamtrHipError(f'bytetrack_update: state[{k!r}] must be a contiguous {dt} tensor of shape {want} (capacity {T}), got {got}')
+    require_gpu(out, counts, *(state[k] for k in ('mean', 'cov', 'meta', 'sc', 'hdr')))
+    need = bytetrack_workspace_bytes(T, nq)
+    if workspace is None:
+        workspace = torch.empty(need, device=out.device, dtype=torch.uint8)
+    require_gpu(workspace)
+    if workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
+        raise _lib.TamtrHipError(f'bytetrack_update: workspace must be a contiguous uint8 tensor of at least {need} bytes')
+    out, counts = _c(out), _c(counts)
+    tracks = torch.empty(B, nq, 8, device=out.device, dtype=torch.float32)
+    tcounts = torch.empty(B, device=out.device, dtype=torch.int32)
+    call('tamtr_bytetrack_update', ptr(out), ptr(counts), B, nq, ptr(state['mean']), ptr(state['cov']), ptr(state['meta']), ptr(state['sc']),
+         ptr(state['hdr']), T, float(track_high_thresh), float(track_low_thresh), float(new_track_thresh), float(match_thresh),
+         int(max_time_lost), ptr(tracks), ptr(tcounts), ptr(workspace), int(workspace.numel()), stream_ptr())
+    return tracks, tcounts
+
+
 @torch.no_grad()
 def val_postprocess_match(y, cls, bboxes, batch_idx, ori_hw, imgsz, conf, iou, single_cls=False, max_wh=7680., return_device_labels=False):
     """engine.Validator.update's per-image work (RTDETRValidator.postprocess, models/rtdetrworld/val.py:102-173, and match_predictions,

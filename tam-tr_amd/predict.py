@@ -78,12 +78,13 @@ def to_model_input(ims_u8, device):
 # ------------------------------------------------------------------------------------------------ results
 class Detections:
     """The boxes of one image (engine/results.py Results + Boxes, detection only): boxes f32 [n, 6] on the host, x1 y1 x2 y2 in
-    pixels of the original image, score, class."""
+    pixels of the original image, score, class.  id: i64 [n] track ids from Predictor.track, else None."""
 
-    def __init__(self, path, orig_shape, names, boxes, orig_img=None):
+    def __init__(self, path, orig_shape, names, boxes, orig_img=None, id=None):
         self.path, self.orig_shape, self.names = path, tuple(orig_shape), names
         self.boxes = boxes
         self.orig_img = orig_img
+        self.id = id
 
     def __len__(self):
         return len(self.boxes)
@@ -114,27 +115,29 @@ class Detections:
         return y
 
     def save_txt(self, txt_file, save_conf=False):
-        """`cls x y w h [conf]` per box, '%g'-formatted, appended; no file when there is no box (engine/results.py:278-311)."""
+        """`cls x y w h [conf] [id]` per box, '%g'-formatted, appended; no file when there is no box (engine/results.py:278-311)."""
         if not len(self):
             return
         texts = []
-        for c, xywhn, conf in zip(self.cls.tolist(), self.xywhn.tolist(), self.conf.tolist()):
-            line = (int(c), *xywhn) + (conf,) * save_conf
+        ids = [None] * len(self) if self.id is None else self.id.tolist()
+        for c, xywhn, conf, tid in zip(self.cls.tolist(), self.xywhn.tolist(), self.conf.tolist(), ids):
+            line = (int(c), *xywhn) + (conf,) * save_conf + (() if tid is None else (int(tid),))
             texts.append(('%g ' * len(line)).rstrip() % line)
         Path(txt_file).parent.mkdir(parents=True, exist_ok=True)
         with open(txt_file, 'a') as f:
             f.writelines(t + '\n' for t in texts)
 
     def save(self, path, line_width=None):
-        """An annotated copy of the original image (boxes and `name score` labels, drawn with PIL)."""
+        """An annotated copy of the original image (boxes and `name score` labels, `id:<n> name score` with track ids; drawn with PIL)."""
         from PIL import Image, ImageDraw
         im = Image.fromarray(self.orig_img if self.orig_img is not None else D.decode_image(self.path))
         draw = ImageDraw.Draw(im)
         lw = line_width or max(round(sum(im.size) / 2 * 0.003), 2)
-        for (x1, y1, x2, y2), conf, c in zip(self.xyxy.tolist(), self.conf.tolist(), self.cls.tolist()):
+        ids = [None] * len(self) if self.id is None else self.id.tolist()
+        for (x1, y1, x2, y2), conf, c, tid in zip(self.xyxy.tolist(), self.conf.tolist(), self.cls.tolist(), ids):
             color = _COLORS[int(c) % len(_COLORS)]
             draw.rectangle((x1, y1, x2, y2), outline=color, width=lw)
-            label = f'{self.names.get(int(c), int(c))} {conf:.2f}'
+            label = ('' if tid is None else f'id:{int(tid)} ') + f'{self.names.get(int(c), int(c))} {conf:.2f}'
             l, t, r, b = draw.textbbox((x1, y1), label)
             top = y1 - (b - t) - 2 if y1 - (b - t) - 2 >= 0 else y1
             draw.rectangle((x1, top, x1 + (r - l) + 2, top + (b - t) + 2), fill=color)
@@ -176,15 +179,18 @@ class Predictor:
         model.set_text_features(tf.reshape(1, len(self.names), -1).to(self.device))
         model.autocast_dtype = self.autocast_dtype
         self.model = model
-        self.times = {'load': 0.0, 'h2d': 0.0, 'forward': 0.0, 'postprocess': 0.0, 'd2h': 0.0}   # ms, summed over batches
+        self.times = {'load': 0.0, 'h2d': 0.0, 'forward': 0.0, 'postprocess': 0.0, 'track': 0.0, 'd2h': 0.0}   # ms, summed over batches
         self.seen = 0
+        self.tracker = None
         self.last_img = self.last_y = None
 
     @torch.no_grad()
-    def run_batch(self, ims):
-        """Network inputs u8 [B, S, S, 3] (host) + original (h, w) per image -> host (out [B, nq, 6], keep [B, nq], counts [B])."""
+    def run_batch(self, ims, tracker=None):
+        """Network inputs u8 [B, S, S, 3] (host) + original (h, w) per image -> host (out [B, nq, 6], keep [B, nq], counts [B]).
+        With a tracker (track.ByteTracker) the batch's frames also go through one tracker launch, and its rows ride in the same copy:
+        -> host (out, keep, counts, tracks [B, nq, 8], tcounts [B])."""
         arr, hw = ims
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(5)]
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
         ev[0].record()
         img = to_model_input(arr, self.device)
         ev[1].record()
@@ -194,23 +200,50 @@ class Predictor:
         ev[2].record()
         out, keep, counts = ops.detect_postprocess(y, hw, self.conf, self.iou, self.classes, self.single_cls)
         ev[3].record()
-        # one device-to-host copy for the three outputs
+        # one device-to-host copy for all the outputs
         B, nq = keep.shape
-        packed = torch.cat([out.view(-1), keep.view(torch.float32).view(-1), counts.view(torch.float32)])
+        parts = [out.view(-1), keep.view(torch.float32).view(-1), counts.view(torch.float32)]
+        if tracker is not None:
+            tracks, tcounts = tracker.update(out, counts)
+            parts += [tracks.view(-1), tcounts.view(torch.float32), tracker.state['hdr'].view(torch.float32)]
+        ev[4].record()
+        packed = torch.cat(parts)
         host = torch.empty(packed.shape, dtype=torch.float32, pin_memory=True)
         host.copy_(packed, non_blocking=True)
-        ev[4].record()
-        ev[4].synchronize()
-        for k, (a, b) in zip(('h2d', 'forward', 'postprocess', 'd2h'), zip(ev[:-1], ev[1:])):
+        ev[5].record()
+        ev[5].synchronize()
+        for k, (a, b) in zip(('h2d', 'forward', 'postprocess', 'track', 'd2h'), zip(ev[:-1], ev[1:])):
             self.times[k] += a.elapsed_time(b)
         if self.keep_raw:
             self.last_img, self.last_y = img, y
-        o, kp, c = host.split([B * nq * 6, B * nq, B])
-        return o.view(B, nq, 6), kp.view(torch.int32).view(B, nq), c.view(torch.int32)
+        o, kp, c, rest = host.split([B * nq * 6, B * nq, B, host.numel() - B * nq * 7 - B])
+        res = o.view(B, nq, 6), kp.view(torch.int32).view(B, nq), c.view(torch.int32)
+        if tracker is None:
+            return res
+        tr, tc, hdr = rest.split([B * nq * 8, B, 8])
+        tracker.check_overflow(hdr.view(torch.int32)[3])
+        return res + (tr.view(B, nq, 8), tc.view(torch.int32))
 
     def predict(self, source):
         """Yields one Detections per image, in the sorted order of list_sources(source)."""
-        files = list_sources(source)
+        yield from self._run(list_sources(source), None)
+
+    def track(self, source, tracker=None, persist=False):
+        """The sorted files of `source` as ONE sequence (the reference's model.track): the batches of predict, then one tracker launch
+        per batch.  Yields one Detections per frame whose boxes are the track rows (x1 y1 x2 y2 from the filter, score, cls) and
+        whose `id` holds the track ids; a frame for which the tracker returned nothing keeps its plain detections and id None
+        (trackers/track.py:46-50).  tracker: a track.ByteTracker, a bytetrack.yaml path, or None for the defaults; persist=True keeps
+        the tracker (and its tracks) of the previous call."""
+        from .track import ByteTracker
+        if isinstance(tracker, ByteTracker):
+            self.tracker = tracker
+            if not persist:
+                tracker.reset()
+        elif self.tracker is None or not persist:
+            self.tracker = ByteTracker.from_yaml(tracker, self.device) if tracker else ByteTracker(self.device)
+        yield from self._run(list_sources(source), self.tracker)
+
+    def _run(self, files, tracker):
         with ThreadPoolExecutor(max_workers=self.workers) as pool:
             chunks = [files[i:i + self.batch] for i in range(0, len(files), self.batch)]
             pending = [pool.submit(load_image, f, self.imgsz) for f in chunks[0]] if chunks else []
@@ -222,11 +255,16 @@ class Predictor:
                 pending = [pool.submit(load_image, f, self.imgsz) for f in chunks[k + 1]] if k + 1 < len(chunks) else []
                 origs = [o for o, _ in loaded]
                 hw = [o.shape[:2] for o in origs]
-                out, keep, counts = self.run_batch((np.stack([r for _, r in loaded]), hw))
+                res = self.run_batch((np.stack([r for _, r in loaded]), hw), tracker)
+                out, counts = res[0], res[2]
                 self.seen += len(chunk)
                 for i, path in enumerate(chunk):
-                    n = int(counts[i])
-                    yield Detections(path, hw[i], self.names, out[i, :n].clone(), orig_img=origs[i])
+                    n, nt = int(counts[i]), int(res[4][i]) if tracker is not None else 0
+                    if nt:
+                        rows = res[3][i, :nt]
+                        yield Detections(path, hw[i], self.names, rows[:, [0, 1, 2, 3, 5, 6]].clone(), orig_img=origs[i], id=rows[:, 4].long())
+                    else:
+                        yield Detections(path, hw[i], self.names, out[i, :n].clone(), orig_img=origs[i])
 
     def __call__(self, source):
         return list(self.predict(source))

@@ -7,7 +7,12 @@
   (b) the predictor end to end at 640 x 640, bf16, batch 4 and 16, from synthetic JPEG files: images/s and ms/image split into
       load (waiting for decode + resize), H2D, forward, postprocess and D2H (device events).
 
-    python tools/predict_bench.py [--images 64] [--kernel-only]
+  (c) --track: the tracker on a seeded synthetic sequence (tests/bytetrack_np.make_scene), per frame: the device path (one
+      tamtr_bytetrack_update launch per batch of 4 frames, device events) against a host path on the same detections - one
+      device-to-host copy of the batch's detections plus the numpy twin tests/bytetrack_np.py per frame (host clock).  The host side
+      is numpy with scipy's assignment, NOT the reference's tracker with `lap`.
+
+    python tools/predict_bench.py [--images 64] [--kernel-only] [--track]
 --kernel-only runs only the kernel loop of (a), for a `rocprofv3 --kernel-trace --stats` run of its own.
 """
 import argparse
@@ -137,14 +142,63 @@ def bench_predictor(n_images, batches, conf=1e-5):
     return rows
 
 
+def bench_track(n_obj, frames=240, B=4, nq=300, capacity=1024):
+    """-> one row: ms per frame of the tracker launch (device events) and of the host path (copy + numpy twin, host clock)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+    import bytetrack_np as T
+    from tamtr_amd.track import ByteTracker
+    scene = T.make_scene(1, n_obj=n_obj, frames=frames, fp_every=3, gaps=[(o, 20 + 7 * o, 5 + 10 * (o % 4)) for o in range(min(n_obj, 8))])
+    out = np.zeros((frames, nq, 6), np.float32)
+    for i, f in enumerate(scene):
+        out[i, :len(f)] = f
+    out_d = torch.from_numpy(out).cuda()
+    cnt_d = torch.tensor([len(f) for f in scene], dtype=torch.int32).cuda()
+    trk = ByteTracker('cuda', capacity=capacity, nq=nq)
+
+    def device_pass():
+        trk.reset()
+        for i in range(0, frames, B):
+            res = trk.update(out_d[i:i + B], cnt_d[i:i + B])
+        return res
+
+    t_dev, n_dev = timed(device_pass, min_s=1.0, warmup=2, chunk=2)
+    sd = trk.state_dict()
+    trk.check_overflow(sd['hdr'][3])
+
+    def host_pass():
+        twin = T.ByteTrackNp(capacity=capacity)
+        rows = 0
+        for i in range(0, frames, B):
+            o, c = out_d[i:i + B].cpu().numpy(), cnt_d[i:i + B].cpu().numpy()      # the copy the reference makes per frame, here per batch
+            for b in range(len(c)):
+                rows += len(twin.update(o[b, :c[b]]))
+        return twin, rows
+
+    host_pass()
+    t0 = time.perf_counter()
+    twin, rows = host_pass()
+    t_host = (time.perf_counter() - t0) * 1e3
+    assert np.array_equal(sd['hdr'], twin.state['hdr']), (sd['hdr'], twin.state['hdr'])     # the two paths tracked the same thing
+    return {'objects': n_obj, 'frames': frames, 'frames_per_launch': B, 'nq': nq, 'capacity': capacity,
+            'detections_per_frame': round(float(np.mean([len(f) for f in scene])), 1), 'track_rows': rows, 'ids': int(sd['hdr'][1]) - 1,
+            'device_launch_ms_per_frame': round(t_dev / frames, 4), 'host_copy_plus_numpy_twin_ms_per_frame': round(t_host / frames, 3),
+            'device_passes_timed': n_dev}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--images', type=int, default=64)
     ap.add_argument('--kernel-only', action='store_true')
+    ap.add_argument('--track', action='store_true', help='only (c): the tracker launch against copy + numpy twin')
     args = ap.parse_args()
     import tamtr_amd  # noqa: F401
     assert torch.cuda.is_available(), 'predict_bench needs an MI355X'
     print(torch.cuda.get_device_name(0), 'torch', torch.__version__)
+    if args.track:
+        print('(c) tracker per frame: one launch per 4 frames (device events) vs device-to-host copy + numpy twin (host clock; numpy and scipy, not the reference with lap)')
+        for n_obj in (24, 100):
+            print(json.dumps(bench_track(n_obj)))
+        return
     if args.kernel_only:
         print(json.dumps({'postprocess_kernel_only': bench_postprocess(True)}))
         return

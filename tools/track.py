@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""Track objects through image sequences (the reference's model.track flow with ByteTrack): per frame the boxes of the confirmed
+tracks with their ids; optional annotated copies, YOLO-format label files with the id appended, and one VisDrone-MOT result file per
+sequence, under an incremented --project/--name folder; one JSON line at the end.
+
+    python tools/track.py --weights runs/train/TAMTR/best.pt --text-feats clip_vitb32.npz --data dataset.yaml \
+        --source sequences/ [--tracker bytetrack.yaml] --conf 0.1 --batch 4 --save-mot [--save --save-txt --save-conf]
+
+--source is a directory of frames (one sequence, frames in sorted order) or a directory of sequence directories (the VisDrone-MOT
+`sequences/<name>/` layout); the tracker is reset for every sequence.  --save-mot writes <save_dir>/<sequence>.txt with lines
+`frame,id,left,top,width,height,score,category,-1,-1`, frames 1-based.  Only `tracker_type: bytetrack` is built.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description='TAM-TR multi-object tracking on image sequences (one HIP tracker launch per batch)')
+    ap.add_argument('--weights', required=True, help="checkpoint written by training ({'model', 'ema', ...} state_dicts)")
+    ap.add_argument('--raw', action='store_true', help='use the raw weights instead of the EMA copy')
+    ap.add_argument('--text-feats', help='.npz {texts, feats} or a torch-saved {text: vector}; or give --clip-weights and --clip-vocab')
+    ap.add_argument('--clip-weights', help='CLIP ViT-B/32 checkpoint (state_dict or TorchScript archive): class names are encoded here')
+    ap.add_argument('--clip-vocab', help="CLIP's BPE merges file (bpe_simple_vocab_16e6.txt.gz), with --clip-weights")
+    g = ap.add_mutually_exclusive_group(required=True)
+    g.add_argument('--data', help="dataset yaml whose 'names' are the classes")
+    g.add_argument('--names', help='comma-separated class names')
+    ap.add_argument('--source', required=True, help='a directory of frames, or a directory of sequence directories')
+    ap.add_argument('--tracker', help="tracker yaml with the reference's keys (cfg/trackers/bytetrack.yaml); default: its values")
+    ap.add_argument('--capacity', type=int, default=1024, help='tracks the device table holds')
+    ap.add_argument('--imgsz', type=int, default=640)
+    ap.add_argument('--batch', type=int, default=4)
+    ap.add_argument('--conf', type=float, default=0.1, help='keep it at or below track_low_thresh so the second association has input')
+    ap.add_argument('--iou', type=float, default=0.7)
+    ap.add_argument('--classes', type=int, nargs='+', default=None, help='keep only these class ids')
+    ap.add_argument('--single-cls', action='store_true', help='class-agnostic NMS')
+    ap.add_argument('--save', action='store_true', help='write annotated frames (id:<n> name score)')
+    ap.add_argument('--save-txt', action='store_true', help='write labels/<sequence>/<stem>.txt: cls x y w h [conf] id')
+    ap.add_argument('--save-conf', action='store_true', help='put the score before the id on every label line')
+    ap.add_argument('--save-mot', action='store_true', help='write <sequence>.txt in the VisDrone-MOT result format')
+    ap.add_argument('--project', default='runs/track')
+    ap.add_argument('--name', default='TAMTR')
+    ap.add_argument('--exist-ok', action='store_true', help='reuse --project/--name instead of incrementing it')
+    ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
+    args = ap.parse_args(argv)
+    if (args.text_feats is None) == (args.clip_weights is None and args.clip_vocab is None) or (args.clip_weights is None) != (args.clip_vocab is None):
+        ap.error('give either --text-feats, or --clip-weights together with --clip-vocab (not both, not neither)')
+    return args
+
+
+def list_sequences(source, is_image):
+    """-> [(name, directory)]: the sub-directories of `source` that hold frames, sorted; `source` itself when it holds frames."""
+    source = os.path.abspath(source)
+    if not os.path.isdir(source):
+        raise FileNotFoundError(f'{source} is not a directory')
+    if any(is_image(os.path.join(source, f)) for f in os.listdir(source)):
+        return [(os.path.basename(source.rstrip(os.sep)), source)]
+    seqs = [(d, os.path.join(source, d)) for d in sorted(os.listdir(source)) if os.path.isdir(os.path.join(source, d))]
+    if not seqs:
+        raise FileNotFoundError(f'no frames and no sequence directories in {source}')
+    return seqs
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import torch
+    import tamtr_amd  # noqa: F401
+    from tamtr_amd import data as D
+    from tamtr_amd.model import RTDETRDetectionWorldModel
+    from tamtr_amd.predict import Predictor, increment_path, is_image_file
+    from tamtr_amd.track import ByteTracker, write_mot
+    from predict import load_names
+
+    dev = torch.device('cuda', 0)
+    names = load_names(args)
+    model = RTDETRDetectionWorldModel(nc=len(names)).to(dev)
+    ck = torch.load(args.weights, map_location=dev)
+    model.load_state_dict(ck['model' if args.raw else 'ema'])
+    pred = Predictor(model, names, D.TextFeatures.from_args(args.text_feats, args.clip_weights, args.clip_vocab, dev), imgsz=args.imgsz, conf=args.conf,
+                     iou=args.iou, classes=args.classes, single_cls=args.single_cls, batch=args.batch, dtype=args.dtype)
+    tracker = ByteTracker.from_yaml(args.tracker, dev, capacity=args.capacity) if args.tracker else ByteTracker(dev, capacity=args.capacity)
+    save_dir = increment_path(os.path.join(args.project, args.name), exist_ok=args.exist_ok)
+    saving = args.save or args.save_txt or args.save_mot
+    if saving:
+        save_dir.mkdir(parents=True, exist_ok=True)
+    n_img = n_rows = n_ids = 0
+    t0 = time.perf_counter()
+    seqs = list_sequences(args.source, is_image_file)
+    for name, folder in seqs:
+        frames, ids = [], set()
+        for det in pred.track(folder, tracker=tracker):     # persist=False: the tracker is reset for the sequence
+            n_img += 1
+            stem = os.path.splitext(os.path.basename(det.path))[0]
+            if det.id is not None:
+                n_rows += len(det)
+                ids.update(det.id.tolist())
+            if args.save_txt:
+                det.save_txt(save_dir / 'labels' / name / f'{stem}.txt', save_conf=args.save_conf)
+            if args.save:
+                det.save(save_dir / name / os.path.basename(det.path))
+            det.orig_img = None
+            frames.append(det)
+        n_ids += len(ids)
+        if args.save_mot:
+            write_mot(save_dir / f'{name}.txt', frames)
+    wall = time.perf_counter() - t0
+    sp = pred.speed()
+    print(json.dumps({'sequences': len(seqs), 'images': n_img, 'track_rows': n_rows, 'ids': n_ids, 'save_dir': str(save_dir) if saving else None,
+                      'ms_per_image': {'load': round(sp['load'], 3), 'forward': round(sp['h2d'] + sp['forward'], 3),
+                                       'postprocess': round(sp['postprocess'], 3), 'track': round(sp['track'], 4), 'd2h': round(sp['d2h'], 3)},
+                      'wall_s': round(wall, 3), 'dtype': args.dtype, 'imgsz': args.imgsz, 'batch': args.batch}))
+
+
+if __name__ == '__main__':
+    main()
