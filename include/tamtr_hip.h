@@ -36,8 +36,8 @@ extern "C" {
 
 /* ABI version, bumped on any signature change.  The CLIP text tower's entries at the end of this file (tamtr_text_embed, tamtr_linear_f32,
  * tamtr_text_pool_project), tamtr_val_confusion, tamtr_val_ap_curves / tamtr_val_ap_tile and tamtr_bytetrack_update /
- * tamtr_bytetrack_workspace_bytes are new symbols only: no existing signature
- * changed, so the version stayed at 36 when they were added. */
+ * tamtr_bytetrack_workspace_bytes, and tamtr_val_coco_match / tamtr_val_coco_workspace_bytes / tamtr_val_coco_accumulate are new symbols
+ * only: no existing signature changed, so the version stayed at 36 when they were added. */
 int tamtr_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -710,6 +710,41 @@ int tamtr_bytetrack_update(const float* out, const int32_t* counts, int B, int n
                            double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts, void* workspace, int workspace_bytes,
                            void* stream);
 int tamtr_bytetrack_workspace_bytes(int T, int nq);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * COCO-protocol bbox evaluation (AP / AR by object size) on the device.  Replaces the step the reference leaves to pycocotools:
+ * valTAMTR.py:15 (save_json=True "if you need to cal coco metrice"), dataset/yolo2coco.py (the annotation file for it) and
+ * requirements.txt:44 (pycocotools, "COCO mAP").  The rule is written out in csrc/cocoeval.hip and stated by engine.coco_evaluate.
+ *
+ * tamtr_val_coco_match: the per-image matching of a whole batch, one launch, one workgroup per image.
+ *      predn f32 [B, nq, 6], counts i32 [B]                 outputs of tamtr_val_postprocess_match (rows in descending score order)
+ *      lab_cls f32 [M], lab_box f32 [M, 4], lab_off i32 [B + 1], scale f32 [B, 4]     the labels as tamtr_val_confusion reads them
+ *      thresholds f64 [10]                                  numpy's linspace(0.5, 0.95, 10)
+ *      max_det                                              the last entry of max_dets: rows of rank >= max_det take part in nothing
+ *      bits i32 [B, nq, 4]   per row and size range (all, small, medium, large): bit t = matched at threshold t, bit 16 + t = ignored
+ *      rank i32 [B, nq]      the row's rank among the image's rows of its class that take part; -1 for a row that takes part in
+ *                            nothing (row >= counts[b], class outside [0, nc), NaN score)
+ *      npig i32 [nc, 4]      ADDED TO: the non-ignored ground truths per class and range (integer atomics, order-free)
+ *      workspace             tamtr_val_coco_workspace_bytes(B, nq, M) bytes, 16-byte aligned, contents irrelevant: the label table of an
+ *                            image with more than 512 labels (no cap on labels per image)
+ *  Nothing is allocated, set or synchronised.  TAMTR_EINVAL: a NULL operand (lab_cls / lab_box may be NULL only when M == 0), B < 1,
+ *  nq < 1, nc < 1, M < 0, max_det < 1, a misaligned operand, a workspace that is too small.  TAMTR_EUNSUP: nq > 512.
+ *
+ * tamtr_val_coco_accumulate: the accumulation of a whole run, one launch, one workgroup per (class, range, cut, threshold).
+ *      bits i32 [N, 4], rank i32 [N]     the rows of the run sorted by class, then score descending, then original order
+ *      seg_off i32 [nc + 1]              rows of class k are seg_off[k] .. seg_off[k + 1]
+ *      npig i32 [nc, 4], max_dets i32 [n_max_dets] (ascending, 1 .. 4 entries), grid f64 [101] = numpy's linspace(0, 1, 101)
+ *      precision f64 [10, 101, nc, 4, n_max_dets]; recall, ap_tkam f64 [10, nc, 4, n_max_dets]     fully written
+ *  ap_tkam = the mean of precision over the 101 grid values, summed serially in grid order; -1 stays -1.  No atomics and no
+ *  floating-point reduction whose order could vary: two runs give the same bits.
+ *  TAMTR_EINVAL: a NULL or misaligned operand, N < 1, nc < 1, n_max_dets outside 1 .. 4.  TAMTR_EUNSUP: nc > 2^16 or N > 2^30. */
+int tamtr_val_coco_match(const float* predn, const int32_t* counts, int B, int nq, int nc, const float* lab_cls, const float* lab_box,
+                         const int32_t* lab_off, int M, const float* scale, const double* thresholds, int max_det, int32_t* bits,
+                         int32_t* rank, int32_t* npig, void* workspace, int workspace_bytes, void* stream);
+int tamtr_val_coco_workspace_bytes(int B, int nq, int M); /* 0 = unsupported */
+int tamtr_val_coco_accumulate(const int32_t* bits, const int32_t* rank, const int32_t* seg_off, int N, int nc, const int32_t* npig,
+                              const int32_t* max_dets, int n_max_dets, const double* grid, double* precision, double* recall,
+                              double* ap_tkam, void* stream);
 
 #ifdef __cplusplus
 }

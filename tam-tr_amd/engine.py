@@ -468,6 +468,161 @@ def curves_as_lists(curves, classes):
     return {**{k: np.asarray(v).tolist() for k, v in curves.items()}, 'classes': [int(c) for c in classes]}
 
 
+# ------------------------------------------------------------------------------------------------ COCO-protocol evaluation
+COCO_T = np.linspace(0.5, 0.95, 10)          # IoU thresholds
+COCO_R = np.linspace(0.0, 1.0, 101)          # recall grid
+COCO_AREAS = ((0.0, 1e10), (0.0, 32.0 ** 2), (32.0 ** 2, 96.0 ** 2), (96.0 ** 2, 1e10))   # all, small, medium, large; inclusive at both ends
+COCO_KEYS = ('AP', 'AP50', 'AP75', 'APs', 'APm', 'APl', 'AR1', 'AR10', 'AR100', 'ARs', 'ARm', 'ARl')
+
+
+def coco_cuts(max_dets):
+    """max_dets as a tuple of ints, checked: 1 to 4 positive entries, strictly ascending."""
+    md = tuple(int(m) for m in max_dets)
+    if not 1 <= len(md) <= 4 or md[0] < 1 or any(b <= a for a, b in zip(md, md[1:])):
+        raise ValueError(f'coco: max_dets must be 1 to 4 ascending positive integers, got {tuple(max_dets)}')
+    return md
+
+
+def _coco_match_image(det, lab, nc, cut):
+    """One image.  det f32 [n, 6] (x1 y1 x2 y2 score cls, any order), lab f32 [m, 5] (cls x1 y1 x2 y2).  -> bits i32 [n, 4] (per size range:
+    bit t = matched at threshold t, bit 16 + t = ignored), rank i32 [n] (rank among the image's participating rows of the class in stable
+    descending score order, -1: takes part in nothing), npig i64 [nc, 4].  The statement of csrc/cocoeval.hip's matching rule."""
+    n = det.shape[0]
+    bits, rank, npig = np.zeros((n, 4), np.int32), np.full(n, -1, np.int32), np.zeros((nc, 4), np.int64)
+    dcl_f, gcl_f = np.trunc(det[:, 5]), np.trunc(lab[:, 0])
+    d_ok = (dcl_f >= 0) & (dcl_f < nc) & ~np.isnan(det[:, 4])         # NaN classes fail both comparisons
+    g_ok = (gcl_f >= 0) & (gcl_f < nc)
+    dbox, gbox = det[:, :4].astype(np.float64), lab[:, 1:5].astype(np.float64)
+    darea = (dbox[:, 2] - dbox[:, 0]) * (dbox[:, 3] - dbox[:, 1])
+    garea = (gbox[:, 2] - gbox[:, 0]) * (gbox[:, 3] - gbox[:, 1])
+    thr = np.minimum(COCO_T, 1 - 1e-10)
+    for k in np.unique(np.concatenate([dcl_f[d_ok], gcl_f[g_ok]])).astype(int):
+        di = np.nonzero(d_ok & (dcl_f == k))[0]
+        di = di[np.argsort(-det[di, 4], kind='stable')]               # COCO's mergesort on -score
+        rank[di] = np.arange(len(di))
+        di = di[:cut]                                                   # later ones take part in nothing and consume no ground truth
+        gi = np.nonzero(g_ok & (gcl_f == k))[0]
+        for a, (lo, hi) in enumerate(COCO_AREAS):
+            g_ign = (garea[gi] < lo) | (garea[gi] > hi)
+            npig[k, a] += int((~g_ign).sum())
+            go = gi[np.argsort(g_ign, kind='stable')]                  # non-ignored first, file order inside each group
+            g_ign = np.sort(g_ign, kind='stable')
+            d_out = (darea[di] < lo) | (darea[di] > hi)
+            if len(go) and len(di):
+                iw = np.minimum(dbox[di, None, 2], gbox[None, go, 2]) - np.maximum(dbox[di, None, 0], gbox[None, go, 0])
+                ih = np.minimum(dbox[di, None, 3], gbox[None, go, 3]) - np.maximum(dbox[di, None, 1], gbox[None, go, 1])
+                inter = iw * ih
+                union = (darea[di, None] + garea[None, go]) - inter
+                with np.errstate(divide='ignore', invalid='ignore'):
+                    iou = np.where((iw > 0) & (ih > 0) & (union > 0), inter / union, 0.0)
+            else:
+                iou = np.zeros((len(di), len(go)))
+            top = iou.max(1) if len(go) else np.zeros(len(di))
+            for t in range(10):
+                taken = np.zeros(len(go), bool)
+                for j in np.nonzero(top >= thr[t])[0]:                  # (the others have no ground truth to walk to: unmatched)
+                    # the walk over `go` with best = thr, "skip when iou < best", "stop at the first ignored one once a non-ignored one is
+                    # held": the arg-max of (non-ignored, IoU, position) over the unmatched ones with IoU >= thr (a NaN IoU never qualifies)
+                    cand = ~taken & (iou[j] >= thr[t])
+                    if cand.any():
+                        pool = cand & ~g_ign if (cand & ~g_ign).any() else cand
+                        m = np.nonzero(pool & (iou[j] == iou[j][pool].max()))[0][-1]           # equal IoUs: the later one
+                        taken[m] = True
+                        bits[di[j], a] |= (1 << t) | (int(g_ign[m]) << (16 + t))
+                unmatched = (bits[di, a] & (1 << t)) == 0
+                bits[di[unmatched & d_out], a] |= 1 << (16 + t)           # an unmatched detection outside the range is ignored
+    return bits, rank, npig
+
+
+def coco_accumulate(score, cls, bits, rank, npig, nc, max_dets):
+    """The run's rows (image order, then row order): score [n], cls [n], bits [n, 4], rank [n] and npig [nc, 4] -> precision f64
+    [10, 101, nc, 4, M], recall f64 [10, nc, 4, M].  The statement of csrc/cocoeval.hip's accumulation rule."""
+    md = coco_cuts(max_dets)
+    precision = -np.ones((10, 101, nc, 4, len(md)))
+    recall = -np.ones((10, nc, 4, len(md)))
+    cls_i = np.trunc(np.where(rank >= 0, cls, -1)).astype(np.int64)
+    tbit = 1 << np.arange(10)
+    for k in range(nc):
+        mine = np.nonzero((rank >= 0) & (cls_i == k))[0]
+        for a in range(4):
+            n_gt = int(npig[k, a])
+            if n_gt == 0:
+                continue
+            for mi, cut in enumerate(md):
+                rows = mine[rank[mine] < cut]
+                rows = rows[np.argsort(-score[rows], kind='stable')]
+                w = bits[rows, a].astype(np.int64)
+                matched, ignored = (w[:, None] & tbit) != 0, ((w[:, None] >> 16) & tbit) != 0
+                tp = (matched & ~ignored).cumsum(0).astype(np.float64)          # [n, 10]
+                fp = (~matched & ~ignored).cumsum(0).astype(np.float64)
+                rc = tp / n_gt
+                pr = tp / ((fp + tp) + 2.220446049250313e-16)
+                pr = np.maximum.accumulate(pr[::-1], axis=0)[::-1]
+                for t in range(10):
+                    recall[t, k, a, mi] = rc[-1, t] if len(rows) else 0.0
+                    at = np.searchsorted(rc[:, t], COCO_R, side='left')
+                    ok = at < len(rows)
+                    q = np.zeros(101)
+                    q[ok] = pr[at[ok], t]
+                    precision[t, :, k, a, mi] = q
+    return precision, recall
+
+
+def coco_summary(ap_tkam, recall, max_dets, npig=None, names=None):
+    """The twelve COCO numbers and the per-class rows from ap_tkam and recall (f64 [10, nc, 4, M]; ap_tkam = the mean of precision over the
+    recall grid, -1 where the class has no ground truth in the range) - the host and the device path both end in these lines.  Each number
+    is the mean over the entries > -1, or -1 when there are none; the cut is the last of max_dets unless it is named (AR1 / AR10 / AR100 =
+    the first three cuts, -1 for a cut max_dets does not have)."""
+    md = coco_cuts(max_dets)
+    ap_tkam, recall = np.asarray(ap_tkam, np.float64), np.asarray(recall, np.float64)
+
+    def mean(x):
+        x = x[x > -1]
+        return float(x.mean()) if x.size else -1.0
+
+    out = {'AP': mean(ap_tkam[:, :, 0, -1]), 'AP50': mean(ap_tkam[0, :, 0, -1]), 'AP75': mean(ap_tkam[5, :, 0, -1]),
+           'APs': mean(ap_tkam[:, :, 1, -1]), 'APm': mean(ap_tkam[:, :, 2, -1]), 'APl': mean(ap_tkam[:, :, 3, -1])}
+    for i, key in enumerate(('AR1', 'AR10', 'AR100')):
+        out[key] = mean(recall[:, :, 0, i]) if i < len(md) else -1.0
+    out.update({'ARs': mean(recall[:, :, 1, -1]), 'ARm': mean(recall[:, :, 2, -1]), 'ARl': mean(recall[:, :, 3, -1]), 'max_dets': list(md)})
+    per_class = []
+    for k in range(ap_tkam.shape[1]):
+        row = {'class': names[k] if names is not None else k, 'AP': mean(ap_tkam[:, k, 0, -1]), 'AP50': mean(ap_tkam[0, k, 0, -1]),
+               'APs': mean(ap_tkam[:, k, 1, -1]), 'APm': mean(ap_tkam[:, k, 2, -1]), 'APl': mean(ap_tkam[:, k, 3, -1])}
+        if npig is not None:
+            row.update({'npig': int(npig[k, 0]), 'npig_s': int(npig[k, 1]), 'npig_m': int(npig[k, 2]), 'npig_l': int(npig[k, 3])})
+        per_class.append(row)
+    out['per_class'] = per_class
+    return out
+
+
+def coco_evaluate(images, nc, max_dets=(1, 10, 100), names=None, return_matches=False):
+    """COCO-protocol bbox evaluation (pycocotools' COCOeval evaluate + accumulate + summarize with iscrowd = 0, restated; the rule is
+    written out in csrc/cocoeval.hip, whose checker this is, and the host Validator's path).  images: per image (det [n, 6] x1 y1 x2 y2
+    score cls in native pixels, labels [m, 5] cls x1 y1 x2 y2), arrays or tensors; EVERY image is evaluated, also one without labels
+    (its detections are false positives).  All arithmetic is fp64 on the fp32 values.
+    -> {'precision' f64 [10, 101, nc, 4, M], 'recall', 'ap_tkam' f64 [10, nc, 4, M], 'npig' i64 [nc, 4], 'summary': coco_summary's dict}
+    and, with return_matches, 'matches': per image (bits i32 [n, 4], rank i32 [n]) in the image's row order."""
+    md, nc = coco_cuts(max_dets), int(nc)
+    as_np = lambda x, w: (x.detach().float().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x, np.float32)).reshape(-1, w)  # noqa: E731
+    npig, matches, score, cls = np.zeros((nc, 4), np.int64), [], [], []
+    for det, lab in images:
+        det, lab = as_np(det, 6), as_np(lab, 5)
+        b, r, g = _coco_match_image(det, lab, nc, md[-1])
+        npig += g
+        matches.append((b, r))
+        score.append(det[:, 4])
+        cls.append(det[:, 5])
+    cat = lambda xs, shape, dt: np.concatenate(xs) if xs else np.zeros(shape, dt)   # noqa: E731
+    precision, recall = coco_accumulate(cat(score, (0,), np.float32), cat(cls, (0,), np.float32), cat([m[0] for m in matches], (0, 4), np.int32),
+                                        cat([m[1] for m in matches], (0,), np.int32), npig, nc, md)
+    ap_tkam = np.where(precision[:, 0] > -1, precision.sum(1) / 101.0, -1.0)
+    out = {'precision': precision, 'recall': recall, 'ap_tkam': ap_tkam, 'npig': npig, 'summary': coco_summary(ap_tkam, recall, md, npig, names)}
+    if return_matches:
+        out['matches'] = matches
+    return out
+
+
 def cm_conf(conf):
     """The confusion matrix's confidence threshold from the validator's: 0.25 when that is None or the default 0.001 (metrics.py:818)."""
     return 0.25 if conf in (None, 0.001) else conf
@@ -546,12 +701,27 @@ class ConfusionMatrix:
 class Validator:
     """Accumulates (correct, conf, pred_cls, target_cls) over batches and reduces to mp, mr, mAP50, mAP50-95.
     confusion: also keep the reference's confusion matrix (ConfusionMatrix above, called where RTDETRValidator.update_metrics calls it);
-    results() then carries 'confusion_matrix'.  nc: its class count, taken from the first prediction when None."""
+    results() then carries 'confusion_matrix'.  nc: its class count, taken from the first prediction when None.
+    coco: also keep every image's native-space rows and labels; results() then carries 'coco', the COCO-protocol numbers of
+    coco_evaluate (AP, AP50, AP75, APs, APm, APl, AR1, AR10, AR100, ARs, ARm, ARl, max_dets, per_class) with the cuts coco_max_dets."""
 
-    def __init__(self, imgsz=640, conf=0.001, iou=0.7, single_cls=False, confusion=False, nc=None):
+    def __init__(self, imgsz=640, conf=0.001, iou=0.7, single_cls=False, confusion=False, nc=None, coco=False, coco_max_dets=(1, 10, 100)):
         self.imgsz, self.conf, self.iou, self.single_cls = imgsz, conf, iou, single_cls
         self.stats, self.seen = [], 0
         self.confusion, self.nc, self.confusion_matrix = confusion, nc, None
+        self.coco, self.coco_max_dets, self._coco_images = coco, coco_cuts(coco_max_dets) if coco else tuple(coco_max_dets), []
+
+    def _coco_image(self, pred, cls, bbox, shape):
+        """(predn [n, 6], labelsn [m, 5]) of one image as numpy, computed as update() computes them."""
+        predn = pred.clone()
+        if self.single_cls:
+            predn[:, 5] = 0
+        predn[..., [0, 2]] *= shape[1] / self.imgsz
+        predn[..., [1, 3]] *= shape[0] / self.imgsz
+        tbox = xywh2xyxy(bbox)
+        tbox[..., [0, 2]] *= shape[1]
+        tbox[..., [1, 3]] *= shape[0]
+        return predn.float().cpu().numpy(), torch.cat((cls, tbox), 1).cpu().numpy()
 
     @torch.no_grad()
     def update(self, preds, batch):
@@ -561,6 +731,8 @@ class Validator:
         if self.confusion and self.confusion_matrix is None:
             self.nc = y.shape[-1] - 4 if self.nc is None else self.nc
             self.confusion_matrix = ConfusionMatrix(self.nc, self.conf)
+        if self.coco and self.nc is None:
+            self.nc = y.shape[-1] - 4
         for si, pred in enumerate(postprocess(preds, self.imgsz, self.conf, self.iou, self.single_cls)):
             idx = batch['batch_idx'].view(-1).to(dev) == si
             cls = batch['cls'].to(dev).view(-1, 1)[idx].float()
@@ -569,6 +741,8 @@ class Validator:
             nl, npr = cls.shape[0], pred.shape[0]
             correct = torch.zeros(npr, iouv.numel(), dtype=torch.bool, device=dev)
             self.seen += 1
+            if self.coco:
+                self._coco_images.append(self._coco_image(pred, cls, bbox, shape))
             if npr == 0:
                 if nl:
                     self.stats.append((correct, torch.zeros(0, device=dev), torch.zeros(0, device=dev), cls.squeeze(-1)))
@@ -597,6 +771,8 @@ class Validator:
             extra['confusion_matrix'] = self.confusion_matrix.matrix.tolist() if self.confusion_matrix is not None else []
         if curves:
             extra['curves'] = {}
+        if self.coco:
+            extra['coco'] = coco_evaluate(self._coco_images, self.nc or 0, self.coco_max_dets)['summary']
         if not self.stats:
             return {'precision': 0.0, 'recall': 0.0, 'mAP50': 0.0, 'mAP50-95': 0.0, 'seen': self.seen, **extra}
         stats = [torch.cat(x, 0).cpu().numpy() for x in zip(*self.stats)]
@@ -627,10 +803,15 @@ class DeviceValidator:
     AP per class and threshold and the P / R / PR curves in one packed buffer, and the run's one device-to-host copy carries that buffer
     (plus the confusion matrix and device-side labels) instead of every row: 8 * (3010 * nc) + 8 * nc bytes, whatever the number of
     rows.  The order of equal confidences is then the defined one (ap_per_class(stable=True)); F1, the operating confidence and the
-    dict come from the same host lines.  Classes are the label classes inside [0, nc).  save_json keeps the row copy for its records."""
+    dict come from the same host lines.  Classes are the label classes inside [0, nc).  save_json keeps the row copy for its records.
+    coco: update() makes one more launch per batch (ops.val_coco_match, csrc/cocoeval.hip) on the outputs and the uploaded labels of
+    the first (the upload confusion=True shares), leaving the COCO match bits and ranks of every row on the device and adding into one
+    device table of ground-truth counts - still nothing synchronises; results() launches ops.val_coco_accumulate once and carries
+    'coco' (coco_summary's dict with the cuts coco_max_dets, equal to Validator's).  The run's one device-to-host copy gains ap_tkam,
+    recall and the count table, 8 * (80 * nc * len(coco_max_dets)) + 16 * nc bytes; the precision array stays on the device."""
 
     def __init__(self, imgsz=640, conf=0.001, iou=0.7, single_cls=False, save_json=False, class_map=None, names=None, confusion=False,
-                 nc=None, device_metrics=False):
+                 nc=None, device_metrics=False, coco=False, coco_max_dets=(1, 10, 100)):
         self.imgsz, self.conf, self.iou, self.single_cls = imgsz, conf, iou, single_cls
         self.save_json, self.class_map, self.names = save_json, class_map, names
         self.batches, self.files, self.seen = [], [], 0
@@ -639,25 +820,54 @@ class DeviceValidator:
         self.confusion, self.nc = confusion, nc
         self._matrix, self._matrix_host = None, None   # i32 [nc + 1, nc + 1] on the device; its copy after _reduce()
         self.device_metrics, self._ncls, self._reduced_dev = device_metrics, nc, None
+        self.coco, self.coco_max_dets = coco, coco_cuts(coco_max_dets) if coco else tuple(coco_max_dets)
+        self._coco_batches, self._npig, self._coco_host = [], None, None   # (bits, rank) per batch; i32 [nc, 4] on the device; the dict
 
     @torch.no_grad()
     def update(self, preds, batch):
         from . import ops
         y = preds[0] if isinstance(preds, (list, tuple)) else preds
         out = ops.val_postprocess_match(y, batch['cls'], batch['bboxes'], batch['batch_idx'], batch.get('ori_shape'), self.imgsz, self.conf,
-                                        self.iou, self.single_cls, return_device_labels=self.confusion)
+                                        self.iou, self.single_cls, return_device_labels=self.confusion or self.coco)
         self.batches.append(out[:5])
         if self.confusion:
             if self._matrix is None:
                 self.nc = y.shape[-1] - 4 if self.nc is None else self.nc
                 self._matrix = torch.zeros(self.nc + 1, self.nc + 1, dtype=torch.int32, device=y.device)
             ops.val_confusion(out[0], out[2], out[5], self.nc, cm_conf(self.conf), 0.45, self._matrix)
+        if self.coco:
+            if self._npig is None:
+                self.nc = y.shape[-1] - 4 if self.nc is None else self.nc
+                self._npig = torch.zeros(self.nc, 4, dtype=torch.int32, device=y.device)
+            self._coco_batches.append(ops.val_coco_match(out[0], out[2], out[5], self.nc, self.coco_max_dets[-1], self._npig))
         self.seen += y.shape[0]
         if self.save_json:
             self.files.extend(batch['im_file'])
         if self._ncls is None:
             self._ncls = y.shape[-1] - 4
         self._reduced = self._reduced_dev = None
+
+    def _coco_parts(self):
+        """coco: what the run's one device-to-host copy carries for it - the head of ops.val_coco_accumulate's packed buffer (ap_tkam and
+        recall; the precision array stays behind) and the ground-truth count table - as flat uint8 device tensors."""
+        if not self.coco or not self._coco_batches:
+            return []
+        from . import ops
+        packed = ops.val_coco_accumulate([(b[0], c[0], c[1]) for b, c in zip(self.batches, self._coco_batches)], self._npig, self.nc,
+                                         self.coco_max_dets, return_packed=True)[-1]
+        return [packed[:80 * self.nc * len(self.coco_max_dets)].view(torch.uint8), self._npig.reshape(-1).view(torch.uint8)]
+
+    def _coco_take(self, flat):
+        """The tail of the copy that _coco_parts() put there -> self._coco_host, by the lines the host path ends in."""
+        from . import ops
+        nc, n_m = self.nc, len(self.coco_max_dets)
+        tail = flat[len(flat) - (640 * nc * n_m + 16 * nc):]
+        ap_tkam, recall, _ = ops.val_coco_split(tail[:640 * nc * n_m].view(np.float64), nc, n_m)
+        self._coco_host = coco_summary(ap_tkam, recall, self.coco_max_dets, tail[640 * nc * n_m:].view(np.int32).reshape(nc, 4))
+
+    def _coco_empty(self):
+        nc = self.nc or 0
+        return coco_summary(-np.ones((10, nc, 4, len(self.coco_max_dets))), -np.ones((10, nc, 4, len(self.coco_max_dets))), self.coco_max_dets)
 
     def _reduce(self):
         """-> (predn [n, 6], correct [n, 10] bool, image [n], target_cls [m], target_image [m]) as numpy, rows in image order."""
@@ -669,7 +879,11 @@ class DeviceValidator:
                 dev_parts += [p.reshape(-1).view(torch.uint8) for p in parts]
             if self._matrix is not None:
                 dev_parts.append(self._matrix.reshape(-1).view(torch.uint8))
+            coco_parts = self._coco_parts() if not self.device_metrics else []      # (device_metrics: _reduce_device()'s copy carries them)
+            dev_parts += coco_parts
             flat = torch.cat(dev_parts).cpu().numpy() if dev_parts else np.zeros(0, np.uint8)   # the run's one device-to-host copy
+            if coco_parts:
+                self._coco_take(flat)
             pos, rows, hits, image, tcls, timage, first = 0, [], [], [], [], [], 0
 
             def take(n, dtype):
@@ -713,7 +927,10 @@ class DeviceValidator:
                     labs.append(lab_cls)
             packed = ops.val_ap_curves([b[:3] for b in self.batches], labs, nc, return_packed=True)[-1]
             parts = [packed] + (dev_labs if not self.save_json else []) + ([self._matrix] if self._matrix is not None and not self.save_json else [])
-            flat = torch.cat([p.reshape(-1).view(torch.uint8) for p in parts]).cpu().numpy()   # the run's one device-to-host copy
+            coco_parts = self._coco_parts()
+            flat = torch.cat([p.reshape(-1).view(torch.uint8) for p in parts] + coco_parts).cpu().numpy()   # the run's one device-to-host copy
+            if coco_parts:
+                self._coco_take(flat)
             out = ops.val_ap_split(flat[:packed.numel() * 8].view(np.float64), nc)
             if self.save_json:                            # the records need the rows: today's copy, which also brings labels and matrix
                 tcls, timage = self._reduce()[3:]
@@ -750,8 +967,11 @@ class DeviceValidator:
         extra = {'curves': {}} if curves else {}
         if self.device_metrics:
             if not self.batches:
-                return {**_EMPTY, 'seen': self.seen, 'per_class': [], **({'confusion_matrix': []} if self.confusion else {}), **extra}
+                return {**_EMPTY, 'seen': self.seen, 'per_class': [], **({'confusion_matrix': []} if self.confusion else {}),
+                        **({'coco': self._coco_empty()} if self.coco else {}), **extra}
             ap, p_curve, r_curve, pr_curve, n_gt, n_pred, tcls, timage = self._reduce_device()
+            if self.coco:
+                extra['coco'] = self._coco_host
             if self.save_json:
                 predn, _, image = self._reduce()[:3]
                 self.jdict = self._records(predn, image)
@@ -769,6 +989,8 @@ class DeviceValidator:
                                                    'pr': pr_curve[has], 'valid': n_pred[has] > 0}, classes)
         else:
             predn, correct, image, tcls, timage = self._reduce()
+            if self.coco:
+                extra['coco'] = self._coco_host if self._coco_host is not None else self._coco_empty()
             if self.save_json:
                 self.jdict = self._records(predn, image)
             if self.confusion:
@@ -810,21 +1032,24 @@ class DeviceValidator:
 
 @torch.no_grad()
 def validate(model, batches, imgsz=640, conf=0.001, iou=0.7, autocast_dtype=None, on_device=False, save_json=None, names=None,
-             confusion=False, device_metrics=False, curves=False):
+             confusion=False, device_metrics=False, curves=False, coco=False, coco_max_dets=(1, 10, 100)):
     """model in eval mode over an iterable of batches -> metric dict (valTAMTR.py's flow without the dataset plumbing).
     on_device: postprocess and label matching in one HIP launch per batch (DeviceValidator; the dict then also carries 'per_class');
     save_json (a file or folder path, needs on_device): also write the reference's predictions.json there.
     confusion: the dict also carries 'confusion_matrix' ([nc + 1][nc + 1] ints, row = predicted, column = true, last = background).
     device_metrics (needs on_device): AP and the curves are reduced on the device too (DeviceValidator(device_metrics=True)).
-    curves: the dict also carries 'curves' (the reference's P / R / F1 / PR curves; see ap_per_class)."""
+    curves: the dict also carries 'curves' (the reference's P / R / F1 / PR curves; see ap_per_class).
+    coco: the dict also carries 'coco', the COCO-protocol AP / AR by object size with the cuts coco_max_dets (coco_evaluate on the host
+    path, csrc/cocoeval.hip with on_device); it needs nothing beyond the path it selects."""
     if save_json and not on_device:
         raise ValueError('validate(save_json=...) needs on_device=True: the records come from the device path')
     if device_metrics and not on_device:
         raise ValueError('validate(device_metrics=True) needs on_device=True: the reduction reads what the device path keeps')
     was_training = model.training
     model.eval()
-    v = (DeviceValidator(imgsz, conf, iou, save_json=bool(save_json), names=names, confusion=confusion, device_metrics=device_metrics) if on_device
-         else Validator(imgsz, conf, iou, confusion=confusion))
+    v = (DeviceValidator(imgsz, conf, iou, save_json=bool(save_json), names=names, confusion=confusion, device_metrics=device_metrics,
+                         coco=coco, coco_max_dets=coco_max_dets) if on_device
+         else Validator(imgsz, conf, iou, confusion=confusion, coco=coco, coco_max_dets=coco_max_dets))
     for batch in batches:
         img = batch['img']
         with torch.autocast(img.device.type, dtype=autocast_dtype or torch.bfloat16, enabled=autocast_dtype is not None):

@@ -2079,6 +2079,124 @@ def val_ap_curves(batches, lab_cls, nc, return_packed=False):
     return (ap, p, r, pr, n_gt, n_pred) + ((packed,) if return_packed else ())
 
 
+_VAL_COCO_GRIDS = {}   # device -> f64 [10 + 101 + 1]: numpy's own linspace(0.5, 0.95, 10) and linspace(0, 1, 101) (+ padding), uploaded once
+
+
+def _coco_grids(dev):
+    import numpy as np
+    g = _VAL_COCO_GRIDS.get(dev)
+    if g is None:
+        g = _VAL_COCO_GRIDS[dev] = torch.from_numpy(np.concatenate([np.linspace(0.5, 0.95, 10), np.linspace(0, 1, 101), [0.0]])).to(dev, non_blocking=True)
+    return g
+
+
+def _coco_max_dets(max_dets):
+    md = tuple(int(m) for m in max_dets)
+    if not 1 <= len(md) <= 4 or md[0] < 1 or any(b <= a for a, b in zip(md, md[1:])):
+        raise _lib.TamtrHipError(f'val_coco: max_dets must be 1 to 4 ascending positive integers, got {tuple(max_dets)}')
+    return md
+
+
+def val_coco_workspace_bytes(B, nq, M):
+    """Bytes of device workspace tamtr_val_coco_match needs for a batch of B images, nq rows and M labels (no GPU call)."""
+    n = _lib.lib().tamtr_val_coco_workspace_bytes(int(B), int(nq), int(M))
+    if n <= 0:
+        raise _lib.TamtrHipError(f'val_coco_match: B {B}, nq {nq}, M {M} is outside what the kernel is built for (nq <= 512)')
+    return n
+
+
+@torch.no_grad()
+def val_coco_match(predn, counts, device_labels, nc, max_det, npig, workspace=None):
+    """The per-image matching of the COCO bbox protocol (pycocotools' COCOeval.evaluateImg, which the reference reaches through
+    valTAMTR.py:15 save_json + dataset/yolo2coco.py) for the whole batch in one launch; the rule is stated in csrc/cocoeval.hip and by
+    engine.coco_evaluate.  predn f32 [B, nq, 6] and counts i32 [B]: the outputs of val_postprocess_match; device_labels: the sixth element
+    it returns with return_device_labels=True; max_det: the last entry of max_dets.  npig i32 [nc, 4] on the device is ADDED TO in place
+    (non-ignored ground truths per class and size range).  Returns bits i32 [B, nq, 4] (per range all / small / medium / large: bit t =
+    matched at threshold t, bit 16 + t = ignored) and rank i32 [B, nq] (rank among the image's rows of the class; -1: the row takes part
+    in nothing).  workspace: a uint8 device tensor of val_coco_workspace_bytes(B, nq, M), made here when None.  Every check comes before
+    the launch; nothing is uploaded or synchronised (the two threshold grids go up once per device)."""
+    require_gpu(predn, counts, npig, *device_labels)
+    d_cls, d_box, d_off, d_scale = device_labels
+    nc, max_det = int(nc), int(max_det)
+    if predn.dim() != 3 or predn.shape[2] != 6 or predn.dtype != torch.float32 or counts.dtype != torch.int32 or counts.numel() != predn.shape[0]:
+        raise _lib.TamtrHipError(f'val_coco_match: expected predn f32 [B, nq, 6] and counts i32 [B], got {tuple(predn.shape)} {predn.dtype}, '
+                                 f'{tuple(counts.shape)} {counts.dtype}')
+    B, nq, _ = predn.shape
+    M = int(d_cls.numel())
+    if nc < 1 or max_det < 1:
+        raise _lib.TamtrHipError(f'val_coco_match: nc and max_det must be positive, got {nc} and {max_det}')
+    if (npig.dtype != torch.int32 or npig.numel() != 4 * nc or not npig.is_contiguous() or d_off.dtype != torch.int32
+            or d_off.numel() != B + 1 or d_scale.numel() != 4 * B or d_box.numel() != 4 * M
+            or any(t.dtype != torch.float32 for t in (d_cls, d_box, d_scale))):
+        raise _lib.TamtrHipError(f'val_coco_match: npig must be contiguous i32 [{nc}, 4] and the labels those of val_postprocess_match')
+    need = val_coco_workspace_bytes(B, nq, M)
+    if workspace is None:
+        workspace = torch.empty(need, device=predn.device, dtype=torch.uint8)
+    require_gpu(workspace)
+    if workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
+        raise _lib.TamtrHipError(f'val_coco_match: workspace must be a contiguous uint8 tensor of at least {need} bytes')
+    predn, counts, d_cls, d_box, d_off, d_scale = _c(predn), _c(counts), _c(d_cls), _c(d_box), _c(d_off), _c(d_scale)
+    bits = torch.empty(B, nq, 4, device=predn.device, dtype=torch.int32)
+    rank = torch.empty(B, nq, device=predn.device, dtype=torch.int32)
+    call('tamtr_val_coco_match', ptr(predn), ptr(counts), B, nq, nc, ptr(d_cls) if M else None, ptr(d_box) if M else None, ptr(d_off), M,
+         ptr(d_scale), ptr(_coco_grids(predn.device)), max_det, ptr(bits), ptr(rank), ptr(npig), ptr(workspace), int(workspace.numel()),
+         stream_ptr())
+    return bits, rank
+
+
+def val_coco_split(packed, nc, n_max_dets):
+    """The packed f64 buffer of val_coco_accumulate (a device tensor, or its copy as a numpy array) -> ap_tkam, recall [10, nc, 4, M] and
+    precision [10, 101, nc, 4, M], all views.  The buffer's head - ap_tkam and recall, 2 * 40 * nc * M values - is what a run copies to
+    the host; given only that head, precision is None."""
+    n = 40 * nc * n_max_dets
+    ap_tkam, recall = (packed[i * n:(i + 1) * n].reshape(10, nc, 4, n_max_dets) for i in range(2))
+    precision = packed[2 * n:103 * n].reshape(10, 101, nc, 4, n_max_dets) if packed.shape[0] >= 103 * n else None
+    return ap_tkam, recall, precision
+
+
+@torch.no_grad()
+def val_coco_accumulate(batches, npig, nc, max_dets, return_packed=False):
+    """The accumulation of the COCO bbox protocol (pycocotools' COCOeval.accumulate) for a whole run in one launch; the rule is stated in
+    csrc/cocoeval.hip and by engine.coco_accumulate.  batches: a list of (predn f32 [B, nq, 6], bits i32 [B, nq, 4], rank i32 [B, nq])
+    device tensors in run order (predn from val_postprocess_match, bits and rank from val_coco_match); npig i32 [nc, 4]: the table
+    val_coco_match added to; max_dets: 1 to 4 ascending cuts, the last one the max_det the matching ran with.
+    The rows are concatenated, rows that take part in nothing (rank < 0) or lie beyond the last cut get the class key nc, two stable
+    torch.sort calls order them by class, then score descending, then original order, torch.searchsorted finds the class segments, and
+    one launch does the rest.  Returns ap_tkam, recall f64 [10, nc, 4, M] and precision f64 [10, 101, nc, 4, M]: views of one packed
+    device buffer (return_packed: a fourth element, that buffer; val_coco_split undoes it).  Nothing synchronises."""
+    nc, md = int(nc), _coco_max_dets(max_dets)
+    if not batches or nc < 1:
+        raise _lib.TamtrHipError('val_coco_accumulate: needs at least one batch and nc >= 1')
+    require_gpu(npig)
+    for predn, bits, rank in batches:
+        require_gpu(predn, bits, rank)
+        if (predn.dim() != 3 or predn.shape[2] != 6 or predn.dtype != torch.float32 or bits.dtype != torch.int32 or rank.dtype != torch.int32
+                or tuple(bits.shape) != (*predn.shape[:2], 4) or tuple(rank.shape) != tuple(predn.shape[:2])):
+            raise _lib.TamtrHipError(f'val_coco_accumulate: expected predn f32 [B, nq, 6], bits i32 [B, nq, 4], rank i32 [B, nq], got '
+                                     f'{tuple(predn.shape)} {predn.dtype}, {tuple(bits.shape)} {bits.dtype}, {tuple(rank.shape)} {rank.dtype}')
+    if npig.dtype != torch.int32 or npig.numel() != 4 * nc or not npig.is_contiguous():
+        raise _lib.TamtrHipError(f'val_coco_accumulate: npig must be contiguous i32 [{nc}, 4]')
+    dev = batches[0][0].device
+    grids = _coco_grids(dev)
+    conf = torch.cat([b[0][..., 4].reshape(-1) for b in batches])
+    cls = torch.cat([b[0][..., 5].reshape(-1) for b in batches])
+    bits = torch.cat([b[1].reshape(-1, 4) for b in batches])
+    rank = torch.cat([b[2].reshape(-1) for b in batches])
+    key = torch.where((rank >= 0) & (rank < md[-1]), torch.trunc(cls), float(nc))
+    _, by_conf = torch.sort(-conf, stable=True)              # the host rule's np.argsort(-score, kind='stable') ...
+    key, by_cls = torch.sort(key[by_conf], stable=True)      # ... and its per-class selection, which keeps that order
+    order = by_conf[by_cls]
+    bits, rank = _c(bits[order]), _c(rank[order])
+    seg = _c(torch.searchsorted(key, torch.arange(nc + 1, device=dev, dtype=torch.float32)).to(torch.int32))
+    cuts = torch.tensor(md, dtype=torch.int32).to(dev, non_blocking=True)
+    N = int(rank.numel())
+    packed = torch.empty(103 * 40 * nc * len(md), device=dev, dtype=torch.float64)
+    ap_tkam, recall, precision = val_coco_split(packed, nc, len(md))
+    call('tamtr_val_coco_accumulate', ptr(bits), ptr(rank), ptr(seg), N, nc, ptr(npig), ptr(cuts), len(md),
+         ctypes.c_void_p(grids.data_ptr() + 80), ptr(precision), ptr(recall), ptr(ap_tkam), stream_ptr())
+    return (ap_tkam, recall, precision) + ((packed,) if return_packed else ())
+
+
 def img_augment(src, inv_affine, luts, flags, out_hw, border=114):
     """The pixel half of the training transforms for a whole batch (affine warp -> HSV look-up -> flips -> CHW float / 255;
     ultralytics/data/augment.py:415-420,590-609,636-666,920-926).  src u8 [B, SH, SW, 3], inv_affine f64 [B, 6]

@@ -12,6 +12,11 @@ column = true, header row and first column = the class names and `background`.
 F1_curve.csv (over confidence), into the run folder: first column = the 1000-point grid, then one column per class that has labels, last
 column `all classes` = their mean.  --device-metrics also reduces AP and the curves on the device (engine.DeviceValidator(device_metrics=True):
 the rows of the run never come to the host).
+--coco adds the COCO-protocol numbers (AP, AP50, AP75, AP / AR by object size, AR at the cuts of --coco-max-dets, default 1 10 100): the
+step the reference leaves to save_json + dataset/yolo2coco.py + pycocotools.  One more launch per batch on the device path
+(csrc/cocoeval.hip), engine.coco_evaluate with --host-postprocess; the twelve lines are printed in pycocotools' wording (to stderr; the
+JSON result line stays the last line of stdout) and coco_metrics.json is written into the run folder.  Every image of the split is
+evaluated, also one without labels.
 """
 import argparse
 import csv
@@ -46,6 +51,8 @@ def main():
     ap.add_argument('--confusion', action='store_true', help='write confusion_matrix.csv and confusion_matrix_normalized.csv')
     ap.add_argument('--curves', action='store_true', help='write PR_curve.csv, P_curve.csv, R_curve.csv and F1_curve.csv')
     ap.add_argument('--device-metrics', action='store_true', help='reduce AP and the curves on the device too (not with --host-postprocess)')
+    ap.add_argument('--coco', action='store_true', help='COCO-protocol AP / AR by object size; writes coco_metrics.json')
+    ap.add_argument('--coco-max-dets', type=int, nargs='+', default=[1, 10, 100], help='ascending cuts, at most 4 (VisDrone: 1 10 100 500)')
     ap.add_argument('--project', default='runs/val')
     ap.add_argument('--name', default='TAMTR')
     args = ap.parse_args()
@@ -55,6 +62,9 @@ def main():
         ap.error('--save-json needs the device path (drop --host-postprocess)')
     if args.device_metrics and args.host_postprocess:
         ap.error('--device-metrics needs the device path (drop --host-postprocess)')
+    if args.coco and (not 1 <= len(args.coco_max_dets) <= 4 or args.coco_max_dets[0] < 1
+                      or any(b <= a for a, b in zip(args.coco_max_dets, args.coco_max_dets[1:]))):
+        ap.error('--coco-max-dets takes 1 to 4 ascending positive integers')
 
     import tamtr_amd  # noqa: F401
     from tamtr_amd import data as D, engine as E
@@ -76,21 +86,51 @@ def main():
     if not args.no_fuse:
         model.fuse()
     save_dir = None
-    if args.save_json or args.confusion or args.curves:
+    if args.save_json or args.confusion or args.curves or args.coco:
         from tamtr_amd.predict import increment_path
         save_dir = str(increment_path(os.path.join(args.project, args.name), mkdir=True))
     short = {k: v.split('/')[0] for k, v in names.items()}
     res = E.validate(model, (D.preprocess_batch(b, None, dev) for b in loader), imgsz=args.imgsz, conf=args.conf, iou=args.iou,
                      autocast_dtype=torch.bfloat16 if args.dtype == 'bf16' else None, on_device=not args.host_postprocess,
                      save_json=save_dir if args.save_json else None, names=short, confusion=args.confusion,
-                     device_metrics=args.device_metrics, curves=args.curves)
+                     device_metrics=args.device_metrics, curves=args.curves, coco=args.coco, coco_max_dets=tuple(args.coco_max_dets))
     if save_dir is not None:
         res['save_dir'] = save_dir
     if args.confusion:
         res['confusion_csv'], res['confusion_normalized_csv'] = write_confusion(res['confusion_matrix'], [short[k] for k in sorted(short)], save_dir)
     if args.curves:
         res['curves_csv'] = write_curves(res.pop('curves'), short, save_dir)
+    if args.coco:
+        res['coco_json'] = write_coco(res['coco'], save_dir)
+        print('\n'.join(coco_lines(res['coco'])), file=sys.stderr)
     print(json.dumps(res))
+
+
+COCO_LINES = (('AP', 'Average Precision', '0.50:0.95', '   all', -1), ('AP50', 'Average Precision', '0.50', '   all', -1),
+              ('AP75', 'Average Precision', '0.75', '   all', -1), ('APs', 'Average Precision', '0.50:0.95', ' small', -1),
+              ('APm', 'Average Precision', '0.50:0.95', 'medium', -1), ('APl', 'Average Precision', '0.50:0.95', ' large', -1),
+              ('AR1', 'Average Recall', '0.50:0.95', '   all', 0), ('AR10', 'Average Recall', '0.50:0.95', '   all', 1),
+              ('AR100', 'Average Recall', '0.50:0.95', '   all', 2), ('ARs', 'Average Recall', '0.50:0.95', ' small', -1),
+              ('ARm', 'Average Recall', '0.50:0.95', 'medium', -1), ('ARl', 'Average Recall', '0.50:0.95', ' large', -1))
+
+
+def coco_lines(coco):
+    """The twelve numbers in the wording of pycocotools' COCOeval.summarize.  maxDets is the cut the number was taken at (the keys AR1,
+    AR10, AR100 name the first three cuts of max_dets whatever their values; a cut max_dets does not have prints as maxDets= -1)."""
+    md = coco['max_dets']
+    out = []
+    for key, title, iou, area, cut in COCO_LINES:
+        m = md[cut] if cut < len(md) else -1
+        out.append(f' {title:<18} ({"AP" if title.endswith("Precision") else "AR"}) @[ IoU={iou:<9} | area={area} | maxDets={m:>3d} ] = {coco[key]:0.3f}')
+    return out
+
+
+def write_coco(coco, save_dir):
+    """coco_metrics.json: the 'coco' dict of results() (twelve numbers, max_dets, per_class) as it is."""
+    path = os.path.join(save_dir, 'coco_metrics.json')
+    with open(path, 'w') as f:
+        json.dump(coco, f, indent=1)
+    return path
 
 
 CURVE_FILES = {'PR_curve.csv': ('pr', 'recall'), 'P_curve.csv': ('p', 'confidence'), 'R_curve.csv': ('r', 'confidence'),

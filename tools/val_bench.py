@@ -14,9 +14,15 @@
       nc = 10 and 80, about a tenth of the rows hit at IoU 0.5): the host reduction (every row to the host, engine.ap_per_class) against
       device_metrics=True (ops.val_ap_curves, one packed copy), ALTERNATING windows as in (a); and the bytes each path copies.
 
-    python tools/val_bench.py [--images 64] [--rounds 3] [--kernel-only] [--confusion | --metrics]
+  (e) --coco: COCO-protocol evaluation at VisDrone-val scale (548 images x 300 rows, 70 labels per image, nc = 10 and 80; the labels are
+      70 of the image's own predicted boxes with their predicted class, so the matching has work): DeviceValidator.update on one batch of
+      16 with and without coco=True, ALTERNATING windows as in (a); DeviceValidator(coco=True).results() over the whole run (the
+      accumulation launch and the run's one copy), windows as in (a), against ONE timed call of engine.coco_evaluate - the project's own
+      numpy statement of the rule, not pycocotools - on the same rows; and the bytes the copy gains.
+
+    python tools/val_bench.py [--images 64] [--rounds 3] [--kernel-only] [--confusion | --metrics | --coco]
 --kernel-only runs only the device loop of (a) - with --confusion the loop with confusion=True, with --metrics the device reduction of
-(d) - for a `rocprofv3 --kernel-trace --stats` run of its own.
+(d), with --coco the update loop with coco=True and the device results() of (e) - for a `rocprofv3 --kernel-trace --stats` run of its own.
 """
 import argparse
 import json
@@ -145,6 +151,86 @@ def bench_metrics(rounds, kernel_only=False):
     return rows
 
 
+def coco_run(nc, images=548, nq=300, per_image=70, batch=16):
+    """(y, batch dict) per batch at VisDrone-val scale: clustered predictions, and as labels 70 of each image's own predicted boxes with
+    their predicted class."""
+    out = []
+    for k, first in enumerate(range(0, images, batch)):
+        B = min(batch, images - first)
+        y = synthetic_preds(B, nq, nc, seed=k)
+        g = torch.Generator().manual_seed(1000 + k)
+        pick = torch.stack([torch.randperm(nq, generator=g)[:per_image] for _ in range(B)])
+        boxes = torch.gather(y[..., :4], 1, pick[..., None].expand(B, per_image, 4)).reshape(-1, 4).clamp(0.005, 0.995)
+        cls = torch.gather(y[..., 4:].argmax(-1), 1, pick).reshape(-1, 1).float()
+        out.append((y.cuda(), {'cls': cls, 'bboxes': boxes, 'batch_idx': torch.arange(B).repeat_interleave(per_image).float(),
+                               'ori_shape': [(540 + 20 * i, 960 - 10 * i) for i in range(B)]}))
+    return out
+
+
+def bench_coco(rounds, kernel_only=False):
+    from tamtr_amd import engine as E
+    rows = []
+    conf, iou = 0.001, 0.7
+    for nc in (10, 80):
+        run = coco_run(nc)
+
+        def update(coco):
+            v = E.DeviceValidator(640, conf, iou, coco=coco)
+            v.update(*run[0])
+            return v
+
+        def whole(coco=True):
+            v = E.DeviceValidator(640, conf, iou, coco=coco)
+            for y, b in run:
+                v.update(y, b)
+            return v
+
+        def results(v):
+            v._reduced = v._reduced_dev = None       # results() keeps its reduction: time it afresh
+            return v.results()
+
+        for _ in range(5):
+            update(True), update(False)
+        dv, plain = whole(), whole(False)
+        for _ in range(2):
+            results(dv), results(plain)
+        if kernel_only:
+            tu, n = window(lambda: update(True))
+            tr, m = window(lambda: results(dv))
+            rows.append({'nc': nc, 'device_update_coco_ms': round(tu, 4), 'update_iters': n, 'device_results_coco_ms': round(tr, 3), 'results_iters': m})
+            continue
+        t = {k: [] for k in ('update', 'update_coco', 'results', 'results_coco')}
+        for _ in range(rounds):      # alternating windows
+            t['update'].append(window(lambda: update(False))[0])
+            t['update_coco'].append(window(lambda: update(True))[0])
+            t['results'].append(window(lambda: results(plain))[0])
+            t['results_coco'].append(window(lambda: results(dv))[0])
+        got = results(dv)['coco']
+        predn, _, image, _, _ = dv._reduce()
+        images, first = [], 0
+        for (y, b), (pn, _, cn, _, _) in zip(run, dv.batches):
+            pn, cn = pn.cpu(), cn.cpu()
+            for i in range(y.shape[0]):
+                h, w = b['ori_shape'][i]
+                mine = b['batch_idx'] == i
+                tbox = E.xywh2xyxy(b['bboxes'][mine])
+                tbox[..., [0, 2]] *= w
+                tbox[..., [1, 3]] *= h
+                images.append((pn[i, :cn[i]].numpy(), torch.cat((b['cls'][mine], tbox), 1).numpy()))
+        t0 = time.perf_counter()
+        want = E.coco_evaluate(images, nc)['summary']
+        host_s = time.perf_counter() - t0
+        err = max(abs(got[k] - want[k]) for k in E.COCO_KEYS)
+        assert err <= 1e-12, (got, want)
+        rows.append({'images': len(images), 'rows': int(len(predn)), 'labels': sum(len(b['cls']) for _, b in run), 'nc': nc,
+                     **{k: round(got[k], 6) for k in E.COCO_KEYS}, 'device_vs_host_max_err': err,
+                     'device_update_ms': [round(x, 4) for x in t['update']], 'device_update_coco_ms': [round(x, 4) for x in t['update_coco']],
+                     'device_results_ms': [round(x, 3) for x in t['results']], 'device_results_coco_ms': [round(x, 3) for x in t['results_coco']],
+                     'host_coco_evaluate_s_one_call': round(host_s, 2), 'copy_gains_bytes': 8 * 80 * nc * 3 + 16 * nc,
+                     'precision_array_bytes_left_on_device': 8 * 10 * 101 * nc * 4 * 3})
+    return rows
+
+
 def bench_update(rounds, kernel_only=False):
     from tamtr_amd import engine as E
     rows = []
@@ -235,10 +321,20 @@ def main():
     ap.add_argument('--skip-validate', action='store_true')
     ap.add_argument('--confusion', action='store_true', help='measurement (c): update with and without the confusion matrix')
     ap.add_argument('--metrics', action='store_true', help='measurement (d): results() on the host path and with device_metrics=True')
+    ap.add_argument('--coco', action='store_true', help='measurement (e): update and results() with and without coco=True, and the host rule')
     args = ap.parse_args()
     import tamtr_amd  # noqa: F401
     assert torch.cuda.is_available(), 'val_bench needs an MI355X'
     print(torch.cuda.get_device_name(0), 'torch', torch.__version__)
+    if args.coco:
+        if args.kernel_only:
+            print(json.dumps({'device_coco_only': bench_coco(0, True)}))
+            return
+        print(f'(e) COCO evaluation: update and results() with and without coco=True ({args.rounds} alternating windows of >= 1 s each, device '
+              'events); engine.coco_evaluate (our numpy rule, not pycocotools) timed once on the same rows')
+        for r in bench_coco(args.rounds):
+            print(json.dumps(r))
+        return
     if args.metrics:
         if args.kernel_only:
             print(json.dumps({'device_results_only': bench_metrics(0, True)}))
