@@ -36,7 +36,8 @@ extern "C" {
 
 /* ABI version, bumped on any signature change.  The CLIP text tower's entries at the end of this file (tamtr_text_embed, tamtr_linear_f32,
  * tamtr_text_pool_project), tamtr_val_confusion, tamtr_val_ap_curves / tamtr_val_ap_tile and tamtr_bytetrack_update /
- * tamtr_bytetrack_workspace_bytes, and tamtr_val_coco_match / tamtr_val_coco_workspace_bytes / tamtr_val_coco_accumulate are new symbols
+ * tamtr_bytetrack_workspace_bytes, tamtr_val_coco_match / tamtr_val_coco_workspace_bytes / tamtr_val_coco_accumulate and tamtr_mot_update /
+ * tamtr_mot_end_sequence / tamtr_mot_workspace_bytes are new symbols
  * only: no existing signature changed, so the version stayed at 36 when they were added. */
 int tamtr_abi_version(void);
 
@@ -745,6 +746,34 @@ int tamtr_val_coco_workspace_bytes(int B, int nq, int M); /* 0 = unsupported */
 int tamtr_val_coco_accumulate(const int32_t* bits, const int32_t* rank, const int32_t* seg_off, int N, int nc, const int32_t* npig,
                               const int32_t* max_dets, int n_max_dets, const double* grid, double* precision, double* recall,
                               double* ap_tkam, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * MOT evaluation on the device: CLEAR-MOT (MOTA, MOTP, FP, FN, IDSW, Frag, MT / PT / ML) and identity (IDF1, IDP, IDR) counts of the
+ * tracker's rows against ground truth, per class (TrackEval's CLEAR and Identity definitions).  The rule is written out in
+ * csrc/mot.hip and stated by engine.mot_evaluate.
+ *
+ * State, owned by the caller, all zero when fresh, updated in place (G = G_cap gt identities, T = T_cap track ids):
+ *      gstate i32 [G, 8]     last-matched track id + 1, frames present, frames matched, runs, last matched frame, class + 1, 0, 0
+ *      counts i32 [nc, 16]   TP FN FP IDSW gt_dets trk_dets Frag MT PT ML IDTP gt_ids drop_region drop_distractor 0 0 (run totals)
+ *      iou_sum f64 [nc]      pair i32 [G, T]      hdr i32 [8] (frame counter, gt ids beyond G, track ids beyond T, rows beyond ng / nq)
+ *
+ * tamtr_mot_update: steps 1 to 4 of the rule for the B frames of a batch, in order, one launch, one workgroup.
+ *      tracks f32 [B, nq, 8], tcounts i32 [B]    exactly as tamtr_bytetrack_update leaves them (id in column 4, class in column 6)
+ *      gt f32 [B, ng, 7], gcounts i32 [B]        x1 y1 x2 y2 id cls kind; the id of a kind-0 row is its dense row in [0, G)
+ *  An id outside its table or a count beyond ng / nq is counted in hdr and the rows are left out; nothing is written past a table.
+ *  The CLEAR counts and iou_sum (an fp64 atomic add: its last bits depend on the order) go straight into the run totals.
+ * tamtr_mot_end_sequence: one launch, one workgroup per class: MT / PT / ML / Frag / gt_ids and the identity assignment (IDTP) of the
+ *  sequence are added to counts; gstate, the used rows of pair and the frame counter are cleared.  G_used: the dense rows handed out.
+ * workspace: tamtr_mot_workspace_bytes(nq, ng, nc, G_cap, T_cap) bytes of device memory for either call, 16-byte aligned, contents
+ *  irrelevant (0 = unsupported).  Nothing is allocated, set or synchronised.
+ * TAMTR_EINVAL: a NULL or misaligned operand, a size < 1, iou_thr <= 0, a workspace that is too small.  TAMTR_EUNSUP: ng and nq whose
+ *  solver state (about 12 ng + 30 nq bytes) exceeds 60 KiB of LDS, G_cap * T_cap > 2^31 - 1, an id range fp32 cannot carry. */
+int tamtr_mot_update(const float* tracks, const int32_t* tcounts, const float* gt, const int32_t* gcounts, int B, int nq, int ng, int nc,
+                     double iou_thr, int32_t* gstate, int32_t* counts, double* iou_sum, int32_t* pair, int32_t* hdr, int G_cap, int T_cap,
+                     void* workspace, int workspace_bytes, void* stream);
+int tamtr_mot_end_sequence(int nc, int32_t* gstate, int32_t* counts, int32_t* pair, int32_t* hdr, int G_cap, int T_cap, int G_used,
+                           void* workspace, int workspace_bytes, void* stream);
+int tamtr_mot_workspace_bytes(int nq, int ng, int nc, int G_cap, int T_cap); /* 0 = unsupported */
 
 #ifdef __cplusplus
 }

@@ -112,6 +112,9 @@ _SIGS = {
     'tamtr_val_coco_match': [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P],
     'tamtr_val_coco_workspace_bytes': [_I, _I, _I],
     'tamtr_val_coco_accumulate': [_P, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P],
+    'tamtr_mot_update': [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P],
+    'tamtr_mot_end_sequence': [_I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P],
+    'tamtr_mot_workspace_bytes': [_I, _I, _I, _I, _I],
 }
 EXPORTS = tuple(_SIGS)
 _lib = None

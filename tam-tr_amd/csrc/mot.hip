@@ -1,0 +1,372 @@
+// mot.hip - MOT evaluation on the device: CLEAR-MOT (MOTA, MOTP, FP, FN, IDSW, Frag, MT / PT / ML) and identity (IDF1, IDP, IDR)
+// counts of the tracker's rows against ground truth, per class.  The reference leaves this to an outside toolkit; the definitions are
+// TrackEval's CLEAR and Identity.  tamtr_mot_update takes the B frames of a predictor batch, in order, in ONE launch, reading the rows
+// tamtr_bytetrack_update left on the device; tamtr_mot_end_sequence reduces a sequence in one launch.  engine.mot_evaluate is the
+// numpy statement of the same rule and this file's checker.
+//
+// THE RULE
+// Inputs, per frame of one sequence, frames in order:
+//   ground-truth rows  x1 y1 x2 y2 id cls kind   kind 0 object, 1 distractor (annotated, not to be scored), 2 ignored region
+//   track rows         x1 y1 x2 y2 id cls        (the device reads them from the tracker's 8-column rows: id at 4, cls at 6)
+//   all fp32, pixels of the original image.  A class outside [0, nc) on a kind-0 row or on a track row takes that row out of
+//   everything; kinds 1 and 2 ignore their class; any other kind takes the row out.
+// Arithmetic: coordinates are promoted to fp64; the object is compiled with -ffp-contract=off, so device and numpy agree to the bit
+// on every IoU and every threshold comparison.
+//   iw = min(ax2, bx2) - max(ax1, bx1), ih likewise; iw <= 0 or ih <= 0 -> 0; else inter = iw * ih,
+//   union = (areaA + areaB) - inter, iou = inter / union, 0 when union <= 0.
+//   ioa(track, region) = inter / area_track, 0 when the track area is not positive.
+//   A pair qualifies when iou >= thr (0.5 by default; exactly thr qualifies).
+// Per frame:
+//   1. Regions.  A track row whose ioa with any kind-2 row is > 0.5 is dropped (exactly 0.5 stays).
+//   2. Distractors.  One assignment between all kind-0 and kind-1 rows and the remaining track rows; score = iou where the pair
+//      qualifies and the classes agree (a kind-1 row agrees with every class), else 0; maximise the total.  Track rows matched with
+//      score > 0 to a kind-1 row are dropped.  Kind-1 and kind-2 rows then leave the frame.
+//   3. CLEAR matching per class c, between the kind-0 rows of class c and the remaining track rows of class c: score = iou + 1000 if
+//      the pair qualifies and the track id equals the id this ground truth was last matched to (in any earlier frame, however long
+//      ago), iou if it only qualifies, else 0.  Maximise the total; matches with score > 0 are TP, unmatched ground truths FN,
+//      unmatched tracks FP.  iou_sum adds the IoU itself.  A matched ground truth whose last-matched id exists and differs is one
+//      IDSW; then its last-matched id is updated.
+//   4. Pair counts.  Every qualifying pair of step 3's two sets adds 1 to pair[gt id, track id], matched or not; gt_dets and trk_dets
+//      count the rows of the two sets, and every gt id counts the frames it is present in.
+// Per sequence:
+//   a gt id present in n frames and matched in m: m / n > 0.8 is MT, < 0.2 is ML, else PT.  Its Frag is the number of maximal runs
+//   of consecutive matched frames, minus 1 (absent or unmatched frames break a run).
+//   Identity, per class: IDTP = the largest total of pair counts over one-to-one matchings of the gt ids and track ids of the class
+//   (TrackEval's (G+T) x (G+T) problem: a matching costs sum(gt_dets) + sum(trk_dets) - 2 sum(pair) there);
+//   IDFN = gt_dets - IDTP, IDFP = trk_dets - IDTP.  An id that changes class mid-sequence is a different identity in each class.
+// Summary (engine.mot_summary), per class and summed: MOTA = 1 - (FN + FP + IDSW) / gt_dets, MOTP = iou_sum / TP, Recall = TP / gt_dets,
+//   Precision = TP / trk_dets, IDF1 = IDTP / (IDTP + 0.5 IDFP + 0.5 IDFN), IDP = IDTP / trk_dets, IDR = IDTP / gt_dets; nan on a zero
+//   denominator.  Counts of several sequences add.
+//
+// STATE (owned by the caller, all zero when fresh; ops.MOT_STATE_SPEC)
+//   gstate  i32 [G, 8]   per gt identity: last-matched track id + 1, frames present, frames matched, runs, last matched frame, class + 1
+//   counts  i32 [nc, 16] TP FN FP IDSW gt_dets trk_dets Frag MT PT ML IDTP gt_ids drop_region drop_distractor 0 0   (run totals)
+//   iou_sum f64 [nc]
+//   pair    i32 [G, T]   the sequence's pair table
+//   hdr     i32 [8]      frame counter of the sequence, gt ids beyond G, track ids beyond T, rows beyond ng / nq, 0...
+// gt ids reach the device as dense rows [0, G) - the host maps (class, id) to them, so a row has one class and pair needs no class
+// axis; track ids are used as they are, [0, T).  An id or a per-frame row count beyond capacity is counted in hdr and the row is left
+// out: nothing is written past a table.  The CLEAR counts add straight into the run totals; Frag, MT / PT / ML, gt_ids and IDTP are
+// added by tamtr_mot_end_sequence, which then clears gstate, the rows of pair it used and the frame counter.
+//
+// DESIGN
+// Update: one workgroup of 256 threads walks the frames in order (step 3 depends on the frame before; the whole update is one launch,
+// so the frames' independent parts are not split over workgroups - that would need a grid-wide barrier).  The frame's IoU matrix
+// (all gt rows x all surviving track rows, fp64) lives in the caller's workspace in global memory (300 x 300 f64 does not fit the
+// LDS), and next to it the cost matrix of the assignment being solved, written once per assignment by all threads so the solver's
+// serial steps read one value each.  Step 3 is solved as ONE assignment over all classes with score 0 on a class mismatch: the
+// problem is block diagonal, so its optimum is the per-class optima.  Step 2 is skipped in a frame without a kind-1 row (it could drop
+// nothing).  Before the solver runs, the pairs that are a connected component of their own (a row and a column that meet only each
+// other) are matched directly - in a typical frame that is most of them - and only the contested rows and columns are solved.  The solver (mot_lsap.h) keeps duals and paths in LDS.  Counts are integer atomics
+// (order-free); iou_sum is an fp64 atomic add, so its last bits depend on the order (n * 2^-53 relative).
+// End of sequence: one workgroup per class.  It lists the class's gt rows, reduces MT / PT / ML / Frag, drops the track ids whose
+// pair column is zero over those rows (a block-wide column scan), solves the identity assignment with the solver's state in the
+// workspace (global memory: 1024 x 4097 does not fit the LDS) and clears what it read.
+#include "common.h"
+#include "mot_lsap.h"
+
+#ifndef MOT_UPDATE_THREADS
+#define MOT_UPDATE_THREADS 256
+#endif
+#define MOT_END_THREADS 256
+
+enum { GS_LAST, GS_PRESENT, GS_MATCHED, GS_RUNS, GS_LASTF, GS_CLS };
+enum { K_TP, K_FN, K_FP, K_IDSW, K_GT, K_TRK, K_FRAG, K_MT, K_PT, K_ML, K_IDTP, K_GTIDS, K_DROP_REGION, K_DROP_DISTRACTOR };
+enum { H_FRAME, H_OVER_GT, H_OVER_TRK, H_OVER_ROWS };
+
+struct MotBox { double x1, y1, x2, y2; };
+__device__ __forceinline__ MotBox mot_box(const float* r) { return MotBox{(double)r[0], (double)r[1], (double)r[2], (double)r[3]}; }
+
+// the intersection area, 0 when the boxes do not overlap
+__device__ __forceinline__ double mot_inter(const MotBox& a, const MotBox& b) {
+  const double iw = fmin(a.x2, b.x2) - fmax(a.x1, b.x1), ih = fmin(a.y2, b.y2) - fmax(a.y1, b.y1);
+  if (iw <= 0.0 || ih <= 0.0 || iw != iw || ih != ih) return 0.0;
+  return iw * ih;
+}
+
+__device__ __forceinline__ double mot_iou(const MotBox& a, const MotBox& b) {
+  const double inter = mot_inter(a, b);
+  if (!(inter > 0.0)) return 0.0;
+  const double uni = ((a.x2 - a.x1) * (a.y2 - a.y1) + (b.x2 - b.x1) * (b.y2 - b.y1)) - inter;
+  return uni > 0.0 ? inter / uni : 0.0;
+}
+
+__device__ __forceinline__ double mot_ioa(const MotBox& t, const MotBox& region) {
+  const double area = (t.x2 - t.x1) * (t.y2 - t.y1);
+  return area > 0.0 ? mot_inter(t, region) / area : 0.0;
+}
+
+__device__ __forceinline__ int mot_kind(const float* g) { return g[6] == 0.0f ? 0 : g[6] == 1.0f ? 1 : g[6] == 2.0f ? 2 : -1; }
+
+struct MotParams {
+  const float* tracks;
+  const int32_t* tcounts;
+  const float* gt;
+  const int32_t* gcounts;
+  int B, nq, ng, nc, G, T;
+  double thr;
+  int32_t* gstate;
+  int32_t* counts;
+  double* iou_sum;
+  int32_t* pair;
+  int32_t* hdr;
+  unsigned char* ws;
+};
+
+static size_t mot_update_ws_bytes(size_t nq, size_t ng) { return 16 * ng * nq + 4 * (8 * ng + 7 * nq); }
+static size_t mot_end_ws_per_class(size_t G, size_t T) { return ((4 * (2 * G + T) + 15) & ~(size_t)15) + mot_lsap_bytes(G, T + 1); }
+
+// A frame's assignment is sparse: most rows meet (have a negative cost with) one column only, and that column meets no other row.
+// Such a pair is a connected component of its own and belongs to the optimum; a row that meets nothing stays unmatched.  Only the
+// rows and columns of larger components go to the solver, as one compacted problem.  S is [n, m]; x[i] receives the column or -1.
+struct MotSparse {
+  int *rcnt, *rone, *rl, *xr;   // [ng]: columns a row meets, one of them, the solver's rows, its result
+  int *ccnt, *cone, *cl;        // [nq]: rows a column meets, one of them, the solver's columns
+};
+
+template <int NT>
+__device__ void mot_assign_sparse(const double* S, int n, int m, const MotLsap& w, const MotSparse& q, int* x, MotCand* red, int* wsum) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < n; i += NT) q.rcnt[i] = 0;
+  for (int j = tid; j < m; j += NT) q.ccnt[j] = 0;
+  __syncthreads();
+  for (int e = tid; e < n * m; e += NT)
+    if (S[e] < 0.0) {
+      const int i = e / m, j = e - i * m;
+      atomicAdd(&q.rcnt[i], 1);
+      atomicAdd(&q.ccnt[j], 1);
+      q.rone[i] = j;
+      q.cone[j] = i;
+    }
+  __syncthreads();
+  for (int i = tid; i < n; i += NT) x[i] = (q.rcnt[i] == 1 && q.ccnt[q.rone[i]] == 1) ? q.rone[i] : -1;
+  const int nr = mot_compact<NT>(n, q.rl, wsum, [&](int i) { return q.rcnt[i] >= 1 && !(q.rcnt[i] == 1 && q.ccnt[q.rone[i]] == 1); });
+  const int ncl = mot_compact<NT>(m, q.cl, wsum, [&](int j) { return q.ccnt[j] >= 1 && !(q.ccnt[j] == 1 && q.rcnt[q.cone[j]] == 1); });
+  __syncthreads();
+  if (nr > 0 && ncl > 0) {
+    mot_assign<NT>([&](int a, int b) -> double { return S[(size_t)q.rl[a] * m + q.cl[b]]; }, nr, ncl, 0.0, w, q.xr, red);
+    for (int a = tid; a < nr; a += NT) x[q.rl[a]] = q.xr[a] >= 0 ? q.cl[q.xr[a]] : -1;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(MOT_UPDATE_THREADS) void mot_update_kernel(MotParams p) {
+  extern __shared__ __align__(16) unsigned char lds[];
+  __shared__ int wsum[(MOT_UPDATE_THREADS / WAVE)];
+  __shared__ MotCand red[(MOT_UPDATE_THREADS / WAVE)];
+  const int tid = threadIdx.x, nq = p.nq, ng = p.ng, nc = p.nc;
+  const MotLsap w = mot_lsap_carve(lds, ng, nq + 1);
+  double* iouM = reinterpret_cast<double*>(p.ws);                  // [ngl, ntl]
+  double* S = iouM + (size_t)ng * nq;                              // the cost (- score) matrix of the assignment being solved
+  int* reg = reinterpret_cast<int*>(S + (size_t)ng * nq);          // rows of kind 2
+  int *gl = reg + ng, *g3 = gl + ng, *xs = g3 + ng;                // kind 0 / 1 rows; positions in gl of step 3's rows; the assignment
+  int *tl = xs + ng, *t3 = tl + nq, *tdrop = t3 + nq, *tm = tdrop + nq;   // track rows; positions in tl of step 3's; flags
+  MotSparse sq;
+  sq.rcnt = tm + nq; sq.rone = sq.rcnt + ng; sq.rl = sq.rone + ng; sq.xr = sq.rl + ng;
+  sq.ccnt = sq.xr + ng; sq.cone = sq.ccnt + nq; sq.cl = sq.cone + nq;
+  const double thr = p.thr;
+  int fid = p.hdr[H_FRAME];
+
+  for (int b = 0; b < p.B; ++b) {
+    ++fid;
+    const int graw = p.gcounts[b], traw = p.tcounts[b];
+    const int ngr = min(max(graw, 0), ng), ntr = min(max(traw, 0), nq);
+    if (tid == 0 && (graw > ng || traw > nq)) atomicAdd(&p.hdr[H_OVER_ROWS], max(graw - ng, 0) + max(traw - nq, 0));
+    const float* G = p.gt + (size_t)b * ng * 7;
+    const float* Tr = p.tracks + (size_t)b * nq * 8;
+    // ---- the frame's lists: regions; kind-0 rows (class in range, id inside the table) and kind-1 rows; track rows that survive step 1
+    const int nreg = mot_compact<MOT_UPDATE_THREADS>(ngr, reg, wsum, [&](int i) { return mot_kind(G + (size_t)i * 7) == 2; });
+    const int ngl = mot_compact<MOT_UPDATE_THREADS>(ngr, gl, wsum, [&](int i) {
+      const float* g = G + (size_t)i * 7;
+      const int k = mot_kind(g);
+      if (k == 1) return true;
+      if (k != 0 || !(g[5] >= 0.0f && g[5] < (float)nc)) return false;
+      if (!(g[4] >= 0.0f && g[4] < (float)p.G)) { atomicAdd(&p.hdr[H_OVER_GT], 1); return false; }
+      return true;
+    });
+    const int ntl = mot_compact<MOT_UPDATE_THREADS>(ntr, tl, wsum, [&](int j) {
+      const float* t = Tr + (size_t)j * 8;
+      if (!(t[6] >= 0.0f && t[6] < (float)nc)) return false;
+      if (!(t[4] >= 0.0f && t[4] < (float)p.T)) { atomicAdd(&p.hdr[H_OVER_TRK], 1); return false; }
+      const MotBox tb = mot_box(t);
+      for (int r = 0; r < nreg; ++r)
+        if (mot_ioa(tb, mot_box(G + (size_t)reg[r] * 7)) > 0.5) { atomicAdd(&p.counts[(int)t[6] * 16 + K_DROP_REGION], 1); return false; }
+      return true;
+    });
+    // ---- the IoU matrix
+    for (int e = tid; e < ngl * ntl; e += MOT_UPDATE_THREADS) {
+      const int i = e / ntl, j = e - i * ntl;
+      iouM[e] = mot_iou(mot_box(G + (size_t)gl[i] * 7), mot_box(Tr + (size_t)tl[j] * 8));
+    }
+    for (int j = tid; j < ntl; j += MOT_UPDATE_THREADS) { tdrop[j] = 0; tm[j] = 0; }
+    __syncthreads();
+    // ---- 2. distractors
+    const int ndis = mot_compact<MOT_UPDATE_THREADS>(ngl, g3, wsum, [&](int i) { return mot_kind(G + (size_t)gl[i] * 7) == 1; });
+    if (ndis > 0 && ntl > 0) {
+      auto cost2 = [&](int i, int j) -> double {
+        const float* g = G + (size_t)gl[i] * 7;
+        const double v = iouM[(size_t)i * ntl + j];
+        return (v >= thr && (g[6] == 1.0f || (int)g[5] == (int)Tr[(size_t)tl[j] * 8 + 6])) ? -v : 0.0;
+      };
+      for (int e = tid; e < ngl * ntl; e += MOT_UPDATE_THREADS) S[e] = cost2(e / ntl, e % ntl);
+      __syncthreads();
+      mot_assign_sparse<MOT_UPDATE_THREADS>(S, ngl, ntl, w, sq, xs, red, wsum);
+      for (int k = tid; k < ndis; k += MOT_UPDATE_THREADS) {
+        const int i = g3[k], j = xs[i];
+        if (j >= 0 && S[(size_t)i * ntl + j] < 0.0) {
+          tdrop[j] = 1;
+          atomicAdd(&p.counts[(int)Tr[(size_t)tl[j] * 8 + 6] * 16 + K_DROP_DISTRACTOR], 1);
+        }
+      }
+      __syncthreads();
+    }
+    // ---- 3. CLEAR matching, all classes in one block-diagonal assignment
+    const int n3 = mot_compact<MOT_UPDATE_THREADS>(ngl, g3, wsum, [&](int i) { return mot_kind(G + (size_t)gl[i] * 7) == 0; });
+    const int m3 = mot_compact<MOT_UPDATE_THREADS>(ntl, t3, wsum, [&](int j) { return !tdrop[j]; });
+    auto qualifies = [&](int a, int c2, double& v) -> bool {
+      const int i = g3[a], j = t3[c2];
+      v = iouM[(size_t)i * ntl + j];
+      return v >= thr && (int)G[(size_t)gl[i] * 7 + 5] == (int)Tr[(size_t)tl[j] * 8 + 6];
+    };
+    auto cost3 = [&](int a, int c2) -> double {
+      double v;
+      if (!qualifies(a, c2, v)) return 0.0;
+      const int gid = (int)G[(size_t)gl[g3[a]] * 7 + 4], trk = (int)Tr[(size_t)tl[t3[c2]] * 8 + 4];
+      return p.gstate[(size_t)gid * 8 + GS_LAST] == trk + 1 ? -(v + 1000.0) : -v;
+    };
+    if (n3 > 0 && m3 > 0) {
+      for (int e = tid; e < n3 * m3; e += MOT_UPDATE_THREADS) S[e] = cost3(e / m3, e % m3);
+      __syncthreads();
+      mot_assign_sparse<MOT_UPDATE_THREADS>(S, n3, m3, w, sq, xs, red, wsum);
+    } else {
+      for (int a = tid; a < n3; a += MOT_UPDATE_THREADS) xs[a] = -1;
+      __syncthreads();
+    }
+    for (int a = tid; a < n3; a += MOT_UPDATE_THREADS) {
+      const float* g = G + (size_t)gl[g3[a]] * 7;
+      const int c = (int)g[5];
+      int32_t* gs = p.gstate + (size_t)(int)g[4] * 8;
+      int32_t* cn = p.counts + c * 16;
+      atomicAdd(&cn[K_GT], 1);
+      gs[GS_PRESENT] += 1;
+      gs[GS_CLS] = c + 1;
+      const int j = xs[a];
+      double v = 0.0;
+      if (j >= 0 && S[(size_t)a * m3 + j] < 0.0 && qualifies(a, j, v)) {
+        const int trk = (int)Tr[(size_t)tl[t3[j]] * 8 + 4];
+        tm[j] = 1;
+        atomicAdd(&cn[K_TP], 1);
+        atomicAdd(&p.iou_sum[c], v);
+        if (gs[GS_LAST] != 0 && gs[GS_LAST] != trk + 1) atomicAdd(&cn[K_IDSW], 1);
+        gs[GS_LAST] = trk + 1;
+        if (gs[GS_MATCHED] == 0 || gs[GS_LASTF] != fid - 1) gs[GS_RUNS] += 1;
+        gs[GS_MATCHED] += 1;
+        gs[GS_LASTF] = fid;
+      } else {
+        atomicAdd(&cn[K_FN], 1);
+      }
+    }
+    __syncthreads();
+    for (int c2 = tid; c2 < m3; c2 += MOT_UPDATE_THREADS) {
+      int32_t* cn = p.counts + (int)Tr[(size_t)tl[t3[c2]] * 8 + 6] * 16;
+      atomicAdd(&cn[K_TRK], 1);
+      if (!tm[c2]) atomicAdd(&cn[K_FP], 1);
+    }
+    // ---- 4. pair counts
+    for (int e = tid; e < n3 * m3; e += MOT_UPDATE_THREADS) {
+      const int a = e / m3, c2 = e - a * m3;
+      if (S[e] < 0.0) {   // the pair qualifies
+        const int gid = (int)G[(size_t)gl[g3[a]] * 7 + 4], trk = (int)Tr[(size_t)tl[t3[c2]] * 8 + 4];
+        atomicAdd(&p.pair[(size_t)gid * p.T + trk], 1);
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) p.hdr[H_FRAME] = fid;
+}
+
+struct MotEndParams {
+  int nc, G, T, G_used;
+  int32_t* gstate;
+  int32_t* counts;
+  int32_t* pair;
+  int32_t* hdr;
+  unsigned char* ws;
+  size_t per_class;
+};
+
+__global__ __launch_bounds__(MOT_END_THREADS) void mot_end_kernel(MotEndParams p) {
+  __shared__ int wsum[(MOT_END_THREADS / WAVE)];
+  __shared__ MotCand red[(MOT_END_THREADS / WAVE)];
+  const int tid = threadIdx.x, c = blockIdx.x, T = p.T;
+  unsigned char* base = p.ws + (size_t)c * p.per_class;
+  int* rows = reinterpret_cast<int*>(base);
+  int *x = rows + p.G, *cols = x + p.G;
+  const MotLsap w = mot_lsap_carve(base + ((4 * (2 * (size_t)p.G + T) + 15) & ~(size_t)15), p.G, T + 1);
+  int32_t* cn = p.counts + c * 16;
+  if (c == 0 && tid == 0) p.hdr[H_FRAME] = 0;
+  const int n = mot_compact<MOT_END_THREADS>(min(p.G_used, p.G), rows, wsum, [&](int g) { return p.gstate[(size_t)g * 8 + GS_CLS] == c + 1; });
+  if (n == 0) return;
+  for (int a = tid; a < n; a += MOT_END_THREADS) {
+    const int32_t* gs = p.gstate + (size_t)rows[a] * 8;
+    const double ratio = (double)gs[GS_MATCHED] / (double)gs[GS_PRESENT];
+    atomicAdd(&cn[ratio > 0.8 ? K_MT : ratio < 0.2 ? K_ML : K_PT], 1);
+    atomicAdd(&cn[K_GTIDS], 1);
+    if (gs[GS_RUNS] > 1) atomicAdd(&cn[K_FRAG], gs[GS_RUNS] - 1);
+  }
+  // the track ids some gt of the class met
+  const int m = mot_compact<MOT_END_THREADS>(T, cols, wsum, [&](int t) {
+    for (int a = 0; a < n; ++a)
+      if (p.pair[(size_t)rows[a] * T + t]) return true;
+    return false;
+  });
+  if (m > 0) {
+    auto cost = [&](int a, int j) -> double { return -(double)p.pair[(size_t)rows[a] * T + cols[j]]; };
+    mot_assign<MOT_END_THREADS>(cost, n, m, 0.0, w, x, red);
+    int idtp = 0;
+    for (int a = tid; a < n; a += MOT_END_THREADS)
+      if (x[a] >= 0) idtp += p.pair[(size_t)rows[a] * T + cols[x[a]]];
+    if (idtp) atomicAdd(&cn[K_IDTP], idtp);
+    __syncthreads();
+  }
+  // clear what this class used
+  for (size_t e = tid; e < (size_t)n * T; e += MOT_END_THREADS) p.pair[(size_t)rows[e / T] * T + e % T] = 0;
+  for (int e = tid; e < n * 8; e += MOT_END_THREADS) p.gstate[(size_t)rows[e >> 3] * 8 + (e & 7)] = 0;
+}
+
+extern "C" int tamtr_mot_workspace_bytes(int nq, int ng, int nc, int G_cap, int T_cap) {
+  if (nq < 1 || ng < 1 || nc < 1 || G_cap < 1 || T_cap < 1) return 0;
+  const size_t a = mot_update_ws_bytes(nq, ng), b = (size_t)nc * mot_end_ws_per_class(G_cap, T_cap);
+  const size_t n = (a > b ? a : b) + 16;
+  return n > 0x7fffffff ? 0 : (int)n;
+}
+
+static bool mot_unsupported(int nq, int ng, int nc, int G, int T) {
+  return tamtr_mot_workspace_bytes(nq, ng, nc, G, T) == 0 || mot_lsap_bytes(ng, (size_t)nq + 1) > 60 * 1024 || (size_t)G * T > 0x7fffffff ||
+         G > (1 << 24) || T > (1 << 24) || nc > (1 << 16);   // ids travel as fp32
+}
+
+extern "C" int tamtr_mot_update(const float* tracks, const int32_t* tcounts, const float* gt, const int32_t* gcounts, int B, int nq, int ng,
+                                int nc, double iou_thr, int32_t* gstate, int32_t* counts, double* iou_sum, int32_t* pair, int32_t* hdr,
+                                int G_cap, int T_cap, void* workspace, int workspace_bytes, void* stream) {
+  if (!tracks || !tcounts || !gt || !gcounts || !gstate || !counts || !iou_sum || !pair || !hdr || !workspace || B < 1 || nq < 1 || ng < 1 ||
+      nc < 1 || G_cap < 1 || T_cap < 1 || !(iou_thr > 0.0) || ((uintptr_t)workspace & 15))
+    return TAMTR_EINVAL;
+  if (mot_unsupported(nq, ng, nc, G_cap, T_cap)) return TAMTR_EUNSUP;
+  if (workspace_bytes < tamtr_mot_workspace_bytes(nq, ng, nc, G_cap, T_cap)) return TAMTR_EINVAL;
+  MotParams p{tracks, tcounts, gt, gcounts, B, nq, ng, nc, G_cap, T_cap, iou_thr, gstate, counts, iou_sum, pair, hdr,
+              static_cast<unsigned char*>(workspace)};
+  hipLaunchKernelGGL(mot_update_kernel, dim3(1), dim3(MOT_UPDATE_THREADS), mot_lsap_bytes(ng, (size_t)nq + 1), (hipStream_t)stream, p);
+  return tamtr_launch_status();
+}
+
+extern "C" int tamtr_mot_end_sequence(int nc, int32_t* gstate, int32_t* counts, int32_t* pair, int32_t* hdr, int G_cap, int T_cap, int G_used,
+                                      void* workspace, int workspace_bytes, void* stream) {
+  if (!gstate || !counts || !pair || !hdr || !workspace || nc < 1 || G_cap < 1 || T_cap < 1 || G_used < 0 || ((uintptr_t)workspace & 15))
+    return TAMTR_EINVAL;
+  if (mot_unsupported(1, 1, nc, G_cap, T_cap)) return TAMTR_EUNSUP;
+  if ((size_t)workspace_bytes < (size_t)nc * mot_end_ws_per_class(G_cap, T_cap)) return TAMTR_EINVAL;
+  MotEndParams p{nc, G_cap, T_cap, G_used, gstate, counts, pair, hdr, static_cast<unsigned char*>(workspace), mot_end_ws_per_class(G_cap, T_cap)};
+  hipLaunchKernelGGL(mot_end_kernel, dim3(nc), dim3(MOT_END_THREADS), 0, (hipStream_t)stream, p);
+  return tamtr_launch_status();
+}

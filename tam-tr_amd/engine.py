@@ -623,6 +623,154 @@ def coco_evaluate(images, nc, max_dets=(1, 10, 100), names=None, return_matches=
     return out
 
 
+# ------------------------------------------------------------------------------------------------ MOT evaluation
+# the columns of the per-class count table, on the host and on the device (csrc/mot.hip keeps them as i32 [nc, 16])
+MOT_COUNT_KEYS = ('TP', 'FN', 'FP', 'IDSW', 'gt_dets', 'trk_dets', 'Frag', 'MT', 'PT', 'ML', 'IDTP', 'gt_ids', 'drop_region', 'drop_distractor')
+
+
+def mot_iou_matrix(a, b):
+    """fp64 IoU of boxes a [n, 4] and b [m, 4] (x1 y1 x2 y2), op by op as csrc/mot.hip: 0 where iw <= 0, ih <= 0 or union <= 0."""
+    a, b = np.asarray(a, np.float64).reshape(-1, 4), np.asarray(b, np.float64).reshape(-1, 4)
+    iw = np.minimum(a[:, None, 2], b[None, :, 2]) - np.maximum(a[:, None, 0], b[None, :, 0])
+    ih = np.minimum(a[:, None, 3], b[None, :, 3]) - np.maximum(a[:, None, 1], b[None, :, 1])
+    inter = iw * ih
+    area_a, area_b = (a[:, 2] - a[:, 0]) * (a[:, 3] - a[:, 1]), (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    union = (area_a[:, None] + area_b[None, :]) - inter
+    ok = (iw > 0) & (ih > 0) & (union > 0)
+    return np.where(ok, inter / np.where(ok, union, 1.0), 0.0), np.where((iw > 0) & (ih > 0), inter, 0.0)
+
+
+def _mot_assign(score):
+    """The (row, column) pairs of the assignment that maximises the total score, those with a score > 0."""
+    from scipy.optimize import linear_sum_assignment
+    if score.size == 0:
+        return []
+    r, c = linear_sum_assignment(score, maximize=True)
+    return [(int(i), int(j)) for i, j in zip(r, c) if score[i, j] > 0]
+
+
+def mot_new_counts(nc):
+    c = {k: np.zeros(int(nc), np.int64) for k in MOT_COUNT_KEYS}
+    c['iou_sum'] = np.zeros(int(nc), np.float64)
+    return c
+
+
+def mot_evaluate(sequences, nc, iou=0.5):
+    """CLEAR-MOT and identity counts of tracker output against ground truth (TrackEval's CLEAR and Identity definitions, restated; the
+    rule is written out in csrc/mot.hip, whose checker this is, and this is the path for a machine without a GPU).
+    sequences: a list of sequences, each a list of frames in order, each frame (gt [m, 7] x1 y1 x2 y2 id cls kind, tracks [k, 6]
+    x1 y1 x2 y2 id cls); kind 0 object, 1 distractor, 2 ignored region.  All arithmetic is fp64 on the fp32 values.  A ground truth
+    (and a track) identity is the pair (class, id).  -> {key: i64 [nc] for key in MOT_COUNT_KEYS, 'iou_sum': f64 [nc]}; counts of
+    several sequences add, and mot_summary turns them into MOTA / MOTP / IDF1 ..."""
+    nc, thr = int(nc), float(iou)
+    out = mot_new_counts(nc)
+    f32 = lambda x, w: np.asarray(x, np.float32).reshape(-1, w)   # noqa: E731
+    for frames in sequences:
+        last, present, matched, runs, last_frame, pair = {}, {}, {}, {}, {}, {}
+        for fid, (gt, trk) in enumerate(frames, 1):
+            gt, trk = f32(gt, 7), f32(trk, 6)
+            kind = gt[:, 6]
+            in_range = lambda c: (c >= 0) & (c < nc)   # noqa: E731
+            trk = trk[in_range(trk[:, 5])]
+            tcls = trk[:, 5].astype(np.int64)
+            # 1. regions
+            reg = gt[kind == 2]
+            if len(reg) and len(trk):
+                _, inter = mot_iou_matrix(trk[:, :4], reg[:, :4])
+                area = (trk[:, 2].astype(np.float64) - trk[:, 0]) * (trk[:, 3].astype(np.float64) - trk[:, 1])
+                ioa = np.where(area[:, None] > 0, inter / np.where(area > 0, area, 1.0)[:, None], 0.0)
+                drop = (ioa > 0.5).any(1)
+                np.add.at(out['drop_region'], tcls[drop], 1)
+                trk, tcls = trk[~drop], tcls[~drop]
+            # 2. distractors
+            g = gt[((kind == 0) & in_range(gt[:, 5])) | (kind == 1)]
+            if (g[:, 6] == 1).any() and len(trk):
+                m, _ = mot_iou_matrix(g[:, :4], trk[:, :4])
+                agree = (g[:, 6] == 1)[:, None] | (g[:, 5].astype(np.int64)[:, None] == tcls[None, :])
+                drop = np.zeros(len(trk), bool)
+                for i, j in _mot_assign(np.where((m >= thr) & agree, m, 0.0)):
+                    drop[j] |= g[i, 6] == 1
+                np.add.at(out['drop_distractor'], tcls[drop], 1)
+                trk, tcls = trk[~drop], tcls[~drop]
+            g = g[g[:, 6] == 0]
+            gcls = g[:, 5].astype(np.int64)
+            # 3. CLEAR matching and 4. pair counts, per class
+            for c in range(nc):
+                gc, tc = g[gcls == c], trk[tcls == c]
+                gid, tid = [(c, int(i)) for i in gc[:, 4]], [int(i) for i in tc[:, 4]]
+                out['gt_dets'][c] += len(gc)
+                out['trk_dets'][c] += len(tc)
+                for k in gid:
+                    present[k] = present.get(k, 0) + 1
+                m, _ = mot_iou_matrix(gc[:, :4], tc[:, :4])
+                q = m >= thr
+                keeps = np.array([[last.get(k) == t for t in tid] for k in gid], bool).reshape(m.shape)
+                pairs = _mot_assign(np.where(q & keeps, m + 1000.0, np.where(q, m, 0.0)))
+                out['TP'][c] += len(pairs)
+                out['FN'][c] += len(gc) - len(pairs)
+                out['FP'][c] += len(tc) - len(pairs)
+                for i, j in pairs:
+                    k = gid[i]
+                    out['iou_sum'][c] += m[i, j]
+                    out['IDSW'][c] += k in last and last[k] != tid[j]
+                    last[k] = tid[j]
+                    runs[k] = runs.get(k, 0) + (last_frame.get(k) != fid - 1)
+                    matched[k] = matched.get(k, 0) + 1
+                    last_frame[k] = fid
+                for i, j in zip(*np.nonzero(q)):
+                    pair[(gid[i], tid[j])] = pair.get((gid[i], tid[j]), 0) + 1
+        # the sequence's reduction
+        for k, n in present.items():
+            c, ratio = k[0], matched.get(k, 0) / n
+            out['gt_ids'][c] += 1
+            out['MT' if ratio > 0.8 else 'ML' if ratio < 0.2 else 'PT'][c] += 1
+            out['Frag'][c] += max(runs.get(k, 0) - 1, 0)
+        for c in range(nc):
+            rows = sorted({g for g, _ in pair if g[0] == c})
+            cols = sorted({t for g, t in pair if g[0] == c})
+            tab = np.zeros((len(rows), len(cols)), np.int64)
+            for (g, t), v in pair.items():
+                if g[0] == c:
+                    tab[rows.index(g), cols.index(t)] = v
+            out['IDTP'][c] += sum(int(tab[i, j]) for i, j in _mot_assign(tab))
+    return out
+
+
+def mot_summary(counts, names=None):
+    """Per-class rows and an 'all' row of summed counts from mot_evaluate's (or MotEvaluator's) counts.  A ratio whose denominator is 0
+    is nan.  -> {'all': row, 'per_class': [row, ...]}; a row holds every count, IDFN / IDFP, and MOTA MOTP Recall Precision IDF1 IDP IDR."""
+    def row(c, label):
+        div = lambda a, b: float(a) / float(b) if b else float('nan')   # noqa: E731
+        r = {'class': label, **{k: int(c[k]) for k in MOT_COUNT_KEYS}, 'iou_sum': float(c['iou_sum'])}
+        r['IDFN'], r['IDFP'] = r['gt_dets'] - r['IDTP'], r['trk_dets'] - r['IDTP']
+        r['MOTA'] = 1.0 - div(r['FN'] + r['FP'] + r['IDSW'], r['gt_dets'])
+        r['MOTP'] = div(r['iou_sum'], r['TP'])
+        r['Recall'], r['Precision'] = div(r['TP'], r['gt_dets']), div(r['TP'], r['trk_dets'])
+        r['IDF1'] = div(r['IDTP'], r['IDTP'] + 0.5 * r['IDFP'] + 0.5 * r['IDFN'])
+        r['IDP'], r['IDR'] = div(r['IDTP'], r['trk_dets']), div(r['IDTP'], r['gt_dets'])
+        return r
+
+    keys = MOT_COUNT_KEYS + ('iou_sum',)
+    nc = len(np.atleast_1d(counts['TP']))
+    per = [row({k: np.atleast_1d(counts[k])[c] for k in keys}, names[c] if names is not None else c) for c in range(nc)]
+    return {'all': row({k: np.atleast_1d(counts[k]).sum() for k in keys}, 'all'), 'per_class': per}
+
+
+def mot_table(summary, title=''):
+    """mot_summary's rows as the table every MOT benchmark prints (percentages for the ratios)."""
+    cols = ('MOTA', 'MOTP', 'IDF1', 'IDP', 'IDR', 'Recall', 'Precision')
+    ints = ('gt_ids', 'MT', 'PT', 'ML', 'TP', 'FP', 'FN', 'IDSW', 'Frag')
+    lines = [f'{title or "class":>16s}' + ''.join(f'{c:>8s}' for c in cols) + ''.join(f'{c:>8s}' for c in ints)]
+    for r in summary['per_class'] + [summary['all']]:
+        lines.append(f'{str(r["class"]):>16s}' + ''.join(f'{100 * r[c]:8.2f}' for c in cols) + ''.join(f'{r[c]:8d}' for c in ints))
+    return '\n'.join(lines)
+
+
+def mot_add_counts(a, b):
+    """Counts of several sequences (or runs) add."""
+    return {k: a[k] + b[k] for k in a}
+
+
 def cm_conf(conf):
     """The confusion matrix's confidence threshold from the validator's: 0.25 when that is None or the default 0.001 (metrics.py:818)."""
     return 0.25 if conf in (None, 0.001) else conf

@@ -1922,6 +1922,80 @@ def bytetrack_update(out, counts, state, capacity, track_high_thresh=0.5, track_
     return tracks, tcounts
 
 
+# the MOT evaluator's state (csrc/mot.hip states the columns): name, dtype, shape from (nc, G, T); all zero when fresh
+MOT_STATE_SPEC = (('gstate', torch.int32, lambda nc, G, T: (G, 8)), ('counts', torch.int32, lambda nc, G, T: (nc, 16)),
+                  ('iou_sum', torch.float64, lambda nc, G, T: (nc,)), ('pair', torch.int32, lambda nc, G, T: (G, T)),
+                  ('hdr', torch.int32, lambda nc, G, T: (8,)))
+
+
+def mot_workspace_bytes(nq, ng, nc, gt_capacity, track_capacity):
+    """Bytes of device workspace tamtr_mot_update and tamtr_mot_end_sequence need (no GPU call)."""
+    n = _lib.lib().tamtr_mot_workspace_bytes(int(nq), int(ng), int(nc), int(gt_capacity), int(track_capacity))
+    if n <= 0:
+        raise _lib.TamtrHipError(f'mot: nq {nq}, ng {ng}, nc {nc} with capacities {gt_capacity} x {track_capacity} is outside what the '
+                                 'kernel is built for')
+    return n
+
+
+def _mot_state(what, state, nc, G, T):
+    for k, dt, shape in MOT_STATE_SPEC:
+        t = state.get(k) if isinstance(state, dict) else None
+        want = shape(nc, G, T)
+        if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
+            got = None if t is None else (t.dtype, tuple(t.shape))
+            raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want}, got {got}')
+    require_gpu(*(state[k] for k, _, _ in MOT_STATE_SPEC))
+
+
+def _mot_workspace(what, workspace, need, device):
+    if workspace is None:
+        workspace = torch.empty(need, device=device, dtype=torch.uint8)
+    require_gpu(workspace)
+    if workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous() or workspace.data_ptr() % 16:
+        raise _lib.TamtrHipError(f'{what}: workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {need} bytes')
+    return workspace
+
+
+def mot_update(tracks, tcounts, gt, gcounts, state, nc, gt_capacity, track_capacity, iou=0.5, workspace=None):
+    """Steps 1 to 4 of the MOT evaluation rule (csrc/mot.hip; engine.mot_evaluate is its numpy statement) for the B frames of a batch,
+    in order, in one launch.  tracks f32 [B, nq, 8] and tcounts i32 [B] are bytetrack_update's outputs on the GPU; gt f32 [B, ng, 7]
+    (x1 y1 x2 y2 id cls kind, the id of a kind-0 row being its dense row in [0, gt_capacity)) and gcounts i32 [B] are on the GPU too.
+    state: a dict of device tensors as MOT_STATE_SPEC lists them, updated in place.  Every check comes before the launch; no
+    synchronisation."""
+    if tracks.dim() != 3 or tracks.shape[-1] != 8 or tracks.shape[0] < 1 or tracks.shape[1] < 1:
+        raise _lib.TamtrHipError(f'mot_update: expected tracks [B, nq, 8], got {tuple(tracks.shape)}')
+    B, nq, _ = tracks.shape
+    if gt.dim() != 3 or gt.shape[0] != B or gt.shape[1] < 1 or gt.shape[2] != 7:
+        raise _lib.TamtrHipError(f'mot_update: expected gt [B, ng, 7] with B = {B}, got {tuple(gt.shape)}')
+    ng = gt.shape[1]
+    if tuple(tcounts.shape) != (B,) or tuple(gcounts.shape) != (B,):
+        raise _lib.TamtrHipError(f'mot_update: tcounts and gcounts must be [B] = [{B}], got {tuple(tcounts.shape)} and {tuple(gcounts.shape)}')
+    if tracks.dtype != torch.float32 or gt.dtype != torch.float32 or tcounts.dtype != torch.int32 or gcounts.dtype != torch.int32:
+        raise _lib.TamtrHipError('mot_update: tracks and gt must be float32, tcounts and gcounts int32')
+    nc, G, T = int(nc), int(gt_capacity), int(track_capacity)
+    if nc < 1 or G < 1 or T < 1 or not float(iou) > 0:
+        raise _lib.TamtrHipError(f'mot_update: nc, the capacities and iou must be positive, got {nc}, {G}, {T}, {iou}')
+    _mot_state('mot_update', state, nc, G, T)
+    require_gpu(tracks, tcounts, gt, gcounts)
+    workspace = _mot_workspace('mot_update', workspace, mot_workspace_bytes(nq, ng, nc, G, T), tracks.device)
+    tracks, tcounts, gt, gcounts = _c(tracks), _c(tcounts), _c(gt), _c(gcounts)
+    call('tamtr_mot_update', ptr(tracks), ptr(tcounts), ptr(gt), ptr(gcounts), B, nq, ng, nc, float(iou), ptr(state['gstate']),
+         ptr(state['counts']), ptr(state['iou_sum']), ptr(state['pair']), ptr(state['hdr']), G, T, ptr(workspace), int(workspace.numel()),
+         stream_ptr())
+
+
+def mot_end_sequence(state, nc, gt_capacity, track_capacity, gt_used, workspace=None):
+    """The per-sequence reduction of the MOT evaluation (MT / PT / ML / Frag and the identity assignment per class) in one launch; adds
+    to state['counts'] and clears the per-sequence state.  gt_used: the number of dense gt rows the host handed out.  No synchronisation."""
+    nc, G, T = int(nc), int(gt_capacity), int(track_capacity)
+    if nc < 1 or G < 1 or T < 1 or int(gt_used) < 0:
+        raise _lib.TamtrHipError(f'mot_end_sequence: nc and the capacities must be positive and gt_used >= 0, got {nc}, {G}, {T}, {gt_used}')
+    _mot_state('mot_end_sequence', state, nc, G, T)
+    workspace = _mot_workspace('mot_end_sequence', workspace, mot_workspace_bytes(1, 1, nc, G, T), state['hdr'].device)
+    call('tamtr_mot_end_sequence', nc, ptr(state['gstate']), ptr(state['counts']), ptr(state['pair']), ptr(state['hdr']), G, T,
+         min(int(gt_used), G), ptr(workspace), int(workspace.numel()), stream_ptr())
+
+
 @torch.no_grad()
 def val_postprocess_match(y, cls, bboxes, batch_idx, ori_hw, imgsz, conf, iou, single_cls=False, max_wh=7680., return_device_labels=False):
     """engine.Validator.update's per-image work (RTDETRValidator.postprocess, models/rtdetrworld/val.py:102-173, and match_predictions,

@@ -185,10 +185,12 @@ class Predictor:
         self.last_img = self.last_y = None
 
     @torch.no_grad()
-    def run_batch(self, ims, tracker=None):
+    def run_batch(self, ims, tracker=None, gt_frames=None, evaluator=None):
         """Network inputs u8 [B, S, S, 3] (host) + original (h, w) per image -> host (out [B, nq, 6], keep [B, nq], counts [B]).
         With a tracker (track.ByteTracker) the batch's frames also go through one tracker launch, and its rows ride in the same copy:
-        -> host (out, keep, counts, tracks [B, nq, 8], tcounts [B])."""
+        -> host (out, keep, counts, tracks [B, nq, 8], tcounts [B]).  With gt_frames (B host arrays [m, 7]) and an evaluator
+        (track.MotEvaluator) as well, one more launch scores the tracker's rows where they lie; the evaluator's header rides in the
+        same copy and the time goes under times['mot']."""
         arr, hw = ims
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
         ev[0].record()
@@ -203,37 +205,53 @@ class Predictor:
         # one device-to-host copy for all the outputs
         B, nq = keep.shape
         parts = [out.view(-1), keep.view(torch.float32).view(-1), counts.view(torch.float32)]
+        scoring = tracker is not None and evaluator is not None and gt_frames is not None
+        ev_mot = None
         if tracker is not None:
             tracks, tcounts = tracker.update(out, counts)
             parts += [tracks.view(-1), tcounts.view(torch.float32), tracker.state['hdr'].view(torch.float32)]
+            if scoring:
+                ev_mot = torch.cuda.Event(enable_timing=True)
+                ev_mot.record()
+                evaluator.update(tracks, tcounts, gt_frames)
+                parts.append(evaluator.state['hdr'].view(torch.float32))
         ev[4].record()
         packed = torch.cat(parts)
         host = torch.empty(packed.shape, dtype=torch.float32, pin_memory=True)
         host.copy_(packed, non_blocking=True)
         ev[5].record()
         ev[5].synchronize()
-        for k, (a, b) in zip(('h2d', 'forward', 'postprocess', 'track', 'd2h'), zip(ev[:-1], ev[1:])):
-            self.times[k] += a.elapsed_time(b)
+        spans = [('h2d', ev[0], ev[1]), ('forward', ev[1], ev[2]), ('postprocess', ev[2], ev[3]), ('track', ev[3], ev_mot or ev[4]), ('d2h', ev[4], ev[5])]
+        if scoring:
+            spans.append(('mot', ev_mot, ev[4]))
+        for k, a, b in spans:
+            self.times[k] = self.times.get(k, 0.0) + a.elapsed_time(b)
         if self.keep_raw:
             self.last_img, self.last_y = img, y
         o, kp, c, rest = host.split([B * nq * 6, B * nq, B, host.numel() - B * nq * 7 - B])
         res = o.view(B, nq, 6), kp.view(torch.int32).view(B, nq), c.view(torch.int32)
         if tracker is None:
             return res
-        tr, tc, hdr = rest.split([B * nq * 8, B, 8])
+        tr, tc, hdr, mhdr = rest.split([B * nq * 8, B, 8, 8 if scoring else 0])
         tracker.check_overflow(hdr.view(torch.int32)[3])
+        if scoring:
+            evaluator.check_overflow(mhdr.view(torch.int32))
         return res + (tr.view(B, nq, 8), tc.view(torch.int32))
 
     def predict(self, source):
         """Yields one Detections per image, in the sorted order of list_sources(source)."""
         yield from self._run(list_sources(source), None)
 
-    def track(self, source, tracker=None, persist=False):
+    def track(self, source, tracker=None, persist=False, gt=None, evaluator=None):
         """The sorted files of `source` as ONE sequence (the reference's model.track): the batches of predict, then one tracker launch
         per batch.  Yields one Detections per frame whose boxes are the track rows (x1 y1 x2 y2 from the filter, score, cls) and
         whose `id` holds the track ids; a frame for which the tracker returned nothing keeps its plain detections and id None
         (trackers/track.py:46-50).  tracker: a track.ByteTracker, a bytetrack.yaml path, or None for the defaults; persist=True keeps
-        the tracker (and its tracks) of the previous call."""
+        the tracker (and its tracks) of the previous call.
+        gt + evaluator: the sequence's ground truth, one array [m, 7] (x1 y1 x2 y2 id cls kind, track.read_mot) per frame in file order
+        (missing frames are empty), and a track.MotEvaluator: every batch's rows are scored on the device right after the tracker's
+        launch (a frame without track rows is an empty track set, as write_mot has it), the sequence is ended after the last frame,
+        and speed() has a 'mot' entry; evaluator.results() then holds the metrics.  Without both, nothing changes."""
         from .track import ByteTracker
         if isinstance(tracker, ByteTracker):
             self.tracker = tracker
@@ -241,9 +259,17 @@ class Predictor:
                 tracker.reset()
         elif self.tracker is None or not persist:
             self.tracker = ByteTracker.from_yaml(tracker, self.device) if tracker else ByteTracker(self.device)
-        yield from self._run(list_sources(source), self.tracker)
+        files = list_sources(source)
+        if gt is None or evaluator is None:
+            self.times.pop('mot', None)      # the key exists only while a run is scored
+            yield from self._run(files, self.tracker)
+            return
+        gt = list(gt)[:len(files)]
+        gt += [np.zeros((0, 7), np.float32)] * (len(files) - len(gt))
+        yield from self._run(files, self.tracker, gt, evaluator)
+        evaluator.end_sequence()
 
-    def _run(self, files, tracker):
+    def _run(self, files, tracker, gt=None, evaluator=None):
         with ThreadPoolExecutor(max_workers=self.workers) as pool:
             chunks = [files[i:i + self.batch] for i in range(0, len(files), self.batch)]
             pending = [pool.submit(load_image, f, self.imgsz) for f in chunks[0]] if chunks else []
@@ -255,7 +281,11 @@ class Predictor:
                 pending = [pool.submit(load_image, f, self.imgsz) for f in chunks[k + 1]] if k + 1 < len(chunks) else []
                 origs = [o for o, _ in loaded]
                 hw = [o.shape[:2] for o in origs]
-                res = self.run_batch((np.stack([r for _, r in loaded]), hw), tracker)
+                ims = (np.stack([r for _, r in loaded]), hw)
+                if evaluator is None:
+                    res = self.run_batch(ims, tracker)
+                else:
+                    res = self.run_batch(ims, tracker, gt[k * self.batch:k * self.batch + len(chunk)], evaluator)
                 out, counts = res[0], res[2]
                 self.seen += len(chunk)
                 for i, path in enumerate(chunk):

@@ -6,6 +6,14 @@ utils/kalman_filter.py, utils/matching.py, cfg/trackers/bytetrack.yaml): one HIP
     tracks, tcounts = tracker.update(out, counts)       # the outputs of ops.detect_postprocess, frames in order; no synchronisation
 
 `Predictor.track(source)` (predict.py) drives it and yields Detections with ids; tools/track.py is the command line.
+
+MOT evaluation next to it (CLEAR-MOT and identity metrics; the rule is written out in csrc/mot.hip, engine.mot_evaluate states it in
+numpy): one more launch per batch on the rows the tracker left on the device, one launch per sequence for the reduction.
+
+    ev = MotEvaluator(device, nc)
+    ev.update(tracks, tcounts, gt_frames)               # gt_frames: B host arrays [m, 7] (read_mot); no synchronisation
+    ev.end_sequence()
+    ev.results(names)                                   # synchronises: {'all': row, 'per_class': [...]}, MOTA / MOTP / IDF1 ...
 """
 import numpy as np
 import torch
@@ -20,6 +28,10 @@ YAML_KEYS = ('track_high_thresh', 'track_low_thresh', 'new_track_thresh', 'track
 
 
 class TrackerOverflow(RuntimeError):
+    pass
+
+
+class MotOverflow(RuntimeError):
     pass
 
 
@@ -106,3 +118,137 @@ def write_mot(path, frames):
     with open(path, 'w') as fh:
         fh.writelines(lines)
     return len(lines)
+
+
+# ------------------------------------------------------------------------------------------------ MOT evaluation
+MOT_HDR_FRAME, MOT_HDR_OVER_GT, MOT_HDR_OVER_TRK, MOT_HDR_OVER_ROWS = 0, 1, 2, 3
+# VisDrone-MOT annotation categories: 0 ignored region, 1 .. 10 the classes, 11 others
+VISDRONE_CATEGORIES = {0: (0, 2), **{c: (c - 1, 0) for c in range(1, 11)}, 11: (0, 1)}
+
+
+class MotEvaluator:
+    """CLEAR-MOT and identity counts of tracker rows against ground truth, kept on `device` (csrc/mot.hip states the rule and the
+    state).  gt_capacity: ground-truth identities (class, id) per sequence; track_capacity: track ids are used as they are and must
+    be below it; nq / ng: track / ground-truth rows per frame the workspace is sized for (a batch with wider track rows gets a larger
+    workspace on its first use; ground-truth rows beyond ng are counted as overflow)."""
+
+    def __init__(self, device, nc, iou=0.5, gt_capacity=1024, track_capacity=4096, nq=300, ng=300):
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise ops._lib.TamtrHipError('MotEvaluator needs an MI355X; engine.mot_evaluate is the host path')
+        self.nc, self.iou = int(nc), float(iou)
+        self.gt_capacity, self.track_capacity, self.nq, self.ng = int(gt_capacity), int(track_capacity), int(nq), int(ng)
+        if min(self.nc, self.gt_capacity, self.track_capacity, self.nq, self.ng) < 1:
+            raise ValueError('nc, the capacities, nq and ng must be positive')
+        self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
+        self.state = {k: torch.zeros(shape(self.nc, self.gt_capacity, self.track_capacity), device=self.device, dtype=dt)
+                      for k, dt, shape in ops.MOT_STATE_SPEC}
+        self.rows, self.open = {}, False
+
+    def _ws_bytes(self):
+        return ops.mot_workspace_bytes(self.nq, self.ng, self.nc, self.gt_capacity, self.track_capacity)
+
+    def reset(self):
+        """Forget every count and the sequence in progress.  No synchronisation."""
+        for v in self.state.values():
+            v.zero_()
+        self.rows, self.open = {}, False
+
+    def upload(self, gt_frames):
+        """B host arrays [m, 7] -> gt f32 [B, ng, 7] and gcounts i32 [B] on the device, in one copy; the ground-truth identities
+        (class, id) of the kind-0 rows are replaced by their dense rows, handed out in order of appearance."""
+        B, ng = len(gt_frames), self.ng
+        n = B * ng * 7
+        buf = np.zeros(n + B, np.float32)
+        gt, cnt = buf[:n].reshape(B, ng, 7), buf[n:].view(np.int32)
+        for b, g in enumerate(gt_frames):
+            g = np.array(g, np.float32).reshape(-1, 7)
+            for i in np.flatnonzero((g[:, 6] == 0) & (g[:, 5] >= 0) & (g[:, 5] < self.nc)):
+                g[i, 4] = self.rows.setdefault((int(g[i, 5]), int(g[i, 4])), len(self.rows))
+            cnt[b] = len(g)
+            gt[b, :min(len(g), ng)] = g[:ng]
+        dev = torch.from_numpy(buf).pin_memory().to(self.device, non_blocking=True)
+        return dev[:n].view(B, ng, 7), dev[n:].view(torch.int32)
+
+    def update(self, tracks, tcounts, gt_frames):
+        """tracks f32 [B, nq, 8], tcounts i32 [B] on the device (ByteTracker.update); gt_frames: B host arrays [m, 7] x1 y1 x2 y2 id
+        cls kind.  The ground truth goes up in one copy (upload), one launch follows; nothing synchronises."""
+        B = tracks.shape[0]
+        if len(gt_frames) != B:
+            raise ValueError(f'{len(gt_frames)} ground-truth frames for a batch of {B}')
+        if tracks.shape[1] > self.nq:
+            self.nq = int(tracks.shape[1])
+            self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
+        gt, gcounts = self.upload(gt_frames)
+        ops.mot_update(tracks, tcounts, gt, gcounts, self.state, self.nc, self.gt_capacity, self.track_capacity, self.iou, self.workspace)
+        self.open = True
+
+    def end_sequence(self):
+        """Reduce the sequence in progress (one launch) and start a new one: ground-truth ids may be used again.  No synchronisation."""
+        ops.mot_end_sequence(self.state, self.nc, self.gt_capacity, self.track_capacity, len(self.rows), self.workspace)
+        self.rows, self.open = {}, False
+
+    def check_overflow(self, hdr):
+        """Raise when the header (read by the caller, e.g. from the predictor's packed copy) counts anything beyond a capacity."""
+        g, t, r = (int(hdr[i]) for i in (MOT_HDR_OVER_GT, MOT_HDR_OVER_TRK, MOT_HDR_OVER_ROWS))
+        if g or t or r:
+            raise MotOverflow(f'{g} rows with a ground-truth identity beyond gt_capacity {self.gt_capacity}, {t} with a track id beyond '
+                              f'track_capacity {self.track_capacity}, {r} rows beyond ng {self.ng} / nq {self.nq} per frame were left out: '
+                              'build the evaluator with larger capacities')
+
+    def counts(self):
+        """The run's counts as engine.mot_evaluate returns them (synchronises; raises MotOverflow)."""
+        from .engine import MOT_COUNT_KEYS
+        if self.open:
+            raise RuntimeError('a sequence is in progress: call end_sequence() before reading the results')
+        c, s, hdr = (self.state[k].cpu().numpy() for k in ('counts', 'iou_sum', 'hdr'))
+        self.check_overflow(hdr)
+        out = {k: c[:, i].astype(np.int64) for i, k in enumerate(MOT_COUNT_KEYS)}
+        out['iou_sum'] = s.copy()
+        return out
+
+    def results(self, names=None):
+        """engine.mot_summary of the sequences ended so far (synchronises; raises MotOverflow)."""
+        from .engine import mot_summary
+        return mot_summary(self.counts(), names)
+
+
+def pack_track_rows(frames, nq, device):
+    """Per-frame host rows [k, 6] (x1 y1 x2 y2 id cls, read_mot(gt=False)) -> tracks f32 [B, nq, 8] and tcounts i32 [B] on `device`, laid
+    out as ByteTracker.update leaves them (score 1, idx = the row), in one copy.  A frame with more than nq rows keeps its count."""
+    B = len(frames)
+    buf = np.zeros(B * nq * 8 + B, np.float32)
+    rows, cnt = buf[:B * nq * 8].reshape(B, nq, 8), buf[B * nq * 8:].view(np.int32)
+    for b, f in enumerate(frames):
+        f = np.asarray(f, np.float32).reshape(-1, 6)
+        k = min(len(f), nq)
+        rows[b, :k, :5], rows[b, :k, 5], rows[b, :k, 6], rows[b, :k, 7] = f[:k, :5], 1.0, f[:k, 5], np.arange(k)
+        cnt[b] = len(f)
+    dev = torch.from_numpy(buf).to(device)
+    return dev[:B * nq * 8].view(B, nq, 8), dev[B * nq * 8:].view(torch.int32)
+
+
+def read_mot(path, gt=True, category_map=None, frames=None):
+    """A VisDrone-MOT file (`frame,id,left,top,width,height,score,category,truncation,occlusion`, frames 1-based) -> one fp32 array per
+    frame 1 .. max(last frame in the file, `frames`).  gt=True: an annotation file -> [m, 7] x1 y1 x2 y2 id cls kind, where category 0
+    (ignored region) gives kind 2, `score == 0` or category 11 (others) gives kind 1, and categories 1 .. 10 give classes 0 .. 9 with
+    kind 0; category_map {category: (cls, kind)} replaces that table (a category it lacks is a distractor).  gt=False: a result file
+    as write_mot writes it -> [k, 6] x1 y1 x2 y2 id cls, the category being the class."""
+    table = VISDRONE_CATEGORIES if category_map is None else category_map
+    rows = {}
+    with open(path) as fh:
+        for line in fh:
+            v = line.replace(',', ' ').split()
+            if not v:
+                continue
+            f, tid, x, y, w, h, score, cat = int(float(v[0])), float(v[1]), *(float(e) for e in v[2:7]), int(float(v[7]))
+            box = [x, y, x + w, y + h, tid]
+            if gt:
+                cls, kind = table.get(cat, (0, 1))
+                if kind == 0 and score == 0:
+                    kind = 1
+                rows.setdefault(f, []).append(box + [cls, kind])
+            else:
+                rows.setdefault(f, []).append(box + [cat])
+    n = max(max(rows, default=0), frames or 0)
+    return [np.asarray(rows.get(f, []), np.float32).reshape(-1, 7 if gt else 6) for f in range(1, n + 1)]

@@ -1,0 +1,71 @@
+#!/usr/bin/env python3
+"""Score VisDrone-MOT result files against annotation files: CLEAR-MOT (MOTA, MOTP, FP, FN, IDSW, Frag, MT / PT / ML) and identity
+(IDF1, IDP, IDR) metrics per class, per sequence and over all sequences.  The rule is written out in tam-tr_amd/csrc/mot.hip.
+
+    python tools/mot_eval.py --gt annotations/ --results runs/track/TAMTR/ --names pedestrian,people,... [--host] [--batch 4]
+
+Every `<sequence>.txt` of --results (as tools/track.py --save-mot writes them) is scored against `<sequence>.txt` of --gt.  By default the
+frames go through the device path in batches (track.MotEvaluator: one launch per batch, one per sequence); --host runs the numpy
+statement of the same rule (engine.mot_evaluate) and needs no GPU.  The tables are printed, then one JSON line.
+"""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def parse_args(argv=None):
+    ap = argparse.ArgumentParser(description='MOT metrics of VisDrone-MOT result files')
+    ap.add_argument('--gt', required=True, help='directory of annotation files <sequence>.txt')
+    ap.add_argument('--results', required=True, help='directory of result files <sequence>.txt')
+    ap.add_argument('--names', required=True, help='comma-separated class names; their number is nc')
+    ap.add_argument('--iou', type=float, default=0.5)
+    ap.add_argument('--host', action='store_true', help='the numpy path (no GPU)')
+    ap.add_argument('--batch', type=int, default=4, help='frames per launch on the device path')
+    ap.add_argument('--gt-capacity', type=int, default=1024)
+    ap.add_argument('--track-capacity', type=int, default=4096)
+    ap.add_argument('--rows', type=int, default=300, help='rows per frame the device path is sized for (nq = ng)')
+    return ap.parse_args(argv)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import numpy as np
+    import tamtr_amd  # noqa: F401
+    from tamtr_amd import engine
+    from tamtr_amd.track import read_mot
+    names = [n.strip() for n in args.names.split(',')]
+    nc = len(names)
+    seqs = sorted(f[:-4] for f in os.listdir(args.results) if f.endswith('.txt') and os.path.exists(os.path.join(args.gt, f)))
+    if not seqs:
+        raise FileNotFoundError(f'no <sequence>.txt of {args.results} has an annotation file in {args.gt}')
+    if not args.host:
+        import torch
+        from tamtr_amd.track import MotEvaluator, pack_track_rows
+        dev = torch.device('cuda', 0)
+        ev = MotEvaluator(dev, nc, iou=args.iou, gt_capacity=args.gt_capacity, track_capacity=args.track_capacity, nq=args.rows, ng=args.rows)
+    total, per_seq = engine.mot_new_counts(nc), {}
+    for name in seqs:
+        res = read_mot(os.path.join(args.results, name + '.txt'), gt=False)
+        gt = read_mot(os.path.join(args.gt, name + '.txt'), frames=len(res))
+        res += [np.zeros((0, 6), np.float32)] * (len(gt) - len(res))
+        if args.host:
+            counts = engine.mot_evaluate([list(zip(gt, res))], nc, iou=args.iou)
+        else:
+            for i in range(0, len(gt), args.batch):
+                ev.update(*pack_track_rows(res[i:i + args.batch], ev.nq, dev), gt[i:i + args.batch])
+            ev.end_sequence()
+            run = ev.counts()
+            counts = {k: run[k] - total[k] for k in run}
+        total = engine.mot_add_counts(total, counts)
+        per_seq[name] = engine.mot_summary(counts, names)
+        print(engine.mot_table(per_seq[name], name))
+    overall = engine.mot_summary(total, names)
+    print(engine.mot_table(overall, 'OVERALL'))
+    print(json.dumps({'sequences': len(seqs), 'path': 'host' if args.host else 'device', 'iou': args.iou, 'per_sequence': per_seq, 'overall': overall}))
+
+
+if __name__ == '__main__':
+    main()

@@ -12,7 +12,13 @@
       device-to-host copy of the batch's detections plus the numpy twin tests/bytetrack_np.py per frame (host clock).  The host side
       is numpy with scipy's assignment, NOT the reference's tracker with `lap`.
 
-    python tools/predict_bench.py [--images 64] [--kernel-only] [--track]
+  (d) --mot: the MOT evaluation on a seeded synthetic sequence (200 frames, about 100 ground-truth rows per frame, 300 ground-truth
+      ids, 600 track ids, nq = 300, batches of 4): the update launch per batch and the end-of-sequence launch (device events around
+      each launch, rows already on the device as the tracker leaves them; median and 10th / 90th percentile over repeated passes after
+      a warm-up pass), the update as MotEvaluator.update runs it (with the ground truth's upload), and the host path on the same rows:
+      the batch's device-to-host copy plus engine.mot_evaluate (numpy and scipy; host clock).
+
+    python tools/predict_bench.py [--images 64] [--kernel-only] [--track] [--mot]
 --kernel-only runs only the kernel loop of (a), for a `rocprofv3 --kernel-trace --stats` run of its own.
 """
 import argparse
@@ -185,11 +191,104 @@ def bench_track(n_obj, frames=240, B=4, nq=300, capacity=1024):
             'device_passes_timed': n_dev}
 
 
+def mot_scene(frames=200, n_obj=300, nc=10, seed=2):
+    """-> per frame (gt [m, 7], tracks [k, 6]): objects live about a third of the sequence (about 100 per frame), every one has two
+    track ids (it changes half way), 5 % misses, loose boxes, strays, three distractors and a region per frame."""
+    rng = np.random.default_rng(seed)
+    start = rng.integers(-frames // 6, frames - frames // 6, n_obj)
+    life = rng.integers(frames // 4, frames // 2, n_obj)
+    pos, vel = rng.uniform([0, 0], [1800, 1000], (n_obj, 2)), rng.uniform(-2, 2, (n_obj, 2))
+    size, cls = rng.uniform(30, 90, (n_obj, 2)), rng.integers(0, nc, n_obj)
+    out = []
+    for f in range(frames):
+        gt, trk = [], []
+        for o in np.flatnonzero((start <= f) & (f < start + life)):
+            p = pos[o] + vel[o] * f
+            box = np.array([p[0], p[1], p[0] + size[o, 0], p[1] + size[o, 1]])
+            gt.append([*box, o + 1, cls[o], 0])
+            if rng.random() > 0.05:
+                jit = rng.normal(0, 0.03, 4) * np.tile(size[o], 2) * (5 if rng.random() < 0.1 else 1)
+                trk.append([*(box + jit), 2 * o + 1 + (f - start[o] > life[o] // 2), cls[o]])
+        for k in range(3):
+            d = [1900 + 70 * k, 50 + f, 1950 + 70 * k, 110 + f]
+            gt.append([*d, 0, 0, 1])
+            trk.append([*(np.array(d) + rng.normal(0, 1, 4)), 700 + k, rng.integers(0, nc)])
+        gt.append([1900, 600, 2200, 900, 0, 0, 2])
+        trk.append([1950 + rng.uniform(0, 100), 650, 2100, 800, 710, 0])
+        for k in range(5):
+            p = rng.uniform([0, 1100], [1800, 1150], 2)
+            trk.append([p[0], p[1], p[0] + 40, p[1] + 40, 720 + (5 * f + k) % 200, rng.integers(0, nc)])
+        out.append((np.asarray(gt, np.float32).reshape(-1, 7), np.asarray(trk, np.float32).reshape(-1, 6)))
+    return out
+
+
+def bench_mot(frames=200, B=4, nq=300, nc=10, repeats=7):
+    from tamtr_amd import engine, ops
+    from tamtr_amd.track import MotEvaluator, pack_track_rows
+    scene = mot_scene(frames, nc=nc)
+    gts, trks = [g for g, _ in scene], [t for _, t in scene]
+    tracks_d, tc_d = pack_track_rows(trks, nq, 'cuda')
+    ev = MotEvaluator('cuda', nc, nq=nq, ng=300)
+    pct = lambda v: [round(float(np.percentile(v, q)), 4) for q in (50, 10, 90)]   # noqa: E731
+    event = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
+    upd, end, full = [], [], []
+    for rep in range(repeats + 1):
+        pairs, ends = [], []
+        for with_upload in (False, True):
+            ev.reset()
+            for i in range(0, frames, B):
+                if not with_upload:
+                    gt_d, gc_d = ev.upload(gts[i:i + B])
+                e0, e1 = event(), event()
+                e0.record()
+                if with_upload:
+                    ev.update(tracks_d[i:i + B], tc_d[i:i + B], gts[i:i + B])
+                else:
+                    ops.mot_update(tracks_d[i:i + B], tc_d[i:i + B], gt_d, gc_d, ev.state, nc, ev.gt_capacity, ev.track_capacity, ev.iou, ev.workspace)
+                e1.record()
+                pairs.append((with_upload, e0, e1))
+            e2, e3 = event(), event()
+            e2.record()
+            ev.end_sequence()
+            e3.record()
+            ends.append((e2, e3))
+        torch.cuda.synchronize()
+        if rep:      # the first pass is the warm-up
+            upd += [a.elapsed_time(b) for w, a, b in pairs if not w]
+            full += [a.elapsed_time(b) for w, a, b in pairs if w]
+            end += [a.elapsed_time(b) for a, b in ends]
+    dev_counts = ev.counts()      # the evaluator holds the last pass only: reset() came before it
+
+    def host_pass():
+        rows = []
+        for i in range(0, frames, B):
+            t, c = tracks_d[i:i + B].cpu().numpy(), tc_d[i:i + B].cpu().numpy()      # the copy a host evaluation needs, per batch
+            rows += [t[b, :c[b]][:, [0, 1, 2, 3, 4, 6]] for b in range(len(c))]
+        return engine.mot_evaluate([list(zip(gts, rows))], nc)
+
+    host_pass()
+    t_host = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        host_counts = host_pass()
+        t_host.append((time.perf_counter() - t0) * 1e3)
+    assert all(np.array_equal(dev_counts[k], host_counts[k]) for k in engine.MOT_COUNT_KEYS), 'the two paths counted different things'
+    s = engine.mot_summary(dev_counts)['all']
+    return {'frames': frames, 'frames_per_launch': B, 'nq': nq, 'nc': nc, 'gt_rows_per_frame': round(float(np.mean([len(g) for g in gts])), 1),
+            'track_rows_per_frame': round(float(np.mean([len(t) for t in trks])), 1), 'gt_ids': s['gt_ids'],
+            'track_ids': len({int(i) for t in trks for i in t[:, 4]}), 'MOTA': round(s['MOTA'], 4), 'IDF1': round(s['IDF1'], 4), 'IDSW': s['IDSW'],
+            'update_launch_ms_per_batch_p50_p10_p90': pct(upd), 'update_with_gt_upload_ms_per_batch_p50_p10_p90': pct(full),
+            'end_sequence_launch_ms_p50_p10_p90': pct(end),
+            'host_copy_plus_numpy_twin_ms_per_sequence_p50_min_max': [round(float(np.median(t_host)), 1), round(min(t_host), 1), round(max(t_host), 1)],
+            'host_ms_per_batch': round(float(np.median(t_host)) / (frames / B), 3), 'passes_timed': repeats}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--images', type=int, default=64)
     ap.add_argument('--kernel-only', action='store_true')
     ap.add_argument('--track', action='store_true', help='only (c): the tracker launch against copy + numpy twin')
+    ap.add_argument('--mot', action='store_true', help='only (d): the MOT evaluation launches against copy + numpy twin')
     args = ap.parse_args()
     import tamtr_amd  # noqa: F401
     assert torch.cuda.is_available(), 'predict_bench needs an MI355X'
@@ -198,6 +297,10 @@ def main():
         print('(c) tracker per frame: one launch per 4 frames (device events) vs device-to-host copy + numpy twin (host clock; numpy and scipy, not the reference with lap)')
         for n_obj in (24, 100):
             print(json.dumps(bench_track(n_obj)))
+        return
+    if args.mot:
+        print('(d) MOT evaluation: update launch per batch of 4 frames and end-of-sequence launch (device events) vs device-to-host copy + numpy twin (host clock)')
+        print(json.dumps(bench_mot()))
         return
     if args.kernel_only:
         print(json.dumps({'postprocess_kernel_only': bench_postprocess(True)}))

@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Track objects through image sequences (the reference's model.track flow with ByteTrack): per frame the boxes of the confirmed
 tracks with their ids; optional annotated copies, YOLO-format label files with the id appended, and one VisDrone-MOT result file per
-sequence, under an incremented --project/--name folder; one JSON line at the end.
+sequence, under an incremented --project/--name folder; one JSON line at the end.  With --gt the tracks are scored on the device
+as they are made (CLEAR-MOT and identity metrics, tam-tr_amd/csrc/mot.hip): a table per sequence and over all, and mot_metrics.json.
 
     python tools/track.py --weights runs/train/TAMTR/best.pt --text-feats clip_vitb32.npz --data dataset.yaml \
-        --source sequences/ [--tracker bytetrack.yaml] --conf 0.1 --batch 4 --save-mot [--save --save-txt --save-conf]
+        --source sequences/ [--tracker bytetrack.yaml] --conf 0.1 --batch 4 --save-mot [--save --save-txt --save-conf] [--gt annotations/]
 
 --source is a directory of frames (one sequence, frames in sorted order) or a directory of sequence directories (the VisDrone-MOT
 `sequences/<name>/` layout); the tracker is reset for every sequence.  --save-mot writes <save_dir>/<sequence>.txt with lines
 `frame,id,left,top,width,height,score,category,-1,-1`, frames 1-based.  Only `tracker_type: bytetrack` is built.
+--gt is a directory of VisDrone-MOT annotation files <sequence>.txt (track.read_mot states how categories become classes and kinds);
+a sequence without a file there is tracked but not scored.
 """
 import argparse
 import json
@@ -42,6 +45,8 @@ def parse_args(argv=None):
     ap.add_argument('--save-txt', action='store_true', help='write labels/<sequence>/<stem>.txt: cls x y w h [conf] id')
     ap.add_argument('--save-conf', action='store_true', help='put the score before the id on every label line')
     ap.add_argument('--save-mot', action='store_true', help='write <sequence>.txt in the VisDrone-MOT result format')
+    ap.add_argument('--gt', help='directory of VisDrone-MOT annotations <sequence>.txt: score the tracks (MOTA, MOTP, IDF1 ...)')
+    ap.add_argument('--mot-iou', type=float, default=0.5, help='IoU a track needs with a ground truth to match it, with --gt')
     ap.add_argument('--project', default='runs/track')
     ap.add_argument('--name', default='TAMTR')
     ap.add_argument('--exist-ok', action='store_true', help='reuse --project/--name instead of incrementing it')
@@ -72,7 +77,8 @@ def main(argv=None):
     from tamtr_amd import data as D
     from tamtr_amd.model import RTDETRDetectionWorldModel
     from tamtr_amd.predict import Predictor, increment_path, is_image_file
-    from tamtr_amd.track import ByteTracker, write_mot
+    from tamtr_amd import engine
+    from tamtr_amd.track import ByteTracker, MotEvaluator, read_mot, write_mot
     from predict import load_names
 
     dev = torch.device('cuda', 0)
@@ -84,7 +90,10 @@ def main(argv=None):
                      iou=args.iou, classes=args.classes, single_cls=args.single_cls, batch=args.batch, dtype=args.dtype)
     tracker = ByteTracker.from_yaml(args.tracker, dev, capacity=args.capacity) if args.tracker else ByteTracker(dev, capacity=args.capacity)
     save_dir = increment_path(os.path.join(args.project, args.name), exist_ok=args.exist_ok)
-    saving = args.save or args.save_txt or args.save_mot
+    saving = args.save or args.save_txt or args.save_mot or bool(args.gt)
+    evaluator = MotEvaluator(dev, len(names), iou=args.mot_iou) if args.gt else None
+    scored, per_seq = engine.mot_new_counts(len(names)), {}
+    class_names = list(names.values()) if isinstance(names, dict) else list(names)
     if saving:
         save_dir.mkdir(parents=True, exist_ok=True)
     n_img = n_rows = n_ids = 0
@@ -92,7 +101,9 @@ def main(argv=None):
     seqs = list_sequences(args.source, is_image_file)
     for name, folder in seqs:
         frames, ids = [], set()
-        for det in pred.track(folder, tracker=tracker):     # persist=False: the tracker is reset for the sequence
+        gt_file = os.path.join(args.gt, name + '.txt') if args.gt else None
+        gt = read_mot(gt_file) if gt_file and os.path.exists(gt_file) else None
+        for det in pred.track(folder, tracker=tracker, gt=gt, evaluator=evaluator if gt is not None else None):     # persist=False: a fresh tracker
             n_img += 1
             stem = os.path.splitext(os.path.basename(det.path))[0]
             if det.id is not None:
@@ -107,9 +118,23 @@ def main(argv=None):
         n_ids += len(ids)
         if args.save_mot:
             write_mot(save_dir / f'{name}.txt', frames)
+        if gt is not None:
+            run = evaluator.counts()
+            counts = {k: run[k] - scored[k] for k in run}
+            scored = engine.mot_add_counts(scored, counts)
+            per_seq[name] = engine.mot_summary(counts, class_names)
+            print(engine.mot_table(per_seq[name], name))
     wall = time.perf_counter() - t0
     sp = pred.speed()
-    print(json.dumps({'sequences': len(seqs), 'images': n_img, 'track_rows': n_rows, 'ids': n_ids, 'save_dir': str(save_dir) if saving else None,
+    extra = {}
+    if args.gt:
+        overall = engine.mot_summary(scored, class_names)
+        print(engine.mot_table(overall, 'OVERALL'))
+        with open(save_dir / 'mot_metrics.json', 'w') as fh:
+            json.dump({'iou': args.mot_iou, 'sequences': per_seq, 'overall': overall}, fh, indent=1)
+        extra = {'mot': {k: overall['all'][k] for k in ('MOTA', 'MOTP', 'IDF1', 'IDSW', 'FP', 'FN')}, 'mot_ms_per_image': round(sp.get('mot', 0.0), 4),
+                 'scored_sequences': len(per_seq)}
+    print(json.dumps({**extra, 'sequences': len(seqs), 'images': n_img, 'track_rows': n_rows, 'ids': n_ids, 'save_dir': str(save_dir) if saving else None,
                       'ms_per_image': {'load': round(sp['load'], 3), 'forward': round(sp['h2d'] + sp['forward'], 3),
                                        'postprocess': round(sp['postprocess'], 3), 'track': round(sp['track'], 4), 'd2h': round(sp['d2h'], 3)},
                       'wall_s': round(wall, 3), 'dtype': args.dtype, 'imgsz': args.imgsz, 'batch': args.batch}))
