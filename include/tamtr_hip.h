@@ -37,7 +37,7 @@ extern "C" {
 /* ABI version, bumped on any signature change.  The CLIP text tower's entries at the end of this file (tamtr_text_embed, tamtr_linear_f32,
  * tamtr_text_pool_project), tamtr_val_confusion, tamtr_val_ap_curves / tamtr_val_ap_tile and tamtr_bytetrack_update /
  * tamtr_bytetrack_workspace_bytes, tamtr_val_coco_match / tamtr_val_coco_workspace_bytes / tamtr_val_coco_accumulate and tamtr_mot_update /
- * tamtr_mot_end_sequence / tamtr_mot_workspace_bytes are new symbols
+ * tamtr_mot_end_sequence / tamtr_mot_workspace_bytes, and tamtr_hota_update / tamtr_hota_end_sequence / tamtr_hota_workspace_bytes are new symbols
  * only: no existing signature changed, so the version stayed at 36 when they were added. */
 int tamtr_abi_version(void);
 
@@ -774,6 +774,39 @@ int tamtr_mot_update(const float* tracks, const int32_t* tcounts, const float* g
 int tamtr_mot_end_sequence(int nc, int32_t* gstate, int32_t* counts, int32_t* pair, int32_t* hdr, int G_cap, int T_cap, int G_used,
                            void* workspace, int workspace_bytes, void* stream);
 int tamtr_mot_workspace_bytes(int nq, int ng, int nc, int G_cap, int T_cap); /* 0 = unsupported */
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * HOTA on the device, next to the MOT evaluation: the counts behind HOTA, DetA, AssA, DetRe / DetPr, AssRe / AssPr and LocA at the 19
+ * localisation thresholds, per class (TrackEval's HOTA.eval_sequence).  The rule is written out in csrc/hota.hip and stated by
+ * engine.hota_evaluate.
+ *
+ * state: a HOST array of 12 device pointers, all zero when fresh, updated in place; caps: a HOST array of the 5 capacities G (gt
+ * identities), T (track ids), P (pair slots), L (log entries), F (frames of a sequence).  In order:
+ *      gstate i32 [G, 2]  frames present, class + 1          tcount i32 [nc, T]  frames a track identity is present in
+ *      pkey i64 [P]  ((gt row << 32) | track id) + 1, 0 free ppot f64 [P]  the pair's pot      phist i32 [P, 20]  its matches by level
+ *      fidx i32 [F, 4]  first log entry, entries, n, m       log i32 [L, 4]  per positive pair: S (f64), slot (i32), row, column (u16)
+ *      dets i32 [nc, 2]  gt_dets, trk_dets                   tp_lvl i32 [nc, 20]      loc_lvl f64 [nc, 20]      ass f64 [3, nc, 19]
+ *      hdr i32 [16]  frames logged, log entries used, then what was left out: gt ids beyond G, track ids beyond T, rows beyond ng / nq,
+ *                    pairs beyond L, frames beyond F, pairs without a slot, 0 ...
+ *  A pair matched at level k (the number of thresholds its IoU passed) is a TP at every threshold a < k: TP[c, a] is the sum of
+ *  tp_lvl[c, k] over k > a, loc_sum likewise.  dets, tp_lvl, loc_lvl and ass are run totals; the rest belongs to the open sequence.
+ *
+ * tamtr_hota_update: steps 1 and 2 of the MOT rule, then pass 1 (presence counts, pot) and the log, for the B frames of a batch, in
+ *  order, one launch, one workgroup.  tracks / tcounts / gt / gcounts as tamtr_mot_update takes them; eps = DBL_EPSILON.
+ *  Whatever exceeds a capacity is counted in hdr and left out; nothing is written past a table.
+ * tamtr_hota_end_sequence: pass 2 and the reduction in three launches: `workgroups` workgroups stride over the logged frames and match
+ *  each (scores gas * S), bumping the level bins; one thread per pair slot adds the pair's terms to ass and clears the slot; the
+ *  sequence's gstate, tcount and counters are cleared.  alpha: HOST pointer to the 19 thresholds, np.arange(0.05, 0.99, 0.05) as made.
+ * workspace: tamtr_hota_workspace_bytes(nq, ng, workgroups) bytes of device memory for either call (update: workgroups is irrelevant),
+ *  16-byte aligned, contents irrelevant (0 = unsupported).  Nothing is allocated, set or synchronised.
+ * TAMTR_EINVAL: a NULL or misaligned operand, a size or capacity < 1, iou_thr or eps <= 0, a workspace that is too small.
+ *  TAMTR_EUNSUP: ng and nq whose solver state exceeds 60 KiB of LDS or 65535, workgroups > 1024, nc * T or 20 P > 2^31 - 1, an id range
+ *  fp32 cannot carry. */
+int tamtr_hota_update(const float* tracks, const int32_t* tcounts, const float* gt, const int32_t* gcounts, int B, int nq, int ng, int nc,
+                      double iou_thr, double eps, void* const* state, const int* caps, void* workspace, int workspace_bytes, void* stream);
+int tamtr_hota_end_sequence(const double* alpha, double eps, int nc, int nq, int ng, int workgroups, void* const* state, const int* caps,
+                            void* workspace, int workspace_bytes, void* stream);
+int tamtr_hota_workspace_bytes(int nq, int ng, int workgroups); /* 0 = unsupported */
 
 #ifdef __cplusplus
 }

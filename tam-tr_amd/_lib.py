@@ -115,6 +115,9 @@ _SIGS = {
     'tamtr_mot_update': [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P],
     'tamtr_mot_end_sequence': [_I, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P],
     'tamtr_mot_workspace_bytes': [_I, _I, _I, _I, _I],
+    'tamtr_hota_update': [_P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P, _P, _I, _P],
+    'tamtr_hota_end_sequence': [_P, _D, _I, _I, _I, _I, _P, _P, _P, _I, _P],
+    'tamtr_hota_workspace_bytes': [_I, _I, _I],
 }
 EXPORTS = tuple(_SIGS)
 _lib = None

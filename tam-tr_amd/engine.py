@@ -655,6 +655,40 @@ def mot_new_counts(nc):
     return c
 
 
+def _mot_preprocess(gt, trk, nc, thr, out=None):
+    """Steps 1 (regions) and 2 (distractors) of the MOT rule on one frame, shared by mot_evaluate and hota_evaluate.
+    -> (kind-0 rows [n, 7], their classes, surviving track rows [k, 6], their classes); the dropped rows are counted into out."""
+    f32 = lambda x, w: np.asarray(x, np.float32).reshape(-1, w)   # noqa: E731
+    gt, trk = f32(gt, 7), f32(trk, 6)
+    kind = gt[:, 6]
+    in_range = lambda c: (c >= 0) & (c < nc)   # noqa: E731
+    trk = trk[in_range(trk[:, 5])]
+    tcls = trk[:, 5].astype(np.int64)
+    # 1. regions
+    reg = gt[kind == 2]
+    if len(reg) and len(trk):
+        _, inter = mot_iou_matrix(trk[:, :4], reg[:, :4])
+        area = (trk[:, 2].astype(np.float64) - trk[:, 0]) * (trk[:, 3].astype(np.float64) - trk[:, 1])
+        ioa = np.where(area[:, None] > 0, inter / np.where(area > 0, area, 1.0)[:, None], 0.0)
+        drop = (ioa > 0.5).any(1)
+        if out is not None:
+            np.add.at(out['drop_region'], tcls[drop], 1)
+        trk, tcls = trk[~drop], tcls[~drop]
+    # 2. distractors
+    g = gt[((kind == 0) & in_range(gt[:, 5])) | (kind == 1)]
+    if (g[:, 6] == 1).any() and len(trk):
+        m, _ = mot_iou_matrix(g[:, :4], trk[:, :4])
+        agree = (g[:, 6] == 1)[:, None] | (g[:, 5].astype(np.int64)[:, None] == tcls[None, :])
+        drop = np.zeros(len(trk), bool)
+        for i, j in _mot_assign(np.where((m >= thr) & agree, m, 0.0)):
+            drop[j] |= g[i, 6] == 1
+        if out is not None:
+            np.add.at(out['drop_distractor'], tcls[drop], 1)
+        trk, tcls = trk[~drop], tcls[~drop]
+    g = g[g[:, 6] == 0]
+    return g, g[:, 5].astype(np.int64), trk, tcls
+
+
 def mot_evaluate(sequences, nc, iou=0.5):
     """CLEAR-MOT and identity counts of tracker output against ground truth (TrackEval's CLEAR and Identity definitions, restated; the
     rule is written out in csrc/mot.hip, whose checker this is, and this is the path for a machine without a GPU).
@@ -664,36 +698,10 @@ def mot_evaluate(sequences, nc, iou=0.5):
     several sequences add, and mot_summary turns them into MOTA / MOTP / IDF1 ..."""
     nc, thr = int(nc), float(iou)
     out = mot_new_counts(nc)
-    f32 = lambda x, w: np.asarray(x, np.float32).reshape(-1, w)   # noqa: E731
     for frames in sequences:
         last, present, matched, runs, last_frame, pair = {}, {}, {}, {}, {}, {}
         for fid, (gt, trk) in enumerate(frames, 1):
-            gt, trk = f32(gt, 7), f32(trk, 6)
-            kind = gt[:, 6]
-            in_range = lambda c: (c >= 0) & (c < nc)   # noqa: E731
-            trk = trk[in_range(trk[:, 5])]
-            tcls = trk[:, 5].astype(np.int64)
-            # 1. regions
-            reg = gt[kind == 2]
-            if len(reg) and len(trk):
-                _, inter = mot_iou_matrix(trk[:, :4], reg[:, :4])
-                area = (trk[:, 2].astype(np.float64) - trk[:, 0]) * (trk[:, 3].astype(np.float64) - trk[:, 1])
-                ioa = np.where(area[:, None] > 0, inter / np.where(area > 0, area, 1.0)[:, None], 0.0)
-                drop = (ioa > 0.5).any(1)
-                np.add.at(out['drop_region'], tcls[drop], 1)
-                trk, tcls = trk[~drop], tcls[~drop]
-            # 2. distractors
-            g = gt[((kind == 0) & in_range(gt[:, 5])) | (kind == 1)]
-            if (g[:, 6] == 1).any() and len(trk):
-                m, _ = mot_iou_matrix(g[:, :4], trk[:, :4])
-                agree = (g[:, 6] == 1)[:, None] | (g[:, 5].astype(np.int64)[:, None] == tcls[None, :])
-                drop = np.zeros(len(trk), bool)
-                for i, j in _mot_assign(np.where((m >= thr) & agree, m, 0.0)):
-                    drop[j] |= g[i, 6] == 1
-                np.add.at(out['drop_distractor'], tcls[drop], 1)
-                trk, tcls = trk[~drop], tcls[~drop]
-            g = g[g[:, 6] == 0]
-            gcls = g[:, 5].astype(np.int64)
+            g, gcls, trk, tcls = _mot_preprocess(gt, trk, nc, thr, out)
             # 3. CLEAR matching and 4. pair counts, per class
             for c in range(nc):
                 gc, tc = g[gcls == c], trk[tcls == c]
@@ -769,6 +777,118 @@ def mot_table(summary, title=''):
 def mot_add_counts(a, b):
     """Counts of several sequences (or runs) add."""
     return {k: a[k] + b[k] for k in a}
+
+
+# ------------------------------------------------------------------------------------------------ HOTA
+# the 19 localisation thresholds and the slack of every threshold comparison, as TrackEval makes them (never k / 20: several differ in the last bit)
+HOTA_ALPHA = np.arange(0.05, 0.99, 0.05)
+HOTA_EPS = float(np.finfo(float).eps)
+HOTA_INT_KEYS, HOTA_SUM_KEYS = ('TP', 'FN', 'FP'), ('loc_sum', 'ass_sum', 'assre_sum', 'asspr_sum')
+HOTA_RATIOS = ('HOTA', 'DetA', 'AssA', 'DetRe', 'DetPr', 'AssRe', 'AssPr', 'LocA')
+
+
+def hota_new_counts(nc):
+    na = len(HOTA_ALPHA)
+    c = {k: np.zeros((int(nc), na), np.int64) for k in HOTA_INT_KEYS}
+    c.update({k: np.zeros((int(nc), na), np.float64) for k in HOTA_SUM_KEYS})
+    c.update({k: np.zeros(int(nc), np.int64) for k in ('gt_dets', 'trk_dets')})
+    return c
+
+
+def hota_add_counts(a, b):
+    """Counts of several sequences (or runs) add: TrackEval's combine_sequences weights the per-sequence ratios by TP, which is this."""
+    return {k: a[k] + b[k] for k in a}
+
+
+def hota_evaluate(sequences, nc, iou=0.5):
+    """HOTA counts of tracker output against ground truth (TrackEval's HOTA.eval_sequence, restated; the rule is written out in
+    csrc/hota.hip, whose checker this is, and this is the path for a machine without a GPU).  Arguments as mot_evaluate; `iou` is the
+    threshold of the region / distractor preprocessing, which is mot_evaluate's.  -> {'TP' 'FN' 'FP': i64 [nc, 19], 'loc_sum' 'ass_sum'
+    'assre_sum' 'asspr_sum': f64 [nc, 19], 'gt_dets' 'trk_dets': i64 [nc]}; counts of several sequences add (hota_add_counts) and
+    hota_summary turns them into HOTA / DetA / AssA ..."""
+    nc, thr = int(nc), float(iou)
+    out = hota_new_counts(nc)
+    for frames in sequences:
+        pot, gcount, tcount, kept = {}, {}, {}, []
+        # pass 1: the global alignment score needs the whole sequence
+        for gt, trk in frames:
+            g, gcls, trk, tcls = _mot_preprocess(gt, trk, nc, thr)
+            for c in range(nc):
+                gc, tc = g[gcls == c], trk[tcls == c]
+                gid, tid = [(c, int(i)) for i in gc[:, 4]], [(c, int(i)) for i in tc[:, 4]]
+                out['gt_dets'][c] += len(gc)
+                out['trk_dets'][c] += len(tc)
+                for k in gid:
+                    gcount[k] = gcount.get(k, 0) + 1
+                for k in tid:
+                    tcount[k] = tcount.get(k, 0) + 1
+                if not len(gc) or not len(tc):
+                    continue
+                S, _ = mot_iou_matrix(gc[:, :4], tc[:, :4])
+                den = (S.sum(1)[:, None] + S.sum(0)[None, :]) - S
+                ok = den > HOTA_EPS
+                sim = np.where(ok, S / np.where(ok, den, 1.0), 0.0)
+                for i, j in zip(*np.nonzero(S)):
+                    pot[(gid[i], tid[j])] = pot.get((gid[i], tid[j]), 0.0) + sim[i, j]
+                kept.append((c, gid, tid, S))
+        # pass 2: one assignment per frame and class, weighted by the alignment score
+        mc = {}
+        for c, gid, tid, S in kept:
+            gas = np.zeros_like(S)
+            for i, j in zip(*np.nonzero(S)):
+                p = pot[(gid[i], tid[j])]
+                gas[i, j] = p / ((gcount[gid[i]] + tcount[tid[j]]) - p)
+            for i, j in _hota_assign(gas * S, S):
+                hit = S[i, j] >= HOTA_ALPHA - HOTA_EPS
+                out['TP'][c] += hit
+                out['loc_sum'][c] += np.where(hit, S[i, j], 0.0)
+                k = (gid[i], tid[j])
+                mc[k] = mc.get(k, 0) + hit.astype(np.int64)
+        for (gk, tk), m in mc.items():
+            sq = (m * m).astype(np.float64)
+            out['ass_sum'][gk[0]] += sq / np.maximum(1, gcount[gk] + tcount[tk] - m)
+            out['assre_sum'][gk[0]] += sq / max(1, gcount[gk])
+            out['asspr_sum'][gk[0]] += sq / max(1, tcount[tk])
+    out['FN'], out['FP'] = out['gt_dets'][:, None] - out['TP'], out['trk_dets'][:, None] - out['TP']
+    return out
+
+
+def _hota_assign(score, S):
+    """The matched pairs of pass 2; hota_evaluate's one call of the solver, so that a test can put another rule in its place."""
+    return _mot_assign(score)
+
+
+def hota_summary(counts, names=None):
+    """Per-class rows and an 'all' row of summed counts (TrackEval's combine_classes_det_averaged) from hota_evaluate's (or
+    HotaEvaluator's) counts.  A row holds, for each of HOTA DetA AssA DetRe DetPr AssRe AssPr LocA, the mean over the 19 thresholds under
+    its name and the 19 values under `<name>_alpha`; 'HOTA(0)', 'LocA(0)' and 'HOTALocA(0)' (the first threshold, and their product);
+    TP / FN / FP per threshold; gt_dets and trk_dets.  A zero denominator gives 0 (LocA: 1), as TrackEval's max(1, .) does."""
+    def row(c, label):
+        tp, fn, fp = (np.asarray(c[k], np.float64) for k in HOTA_INT_KEYS)
+        v = {'DetA': tp / np.maximum(1.0, tp + fn + fp), 'DetRe': tp / np.maximum(1.0, tp + fn), 'DetPr': tp / np.maximum(1.0, tp + fp),
+             'AssA': c['ass_sum'] / np.maximum(1.0, tp), 'AssRe': c['assre_sum'] / np.maximum(1.0, tp),
+             'AssPr': c['asspr_sum'] / np.maximum(1.0, tp), 'LocA': np.maximum(1e-10, c['loc_sum']) / np.maximum(1e-10, tp)}
+        v['HOTA'] = np.sqrt(v['DetA'] * v['AssA'])
+        r = {'class': label, 'gt_dets': int(c['gt_dets']), 'trk_dets': int(c['trk_dets']), **{k: [int(x) for x in c[k]] for k in HOTA_INT_KEYS}}
+        for k in HOTA_RATIOS:
+            r[k], r[k + '_alpha'] = float(np.mean(v[k])), [float(x) for x in v[k]]
+        r['HOTA(0)'], r['LocA(0)'] = float(v['HOTA'][0]), float(v['LocA'][0])
+        r['HOTALocA(0)'] = r['HOTA(0)'] * r['LocA(0)']
+        return r
+
+    nc = len(np.atleast_1d(counts['gt_dets']))
+    per = [row({k: np.asarray(v)[c] for k, v in counts.items()}, names[c] if names is not None else c) for c in range(nc)]
+    return {'all': row({k: np.asarray(v).sum(0) for k, v in counts.items()}, 'all'), 'per_class': per}
+
+
+def hota_table(summary, title=''):
+    """hota_summary's rows as TrackEval prints them (percentages)."""
+    cols = HOTA_RATIOS + ('HOTA(0)', 'LocA(0)', 'HOTALocA(0)')
+    lines = [f'{title or "class":>16s}' + ''.join(f'{c:>12s}' if '(' in c else f'{c:>8s}' for c in cols) + f'{"gt_dets":>9s}{"trk_dets":>9s}']
+    for r in summary['per_class'] + [summary['all']]:
+        lines.append(f'{str(r["class"]):>16s}' + ''.join(f'{100 * r[c]:12.2f}' if '(' in c else f'{100 * r[c]:8.2f}' for c in cols) +
+                     f'{r["gt_dets"]:9d}{r["trk_dets"]:9d}')
+    return '\n'.join(lines)
 
 
 def cm_conf(conf):

@@ -1996,6 +1996,81 @@ def mot_end_sequence(state, nc, gt_capacity, track_capacity, gt_used, workspace=
          min(int(gt_used), G), ptr(workspace), int(workspace.numel()), stream_ptr())
 
 
+# the HOTA evaluator's state (csrc/hota.hip states it): name, dtype, shape from (nc, caps); caps = (gt identities, track ids, pair
+# slots, log entries, frames of a sequence); all zero when fresh.  The order is the kernel's.
+HOTA_STATE_SPEC = (('gstate', torch.int32, lambda nc, c: (c[0], 2)), ('tcount', torch.int32, lambda nc, c: (nc, c[1])),
+                   ('pkey', torch.int64, lambda nc, c: (c[2],)), ('ppot', torch.float64, lambda nc, c: (c[2],)),
+                   ('phist', torch.int32, lambda nc, c: (c[2], 20)), ('fidx', torch.int32, lambda nc, c: (c[4], 4)),
+                   ('log', torch.int32, lambda nc, c: (c[3], 4)), ('dets', torch.int32, lambda nc, c: (nc, 2)),
+                   ('tp_lvl', torch.int32, lambda nc, c: (nc, 20)), ('loc_lvl', torch.float64, lambda nc, c: (nc, 20)),
+                   ('ass', torch.float64, lambda nc, c: (3, nc, 19)), ('hdr', torch.int32, lambda nc, c: (16,)))
+HOTA_END_WORKGROUPS = 64     # workgroups of the matching launch: each strides over the logged frames and owns a slice of the workspace
+HOTA_EPS = 2.0 ** -52        # np.finfo(float).eps
+
+
+def hota_workspace_bytes(nq, ng, workgroups=HOTA_END_WORKGROUPS):
+    """Bytes of device workspace tamtr_hota_update and tamtr_hota_end_sequence need (no GPU call)."""
+    n = _lib.lib().tamtr_hota_workspace_bytes(int(nq), int(ng), int(workgroups))
+    if n <= 0:
+        raise _lib.TamtrHipError(f'hota: nq {nq}, ng {ng} with {workgroups} workgroups is outside what the kernel is built for')
+    return n
+
+
+def _hota_state(what, state, nc, caps):
+    """Check the state against HOTA_STATE_SPEC -> (host array of its 12 device pointers, host array of the 5 capacities)."""
+    caps = tuple(int(c) for c in caps)
+    if int(nc) < 1 or len(caps) != 5 or min(caps) < 1:
+        raise _lib.TamtrHipError(f'{what}: nc and the 5 capacities (gt, tracks, pairs, log, frames) must be positive, got {nc} and {caps}')
+    for k, dt, shape in HOTA_STATE_SPEC:
+        t = state.get(k) if isinstance(state, dict) else None
+        want = shape(int(nc), caps)
+        if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
+            got = None if t is None else (t.dtype, tuple(t.shape))
+            raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want}, got {got}')
+    require_gpu(*(state[k] for k, _, _ in HOTA_STATE_SPEC))
+    return (ctypes.c_void_p * len(HOTA_STATE_SPEC))(*(state[k].data_ptr() for k, _, _ in HOTA_STATE_SPEC)), (ctypes.c_int * 5)(*caps)
+
+
+def hota_update(tracks, tcounts, gt, gcounts, state, nc, caps, iou=0.5, workspace=None):
+    """Steps 1 and 2 of the MOT rule and pass 1 of HOTA (csrc/hota.hip; engine.hota_evaluate is its numpy statement) for the B frames of a
+    batch, in order, in one launch.  tracks / tcounts / gt / gcounts as mot_update takes them.  state: a dict of device tensors as
+    HOTA_STATE_SPEC lists them, updated in place; caps: (gt identities, track ids, pair slots, log entries, frames).  Every check
+    comes before the launch; no synchronisation."""
+    if tracks.dim() != 3 or tracks.shape[-1] != 8 or tracks.shape[0] < 1 or tracks.shape[1] < 1:
+        raise _lib.TamtrHipError(f'hota_update: expected tracks [B, nq, 8], got {tuple(tracks.shape)}')
+    B, nq, _ = tracks.shape
+    if gt.dim() != 3 or gt.shape[0] != B or gt.shape[1] < 1 or gt.shape[2] != 7:
+        raise _lib.TamtrHipError(f'hota_update: expected gt [B, ng, 7] with B = {B}, got {tuple(gt.shape)}')
+    ng = gt.shape[1]
+    if tuple(tcounts.shape) != (B,) or tuple(gcounts.shape) != (B,):
+        raise _lib.TamtrHipError(f'hota_update: tcounts and gcounts must be [B] = [{B}], got {tuple(tcounts.shape)} and {tuple(gcounts.shape)}')
+    if tracks.dtype != torch.float32 or gt.dtype != torch.float32 or tcounts.dtype != torch.int32 or gcounts.dtype != torch.int32:
+        raise _lib.TamtrHipError('hota_update: tracks and gt must be float32, tcounts and gcounts int32')
+    if not float(iou) > 0:
+        raise _lib.TamtrHipError(f'hota_update: iou must be positive, got {iou}')
+    ptrs, ccaps = _hota_state('hota_update', state, nc, caps)
+    require_gpu(tracks, tcounts, gt, gcounts)
+    workspace = _mot_workspace('hota_update', workspace, hota_workspace_bytes(nq, ng, 1), tracks.device)
+    tracks, tcounts, gt, gcounts = _c(tracks), _c(tcounts), _c(gt), _c(gcounts)
+    call('tamtr_hota_update', ptr(tracks), ptr(tcounts), ptr(gt), ptr(gcounts), B, nq, ng, int(nc), float(iou), HOTA_EPS, ptrs, ccaps,
+         ptr(workspace), int(workspace.numel()), stream_ptr())
+
+
+def hota_end_sequence(state, nc, caps, nq, ng, workspace=None, workgroups=HOTA_END_WORKGROUPS):
+    """Pass 2 of HOTA and the per-sequence reduction in three launches (matching over `workgroups` workgroups, the reduction over the
+    pair table, the clearing of the sequence's state); adds to the run totals of `state`.  nq / ng: the widest rows any update of the
+    sequence was given.  No synchronisation."""
+    nq, ng, workgroups = int(nq), int(ng), int(workgroups)
+    if nq < 1 or ng < 1 or workgroups < 1:
+        raise _lib.TamtrHipError(f'hota_end_sequence: nq, ng and workgroups must be positive, got {nq}, {ng}, {workgroups}')
+    ptrs, ccaps = _hota_state('hota_end_sequence', state, nc, caps)
+    workspace = _mot_workspace('hota_end_sequence', workspace, hota_workspace_bytes(nq, ng, workgroups), state['hdr'].device)
+    import numpy as np
+    alpha = (ctypes.c_double * 19)(*np.arange(0.05, 0.99, 0.05))   # the thresholds as TrackEval makes them, never k / 20
+    call('tamtr_hota_end_sequence', alpha, HOTA_EPS, int(nc), nq, ng, workgroups, ptrs, ccaps, ptr(workspace), int(workspace.numel()),
+         stream_ptr())
+
+
 @torch.no_grad()
 def val_postprocess_match(y, cls, bboxes, batch_idx, ori_hw, imgsz, conf, iou, single_cls=False, max_wh=7680., return_device_labels=False):
     """engine.Validator.update's per-image work (RTDETRValidator.postprocess, models/rtdetrworld/val.py:102-173, and match_predictions,

@@ -189,8 +189,8 @@ class Predictor:
         """Network inputs u8 [B, S, S, 3] (host) + original (h, w) per image -> host (out [B, nq, 6], keep [B, nq], counts [B]).
         With a tracker (track.ByteTracker) the batch's frames also go through one tracker launch, and its rows ride in the same copy:
         -> host (out, keep, counts, tracks [B, nq, 8], tcounts [B]).  With gt_frames (B host arrays [m, 7]) and an evaluator
-        (track.MotEvaluator) as well, one more launch scores the tracker's rows where they lie; the evaluator's header rides in the
-        same copy and the time goes under times['mot']."""
+        (track.MotEvaluator or track.HotaEvaluator, or a list of them) as well, one more launch per evaluator scores the tracker's rows
+        where they lie; each evaluator's header rides in the same copy and its time goes under its own key of times ('mot', 'hota')."""
         arr, hw = ims
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
         ev[0].record()
@@ -205,25 +205,26 @@ class Predictor:
         # one device-to-host copy for all the outputs
         B, nq = keep.shape
         parts = [out.view(-1), keep.view(torch.float32).view(-1), counts.view(torch.float32)]
-        scoring = tracker is not None and evaluator is not None and gt_frames is not None
-        ev_mot = None
+        evaluators = list(evaluator) if isinstance(evaluator, (list, tuple)) else [] if evaluator is None else [evaluator]
+        scoring = tracker is not None and bool(evaluators) and gt_frames is not None
+        ev_eval = []
         if tracker is not None:
             tracks, tcounts = tracker.update(out, counts)
             parts += [tracks.view(-1), tcounts.view(torch.float32), tracker.state['hdr'].view(torch.float32)]
-            if scoring:
-                ev_mot = torch.cuda.Event(enable_timing=True)
-                ev_mot.record()
-                evaluator.update(tracks, tcounts, gt_frames)
-                parts.append(evaluator.state['hdr'].view(torch.float32))
+            for e in evaluators if scoring else []:
+                ev_eval.append(torch.cuda.Event(enable_timing=True))
+                ev_eval[-1].record()
+                e.update(tracks, tcounts, gt_frames)
+                parts.append(e.state['hdr'].view(torch.float32))
         ev[4].record()
         packed = torch.cat(parts)
         host = torch.empty(packed.shape, dtype=torch.float32, pin_memory=True)
         host.copy_(packed, non_blocking=True)
         ev[5].record()
         ev[5].synchronize()
-        spans = [('h2d', ev[0], ev[1]), ('forward', ev[1], ev[2]), ('postprocess', ev[2], ev[3]), ('track', ev[3], ev_mot or ev[4]), ('d2h', ev[4], ev[5])]
-        if scoring:
-            spans.append(('mot', ev_mot, ev[4]))
+        spans = [('h2d', ev[0], ev[1]), ('forward', ev[1], ev[2]), ('postprocess', ev[2], ev[3]), ('track', ev[3], (ev_eval + [ev[4]])[0]), ('d2h', ev[4], ev[5])]
+        for i, e in enumerate(evaluators if scoring else []):
+            spans.append((e.times_key, ev_eval[i], (ev_eval + [ev[4]])[i + 1]))
         for k, a, b in spans:
             self.times[k] = self.times.get(k, 0.0) + a.elapsed_time(b)
         if self.keep_raw:
@@ -232,10 +233,10 @@ class Predictor:
         res = o.view(B, nq, 6), kp.view(torch.int32).view(B, nq), c.view(torch.int32)
         if tracker is None:
             return res
-        tr, tc, hdr, mhdr = rest.split([B * nq * 8, B, 8, 8 if scoring else 0])
+        tr, tc, hdr, *ehdr = rest.split([B * nq * 8, B, 8] + [e.state['hdr'].numel() for e in evaluators if scoring])
         tracker.check_overflow(hdr.view(torch.int32)[3])
-        if scoring:
-            evaluator.check_overflow(mhdr.view(torch.int32))
+        for e, h in zip(evaluators, ehdr):
+            e.check_overflow(h.view(torch.int32))
         return res + (tr.view(B, nq, 8), tc.view(torch.int32))
 
     def predict(self, source):
@@ -249,9 +250,10 @@ class Predictor:
         (trackers/track.py:46-50).  tracker: a track.ByteTracker, a bytetrack.yaml path, or None for the defaults; persist=True keeps
         the tracker (and its tracks) of the previous call.
         gt + evaluator: the sequence's ground truth, one array [m, 7] (x1 y1 x2 y2 id cls kind, track.read_mot) per frame in file order
-        (missing frames are empty), and a track.MotEvaluator: every batch's rows are scored on the device right after the tracker's
-        launch (a frame without track rows is an empty track set, as write_mot has it), the sequence is ended after the last frame,
-        and speed() has a 'mot' entry; evaluator.results() then holds the metrics.  Without both, nothing changes."""
+        (missing frames are empty), and a track.MotEvaluator or track.HotaEvaluator, or a list / tuple of them: every batch's rows are
+        scored on the device right after the tracker's launch, by each evaluator in turn (a frame without track rows is an empty
+        track set, as write_mot has it), the sequence is ended after the last frame, and speed() has an entry per evaluator ('mot',
+        'hota'); each evaluator's results() then holds the metrics.  Without both, nothing changes."""
         from .track import ByteTracker
         if isinstance(tracker, ByteTracker):
             self.tracker = tracker
@@ -260,14 +262,17 @@ class Predictor:
         elif self.tracker is None or not persist:
             self.tracker = ByteTracker.from_yaml(tracker, self.device) if tracker else ByteTracker(self.device)
         files = list_sources(source)
-        if gt is None or evaluator is None:
-            self.times.pop('mot', None)      # the key exists only while a run is scored
+        evaluators = list(evaluator) if isinstance(evaluator, (list, tuple)) else [] if evaluator is None else [evaluator]
+        for k in {'mot', 'hota'} - ({e.times_key for e in evaluators} if gt is not None else set()):
+            self.times.pop(k, None)          # an evaluator's key exists only while a run is scored by it
+        if gt is None or not evaluators:
             yield from self._run(files, self.tracker)
             return
         gt = list(gt)[:len(files)]
         gt += [np.zeros((0, 7), np.float32)] * (len(files) - len(gt))
-        yield from self._run(files, self.tracker, gt, evaluator)
-        evaluator.end_sequence()
+        yield from self._run(files, self.tracker, gt, evaluators)
+        for e in evaluators:
+            e.end_sequence()
 
     def _run(self, files, tracker, gt=None, evaluator=None):
         with ThreadPoolExecutor(max_workers=self.workers) as pool:

@@ -14,6 +14,9 @@ numpy): one more launch per batch on the rows the tracker left on the device, on
     ev.update(tracks, tcounts, gt_frames)               # gt_frames: B host arrays [m, 7] (read_mot); no synchronisation
     ev.end_sequence()
     ev.results(names)                                   # synchronises: {'all': row, 'per_class': [...]}, MOTA / MOTP / IDF1 ...
+
+HotaEvaluator has the same methods and scores the same rows by HOTA (the rule is written out in csrc/hota.hip, engine.hota_evaluate
+states it in numpy): one launch per batch, three per sequence.  `Predictor.track(..., evaluator=[mot, hota])` feeds both.
 """
 import numpy as np
 import torch
@@ -32,6 +35,10 @@ class TrackerOverflow(RuntimeError):
 
 
 class MotOverflow(RuntimeError):
+    pass
+
+
+class HotaOverflow(RuntimeError):
     pass
 
 
@@ -131,6 +138,7 @@ class MotEvaluator:
     state).  gt_capacity: ground-truth identities (class, id) per sequence; track_capacity: track ids are used as they are and must
     be below it; nq / ng: track / ground-truth rows per frame the workspace is sized for (a batch with wider track rows gets a larger
     workspace on its first use; ground-truth rows beyond ng are counted as overflow)."""
+    times_key = 'mot'      # the key of Predictor.times this evaluator's launches go under
 
     def __init__(self, device, nc, iou=0.5, gt_capacity=1024, track_capacity=4096, nq=300, ng=300):
         self.device = torch.device(device)
@@ -211,6 +219,84 @@ class MotEvaluator:
         """engine.mot_summary of the sequences ended so far (synchronises; raises MotOverflow)."""
         from .engine import mot_summary
         return mot_summary(self.counts(), names)
+
+
+# ------------------------------------------------------------------------------------------------ HOTA
+HOTA_HDR_OVER = ('gt identities beyond gt_capacity', 'track ids beyond track_capacity', 'rows beyond ng / nq per frame',
+                 'pairs beyond log_capacity', 'frames beyond frame_capacity', 'pairs that found no slot in pair_capacity')   # hdr[2:8]
+
+
+class HotaEvaluator:
+    """HOTA counts of tracker rows against ground truth, kept on `device` (csrc/hota.hip states the rule and the state).  The methods
+    are MotEvaluator's.  gt_capacity / track_capacity / nq / ng as there; pair_capacity: slots of the sparse pair table (distinct
+    (ground truth, track) pairs with a positive IoU in a sequence; the table fills badly beyond about half); log_capacity: positive
+    pairs logged over the frames of a sequence; frame_capacity: frames of a sequence.  The defaults hold a 2 000-frame sequence of
+    100 rows a side several times over and take 85 MiB with the workspace."""
+    times_key = 'hota'
+
+    def __init__(self, device, nc, iou=0.5, gt_capacity=1024, track_capacity=4096, pair_capacity=1 << 18, log_capacity=1 << 20,
+                 frame_capacity=4096, nq=300, ng=300):
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise ops._lib.TamtrHipError('HotaEvaluator needs an MI355X; engine.hota_evaluate is the host path')
+        self.nc, self.iou, self.nq, self.ng = int(nc), float(iou), int(nq), int(ng)
+        self.caps = (int(gt_capacity), int(track_capacity), int(pair_capacity), int(log_capacity), int(frame_capacity))
+        self.gt_capacity = self.caps[0]
+        if min(self.nc, self.nq, self.ng, *self.caps) < 1:
+            raise ValueError('nc, the capacities, nq and ng must be positive')
+        self.workspace = torch.empty(ops.hota_workspace_bytes(self.nq, self.ng), device=self.device, dtype=torch.uint8)
+        self.state = {k: torch.zeros(shape(self.nc, self.caps), device=self.device, dtype=dt) for k, dt, shape in ops.HOTA_STATE_SPEC}
+        self.rows, self.open = {}, False
+
+    upload = MotEvaluator.upload
+
+    def reset(self):
+        """Forget every count and the sequence in progress.  No synchronisation."""
+        for v in self.state.values():
+            v.zero_()
+        self.rows, self.open = {}, False
+
+    def update(self, tracks, tcounts, gt_frames):
+        """As MotEvaluator.update: the ground truth goes up in one copy, one launch follows; nothing synchronises."""
+        B = tracks.shape[0]
+        if len(gt_frames) != B:
+            raise ValueError(f'{len(gt_frames)} ground-truth frames for a batch of {B}')
+        if tracks.shape[1] > self.nq:
+            self.nq = int(tracks.shape[1])
+            self.workspace = torch.empty(ops.hota_workspace_bytes(self.nq, self.ng), device=self.device, dtype=torch.uint8)
+        gt, gcounts = self.upload(gt_frames)
+        ops.hota_update(tracks, tcounts, gt, gcounts, self.state, self.nc, self.caps, self.iou, self.workspace)
+        self.open = True
+
+    def end_sequence(self):
+        """The second pass and the reduction of the sequence in progress (three launches), then a new one starts: ground-truth ids may
+        be used again.  No synchronisation."""
+        ops.hota_end_sequence(self.state, self.nc, self.caps, self.nq, self.ng, self.workspace)
+        self.rows, self.open = {}, False
+
+    def check_overflow(self, hdr):
+        """Raise when the header (read by the caller, e.g. from the predictor's packed copy) counts anything beyond a capacity."""
+        over = [(int(hdr[2 + i]), what) for i, what in enumerate(HOTA_HDR_OVER)]
+        if any(n for n, _ in over):
+            raise HotaOverflow('; '.join(f'{n} {what}' for n, what in over if n) + f' were left out (capacities gt, tracks, pairs, log, frames '
+                               f'= {self.caps}, ng {self.ng}, nq {self.nq}): build the evaluator with larger capacities')
+
+    def counts(self):
+        """The run's counts as engine.hota_evaluate returns them (synchronises; raises HotaOverflow)."""
+        if self.open:
+            raise RuntimeError('a sequence is in progress: call end_sequence() before reading the results')
+        dets, tp, loc, ass, hdr = (self.state[k].cpu().numpy() for k in ('dets', 'tp_lvl', 'loc_lvl', 'ass', 'hdr'))
+        self.check_overflow(hdr)
+        above = lambda lvl: np.cumsum(lvl[:, ::-1], 1)[:, ::-1][:, 1:]   # noqa: E731  a pair at level k counts for every threshold a < k
+        out = {'TP': above(tp.astype(np.int64)), 'loc_sum': above(loc), 'ass_sum': ass[0].copy(), 'assre_sum': ass[1].copy(),
+               'asspr_sum': ass[2].copy(), 'gt_dets': dets[:, 0].astype(np.int64), 'trk_dets': dets[:, 1].astype(np.int64)}
+        out['FN'], out['FP'] = out['gt_dets'][:, None] - out['TP'], out['trk_dets'][:, None] - out['TP']
+        return out
+
+    def results(self, names=None):
+        """engine.hota_summary of the sequences ended so far (synchronises; raises HotaOverflow)."""
+        from .engine import hota_summary
+        return hota_summary(self.counts(), names)
 
 
 def pack_track_rows(frames, nq, device):

@@ -6,7 +6,9 @@
 
 Every `<sequence>.txt` of --results (as tools/track.py --save-mot writes them) is scored against `<sequence>.txt` of --gt.  By default the
 frames go through the device path in batches (track.MotEvaluator: one launch per batch, one per sequence); --host runs the numpy
-statement of the same rule (engine.mot_evaluate) and needs no GPU.  The tables are printed, then one JSON line.
+statement of the same rule (engine.mot_evaluate) and needs no GPU.  The tables are printed, then one JSON line.  --hota adds the HOTA
+tables (HOTA, DetA, AssA ... per class; the rule is written out in tam-tr_amd/csrc/hota.hip) and a `hota` key to the JSON line, through
+the same path: track.HotaEvaluator on the device, engine.hota_evaluate with --host.
 """
 import argparse
 import json
@@ -23,6 +25,7 @@ def parse_args(argv=None):
     ap.add_argument('--names', required=True, help='comma-separated class names; their number is nc')
     ap.add_argument('--iou', type=float, default=0.5)
     ap.add_argument('--host', action='store_true', help='the numpy path (no GPU)')
+    ap.add_argument('--hota', action='store_true', help='score by HOTA as well')
     ap.add_argument('--batch', type=int, default=4, help='frames per launch on the device path')
     ap.add_argument('--gt-capacity', type=int, default=1024)
     ap.add_argument('--track-capacity', type=int, default=4096)
@@ -43,28 +46,48 @@ def main(argv=None):
         raise FileNotFoundError(f'no <sequence>.txt of {args.results} has an annotation file in {args.gt}')
     if not args.host:
         import torch
-        from tamtr_amd.track import MotEvaluator, pack_track_rows
+        from tamtr_amd.track import HotaEvaluator, MotEvaluator, pack_track_rows
         dev = torch.device('cuda', 0)
         ev = MotEvaluator(dev, nc, iou=args.iou, gt_capacity=args.gt_capacity, track_capacity=args.track_capacity, nq=args.rows, ng=args.rows)
+        hev = HotaEvaluator(dev, nc, iou=args.iou, gt_capacity=args.gt_capacity, track_capacity=args.track_capacity, nq=args.rows,
+                            ng=args.rows) if args.hota else None
     total, per_seq = engine.mot_new_counts(nc), {}
+    htotal, hper_seq = engine.hota_new_counts(nc), {}
     for name in seqs:
         res = read_mot(os.path.join(args.results, name + '.txt'), gt=False)
         gt = read_mot(os.path.join(args.gt, name + '.txt'), frames=len(res))
         res += [np.zeros((0, 6), np.float32)] * (len(gt) - len(res))
         if args.host:
             counts = engine.mot_evaluate([list(zip(gt, res))], nc, iou=args.iou)
+            hcounts = engine.hota_evaluate([list(zip(gt, res))], nc, iou=args.iou) if args.hota else None
         else:
             for i in range(0, len(gt), args.batch):
-                ev.update(*pack_track_rows(res[i:i + args.batch], ev.nq, dev), gt[i:i + args.batch])
+                rows = pack_track_rows(res[i:i + args.batch], ev.nq, dev)
+                ev.update(*rows, gt[i:i + args.batch])
+                if args.hota:
+                    hev.update(*rows, gt[i:i + args.batch])
             ev.end_sequence()
             run = ev.counts()
             counts = {k: run[k] - total[k] for k in run}
+            if args.hota:
+                hev.end_sequence()
+                run = hev.counts()
+                hcounts = {k: run[k] - htotal[k] for k in run}
         total = engine.mot_add_counts(total, counts)
         per_seq[name] = engine.mot_summary(counts, names)
         print(engine.mot_table(per_seq[name], name))
+        if args.hota:
+            htotal = engine.hota_add_counts(htotal, hcounts)
+            hper_seq[name] = engine.hota_summary(hcounts, names)
+            print(engine.hota_table(hper_seq[name], name))
     overall = engine.mot_summary(total, names)
     print(engine.mot_table(overall, 'OVERALL'))
-    print(json.dumps({'sequences': len(seqs), 'path': 'host' if args.host else 'device', 'iou': args.iou, 'per_sequence': per_seq, 'overall': overall}))
+    extra = {}
+    if args.hota:
+        extra['hota'] = {'per_sequence': hper_seq, 'overall': engine.hota_summary(htotal, names)}
+        print(engine.hota_table(extra['hota']['overall'], 'OVERALL'))
+    print(json.dumps({'sequences': len(seqs), 'path': 'host' if args.host else 'device', 'iou': args.iou, 'per_sequence': per_seq, 'overall': overall,
+                      **extra}))
 
 
 if __name__ == '__main__':

@@ -17,8 +17,10 @@
       each launch, rows already on the device as the tracker leaves them; median and 10th / 90th percentile over repeated passes after
       a warm-up pass), the update as MotEvaluator.update runs it (with the ground truth's upload), and the host path on the same rows:
       the batch's device-to-host copy plus engine.mot_evaluate (numpy and scipy; host clock).
+  (e) --hota: the HOTA launches on the same sequence, the same way: the update launch per batch next to the MOT update launch, the
+      three end-of-sequence launches, and the host path (the batches' copies plus engine.hota_evaluate).
 
-    python tools/predict_bench.py [--images 64] [--kernel-only] [--track] [--mot]
+    python tools/predict_bench.py [--images 64] [--kernel-only] [--track] [--mot] [--hota]
 --kernel-only runs only the kernel loop of (a), for a `rocprofv3 --kernel-trace --stats` run of its own.
 """
 import argparse
@@ -283,12 +285,87 @@ def bench_mot(frames=200, B=4, nq=300, nc=10, repeats=7):
             'host_ms_per_batch': round(float(np.median(t_host)) / (frames / B), 3), 'passes_timed': repeats}
 
 
+def bench_hota(frames=200, B=4, nq=300, nc=10, repeats=7):
+    """The HOTA launches on bench_mot's sequence: the update launch per batch (alone, and as HotaEvaluator.update runs it with the ground
+    truth's upload), the MOT update launch on the same batches next to it, the three end-of-sequence launches, and the host path on
+    the same rows: the batches' device-to-host copies plus engine.hota_evaluate."""
+    from tamtr_amd import engine, ops
+    from tamtr_amd.track import HotaEvaluator, MotEvaluator, pack_track_rows
+    scene = mot_scene(frames, nc=nc)
+    gts, trks = [g for g, _ in scene], [t for _, t in scene]
+    tracks_d, tc_d = pack_track_rows(trks, nq, 'cuda')
+    ev, mot = HotaEvaluator('cuda', nc, nq=nq, ng=300), MotEvaluator('cuda', nc, nq=nq, ng=300)
+    pct = lambda v: [round(float(np.percentile(v, q)), 4) for q in (50, 10, 90)]   # noqa: E731
+    event = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
+    upd, end, full, mupd = [], [], [], []
+    for rep in range(repeats + 1):
+        pairs, ends = [], []
+        for mode in ('mot', 'launch', 'upload'):      # a HOTA pass comes last: its counts are read below
+            ev.reset(), mot.reset()
+            for i in range(0, frames, B):
+                if mode != 'upload':
+                    gt_d, gc_d = (mot if mode == 'mot' else ev).upload(gts[i:i + B])
+                e0, e1 = event(), event()
+                e0.record()
+                if mode == 'upload':
+                    ev.update(tracks_d[i:i + B], tc_d[i:i + B], gts[i:i + B])
+                elif mode == 'launch':
+                    ops.hota_update(tracks_d[i:i + B], tc_d[i:i + B], gt_d, gc_d, ev.state, nc, ev.caps, ev.iou, ev.workspace)
+                else:
+                    ops.mot_update(tracks_d[i:i + B], tc_d[i:i + B], gt_d, gc_d, mot.state, nc, mot.gt_capacity, mot.track_capacity, mot.iou, mot.workspace)
+                e1.record()
+                pairs.append((mode, e0, e1))
+            if mode == 'mot':
+                continue
+            e2, e3 = event(), event()
+            e2.record()
+            ev.end_sequence()
+            e3.record()
+            ends.append((e2, e3))
+        torch.cuda.synchronize()
+        if rep:      # the first pass is the warm-up
+            upd += [a.elapsed_time(b) for w, a, b in pairs if w == 'launch']
+            full += [a.elapsed_time(b) for w, a, b in pairs if w == 'upload']
+            mupd += [a.elapsed_time(b) for w, a, b in pairs if w == 'mot']
+            end += [a.elapsed_time(b) for a, b in ends]
+    dev_counts = ev.counts()      # the evaluator holds the last ended pass only: reset() came before it
+    hdr = ev.state['hdr'].cpu().tolist()
+
+    def host_pass():
+        rows = []
+        for i in range(0, frames, B):
+            t, c = tracks_d[i:i + B].cpu().numpy(), tc_d[i:i + B].cpu().numpy()      # the copy a host evaluation needs, per batch
+            rows += [t[b, :c[b]][:, [0, 1, 2, 3, 4, 6]] for b in range(len(c))]
+        return engine.hota_evaluate([list(zip(gts, rows))], nc)
+
+    host_pass()
+    t_host = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        host_counts = host_pass()
+        t_host.append((time.perf_counter() - t0) * 1e3)
+    assert all(np.array_equal(dev_counts[k], host_counts[k]) for k in ('TP', 'FN', 'FP', 'gt_dets', 'trk_dets')), 'the two paths counted different things'
+    assert all(np.allclose(dev_counts[k], host_counts[k], rtol=1e-9, atol=0) for k in engine.HOTA_SUM_KEYS), 'the two paths summed different things'
+    s = engine.hota_summary(dev_counts)['all']
+    n_batches = frames / B
+    dev_seq = float(np.median(upd)) * n_batches + float(np.median(end))
+    return {'frames': frames, 'frames_per_launch': B, 'nq': nq, 'nc': nc, 'gt_rows_per_frame': round(float(np.mean([len(g) for g in gts])), 1),
+            'track_rows_per_frame': round(float(np.mean([len(t) for t in trks])), 1), 'HOTA': round(s['HOTA'], 4), 'DetA': round(s['DetA'], 4),
+            'AssA': round(s['AssA'], 4), 'header_after_the_run': hdr[:8],
+            'hota_update_launch_ms_per_batch_p50_p10_p90': pct(upd), 'hota_update_with_gt_upload_ms_per_batch_p50_p10_p90': pct(full),
+            'mot_update_launch_ms_per_batch_p50_p10_p90': pct(mupd), 'end_sequence_3_launches_ms_p50_p10_p90': pct(end),
+            'device_ms_per_sequence': round(dev_seq, 2),
+            'host_copy_plus_numpy_twin_ms_per_sequence_p50_min_max': [round(float(np.median(t_host)), 1), round(min(t_host), 1), round(max(t_host), 1)],
+            'host_ms_per_batch': round(float(np.median(t_host)) / n_batches, 3), 'passes_timed': repeats}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--images', type=int, default=64)
     ap.add_argument('--kernel-only', action='store_true')
     ap.add_argument('--track', action='store_true', help='only (c): the tracker launch against copy + numpy twin')
     ap.add_argument('--mot', action='store_true', help='only (d): the MOT evaluation launches against copy + numpy twin')
+    ap.add_argument('--hota', action='store_true', help='only (e): the HOTA launches against copy + numpy twin, on the sequence of --mot')
     args = ap.parse_args()
     import tamtr_amd  # noqa: F401
     assert torch.cuda.is_available(), 'predict_bench needs an MI355X'
@@ -301,6 +378,10 @@ def main():
     if args.mot:
         print('(d) MOT evaluation: update launch per batch of 4 frames and end-of-sequence launch (device events) vs device-to-host copy + numpy twin (host clock)')
         print(json.dumps(bench_mot()))
+        return
+    if args.hota:
+        print('(e) HOTA: update launch per batch of 4 frames and the end-of-sequence launches (device events) vs device-to-host copy + numpy twin (host clock)')
+        print(json.dumps(bench_hota()))
         return
     if args.kernel_only:
         print(json.dumps({'postprocess_kernel_only': bench_postprocess(True)}))

@@ -2,7 +2,8 @@
 """Track objects through image sequences (the reference's model.track flow with ByteTrack): per frame the boxes of the confirmed
 tracks with their ids; optional annotated copies, YOLO-format label files with the id appended, and one VisDrone-MOT result file per
 sequence, under an incremented --project/--name folder; one JSON line at the end.  With --gt the tracks are scored on the device
-as they are made (CLEAR-MOT and identity metrics, tam-tr_amd/csrc/mot.hip): a table per sequence and over all, and mot_metrics.json.
+as they are made (CLEAR-MOT and identity metrics, tam-tr_amd/csrc/mot.hip): a table per sequence and over all, and mot_metrics.json;
+--hota scores them by HOTA as well (tam-tr_amd/csrc/hota.hip): its tables next to the others and a `hota` key in mot_metrics.json.
 
     python tools/track.py --weights runs/train/TAMTR/best.pt --text-feats clip_vitb32.npz --data dataset.yaml \
         --source sequences/ [--tracker bytetrack.yaml] --conf 0.1 --batch 4 --save-mot [--save --save-txt --save-conf] [--gt annotations/]
@@ -46,6 +47,7 @@ def parse_args(argv=None):
     ap.add_argument('--save-conf', action='store_true', help='put the score before the id on every label line')
     ap.add_argument('--save-mot', action='store_true', help='write <sequence>.txt in the VisDrone-MOT result format')
     ap.add_argument('--gt', help='directory of VisDrone-MOT annotations <sequence>.txt: score the tracks (MOTA, MOTP, IDF1 ...)')
+    ap.add_argument('--hota', action='store_true', help='with --gt: HOTA, DetA, AssA ... as well')
     ap.add_argument('--mot-iou', type=float, default=0.5, help='IoU a track needs with a ground truth to match it, with --gt')
     ap.add_argument('--project', default='runs/track')
     ap.add_argument('--name', default='TAMTR')
@@ -78,7 +80,7 @@ def main(argv=None):
     from tamtr_amd.model import RTDETRDetectionWorldModel
     from tamtr_amd.predict import Predictor, increment_path, is_image_file
     from tamtr_amd import engine
-    from tamtr_amd.track import ByteTracker, MotEvaluator, read_mot, write_mot
+    from tamtr_amd.track import ByteTracker, HotaEvaluator, MotEvaluator, read_mot, write_mot
     from predict import load_names
 
     dev = torch.device('cuda', 0)
@@ -92,7 +94,9 @@ def main(argv=None):
     save_dir = increment_path(os.path.join(args.project, args.name), exist_ok=args.exist_ok)
     saving = args.save or args.save_txt or args.save_mot or bool(args.gt)
     evaluator = MotEvaluator(dev, len(names), iou=args.mot_iou) if args.gt else None
+    hota = HotaEvaluator(dev, len(names), iou=args.mot_iou) if args.gt and args.hota else None
     scored, per_seq = engine.mot_new_counts(len(names)), {}
+    hscored, hper_seq = engine.hota_new_counts(len(names)), {}
     class_names = list(names.values()) if isinstance(names, dict) else list(names)
     if saving:
         save_dir.mkdir(parents=True, exist_ok=True)
@@ -103,7 +107,7 @@ def main(argv=None):
         frames, ids = [], set()
         gt_file = os.path.join(args.gt, name + '.txt') if args.gt else None
         gt = read_mot(gt_file) if gt_file and os.path.exists(gt_file) else None
-        for det in pred.track(folder, tracker=tracker, gt=gt, evaluator=evaluator if gt is not None else None):     # persist=False: a fresh tracker
+        for det in pred.track(folder, tracker=tracker, gt=gt, evaluator=(evaluator if hota is None else [evaluator, hota]) if gt is not None else None):     # persist=False: a fresh tracker
             n_img += 1
             stem = os.path.splitext(os.path.basename(det.path))[0]
             if det.id is not None:
@@ -124,16 +128,29 @@ def main(argv=None):
             scored = engine.mot_add_counts(scored, counts)
             per_seq[name] = engine.mot_summary(counts, class_names)
             print(engine.mot_table(per_seq[name], name))
+            if hota is not None:
+                run = hota.counts()
+                counts = {k: run[k] - hscored[k] for k in run}
+                hscored = engine.hota_add_counts(hscored, counts)
+                hper_seq[name] = engine.hota_summary(counts, class_names)
+                print(engine.hota_table(hper_seq[name], name))
     wall = time.perf_counter() - t0
     sp = pred.speed()
     extra = {}
     if args.gt:
         overall = engine.mot_summary(scored, class_names)
         print(engine.mot_table(overall, 'OVERALL'))
+        metrics = {'iou': args.mot_iou, 'sequences': per_seq, 'overall': overall}
+        if hota is not None:
+            metrics['hota'] = {'sequences': hper_seq, 'overall': engine.hota_summary(hscored, class_names)}
+            print(engine.hota_table(metrics['hota']['overall'], 'OVERALL'))
         with open(save_dir / 'mot_metrics.json', 'w') as fh:
-            json.dump({'iou': args.mot_iou, 'sequences': per_seq, 'overall': overall}, fh, indent=1)
+            json.dump(metrics, fh, indent=1)
         extra = {'mot': {k: overall['all'][k] for k in ('MOTA', 'MOTP', 'IDF1', 'IDSW', 'FP', 'FN')}, 'mot_ms_per_image': round(sp.get('mot', 0.0), 4),
                  'scored_sequences': len(per_seq)}
+        if hota is not None:
+            extra['hota'] = {k: metrics['hota']['overall']['all'][k] for k in ('HOTA', 'DetA', 'AssA', 'LocA')}
+            extra['hota_ms_per_image'] = round(sp.get('hota', 0.0), 4)
     print(json.dumps({**extra, 'sequences': len(seqs), 'images': n_img, 'track_rows': n_rows, 'ids': n_ids, 'save_dir': str(save_dir) if saving else None,
                       'ms_per_image': {'load': round(sp['load'], 3), 'forward': round(sp['h2d'] + sp['forward'], 3),
                                        'postprocess': round(sp['postprocess'], 3), 'track': round(sp['track'], 4), 'd2h': round(sp['d2h'], 3)},
