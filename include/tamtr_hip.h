@@ -37,8 +37,8 @@ extern "C" {
 /* ABI version, bumped on any signature change.  The CLIP text tower's entries at the end of this file (tamtr_text_embed, tamtr_linear_f32,
  * tamtr_text_pool_project), tamtr_val_confusion, tamtr_val_ap_curves / tamtr_val_ap_tile and tamtr_bytetrack_update /
  * tamtr_bytetrack_workspace_bytes, tamtr_val_coco_match / tamtr_val_coco_workspace_bytes / tamtr_val_coco_accumulate and tamtr_mot_update /
- * tamtr_mot_end_sequence / tamtr_mot_workspace_bytes, and tamtr_hota_update / tamtr_hota_end_sequence / tamtr_hota_workspace_bytes are new symbols
- * only: no existing signature changed, so the version stayed at 36 when they were added. */
+ * tamtr_mot_end_sequence / tamtr_mot_workspace_bytes, tamtr_hota_update / tamtr_hota_end_sequence / tamtr_hota_workspace_bytes, and
+ * tamtr_dw_slices / tamtr_dw_bf16 are new symbols only: no existing signature changed, so the version stayed at 36 when they were added. */
 int tamtr_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -348,6 +348,15 @@ int tamtr_colsum_bf16(const void* X, float* partial, long long M, int N, void* s
  *      multi-workgroup reduction zeroes a semaphore buffer with a memset node per launch, which a HIP-graph replay under AQL packet
  *      capture does not keep in order with the kernels around it.  C % 4 == 0; in 16-byte (f32) / 8-byte (bf16) aligned. */
 int tamtr_slab_sum_rows(const void* in, float* out, int R, long long C, int dtype, void* stream);
+/*      Weight (and bias) gradient of a token-wise linear or 1x1 convolution for SHORT and MID-SIZE M, as row-slice partials
+ *      (csrc/dwgrad.hip):  part[s][n * K + k] = sum over the rows m of slice s of dY[m, n] X[m, k];  part[s][N * K + n] = the slice's
+ *      column sums of dY (with_db) or 0.  dY bf16 [M, N], X bf16 [M, K], part f32 [S][N * K + Npad] (Npad = N rounded up to 4), all
+ *      contiguous and 16-byte aligned; S = tamtr_dw_slices(M, N, K) (host only, 1 .. 64; 0: shape not served - N, K multiples of 16 up
+ *      to 16 384, any M >= 1).  Slice s covers rows [s * R, min(M, (s + 1) * R)) with R = ceil(ceil(M / S) / 64) * 64.  One kernel,
+ *      plain stores, every element of part written once: no atomics, no memset.  The caller adds the S rows in order
+ *      (tamtr_slab_sum_rows: dW and db in one launch); bf16 MFMA with fp32 accumulators, the column sums in fp32 in a fixed order. */
+int tamtr_dw_slices(long long M, int N, int K);
+int tamtr_dw_bf16(const void* dY, const void* X, float* part, int with_db, long long M, int N, int K, void* stream);
 int tamtr_fold_add(const float* g4, const void* m0, const void* m1, float* out, int B, long long n, int dtype, void* stream);
 
 /*      tamtr_layernorm_* : LayerNorm over the channel axis of a token-major map, VSSBlock.norm / norm2

@@ -62,6 +62,8 @@ _SIGS = {
     'tamtr_colsum_bf16': [_P, _P, _LL, _I, _P],
     'tamtr_fold_add': [_P, _P, _P, _P, _I, _LL, _I, _P],
     'tamtr_slab_sum_rows': [_P, _P, _I, _LL, _I, _P],
+    'tamtr_dw_slices': [_LL, _I, _I],
+    'tamtr_dw_bf16': [_P, _P, _P, _I, _LL, _I, _I, _P],
     'tamtr_graph_capture_census': [_P, _P, _I],
     'tamtr_box_refine_fwd': [_P, _P, _P, _LL, _P],
     'tamtr_box_refine_bwd': [_P, _P, _P, _P, _P, _LL, _P],

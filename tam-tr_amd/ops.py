@@ -552,14 +552,46 @@ def _split_count(M, min_rows=2048, max_split=None):
 
 _BMM_F32_OUT = None  # does this torch build take bmm(..., out_dtype=float32) on the GPU?
 
+_DW_OWN = _os.environ.get('TAMTR_DW_OWN') != '0'   # A/B switch: 0 = every weight gradient on the batched library product, as before csrc/dwgrad.hip
+# Below this many rows dW = dY^T X (and db) runs on csrc/dwgrad.hip; from it on, on the batched library product.  Measured per shape in
+# profiles/r17_dw_shapes.txt: the decoder-side linears (M = B Q = 4 672) 1.25 - 3.2 x and the trunk's 1x1 convolutions at M <= 6 400 mostly
+# 1.1 - 1.3 x faster; at M = 25 600 and 102 400 wins and losses alternate by shape, from 409 600 rows on the library wins throughout.
+_DW_OWN_MAX_ROWS = 8192
+
+
+def _dw_own_slices(g2, x2):
+    """The slice count of csrc/dwgrad.hip for dW = g2^T x2, or 0 where the product stays on the library: not bf16 on the GPU, not contiguous
+    or not 16-byte aligned, a shape the kernel does not serve (N, K multiples of 16), M at or above _DW_OWN_MAX_ROWS, TAMTR_DW_OWN=0."""
+    if not (_DW_OWN and g2.is_cuda and x2.is_cuda and g2.dtype == torch.bfloat16 and x2.dtype == torch.bfloat16 and g2.dim() == 2 and x2.dim() == 2
+            and g2.shape[0] == x2.shape[0] and 0 < g2.shape[0] < _DW_OWN_MAX_ROWS and g2.is_contiguous() and x2.is_contiguous()
+            and g2.data_ptr() % 16 == 0 and x2.data_ptr() % 16 == 0):
+        return 0
+    return _lib.lib().tamtr_dw_slices(g2.shape[0], g2.shape[1], x2.shape[1])
+
+
+def _dw_own(g2, x2, S, with_db):
+    """(dW f32 [N, K], db f32 [N]) = (g2^T x2, column sums of g2) in two launches: the S row slices' partial products and column sums
+    (tamtr_dw_bf16), then the ordered sum over the slices of both at once (slab_sum).  Bitwise reproducible; no memset, no atomics.
+    db is zeros without with_db."""
+    M, N = g2.shape
+    K = x2.shape[1]
+    part = torch.empty(S, N * K + N, device=g2.device, dtype=torch.float32)   # (N % 16 == 0: the row pitch N K + N needs no padding)
+    call('tamtr_dw_bf16', ptr(g2), ptr(x2), ptr(part), int(with_db), M, N, K, stream_ptr())
+    tot = slab_sum(part)
+    return tot[:N * K].view(N, K), tot[N * K:]
+
 
 def dw_splitk(g2, x2, min_rows=2048):
     """dW [N, K] = g2^T x2 for very tall operands (M = B*L rows >> N, K), fp32 result.
     A single M-reduction GEMM of this shape has only (N/64)*(K/128) = 8..32 output tiles: hipBLASLt ran it on that many
     workgroups (945 us for M = 537 600, N = K = 512: 0.3 PF/s).  Sliced into S row blocks it is ONE batched GEMM with S x
-    the tiles, and the S partial products are summed in fp32."""
+    the tiles, and the S partial products are summed in fp32.  Short operands (fewer than _DW_OWN_MAX_ROWS rows, bf16) take the own
+    row-slice kernel instead (_dw_own: csrc/dwgrad.hip), whose slice count follows the shape."""
     M, N = g2.shape
     K = x2.shape[1]
+    S = _dw_own_slices(g2, x2)
+    if S:
+        return _dw_own(g2, x2, S, False)[0]
     S = _split_count(M, min_rows)
     if S == 1:
         return (g2.t() @ x2).float()
@@ -676,7 +708,13 @@ def _bias_rows(y, idx, b32):
 
 def _param_grads(g2, x2, w_dt, b_dt, need_w, need_b, min_rows=2048):
     """(dW, db) of a token-wise linear from dY [M, N] and X [M, K], in the parameters' dtypes: dW = dY^T X by row slices (dw_splitk), db the
-    ordered column sums of dY (colsum); None for one that is not needed (b_dt None: no bias)."""
+    ordered column sums of dY (colsum); None for one that is not needed (b_dt None: no bias).  Short and mid-size bf16 operands: both from
+    csrc/dwgrad.hip's one product launch and one ordered sum (_dw_own)."""
+    S = _dw_own_slices(g2, x2) if need_w else 0
+    if S:
+        with_db = b_dt is not None and need_b
+        gw, gb = _dw_own(g2, x2, S, with_db)
+        return gw.to(w_dt), (gb.to(b_dt) if with_db else None)
     gw = dw_splitk(g2, x2, min_rows).to(w_dt) if need_w else None
     gb = colsum(g2).to(b_dt) if (b_dt is not None and need_b) else None
     return gw, gb
