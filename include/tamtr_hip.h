@@ -35,7 +35,7 @@ extern "C" {
 #define TAMTR_ELAUNCH (-3)
 
 /* ABI version, bumped on any signature change.  The CLIP text tower's entries at the end of this file (tamtr_text_embed, tamtr_linear_f32,
- * tamtr_text_pool_project), tamtr_val_confusion, tamtr_val_ap_curves / tamtr_val_ap_tile and tamtr_bytetrack_update /
+ * tamtr_text_pool_project), tamtr_val_confusion, tamtr_val_ap_curves / tamtr_val_ap_tile and tamtr_bytetrack_update / tamtr_botsort_update /
  * tamtr_bytetrack_workspace_bytes, tamtr_val_coco_match / tamtr_val_coco_workspace_bytes / tamtr_val_coco_accumulate and tamtr_mot_update /
  * tamtr_mot_end_sequence / tamtr_mot_workspace_bytes, tamtr_hota_update / tamtr_hota_end_sequence / tamtr_hota_workspace_bytes, and
  * tamtr_dw_slices / tamtr_dw_bf16 are new symbols only: no existing signature changed, so the version stayed at 36 when they were added. */
@@ -720,6 +720,43 @@ int tamtr_bytetrack_update(const float* out, const int32_t* counts, int B, int n
                            double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts, void* workspace, int workspace_bytes,
                            void* stream);
 int tamtr_bytetrack_workspace_bytes(int T, int nq);
+
+/*      tamtr_botsort_update: BOTSORT.update, ultralytics/trackers/bot_sort.py (with STrack.multi_gmc, byte_tracker.py:81-97, and
+ *      KalmanFilterXYWH, utils/kalman_filter.py:222-368), for the B frames of a batch: the launch, the table, the workspace
+ *      (tamtr_bytetrack_workspace_bytes) and the error codes of tamtr_bytetrack_update, with the filter state (x, y, w, h and their
+ *      velocities), mean[6] = mean[7] = 0 before a track that is not Tracked is predicted, and the frame's warp applied to every pool
+ *      and every unconfirmed track between the prediction and the first association (csrc/track.hip states all three).
+ *      warps f64 [B, 2, 3], row-major, in the pixels of `out`, on the device, 8-byte aligned (else TAMTR_EINVAL); NULL = the identity
+ *      for every frame.  The warp of a frame with counts[b] <= 0 is not applied.  With with_reid off - the reference builds no
+ *      embeddings - the costs are ByteTrack's; proximity_thresh and appearance_thresh are not arguments.  A table written by one of
+ *      the two trackers must not be handed to the other: the means differ in meaning.  (New symbol only; the ABI version stays 36.) */
+int tamtr_botsort_update(const float* out, const int32_t* counts, const double* warps, int B, int nq, double* mean, double* cov,
+                         int32_t* meta, float* sc, int32_t* hdr, int T, float track_high_thresh, float track_low_thresh,
+                         float new_track_thresh, double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts, void* workspace,
+                         int workspace_bytes, void* stream);
+
+/*      tamtr_gmc_estimate: the warps tamtr_botsort_update reads, estimated from the frames of the batch on the device.  It stands where
+ *      the reference runs OpenCV on the host (trackers/utils/gmc.py:247-302, applySparseOptFlow); the rule is the project's own and is
+ *      written out in csrc/gmc.hip (grey + pyramid, grid keypoints, pyramidal Lucas-Kanade, 512-hypothesis similarity fit).
+ *      frames u8 [B, H, W, 3] RGB, the network input as uploaded; H, W multiples of 8 and at least 64 (else TAMTR_EINVAL)
+ *      counts i32 [B]        the detections per frame: a frame with counts[b] <= 0 gets the identity and never becomes "previous"
+ *      scale  f64 [B, 2]     (sx, sy) = (w0 / W, h0 / H): network pixels -> the original pixels the tracker's states live in
+ *      st_pyr u8 [tamtr_gmc_state_bytes(H, W)], st_kp i32 [1024], st_hdr i32 [4]   the persistent state: pyramid and keypoint slots of
+ *                            the last frame that reached the tracker, st_hdr[0] = valid; updated in place; st_hdr all zero = fresh
+ *      warps  f64 [B, 2, 3]  out, original pixels, warp b maps the paired earlier frame's coordinates to frame b's
+ *      stats  i32 [B, 4]     out: keypoints, tracked, inliers, used
+ *      workspace: tamtr_gmc_workspace_bytes(B, H, W) bytes, 16-byte aligned, contents irrelevant.  tamtr_gmc_workspace_offset(B, H, W, i)
+ *      is the byte offset of section i (csrc/gmc.hip lists them: pyramids, corner response, tile maxima, keypoint slots, point pairs,
+ *      status, fit record, pairing), so that a test can read and prescribe every stage; `stages` is a mask of the launches to run
+ *      (1 pyramid + corner response, 2 cells, 4 LK, 8 fit + state copy; 15 = all, the only value outside tests).
+ *      At most four launches on `stream`; nothing is allocated, set or synchronised.  Every check comes before any GPU call.
+ *      (New symbols only; the ABI version stays 36.) */
+int tamtr_gmc_workspace_bytes(int B, int H, int W);      /* -1: H, W or B outside what is built, or more than 2^31 - 1 bytes */
+int tamtr_gmc_workspace_offset(int B, int H, int W, int which);
+int tamtr_gmc_state_bytes(int H, int W);
+int tamtr_gmc_estimate(const uint8_t* frames, const int32_t* counts, const double* scale, int B, int H, int W, uint8_t* st_pyr,
+                       int32_t* st_kp, int32_t* st_hdr, double* warps, int32_t* stats, void* workspace, int workspace_bytes,
+                       int stages, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * COCO-protocol bbox evaluation (AP / AR by object size) on the device.  Replaces the step the reference leaves to pycocotools:

@@ -36,6 +36,26 @@
 // a barrier between the steps.  Lists (pool, unconfirmed, high / low detections ...) are built in index order with ballots, the cost
 // matrices and lists live in a workspace in global memory (L2-resident), the solver's duals and paths in LDS.  One lane runs one
 // track's filter.  The work is tiny and latency-bound.
+//
+// BoT-SORT (tamtr_botsort_update): BOTSORT.update (trackers/bot_sort.py with byte_tracker.py:81-97 and utils/kalman_filter.py:222-368)
+// is the same kernel compiled with KF = KF_XYWH; the table, the lists, the costs and the assignment are the ones above.  It differs in:
+//   filter   KalmanFilterXYWH: the state is (x, y, w, h, vx, vy, vw, vh), the measurement tlwh_to_xywh in fp32 (x1 + w / 2, y1 + h / 2,
+//            w, h), and every std comes from mean[2] and mean[3].  A new track's mean AND covariance are fp32 arrays in numpy (every
+//            entry of initiate's std list is an fp32 scalar, so the squares are fp32 too); while the mean still is that measurement
+//            (TRK_RAW) predict and project derive their stds and square them in fp32.  The tlbr of a mean is x - w/2, y - h/2,
+//            w + x1, h + y1.
+//   predict  a pool track that is not Tracked gets mean[6] = mean[7] = 0 first (bot_sort.py:97-110; ByteTrack zeroes mean[7] only).
+//   warp     after the pool's predict and before the first association frame b's warp H = warps[b] (f64 [2, 3], row-major, original
+//            pixels; a null `warps` is the identity for every frame) goes to every pool track and every unconfirmed track
+//            (byte_tracker.py:277-280, multi_gmc): with R = H[:, :2], t = H[:, 2]: mean = kron(I4, R) @ mean, mean[:2] += t,
+//            cov = (R8 @ cov) @ R8^T.  R8 is block diagonal, so each entry of a product has two terms that are not a product with
+//            zero: two products and one sum, each rounded on its own here (-ffp-contract=off).  numpy's R8.dot(cov) goes through
+//            BLAS, which may fuse a product into the sum, so the two can differ in the last bit; the tests hold mean and cov to 1e-6
+//            relative, not to the bit.  The result is an fp64 array: a warped track is no longer TRK_RAW, also under the
+//            identity warp (the reference run with an image).  A frame without detections does not reach the tracker, and its
+//            warp is not applied.
+//   costs    get_dists with with_reid off (the reference builds no embeddings) is ByteTrack's fused IoU distance; proximity_thresh
+//            and appearance_thresh act on embeddings only and are not read here.
 #include "common.h"
 
 #define TRK_FREE 0
@@ -44,6 +64,7 @@
 #define TRK_LIMBO 3
 #define TRK_RAW 1
 #define TRK_EVER_REMOVED 2
+enum { KF_XYAH, KF_XYWH };
 enum { M_STATE, M_ACT, M_ID, M_FRAME, M_START, M_LEN, M_IDX, M_FLAGS };
 
 // ---------------------------------------------------------------------------------------------------------------- small helpers
@@ -74,8 +95,10 @@ __device__ __forceinline__ float trk_iou(const float* a, const float* b) {
 }
 
 // STrack.tlbr from the filter mean (byte_tracker.py:151-166), fp64, then the cast to fp32
+// (KF_XYWH: BOTrack.tlwh, bot_sort.py:87-94: the width is mean[2] itself)
+template <int KF>
 __device__ __forceinline__ void trk_tlbr(const double* m, float* o) {
-  const double w = m[2] * m[3];
+  const double w = KF == KF_XYWH ? m[2] : m[2] * m[3];
   const double x1 = m[0] - w / 2, y1 = m[1] - m[3] / 2;
   o[0] = (float)x1;
   o[1] = (float)y1;
@@ -83,17 +106,28 @@ __device__ __forceinline__ void trk_tlbr(const double* m, float* o) {
   o[3] = (float)(m[3] + y1);
 }
 
-// convert_coords of a detection (tlbr_to_tlwh, tlwh_to_xyah): fp32 throughout
+// convert_coords of a detection (tlbr_to_tlwh, then tlwh_to_xyah or tlwh_to_xywh): fp32 throughout
+template <int KF>
 __device__ __forceinline__ void trk_xyah(const float* d, float* z) {
   const float w = d[2] - d[0], h = d[3] - d[1];
   z[0] = d[0] + w / 2.0f;
   z[1] = d[1] + h / 2.0f;
-  z[2] = w / h;
+  z[2] = KF == KF_XYWH ? w : w / h;
   z[3] = h;
 }
 
 // ---------------------------------------------------------------------------------------------------------------- Kalman filter
+template <int KF>
 __device__ void kf_initiate(double* m, double* P, const float* z) {
+  if (KF == KF_XYWH) {   // every std and its square in fp32: 2 * (1 / 20) and 10 * (1 / 160), times an fp32 width or height
+    const float pw = (float)0.1 * z[2], ph = (float)0.1 * z[3], vw = (float)0.0625 * z[2], vh = (float)0.0625 * z[3];
+    const float dg[8] = {pw * pw, ph * ph, pw * pw, ph * ph, vw * vw, vh * vh, vw * vw, vh * vh};
+    for (int i = 0; i < 8; ++i) {
+      m[i] = i < 4 ? (double)z[i] : 0.0;
+      for (int j = 0; j < 8; ++j) P[i * 8 + j] = i == j ? (double)dg[i] : 0.0;
+    }
+    return;
+  }
   const float sp32 = (float)0.1 * z[3], sv32 = (float)0.0625 * z[3];   // 2 * (1 / 20) and 10 * (1 / 160), times an fp32 height
   const double sp = sp32, sv = sv32;
   const double dg[8] = {sp * sp, sp * sp, 1e-2 * 1e-2, sp * sp, sv * sv, sv * sv, 1e-5 * 1e-5, sv * sv};
@@ -103,10 +137,30 @@ __device__ void kf_initiate(double* m, double* P, const float* z) {
   }
 }
 
-__device__ void kf_predict(double* m, double* P, bool raw, bool not_tracked) {
-  if (not_tracked) m[7] = 0.0;
-  double q[8];
+// KalmanFilterXYWH's squared stds (position of w, of h, velocity of w, of h): fp32 while the mean is the fp32 measurement
+__device__ __forceinline__ void kf_stds_xywh(const double* m, bool raw, double* o) {
   if (raw) {
+    const float w = (float)m[2], h = (float)m[3];
+    const float s[4] = {(float)(1.0 / 20) * w, (float)(1.0 / 20) * h, (float)(1.0 / 160) * w, (float)(1.0 / 160) * h};
+    for (int i = 0; i < 4; ++i) o[i] = s[i] * s[i];
+  } else {
+    const double s[4] = {1.0 / 20 * m[2], 1.0 / 20 * m[3], 1.0 / 160 * m[2], 1.0 / 160 * m[3]};
+    for (int i = 0; i < 4; ++i) o[i] = s[i] * s[i];
+  }
+}
+
+template <int KF>
+__device__ void kf_predict(double* m, double* P, bool raw, bool not_tracked) {
+  if (not_tracked) {
+    if (KF == KF_XYWH) m[6] = 0.0;
+    m[7] = 0.0;
+  }
+  double q[8];
+  if (KF == KF_XYWH) {
+    double s[4];
+    kf_stds_xywh(m, raw, s);
+    for (int i = 0; i < 8; ++i) q[i] = s[(i >> 2) * 2 + (i & 1)];
+  } else if (raw) {
     const float h = (float)m[3];
     const float sp = (float)(1.0 / 20) * h, sv = (float)(1.0 / 160) * h;
     const float cp = (float)1e-2, cv = (float)1e-5;
@@ -128,12 +182,20 @@ __device__ void kf_predict(double* m, double* P, bool raw, bool not_tracked) {
   for (int i = 0; i < 8; ++i) P[i * 9] += q[i];
 }
 
+template <int KF>
 __device__ void kf_update(double* mg, double* Pg, const float* z, bool raw) {
   double m[8], P[64];
   for (int i = 0; i < 8; ++i) m[i] = mg[i];
   for (int i = 0; i < 64; ++i) P[i] = Pg[i];
-  const double sp = raw ? (double)((float)(1.0 / 20) * (float)m[3]) : 1.0 / 20 * m[3];
-  const double dg[4] = {sp * sp, sp * sp, 1e-1 * 1e-1, sp * sp};
+  double dg[4];
+  if (KF == KF_XYWH) {
+    double s[4];
+    kf_stds_xywh(m, raw, s);
+    dg[0] = s[0]; dg[1] = s[1]; dg[2] = s[0]; dg[3] = s[1];
+  } else {
+    const double sp = raw ? (double)((float)(1.0 / 20) * (float)m[3]) : 1.0 / 20 * m[3];
+    dg[0] = sp * sp; dg[1] = sp * sp; dg[2] = 1e-1 * 1e-1; dg[3] = sp * sp;
+  }
   double S[4][4], L[4][4];
   for (int i = 0; i < 4; ++i)
     for (int j = 0; j < 4; ++j) { S[i][j] = P[i * 8 + j] + (i == j ? dg[i] : 0.0); L[i][j] = 0.0; }
@@ -179,6 +241,30 @@ __device__ void kf_update(double* mg, double* Pg, const float* z, bool raw) {
       Pg[i * 8 + j] = P[i * 8 + j] - c;
     }
   }
+}
+
+// STrack.multi_gmc for one track (byte_tracker.py:81-97), in place: H = a b tx / c d ty
+__device__ void kf_warp(double* m, double* P, const double* H) {
+  const double a = H[0], b = H[1], tx = H[2], c = H[3], d = H[4], ty = H[5];
+  for (int k = 0; k < 8; k += 2) {
+    const double x = m[k], y = m[k + 1];
+    m[k] = a * x + b * y;
+    m[k + 1] = c * x + d * y;
+  }
+  m[0] += tx;
+  m[1] += ty;
+  for (int k = 0; k < 8; k += 2)      // R8 @ P: rows in pairs
+    for (int j = 0; j < 8; ++j) {
+      const double x = P[k * 8 + j], y = P[(k + 1) * 8 + j];
+      P[k * 8 + j] = a * x + b * y;
+      P[(k + 1) * 8 + j] = c * x + d * y;
+    }
+  for (int i = 0; i < 8; ++i)         // (R8 @ P) @ R8^T: columns in pairs
+    for (int k = 0; k < 8; k += 2) {
+      const double x = P[i * 8 + k], y = P[i * 8 + k + 1];
+      P[i * 8 + k] = x * a + y * b;
+      P[i * 8 + k + 1] = x * c + y * d;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- assignment
@@ -287,6 +373,7 @@ struct TrkParams {
   float* tracks;
   int32_t* tcounts;
   unsigned char* ws;
+  const double* warps;   // KF_XYWH only: [B, 2, 3] or null
 };
 
 static size_t trk_ws_bytes(int T, int nq) { return 4 * ((size_t)T * nq + 4 * (size_t)T + 4 * (size_t)nq + 7 * (size_t)T + 5 * (size_t)nq); }
@@ -296,11 +383,12 @@ static size_t trk_lds_bytes(int T, int nq) {
 }
 
 // a matched track: STrack.update / re_activate (byte_tracker.py:112-145)
+template <int KF>
 __device__ __forceinline__ void trk_matched(const TrkParams& p, int s, const float* d, int dj, int fid, bool keep_len) {
   int32_t* mt = p.meta + (size_t)s * 8;
   float z[4];
-  trk_xyah(d + (size_t)dj * 6, z);
-  kf_update(p.mean + (size_t)s * 8, p.cov + (size_t)s * 64, z, mt[M_FLAGS] & TRK_RAW);
+  trk_xyah<KF>(d + (size_t)dj * 6, z);
+  kf_update<KF>(p.mean + (size_t)s * 8, p.cov + (size_t)s * 64, z, mt[M_FLAGS] & TRK_RAW);
   mt[M_FLAGS] &= ~TRK_RAW;
   mt[M_LEN] = keep_len ? mt[M_LEN] + 1 : 0;
   mt[M_STATE] = TRK_TRACKED;
@@ -311,6 +399,7 @@ __device__ __forceinline__ void trk_matched(const TrkParams& p, int s, const flo
   p.sc[2 * s + 1] = d[(size_t)dj * 6 + 5];
 }
 
+template <int KF>
 __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
   extern __shared__ __align__(16) unsigned char lds[];
   const int lane = threadIdx.x, T = p.T, nq = p.nq;
@@ -364,15 +453,26 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
     });
     for (int s = lane; s < T; s += WAVE) { newly_lost[s] = 0; dup[s] = 0; }
     __syncthreads();
-    // ---- 3. predict the pool (not the unconfirmed tracks)
+    // ---- 3. predict the pool (not the unconfirmed tracks); KF_XYWH: then the frame's warp, to the pool and the unconfirmed tracks
+    double H[6] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0};
+    if (KF == KF_XYWH && p.warps)
+      for (int i = 0; i < 6; ++i) H[i] = p.warps[(size_t)b * 6 + i];
     for (int i = lane; i < npool; i += WAVE) {
       const int s = pool[i];
       int32_t* mt = p.meta + (size_t)s * 8;
-      kf_predict(p.mean + (size_t)s * 8, p.cov + (size_t)s * 64, mt[M_FLAGS] & TRK_RAW, mt[M_STATE] != TRK_TRACKED);
+      kf_predict<KF>(p.mean + (size_t)s * 8, p.cov + (size_t)s * 64, mt[M_FLAGS] & TRK_RAW, mt[M_STATE] != TRK_TRACKED);
       mt[M_FLAGS] &= ~TRK_RAW;
-      trk_tlbr(p.mean + (size_t)s * 8, tb + 4 * s);
+      if (KF == KF_XYWH) kf_warp(p.mean + (size_t)s * 8, p.cov + (size_t)s * 64, H);
+      trk_tlbr<KF>(p.mean + (size_t)s * 8, tb + 4 * s);
     }
-    for (int i = lane; i < nun; i += WAVE) trk_tlbr(p.mean + (size_t)unconf[i] * 8, tb + 4 * unconf[i]);
+    for (int i = lane; i < nun; i += WAVE) {
+      const int s = unconf[i];
+      if (KF == KF_XYWH) {
+        kf_warp(p.mean + (size_t)s * 8, p.cov + (size_t)s * 64, H);
+        p.meta[(size_t)s * 8 + M_FLAGS] &= ~TRK_RAW;
+      }
+      trk_tlbr<KF>(p.mean + (size_t)s * 8, tb + 4 * s);
+    }
     __syncthreads();
     // ---- 4. first association: pool x high detections, fused distance, match_thresh
     if (npool > 0 && nhi > 0) {
@@ -391,7 +491,7 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
       const int j = xs[i];
       if (j >= 0) {
         const int s = pool[i];
-        trk_matched(p, s, d, hi[j], fid, p.meta[s * 8 + M_STATE] == TRK_TRACKED);
+        trk_matched<KF>(p, s, d, hi[j], fid, p.meta[s * 8 + M_STATE] == TRK_TRACKED);
         used[hi[j]] = 1;
       }
     }
@@ -413,7 +513,7 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
     for (int i = lane; i < nrest; i += WAVE) {
       const int s = pool[rest[i]], j = xs[i];
       if (j >= 0) {
-        trk_matched(p, s, d, lo[j], fid, true);
+        trk_matched<KF>(p, s, d, lo[j], fid, true);
       } else if (p.meta[s * 8 + M_FLAGS] & TRK_EVER_REMOVED) {
         p.meta[s * 8 + M_STATE] = TRK_FREE;
       } else {
@@ -440,7 +540,7 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
     for (int i = lane; i < nun; i += WAVE) {
       const int s = unconf[i], j = xs[i];
       if (j >= 0) {
-        trk_matched(p, s, d, hi[left[j]], fid, true);
+        trk_matched<KF>(p, s, d, hi[left[j]], fid, true);
         used[hi[left[j]]] = 1;
       } else {
         p.meta[s * 8 + M_STATE] = TRK_FREE;
@@ -456,8 +556,8 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
     for (int k = lane; k < ncreate; k += WAVE) {
       const int s = freel[k], dj = hi[left[newd[k]]];
       float z[4];
-      trk_xyah(d + (size_t)dj * 6, z);
-      kf_initiate(p.mean + (size_t)s * 8, p.cov + (size_t)s * 64, z);
+      trk_xyah<KF>(d + (size_t)dj * 6, z);
+      kf_initiate<KF>(p.mean + (size_t)s * 8, p.cov + (size_t)s * 64, z);
       int32_t* mt = p.meta + (size_t)s * 8;
       mt[M_STATE] = TRK_TRACKED;
       mt[M_ACT] = fid == 1;
@@ -487,7 +587,7 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
     const int nA = trk_compact(T, pool, lane, [&](int s) { return p.meta[s * 8 + M_STATE] == TRK_TRACKED; });
     const int nB = trk_compact(T, unconf, lane, [&](int s) { const int st = p.meta[s * 8 + M_STATE]; return st == TRK_LOST || st == TRK_LIMBO; });
     for (int s = lane; s < T; s += WAVE)
-      if (p.meta[s * 8 + M_STATE] != TRK_FREE) trk_tlbr(p.mean + (size_t)s * 8, tb + 4 * s);
+      if (p.meta[s * 8 + M_STATE] != TRK_FREE) trk_tlbr<KF>(p.mean + (size_t)s * 8, tb + 4 * s);
     __syncthreads();
     for (int e = lane; e < nA * nB; e += WAVE) {
       const int i = e / nB, sa = pool[i], sb = unconf[e - i * nB];
@@ -528,16 +628,34 @@ extern "C" int tamtr_bytetrack_workspace_bytes(int T, int nq) {
   return n > 0x7fffffff ? 0 : (int)n;
 }
 
-extern "C" int tamtr_bytetrack_update(const float* out, const int32_t* counts, int B, int nq, double* mean, double* cov, int32_t* meta,
-                                      float* sc, int32_t* hdr, int T, float track_high_thresh, float track_low_thresh,
-                                      float new_track_thresh, double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts,
-                                      void* workspace, int workspace_bytes, void* stream) {
+template <int KF>
+static int trk_launch(const float* out, const int32_t* counts, const double* warps, int B, int nq, double* mean, double* cov, int32_t* meta,
+                      float* sc, int32_t* hdr, int T, float track_high_thresh, float track_low_thresh, float new_track_thresh,
+                      double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts, void* workspace, int workspace_bytes,
+                      void* stream) {
   if (!out || !counts || !mean || !cov || !meta || !sc || !hdr || !tracks || !tcounts || !workspace || B < 1 || nq < 1 || T < 1)
     return TAMTR_EINVAL;
   if (tamtr_bytetrack_workspace_bytes(T, nq) == 0 || trk_lds_bytes(T, nq) > 64 * 1024) return TAMTR_EUNSUP;
   if (workspace_bytes < tamtr_bytetrack_workspace_bytes(T, nq)) return TAMTR_EINVAL;
   TrkParams p{out, counts, B, nq, T, mean, cov, meta, sc, hdr, track_high_thresh, track_low_thresh, new_track_thresh, match_thresh,
-              max_time_lost, tracks, tcounts, static_cast<unsigned char*>(workspace)};
-  hipLaunchKernelGGL(bytetrack_kernel, dim3(1), dim3(WAVE), trk_lds_bytes(T, nq), (hipStream_t)stream, p);
+              max_time_lost, tracks, tcounts, static_cast<unsigned char*>(workspace), warps};
+  hipLaunchKernelGGL(bytetrack_kernel<KF>, dim3(1), dim3(WAVE), trk_lds_bytes(T, nq), (hipStream_t)stream, p);
   return tamtr_launch_status();
+}
+
+extern "C" int tamtr_bytetrack_update(const float* out, const int32_t* counts, int B, int nq, double* mean, double* cov, int32_t* meta,
+                                      float* sc, int32_t* hdr, int T, float track_high_thresh, float track_low_thresh,
+                                      float new_track_thresh, double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts,
+                                      void* workspace, int workspace_bytes, void* stream) {
+  return trk_launch<KF_XYAH>(out, counts, nullptr, B, nq, mean, cov, meta, sc, hdr, T, track_high_thresh, track_low_thresh, new_track_thresh,
+                             match_thresh, max_time_lost, tracks, tcounts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tamtr_botsort_update(const float* out, const int32_t* counts, const double* warps, int B, int nq, double* mean, double* cov,
+                                    int32_t* meta, float* sc, int32_t* hdr, int T, float track_high_thresh, float track_low_thresh,
+                                    float new_track_thresh, double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts,
+                                    void* workspace, int workspace_bytes, void* stream) {
+  if (warps && (reinterpret_cast<uintptr_t>(warps) & 7)) return TAMTR_EINVAL;
+  return trk_launch<KF_XYWH>(out, counts, warps, B, nq, mean, cov, meta, sc, hdr, T, track_high_thresh, track_low_thresh, new_track_thresh,
+                             match_thresh, max_time_lost, tracks, tcounts, workspace, workspace_bytes, stream);
 }

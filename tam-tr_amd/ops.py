@@ -1928,33 +1928,155 @@ def bytetrack_update(out, counts, state, capacity, track_high_thresh=0.5, track_
     a dict of device tensors mean f64 [T, 8], cov f64 [T, 8, 8], meta i32 [T, 8], sc f32 [T, 2], hdr i32 [8] with T = capacity,
     updated in place.  Returns device tensors tracks f32 [B, nq, 8] (x1 y1 x2 y2 id score cls idx, zero after the count) and
     tcounts i32 [B].  hdr[3] counts the new tracks that found no free slot.  Every check comes before the launch; no synchronisation."""
+    return _tracker_update('bytetrack_update', None, out, counts, state, capacity, track_high_thresh, track_low_thresh, new_track_thresh,
+                           match_thresh, max_time_lost, workspace)
+
+
+def botsort_update(out, counts, state, capacity, warps=None, track_high_thresh=0.5, track_low_thresh=0.1, new_track_thresh=0.6,
+                   match_thresh=0.8, max_time_lost=30, workspace=None):
+    """BOTSORT.update (trackers/bot_sort.py; with_reid off, as the reference runs it) for the B frames of a batch, in order, in one
+    launch: bytetrack_update's operands, table layout, workspace and outputs, with the XYWH filter and the frames' warps; the rule is
+    stated in csrc/track.hip.  warps f64 [B, 2, 3] on the GPU, in the pixels of `out` (gmc_estimate's output or the caller's own);
+    None = the identity for every frame.  Every check comes before the launch; no synchronisation."""
+    return _tracker_update('botsort_update', warps, out, counts, state, capacity, track_high_thresh, track_low_thresh, new_track_thresh,
+                           match_thresh, max_time_lost, workspace)
+
+
+# ------------------------------------------------------------------------------------------------ camera-motion estimate (csrc/gmc.hip)
+GMC_SLOTS = 1024
+GMC_SECTIONS = (('pyr', torch.uint8), ('lam', torch.float32), ('tilemax', torch.float32), ('kp', torch.int32), ('pts', torch.float32),
+                ('status', torch.int32), ('fit', torch.int32), ('pair', torch.int32))
+
+
+def _gmc_check_hw(H, W):
+    if H < 64 or W < 64 or H % 8 or W % 8 or H > 8192 or W > 8192:
+        raise _lib.TamtrHipError(f'gmc: frames must be at least 64 x 64 and at most 8192 x 8192 with H and W multiples of 8, got {H} x {W}')
+
+
+def gmc_workspace_bytes(B, H, W):
+    """Bytes of device workspace tamtr_gmc_estimate needs for B frames of H x W (no GPU call)."""
+    _gmc_check_hw(int(H), int(W))
+    n = _lib.lib().tamtr_gmc_workspace_bytes(int(B), int(H), int(W))
+    if n <= 0:
+        raise _lib.TamtrHipError(f'gmc: a batch of {B} frames of {H} x {W} is outside what the kernels are built for')
+    return n
+
+
+def gmc_levels(H, W):
+    """The pyramid of an H x W frame as the kernels lay it out: [(h, w, byte offset)] per level."""
+    _gmc_check_hw(int(H), int(W))
+    m, L = min(H, W) // 32, 1
+    while L < 4 and (m >> L):
+        L += 1
+    out, o = [], 0
+    for l in range(L):
+        out.append((H >> l, W >> l, o))
+        o += (H >> l) * (W >> l)
+    return out
+
+
+def gmc_state(H, W, device):
+    """A fresh persistent state for frames of H x W: the pyramid and keypoint slots of the last tracked frame, hdr[0] = valid."""
+    _gmc_check_hw(int(H), int(W))
+    n = _lib.lib().tamtr_gmc_state_bytes(int(H), int(W))
+    return {'pyr': torch.zeros(n, device=device, dtype=torch.uint8), 'kp': torch.full((GMC_SLOTS,), -1, device=device, dtype=torch.int32),
+            'hdr': torch.zeros(4, device=device, dtype=torch.int32)}
+
+
+def gmc_workspace_views(workspace, B, H, W):
+    """The sections of a gmc workspace as tensors sharing its memory (csrc/gmc.hip lists them): what each stage left, for tests."""
+    off = [_lib.lib().tamtr_gmc_workspace_offset(int(B), int(H), int(W), i) for i in range(9)]
+    P = _lib.lib().tamtr_gmc_state_bytes(int(H), int(W))
+    nt = ((H + 63) // 64) * ((W + 63) // 64)
+    shapes = {'pyr': (B, P), 'lam': (B, H, W), 'tilemax': (B, nt), 'kp': (B, GMC_SLOTS), 'pts': (B, GMC_SLOTS, 4), 'status': (B, GMC_SLOTS),
+              'fit': (B, GMC_SLOTS + 8), 'pair': (B,)}
+    out = {}
+    for i, (k, dt) in enumerate(GMC_SECTIONS):
+        n = math.prod(shapes[k]) * torch.empty(0, dtype=dt).element_size()
+        out[k] = workspace[off[i]:off[i] + n].view(dt).view(shapes[k])
+    return out
+
+
+def gmc_estimate(frames, counts, scale, state, workspace=None, stages=15):
+    """One 2x3 camera-motion warp per frame from the frames of a batch, on the device; the rule is written out in csrc/gmc.hip (it is
+    the project's own, standing where the reference runs OpenCV's sparse optical flow on the host, trackers/utils/gmc.py:247-302).
+    frames u8 [B, H, W, 3] RGB on the GPU (the network input as uploaded), counts i32 [B] on the GPU, scale [B, 2] = (w0 / W, h0 / H)
+    (any array-like; a host one goes up in one copy), state: gmc_state(H, W), updated in place.  Returns device tensors warps f64
+    [B, 2, 3] in original pixels, ready for botsort_update, and stats i32 [B, 4] (keypoints, tracked, inliers, used).  `stages` is for
+    tests (see the header).  At most four launches; every check comes before the first; no synchronisation."""
+    if not torch.is_tensor(frames) or frames.dim() != 4 or frames.shape[-1] != 3 or frames.shape[0] < 1:
+        got = tuple(frames.shape) if torch.is_tensor(frames) else type(frames).__name__
+        raise _lib.TamtrHipError(f'gmc_estimate: expected frames [B, H, W, 3], got {got}')
+    if frames.dtype != torch.uint8:
+        raise _lib.TamtrHipError(f'gmc_estimate: frames must be uint8 (the network input as uploaded), got {frames.dtype}')
+    B, H, W, _ = frames.shape
+    _gmc_check_hw(H, W)
+    if not torch.is_tensor(counts) or tuple(counts.shape) != (B,) or counts.dtype != torch.int32:
+        got = (counts.dtype, tuple(counts.shape)) if torch.is_tensor(counts) else type(counts).__name__
+        raise _lib.TamtrHipError(f'gmc_estimate: counts must be an int32 tensor [B] = [{B}], got {got}')
+    if not torch.is_tensor(scale):
+        scale = torch.as_tensor(scale, dtype=torch.float64)
+    if tuple(scale.shape) != (B, 2) or scale.dtype != torch.float64:
+        raise _lib.TamtrHipError(f'gmc_estimate: scale must be float64 [B, 2] = [{B}, 2], got {scale.dtype} {tuple(scale.shape)}')
+    need_st = _lib.lib().tamtr_gmc_state_bytes(H, W)
+    for k, dt, shape in (('pyr', torch.uint8, (need_st,)), ('kp', torch.int32, (GMC_SLOTS,)), ('hdr', torch.int32, (4,))):
+        t = state.get(k) if isinstance(state, dict) else None
+        if t is None or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            got = None if t is None else (t.dtype, tuple(t.shape))
+            raise _lib.TamtrHipError(f'gmc_estimate: state[{k!r}] must be a contiguous {dt} tensor of shape {shape} (gmc_state({H}, {W})), got {got}')
+    if int(stages) < 1 or int(stages) > 15:
+        raise _lib.TamtrHipError(f'gmc_estimate: stages must be a mask in 1 .. 15, got {stages}')
+    require_gpu(frames, counts, state['pyr'], state['kp'], state['hdr'])
+    if not scale.is_cuda:
+        scale = scale.to(frames.device, non_blocking=True)
+    need = gmc_workspace_bytes(B, H, W)
+    if workspace is None:
+        workspace = torch.empty(need, device=frames.device, dtype=torch.uint8)
+    require_gpu(workspace)
+    if workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
+        raise _lib.TamtrHipError(f'gmc_estimate: workspace must be a contiguous uint8 tensor of at least {need} bytes')
+    frames, counts, scale = _c(frames), _c(counts), _c(scale)
+    warps = torch.empty(B, 2, 3, device=frames.device, dtype=torch.float64)
+    stats = torch.empty(B, 4, device=frames.device, dtype=torch.int32)
+    call('tamtr_gmc_estimate', ptr(frames), ptr(counts), ptr(scale), B, H, W, ptr(state['pyr']), ptr(state['kp']), ptr(state['hdr']),
+         ptr(warps), ptr(stats), ptr(workspace), workspace.numel(), int(stages), stream_ptr())
+    return warps, stats
+
+
+def _tracker_update(what, warps, out, counts, state, capacity, track_high_thresh, track_low_thresh, new_track_thresh, match_thresh,
+                    max_time_lost, workspace):
     if out.dim() != 3 or out.shape[-1] != 6 or out.shape[0] < 1 or out.shape[1] < 1:
-        raise _lib.TamtrHipError(f'bytetrack_update: expected out [B, nq, 6], got {tuple(out.shape)}')
+        raise _lib.TamtrHipError(f'{what}: expected out [B, nq, 6], got {tuple(out.shape)}')
     B, nq, _ = out.shape
     if tuple(counts.shape) != (B,):
-        raise _lib.TamtrHipError(f'bytetrack_update: counts must be [B] = [{B}], got {tuple(counts.shape)}')
+        raise _lib.TamtrHipError(f'{what}: counts must be [B] = [{B}], got {tuple(counts.shape)}')
     if out.dtype != torch.float32 or counts.dtype != torch.int32:
-        raise _lib.TamtrHipError(f'bytetrack_update: out must be float32 and counts int32, got {out.dtype} and {counts.dtype}')
+        raise _lib.TamtrHipError(f'{what}: out must be float32 and counts int32, got {out.dtype} and {counts.dtype}')
     T = int(capacity)
     if T < 1:
-        raise _lib.TamtrHipError(f'bytetrack_update: capacity must be positive, got {capacity}')
+        raise _lib.TamtrHipError(f'{what}: capacity must be positive, got {capacity}')
     for k, dt, tail in TRACK_STATE_SPEC + (('hdr', torch.int32, None),):
         t = state.get(k) if isinstance(state, dict) else None
         want = (8,) if tail is None else (T,) + tail
         if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
             got = None if t is None else (t.dtype, tuple(t.shape))
-            raise _lib.TamtrHipError(f'bytetrack_update: state[{k!r}] must be a contiguous {dt} tensor of shape {want} (capacity {T}), got {got}')
-    require_gpu(out, counts, *(state[k] for k in ('mean', 'cov', 'meta', 'sc', 'hdr')))
+            raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want} (capacity {T}), got {got}')
+    if warps is not None and (not torch.is_tensor(warps) or tuple(warps.shape) != (B, 2, 3) or warps.dtype != torch.float64):
+        got = (warps.dtype, tuple(warps.shape)) if torch.is_tensor(warps) else type(warps).__name__
+        raise _lib.TamtrHipError(f'{what}: warps must be a float64 tensor [B, 2, 3] = [{B}, 2, 3], got {got}')
+    require_gpu(out, counts, warps, *(state[k] for k in ('mean', 'cov', 'meta', 'sc', 'hdr')))
+    warps = _c(warps) if warps is not None else None
     need = bytetrack_workspace_bytes(T, nq)
     if workspace is None:
         workspace = torch.empty(need, device=out.device, dtype=torch.uint8)
     require_gpu(workspace)
     if workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
-        raise _lib.TamtrHipError(f'bytetrack_update: workspace must be a contiguous uint8 tensor of at least {need} bytes')
+        raise _lib.TamtrHipError(f'{what}: workspace must be a contiguous uint8 tensor of at least {need} bytes')
     out, counts = _c(out), _c(counts)
     tracks = torch.empty(B, nq, 8, device=out.device, dtype=torch.float32)
     tcounts = torch.empty(B, device=out.device, dtype=torch.int32)
-    call('tamtr_bytetrack_update', ptr(out), ptr(counts), B, nq, ptr(state['mean']), ptr(state['cov']), ptr(state['meta']), ptr(state['sc']),
+    args = (ptr(out), ptr(counts)) + ((ptr(warps) if warps is not None else None,) if what == 'botsort_update' else ())
+    call('tamtr_' + what, *args, B, nq, ptr(state['mean']), ptr(state['cov']), ptr(state['meta']), ptr(state['sc']),
          ptr(state['hdr']), T, float(track_high_thresh), float(track_low_thresh), float(new_track_thresh), float(match_thresh),
          int(max_time_lost), ptr(tracks), ptr(tcounts), ptr(workspace), int(workspace.numel()), stream_ptr())
     return tracks, tcounts

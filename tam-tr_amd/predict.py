@@ -67,12 +67,14 @@ def load_image(path, imgsz):
     return im, letterbox_scalefill(im, imgsz)
 
 
-def to_model_input(ims_u8, device):
-    """u8 [B, S, S, 3] host batch -> f32 [B, 3, S, S] / 255 on the device (engine/predictor.py:111-129: RGB, CHW, float, / 255)."""
+def to_model_input(ims_u8, device, keep_u8=False):
+    """u8 [B, S, S, 3] host batch -> f32 [B, 3, S, S] / 255 on the device (engine/predictor.py:111-129: RGB, CHW, float, / 255).
+    keep_u8: -> (that, the u8 batch as it was uploaded), which BoT-SORT's camera-motion estimate reads."""
     t = torch.from_numpy(ims_u8)
     if device.type == 'cuda':
         t = t.pin_memory().to(device, non_blocking=True)
-    return t.permute(0, 3, 1, 2).contiguous().float() / 255
+    x = t.permute(0, 3, 1, 2).contiguous().float() / 255
+    return (x, t) if keep_u8 else x
 
 
 # ------------------------------------------------------------------------------------------------ results
@@ -187,14 +189,15 @@ class Predictor:
     @torch.no_grad()
     def run_batch(self, ims, tracker=None, gt_frames=None, evaluator=None):
         """Network inputs u8 [B, S, S, 3] (host) + original (h, w) per image -> host (out [B, nq, 6], keep [B, nq], counts [B]).
-        With a tracker (track.ByteTracker) the batch's frames also go through one tracker launch, and its rows ride in the same copy:
+        With a tracker (track.ByteTracker or track.BotSort) the batch's frames also go through one tracker launch, and its rows ride in the same copy:
         -> host (out, keep, counts, tracks [B, nq, 8], tcounts [B]).  With gt_frames (B host arrays [m, 7]) and an evaluator
         (track.MotEvaluator or track.HotaEvaluator, or a list of them) as well, one more launch per evaluator scores the tracker's rows
         where they lie; each evaluator's header rides in the same copy and its time goes under its own key of times ('mot', 'hota')."""
         arr, hw = ims
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
         ev[0].record()
-        img = to_model_input(arr, self.device)
+        gmc = getattr(tracker, 'gmc_method', None) == 'sparseOptFlow'      # a track.BotSort that estimates its warps from the frames
+        img, u8 = to_model_input(arr, self.device, keep_u8=True)
         ev[1].record()
         with torch.autocast('cuda', dtype=self.autocast_dtype or torch.bfloat16, enabled=self.autocast_dtype is not None):
             preds = self.model(img)
@@ -208,8 +211,16 @@ class Predictor:
         evaluators = list(evaluator) if isinstance(evaluator, (list, tuple)) else [] if evaluator is None else [evaluator]
         scoring = tracker is not None and bool(evaluators) and gt_frames is not None
         ev_eval = []
+        ev_gmc = None
         if tracker is not None:
-            tracks, tcounts = tracker.update(out, counts)
+            if gmc:      # the warps stay on the device; the tracker launch reads them there
+                H, W = float(arr.shape[1]), float(arr.shape[2])
+                warps = tracker.estimate_warps(u8, counts, [[w0 / W, h0 / H] for h0, w0 in np.asarray(hw).reshape(-1, 2).tolist()])
+                ev_gmc = torch.cuda.Event(enable_timing=True)
+                ev_gmc.record()
+                tracks, tcounts = tracker.update(out, counts, warps=warps)
+            else:
+                tracks, tcounts = tracker.update(out, counts)
             parts += [tracks.view(-1), tcounts.view(torch.float32), tracker.state['hdr'].view(torch.float32)]
             for e in evaluators if scoring else []:
                 ev_eval.append(torch.cuda.Event(enable_timing=True))
@@ -222,7 +233,8 @@ class Predictor:
         host.copy_(packed, non_blocking=True)
         ev[5].record()
         ev[5].synchronize()
-        spans = [('h2d', ev[0], ev[1]), ('forward', ev[1], ev[2]), ('postprocess', ev[2], ev[3]), ('track', ev[3], (ev_eval + [ev[4]])[0]), ('d2h', ev[4], ev[5])]
+        spans = [('h2d', ev[0], ev[1]), ('forward', ev[1], ev[2]), ('postprocess', ev[2], ev[3]), ('track', ev_gmc or ev[3], (ev_eval + [ev[4]])[0]),
+                 ('d2h', ev[4], ev[5])] + ([('gmc', ev[3], ev_gmc)] if ev_gmc is not None else [])
         for i, e in enumerate(evaluators if scoring else []):
             spans.append((e.times_key, ev_eval[i], (ev_eval + [ev[4]])[i + 1]))
         for k, a, b in spans:
@@ -247,24 +259,28 @@ class Predictor:
         """The sorted files of `source` as ONE sequence (the reference's model.track): the batches of predict, then one tracker launch
         per batch.  Yields one Detections per frame whose boxes are the track rows (x1 y1 x2 y2 from the filter, score, cls) and
         whose `id` holds the track ids; a frame for which the tracker returned nothing keeps its plain detections and id None
-        (trackers/track.py:46-50).  tracker: a track.ByteTracker, a bytetrack.yaml path, or None for the defaults; persist=True keeps
-        the tracker (and its tracks) of the previous call.
+        (trackers/track.py:46-50).  tracker: a track.ByteTracker or track.BotSort, a bytetrack.yaml or botsort.yaml path
+        (track.tracker_from_yaml), or None for ByteTrack's defaults; persist=True keeps the tracker (and its tracks) of the previous
+        call.  A BotSort estimates its camera-motion warps from the uploaded frames of each batch (unless its gmc_method is none), and
+        speed() then has a 'gmc' entry for those launches.
         gt + evaluator: the sequence's ground truth, one array [m, 7] (x1 y1 x2 y2 id cls kind, track.read_mot) per frame in file order
         (missing frames are empty), and a track.MotEvaluator or track.HotaEvaluator, or a list / tuple of them: every batch's rows are
         scored on the device right after the tracker's launch, by each evaluator in turn (a frame without track rows is an empty
         track set, as write_mot has it), the sequence is ended after the last frame, and speed() has an entry per evaluator ('mot',
         'hota'); each evaluator's results() then holds the metrics.  Without both, nothing changes."""
-        from .track import ByteTracker
+        from .track import ByteTracker, tracker_from_yaml
         if isinstance(tracker, ByteTracker):
             self.tracker = tracker
             if not persist:
                 tracker.reset()
         elif self.tracker is None or not persist:
-            self.tracker = ByteTracker.from_yaml(tracker, self.device) if tracker else ByteTracker(self.device)
+            self.tracker = tracker_from_yaml(tracker, self.device) if tracker else ByteTracker(self.device)
         files = list_sources(source)
         evaluators = list(evaluator) if isinstance(evaluator, (list, tuple)) else [] if evaluator is None else [evaluator]
         for k in {'mot', 'hota'} - ({e.times_key for e in evaluators} if gt is not None else set()):
             self.times.pop(k, None)          # an evaluator's key exists only while a run is scored by it
+        if getattr(self.tracker, 'gmc_method', None) != 'sparseOptFlow':
+            self.times.pop('gmc', None)      # and the estimator's only while a BotSort run is in progress
         if gt is None or not evaluators:
             yield from self._run(files, self.tracker)
             return

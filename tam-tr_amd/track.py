@@ -7,6 +7,15 @@ utils/kalman_filter.py, utils/matching.py, cfg/trackers/bytetrack.yaml): one HIP
 
 `Predictor.track(source)` (predict.py) drives it and yields Detections with ids; tools/track.py is the command line.
 
+BotSort is the reference's other tracker (trackers/bot_sort.py, cfg/trackers/botsort.yaml) on the same table and launch: the XYWH
+filter and one camera-motion warp per frame applied to the track states.  The warps are estimated on the device from the frames of
+the batch (csrc/gmc.hip states that rule, which is the project's own), or come from the caller:
+
+    tracker = BotSort(device)                           # or tracker_from_yaml('botsort.yaml', device)
+    tracks, tcounts = tracker.update(out, counts, frames=u8, scale=s)   # u8 [B, H, W, 3] on the device, s [B, 2] = (w0 / W, h0 / H)
+    tracks, tcounts = tracker.update(out, counts, warps=w)      # w f64 [B, 2, 3] in original pixels, device or host
+    tracks, tcounts = tracker.update(out, counts)               # identity warps (the reference without an image)
+
 MOT evaluation next to it (CLEAR-MOT and identity metrics; the rule is written out in csrc/mot.hip, engine.mot_evaluate states it in
 numpy): one more launch per batch on the rows the tracker left on the device, one launch per sequence for the reduction.
 
@@ -43,7 +52,8 @@ class HotaOverflow(RuntimeError):
 
 
 def read_tracker_yaml(path):
-    """The keys of the reference's cfg/trackers/bytetrack.yaml -> constructor arguments.  Only `tracker_type: bytetrack` is built."""
+    """The keys of the reference's cfg/trackers/bytetrack.yaml -> ByteTracker's constructor arguments; any other tracker_type raises.
+    tracker_from_yaml reads either of the reference's tracker files and builds ByteTracker or BotSort."""
     import yaml
     with open(path) as f:
         cfg = yaml.safe_load(f) or {}
@@ -84,12 +94,16 @@ class ByteTracker:
         self.state['meta'].zero_()
         self.state['hdr'].copy_(self._fresh_hdr)
 
-    def update(self, out, counts):
-        """out f32 [B, nq, 6], counts i32 [B] on the device (ops.detect_postprocess) -> tracks f32 [B, nq, 8] (x1 y1 x2 y2 id score
-        cls idx, zero after the count), tcounts i32 [B], on the device.  The B frames are consumed in order in one launch."""
+    def _grow(self, out):
+        """A batch with more rows per frame than the workspace was sized for gets a larger workspace."""
         if out.dim() == 3 and out.shape[1] > self.nq:
             self.nq = out.shape[1]
             self.workspace = torch.empty(ops.bytetrack_workspace_bytes(self.capacity, self.nq), device=self.device, dtype=torch.uint8)
+
+    def update(self, out, counts):
+        """out f32 [B, nq, 6], counts i32 [B] on the device (ops.detect_postprocess) -> tracks f32 [B, nq, 8] (x1 y1 x2 y2 id score
+        cls idx, zero after the count), tcounts i32 [B], on the device.  The B frames are consumed in order in one launch."""
+        self._grow(out)
         return ops.bytetrack_update(out, counts, self.state, self.capacity, self.track_high_thresh, self.track_low_thresh,
                                     self.new_track_thresh, self.match_thresh, self.max_time_lost, self.workspace)
 
@@ -111,6 +125,108 @@ class ByteTracker:
                 raise ValueError(f'state {k!r} has shape {a.shape}, this tracker (capacity {self.capacity}) needs {tuple(v.shape)}')
             v.copy_(torch.from_numpy(np.ascontiguousarray(a)).to(v.dtype))
         self.check_overflow(np.asarray(sd['hdr'])[HDR_OVERFLOW])
+
+
+BOTSORT_YAML_KEYS = YAML_KEYS + ('gmc_method', 'proximity_thresh', 'appearance_thresh', 'with_reid')
+GMC_BUILT = ('sparseOptFlow', 'none')      # what `gmc_method` may name; the reference's orb, sift and ecc (utils/gmc.py) are not built
+
+
+class BotSort(ByteTracker):
+    """BoT-SORT on the device (the reference's trackers/bot_sort.py, cfg/trackers/botsort.yaml): ByteTracker's table, launch and
+    methods with the XYWH Kalman filter, `vw = vh = 0` before a lost track is predicted, and each frame's 2x3 camera-motion warp
+    applied to the track states between the prediction and the first association (csrc/track.hip states the rule; it is pinned to
+    the reference's BOTSORT by tests/golden/botsort.npz).
+
+    gmc_method 'sparseOptFlow' (the default, as in botsort.yaml) estimates the warps on the device from the frames handed to
+    update(): grid keypoints, pyramidal Lucas-Kanade and a similarity fit, at most four launches (csrc/gmc.hip writes the rule out;
+    it is the project's own, not OpenCV's, whose role it takes).  The estimator keeps the previous tracked frame on the device
+    across batches; reset() forgets it.  'none' (or None) never estimates: every warp is the identity unless update() is given
+    warps.  'orb', 'sift' and 'ecc' raise ValueError.
+    proximity_thresh and appearance_thresh gate ReID embeddings, which the reference itself does not build ("Haven't supported
+    BoT-SORT(reid) yet"): with with_reid off its get_dists is ByteTrack's fused IoU distance, so the constructor accepts and keeps
+    the two thresholds and the kernel does not read them.  with_reid=True raises."""
+
+    def __init__(self, device, gmc_method='sparseOptFlow', proximity_thresh=0.5, appearance_thresh=0.25, with_reid=False, **kw):
+        method = 'none' if gmc_method is None else str(gmc_method)
+        if method not in GMC_BUILT:
+            raise ValueError(f"gmc_method {gmc_method!r} is not built: 'sparseOptFlow' (estimated on the device) and 'none' are; the "
+                             "reference's orb, sift and ecc run OpenCV on the host")
+        if with_reid:
+            raise ValueError('with_reid=True is not built: the reference has no ReID encoder for BoT-SORT either')
+        self.gmc_method, self.with_reid = method, False
+        self.proximity_thresh, self.appearance_thresh = float(proximity_thresh), float(appearance_thresh)
+        self.last_warps = self.last_stats = None
+        self.gmc, self.gmc_hw, self.gmc_workspace = None, None, None      # the estimator's state, made for the first frames' size
+        super().__init__(device, **kw)
+
+    def reset(self):
+        """Forget every track and the estimator's previous frame.  No synchronisation."""
+        super().reset()
+        if self.gmc is not None:
+            self.gmc['hdr'].zero_()
+
+    def estimate_warps(self, frames, counts, scale=None):
+        """frames u8 [B, H, W, 3] on the device (the network input as uploaded), counts i32 [B], scale [B, 2] = (w0 / W, h0 / H) or
+        None for ones -> warps f64 [B, 2, 3] on the device (ops.gmc_estimate); last_stats keeps i32 [B, 4] (keypoints, tracked,
+        inliers, used).  Frames of another size than the last start a new sequence for the estimator."""
+        B, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        if self.gmc_hw != (H, W):
+            self.gmc, self.gmc_hw = ops.gmc_state(H, W, self.device), (H, W)
+        need = ops.gmc_workspace_bytes(B, H, W)
+        if self.gmc_workspace is None or self.gmc_workspace.numel() < need:
+            self.gmc_workspace = torch.empty(need, device=self.device, dtype=torch.uint8)
+        if scale is None:
+            scale = np.ones((B, 2))
+        warps, self.last_stats = ops.gmc_estimate(frames, counts, scale, self.gmc, self.gmc_workspace)
+        return warps
+
+    def update(self, out, counts, frames=None, scale=None, warps=None):
+        """As ByteTracker.update.  With `frames` (and gmc_method 'sparseOptFlow') the warps are estimated first (estimate_warps) and
+        read by the tracker launch where they lie; with `warps` (f64 [B, 2, 3], device tensor, host tensor or array; a host one goes
+        up in one copy) nothing is estimated; with neither every warp is the identity, as in the reference when no image is given.
+        The warp of a frame without detections is not applied.  last_warps keeps the device tensor."""
+        self._grow(out)
+        if warps is None and frames is not None and self.gmc_method == 'sparseOptFlow':
+            warps = self.estimate_warps(frames, counts, scale)
+        elif warps is not None and not (torch.is_tensor(warps) and warps.is_cuda):
+            warps = torch.as_tensor(np.asarray(warps, np.float64)).to(self.device, non_blocking=True)
+        self.last_warps = warps
+        return ops.botsort_update(out, counts, self.state, self.capacity, warps, self.track_high_thresh, self.track_low_thresh,
+                                  self.new_track_thresh, self.match_thresh, self.max_time_lost, self.workspace)
+
+    def state_dict(self):
+        """ByteTracker's table plus the estimator's state (gmc_pyr, gmc_kp, gmc_hdr, gmc_hw) once it exists (synchronises)."""
+        sd = super().state_dict()
+        if self.gmc is not None:
+            sd.update({'gmc_' + k: v.cpu().numpy().copy() for k, v in self.gmc.items()})
+            sd['gmc_hw'] = np.asarray(self.gmc_hw, np.int64)
+        return sd
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        self.gmc, self.gmc_hw = None, None
+        if 'gmc_hw' in sd:
+            H, W = (int(v) for v in np.asarray(sd['gmc_hw']))
+            self.gmc, self.gmc_hw = ops.gmc_state(H, W, self.device), (H, W)
+            for k, v in self.gmc.items():
+                a = np.asarray(sd['gmc_' + k])
+                if a.shape != tuple(v.shape):
+                    raise ValueError(f'state gmc_{k} has shape {a.shape}, frames of {H} x {W} need {tuple(v.shape)}')
+                v.copy_(torch.from_numpy(np.ascontiguousarray(a)).to(v.dtype))
+
+
+def tracker_from_yaml(path, device, **kw):
+    """A tracker yaml with the reference's keys (cfg/trackers/bytetrack.yaml or botsort.yaml) -> ByteTracker or BotSort, by its
+    `tracker_type`; keyword arguments override the file (e.g. gmc_method='none')."""
+    import yaml
+    with open(path) as f:
+        cfg = yaml.safe_load(f) or {}
+    kind = cfg.get('tracker_type', 'bytetrack')
+    if kind == 'bytetrack':      # which has no use for a gmc_method
+        return ByteTracker(device, **{**{k: cfg[k] for k in YAML_KEYS if k in cfg}, **{k: v for k, v in kw.items() if k != 'gmc_method'}})
+    if kind == 'botsort':
+        return BotSort(device, **{**{k: cfg[k] for k in BOTSORT_YAML_KEYS if k in cfg}, **kw})
+    raise ValueError(f"tracker_type {kind!r} is not supported: 'bytetrack' and 'botsort' are built")
 
 
 def write_mot(path, frames):

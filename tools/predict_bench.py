@@ -10,7 +10,13 @@
   (c) --track: the tracker on a seeded synthetic sequence (tests/bytetrack_np.make_scene), per frame: the device path (one
       tamtr_bytetrack_update launch per batch of 4 frames, device events) against a host path on the same detections - one
       device-to-host copy of the batch's detections plus the numpy twin tests/bytetrack_np.py per frame (host clock).  The host side
-      is numpy with scipy's assignment, NOT the reference's tracker with `lap`.
+      is numpy with scipy's assignment, NOT the reference's tracker with `lap`.  With --botsort as well: the same scene seen by a
+      panning camera (tests/botsort_np.camera_path), the camera's warps on the device, one tamtr_botsort_update launch per batch
+      against the twin tests/botsort_np.py.
+  (c') --gmc: BoT-SORT with its camera-motion estimate on a seeded 640 x 640 sequence (tests/gmc_np.make_frames, 8 frames, batches of
+      4, 60 boxes that sit in the scene): the estimate's launches (csrc/gmc.hip) and the tracker launch that reads their warps, device
+      events around each, median and 10th / 90th percentile over repeated passes after a warm-up pass, per frame; against a host path
+      that makes one copy of the batch and runs the numpy statements tests/gmc_np.py (in fp32) and tests/botsort_np.py (host clock).
 
   (d) --mot: the MOT evaluation on a seeded synthetic sequence (200 frames, about 100 ground-truth rows per frame, 300 ground-truth
       ids, 600 track ids, nq = 300, batches of 4): the update launch per batch and the end-of-sequence launch (device events around
@@ -20,7 +26,7 @@
   (e) --hota: the HOTA launches on the same sequence, the same way: the update launch per batch next to the MOT update launch, the
       three end-of-sequence launches, and the host path (the batches' copies plus engine.hota_evaluate).
 
-    python tools/predict_bench.py [--images 64] [--kernel-only] [--track] [--mot] [--hota]
+    python tools/predict_bench.py [--images 64] [--kernel-only] [--track [--botsort]] [--gmc] [--mot] [--hota]
 --kernel-only runs only the kernel loop of (a), for a `rocprofv3 --kernel-trace --stats` run of its own.
 """
 import argparse
@@ -150,23 +156,28 @@ def bench_predictor(n_images, batches, conf=1e-5):
     return rows
 
 
-def bench_track(n_obj, frames=240, B=4, nq=300, capacity=1024):
+def bench_track(n_obj, frames=240, B=4, nq=300, capacity=1024, botsort=False):
     """-> one row: ms per frame of the tracker launch (device events) and of the host path (copy + numpy twin, host clock)."""
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
     import bytetrack_np as T
-    from tamtr_amd.track import ByteTracker
+    import botsort_np as BS
+    from tamtr_amd.track import BotSort, ByteTracker
     scene = T.make_scene(1, n_obj=n_obj, frames=frames, fp_every=3, gaps=[(o, 20 + 7 * o, 5 + 10 * (o % 4)) for o in range(min(n_obj, 8))])
+    if botsort:
+        warps = BS.camera_path(1, frames, jumps={frames // 2: (40.0, 25.0)})
+        scene = BS.through_camera(scene, warps)
+        warps_d = torch.from_numpy(warps).cuda()
     out = np.zeros((frames, nq, 6), np.float32)
     for i, f in enumerate(scene):
         out[i, :len(f)] = f
     out_d = torch.from_numpy(out).cuda()
     cnt_d = torch.tensor([len(f) for f in scene], dtype=torch.int32).cuda()
-    trk = ByteTracker('cuda', capacity=capacity, nq=nq)
+    trk = (BotSort if botsort else ByteTracker)('cuda', capacity=capacity, nq=nq)
 
     def device_pass():
         trk.reset()
         for i in range(0, frames, B):
-            res = trk.update(out_d[i:i + B], cnt_d[i:i + B])
+            res = trk.update(out_d[i:i + B], cnt_d[i:i + B], warps=warps_d[i:i + B]) if botsort else trk.update(out_d[i:i + B], cnt_d[i:i + B])
         return res
 
     t_dev, n_dev = timed(device_pass, min_s=1.0, warmup=2, chunk=2)
@@ -174,12 +185,12 @@ def bench_track(n_obj, frames=240, B=4, nq=300, capacity=1024):
     trk.check_overflow(sd['hdr'][3])
 
     def host_pass():
-        twin = T.ByteTrackNp(capacity=capacity)
+        twin = BS.BotSortNp(capacity=capacity) if botsort else T.ByteTrackNp(capacity=capacity)
         rows = 0
         for i in range(0, frames, B):
             o, c = out_d[i:i + B].cpu().numpy(), cnt_d[i:i + B].cpu().numpy()      # the copy the reference makes per frame, here per batch
             for b in range(len(c)):
-                rows += len(twin.update(o[b, :c[b]]))
+                rows += len(twin.update(o[b, :c[b]], warps[i + b]) if botsort else twin.update(o[b, :c[b]]))
         return twin, rows
 
     host_pass()
@@ -187,10 +198,64 @@ def bench_track(n_obj, frames=240, B=4, nq=300, capacity=1024):
     twin, rows = host_pass()
     t_host = (time.perf_counter() - t0) * 1e3
     assert np.array_equal(sd['hdr'], twin.state['hdr']), (sd['hdr'], twin.state['hdr'])     # the two paths tracked the same thing
-    return {'objects': n_obj, 'frames': frames, 'frames_per_launch': B, 'nq': nq, 'capacity': capacity,
+    return {'tracker': 'botsort' if botsort else 'bytetrack', 'objects': n_obj, 'frames': frames, 'frames_per_launch': B, 'nq': nq, 'capacity': capacity,
             'detections_per_frame': round(float(np.mean([len(f) for f in scene])), 1), 'track_rows': rows, 'ids': int(sd['hdr'][1]) - 1,
             'device_launch_ms_per_frame': round(t_dev / frames, 4), 'host_copy_plus_numpy_twin_ms_per_frame': round(t_host / frames, 3),
             'device_passes_timed': n_dev}
+
+
+def bench_gmc(frames=8, S=640, B=4, nq=300, n_obj=60, repeats=7):
+    """-> one row: ms per frame of the camera-motion estimate's launches and of the BoT-SORT tracker launch that reads its warps
+    (device events, median and 10th / 90th percentile over `repeats` passes after one warm-up pass), and of a host path that makes
+    one copy of the batch and runs the numpy statements (tests/gmc_np.py, tests/botsort_np.py; host clock, one pass)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+    import botsort_np as BS
+    import gmc_np as G
+    from tamtr_amd.track import BotSort
+    imgs, truth = G.make_frames(1, S, frames, G.random_motions(2, frames - 1, S=S))
+    rng = np.random.default_rng(3)
+    pos, dets = rng.uniform(60, S - 100, (n_obj, 2)), []
+    for t in range(frames):      # boxes that sit in the scene: they move as the camera's warp says
+        pos = pos @ truth[t][:, :2].T + truth[t][:, 2]
+        dets.append(np.concatenate([pos, pos + 24, np.full((n_obj, 1), 0.9), np.zeros((n_obj, 1))], 1).astype(np.float32))
+    out = np.zeros((frames, nq, 6), np.float32)
+    out[:, :n_obj] = np.stack(dets)
+    out_d, cnt_d = torch.from_numpy(out).cuda(), torch.full((frames,), n_obj, dtype=torch.int32).cuda()
+    fr_d, scale = torch.from_numpy(imgs).cuda(), torch.ones(frames, 2, dtype=torch.float64).cuda()
+    trk = BotSort('cuda', nq=nq)
+    pct = lambda v: [round(float(np.percentile(v, q)) / B, 4) for q in (50, 10, 90)]   # noqa: E731  per frame
+    event = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
+    gmc, track = [], []
+    for rep in range(repeats + 1):
+        trk.reset()
+        evs = []
+        for i in range(0, frames, B):
+            e = [event(), event(), event()]
+            e[0].record()
+            w = trk.estimate_warps(fr_d[i:i + B], cnt_d[i:i + B], scale[i:i + B])
+            e[1].record()
+            trk.update(out_d[i:i + B], cnt_d[i:i + B], warps=w)
+            e[2].record()
+            evs.append(e)
+        torch.cuda.synchronize()
+        if rep:      # the first pass is the warm-up
+            gmc += [e[0].elapsed_time(e[1]) for e in evs]
+            track += [e[1].elapsed_time(e[2]) for e in evs]
+    sd = trk.state_dict()
+    t0 = time.perf_counter()
+    est, twin, errs = G.GmcNp(np.float32), BS.BotSortNp(capacity=1024), []
+    for i in range(0, frames, B):
+        f, o, c = fr_d[i:i + B].cpu().numpy(), out_d[i:i + B].cpu().numpy(), cnt_d[i:i + B].cpu().numpy()      # one copy of the batch
+        w, _ = est.estimate(f, c)
+        for b in range(len(c)):
+            twin.update(o[b, :c[b]], w[b])
+            errs.append(G.corner_error(w[b], truth[i + b], S, S))
+    t_host = (time.perf_counter() - t0) * 1e3
+    return {'frames': frames, 'size': S, 'same_tracker_header_on_both_paths': bool(np.array_equal(sd['hdr'], twin.state['hdr'])), 'frames_per_launch': B, 'detections_per_frame': n_obj, 'ids': int(sd['hdr'][1]) - 1,
+            'last_batch_stats_keypoints_tracked_inliers_used': trk.last_stats.cpu().tolist(),
+            'twin_corner_error_px_max': round(max(errs), 3),
+            'gmc_launches_ms_per_frame_p50_p10_p90': pct(gmc), 'botsort_launch_ms_per_frame_p50_p10_p90': pct(track),
+            'host_copy_plus_numpy_twins_ms_per_frame': round(t_host / frames, 1), 'passes_timed': repeats}
 
 
 def mot_scene(frames=200, n_obj=300, nc=10, seed=2):
@@ -364,6 +429,8 @@ def main():
     ap.add_argument('--images', type=int, default=64)
     ap.add_argument('--kernel-only', action='store_true')
     ap.add_argument('--track', action='store_true', help='only (c): the tracker launch against copy + numpy twin')
+    ap.add_argument('--botsort', action='store_true', help='with --track: the BoT-SORT form of the launch, with warps on the device')
+    ap.add_argument('--gmc', action='store_true', help="only (c'): BoT-SORT's camera-motion estimate and tracker launch on a 640 x 640 sequence")
     ap.add_argument('--mot', action='store_true', help='only (d): the MOT evaluation launches against copy + numpy twin')
     ap.add_argument('--hota', action='store_true', help='only (e): the HOTA launches against copy + numpy twin, on the sequence of --mot')
     args = ap.parse_args()
@@ -373,7 +440,12 @@ def main():
     if args.track:
         print('(c) tracker per frame: one launch per 4 frames (device events) vs device-to-host copy + numpy twin (host clock; numpy and scipy, not the reference with lap)')
         for n_obj in (24, 100):
-            print(json.dumps(bench_track(n_obj)))
+            print(json.dumps(bench_track(n_obj, botsort=args.botsort)))
+        return
+    if args.gmc:
+        print("(c') BoT-SORT with camera-motion compensation, per frame: the estimate's launches and the tracker launch per 4 frames (device events) vs one "
+              'copy of the batch + the numpy statements (host clock)')
+        print(json.dumps(bench_gmc()))
         return
     if args.mot:
         print('(d) MOT evaluation: update launch per batch of 4 frames and end-of-sequence launch (device events) vs device-to-host copy + numpy twin (host clock)')

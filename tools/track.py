@@ -1,16 +1,19 @@
 #!/usr/bin/env python3
-"""Track objects through image sequences (the reference's model.track flow with ByteTrack): per frame the boxes of the confirmed
+"""Track objects through image sequences (the reference's model.track flow with ByteTrack or BoT-SORT): per frame the boxes of the confirmed
 tracks with their ids; optional annotated copies, YOLO-format label files with the id appended, and one VisDrone-MOT result file per
 sequence, under an incremented --project/--name folder; one JSON line at the end.  With --gt the tracks are scored on the device
 as they are made (CLEAR-MOT and identity metrics, tam-tr_amd/csrc/mot.hip): a table per sequence and over all, and mot_metrics.json;
 --hota scores them by HOTA as well (tam-tr_amd/csrc/hota.hip): its tables next to the others and a `hota` key in mot_metrics.json.
 
     python tools/track.py --weights runs/train/TAMTR/best.pt --text-feats clip_vitb32.npz --data dataset.yaml \
-        --source sequences/ [--tracker bytetrack.yaml] --conf 0.1 --batch 4 --save-mot [--save --save-txt --save-conf] [--gt annotations/]
+        --source sequences/ [--tracker bytetrack.yaml | --tracker botsort.yaml [--gmc none]] --conf 0.1 --batch 4 --save-mot [--save --save-txt --save-conf] [--gt annotations/]
 
 --source is a directory of frames (one sequence, frames in sorted order) or a directory of sequence directories (the VisDrone-MOT
 `sequences/<name>/` layout); the tracker is reset for every sequence.  --save-mot writes <save_dir>/<sequence>.txt with lines
-`frame,id,left,top,width,height,score,category,-1,-1`, frames 1-based.  Only `tracker_type: bytetrack` is built.
+`frame,id,left,top,width,height,score,category,-1,-1`, frames 1-based.  --tracker takes the reference's bytetrack.yaml or botsort.yaml (track.tracker_from_yaml); BoT-SORT runs on
+the device as well: the tracker rule (XYWH filter, warped track states) in the tracker launch, and the camera-motion warps
+(gmc_method: sparseOptFlow, the reference's default) estimated from each batch's uploaded frames in at most four more launches
+(tam-tr_amd/csrc/gmc.hip).  --gmc overrides the yaml's gmc_method: `none` runs identity warps.
 --gt is a directory of VisDrone-MOT annotation files <sequence>.txt (track.read_mot states how categories become classes and kinds);
 a sequence without a file there is tracked but not scored.
 """
@@ -34,7 +37,10 @@ def parse_args(argv=None):
     g.add_argument('--data', help="dataset yaml whose 'names' are the classes")
     g.add_argument('--names', help='comma-separated class names')
     ap.add_argument('--source', required=True, help='a directory of frames, or a directory of sequence directories')
-    ap.add_argument('--tracker', help="tracker yaml with the reference's keys (cfg/trackers/bytetrack.yaml); default: its values")
+    ap.add_argument('--tracker', help="tracker yaml with the reference's keys (cfg/trackers/bytetrack.yaml or botsort.yaml); default: "
+                    "bytetrack.yaml's values")
+    ap.add_argument('--gmc', choices=['sparseOptFlow', 'none'], help="with a botsort.yaml: override its gmc_method (sparseOptFlow = warps "
+                    "estimated on the device from the frames, none = identity warps)")
     ap.add_argument('--capacity', type=int, default=1024, help='tracks the device table holds')
     ap.add_argument('--imgsz', type=int, default=640)
     ap.add_argument('--batch', type=int, default=4)
@@ -80,7 +86,7 @@ def main(argv=None):
     from tamtr_amd.model import RTDETRDetectionWorldModel
     from tamtr_amd.predict import Predictor, increment_path, is_image_file
     from tamtr_amd import engine
-    from tamtr_amd.track import ByteTracker, HotaEvaluator, MotEvaluator, read_mot, write_mot
+    from tamtr_amd.track import ByteTracker, HotaEvaluator, MotEvaluator, read_mot, tracker_from_yaml, write_mot
     from predict import load_names
 
     dev = torch.device('cuda', 0)
@@ -90,7 +96,10 @@ def main(argv=None):
     model.load_state_dict(ck['model' if args.raw else 'ema'])
     pred = Predictor(model, names, D.TextFeatures.from_args(args.text_feats, args.clip_weights, args.clip_vocab, dev), imgsz=args.imgsz, conf=args.conf,
                      iou=args.iou, classes=args.classes, single_cls=args.single_cls, batch=args.batch, dtype=args.dtype)
-    tracker = ByteTracker.from_yaml(args.tracker, dev, capacity=args.capacity) if args.tracker else ByteTracker(dev, capacity=args.capacity)
+    if args.tracker:
+        tracker = tracker_from_yaml(args.tracker, dev, capacity=args.capacity, **({'gmc_method': args.gmc} if args.gmc else {}))
+    else:
+        tracker = ByteTracker(dev, capacity=args.capacity)
     save_dir = increment_path(os.path.join(args.project, args.name), exist_ok=args.exist_ok)
     saving = args.save or args.save_txt or args.save_mot or bool(args.gt)
     evaluator = MotEvaluator(dev, len(names), iou=args.mot_iou) if args.gt else None
