@@ -727,13 +727,48 @@ int tamtr_bytetrack_workspace_bytes(int T, int nq);
  *      velocities), mean[6] = mean[7] = 0 before a track that is not Tracked is predicted, and the frame's warp applied to every pool
  *      and every unconfirmed track between the prediction and the first association (csrc/track.hip states all three).
  *      warps f64 [B, 2, 3], row-major, in the pixels of `out`, on the device, 8-byte aligned (else TAMTR_EINVAL); NULL = the identity
- *      for every frame.  The warp of a frame with counts[b] <= 0 is not applied.  With with_reid off - the reference builds no
- *      embeddings - the costs are ByteTrack's; proximity_thresh and appearance_thresh are not arguments.  A table written by one of
+ *      for every frame.  The warp of a frame with counts[b] <= 0 is not applied.  This entry is the tracker with with_reid off - as
+ *      the reference runs it, which builds no embeddings: the costs are ByteTrack's, and proximity_thresh and appearance_thresh are
+ *      arguments of tamtr_botsort_reid_update below only.  A table written by one of
  *      the two trackers must not be handed to the other: the means differ in meaning.  (New symbol only; the ABI version stays 36.) */
 int tamtr_botsort_update(const float* out, const int32_t* counts, const double* warps, int B, int nq, double* mean, double* cov,
                          int32_t* meta, float* sc, int32_t* hdr, int T, float track_high_thresh, float track_low_thresh,
                          float new_track_thresh, double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts, void* workspace,
                          int workspace_bytes, void* stream);
+
+/*      tamtr_botsort_reid_update: BOTSORT.update with with_reid on - the appearance half of the rule, which the reference writes out
+ *      (BOTrack.update_features bot_sort.py:55-64, BOTSORT.init_track :166-174, BOTSORT.get_dists :176-190,
+ *      matching.embedding_distance utils/matching.py:84-105) and never runs for want of an encoder.  tamtr_botsort_update's operands,
+ *      table, outputs and launch, plus
+ *      feat  f32 [B, nq, D]  one feature row per row of `out` (tamtr_reid_rows writes them; rows after counts[b] are not read),
+ *      tfeat f32 [T, D]      the table's smooth_feat per slot, updated in place; a fresh table needs no fill (a new track copies
+ *                            its detection's row),
+ *      proximity_thresh (compared in fp32 with the raw IoU distance) and appearance_thresh (compared in fp64 with the halved cosine
+ *      distance): in the first association and in the unconfirmed tracks' a pair whose IoU distance is not above proximity_thresh
+ *      costs min(fused IoU distance, e), e = max(0, cosine distance) / 2 set to 1 where it is above appearance_thresh; matched tracks
+ *      smooth their row with alpha = 0.9 and renormalise it (csrc/track.hip states the arithmetic and the summation orders).  With
+ *      appearance_thresh < 0 no embedding can act and rows and table are those of tamtr_botsort_update, bit for bit.
+ *      workspace: tamtr_botsort_reid_workspace_bytes(T, nq) bytes (the cost matrix is fp64 here), 8-byte aligned.
+ *      TAMTR_EINVAL: as tamtr_botsort_update, a NULL feat or tfeat, D < 1, a misaligned or too small workspace.  TAMTR_EUNSUP:
+ *      D > 1024, and as tamtr_bytetrack_update.  The checks come before any GPU call; one launch, nothing allocated, set or
+ *      synchronised.  (New symbols only; the ABI version stays 36.) */
+int tamtr_botsort_reid_update(const float* out, const int32_t* counts, const double* warps, const float* feat, int B, int nq,
+                              double* mean, double* cov, int32_t* meta, float* sc, int32_t* hdr, float* tfeat, int D, int T,
+                              float track_high_thresh, float track_low_thresh, float new_track_thresh, double match_thresh,
+                              int max_time_lost, float proximity_thresh, double appearance_thresh, float* tracks, int32_t* tcounts,
+                              void* workspace, int workspace_bytes, void* stream);
+int tamtr_botsort_reid_workspace_bytes(int T, int nq);
+
+/*      tamtr_reid_rows: the feature rows tamtr_botsort_reid_update reads, gathered from a per-query embedding (e.g. the decoder's
+ *      hidden state that goes into the score head) by the `keep` of tamtr_detect_postprocess: feat[b, j, :] = embed[b, keep[b, j], :]
+ *      widened to fp32 and divided by its norm twice, as BOTrack.__init__ -> update_features does to a detection's feature
+ *      (bot_sort.py:50-64: feat /= |feat|, then smooth_feat, the same array, /= |smooth_feat|), for j < counts[b]; zero rows after.
+ *      embed (T) [B, nqm, D] (dtype TAMTR_F32 or TAMTR_BF16), keep i32 [B, nq], counts i32 [B], feat f32 [B, nq, D].  A keep index
+ *      outside [0, nqm) gives a zero row; a row of zero norm is outside the contract.  One wavefront per row, 16-byte loads where
+ *      D % 4 == 0 and the bases are aligned; csrc/track.hip states the order of the sums.
+ *      TAMTR_EINVAL: a NULL operand, B, nqm, nq or D < 1.  TAMTR_EUNSUP: D > 1024, another dtype.  One launch, checks first. */
+int tamtr_reid_rows(const void* embed, int dtype, const int32_t* keep, const int32_t* counts, int B, int nqm, int nq, int D, float* feat,
+                    void* stream);
 
 /*      tamtr_gmc_estimate: the warps tamtr_botsort_update reads, estimated from the frames of the batch on the device.  It stands where
  *      the reference runs OpenCV on the host (trackers/utils/gmc.py:247-302, applySparseOptFlow); the rule is the project's own and is

@@ -112,6 +112,9 @@ _SIGS = {
     'tamtr_bytetrack_update': [_P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _F, _F, _F, _D, _I, _P, _P, _P, _I, _P],
     'tamtr_bytetrack_workspace_bytes': [_I, _I],
     'tamtr_botsort_update': [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _I, _F, _F, _F, _D, _I, _P, _P, _P, _I, _P],
+    'tamtr_botsort_reid_update': [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _D, _I, _F, _D, _P, _P, _P, _I, _P],
+    'tamtr_botsort_reid_workspace_bytes': [_I, _I],
+    'tamtr_reid_rows': [_P, _I, _P, _P, _I, _I, _I, _I, _P, _P],
     'tamtr_gmc_workspace_bytes': [_I, _I, _I],
     'tamtr_gmc_workspace_offset': [_I, _I, _I, _I],
     'tamtr_gmc_state_bytes': [_I, _I],

@@ -55,7 +55,27 @@
 //            identity warp (the reference run with an image).  A frame without detections does not reach the tracker, and its
 //            warp is not applied.
 //   costs    get_dists with with_reid off (the reference builds no embeddings) is ByteTrack's fused IoU distance; proximity_thresh
-//            and appearance_thresh act on embeddings only and are not read here.
+//            and appearance_thresh act on embeddings only and are not read by tamtr_botsort_update.
+//
+// BoT-SORT with ReID (tamtr_botsort_reid_update): the KF_XYWH kernel once more, with the appearance half of the reference's rule
+// (BOTrack.update_features bot_sort.py:55-64, BOTSORT.init_track :166-174, BOTSORT.get_dists :176-190, matching.embedding_distance
+// utils/matching.py:84-105; the numpy twin is tests/botsort_reid_np.py).  The reference ships no encoder; here every detection row
+// comes with a feature row feat f32 [B, nq, D] (tamtr_reid_rows below gathers and normalises them), and the table gains
+// tfeat f32 [T, D], a track's smooth_feat.  It differs from the kernel above in two places:
+//   costs    steps 4 and 6 (get_dists): with d the raw fp32 IoU distance and f its fused form, a pair with !(d > proximity_thresh)
+//            (fp32 compare, as numpy compares an fp32 array with a python scalar) also gets the embedding distance
+//            e = max(0, 1 - uv / (sqrt(uu) * sqrt(vv))) / 2 with uv, uu, vv the fp64 dot products of the track's smooth_feat and the
+//            detection's row (scipy's cdist(..., 'cosine') widens fp32 inputs to fp64; a |cosine| above 1 is clipped to 1 first, as
+//            scipy does); e > appearance_thresh (fp64) gives 1; the cost is min(f, e) in fp64, which is what np.minimum of an fp32
+//            and an fp64 array returns - so this instantiation keeps its cost matrix in fp64.  The other pairs keep f.  The gated
+//            pairs of 64 matrix entries are collected with one ballot and the wave takes them one at a time: lane l sums the
+//            products of elements l, l + 64, ... in that order, the 64 partial sums go through an xor butterfly (32, 16, ... 1).
+//            The second association stays plain IoU distance (byte_tracker.py:298).
+//   features after each of the three match loops the wave walks the matched (slot, detection) pairs; update_features in fp32, every
+//            operation rounded on its own: x = f / |f|, s = fp32(0.9) * s + fp32(1 - 0.9) * x, s = s / |s|, where |.| is the square
+//            root of the sum of squares taken as above (lane partial sums in element order, xor butterfly) in fp32.  A new track's
+//            row is a copy of its detection's row (there smooth_feat IS curr_feat).  A lost track keeps its row.
+//            A feature row of zero norm is outside the contract (the reference divides by zero there).
 #include "common.h"
 
 #define TRK_FREE 0
@@ -288,7 +308,8 @@ struct TrkLsap {   // LDS, sized for R <= T rows and Cn <= nq + 1 columns
 
 // The partial matching of n rows and m columns that minimises sum(c_ij - L): lsap.hip's solver with the extra column m of cost L that
 // any number of rows may take.  cost is [n, m] row-major; x[i] receives the column of row i, or -1.  Called by the whole wave.
-__device__ void trk_assign(const float* cost, int n, int m, double L, const TrkLsap& w, int* x, int lane) {
+template <typename C>
+__device__ void trk_assign(const C* cost, int n, int m, double L, const TrkLsap& w, int* x, int lane) {
   const int Cn = m + 1;
   for (int i = lane; i < n; i += WAVE) { w.u[i] = 0.0; w.col4row[i] = -1; }
   for (int j = lane; j < Cn; j += WAVE) { w.v[j] = 0.0; w.row4col[j] = -1; w.path[j] = -1; }
@@ -374,12 +395,111 @@ struct TrkParams {
   int32_t* tcounts;
   unsigned char* ws;
   const double* warps;   // KF_XYWH only: [B, 2, 3] or null
+  static constexpr bool reid = false;
+  using cost_t = float;
+};
+
+struct TrkReidParams : TrkParams {
+  const float* feat;   // [B, nq, D], the rows of tamtr_reid_rows
+  float* tfeat;        // [T, D], smooth_feat of a slot's track
+  int D;
+  float prox;
+  double app;
+  static constexpr bool reid = true;
+  using cost_t = double;   // np.minimum(fp32 fused cost, fp64 embedding distance) is fp64
 };
 
 static size_t trk_ws_bytes(int T, int nq) { return 4 * ((size_t)T * nq + 4 * (size_t)T + 4 * (size_t)nq + 7 * (size_t)T + 5 * (size_t)nq); }
+static size_t trk_reid_ws_bytes(int T, int nq) { return trk_ws_bytes(T, nq) + 4 * (size_t)T * nq; }   // the cost matrix is fp64
 static size_t trk_lds_bytes(int T, int nq) {
   const size_t R = T, Cn = (size_t)nq + 1;
   return 8 * (R + 2 * Cn) + 4 * (3 * Cn + R) + R + Cn + 16;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- ReID
+template <typename V>
+__device__ __forceinline__ V trk_wave_sum(V x) {
+#pragma unroll
+  for (int o = WAVE / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, WAVE);
+  return x;
+}
+
+// BOTrack.update_features (bot_sort.py:55-64) of a track that has a smooth_feat `sm`, with the detection's row f: fp32, op by op.
+// Called by the whole wave; lane l owns elements l, l + 64, ...
+__device__ __forceinline__ void trk_feat_update(float* sm, const float* f, int D, int lane) {
+  float ss = 0.0f;
+  for (int k = lane; k < D; k += WAVE) { const float x = f[k]; ss += x * x; }
+  const float n1 = sqrtf(trk_wave_sum(ss));
+  float s2 = 0.0f;
+  for (int k = lane; k < D; k += WAVE) {
+    const float x = f[k] / n1;
+    const float y = (float)0.9 * sm[k] + (float)(1 - 0.9) * x;
+    sm[k] = y;
+    s2 += y * y;
+  }
+  const float n2 = sqrtf(trk_wave_sum(s2));
+  for (int k = lane; k < D; k += WAVE) sm[k] = sm[k] / n2;
+}
+
+// the matched pairs (row i of a cost matrix, its column xs[i] >= 0) in row order, one at a time: the slot's feature row is updated
+template <typename FS, typename FD>
+__device__ __forceinline__ void trk_reid_matched(const TrkReidParams& p, const float* fb, const int* xs, int n, int lane, FS slot_of,
+                                                 FD det_of) {
+  for (int i0 = 0; i0 < n; i0 += WAVE) {
+    const int i = i0 + lane;
+    const int j = i < n ? xs[i] : -1;
+    const int s = j >= 0 ? slot_of(i) : 0, dj = j >= 0 ? det_of(j) : 0;
+    unsigned long long todo = __ballot(j >= 0);
+    while (todo) {
+      const int l = __ffsll(todo) - 1;
+      todo &= todo - 1;
+      trk_feat_update(p.tfeat + (size_t)__shfl(s, l, WAVE) * p.D, fb + (size_t)__shfl(dj, l, WAVE) * p.D, p.D, lane);
+    }
+  }
+}
+
+// BOTSORT.get_dists (bot_sort.py:176-190) for n tracks x m detections -> cost [n, m] fp64
+template <typename FS, typename FD>
+__device__ __forceinline__ void trk_reid_costs(const TrkReidParams& p, double* cost, const float* tb, const float* db, const float* d,
+                                               const float* fb, int n, int m, int lane, FS slot_of, FD det_of) {
+  const int D = p.D;
+  for (int e0 = 0; e0 < n * m; e0 += WAVE) {
+    const int e = e0 + lane;
+    int s = 0, dj = 0;
+    double c = 0.0;
+    bool near = false;
+    if (e < n * m) {
+      const int i = e / m;
+      s = slot_of(i);
+      dj = det_of(e - i * m);
+      const float dist = 1.0f - trk_iou(tb + 4 * s, db + 4 * dj);
+      c = 1.0f - (1.0f - dist) * d[(size_t)dj * 6 + 4];
+      near = !(dist > p.prox);
+    }
+    unsigned long long todo = __ballot(near);
+    while (todo) {
+      const int l = __ffsll(todo) - 1;
+      todo &= todo - 1;
+      const float* u = p.tfeat + (size_t)__shfl(s, l, WAVE) * D;
+      const float* v = fb + (size_t)__shfl(dj, l, WAVE) * D;
+      double uv = 0.0, uu = 0.0, vv = 0.0;
+      for (int k = lane; k < D; k += WAVE) {
+        const double a = u[k], b = v[k];
+        uv += a * b;
+        uu += a * a;
+        vv += b * b;
+      }
+      uv = trk_wave_sum(uv);
+      uu = trk_wave_sum(uu);
+      vv = trk_wave_sum(vv);
+      double cs = uv / (sqrt(uu) * sqrt(vv));
+      if (fabs(cs) > 1.0) cs = copysign(1.0, cs);
+      double em = fmax(0.0, 1.0 - cs) / 2.0;
+      if (em > p.app) em = 1.0;
+      if (lane == l) c = fmin(c, em);
+    }
+    if (e < n * m) cost[e] = c;
+  }
 }
 
 // a matched track: STrack.update / re_activate (byte_tracker.py:112-145)
@@ -399,8 +519,10 @@ __device__ __forceinline__ void trk_matched(const TrkParams& p, int s, const flo
   p.sc[2 * s + 1] = d[(size_t)dj * 6 + 5];
 }
 
-template <int KF>
-__global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
+template <int KF, typename P>
+__global__ __launch_bounds__(WAVE) void bytetrack_kernel(P p) {
+  constexpr bool REID = P::reid;
+  using cost_t = typename P::cost_t;
   extern __shared__ __align__(16) unsigned char lds[];
   const int lane = threadIdx.x, T = p.T, nq = p.nq;
   TrkLsap w;
@@ -416,8 +538,8 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
     w.SR = reinterpret_cast<unsigned char*>(w.col4row + R);
     w.SC = w.SR + R;
   }
-  float* cost = reinterpret_cast<float*>(p.ws);   // [T, nq]
-  float* tb = cost + (size_t)T * nq;              // tlbr of a slot's track [T, 4]
+  cost_t* cost = reinterpret_cast<cost_t*>(p.ws);               // [T, nq]
+  float* tb = reinterpret_cast<float*>(cost + (size_t)T * nq);   // tlbr of a slot's track [T, 4]
   float* db = tb + 4 * (size_t)T;                 // tlbr of a detection [nq, 4]
   int* pool = reinterpret_cast<int*>(db + 4 * (size_t)nq);
   int *unconf = pool + T, *rest = unconf + T, *freel = rest + T, *xs = freel + T, *newly_lost = xs + T, *dup = newly_lost + T;
@@ -428,6 +550,8 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
     const int nd = min(max(p.counts[b], 0), nq);
     const float* d = p.out + (size_t)b * nq * 6;
     float* trow = p.tracks + (size_t)b * nq * 8;
+    const float* fb = nullptr;   // ReID: the frame's feature rows [nq, D]
+    if constexpr (REID) fb = p.feat + (size_t)b * nq * p.D;
     if (nd == 0) {   // trackers/track.py:46-47: the tracker is not called, nothing ages
       for (int e = lane; e < nq * 8; e += WAVE) trow[e] = 0.0f;
       if (lane == 0) p.tcounts[b] = 0;
@@ -476,10 +600,14 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
     __syncthreads();
     // ---- 4. first association: pool x high detections, fused distance, match_thresh
     if (npool > 0 && nhi > 0) {
-      for (int e = lane; e < npool * nhi; e += WAVE) {
-        const int i = e / nhi, j = e - i * nhi, dj = hi[j];
-        const float dist = 1.0f - trk_iou(tb + 4 * pool[i], db + 4 * dj);
-        cost[e] = 1.0f - (1.0f - dist) * d[(size_t)dj * 6 + 4];
+      if constexpr (REID) {
+        trk_reid_costs(p, cost, tb, db, d, fb, npool, nhi, lane, [&](int i) { return pool[i]; }, [&](int j) { return hi[j]; });
+      } else {
+        for (int e = lane; e < npool * nhi; e += WAVE) {
+          const int i = e / nhi, j = e - i * nhi, dj = hi[j];
+          const float dist = 1.0f - trk_iou(tb + 4 * pool[i], db + 4 * dj);
+          cost[e] = 1.0f - (1.0f - dist) * d[(size_t)dj * 6 + 4];
+        }
       }
       __syncthreads();
       trk_assign(cost, npool, nhi, p.match, w, xs, lane);
@@ -495,6 +623,7 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
         used[hi[j]] = 1;
       }
     }
+    if constexpr (REID) trk_reid_matched(p, fb, xs, npool, lane, [&](int i) { return pool[i]; }, [&](int j) { return hi[j]; });
     __syncthreads();
     // ---- 5. second association: the unmatched pool tracks in state Tracked x low detections, plain IoU distance, 0.5
     const int nrest = trk_compact(npool, rest, lane, [&](int i) { return xs[i] < 0 && p.meta[pool[i] * 8 + M_STATE] == TRK_TRACKED; });
@@ -521,15 +650,20 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
         newly_lost[s] = 1;
       }
     }
+    if constexpr (REID) trk_reid_matched(p, fb, xs, nrest, lane, [&](int i) { return pool[rest[i]]; }, [&](int j) { return lo[j]; });
     __syncthreads();
     // ---- 6. unconfirmed tracks x the high detections still free, fused distance, 0.7; the unmatched ones are removed
     const int nleft = trk_compact(nhi, left, lane, [&](int k) { return !used[hi[k]]; });
     __syncthreads();
     if (nun > 0 && nleft > 0) {
-      for (int e = lane; e < nun * nleft; e += WAVE) {
-        const int i = e / nleft, j = e - i * nleft, dj = hi[left[j]];
-        const float dist = 1.0f - trk_iou(tb + 4 * unconf[i], db + 4 * dj);
-        cost[e] = 1.0f - (1.0f - dist) * d[(size_t)dj * 6 + 4];
+      if constexpr (REID) {
+        trk_reid_costs(p, cost, tb, db, d, fb, nun, nleft, lane, [&](int i) { return unconf[i]; }, [&](int j) { return hi[left[j]]; });
+      } else {
+        for (int e = lane; e < nun * nleft; e += WAVE) {
+          const int i = e / nleft, j = e - i * nleft, dj = hi[left[j]];
+          const float dist = 1.0f - trk_iou(tb + 4 * unconf[i], db + 4 * dj);
+          cost[e] = 1.0f - (1.0f - dist) * d[(size_t)dj * 6 + 4];
+        }
       }
       __syncthreads();
       trk_assign(cost, nun, nleft, 0.7, w, xs, lane);
@@ -546,6 +680,7 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
         p.meta[s * 8 + M_STATE] = TRK_FREE;
       }
     }
+    if constexpr (REID) trk_reid_matched(p, fb, xs, nun, lane, [&](int i) { return unconf[i]; }, [&](int j) { return hi[left[j]]; });
     __syncthreads();
     // ---- 7. new tracks from what is left, score >= new_track_thresh, into the lowest free slots
     const int nnew = trk_compact(nleft, newd, lane, [&](int k) { const int dj = hi[left[k]]; return !used[dj] && !(d[(size_t)dj * 6 + 4] < p.newt); });
@@ -571,6 +706,12 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(TrkParams p) {
       p.sc[2 * s + 1] = d[(size_t)dj * 6 + 5];
     }
     next_id += ncreate;
+    if constexpr (REID)      // a new track's smooth_feat is its detection's row
+      for (int k = 0; k < ncreate; ++k) {
+        float* sm = p.tfeat + (size_t)freel[k] * p.D;
+        const float* f = fb + (size_t)hi[left[newd[k]]] * p.D;
+        for (int c = lane; c < p.D; c += WAVE) sm[c] = f[c];
+      }
     __syncthreads();
     // ---- 8. lost tracks age out; one removed a frame ago leaves now
     for (int s = lane; s < T; s += WAVE) {
@@ -639,7 +780,7 @@ static int trk_launch(const float* out, const int32_t* counts, const double* war
   if (workspace_bytes < tamtr_bytetrack_workspace_bytes(T, nq)) return TAMTR_EINVAL;
   TrkParams p{out, counts, B, nq, T, mean, cov, meta, sc, hdr, track_high_thresh, track_low_thresh, new_track_thresh, match_thresh,
               max_time_lost, tracks, tcounts, static_cast<unsigned char*>(workspace), warps};
-  hipLaunchKernelGGL(bytetrack_kernel<KF>, dim3(1), dim3(WAVE), trk_lds_bytes(T, nq), (hipStream_t)stream, p);
+  hipLaunchKernelGGL((bytetrack_kernel<KF, TrkParams>), dim3(1), dim3(WAVE), trk_lds_bytes(T, nq), (hipStream_t)stream, p);
   return tamtr_launch_status();
 }
 
@@ -658,4 +799,120 @@ extern "C" int tamtr_botsort_update(const float* out, const int32_t* counts, con
   if (warps && (reinterpret_cast<uintptr_t>(warps) & 7)) return TAMTR_EINVAL;
   return trk_launch<KF_XYWH>(out, counts, warps, B, nq, mean, cov, meta, sc, hdr, T, track_high_thresh, track_low_thresh, new_track_thresh,
                              match_thresh, max_time_lost, tracks, tcounts, workspace, workspace_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------- BoT-SORT with ReID
+#define REID_MAX_D 1024
+
+extern "C" int tamtr_botsort_reid_workspace_bytes(int T, int nq) {
+  if (T < 1 || nq < 1) return 0;
+  const size_t n = trk_reid_ws_bytes(T, nq);
+  return n > 0x7fffffff ? 0 : (int)n;
+}
+
+extern "C" int tamtr_botsort_reid_update(const float* out, const int32_t* counts, const double* warps, const float* feat, int B, int nq,
+                                         double* mean, double* cov, int32_t* meta, float* sc, int32_t* hdr, float* tfeat, int D, int T,
+                                         float track_high_thresh, float track_low_thresh, float new_track_thresh, double match_thresh,
+                                         int max_time_lost, float proximity_thresh, double appearance_thresh, float* tracks,
+                                         int32_t* tcounts, void* workspace, int workspace_bytes, void* stream) {
+  if (!out || !counts || !feat || !mean || !cov || !meta || !sc || !hdr || !tfeat || !tracks || !tcounts || !workspace || B < 1 || nq < 1 ||
+      T < 1 || D < 1)
+    return TAMTR_EINVAL;
+  if ((warps && (reinterpret_cast<uintptr_t>(warps) & 7)) || (reinterpret_cast<uintptr_t>(workspace) & 7)) return TAMTR_EINVAL;
+  if (D > REID_MAX_D || tamtr_botsort_reid_workspace_bytes(T, nq) == 0 || trk_lds_bytes(T, nq) > 64 * 1024) return TAMTR_EUNSUP;
+  if (workspace_bytes < tamtr_botsort_reid_workspace_bytes(T, nq)) return TAMTR_EINVAL;
+  TrkReidParams p;
+  static_cast<TrkParams&>(p) = TrkParams{out, counts, B, nq, T, mean, cov, meta, sc, hdr, track_high_thresh, track_low_thresh,
+                                         new_track_thresh, match_thresh, max_time_lost, tracks, tcounts,
+                                         static_cast<unsigned char*>(workspace), warps};
+  p.feat = feat;
+  p.tfeat = tfeat;
+  p.D = D;
+  p.prox = proximity_thresh;
+  p.app = appearance_thresh;
+  hipLaunchKernelGGL((bytetrack_kernel<KF_XYWH, TrkReidParams>), dim3(1), dim3(WAVE), trk_lds_bytes(T, nq), (hipStream_t)stream, p);
+  return tamtr_launch_status();
+}
+
+// reid_rows: feat[b, j, :] = the row embed[b, keep[b, j], :] widened to fp32 and normalised twice, for j < counts[b]; zero after the
+// count.  Twice, because the reference's BOTrack(feat) runs update_features on a track without a smooth_feat: feat /= |feat|, then
+// smooth_feat = feat - the same array - and smooth_feat /= |smooth_feat| (bot_sort.py:57-64).  One wavefront per row.  |x| is the
+// fp32 square root of the fp32 sum of squares taken in this order: lane l adds up the squares of its elements in ascending index
+// (VEC: elements 4 (l + 64 c) .. + 3 for c = 0, 1, ...; scalar: elements l + 64 c), then the 64 partial sums go through an xor
+// butterfly (32, 16, ... 1).  A keep index outside [0, nqm) gives a zero row; a row of zero norm is outside the contract.
+#define REID_WAVES 4
+
+template <typename TE, bool VEC>
+__device__ __forceinline__ float reid_sumsq_load(const TE* x, int D, int lane) {
+  float ss = 0.0f;
+  if (VEC) {
+    for (int k = 4 * lane; k < D; k += 4 * WAVE) {
+      float v[4];
+      Elt<TE>::ld4(x + k, v);
+      ss += v[0] * v[0]; ss += v[1] * v[1]; ss += v[2] * v[2]; ss += v[3] * v[3];
+    }
+  } else {
+    for (int k = lane; k < D; k += WAVE) { const float v = Elt<TE>::ld(x + k); ss += v * v; }
+  }
+  return ss;
+}
+
+template <typename TE, bool VEC>
+__global__ __launch_bounds__(REID_WAVES* WAVE) void reid_rows_kernel(const TE* __restrict__ embed, const int32_t* __restrict__ keep,
+                                                                     const int32_t* __restrict__ counts, int B, int nqm, int nq, int D,
+                                                                     float* __restrict__ feat) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const long long row = (long long)blockIdx.x * REID_WAVES + (threadIdx.x >> 6);
+  if (row >= (long long)B * nq) return;
+  const int b = (int)(row / nq), j = (int)(row - (long long)b * nq);
+  float* o = feat + (size_t)row * D;
+  const int q = j < min(max(counts[b], 0), nq) ? keep[row] : -1;
+  if (q < 0 || q >= nqm) {
+    for (int k = lane; k < D; k += WAVE) o[k] = 0.0f;
+    return;
+  }
+  const TE* x = embed + ((size_t)b * nqm + q) * D;
+  const float n1 = sqrtf(trk_wave_sum(reid_sumsq_load<TE, VEC>(x, D, lane)));
+  float s2 = 0.0f;
+  if (VEC) {
+    for (int k = 4 * lane; k < D; k += 4 * WAVE) {
+      float v[4];
+      Elt<TE>::ld4(x + k, v);
+      for (int i = 0; i < 4; ++i) { v[i] = v[i] / n1; s2 += v[i] * v[i]; }
+      *reinterpret_cast<float4*>(o + k) = make_float4(v[0], v[1], v[2], v[3]);
+    }
+  } else {
+    for (int k = lane; k < D; k += WAVE) { const float v = Elt<TE>::ld(x + k) / n1; s2 += v * v; o[k] = v; }
+  }
+  const float n2 = sqrtf(trk_wave_sum(s2));
+  if (VEC) {
+    for (int k = 4 * lane; k < D; k += 4 * WAVE) {
+      float4 v = *reinterpret_cast<float4*>(o + k);
+      v.x = v.x / n2; v.y = v.y / n2; v.z = v.z / n2; v.w = v.w / n2;
+      *reinterpret_cast<float4*>(o + k) = v;
+    }
+  } else {
+    for (int k = lane; k < D; k += WAVE) o[k] = o[k] / n2;
+  }
+}
+
+template <typename TE>
+static void reid_rows_launch(const void* embed, const int32_t* keep, const int32_t* counts, int B, int nqm, int nq, int D, float* feat,
+                             hipStream_t stream) {
+  const long long rows = (long long)B * nq;
+  const dim3 grid((unsigned)((rows + REID_WAVES - 1) / REID_WAVES)), block(REID_WAVES * WAVE);
+  const bool vec = D % 4 == 0 && !(reinterpret_cast<uintptr_t>(embed) & (4 * sizeof(TE) - 1)) && !(reinterpret_cast<uintptr_t>(feat) & 15);
+  if (vec)
+    hipLaunchKernelGGL((reid_rows_kernel<TE, true>), grid, block, 0, stream, static_cast<const TE*>(embed), keep, counts, B, nqm, nq, D, feat);
+  else
+    hipLaunchKernelGGL((reid_rows_kernel<TE, false>), grid, block, 0, stream, static_cast<const TE*>(embed), keep, counts, B, nqm, nq, D, feat);
+}
+
+extern "C" int tamtr_reid_rows(const void* embed, int dtype, const int32_t* keep, const int32_t* counts, int B, int nqm, int nq, int D,
+                               float* feat, void* stream) {
+  if (!embed || !keep || !counts || !feat || B < 1 || nqm < 1 || nq < 1 || D < 1) return TAMTR_EINVAL;
+  if (D > REID_MAX_D || (dtype != TAMTR_F32 && dtype != TAMTR_BF16) || (long long)B * nq > 0x7fffffffll / REID_WAVES) return TAMTR_EUNSUP;
+  if (dtype == TAMTR_F32) reid_rows_launch<float>(embed, keep, counts, B, nqm, nq, D, feat, (hipStream_t)stream);
+  else reid_rows_launch<bf16_t>(embed, keep, counts, B, nqm, nq, D, feat, (hipStream_t)stream);
+  return tamtr_launch_status();
 }

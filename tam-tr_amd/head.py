@@ -55,6 +55,22 @@ class ManbaWorldDecoder(nn.Module):
     def forward(self, x, text, batch=None):
         return self.decode(*self.encode(x), text, batch)
 
+    @property
+    def keep_query_embed(self):
+        """Off by default.  On, an evaluation forward leaves the decoder's per-query hidden state - the input of the score head of
+        layer eval_idx, [B, nq, hd] - in last_query_embed (see TextDeformableTransformerDecoder); the outputs keep their bits."""
+        return self.decoder.keep_query_embed
+
+    @keep_query_embed.setter
+    def keep_query_embed(self, flag):
+        self.decoder.keep_query_embed = bool(flag)
+        if not flag:
+            self.decoder.last_query_embed = None
+
+    @property
+    def last_query_embed(self):
+        return self.decoder.last_query_embed
+
     def draw_drop_scales(self, n, device):
         """[num_Blocks, 2, n]: this step's DropPath factors of the VSS blocks (vss.VSSBlock.draw_drop_scales), drawn outside encode()
         so that a recorded graph of encode() is a deterministic function of its inputs."""

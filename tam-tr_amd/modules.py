@@ -250,6 +250,11 @@ class TextDeformableTransformerDecoder(nn.Module):
         self.num_layers = num_layers
         self.hidden_dim = hidden_dim
         self.eval_idx = eval_idx if eval_idx >= 0 else num_layers + eval_idx
+        # off by default.  On, an evaluation forward keeps a reference to the output of layer eval_idx - the [B, nq, hd] tensor that
+        # goes into score_head[eval_idx], one vector per query - as last_query_embed (the tracker's ReID embedding, track.BotSort).
+        # Nothing is copied or computed for it, so the outputs have the same bits either way; training does not look at it.
+        self.keep_query_embed = False
+        self.last_query_embed = None
 
     def forward(self, embed, refer_bbox, feats, shapes, text, bbox_head, score_head, pos_mlp, attn_mask=None,
                 padding_mask=None):
@@ -264,6 +269,8 @@ class TextDeformableTransformerDecoder(nn.Module):
                 dec_cls.append(score_head[i](output, text))
                 dec_bboxes.append(refined if i == 0 else ops.box_refine(bbox, last_refined))
             elif i == self.eval_idx:
+                if self.keep_query_embed:
+                    self.last_query_embed = output
                 dec_cls.append(score_head[i](output, text))
                 dec_bboxes.append(refined)
                 break

@@ -1942,6 +1942,65 @@ def botsort_update(out, counts, state, capacity, warps=None, track_high_thresh=0
                            match_thresh, max_time_lost, workspace)
 
 
+REID_MAX_D = 1024
+
+
+def botsort_reid_workspace_bytes(capacity, nq):
+    """Bytes of device workspace tamtr_botsort_reid_update needs (its cost matrix is fp64; no GPU call)."""
+    n = _lib.lib().tamtr_botsort_reid_workspace_bytes(int(capacity), int(nq))
+    if n <= 0:
+        raise _lib.TamtrHipError(f'botsort_reid: capacity {capacity} with nq {nq} is outside what the kernel is built for')
+    return n
+
+
+def reid_rows(embed, keep, counts):
+    """One feature row per kept detection, for botsort_reid_update: feat[b, j] = embed[b, keep[b, j]] widened to fp32 and divided by
+    its norm twice (what BOTrack.__init__ does to a detection's feature, bot_sort.py:50-64) for j < counts[b], zero after.  embed
+    f32 | bf16 [B, nqm, D] (e.g. the decoder's per-query hidden state), keep i32 [B, nq] and counts i32 [B] are detect_postprocess's;
+    all on the GPU.  Returns feat f32 [B, nq, D].  One launch; every check comes before it; no synchronisation."""
+    if not torch.is_tensor(embed) or embed.dim() != 3 or min(embed.shape) < 1:
+        got = tuple(embed.shape) if torch.is_tensor(embed) else type(embed).__name__
+        raise _lib.TamtrHipError(f'reid_rows: expected embed [B, nqm, D], got {got}')
+    B, nqm, D = embed.shape
+    if D > REID_MAX_D:
+        raise _lib.TamtrHipError(f'reid_rows: D = {D} is above the {REID_MAX_D} the kernels are built for')
+    if not torch.is_tensor(keep) or keep.dim() != 2 or keep.shape[0] != B or keep.shape[1] < 1 or keep.dtype != torch.int32:
+        got = (keep.dtype, tuple(keep.shape)) if torch.is_tensor(keep) else type(keep).__name__
+        raise _lib.TamtrHipError(f'reid_rows: keep must be an int32 tensor [B, nq] with B = {B}, got {got}')
+    if not torch.is_tensor(counts) or tuple(counts.shape) != (B,) or counts.dtype != torch.int32:
+        got = (counts.dtype, tuple(counts.shape)) if torch.is_tensor(counts) else type(counts).__name__
+        raise _lib.TamtrHipError(f'reid_rows: counts must be an int32 tensor [B] = [{B}], got {got}')
+    code = dtype_code(embed)
+    require_gpu(embed, keep, counts)
+    embed, keep, counts = _c(embed), _c(keep), _c(counts)
+    nq = keep.shape[1]
+    feat = torch.empty(B, nq, D, device=embed.device, dtype=torch.float32)
+    call('tamtr_reid_rows', ptr(embed), code, ptr(keep), ptr(counts), B, nqm, nq, D, ptr(feat), stream_ptr())
+    return feat
+
+
+def botsort_reid_update(out, counts, feat, state, capacity, warps=None, track_high_thresh=0.5, track_low_thresh=0.1, new_track_thresh=0.6,
+                        match_thresh=0.8, max_time_lost=30, proximity_thresh=0.5, appearance_thresh=0.25, workspace=None):
+    """BOTSORT.update with with_reid on (trackers/bot_sort.py:55-64, 166-190 with utils/matching.py:84-105) for the B frames of a
+    batch, in order, in one launch: botsort_update's operands and outputs plus feat f32 [B, nq, D], one feature row per row of `out`
+    (reid_rows), and state['feat'] f32 [T, D], the tracks' smooth features, updated in place; the rule is stated in csrc/track.hip.
+    The workspace is botsort_reid_workspace_bytes(T, nq).  Every check comes before the launch; no synchronisation."""
+    what = 'botsort_reid_update'
+    if not torch.is_tensor(feat) or feat.dim() != 3 or feat.dtype != torch.float32 or out.dim() != 3 or tuple(feat.shape[:2]) != tuple(out.shape[:2]) \
+            or feat.shape[2] < 1:
+        got = (feat.dtype, tuple(feat.shape)) if torch.is_tensor(feat) else type(feat).__name__
+        raise _lib.TamtrHipError(f'{what}: feat must be a float32 tensor [B, nq, D] aligned with out {tuple(out.shape)}, got {got}')
+    D = int(feat.shape[2])
+    if D > REID_MAX_D:
+        raise _lib.TamtrHipError(f'{what}: D = {D} is above the {REID_MAX_D} the kernel is built for')
+    tf = state.get('feat') if isinstance(state, dict) else None
+    if tf is None or tf.dtype != torch.float32 or tuple(tf.shape) != (int(capacity), D) or not tf.is_contiguous():
+        got = None if tf is None else (tf.dtype, tuple(tf.shape))
+        raise _lib.TamtrHipError(f"{what}: state['feat'] must be a contiguous float32 tensor of shape {(int(capacity), D)}, got {got}")
+    return _tracker_update(what, warps, out, counts, state, capacity, track_high_thresh, track_low_thresh, new_track_thresh,
+                           match_thresh, max_time_lost, workspace, reid=(feat, tf, D, float(proximity_thresh), float(appearance_thresh)))
+
+
 # ------------------------------------------------------------------------------------------------ camera-motion estimate (csrc/gmc.hip)
 GMC_SLOTS = 1024
 GMC_SECTIONS = (('pyr', torch.uint8), ('lam', torch.float32), ('tilemax', torch.float32), ('kp', torch.int32), ('pts', torch.float32),
@@ -2044,7 +2103,7 @@ def gmc_estimate(frames, counts, scale, state, workspace=None, stages=15):
 
 
 def _tracker_update(what, warps, out, counts, state, capacity, track_high_thresh, track_low_thresh, new_track_thresh, match_thresh,
-                    max_time_lost, workspace):
+                    max_time_lost, workspace, reid=None):
     if out.dim() != 3 or out.shape[-1] != 6 or out.shape[0] < 1 or out.shape[1] < 1:
         raise _lib.TamtrHipError(f'{what}: expected out [B, nq, 6], got {tuple(out.shape)}')
     B, nq, _ = out.shape
@@ -2064,9 +2123,9 @@ def _tracker_update(what, warps, out, counts, state, capacity, track_high_thresh
     if warps is not None and (not torch.is_tensor(warps) or tuple(warps.shape) != (B, 2, 3) or warps.dtype != torch.float64):
         got = (warps.dtype, tuple(warps.shape)) if torch.is_tensor(warps) else type(warps).__name__
         raise _lib.TamtrHipError(f'{what}: warps must be a float64 tensor [B, 2, 3] = [{B}, 2, 3], got {got}')
-    require_gpu(out, counts, warps, *(state[k] for k in ('mean', 'cov', 'meta', 'sc', 'hdr')))
+    require_gpu(out, counts, warps, *(state[k] for k in ('mean', 'cov', 'meta', 'sc', 'hdr')), *(reid[:2] if reid else ()))
     warps = _c(warps) if warps is not None else None
-    need = bytetrack_workspace_bytes(T, nq)
+    need = botsort_reid_workspace_bytes(T, nq) if reid else bytetrack_workspace_bytes(T, nq)
     if workspace is None:
         workspace = torch.empty(need, device=out.device, dtype=torch.uint8)
     require_gpu(workspace)
@@ -2075,6 +2134,13 @@ def _tracker_update(what, warps, out, counts, state, capacity, track_high_thresh
     out, counts = _c(out), _c(counts)
     tracks = torch.empty(B, nq, 8, device=out.device, dtype=torch.float32)
     tcounts = torch.empty(B, device=out.device, dtype=torch.int32)
+    if reid:
+        feat, tf, D, prox, app = reid
+        call('tamtr_' + what, ptr(out), ptr(counts), ptr(warps) if warps is not None else None, ptr(_c(feat)), B, nq, ptr(state['mean']),
+             ptr(state['cov']), ptr(state['meta']), ptr(state['sc']), ptr(state['hdr']), ptr(tf), D, T, float(track_high_thresh),
+             float(track_low_thresh), float(new_track_thresh), float(match_thresh), int(max_time_lost), prox, app, ptr(tracks), ptr(tcounts),
+             ptr(workspace), int(workspace.numel()), stream_ptr())
+        return tracks, tcounts
     args = (ptr(out), ptr(counts)) + ((ptr(warps) if warps is not None else None,) if what == 'botsort_update' else ())
     call('tamtr_' + what, *args, B, nq, ptr(state['mean']), ptr(state['cov']), ptr(state['meta']), ptr(state['sc']),
          ptr(state['hdr']), T, float(track_high_thresh), float(track_low_thresh), float(new_track_thresh), float(match_thresh),

@@ -197,6 +197,7 @@ class Predictor:
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
         ev[0].record()
         gmc = getattr(tracker, 'gmc_method', None) == 'sparseOptFlow'      # a track.BotSort that estimates its warps from the frames
+        reid = bool(getattr(tracker, 'with_reid', False))                  # a track.BotSort that takes the decoder's query embeddings
         img, u8 = to_model_input(arr, self.device, keep_u8=True)
         ev[1].record()
         with torch.autocast('cuda', dtype=self.autocast_dtype or torch.bfloat16, enabled=self.autocast_dtype is not None):
@@ -218,9 +219,9 @@ class Predictor:
                 warps = tracker.estimate_warps(u8, counts, [[w0 / W, h0 / H] for h0, w0 in np.asarray(hw).reshape(-1, 2).tolist()])
                 ev_gmc = torch.cuda.Event(enable_timing=True)
                 ev_gmc.record()
-                tracks, tcounts = tracker.update(out, counts, warps=warps)
+                tracks, tcounts = tracker.update(out, counts, warps=warps, **self._reid_operands(reid, keep))
             else:
-                tracks, tcounts = tracker.update(out, counts)
+                tracks, tcounts = tracker.update(out, counts, **self._reid_operands(reid, keep))
             parts += [tracks.view(-1), tcounts.view(torch.float32), tracker.state['hdr'].view(torch.float32)]
             for e in evaluators if scoring else []:
                 ev_eval.append(torch.cuda.Event(enable_timing=True))
@@ -251,6 +252,16 @@ class Predictor:
             e.check_overflow(h.view(torch.int32))
         return res + (tr.view(B, nq, 8), tc.view(torch.int32))
 
+    def _reid_operands(self, reid, keep):
+        """For a BotSort with ReID: the decoder's per-query hidden state of this forward (head.keep_query_embed) and the source query
+        of every kept row, both where they lie on the device; the gather (ops.reid_rows) runs inside tracker.update, under 'track'."""
+        if not reid:
+            return {}
+        embed = self.model.model[-1].last_query_embed
+        if embed is None:
+            raise RuntimeError('the tracker has with_reid on and the decoder kept no query embedding: set head.keep_query_embed (track() does)')
+        return {'embed': embed, 'keep': keep}
+
     def predict(self, source):
         """Yields one Detections per image, in the sorted order of list_sources(source)."""
         yield from self._run(list_sources(source), None)
@@ -262,7 +273,10 @@ class Predictor:
         (trackers/track.py:46-50).  tracker: a track.ByteTracker or track.BotSort, a bytetrack.yaml or botsort.yaml path
         (track.tracker_from_yaml), or None for ByteTrack's defaults; persist=True keeps the tracker (and its tracks) of the previous
         call.  A BotSort estimates its camera-motion warps from the uploaded frames of each batch (unless its gmc_method is none), and
-        speed() then has a 'gmc' entry for those launches.
+        speed() then has a 'gmc' entry for those launches.  A BotSort with ReID (with_reid=True, or a yaml with `with_reid: True`,
+        which is built with reid_dim = the decoder's hidden size) takes the decoder's per-query hidden state as the embedding of a
+        detection: the decoder keeps it for the run (head.keep_query_embed, switched back afterwards), the tracker gathers the kept
+        rows on the device; nothing more is copied to the host.
         gt + evaluator: the sequence's ground truth, one array [m, 7] (x1 y1 x2 y2 id cls kind, track.read_mot) per frame in file order
         (missing frames are empty), and a track.MotEvaluator or track.HotaEvaluator, or a list / tuple of them: every batch's rows are
         scored on the device right after the tracker's launch, by each evaluator in turn (a frame without track rows is an empty
@@ -274,8 +288,25 @@ class Predictor:
             if not persist:
                 tracker.reset()
         elif self.tracker is None or not persist:
-            self.tracker = tracker_from_yaml(tracker, self.device) if tracker else ByteTracker(self.device)
+            head = self.model.model[-1]
+            self.tracker = tracker_from_yaml(tracker, self.device, reid_dim=head.hidden_dim) if tracker else ByteTracker(self.device)
         files = list_sources(source)
+        if getattr(self.tracker, 'with_reid', False):
+            yield from self._with_query_embed(self._track(files, gt, evaluator))
+        else:
+            yield from self._track(files, gt, evaluator)
+
+    def _with_query_embed(self, frames):
+        head = self.model.model[-1]
+        if self.tracker.reid_dim != head.hidden_dim:
+            raise ValueError(f'the tracker was built with reid_dim {self.tracker.reid_dim}, the decoder\'s query embedding has {head.hidden_dim}')
+        was, head.keep_query_embed = head.keep_query_embed, True
+        try:
+            yield from frames
+        finally:
+            head.keep_query_embed = was
+
+    def _track(self, files, gt, evaluator):
         evaluators = list(evaluator) if isinstance(evaluator, (list, tuple)) else [] if evaluator is None else [evaluator]
         for k in {'mot', 'hota'} - ({e.times_key for e in evaluators} if gt is not None else set()):
             self.times.pop(k, None)          # an evaluator's key exists only while a run is scored by it

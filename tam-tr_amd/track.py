@@ -16,6 +16,13 @@ the batch (csrc/gmc.hip states that rule, which is the project's own), or come f
     tracks, tcounts = tracker.update(out, counts, warps=w)      # w f64 [B, 2, 3] in original pixels, device or host
     tracks, tcounts = tracker.update(out, counts)               # identity warps (the reference without an image)
 
+BotSort(device, with_reid=True, reid_dim=D) adds the appearance half of BoT-SORT (the reference writes the rule out and ships no
+encoder for it): every detection comes with a D-vector, either gathered from a per-query embedding by detect_postprocess's `keep`
+(the decoder's hidden state is such an embedding: head.keep_query_embed) or handed in ready:
+
+    tracks, tcounts = tracker.update(out, counts, frames=u8, scale=s, embed=e, keep=keep)   # e f32 | bf16 [B, nqm, D]
+    tracks, tcounts = tracker.update(out, counts, feats=f)                                   # f f32 [B, nq, D], rows aligned with out
+
 MOT evaluation next to it (CLEAR-MOT and identity metrics; the rule is written out in csrc/mot.hip, engine.mot_evaluate states it in
 numpy): one more launch per batch on the rows the tracker left on the device, one launch per sequence for the reduction.
 
@@ -143,24 +150,48 @@ class BotSort(ByteTracker):
     across batches; reset() forgets it.  'none' (or None) never estimates: every warp is the identity unless update() is given
     warps.  'orb', 'sift' and 'ecc' raise ValueError.
     proximity_thresh and appearance_thresh gate ReID embeddings, which the reference itself does not build ("Haven't supported
-    BoT-SORT(reid) yet"): with with_reid off its get_dists is ByteTrack's fused IoU distance, so the constructor accepts and keeps
-    the two thresholds and the kernel does not read them.  with_reid=True raises."""
+    BoT-SORT(reid) yet"): with with_reid off its get_dists is ByteTrack's fused IoU distance, the constructor keeps the two
+    thresholds and the launch does not read them.
+    with_reid=True needs reid_dim=D, the length of the embedding update() will be given per detection (embed + keep, or feats):
+    the table gains state['feat'] f32 [capacity, D], the tracks' smoothed features, and update() launches the ReID instantiation
+    of the kernel (ops.botsort_reid_update; csrc/track.hip states the rule, tests/golden/botsort_reid.npz pins it to the
+    reference's BOTSORT run with a stub encoder).  Which embedding separates identities, and how well, is the caller's matter:
+    nothing here has been measured with trained weights.  A feature row of zero norm is outside the contract."""
 
-    def __init__(self, device, gmc_method='sparseOptFlow', proximity_thresh=0.5, appearance_thresh=0.25, with_reid=False, **kw):
+    def __init__(self, device, gmc_method='sparseOptFlow', proximity_thresh=0.5, appearance_thresh=0.25, with_reid=False, reid_dim=None,
+                 **kw):
         method = 'none' if gmc_method is None else str(gmc_method)
         if method not in GMC_BUILT:
             raise ValueError(f"gmc_method {gmc_method!r} is not built: 'sparseOptFlow' (estimated on the device) and 'none' are; the "
                              "reference's orb, sift and ecc run OpenCV on the host")
-        if with_reid:
-            raise ValueError('with_reid=True is not built: the reference has no ReID encoder for BoT-SORT either')
-        self.gmc_method, self.with_reid = method, False
+        if with_reid and reid_dim is None:
+            raise ValueError('with_reid=True needs reid_dim=D, the length of the embedding each detection comes with (the reference '
+                             'has no ReID encoder for BoT-SORT; update() takes embed + keep, or feats)')
+        if reid_dim is not None and not with_reid:
+            raise ValueError(f'reid_dim={reid_dim!r} has no meaning with with_reid off')
+        if with_reid and not 1 <= int(reid_dim) <= ops.REID_MAX_D:
+            raise ValueError(f'reid_dim must be in 1 .. {ops.REID_MAX_D} with with_reid on, got {reid_dim!r}')
+        self.gmc_method, self.with_reid = method, bool(with_reid)
+        self.reid_dim = int(reid_dim) if with_reid else None
         self.proximity_thresh, self.appearance_thresh = float(proximity_thresh), float(appearance_thresh)
         self.last_warps = self.last_stats = None
         self.gmc, self.gmc_hw, self.gmc_workspace = None, None, None      # the estimator's state, made for the first frames' size
         super().__init__(device, **kw)
+        if self.with_reid:
+            self.state['feat'] = torch.zeros(self.capacity, self.reid_dim, device=self.device, dtype=torch.float32)
+            self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
+
+    def _ws_bytes(self):
+        return (ops.botsort_reid_workspace_bytes if self.with_reid else ops.bytetrack_workspace_bytes)(self.capacity, self.nq)
+
+    def _grow(self, out):
+        if out.dim() == 3 and out.shape[1] > self.nq:
+            self.nq = out.shape[1]
+            self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
 
     def reset(self):
-        """Forget every track and the estimator's previous frame.  No synchronisation."""
+        """Forget every track and the estimator's previous frame.  state['feat'] is left as it is: a slot's row is read only while
+        the slot holds a track, and a new track overwrites it.  No synchronisation."""
         super().reset()
         if self.gmc is not None:
             self.gmc['hdr'].zero_()
@@ -180,22 +211,46 @@ class BotSort(ByteTracker):
         warps, self.last_stats = ops.gmc_estimate(frames, counts, scale, self.gmc, self.gmc_workspace)
         return warps
 
-    def update(self, out, counts, frames=None, scale=None, warps=None):
+    def update(self, out, counts, frames=None, scale=None, warps=None, embed=None, keep=None, feats=None):
         """As ByteTracker.update.  With `frames` (and gmc_method 'sparseOptFlow') the warps are estimated first (estimate_warps) and
         read by the tracker launch where they lie; with `warps` (f64 [B, 2, 3], device tensor, host tensor or array; a host one goes
         up in one copy) nothing is estimated; with neither every warp is the identity, as in the reference when no image is given.
-        The warp of a frame without detections is not applied.  last_warps keeps the device tensor."""
+        The warp of a frame without detections is not applied.  last_warps keeps the device tensor.
+        With ReID on, either `embed` (f32 | bf16 [B, nqm, D], one vector per query) with `keep` (i32 [B, nq], detect_postprocess's)
+        - the rows are gathered and normalised on the device (ops.reid_rows) - or `feats` (f32 [B, nq, D], ready rows aligned with
+        `out`, from any other encoder; they go through the same double normalisation).  With ReID off neither may be given."""
+        given = embed is not None or keep is not None or feats is not None
+        if not self.with_reid and given:
+            raise ValueError('embed / keep / feats were given to a tracker built with with_reid off')
+        if self.with_reid:
+            if feats is not None and (embed is not None or keep is not None):
+                raise ValueError('with_reid: give either embed with keep, or feats, not both')
+            if feats is None and (embed is None or keep is None):
+                raise ValueError('with_reid is on: update() needs embed with keep (gathered by ops.reid_rows), or feats')
+            src = feats if feats is not None else embed
+            if not torch.is_tensor(src) or src.dim() != 3 or src.shape[-1] != self.reid_dim:
+                got = tuple(src.shape) if torch.is_tensor(src) else type(src).__name__
+                raise ValueError(f'with_reid: the embedding must be a tensor [B, n, {self.reid_dim}] (reid_dim), got {got}')
         self._grow(out)
         if warps is None and frames is not None and self.gmc_method == 'sparseOptFlow':
             warps = self.estimate_warps(frames, counts, scale)
         elif warps is not None and not (torch.is_tensor(warps) and warps.is_cuda):
             warps = torch.as_tensor(np.asarray(warps, np.float64)).to(self.device, non_blocking=True)
         self.last_warps = warps
+        if self.with_reid:
+            if feats is not None:      # ready rows: row j of frame b is its own source
+                keep = torch.arange(feats.shape[1], device=feats.device, dtype=torch.int32).expand(feats.shape[0], -1)
+                embed = feats
+            feat = ops.reid_rows(embed, keep, counts)
+            return ops.botsort_reid_update(out, counts, feat, self.state, self.capacity, warps, self.track_high_thresh, self.track_low_thresh,
+                                           self.new_track_thresh, self.match_thresh, self.max_time_lost, self.proximity_thresh,
+                                           self.appearance_thresh, self.workspace)
         return ops.botsort_update(out, counts, self.state, self.capacity, warps, self.track_high_thresh, self.track_low_thresh,
                                   self.new_track_thresh, self.match_thresh, self.max_time_lost, self.workspace)
 
     def state_dict(self):
-        """ByteTracker's table plus the estimator's state (gmc_pyr, gmc_kp, gmc_hdr, gmc_hw) once it exists (synchronises)."""
+        """ByteTracker's table (with ReID on it includes feat f32 [capacity, D]) plus the estimator's state (gmc_pyr, gmc_kp, gmc_hdr,
+        gmc_hw) once it exists (synchronises).  load_state_dict refuses a feat of another D."""
         sd = super().state_dict()
         if self.gmc is not None:
             sd.update({'gmc_' + k: v.cpu().numpy().copy() for k, v in self.gmc.items()})
@@ -203,6 +258,9 @@ class BotSort(ByteTracker):
         return sd
 
     def load_state_dict(self, sd):
+        if ('feat' in sd) != self.with_reid:
+            raise ValueError("the state has a 'feat' table and this tracker was built with with_reid off" if 'feat' in sd else
+                             f"the state has no 'feat' table: this tracker was built with with_reid on (reid_dim {self.reid_dim})")
         super().load_state_dict(sd)
         self.gmc, self.gmc_hw = None, None
         if 'gmc_hw' in sd:
@@ -217,15 +275,21 @@ class BotSort(ByteTracker):
 
 def tracker_from_yaml(path, device, **kw):
     """A tracker yaml with the reference's keys (cfg/trackers/bytetrack.yaml or botsort.yaml) -> ByteTracker or BotSort, by its
-    `tracker_type`; keyword arguments override the file (e.g. gmc_method='none')."""
+    `tracker_type`; keyword arguments override the file (e.g. gmc_method='none', with_reid=True, reid_dim=256)."""
     import yaml
     with open(path) as f:
         cfg = yaml.safe_load(f) or {}
     kind = cfg.get('tracker_type', 'bytetrack')
-    if kind == 'bytetrack':      # which has no use for a gmc_method
-        return ByteTracker(device, **{**{k: cfg[k] for k in YAML_KEYS if k in cfg}, **{k: v for k, v in kw.items() if k != 'gmc_method'}})
-    if kind == 'botsort':
-        return BotSort(device, **{**{k: cfg[k] for k in BOTSORT_YAML_KEYS if k in cfg}, **kw})
+    if kind == 'bytetrack':      # which has no use for a gmc_method or a reid_dim
+        if kw.get('with_reid'):
+            raise ValueError("with_reid is BoT-SORT's: the yaml's tracker_type is 'bytetrack'")
+        return ByteTracker(device, **{**{k: cfg[k] for k in YAML_KEYS if k in cfg},
+                                      **{k: v for k, v in kw.items() if k not in ('gmc_method', 'reid_dim', 'with_reid')}})
+    if kind == 'botsort':      # with_reid: True needs reid_dim from the caller; with it off a reid_dim is dropped
+        args = {**{k: cfg[k] for k in BOTSORT_YAML_KEYS if k in cfg}, **kw}
+        if not args.get('with_reid'):
+            args.pop('reid_dim', None)
+        return BotSort(device, **args)
     raise ValueError(f"tracker_type {kind!r} is not supported: 'bytetrack' and 'botsort' are built")
 
 

@@ -26,7 +26,7 @@
   (e) --hota: the HOTA launches on the same sequence, the same way: the update launch per batch next to the MOT update launch, the
       three end-of-sequence launches, and the host path (the batches' copies plus engine.hota_evaluate).
 
-    python tools/predict_bench.py [--images 64] [--kernel-only] [--track [--botsort]] [--gmc] [--mot] [--hota]
+    python tools/predict_bench.py [--images 64] [--kernel-only] [--track [--botsort [--reid]]] [--gmc] [--mot] [--hota]
 --kernel-only runs only the kernel loop of (a), for a `rocprofv3 --kernel-trace --stats` run of its own.
 """
 import argparse
@@ -202,6 +202,74 @@ def bench_track(n_obj, frames=240, B=4, nq=300, capacity=1024, botsort=False):
             'detections_per_frame': round(float(np.mean([len(f) for f in scene])), 1), 'track_rows': rows, 'ids': int(sd['hdr'][1]) - 1,
             'device_launch_ms_per_frame': round(t_dev / frames, 4), 'host_copy_plus_numpy_twin_ms_per_frame': round(t_host / frames, 3),
             'device_passes_timed': n_dev}
+
+
+def bench_track_reid(n_obj, frames=240, B=4, nq=300, capacity=1024, dim=256, rounds=3):
+    """-> one row: ms per frame of the BoT-SORT launch with ReID (tamtr_botsort_reid_update, feature rows ready), of the gather that
+    makes those rows (tamtr_reid_rows, from an fp32 embedding of all nq queries) and of the plain BoT-SORT launch, on bench_track's
+    scene with one seeded feature axis per object (tests/botsort_reid_np.object_features) at D = dim; the three are timed in turn,
+    `rounds` times, in this process, and the median round is reported; a fourth pass runs the ReID launch with proximity_thresh = -1, which
+    leaves the feature updates and removes the gated pairs' dot products.  The numpy twin says how many pairs passed the gate."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+    import botsort_np as BS
+    import botsort_reid_np as R
+    from tamtr_amd import ops
+    from tamtr_amd.track import BotSort
+    scene, who = R.make_scene(1, n_obj=n_obj, frames=frames, fp_every=3, gaps=[(o, 20 + 7 * o, 5 + 10 * (o % 4)) for o in range(min(n_obj, 8))])
+    warps = BS.camera_path(1, frames, jumps={frames // 2: (40.0, 25.0)})
+    scene = BS.through_camera(scene, warps)
+    feats = R.object_features(1, who, n_obj, dim)
+    rng = np.random.default_rng(1)
+    out, embed, keep = np.zeros((frames, nq, 6), np.float32), rng.normal(size=(frames, nq, dim)).astype(np.float32), np.zeros((frames, nq), np.int32)
+    for i, (f, ft) in enumerate(zip(scene, feats)):
+        out[i, :len(f)] = f
+        keep[i] = rng.permutation(nq)
+        embed[i, keep[i, :len(f)]] = ft
+    out_d, embed_d, keep_d, warps_d = (torch.from_numpy(a).cuda() for a in (out, embed, keep, warps))
+    cnt_d = torch.tensor([len(f) for f in scene], dtype=torch.int32).cuda()
+    plain, reid = BotSort('cuda', capacity=capacity, nq=nq, gmc_method='none'), BotSort('cuda', capacity=capacity, nq=nq, gmc_method='none', with_reid=True,
+                                                                                         reid_dim=dim)
+    feat_d = torch.cat([ops.reid_rows(embed_d[i:i + B], keep_d[i:i + B], cnt_d[i:i + B]) for i in range(0, frames, B)])
+
+    def plain_pass():
+        plain.reset()
+        for i in range(0, frames, B):
+            plain.update(out_d[i:i + B], cnt_d[i:i + B], warps=warps_d[i:i + B])
+
+    def reid_pass():
+        reid.reset()
+        for i in range(0, frames, B):
+            ops.botsort_reid_update(out_d[i:i + B], cnt_d[i:i + B], feat_d[i:i + B], reid.state, capacity, warps_d[i:i + B], reid.track_high_thresh,
+                                    reid.track_low_thresh, reid.new_track_thresh, reid.match_thresh, reid.max_time_lost, reid.proximity_thresh,
+                                    reid.appearance_thresh, reid.workspace)
+
+    def reid_pass_ungated():      # proximity_thresh = -1: no pair passes the gate, so no embedding distance is computed; the matches (and with
+        reid.reset()              # them the feature updates) are plain BoT-SORT's
+        for i in range(0, frames, B):
+            ops.botsort_reid_update(out_d[i:i + B], cnt_d[i:i + B], feat_d[i:i + B], reid.state, capacity, warps_d[i:i + B], reid.track_high_thresh,
+                                    reid.track_low_thresh, reid.new_track_thresh, reid.match_thresh, reid.max_time_lost, -1.0,
+                                    reid.appearance_thresh, reid.workspace)
+
+    def gather_pass():
+        for i in range(0, frames, B):
+            ops.reid_rows(embed_d[i:i + B], keep_d[i:i + B], cnt_d[i:i + B])
+
+    t = {'plain': [], 'reid': [], 'reid_ungated': [], 'gather': []}
+    for _ in range(rounds):
+        for k, fn in (('plain', plain_pass), ('reid_ungated', reid_pass_ungated), ('reid', reid_pass), ('gather', gather_pass)):
+            t[k].append(timed(fn, min_s=0.7, warmup=1, chunk=2)[0] / frames)
+    sd = reid.state_dict()
+    reid.check_overflow(sd['hdr'][3])
+    twin = R.BotSortReidNp(dim, capacity=capacity)
+    rows = sum(len(twin.update(f, w, ft)) for f, w, ft in zip(scene, warps, feats))
+    ev = twin.events
+    med = lambda v: round(float(np.median(v)), 4)      # noqa: E731
+    return {'tracker': 'botsort+reid', 'objects': n_obj, 'frames': frames, 'frames_per_launch': B, 'nq': nq, 'capacity': capacity, 'D': dim,
+            'detections_per_frame': round(float(np.mean([len(f) for f in scene])), 1), 'track_rows': rows, 'ids': int(sd['hdr'][1]) - 1,
+            'same_header_as_the_numpy_twin': bool(np.array_equal(sd['hdr'], twin.state['hdr'])), 'gated_pairs_per_frame': round((ev['pairs'] - ev['prox_masked']) / frames, 1), 'cost_pairs_per_frame': round(ev['pairs'] / frames, 1),
+            'feature_updates_per_frame': round((ev['match1'] + ev['match2'] + ev['match_unconfirmed']) / frames, 1),
+            'reid_launch_ms_per_frame': med(t['reid']), 'reid_launch_without_gated_pairs_ms_per_frame': med(t['reid_ungated']), 'gather_ms_per_frame': med(t['gather']), 'plain_botsort_launch_ms_per_frame': med(t['plain']),
+            'rounds_ms_per_frame': {k: [round(x, 4) for x in v] for k, v in t.items()}}
 
 
 def bench_gmc(frames=8, S=640, B=4, nq=300, n_obj=60, repeats=7):
@@ -430,6 +498,8 @@ def main():
     ap.add_argument('--kernel-only', action='store_true')
     ap.add_argument('--track', action='store_true', help='only (c): the tracker launch against copy + numpy twin')
     ap.add_argument('--botsort', action='store_true', help='with --track: the BoT-SORT form of the launch, with warps on the device')
+    ap.add_argument('--reid', action='store_true', help='with --track --botsort: the ReID launch and the feature gather next to the plain BoT-SORT '
+                    'launch on the same scene, D = 256')
     ap.add_argument('--gmc', action='store_true', help="only (c'): BoT-SORT's camera-motion estimate and tracker launch on a 640 x 640 sequence")
     ap.add_argument('--mot', action='store_true', help='only (d): the MOT evaluation launches against copy + numpy twin')
     ap.add_argument('--hota', action='store_true', help='only (e): the HOTA launches against copy + numpy twin, on the sequence of --mot')
@@ -441,6 +511,10 @@ def main():
         print('(c) tracker per frame: one launch per 4 frames (device events) vs device-to-host copy + numpy twin (host clock; numpy and scipy, not the reference with lap)')
         for n_obj in (24, 100):
             print(json.dumps(bench_track(n_obj, botsort=args.botsort)))
+        if args.botsort and args.reid:
+            print('(c+) BoT-SORT with ReID per frame: the ReID launch (rows ready), the gather of the rows and the plain launch, timed in turn (device events)')
+            for n_obj in (24, 100):
+                print(json.dumps(bench_track_reid(n_obj)))
         return
     if args.gmc:
         print("(c') BoT-SORT with camera-motion compensation, per frame: the estimate's launches and the tracker launch per 4 frames (device events) vs one "

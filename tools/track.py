@@ -6,14 +6,16 @@ as they are made (CLEAR-MOT and identity metrics, tam-tr_amd/csrc/mot.hip): a ta
 --hota scores them by HOTA as well (tam-tr_amd/csrc/hota.hip): its tables next to the others and a `hota` key in mot_metrics.json.
 
     python tools/track.py --weights runs/train/TAMTR/best.pt --text-feats clip_vitb32.npz --data dataset.yaml \
-        --source sequences/ [--tracker bytetrack.yaml | --tracker botsort.yaml [--gmc none]] --conf 0.1 --batch 4 --save-mot [--save --save-txt --save-conf] [--gt annotations/]
+        --source sequences/ [--tracker bytetrack.yaml | --tracker botsort.yaml [--gmc none] [--reid on]] --conf 0.1 --batch 4 --save-mot [--save --save-txt --save-conf] [--gt annotations/]
 
 --source is a directory of frames (one sequence, frames in sorted order) or a directory of sequence directories (the VisDrone-MOT
 `sequences/<name>/` layout); the tracker is reset for every sequence.  --save-mot writes <save_dir>/<sequence>.txt with lines
 `frame,id,left,top,width,height,score,category,-1,-1`, frames 1-based.  --tracker takes the reference's bytetrack.yaml or botsort.yaml (track.tracker_from_yaml); BoT-SORT runs on
 the device as well: the tracker rule (XYWH filter, warped track states) in the tracker launch, and the camera-motion warps
 (gmc_method: sparseOptFlow, the reference's default) estimated from each batch's uploaded frames in at most four more launches
-(tam-tr_amd/csrc/gmc.hip).  --gmc overrides the yaml's gmc_method: `none` runs identity warps.
+(tam-tr_amd/csrc/gmc.hip).  --gmc overrides the yaml's gmc_method: `none` runs identity warps.  --reid overrides the yaml's with_reid:
+`on` adds BoT-SORT's appearance association with the decoder's per-query hidden state as the embedding of a detection (gathered
+and compared on the device; how well those embeddings tell identities apart with trained weights has not been measured).
 --gt is a directory of VisDrone-MOT annotation files <sequence>.txt (track.read_mot states how categories become classes and kinds);
 a sequence without a file there is tracked but not scored.
 """
@@ -41,6 +43,8 @@ def parse_args(argv=None):
                     "bytetrack.yaml's values")
     ap.add_argument('--gmc', choices=['sparseOptFlow', 'none'], help="with a botsort.yaml: override its gmc_method (sparseOptFlow = warps "
                     "estimated on the device from the frames, none = identity warps)")
+    ap.add_argument('--reid', choices=['on', 'off'], help="with a botsort.yaml: override its with_reid (on = appearance association on the "
+                    "decoder's query embeddings, next to IoU; off = IoU only)")
     ap.add_argument('--capacity', type=int, default=1024, help='tracks the device table holds')
     ap.add_argument('--imgsz', type=int, default=640)
     ap.add_argument('--batch', type=int, default=4)
@@ -62,6 +66,8 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if (args.text_feats is None) == (args.clip_weights is None and args.clip_vocab is None) or (args.clip_weights is None) != (args.clip_vocab is None):
         ap.error('give either --text-feats, or --clip-weights together with --clip-vocab (not both, not neither)')
+    if args.reid and not args.tracker:
+        ap.error('--reid overrides a botsort.yaml: give --tracker')
     return args
 
 
@@ -97,7 +103,8 @@ def main(argv=None):
     pred = Predictor(model, names, D.TextFeatures.from_args(args.text_feats, args.clip_weights, args.clip_vocab, dev), imgsz=args.imgsz, conf=args.conf,
                      iou=args.iou, classes=args.classes, single_cls=args.single_cls, batch=args.batch, dtype=args.dtype)
     if args.tracker:
-        tracker = tracker_from_yaml(args.tracker, dev, capacity=args.capacity, **({'gmc_method': args.gmc} if args.gmc else {}))
+        over = {**({'gmc_method': args.gmc} if args.gmc else {}), **({'with_reid': args.reid == 'on'} if args.reid else {})}
+        tracker = tracker_from_yaml(args.tracker, dev, capacity=args.capacity, reid_dim=model.model[-1].hidden_dim, **over)
     else:
         tracker = ByteTracker(dev, capacity=args.capacity)
     save_dir = increment_path(os.path.join(args.project, args.name), exist_ok=args.exist_ok)
