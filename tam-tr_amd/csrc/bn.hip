@@ -89,9 +89,12 @@ __device__ __forceinline__ void combine_slices(const float* __restrict__ part, i
   for (int s = threadIdx.x; s < S; s += BN_THREADS) {
     const float* p = part + ((size_t)c * S + s) * 3;
     const float nb = p[0], mb = p[1], m2b = p[2];
-    const float nt = n + nb, d = mb - mean;
-    mean += d * (nb / nt);
-    m2 += m2b + d * d * (n * nb / nt);
+    const float nt = n + nb;
+    if (nt > 0.f) {   // an empty partial is a no-op, as in the stages below
+      const float d = mb - mean;
+      mean += d * (nb / nt);
+      m2 += m2b + d * d * (n * nb / nt);
+    }
     n = nt;
   }
 #pragma unroll

@@ -1,6 +1,7 @@
 """fp64 references with an error model for the bf16 hot-path kernels (tests/test_gpu_bf16_kernels.py, tests/test_ref64_host.py) and for the
 text gate and CPAM kernels in fp32 and bf16 (tests/test_gpu_gates_ref64.py), and for the LayerNorm, cross-merge and depthwise SS2D kernels
-(tests/test_gpu_ss2d_ref64.py), and for the MFMA linear and x_proj kernels (tests/test_gpu_gemm_ref64.py).
+(tests/test_gpu_ss2d_ref64.py), and for the MFMA linear and x_proj kernels (tests/test_gpu_gemm_ref64.py), and for the BatchNorm kernels of
+csrc/bn.hip in both layouts, the pair, the segmented form and the statistics alone (tests/test_gpu_bn_ref64.py).
 
 Every reference takes the operands exactly as the kernel sees them (bf16 tensors, fp32 side inputs), promotes them to float64 and
 computes on the CPU.  Next to each value it returns a magnitude: the same computation on absolute values.  check() then asserts,
@@ -799,3 +800,216 @@ def xproj_bounds(B, D, L, plane_bf16):
     """{name: (a, b)} for xproj()'s outputs; the counts are written out in xproj()'s docstring."""
     fwd = (1, fp32_b(D + 1))
     return {'dtr': fwd, 'Bs': fwd, 'Cs': fwd, 'gu2': (1 if plane_bf16 else 0, 1.0), 'dw': (0, fp32_b(min(L, XP_SLICE) + B * xproj_slices(L)))}
+
+
+# ------------------------------------------------------------------------------------------------ BatchNorm (csrc/bn.hip)
+def _rows(t):
+    """[N, C] as it is, an NCHW map given as [B, C, HW] permuted to [B * HW, C]; fp64."""
+    t = _d(t)
+    return t if t.dim() == 2 else t.permute(0, 2, 1).reshape(-1, t.shape[1])
+
+
+def _bn_parts(x, chunk_rows, parts):
+    """The rows of each partial triple, as a partial index per row: an NCHW map [B, C, HW]: image by image, slices of BN_SLICE pixels;
+    channels-last rows with chunk_rows: chunks of that many rows; parts: a list of row counts (hand-made partials); else one partial."""
+    if x.dim() == 3:
+        B, _, HW = x.shape
+        sh = -(-HW // BN_SLICE)
+        return (torch.arange(B).view(B, 1) * sh + torch.arange(HW).view(1, HW) // BN_SLICE).reshape(-1)
+    if chunk_rows is not None:
+        return torch.arange(x.shape[0]) // chunk_rows
+    if parts is not None:
+        return torch.repeat_interleave(torch.arange(len(parts)), torch.tensor(parts))
+    return torch.zeros(x.shape[0], dtype=torch.long)
+
+
+def _bn_stats(x, eps, pid, shifted):
+    """Batch statistics of the rows x [N, C] (fp64) and their magnitudes; pid: the partial (slice | chunk) of each row.  A channel that
+    holds a NaN or an Inf has NaN statistics: the kernels' Chan combine forms inf - inf, or inf * 0 against an empty lane, for it
+    (nn.BatchNorm2d would report a mean of inf; check() could not hold an inf anyway).
+
+    Magnitudes.  mean: the NCHW kernels sum x itself, M = mean|x|.  The channels-last kernels (shifted) sum d = x - k, k the first row of
+    the row's chunk, and add k back: M = mean(|k| + |d|).  var: a sum of squares, relative to itself, where the squares are those the
+    kernel forms: (x - slice mean)^2 and the Chan terms for NCHW (they add up to N var), d^2 for channels-last, whose
+    M2 = s2 - s1 s1 / n inherits the roundings of s2 = sum d^2 (spread = mean d^2 >= var).  Besides, a Chan combine adds
+    n_A n_B / (n_A + n_B) (mean_B - mean_A)^2 from rounded means: an error e in either moves it by at most 2 e times
+    sum over the partials s of A and B of n_s |mean_s - mean|, in first order; over one level of combines that is 2 e N D, D the weighted
+    mean of |mean_s - mean| (0 for one partial): m_var = spread + 2 D M, and bn_stat_counts() counts the levels.  rstd = (var + eps)^-1/2
+    moves by rstd / 2 per relative change of var + eps: m_rstd = rstd (1 + rho), rho = m_var / (2 (var + eps)).  xhat = (x - mean) rstd:
+    X = |xhat| (1 + rho) + rstd M, as layer_norm() has it with rho = 0 (its variance is one exact two-pass)."""
+    N = x.shape[0]
+    bad = ~torch.isfinite(x).all(0)
+    nan = torch.full_like(x[0], float('nan'))
+    mean = torch.where(bad, nan, x.mean(0))
+    var = ((x - mean) ** 2).mean(0)
+    S = int(pid.max()) + 1
+    n_s = torch.bincount(pid, minlength=S).double().view(S, 1)
+    mean_s = torch.zeros(S, x.shape[1], dtype=torch.float64).index_add_(0, pid, x) / n_s
+    D = (n_s * (mean_s - mean).abs()).sum(0) / N
+    if shifted:
+        first = torch.cat([torch.zeros(1, dtype=torch.long), torch.cumsum(n_s.view(-1).long(), 0)[:-1]])
+        k = x[first[pid]]
+        M, spread = (k.abs() + (x - k).abs()).mean(0), ((x - k) ** 2).mean(0)
+    else:
+        M, spread = x.abs().mean(0), var
+    m_var = spread + 2 * D * M
+    rstd = (var + eps).rsqrt()
+    rho = m_var / (2 * (var + eps))
+    xh = (x - mean) * rstd
+    return {'mean': mean, 'var': var, 'rstd': rstd, 'M': M, 'm_var': m_var, 'rho': rho, 'xh': xh, 'X': xh.abs() * (1 + rho) + rstd * M}
+
+
+def _bn_act(z, m_z, act):
+    """act(z), its magnitude, act'(z), its magnitude (identity: act' is an exact 1).  SiLU as dwconv_silu_cross() has it, with the
+    derivative's magnitude sig_mag(s, m_z) (1 + |z|): s' = s (1 + z (1 - s)) carries s's error 1 + |z| times and z's twice."""
+    if not act:
+        one = torch.ones_like(z)
+        return z, m_z, one, one
+    s = torch.sigmoid(z)
+    m_s = sig_mag(s, m_z)
+    return z * s, m_z * m_s, s * (1 + z * (1 - s)), m_s * (1 + z.abs())
+
+
+def _bn_running(st, N, momentum, rm, rv):
+    unb = N / (N - 1) if N > 1 else 1.0           # one value per channel: the biased variance (bn_finalize_kernel, n > 1.f ?)
+    rm, rv = _d(rm), _d(rv)
+    return {'running_mean': ((1 - momentum) * rm + momentum * st['mean'], (1 - momentum) * rm.abs() + momentum * st['M']),
+            'running_var': ((1 - momentum) * rv + momentum * st['var'] * unb, (1 - momentum) * rv.abs() + momentum * st['m_var'] * unb)}
+
+
+def _bn_core(xs, gammas, betas, gout, eps, momentum, rms, rvs, act, residual, chunk_rows, parts=None):
+    """act(sum_i bn_i(x_i)) [+ residual] and its backward for one or two BatchNorms over the same [N, C] shape."""
+    pid = _bn_parts(xs[0], chunk_rows, parts)
+    xs = [_rows(x) for x in xs]
+    N = xs[0].shape[0]
+    g = _rows(gout)
+    sts = [_bn_stats(x, eps, pid, chunk_rows is not None) for x in xs]
+    ga, be = [_d(t) for t in gammas], [_d(t) for t in betas]
+    z = sum(a * st['xh'] for a, st in zip(ga, sts)) + sum(be)
+    m_z = sum(a.abs() * st['X'] for a, st in zip(ga, sts)) + sum(b.abs() for b in be)
+    y, m_y, d, m_d = _bn_act(z, m_z, act)
+    fin = torch.isfinite(z)
+    res = {'zmax': float(z[fin].abs().max()) if bool(fin.any()) else 0.0}
+    if residual is not None:
+        r = _rows(residual)
+        y, m_y = y + r, m_y + r.abs()
+        res['dres'] = (g, g.abs())
+    res['out'] = (y, m_y)
+    dz, m_dz = g * d, g.abs() * m_d
+    db, m_db = dz.sum(0), m_dz.sum(0)
+    for i, (a, st) in enumerate(zip(ga, sts)):
+        s = '' if len(xs) == 1 else str(i + 1)
+        dg, m_dg = (dz * st['xh']).sum(0), (m_dz * st['X']).sum(0)
+        res['dgamma' + s], res['dbeta' + s] = (dg, m_dg), (db, m_db)
+        res['dx' + s] = (a * st['rstd'] * (dz - db / N - st['xh'] * dg / N),
+                         a.abs() * st['rstd'] * (1 + st['rho']) * (m_dz + m_db / N + st['X'] * m_dg / N))
+        res['mean' + s], res['rstd' + s] = (st['mean'], st['M']), (st['rstd'], st['rstd'] * (1 + st['rho']))
+        if rms[i] is not None:
+            for n, v in _bn_running(st, N, momentum, rms[i], rvs[i]).items():
+                res[n + s] = v
+    return res
+
+
+def batch_norm(x, gamma, beta, gout, eps, momentum, running_mean, running_var, act, residual=None, chunk_rows=None, parts=None):
+    """csrc/bn.hip: out = act(BatchNorm(x; gamma, beta)) [+ residual] with batch statistics (nn.BatchNorm2d in training mode), act =
+    identity (0) | SiLU (1), the running statistics after the call, and dx, dgamma, dbeta [, dres] for the cotangent gout.
+
+    x, gout [, residual] [N, C], or an NCHW map as [B, C, HW] (results come back as [N, C] rows, image-major); operands as the kernel
+    reads them.  rstd from the biased variance, the running variance from the unbiased one (the biased one where a channel has one
+    value).  running_mean = None: no running statistics.  chunk_rows: the rows of one workgroup's chunk of the channels-last kernels
+    (bn_cases.cl_plan); it changes no value, only the magnitudes of the statistics (_bn_stats).  No intermediate rounding: out and dx
+    are stored in x's dtype, everything else in fp32; the residual is added in fp32 before the one rounding.
+    Returns {name: (value, magnitude)} for out, dx, dgamma, dbeta, mean, rstd, running_mean,
+    running_var, dres, and 'zmax' (the largest finite |gamma xhat + beta|: the range of __expf)."""
+    return _bn_core([x], [gamma], [beta], gout, eps, momentum, [running_mean], [running_var], act, residual, chunk_rows, parts)
+
+
+def batch_norm_pair(x1, x2, gamma1, beta1, gamma2, beta2, gout, eps, momentum, running_mean1, running_var1, running_mean2, running_var2, act,
+                    chunk_rows=None):
+    """csrc/bn.hip tamtr_bncl2_act_*: out = act(bn1(x1) + bn2(x2)), both in training mode over the same [N, C] shape.  As batch_norm();
+    the names carry the BatchNorm's number: dx1, dx2, dgamma1, ..., running_var2 (dbeta1 == dbeta2)."""
+    return _bn_core([x1, x2], [gamma1, gamma2], [beta1, beta2], gout, eps, momentum, [running_mean1, running_mean2], [running_var1, running_var2],
+                    act, None, chunk_rows)
+
+
+BN_SLICE = 4096       # csrc/bn.hip BN_SLICE: the elements of one (image, channel) plane that one workgroup of the NCHW kernels holds
+
+
+def bn_combine_steps(S):
+    """Chan combines behind one channel in combine_slices: a thread's strided loop over ceil(S / 256) triples, the 64-lane butterfly (6),
+    the 4 waves in order (4).  A combine with an empty triple changes nothing, so this is an upper bound at small S."""
+    return -(-S // 256) + 6 + 4
+
+
+def bn_stat_counts(layout, plan):
+    """(roundings behind the batch mean, roundings behind var + eps) for a plan of tests/bn_cases.py, counted from csrc/bn.hip.
+
+    One Chan combine: d = mb - mean (1), nb / nt (1), d * (.) (1), mean += (1): 4 on the mean; n * nb (1), / nt (1), d * d (1, and d's
+    own rounding twice: 2), * (1), + m2b (1), m2 += (1): 8 on M2, less the one that d shares with the mean's count: 7.
+    NCHW (bn_stats_kernel, exact two-pass inside a slice): mean_s = 16 elements per thread in sequence (16), butterfly (6), 4 waves
+    (4), / n (1) = 27; M2_s = d = v - mean_s counts twice in d^2 (2), 16 FMAs (16), butterfly (6), waves (4) = 28.
+    Channels-last (bncl_stats_kernel, sums of d = x - k and d^2): d (1), iters additions per thread, 256 / cg in fold_row_lanes, s1 / n
+    (1), k + m (1): iters + 256 / cg + 3 on the mean; s2 the same chain with d twice and without the last two: iters + 256 / cg + 2;
+    M2 = s2 - s1 m: the product and the difference (2), and s1 m carries s1's chain twice (s1 and m = s1 / n; (sum |d|)^2 / n <= sum d^2):
+    3 (iters + 256 / cg) + 8.
+    var + eps: M2's count, / n (1).  The first-order term of _bn_stats (2 D M) carries the mean's count twice (d = mb - mean has the errors
+    of both) once per level of combines that a partial can pass: min(S - 1, bn_combine_steps(S)).  The two terms of m_var are separate,
+    so the larger count holds for both."""
+    if layout == 'nchw':
+        S = plan[2]
+        c_mean, c_m2 = 27, 28
+    else:
+        V, cg, iters, _, S = plan
+        c_mean, c_m2 = iters + 256 // cg + 3, 3 * (iters + 256 // cg) + 8
+    T = bn_combine_steps(S)
+    n_mean = c_mean + 4 * T
+    return n_mean, max(c_m2 + 7 * T + 1, 2 * n_mean * min(S - 1, T))
+
+
+def bn_sum_chain(layout, plan):
+    """Additions behind one backward sum (sum dz, sum dz xhat): NCHW: 16 FMAs per thread, block_sum (6 + 4) per slice, then every apply
+    workgroup's strided loop over ceil(S / 256) partials and block_sum (10).  Channels-last: iters per thread, 256 / cg in fold_row_lanes,
+    then bncl_sum_kernel: ceil(S / 256) and block_sum (10)."""
+    if layout == 'nchw':
+        return 16 + 10 + -(-plan[2] // 256) + 10
+    V, cg, iters, _, S = plan
+    return iters + 256 // cg + -(-S // 256) + 10
+
+
+def bn_bounds(layout, plan, bf16, act, zmax=None, residual=False):
+    """{name: (a, b)} for batch_norm()'s outputs (layout 'nchw' | 'cl') and batch_norm_pair()'s ('cl2'); plan = bn_cases.nchw_plan() or
+    cl_plan().  zmax: ref['zmax'], needed for SiLU.  Every figure is a count of fp32 roundings along the kernel's chain:
+      mean          bn_stat_counts()[0]; running_mean: 1 - momentum, two products, the sum (4) more
+      rstd          n_var = bn_stat_counts()[1], then eps as an fp32 constant (1), + eps (1), rsqrtf (2): n_var + 4
+      running_var   n_var, n - 1 is exact, / (1), 1 - momentum, two products, the sum (4): n_var + 5
+      xhat          rstd (n_var + 4), x - mean (1; the mean's count is below n_var and multiplies a separate term of X), * rstd (1): n_var + 6
+      z             a = rstd gamma (1), the FMA (1): n_var + 8; the backward forms (x - mean) rstd, then the FMA with gamma and beta: the same;
+                    the pair adds beta1 + beta2 (1) and the second FMA (1)
+      out           identity: z.  SiLU: z, 1 + e, the division, the product form (3) and one __expf.  A residual: the sum (1).
+      dz            identity: exact (gout times 1).  SiLU: z twice (_bn_act), s = 1 / (1 + e) (2 and __expf), 1 - s, z (.), 1 + (.), s (.),
+                    gout (.) (5)
+      dbeta         dz and bn_sum_chain(); dgamma: dz, xhat, the product (1), bn_sum_chain()
+      dx            gamma rstd (n_var + 4 and 1), dz, k1 = sum dz / N: 1 / N as an fp32 constant and the product (2) on dbeta's chain, xhat k2:
+                    xhat, the product (1), the same 2 on dgamma's chain (which holds dz and xhat again); two differences, the last product (3)
+    a = 1 where the kernel stores bf16 (out, dx; a residual is added in fp32 and the sum rounded once); everything else is fp32.  dres is
+    gout itself: (0, 0), an exact copy."""
+    lay = 'cl' if layout == 'cl2' else layout
+    n_mean, n_var = bn_stat_counts(lay, plan)
+    chain = bn_sum_chain(lay, plan)
+    a = 1 if bf16 else 0
+    e = expf_b(zmax) if act else 0.0
+    n_xhat = n_var + 6
+    n_z = n_var + 8 + (2 if layout == 'cl2' else 0)
+    b_out = fp32_b(n_z + (3 if act else 0) + (1 if residual else 0)) + e
+    b_dz = fp32_b(2 * n_z + 2 + 5) + e if act else 0.0
+    b_db = b_dz + fp32_b(chain)
+    b_dg = b_dz + fp32_b(n_xhat + 1 + chain)
+    b_dx = fp32_b(n_var + 5) + b_dz + fp32_b(2 + n_xhat + 1) + b_dg + fp32_b(3)
+    one = {'out': (a, b_out), 'dx': (a, b_dx), 'dgamma': (0, b_dg), 'dbeta': (0, b_db), 'mean': (0, fp32_b(n_mean)), 'rstd': (0, fp32_b(n_var + 4)),
+           'running_mean': (0, fp32_b(n_mean + 4)), 'running_var': (0, fp32_b(n_var + 5)), 'dres': (0, 0.0)}
+    if layout != 'cl2':
+        return one
+    two = {'out': one['out']}
+    for n in ('dx', 'dgamma', 'dbeta', 'mean', 'rstd', 'running_mean', 'running_var'):
+        two[n + '1'] = two[n + '2'] = one[n]
+    return two

@@ -1051,3 +1051,356 @@ def test_xproj_mutants_fail():
     old, new = run((2, 256, 1032, 16), 'dw', 'second dW slice (8 pixels) dropped', drop_second_slice=True)
     assert not new
     _report_mutants('xproj')
+
+
+# ================================================================================================ BatchNorm (tests/bn_cases.py)
+import bn_cases as K
+
+
+def _f(v):
+    return torch.tensor(v, dtype=torch.float32)
+
+
+def _fma(a, b, c):
+    """fmaf: the product of two fp32 values is exact in fp64; the sum is rounded to fp64 and then to fp32 (the second rounding is the one
+    that counts)."""
+    return (a.double() * b.double() + c.double()).float()
+
+
+def _chan(a, b):
+    """One Chan combine of (n, mean, M2) triples as combine_slices does it, an empty result left alone."""
+    (n, mean, m2), (nb, mb, m2b) = a, b
+    nt = n + nb
+    ok = nt > 0
+    div = torch.where(ok, nt, torch.ones_like(nt))
+    d = mb - mean
+    return nt, torch.where(ok, mean + d * (nb / div), mean), torch.where(ok, m2 + (m2b + d * d * (n * nb / div)), m2)
+
+
+def emu_bn_combine(part):
+    """combine_slices on partials [C, S, 3]: thread t takes triples t, t + 256, ... in sequence, the 64-lane butterfly, the 4 waves in order."""
+    C, S, _ = part.shape
+    rounds = -(-S // 256)
+    p = torch.zeros(C, rounds * 256, 3)
+    p[:, :S] = part
+    p = p.view(C, rounds, 256, 3)
+    acc = tuple(torch.zeros(C, 256) for _ in range(3))
+    for r in range(rounds):
+        acc = _chan(acc, tuple(p[:, r, :, i] for i in range(3)))
+    lanes = torch.arange(256)
+    for o in (32, 16, 8, 4, 2, 1):
+        acc = _chan(acc, tuple(t[:, lanes ^ o] for t in acc))
+    tot = tuple(torch.zeros(C) for _ in range(3))
+    for w in range(4):
+        tot = _chan(tot, tuple(t[:, 64 * w] for t in acc))
+    return tot
+
+
+def emu_bn_finalize(part, eps, mom, rm, rv, rv_biased=False, rstd_unbiased=False):
+    """bn_finalize_kernel / the head of bn_apply_kernel -> {mean, rstd, running_mean, running_var}.  Mutants: the running variance updated
+    with the biased variance; rstd taken from the unbiased one."""
+    n, mean, m2 = emu_bn_combine(part)
+    var = m2 / n
+    unb = torch.where(n > 1, m2 / (n - 1).clamp_min(1), var)
+    got = {'mean': mean, 'rstd': torch.rsqrt((unb if rstd_unbiased else var) + _f(eps))}
+    if rm is not None:
+        keep = _f(1.0) - _f(mom)
+        got.update({'running_mean': keep * rm + _f(mom) * mean, 'running_var': keep * rv + _f(mom) * (var if rv_biased else unb)})
+    return got
+
+
+def _bn_gather(layout, dims, plan, N):
+    """Row indices [S, L] of every partial's rows and the mask of the real ones; a slot past the end re-reads the partial's first row
+    (the channels-last kernels' redirected load)."""
+    if layout == 'nchw':
+        B, HW = dims
+        sh = plan[1]
+        starts = (torch.arange(B).view(B, 1) * HW + torch.arange(sh).view(1, sh) * R.BN_SLICE).reshape(-1)
+        lens = torch.tensor([min(R.BN_SLICE, HW - s * R.BN_SLICE) for s in range(sh)]).repeat(B)
+    else:
+        starts = torch.arange(plan[4]) * plan[3]
+        lens = (N - starts).clamp_max(plan[3])
+    L = int(lens.max())
+    mask = torch.arange(L).view(1, L) < lens.view(-1, 1)
+    idx = torch.where(mask, starts.view(-1, 1) + torch.arange(L).view(1, L), starts.view(-1, 1))
+    return idx, mask, lens.float()
+
+
+def _bn_partials(layout, xf, idx, mask, lens, tail_4096=False, unshifted=False):
+    """bn_stats_kernel (two-pass inside a slice) | bncl_stats_kernel (sums of x - k and (x - k)^2, M2 = s2 - s1 m) -> [C, S, 3].
+    Mutants: the NCHW tail slice counted as 4096 elements; the channels-last sums taken of x itself."""
+    xp, m = xf[idx], mask.unsqueeze(-1)
+    n = lens.view(-1, 1)
+    if layout == 'nchw':
+        cnt = torch.full_like(n, float(R.BN_SLICE)) if tail_4096 else n
+        mean = torch.where(m, xp, torch.zeros(())).sum(1) / cnt
+        d = torch.where(m, xp - mean.unsqueeze(1), torch.zeros(()))
+        m2 = (d * d).sum(1)
+        n = cnt
+    else:
+        k = torch.zeros_like(xp[:, 0]) if unshifted else xp[:, 0]
+        d = xp - k.unsqueeze(1)
+        if unshifted:
+            d = torch.where(m, d, torch.zeros(()))
+        s1, s2 = d.sum(1), (d * d).sum(1)
+        mm = s1 / n
+        mean, m2 = k + mm, s2 - s1 * mm
+    return torch.stack([n.expand_as(mean), mean, m2], -1).permute(1, 0, 2).contiguous()
+
+
+def _silu(z):
+    return z / (1 + torch.exp(-z))
+
+
+def _dsilu(z):
+    s = 1 / (1 + torch.exp(-z))
+    return s * (1 + z * (1 - s))
+
+
+def emu_bn(layout, dims, plan, x, gamma, beta, gout, eps, mom, rm, rv, act, residual=None, tail_4096=False, unshifted=False, rv_biased=False,
+           rstd_unbiased=False, no_live=False, no_k2=False, dsilu_at_xhat=False, z_bf16=False, res_after_store=False):
+    """The body of emu_bn_nchw / emu_bn_cl: one BatchNorm in either layout on rows [N, C] (layout 'nchw': dims = (B, HW), rows image-major), fp32
+    arithmetic in the kernels' order: slice-wise two-pass | shift-by-first-row sums, the Chan combine, the apply with a = rstd gamma in one
+    FMA, the backward from the stored mean and rstd with per-partial sums; bf16 rounding only at the stores.  Mutants: see the arguments."""
+    st = bf if x.dtype == BF16 else (lambda t: t)
+    N, C = x.shape
+    xf, g = x.float(), gout.float()
+    idx, mask, lens = _bn_gather(layout, dims, plan, N)
+    got = emu_bn_finalize(_bn_partials(layout, xf, idx, mask, lens, tail_4096, unshifted), eps, mom, rm, rv, rv_biased, rstd_unbiased)
+    mean, rstd = got['mean'], got['rstd']
+    z = _fma(xf - mean, rstd * gamma, beta)
+    if z_bf16:
+        z = bf(z)
+    y = _silu(z) if act else z
+    if residual is not None:
+        y = st(st(y) + residual.float()) if res_after_store else y + residual.float()
+        got['dres'] = gout.clone()
+    got['out'] = st(y)
+    xh = (xf - mean) * rstd
+    dz = g * (_dsilu(xh if dsilu_at_xhat else _fma(xh, gamma, beta)) if act else torch.ones(()))
+    live = torch.ones_like(mask) if no_live else mask
+    s1 = torch.where(live.unsqueeze(-1), dz[idx], torch.zeros(())).sum(1).sum(0)
+    s2 = torch.where(live.unsqueeze(-1), (dz * xh)[idx], torch.zeros(())).sum(1).sum(0)
+    inv = _f(1.0) / _f(float(N))
+    got['dbeta'], got['dgamma'] = s1, s2
+    got['dx'] = st(gamma * rstd * (dz - s1 * inv - (0 if no_k2 else xh * (s2 * inv))))
+    return got
+
+
+def emu_bn_nchw(B, HW, plan, *args, **mut):
+    """tamtr_bn_act_fwd / _bwd on rows [B * HW, C] (image-major)."""
+    return emu_bn('nchw', (B, HW), plan, *args, **mut)
+
+
+def emu_bn_cl(plan, *args, **mut):
+    """tamtr_bncl_act_fwd / _bwd on rows [N, C]."""
+    return emu_bn('cl', None, plan, *args, **mut)
+
+
+def emu_bn_pair(plan, x1, x2, p1, p2, gout, eps, mom, act, drop_beta2=False, swap_k=False):
+    """tamtr_bncl2_act_*: both statistics as emu_bn, z = fma(x2 - m2, a2, fma(x1 - m1, a1, beta1 + beta2)).  Mutants: bn2's beta dropped;
+    k2 and k3 exchanged in the backward."""
+    st = bf if x1.dtype == BF16 else (lambda t: t)
+    N, C = x1.shape
+    idx, mask, lens = _bn_gather('cl', None, plan, N)
+    got, s = {}, []
+    for i, (x, p) in enumerate(((x1, p1), (x2, p2))):
+        f = emu_bn_finalize(_bn_partials('cl', x.float(), idx, mask, lens), eps, mom, p[2], p[3])
+        got.update({f'{n}{i + 1}': v for n, v in f.items()})
+        s.append((x.float(), f['mean'], f['rstd'], p[0]))
+    be = p1[1] if drop_beta2 else p1[1] + p2[1]
+    (xa, ma, ra, ga), (xb, mb, rb, gb) = s
+    z = _fma(xb - mb, rb * gb, _fma(xa - ma, ra * ga, be))
+    got['out'] = st(_silu(z) if act else z)
+    h1, h2 = (xa - ma) * ra, (xb - mb) * rb
+    dz = gout.float() * (_dsilu(_fma(h2, gb, _fma(h1, ga, be))) if act else torch.ones(()))
+    m = mask.unsqueeze(-1)
+    sums = [torch.where(m, t[idx], torch.zeros(())).sum(1).sum(0) for t in (dz, dz * h1, dz * h2)]
+    inv = _f(1.0) / _f(float(N))
+    k1, k2, k3 = (t * inv for t in sums)
+    if swap_k:
+        k2, k3 = k3, k2
+    got.update({'dbeta1': sums[0], 'dbeta2': sums[0], 'dgamma1': sums[1], 'dgamma2': sums[2],
+                'dx1': st(ga * ra * (dz - k1 - h1 * k2)), 'dx2': st(gb * rb * (dz - k1 - h2 * k3))})
+    return got
+
+
+def _bn_case_inputs(layout, N, C, dt, kind, dims=None):
+    bf16 = dt == BF16
+    plan = K.nchw_plan(dims[0], C, dims[1], bf16) if layout == 'nchw' else K.cl_plan(N, C, bf16)
+    home = K.home_row(layout, plan, N, *(dims or ()))
+    x, g = K.bn_rows(N, C, dt, kind, 900 + N % 1000 + C, home)
+    return plan, x, g, K.bn_params(C, 11 + C)
+
+
+def _emu_single(layout, N, C, dt, kind, act, dims=None, residual=False, eps=1e-3, mom=0.03, tag='emu', **mut):
+    plan, x, g, p = _bn_case_inputs(layout, N, C, dt, kind, dims)
+    r = (0.5 * rnd((N, C), 300 + C)).to(dt) if residual else None
+    args = (plan, x, p[0], p[1], g, eps, mom, p[2], p[3], act, r)
+    got = emu_bn_nchw(*dims, *args, **mut) if layout == 'nchw' else emu_bn_cl(*args, **mut)
+    xr, gr = (K.nchw(x, *dims), K.nchw(g, *dims)) if layout == 'nchw' else (x, g)
+    K.bn_single_assert(f'{tag} bn[{layout},{K.dtn(dt)},{N}x{C},{kind},act={act}]', got, layout, plan, xr, p[0], p[1], gr, eps, mom, p[2], p[3], act, r)
+    if kind == 'constant' and not mut:
+        K.bn_constant_assert(tag, got, C, p[1], act, dt, eps)
+    return got
+
+
+def test_bn_cases_reach_the_branches_they_are_listed_for():
+    """The dispatch of csrc/bn.hip as restated in tests/bn_cases.py, on every listed case."""
+    assert K.reached() == K.REACH, K.reached() ^ K.REACH
+    assert K.cl_plan(*K.CL_LARGE['S>256'][:0:-1], False)[4] == 257 and K.cl_plan(*K.CL_LARGE['iters=8'][:0:-1], False)[2:] == (8, 128, 641)
+    assert K.cl_plan(K.CL_LARGE['iters=8'][2] - 6, 64, False)[2] == 4                      # one row less than 5 * 2^20 elements: still iters = 4
+    assert K.cl_plan(1, 4, True)[:2] == (4, 1) and K.cl_plan(1, 8, True)[:2] == (8, 1) and K.cl_plan(1, 1024, False)[1] == 256
+    for dt, C in K.SEG_CASES:                                                              # an image boundary inside a chunk and inside a piece
+        V, cg, iters, chunk_rows, S = K.cl_plan(K.SEG_B * K.SEG_LS[0], C, dt == 'bf16')
+        assert any(L % chunk_rows and L % (256 * V // C) for L in K.SEG_LS)
+    assert all((B * HW) & (B * HW - 1) == 0 for B, C, HW, k in K.NCHW_KIND_CASES if k == 'constant')
+
+
+@pytest.mark.parametrize('dt', ('fp32', 'bf16'))
+def test_bn_nchw_emulation_passes_every_case(dt):
+    for B, C, HW in K.NCHW_SHAPES:
+        for act in (0, 1):
+            for eps, mom in K.EPS_MOM:
+                _emu_single('nchw', B * HW, C, K.DT[dt], 'ordinary', act, (B, HW), eps=eps, mom=mom)
+    for B, C, HW, kind in K.NCHW_KIND_CASES:
+        for act in (0, 1):
+            _emu_single('nchw', B * HW, C, K.DT[dt], kind, act, (B, HW))
+
+
+@pytest.mark.parametrize('dt', ('fp32', 'bf16'))
+def test_bn_channels_last_emulation_passes_every_case(dt):
+    for C in K.CL_C[dt]:
+        for N in K.cl_rows(C, dt == 'bf16').values():
+            for act, residual, _ in K.CL_VARIANTS[:3]:                  # (a strided gy is the same arithmetic)
+                _emu_single('cl', N, C, K.DT[dt], 'ordinary', act, residual=residual)
+            _emu_single('cl', N, C, K.DT[dt], 'ordinary', 1, eps=1e-5, mom=0.1)
+    for inst, C in K.CL_KIND_C.items():
+        if inst.startswith(dt):
+            for kind in K.KINDS[1:]:
+                N = K.cl_rows(C, dt == 'bf16')['chunk' if kind == 'constant' else 'inside']
+                for act in (0, 1):
+                    _emu_single('cl', N, C, K.DT[dt], kind, act, residual=act == 1 and kind != 'constant')
+
+
+@pytest.mark.parametrize('case', list(K.CL_LARGE))
+def test_bn_channels_last_emulation_passes_the_long_chains(case):
+    """Both large cases at full size (S = 257 and iters = 8 with S = 641): the emulation is vectorised over the chunks."""
+    dt, C, N = K.CL_LARGE[case]
+    _emu_single('cl', N, C, K.DT[dt], 'ordinary', 1)
+
+
+def test_bn_pair_segment_and_statistics_emulations_pass():
+    eps, mom = 1e-3, 0.03
+    for dt, C, rows_, _ in K.PAIR_CASES:
+        N = K.cl_rows(C, dt == 'bf16')[rows_]
+        plan = K.cl_plan(N, C, dt == 'bf16')
+        x1, g = K.bn_rows(N, C, K.DT[dt], 'ordinary', 400 + C)
+        x2 = (1.3 * rnd((N, C), 401 + C) - 0.7).to(K.DT[dt])
+        p1, p2 = K.bn_params(C, 21 + C), K.bn_params(C, 31 + C)
+        K.bn_pair_assert(f'emu bn2[{dt},{N}x{C}]', emu_bn_pair(plan, x1, x2, p1, p2, g, eps, mom, 1), plan, x1, x2, p1, p2, g, eps, mom, 1)
+    for dt, C in K.SEG_CASES:
+        _emu_segments(dt, C, False)
+    for S in K.FINALIZE_S:
+        for empty in ((), (0,), (S // 2,)) if S > 1 else ((),):
+            part, data, counts = K.finalize_partials(S, 3, empty)
+            _, _, rm, rv = K.bn_params(3, 50)
+            K.finalize_assert(f'emu bn_finalize[S={S},empty={empty}]', emu_bn_finalize(part, eps, mom, rm, rv), S, counts, data, eps, mom, rm, rv)
+    # the parent's loop (no guard): an empty first triple divides 0 by 0
+    n, mean, m2 = (torch.zeros(3) for _ in range(3))
+    assert bool(torch.isnan(mean + (mean - mean) * (n / (n + n))).all())
+    for dt in K.CL_C:
+        for C in K.CL_C[dt]:
+            for N in K.cl_rows(C, dt == 'bf16').values():
+                for kind in ('ordinary', 'offset'):
+                    plan = K.cl_plan(N, C, dt == 'bf16')
+                    x, _ = K.bn_rows(N, C, K.DT[dt], kind, 600 + C + N % 1000)
+                    p = K.bn_params(C, 11 + C)
+                    idx, mask, lens = _bn_gather('cl', None, plan, N)
+                    got = emu_bn_finalize(_bn_partials('cl', x.float(), idx, mask, lens), eps, mom, p[2], p[3])
+                    K.stats_assert(f'emu bn_stats[{dt},{N}x{C},{kind}]', got, 'cl', plan, x, eps, mom, p[2], p[3])
+
+
+def _emu_segments(dt, C, wrong_pitch):
+    """ops.bn_cat_cl: every level's BatchNorm written into its segment of the [B, sum L, C] token memory.  Mutant: image b of a level
+    placed at b * seg_rows * C instead of b * seg_pitch."""
+    B, Ls, eps, mom = K.SEG_B, K.SEG_LS, 1e-5, 0.1
+    Lt = sum(Ls)
+    feats = torch.zeros(B * Lt * C, dtype=K.DT[dt])
+    ins = [K.bn_rows(B * L, C, K.DT[dt], 'ordinary', 500 + L + C) for L in Ls]
+    ps = [K.bn_params(C, 41 + i + C) for i in range(len(Ls))]
+    gots, at = [], 0
+    for (x, g), p, L in zip(ins, ps, Ls):
+        plan = K.cl_plan(B * L, C, dt == 'bf16')
+        got = emu_bn_cl(plan, x, p[0], p[1], g, eps, mom, p[2], p[3], 0)
+        for b in range(B):
+            o = at * C + b * (L * C if wrong_pitch else Lt * C)
+            feats[o:o + L * C] = got['out'][b * L:(b + 1) * L].reshape(-1)
+        gots.append((got, plan))
+        at += L
+    at = 0
+    for (got, plan), (x, g), p, L in zip(gots, ins, ps, Ls):
+        got = dict(got, out=feats.view(B, Lt, C)[:, at:at + L].reshape(B * L, C))
+        del got['mean'], got['rstd']
+        K.bn_single_assert(f'emu bn_seg[{dt},C={C},{B}x{L}]', got, 'cl', plan, x, p[0], p[1], g, eps, mom, p[2], p[3], 0)
+        at += L
+
+
+def _old_bn_ok(got, ref, dt, N):
+    """The rule of tests/test_gpu_ops.py (test_bn_act_vs_torch and its siblings): out 2e-2 (bf16) | 2e-5 (fp32) relative and absolute, ten
+    times that on dx, dgamma and dbeta with sqrt(N) times the absolute term, the running statistics 1e-5 / 1e-6."""
+    tol = 2e-2 if dt == BF16 else 2e-5
+    rule = {'out': (tol, tol), 'dx': (10 * tol, 10 * tol), 'dgamma': (10 * tol, 10 * tol * N ** 0.5), 'dbeta': (10 * tol, 10 * tol * N ** 0.5),
+            'running_mean': (1e-5, 1e-6), 'running_var': (1e-5, 1e-6), 'dres': (tol, tol)}
+    return all(R.old_close(t.float(), ref[n][0], *rule[n.rstrip('12')]) for n, t in got.items() if n.rstrip('12') in rule)
+
+
+def test_bn_mutants_fail():
+    """Every mutant misses a counted bound on at least one case; whether the old rule of tests/test_gpu_ops.py accepts it is recorded in
+    the mutant table (profiles/r18_bn_ref64.txt)."""
+    def single(name, layout, N, C, dt, kind, act, dims=None, residual=False, **mut):
+        plan, x, g, p = _bn_case_inputs(layout, N, C, dt, kind, dims)
+        r = (0.5 * rnd((N, C), 300 + C)).to(dt) if residual else None
+        xr, gr = (K.nchw(x, *dims), K.nchw(g, *dims)) if layout == 'nchw' else (x, g)
+        ref = R.batch_norm(xr, p[0], p[1], gr, 1e-3, 0.03, p[2], p[3], act, r, chunk_rows=plan[3] if layout == 'cl' else None)
+        assert _old_bn_ok(emu_bn(layout, dims, plan, x, p[0], p[1], g, 1e-3, 0.03, p[2], p[3], act, r), ref, dt, N)
+        old = _old_bn_ok(emu_bn(layout, dims, plan, x, p[0], p[1], g, 1e-3, 0.03, p[2], p[3], act, r, **mut), ref, dt, N)
+        new = _new_rule(lambda: _emu_single(layout, N, C, dt, kind, act, dims, residual, tag='mutant', **mut))
+        MUTANT_TABLE.append(('bn', f'{name} [{layout},{K.dtn(dt)},{N}x{C},{kind}]', old, new))
+        assert not new, name
+        return old
+    n64 = K.cl_rows(64, False)
+    n256 = K.cl_rows(256, True)
+    single('running variance updated with the biased variance', 'nchw', 128, 3, K.F32, 'ordinary', 0, (2, 64), rv_biased=True)
+    single('running variance updated with the biased variance', 'cl', n256['inside'], 256, BF16, 'ordinary', 0, rv_biased=True)
+    single('rstd from the unbiased variance', 'nchw', 128, 3, BF16, 'ordinary', 1, (2, 64), rstd_unbiased=True)
+    single('rstd from the unbiased variance', 'cl', n64['inside'], 64, K.F32, 'ordinary', 1, rstd_unbiased=True)
+    single('NCHW tail slice counted as 4096 elements', 'nchw', 4100, 2, BF16, 'ordinary', 1, (1, 4100), tail_4096=True)
+    single('channels-last statistics as unshifted E[x^2] - E[x]^2', 'cl', n64['chunk'], 64, K.F32, 'offset', 0, unshifted=True)
+    single('backward reduce without the live mask', 'cl', n256['inside'], 256, BF16, 'ordinary', 1, no_live=True)
+    single('backward reduce without the live mask', 'cl', n64['inside'], 64, K.F32, 'ordinary', 1, no_live=True)
+    single('dx without the xhat k2 term', 'cl', n256['inside'], 256, BF16, 'ordinary', 1, no_k2=True)
+    single('dx without the xhat k2 term', 'nchw', 8200 * 2, 2, BF16, 'ordinary', 1, (2, 8200), no_k2=True)
+    single('SiLU\' taken at xhat', 'cl', n256['inside'], 256, BF16, 'ordinary', 1, dsilu_at_xhat=True)
+    old = single('z rounded to bf16 before the activation', 'cl', n256['inside'], 256, BF16, 'ordinary', 1, z_bf16=True)
+    assert old, 'the old rule was expected to accept a double rounding'
+    single('residual added after the bf16 store', 'cl', n256['inside'], 256, BF16, 'ordinary', 1, residual=True, res_after_store=True)
+    # the pair
+    dt, C = BF16, 256
+    N = n256['inside']
+    plan = K.cl_plan(N, C, True)
+    x1, g = K.bn_rows(N, C, dt, 'ordinary', 400 + C)
+    x2 = (1.3 * rnd((N, C), 401 + C) - 0.7).to(dt)
+    p1, p2 = K.bn_params(C, 21 + C), K.bn_params(C, 31 + C)
+    ref = R.batch_norm_pair(x1, x2, p1[0], p1[1], p2[0], p2[1], g, 1e-3, 0.03, p1[2], p1[3], p2[2], p2[3], 1, chunk_rows=plan[3])
+    for name, mut in (('pair with bn2\'s beta dropped', {'drop_beta2': True}), ('pair with k2 and k3 exchanged', {'swap_k': True})):
+        m = emu_bn_pair(plan, x1, x2, p1, p2, g, 1e-3, 0.03, 1, **mut)
+        new = _new_rule(lambda: K.bn_pair_assert('mutant', m, plan, x1, x2, p1, p2, g, 1e-3, 0.03, 1))
+        MUTANT_TABLE.append(('bn', f'{name} [bf16,{N}x{C}]', _old_bn_ok(m, ref, dt, N), new))
+        assert not new, name
+    # the segments
+    for dt_, C_ in K.SEG_CASES:
+        new = _new_rule(lambda: _emu_segments(dt_, C_, True))
+        MUTANT_TABLE.append(('bn', f'segment b at b * seg_rows * C [{dt_},C={C_}]', False, new))      # (the old test compares bits with ops.bn_act)
+        assert not new
+    _report_mutants('bn')
