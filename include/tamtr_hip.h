@@ -37,8 +37,8 @@ extern "C" {
 /* ABI version, bumped on any signature change.  The CLIP text tower's entries at the end of this file (tamtr_text_embed, tamtr_linear_f32,
  * tamtr_text_pool_project), tamtr_val_confusion, tamtr_val_ap_curves / tamtr_val_ap_tile and tamtr_bytetrack_update / tamtr_botsort_update /
  * tamtr_bytetrack_workspace_bytes, tamtr_val_coco_match / tamtr_val_coco_workspace_bytes / tamtr_val_coco_accumulate and tamtr_mot_update /
- * tamtr_mot_end_sequence / tamtr_mot_workspace_bytes, tamtr_hota_update / tamtr_hota_end_sequence / tamtr_hota_workspace_bytes, and
- * tamtr_dw_slices / tamtr_dw_bf16 are new symbols only: no existing signature changed, so the version stayed at 36 when they were added. */
+ * tamtr_mot_end_sequence / tamtr_mot_workspace_bytes, tamtr_hota_update / tamtr_hota_end_sequence / tamtr_hota_workspace_bytes,
+ * tamtr_trackmap_update / tamtr_trackmap_end_sequence / tamtr_trackmap_workspace_bytes and tamtr_dw_slices / tamtr_dw_bf16 are new symbols only: no existing signature changed, so the version stayed at 36 when they were added. */
 int tamtr_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -888,6 +888,42 @@ int tamtr_hota_update(const float* tracks, const int32_t* tcounts, const float* 
 int tamtr_hota_end_sequence(const double* alpha, double eps, int nc, int nq, int ng, int workgroups, void* const* state, const int* caps,
                             void* workspace, int workspace_bytes, void* stream);
 int tamtr_hota_workspace_bytes(int nq, int ng, int workgroups); /* 0 = unsupported */
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Track-mAP on the device, next to the MOT evaluation and HOTA: average precision over whole tracks, ranked by mean score and matched
+ * to ground-truth tracks by spatio-temporal IoU (TrackEval's TrackMAP for boxes, no area or time ranges; VisDrone-MOT's ranking
+ * score).  The rule is written out in csrc/trackmap.hip and stated by engine.track_map_evaluate.
+ *
+ * state: a HOST array of 10 device pointers, all zero when fresh, updated in place; caps: a HOST array of the 4 capacities G (gt
+ * identities), T (track ids), P (pair slots), R (rows of the run's table).  In order:
+ *      gstate i32 [G, 2]  frames present, class + 1          garea f64 [G]  the identity's area sum
+ *      tframes i32 [nc, T]  frames a track identity is present in      tsum f64 [nc, T, 2]  its area sum, its score sum
+ *      pkey i64 [P]  ((gt row << 32) | track id) + 1, 0 free pinter f64 [P]  the pair's intersection sum
+ *      rscore f64 [R]  a track's mean score                  rmeta i32 [R, 2]  its class, its bits (bit a = matched at threshold a)
+ *      gt_tracks i32 [nc]  ground-truth identities
+ *      hdr i32 [16]  run rows used, sequences ended, then what was left out: gt ids beyond G, track ids beyond T, rows beyond ng / nq,
+ *                    pairs without a slot, tracks beyond R, 0 ...
+ *  rscore, rmeta, gt_tracks and hdr belong to the run; the rest to the open sequence.
+ *
+ * tamtr_trackmap_update: steps 1 and 2 of the MOT rule, then the area, score and intersection sums, for the B frames of a batch, in
+ *  order, one launch, one workgroup: plain fp64 adds in frame order, no floating-point atomics.  tracks / tcounts / gt / gcounts as
+ *  tamtr_mot_update takes them; a track's score is column 5 of its row.
+ * tamtr_trackmap_end_sequence: six launches: mean scores; the tracks' order per class (score descending, id ascending; a counting
+ *  rank against LDS tiles, for any T) with the candidates per track; their offsets; the candidate lists (gt row, IoU); the greedy
+ *  matching, one wave per (threshold, class), serial over the tracks; the append to the run's table, and the sequence's state
+ *  cleared.  thresholds: HOST pointer to 1 .. 10 fp64 values; eps = DBL_EPSILON.  The run's accumulation is
+ *  tamtr_val_coco_accumulate on rmeta's bits (one range, one cut).
+ *  Whatever exceeds a capacity is counted in hdr and left out; nothing is written past a table.
+ * workspace: tamtr_trackmap_workspace_bytes(nq, ng, nc, G, T, P) bytes of device memory for either call (end_sequence: nq and ng are
+ *  irrelevant), 16-byte aligned, contents irrelevant (0 = unsupported).  Nothing is allocated, set or synchronised.
+ * TAMTR_EINVAL: a NULL or misaligned operand, a size or capacity < 1, n_thresholds outside 1 .. 10, iou_thr or eps <= 0, a workspace
+ *  that is too small.  TAMTR_EUNSUP: ng and nq whose solver state exceeds 60 KiB of LDS or 65535, nc > 4096, G or T > 2^24, P > 2^28,
+ *  R > 2^30, a workspace beyond 2^31 - 1 bytes. */
+int tamtr_trackmap_update(const float* tracks, const int32_t* tcounts, const float* gt, const int32_t* gcounts, int B, int nq, int ng,
+                          int nc, double iou_thr, void* const* state, const int* caps, void* workspace, int workspace_bytes, void* stream);
+int tamtr_trackmap_end_sequence(const double* thresholds, int n_thresholds, double eps, int nc, void* const* state, const int* caps,
+                                void* workspace, int workspace_bytes, void* stream);
+int tamtr_trackmap_workspace_bytes(int nq, int ng, int nc, int G_cap, int T_cap, int P_cap); /* 0 = unsupported */
 
 #ifdef __cplusplus
 }

@@ -656,10 +656,12 @@ def mot_new_counts(nc):
 
 
 def _mot_preprocess(gt, trk, nc, thr, out=None):
-    """Steps 1 (regions) and 2 (distractors) of the MOT rule on one frame, shared by mot_evaluate and hota_evaluate.
-    -> (kind-0 rows [n, 7], their classes, surviving track rows [k, 6], their classes); the dropped rows are counted into out."""
+    """Steps 1 (regions) and 2 (distractors) of the MOT rule on one frame, shared by mot_evaluate, hota_evaluate and track_map_evaluate.
+    -> (kind-0 rows [n, 7], their classes, surviving track rows [k, 6] - [k, 7] when they came with a score -, their classes); the dropped
+    rows are counted into out."""
     f32 = lambda x, w: np.asarray(x, np.float32).reshape(-1, w)   # noqa: E731
-    gt, trk = f32(gt, 7), f32(trk, 6)
+    trk = np.asarray(trk, np.float32)
+    gt, trk = f32(gt, 7), f32(trk, 7 if trk.ndim == 2 and trk.shape[1] == 7 else 6)   # a seventh column (the score) rides along
     kind = gt[:, 6]
     in_range = lambda c: (c >= 0) & (c < nc)   # noqa: E731
     trk = trk[in_range(trk[:, 5])]
@@ -888,6 +890,150 @@ def hota_table(summary, title=''):
     for r in summary['per_class'] + [summary['all']]:
         lines.append(f'{str(r["class"]):>16s}' + ''.join(f'{100 * r[c]:12.2f}' if '(' in c else f'{100 * r[c]:8.2f}' for c in cols) +
                      f'{r["gt_dets"]:9d}{r["trk_dets"]:9d}')
+    return '\n'.join(lines)
+
+
+# ------------------------------------------------------------------------------------------------ track-mAP
+TRACK_MAP_THRESHOLDS = (0.25, 0.5, 0.75)     # VisDrone-MOT's; np.linspace(0.5, 0.95, 10) gives TrackEval's
+
+
+def track_map_thresholds(thresholds):
+    """The thresholds as an f64 array, checked: 1 to 10 values in (0, 1]."""
+    thr = np.asarray(thresholds, np.float64).reshape(-1)
+    if not 1 <= len(thr) <= 10 or not np.all((thr > 0) & (thr <= 1)):
+        raise ValueError(f'track-mAP: 1 to 10 thresholds in (0, 1] are needed, got {thresholds}')
+    return thr
+
+
+def track_map_new_counts(nc, thresholds=TRACK_MAP_THRESHOLDS):
+    return {'score': np.zeros(0, np.float64), 'cls': np.zeros(0, np.int64), 'bits': np.zeros(0, np.int32),
+            'gt_tracks': np.zeros(int(nc), np.int64), 'thresholds': track_map_thresholds(thresholds)}
+
+
+def track_map_add_counts(a, b):
+    """Counts of several sequences (or runs) add: the rows are concatenated in order and gt_tracks add."""
+    if not np.array_equal(a['thresholds'], b['thresholds']):
+        raise ValueError('track-mAP: the counts were made with different thresholds')
+    out = {k: np.concatenate([a[k], b[k]]) for k in ('score', 'cls', 'bits')}
+    out.update({'gt_tracks': a['gt_tracks'] + b['gt_tracks'], 'thresholds': a['thresholds']})
+    return out
+
+
+def track_map_since(run, before):
+    """The counts that `run` holds beyond `before`, an earlier reading of the same run: what the sequences ended in between added."""
+    n = len(before['score'])
+    out = {k: run[k][n:] for k in ('score', 'cls', 'bits')}
+    out.update({'gt_tracks': run['gt_tracks'] - before['gt_tracks'], 'thresholds': run['thresholds']})
+    return out
+
+
+def track_map_evaluate(sequences, nc, iou=0.5, thresholds=TRACK_MAP_THRESHOLDS, detail=None):
+    """Track-mAP counts of tracker output against ground truth (TrackEval's TrackMAP for boxes, restated, with no area or time ranges and
+    no cap on tracks; the rule is written out in csrc/trackmap.hip, whose checker this is, and this is the path for a machine without a
+    GPU).  Arguments as mot_evaluate; a track row may carry a seventh column, its score ([k, 6] rows have score 1); `iou` is the
+    threshold of the region / distractor preprocessing, which is mot_evaluate's.  A ground-truth identity's dense row is its place in
+    the order of first appearance within the sequence.
+    -> {'score' f64 [n], 'cls' i64 [n], 'bits' i32 [n]: one row per track identity of the run (sequences in order, classes in order,
+    then score descending and id ascending), bit a = matched at thresholds[a]; 'gt_tracks' i64 [nc]; 'thresholds' f64}.  Counts of
+    several sequences add (track_map_add_counts) and track_map_summary turns them into AP / AR.
+    detail: a list that receives, per sequence, {'iou': {(dense row, (cls, id)): IoU}, 'mean': {(cls, id): score}, 'gaps': [best minus
+    second-best IoU of every greedy step with two candidates]} - what tests/trackmap_cases.margins reads."""
+    nc, thr, ts = int(nc), float(iou), track_map_thresholds(thresholds)
+    out = track_map_new_counts(nc, ts)
+    score, cls, bits = [], [], []
+    for frames in sequences:
+        rows, garea, tarea, tscore, tframes, inter = {}, {}, {}, {}, {}, {}
+        for gt, trk in frames:
+            g, gcls, trk, tcls = _mot_preprocess(gt, trk, nc, thr)
+            sc = trk[:, 6].astype(np.float64) if trk.shape[1] == 7 else np.ones(len(trk))
+            area = lambda b: (b[:, 2].astype(np.float64) - b[:, 0]) * (b[:, 3].astype(np.float64) - b[:, 1])   # noqa: E731
+            ga, ta = area(g), area(trk)
+            gid = [rows.setdefault((int(c), int(i)), len(rows)) for c, i in zip(gcls, g[:, 4])]
+            tid = [(int(c), int(i)) for c, i in zip(tcls, trk[:, 4])]
+            for k, a in zip(gid, ga):
+                garea[k] = garea.get(k, 0.0) + a
+            for k, a, s in zip(tid, ta, sc):
+                tarea[k], tscore[k], tframes[k] = tarea.get(k, 0.0) + a, tscore.get(k, 0.0) + s, tframes.get(k, 0) + 1
+            _, it = mot_iou_matrix(g[:, :4], trk[:, :4])
+            for i, j in zip(*np.nonzero((it > 0) & (gcls[:, None] == tcls[None, :]))):
+                inter[(gid[i], tid[j])] = inter.get((gid[i], tid[j]), 0.0) + it[i, j]
+        ious = {}
+        for (g, t), v in inter.items():
+            union = (garea[g] + tarea[t]) - v
+            ious[(g, t)] = v / union if union > 0 else 0.0
+        mean = {t: tscore[t] / tframes[t] for t in tscore}
+        gaps = []
+        for c in range(nc):
+            gts = sorted(r for (k, _), r in rows.items() if k == c)
+            order = sorted((t for t in mean if t[0] == c), key=lambda t: (-mean[t], t[1]))
+            word = np.zeros(len(order), np.int32)
+            for a, th in enumerate(ts):
+                taken = set()
+                for n, t in enumerate(order):
+                    best, choice = min(th, 1 - 1e-10), None
+                    for g in gts:
+                        v = ious.get((g, t), 0.0)
+                        if g not in taken and v >= best - HOTA_EPS:
+                            best, choice = v, g
+                    if detail is not None:
+                        cand = sorted((ious.get((g, t), 0.0) for g in gts if g not in taken), reverse=True)
+                        if len(cand) > 1 and cand[1] > 0:
+                            gaps.append(cand[0] - cand[1])
+                    if choice is not None:
+                        taken.add(choice)
+                        word[n] |= 1 << a
+            score += [mean[t] for t in order]
+            cls += [c] * len(order)
+            bits += word.tolist()
+            out['gt_tracks'][c] += len(gts)
+        if detail is not None:
+            detail.append({'iou': ious, 'mean': mean, 'gaps': gaps})
+    out.update({'score': np.asarray(score, np.float64), 'cls': np.asarray(cls, np.int64), 'bits': np.asarray(bits, np.int32)})
+    return out
+
+
+def track_map_accumulate(counts):
+    """The run's AP and AR per threshold and class from track_map_evaluate's counts: coco_accumulate on one range and one cut.
+    -> ap, ar f64 [n_thresholds, nc]; -1 for a class without ground truth."""
+    n, nc, nt = len(counts['score']), len(counts['gt_tracks']), len(counts['thresholds'])
+    bits, npig = np.zeros((n, 4), np.int32), np.zeros((nc, 4), np.int64)
+    bits[:, 0], npig[:, 0] = counts['bits'], counts['gt_tracks']
+    precision, recall = coco_accumulate(np.asarray(counts['score'], np.float64), np.asarray(counts['cls'], np.float64), bits, np.zeros(n, np.int32),
+                                        npig, nc, (1,))
+    ap = np.where(precision[:, 0] > -1, precision.sum(1) / 101.0, -1.0)
+    return ap[:nt, :, 0, 0].copy(), recall[:nt, :, 0, 0].copy()
+
+
+def track_map_rows(ap, ar, gt_tracks, tracks, thresholds, names=None):
+    """ap, ar f64 [n_thresholds, nc] (-1 without ground truth), gt_tracks and tracks [nc] -> {'all': row, 'per_class': [row, ...],
+    'thresholds'}: a row holds AP (the mean over the thresholds), AP_thr and AR_thr (lists), gt_tracks and tracks; the 'all' row holds the
+    means over the classes that have ground truth (-1 when none has) and the summed counts.  The host and the device path both end here."""
+    ap, ar = np.asarray(ap, np.float64), np.asarray(ar, np.float64)
+    has = np.asarray(gt_tracks) > 0
+    per = [{'class': names[c] if names is not None else c, 'AP': float(ap[:, c].mean()) if has[c] else -1.0,
+            'AP_thr': [float(x) for x in ap[:, c]], 'AR_thr': [float(x) for x in ar[:, c]], 'gt_tracks': int(gt_tracks[c]),
+            'tracks': int(tracks[c])} for c in range(ap.shape[1])]
+    mean = lambda x: [float(v) for v in x[:, has].mean(1)] if has.any() else [-1.0] * x.shape[0]   # noqa: E731
+    row = {'class': 'all', 'AP': float(np.mean([r['AP'] for r, h in zip(per, has) if h])) if has.any() else -1.0, 'AP_thr': mean(ap),
+           'AR_thr': mean(ar), 'gt_tracks': int(np.sum(gt_tracks)), 'tracks': int(np.sum(tracks))}
+    return {'all': row, 'per_class': per, 'thresholds': [float(t) for t in thresholds]}
+
+
+def track_map_summary(counts, names=None):
+    """Per-class rows and an 'all' row (track_map_rows) from track_map_evaluate's (or TrackMapEvaluator's) counts."""
+    ap, ar = track_map_accumulate(counts)
+    nc = len(counts['gt_tracks'])
+    return track_map_rows(ap, ar, counts['gt_tracks'], np.bincount(np.asarray(counts['cls'], np.int64), minlength=nc)[:nc], counts['thresholds'], names)
+
+
+def track_map_table(summary, title=''):
+    """track_map_summary's rows as a table (percentages; a class without ground truth shows -100)."""
+    ts = summary['thresholds']
+    lines = [f'{title or "class":>16s}{"AP":>8s}' + ''.join(f'{"AP@%.2f" % t:>9s}' for t in ts) + ''.join(f'{"AR@%.2f" % t:>9s}' for t in ts) +
+             f'{"gt_tracks":>10s}{"tracks":>8s}']
+    for r in summary['per_class'] + [summary['all']]:
+        lines.append(f'{str(r["class"]):>16s}{100 * r["AP"]:8.2f}' + ''.join(f'{100 * v:9.2f}' for v in r['AP_thr'] + r['AR_thr']) +
+                     f'{r["gt_tracks"]:10d}{r["tracks"]:8d}')
     return '\n'.join(lines)
 
 

@@ -2297,6 +2297,117 @@ def hota_end_sequence(state, nc, caps, nq, ng, workspace=None, workgroups=HOTA_E
          stream_ptr())
 
 
+# the track-mAP evaluator's state (csrc/trackmap.hip states it): name, dtype, shape from (nc, caps); caps = (gt identities, track ids,
+# pair slots, rows of the run's table); all zero when fresh.  The order is the kernel's.
+TRACKMAP_STATE_SPEC = (('gstate', torch.int32, lambda nc, c: (c[0], 2)), ('garea', torch.float64, lambda nc, c: (c[0],)),
+                       ('tframes', torch.int32, lambda nc, c: (nc, c[1])), ('tsum', torch.float64, lambda nc, c: (nc, c[1], 2)),
+                       ('pkey', torch.int64, lambda nc, c: (c[2],)), ('pinter', torch.float64, lambda nc, c: (c[2],)),
+                       ('rscore', torch.float64, lambda nc, c: (c[3],)), ('rmeta', torch.int32, lambda nc, c: (c[3], 2)),
+                       ('gt_tracks', torch.int32, lambda nc, c: (nc,)), ('hdr', torch.int32, lambda nc, c: (16,)))
+
+
+def trackmap_workspace_bytes(nq, ng, nc, caps):
+    """Bytes of device workspace tamtr_trackmap_update and tamtr_trackmap_end_sequence need (no GPU call)."""
+    caps = tuple(int(c) for c in caps)
+    if len(caps) != 4:
+        raise _lib.TamtrHipError(f'trackmap: 4 capacities (gt, tracks, pairs, rows) are needed, got {caps}')
+    ok = all(0 < v < 2 ** 31 for v in (int(nq), int(ng), int(nc)) + caps)
+    n = _lib.lib().tamtr_trackmap_workspace_bytes(int(nq), int(ng), int(nc), *caps[:3]) if ok else 0
+    if n <= 0:
+        raise _lib.TamtrHipError(f'trackmap: nq {nq}, ng {ng}, nc {nc} with capacities {caps} is outside what the kernel is built for')
+    return n
+
+
+def _trackmap_state(what, state, nc, caps):
+    """Check the state against TRACKMAP_STATE_SPEC -> (host array of its 10 device pointers, host array of the 4 capacities)."""
+    caps = tuple(int(c) for c in caps)
+    if int(nc) < 1 or len(caps) != 4 or min(caps) < 1:
+        raise _lib.TamtrHipError(f'{what}: nc and the 4 capacities (gt, tracks, pairs, rows) must be positive, got {nc} and {caps}')
+    for k, dt, shape in TRACKMAP_STATE_SPEC:
+        t = state.get(k) if isinstance(state, dict) else None
+        want = shape(int(nc), caps)
+        if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
+            got = None if t is None else (t.dtype, tuple(t.shape))
+            raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want}, got {got}')
+    require_gpu(*(state[k] for k, _, _ in TRACKMAP_STATE_SPEC))
+    return (ctypes.c_void_p * len(TRACKMAP_STATE_SPEC))(*(state[k].data_ptr() for k, _, _ in TRACKMAP_STATE_SPEC)), (ctypes.c_int * 4)(*caps)
+
+
+def trackmap_update(tracks, tcounts, gt, gcounts, state, nc, caps, iou=0.5, workspace=None):
+    """Steps 1 and 2 of the MOT rule and the sums of track-mAP (csrc/trackmap.hip; engine.track_map_evaluate is its numpy statement) for
+    the B frames of a batch, in order, in one launch.  tracks / tcounts / gt / gcounts as mot_update takes them; a track's score is
+    column 5 of its row.  state: a dict of device tensors as TRACKMAP_STATE_SPEC lists them, updated in place; caps: (gt identities,
+    track ids, pair slots, run rows).  Every check comes before the launch; no synchronisation."""
+    if tracks.dim() != 3 or tracks.shape[-1] != 8 or tracks.shape[0] < 1 or tracks.shape[1] < 1:
+        raise _lib.TamtrHipError(f'trackmap_update: expected tracks [B, nq, 8], got {tuple(tracks.shape)}')
+    B, nq, _ = tracks.shape
+    if gt.dim() != 3 or gt.shape[0] != B or gt.shape[1] < 1 or gt.shape[2] != 7:
+        raise _lib.TamtrHipError(f'trackmap_update: expected gt [B, ng, 7] with B = {B}, got {tuple(gt.shape)}')
+    ng = gt.shape[1]
+    if tuple(tcounts.shape) != (B,) or tuple(gcounts.shape) != (B,):
+        raise _lib.TamtrHipError(f'trackmap_update: tcounts and gcounts must be [B] = [{B}], got {tuple(tcounts.shape)} and {tuple(gcounts.shape)}')
+    if tracks.dtype != torch.float32 or gt.dtype != torch.float32 or tcounts.dtype != torch.int32 or gcounts.dtype != torch.int32:
+        raise _lib.TamtrHipError('trackmap_update: tracks and gt must be float32, tcounts and gcounts int32')
+    if not float(iou) > 0:
+        raise _lib.TamtrHipError(f'trackmap_update: iou must be positive, got {iou}')
+    ptrs, ccaps = _trackmap_state('trackmap_update', state, nc, caps)
+    require_gpu(tracks, tcounts, gt, gcounts)
+    workspace = _mot_workspace('trackmap_update', workspace, trackmap_workspace_bytes(nq, ng, nc, caps), tracks.device)
+    tracks, tcounts, gt, gcounts = _c(tracks), _c(tcounts), _c(gt), _c(gcounts)
+    call('tamtr_trackmap_update', ptr(tracks), ptr(tcounts), ptr(gt), ptr(gcounts), B, nq, ng, int(nc), float(iou), ptrs, ccaps,
+         ptr(workspace), int(workspace.numel()), stream_ptr())
+
+
+def _trackmap_thresholds(what, thresholds):
+    import numpy as np
+    thr = np.asarray(thresholds, np.float64).reshape(-1)
+    if not 1 <= len(thr) <= 10 or not np.all((thr > 0) & (thr <= 1)):
+        raise _lib.TamtrHipError(f'{what}: 1 to 10 thresholds in (0, 1] are needed, got {thresholds}')
+    return thr
+
+
+def trackmap_end_sequence(state, nc, caps, thresholds, workspace=None):
+    """The end of a sequence of track-mAP in six launches (csrc/trackmap.hip: mean scores, the tracks' order, the candidate lists, the
+    greedy matching at every threshold, the append to the run's table, the clearing of the sequence's state).  thresholds: 1 to 10
+    fp64 values, handed over as they are.  No synchronisation."""
+    thr = _trackmap_thresholds('trackmap_end_sequence', thresholds)
+    ptrs, ccaps = _trackmap_state('trackmap_end_sequence', state, nc, caps)
+    workspace = _mot_workspace('trackmap_end_sequence', workspace, trackmap_workspace_bytes(1, 1, nc, caps), state['hdr'].device)
+    call('tamtr_trackmap_end_sequence', (ctypes.c_double * len(thr))(*thr), len(thr), HOTA_EPS, int(nc), ptrs, ccaps, ptr(workspace),
+         int(workspace.numel()), stream_ptr())
+
+
+@torch.no_grad()
+def trackmap_accumulate(state, nc, caps, n_thresholds):
+    """The run's accumulation of track-mAP: tamtr_val_coco_accumulate (csrc/cocoeval.hip; fp64, serial in grid order, no floating-point
+    atomics) on the run's table with one range and one cut.  The rows in use (state['hdr'][0], read on the device) are ordered by
+    class, then score descending, then table order with two stable torch.sort calls, as val_coco_accumulate orders its rows.
+    -> ap, ar f64 [n_thresholds, nc] on the device, -1 for a class without ground truth.  Nothing synchronises."""
+    nt = int(n_thresholds)
+    if not 1 <= nt <= 10:
+        raise _lib.TamtrHipError(f'trackmap_accumulate: n_thresholds must be 1 .. 10, got {n_thresholds}')
+    _trackmap_state('trackmap_accumulate', state, nc, caps)
+    nc, R = int(nc), int(caps[3])
+    dev = state['hdr'].device
+    valid = torch.arange(R, device=dev, dtype=torch.int32) < state['hdr'][0]
+    key = torch.where(valid, state['rmeta'][:, 0], nc)
+    _, by_score = torch.sort(-state['rscore'], stable=True)
+    key, by_cls = torch.sort(key[by_score], stable=True)
+    order = by_score[by_cls]
+    bits = torch.zeros(R, 4, device=dev, dtype=torch.int32)
+    bits[:, 0] = state['rmeta'][:, 1][order]
+    rank = _c(torch.where(valid[order], 0, -1).to(torch.int32))
+    seg = _c(torch.searchsorted(key, torch.arange(nc + 1, device=dev, dtype=key.dtype)).to(torch.int32))
+    npig = torch.zeros(nc, 4, device=dev, dtype=torch.int32)
+    npig[:, 0] = state['gt_tracks']
+    cuts = torch.ones(1, device=dev, dtype=torch.int32)
+    packed = torch.empty(103 * 40 * nc, device=dev, dtype=torch.float64)
+    ap_tkam, recall, precision = val_coco_split(packed, nc, 1)
+    call('tamtr_val_coco_accumulate', ptr(bits), ptr(rank), ptr(seg), R, nc, ptr(npig), ptr(cuts), 1,
+         ctypes.c_void_p(_coco_grids(dev).data_ptr() + 80), ptr(precision), ptr(recall), ptr(ap_tkam), stream_ptr())
+    return ap_tkam[:nt, :, 0, 0], recall[:nt, :, 0, 0]
+
+
 @torch.no_grad()
 def val_postprocess_match(y, cls, bboxes, batch_idx, ori_hw, imgsz, conf, iou, single_cls=False, max_wh=7680., return_device_labels=False):
     """engine.Validator.update's per-image work (RTDETRValidator.postprocess, models/rtdetrworld/val.py:102-173, and match_predictions,

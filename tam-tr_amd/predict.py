@@ -191,8 +191,9 @@ class Predictor:
         """Network inputs u8 [B, S, S, 3] (host) + original (h, w) per image -> host (out [B, nq, 6], keep [B, nq], counts [B]).
         With a tracker (track.ByteTracker or track.BotSort) the batch's frames also go through one tracker launch, and its rows ride in the same copy:
         -> host (out, keep, counts, tracks [B, nq, 8], tcounts [B]).  With gt_frames (B host arrays [m, 7]) and an evaluator
-        (track.MotEvaluator or track.HotaEvaluator, or a list of them) as well, one more launch per evaluator scores the tracker's rows
-        where they lie; each evaluator's header rides in the same copy and its time goes under its own key of times ('mot', 'hota')."""
+        (track.MotEvaluator, track.HotaEvaluator or track.TrackMapEvaluator, or a list of them) as well, one more launch per evaluator
+        scores the tracker's rows where they lie; each evaluator's header rides in the same copy and its time goes under its own key
+        of times ('mot', 'hota', 'tmap')."""
         arr, hw = ims
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
         ev[0].record()
@@ -278,10 +279,10 @@ class Predictor:
         detection: the decoder keeps it for the run (head.keep_query_embed, switched back afterwards), the tracker gathers the kept
         rows on the device; nothing more is copied to the host.
         gt + evaluator: the sequence's ground truth, one array [m, 7] (x1 y1 x2 y2 id cls kind, track.read_mot) per frame in file order
-        (missing frames are empty), and a track.MotEvaluator or track.HotaEvaluator, or a list / tuple of them: every batch's rows are
-        scored on the device right after the tracker's launch, by each evaluator in turn (a frame without track rows is an empty
-        track set, as write_mot has it), the sequence is ended after the last frame, and speed() has an entry per evaluator ('mot',
-        'hota'); each evaluator's results() then holds the metrics.  Without both, nothing changes."""
+        (missing frames are empty), and a track.MotEvaluator, track.HotaEvaluator or track.TrackMapEvaluator, or a list / tuple of them:
+        every batch's rows are scored on the device right after the tracker's launch, by each evaluator in turn (a frame without track
+        rows is an empty track set, as write_mot has it), the sequence is ended after the last frame, and speed() has an entry per
+        evaluator ('mot', 'hota', 'tmap'); each evaluator's results() then holds the metrics.  Without both, nothing changes."""
         from .track import ByteTracker, tracker_from_yaml
         if isinstance(tracker, ByteTracker):
             self.tracker = tracker
@@ -308,7 +309,7 @@ class Predictor:
 
     def _track(self, files, gt, evaluator):
         evaluators = list(evaluator) if isinstance(evaluator, (list, tuple)) else [] if evaluator is None else [evaluator]
-        for k in {'mot', 'hota'} - ({e.times_key for e in evaluators} if gt is not None else set()):
+        for k in {'mot', 'hota', 'tmap'} - ({e.times_key for e in evaluators} if gt is not None else set()):
             self.times.pop(k, None)          # an evaluator's key exists only while a run is scored by it
         if getattr(self.tracker, 'gmc_method', None) != 'sparseOptFlow':
             self.times.pop('gmc', None)      # and the estimator's only while a BotSort run is in progress

@@ -58,6 +58,10 @@ class HotaOverflow(RuntimeError):
     pass
 
 
+class TrackMapOverflow(RuntimeError):
+    pass
+
+
 def read_tracker_yaml(path):
     """The keys of the reference's cfg/trackers/bytetrack.yaml -> ByteTracker's constructor arguments; any other tracker_type raises.
     tracker_from_yaml reads either of the reference's tracker files and builds ByteTracker or BotSort."""
@@ -479,27 +483,117 @@ class HotaEvaluator:
         return hota_summary(self.counts(), names)
 
 
+# ------------------------------------------------------------------------------------------------ track-mAP
+TRACKMAP_HDR_OVER = ('gt identities beyond gt_capacity', 'track ids beyond track_capacity', 'rows beyond ng / nq per frame',
+                     'pairs that found no slot in pair_capacity', 'tracks beyond row_capacity')   # hdr[2:7]
+
+
+class TrackMapEvaluator:
+    """Track-mAP of tracker rows against ground truth, kept on `device` (csrc/trackmap.hip states the rule and the state): average
+    precision over whole tracks, ranked by mean score and matched by spatio-temporal IoU at `thresholds` (1 to 10 values; the default
+    is VisDrone-MOT's, np.linspace(0.5, 0.95, 10) gives TrackEval's).  The methods are MotEvaluator's.  gt_capacity / track_capacity /
+    nq / ng as there; pair_capacity: slots of the sparse pair table (distinct (ground truth, track) pairs that intersect in a sequence;
+    the table fills badly beyond about half); row_capacity: track identities of the whole run."""
+    times_key = 'tmap'
+
+    def __init__(self, device, nc, thresholds=(0.25, 0.5, 0.75), iou=0.5, gt_capacity=1024, track_capacity=4096, pair_capacity=1 << 18,
+                 row_capacity=1 << 16, nq=300, ng=300):
+        from .engine import track_map_thresholds
+        self.device = torch.device(device)
+        if self.device.type != 'cuda':
+            raise ops._lib.TamtrHipError('TrackMapEvaluator needs an MI355X; engine.track_map_evaluate is the host path')
+        self.nc, self.iou, self.nq, self.ng = int(nc), float(iou), int(nq), int(ng)
+        self.thresholds = track_map_thresholds(thresholds)
+        self.caps = (int(gt_capacity), int(track_capacity), int(pair_capacity), int(row_capacity))
+        self.gt_capacity = self.caps[0]
+        if min(self.nc, self.nq, self.ng, *self.caps) < 1:
+            raise ValueError('nc, the capacities, nq and ng must be positive')
+        self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
+        self.state = {k: torch.zeros(shape(self.nc, self.caps), device=self.device, dtype=dt) for k, dt, shape in ops.TRACKMAP_STATE_SPEC}
+        self.rows, self.open = {}, False
+
+    def _ws_bytes(self):
+        return ops.trackmap_workspace_bytes(self.nq, self.ng, self.nc, self.caps)
+
+    upload = MotEvaluator.upload
+
+    def reset(self):
+        """Forget every row and the sequence in progress.  No synchronisation."""
+        for v in self.state.values():
+            v.zero_()
+        self.rows, self.open = {}, False
+
+    def update(self, tracks, tcounts, gt_frames):
+        """As MotEvaluator.update: the ground truth goes up in one copy, one launch follows; nothing synchronises."""
+        B = tracks.shape[0]
+        if len(gt_frames) != B:
+            raise ValueError(f'{len(gt_frames)} ground-truth frames for a batch of {B}')
+        if tracks.shape[1] > self.nq:
+            self.nq = int(tracks.shape[1])
+            self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
+        gt, gcounts = self.upload(gt_frames)
+        ops.trackmap_update(tracks, tcounts, gt, gcounts, self.state, self.nc, self.caps, self.iou, self.workspace)
+        self.open = True
+
+    def end_sequence(self):
+        """Match the tracks of the sequence in progress and append them to the run's table (six launches), then a new one starts:
+        ground-truth and track ids may be used again.  No synchronisation."""
+        ops.trackmap_end_sequence(self.state, self.nc, self.caps, self.thresholds, self.workspace)
+        self.rows, self.open = {}, False
+
+    def check_overflow(self, hdr):
+        """Raise when the header (read by the caller, e.g. from the predictor's packed copy) counts anything beyond a capacity."""
+        over = [(int(hdr[2 + i]), what) for i, what in enumerate(TRACKMAP_HDR_OVER)]
+        if any(n for n, _ in over):
+            raise TrackMapOverflow('; '.join(f'{n} {what}' for n, what in over if n) + f' were left out (capacities gt, tracks, pairs, rows '
+                                   f'= {self.caps}, ng {self.ng}, nq {self.nq}): build the evaluator with larger capacities')
+
+    def _read(self, *keys):
+        if self.open:
+            raise RuntimeError('a sequence is in progress: call end_sequence() before reading the results')
+        hdr = self.state['hdr'].cpu().numpy()
+        self.check_overflow(hdr)
+        n = int(hdr[0])
+        return n, [self.state[k][:n].cpu().numpy() if k != 'gt_tracks' else self.state[k].cpu().numpy() for k in keys]
+
+    def counts(self):
+        """The run's counts as engine.track_map_evaluate returns them (synchronises; raises TrackMapOverflow)."""
+        _, (score, meta, gtt) = self._read('rscore', 'rmeta', 'gt_tracks')
+        return {'score': score.copy(), 'cls': meta[:, 0].astype(np.int64), 'bits': meta[:, 1].astype(np.int32),
+                'gt_tracks': gtt.astype(np.int64), 'thresholds': self.thresholds.copy()}
+
+    def results(self, names=None):
+        """engine.track_map_rows of the sequences ended so far, accumulated on the device (ops.trackmap_accumulate; synchronises;
+        raises TrackMapOverflow)."""
+        from .engine import track_map_rows
+        n, (meta, gtt) = self._read('rmeta', 'gt_tracks')
+        ap, ar = (x.cpu().numpy() for x in ops.trackmap_accumulate(self.state, self.nc, self.caps, len(self.thresholds)))
+        return track_map_rows(ap, ar, gtt, np.bincount(meta[:, 0], minlength=self.nc)[:self.nc], self.thresholds, names)
+
+
 def pack_track_rows(frames, nq, device):
-    """Per-frame host rows [k, 6] (x1 y1 x2 y2 id cls, read_mot(gt=False)) -> tracks f32 [B, nq, 8] and tcounts i32 [B] on `device`, laid
-    out as ByteTracker.update leaves them (score 1, idx = the row), in one copy.  A frame with more than nq rows keeps its count."""
+    """Per-frame host rows [k, 6] (x1 y1 x2 y2 id cls, read_mot(gt=False)) or [k, 7] (with the score, read_mot(gt=False, scores=True)) ->
+    tracks f32 [B, nq, 8] and tcounts i32 [B] on `device`, laid out as ByteTracker.update leaves them (the score in column 5, 1 for
+    [k, 6] rows; idx = the row), in one copy.  A frame with more than nq rows keeps its count."""
     B = len(frames)
     buf = np.zeros(B * nq * 8 + B, np.float32)
     rows, cnt = buf[:B * nq * 8].reshape(B, nq, 8), buf[B * nq * 8:].view(np.int32)
     for b, f in enumerate(frames):
-        f = np.asarray(f, np.float32).reshape(-1, 6)
+        f = np.asarray(f, np.float32)
+        f = f.reshape(-1, 7 if f.ndim == 2 and f.shape[1] == 7 else 6)
         k = min(len(f), nq)
-        rows[b, :k, :5], rows[b, :k, 5], rows[b, :k, 6], rows[b, :k, 7] = f[:k, :5], 1.0, f[:k, 5], np.arange(k)
+        rows[b, :k, :5], rows[b, :k, 5], rows[b, :k, 6], rows[b, :k, 7] = f[:k, :5], f[:k, 6] if f.shape[1] == 7 else 1.0, f[:k, 5], np.arange(k)
         cnt[b] = len(f)
     dev = torch.from_numpy(buf).to(device)
     return dev[:B * nq * 8].view(B, nq, 8), dev[B * nq * 8:].view(torch.int32)
 
 
-def read_mot(path, gt=True, category_map=None, frames=None):
+def read_mot(path, gt=True, category_map=None, frames=None, scores=False):
     """A VisDrone-MOT file (`frame,id,left,top,width,height,score,category,truncation,occlusion`, frames 1-based) -> one fp32 array per
     frame 1 .. max(last frame in the file, `frames`).  gt=True: an annotation file -> [m, 7] x1 y1 x2 y2 id cls kind, where category 0
     (ignored region) gives kind 2, `score == 0` or category 11 (others) gives kind 1, and categories 1 .. 10 give classes 0 .. 9 with
     kind 0; category_map {category: (cls, kind)} replaces that table (a category it lacks is a distractor).  gt=False: a result file
-    as write_mot writes it -> [k, 6] x1 y1 x2 y2 id cls, the category being the class."""
+    as write_mot writes it -> [k, 6] x1 y1 x2 y2 id cls, the category being the class; with scores=True [k, 7], the file's score last."""
     table = VISDRONE_CATEGORIES if category_map is None else category_map
     rows = {}
     with open(path) as fh:
@@ -515,6 +609,6 @@ def read_mot(path, gt=True, category_map=None, frames=None):
                     kind = 1
                 rows.setdefault(f, []).append(box + [cls, kind])
             else:
-                rows.setdefault(f, []).append(box + [cat])
+                rows.setdefault(f, []).append(box + [cat] + ([score] if scores else []))
     n = max(max(rows, default=0), frames or 0)
-    return [np.asarray(rows.get(f, []), np.float32).reshape(-1, 7 if gt else 6) for f in range(1, n + 1)]
+    return [np.asarray(rows.get(f, []), np.float32).reshape(-1, 7 if gt or scores else 6) for f in range(1, n + 1)]

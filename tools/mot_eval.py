@@ -8,7 +8,9 @@ Every `<sequence>.txt` of --results (as tools/track.py --save-mot writes them) i
 frames go through the device path in batches (track.MotEvaluator: one launch per batch, one per sequence); --host runs the numpy
 statement of the same rule (engine.mot_evaluate) and needs no GPU.  The tables are printed, then one JSON line.  --hota adds the HOTA
 tables (HOTA, DetA, AssA ... per class; the rule is written out in tam-tr_amd/csrc/hota.hip) and a `hota` key to the JSON line, through
-the same path: track.HotaEvaluator on the device, engine.hota_evaluate with --host.
+the same path: track.HotaEvaluator on the device, engine.hota_evaluate with --host.  --track-map adds track-mAP, the score VisDrone-MOT
+ranks by (AP over whole tracks at --track-map-iou, default 0.25 0.5 0.75; the rule is written out in tam-tr_amd/csrc/trackmap.hip), with
+the scores of the result files: track.TrackMapEvaluator on the device, engine.track_map_evaluate with --host; a `track_map` key.
 """
 import argparse
 import json
@@ -26,6 +28,8 @@ def parse_args(argv=None):
     ap.add_argument('--iou', type=float, default=0.5)
     ap.add_argument('--host', action='store_true', help='the numpy path (no GPU)')
     ap.add_argument('--hota', action='store_true', help='score by HOTA as well')
+    ap.add_argument('--track-map', action='store_true', help='score by track-mAP as well, with the scores of the result files')
+    ap.add_argument('--track-map-iou', type=float, nargs='+', default=[0.25, 0.5, 0.75], help='the spatio-temporal IoU thresholds of track-mAP (1 to 10)')
     ap.add_argument('--batch', type=int, default=4, help='frames per launch on the device path')
     ap.add_argument('--gt-capacity', type=int, default=1024)
     ap.add_argument('--track-capacity', type=int, default=4096)
@@ -46,26 +50,32 @@ def main(argv=None):
         raise FileNotFoundError(f'no <sequence>.txt of {args.results} has an annotation file in {args.gt}')
     if not args.host:
         import torch
-        from tamtr_amd.track import HotaEvaluator, MotEvaluator, pack_track_rows
+        from tamtr_amd.track import HotaEvaluator, MotEvaluator, TrackMapEvaluator, pack_track_rows
         dev = torch.device('cuda', 0)
         ev = MotEvaluator(dev, nc, iou=args.iou, gt_capacity=args.gt_capacity, track_capacity=args.track_capacity, nq=args.rows, ng=args.rows)
         hev = HotaEvaluator(dev, nc, iou=args.iou, gt_capacity=args.gt_capacity, track_capacity=args.track_capacity, nq=args.rows,
                             ng=args.rows) if args.hota else None
+        tev = TrackMapEvaluator(dev, nc, thresholds=args.track_map_iou, iou=args.iou, gt_capacity=args.gt_capacity,
+                                track_capacity=args.track_capacity, nq=args.rows, ng=args.rows) if args.track_map else None
     total, per_seq = engine.mot_new_counts(nc), {}
     htotal, hper_seq = engine.hota_new_counts(nc), {}
+    ttotal, tper_seq = engine.track_map_new_counts(nc, args.track_map_iou), {}
     for name in seqs:
-        res = read_mot(os.path.join(args.results, name + '.txt'), gt=False)
+        res = read_mot(os.path.join(args.results, name + '.txt'), gt=False, scores=args.track_map)
         gt = read_mot(os.path.join(args.gt, name + '.txt'), frames=len(res))
-        res += [np.zeros((0, 6), np.float32)] * (len(gt) - len(res))
+        res += [np.zeros((0, 7 if args.track_map else 6), np.float32)] * (len(gt) - len(res))
         if args.host:
             counts = engine.mot_evaluate([list(zip(gt, res))], nc, iou=args.iou)
             hcounts = engine.hota_evaluate([list(zip(gt, res))], nc, iou=args.iou) if args.hota else None
+            tcounts = engine.track_map_evaluate([list(zip(gt, res))], nc, iou=args.iou, thresholds=args.track_map_iou) if args.track_map else None
         else:
             for i in range(0, len(gt), args.batch):
                 rows = pack_track_rows(res[i:i + args.batch], ev.nq, dev)
                 ev.update(*rows, gt[i:i + args.batch])
                 if args.hota:
                     hev.update(*rows, gt[i:i + args.batch])
+                if args.track_map:
+                    tev.update(*rows, gt[i:i + args.batch])
             ev.end_sequence()
             run = ev.counts()
             counts = {k: run[k] - total[k] for k in run}
@@ -73,6 +83,9 @@ def main(argv=None):
                 hev.end_sequence()
                 run = hev.counts()
                 hcounts = {k: run[k] - htotal[k] for k in run}
+            if args.track_map:
+                tev.end_sequence()
+                tcounts = engine.track_map_since(tev.counts(), ttotal)
         total = engine.mot_add_counts(total, counts)
         per_seq[name] = engine.mot_summary(counts, names)
         print(engine.mot_table(per_seq[name], name))
@@ -80,12 +93,19 @@ def main(argv=None):
             htotal = engine.hota_add_counts(htotal, hcounts)
             hper_seq[name] = engine.hota_summary(hcounts, names)
             print(engine.hota_table(hper_seq[name], name))
+        if args.track_map:
+            ttotal = engine.track_map_add_counts(ttotal, tcounts)
+            tper_seq[name] = engine.track_map_summary(tcounts, names)
+            print(engine.track_map_table(tper_seq[name], name))
     overall = engine.mot_summary(total, names)
     print(engine.mot_table(overall, 'OVERALL'))
     extra = {}
     if args.hota:
         extra['hota'] = {'per_sequence': hper_seq, 'overall': engine.hota_summary(htotal, names)}
         print(engine.hota_table(extra['hota']['overall'], 'OVERALL'))
+    if args.track_map:      # on the device path the overall numbers are the evaluator's own accumulation
+        extra['track_map'] = {'per_sequence': tper_seq, 'overall': engine.track_map_summary(ttotal, names) if args.host else tev.results(names)}
+        print(engine.track_map_table(extra['track_map']['overall'], 'OVERALL'))
     print(json.dumps({'sequences': len(seqs), 'path': 'host' if args.host else 'device', 'iou': args.iou, 'per_sequence': per_seq, 'overall': overall,
                       **extra}))
 

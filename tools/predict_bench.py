@@ -25,8 +25,11 @@
       the batch's device-to-host copy plus engine.mot_evaluate (numpy and scipy; host clock).
   (e) --hota: the HOTA launches on the same sequence, the same way: the update launch per batch next to the MOT update launch, the
       three end-of-sequence launches, and the host path (the batches' copies plus engine.hota_evaluate).
+  (f) --track-map: the track-mAP launches on the same sequence with a seeded score per row: the update launch per batch next to the
+      HOTA update launch, the six end-of-sequence launches, the run's accumulation, and the host path (the batches' copies plus
+      engine.track_map_evaluate).
 
-    python tools/predict_bench.py [--images 64] [--kernel-only] [--track [--botsort [--reid]]] [--gmc] [--mot] [--hota]
+    python tools/predict_bench.py [--images 64] [--kernel-only] [--track [--botsort [--reid]]] [--gmc] [--mot] [--hota] [--track-map]
 --kernel-only runs only the kernel loop of (a), for a `rocprofv3 --kernel-trace --stats` run of its own.
 """
 import argparse
@@ -492,6 +495,89 @@ def bench_hota(frames=200, B=4, nq=300, nc=10, repeats=7):
             'host_ms_per_batch': round(float(np.median(t_host)) / n_batches, 3), 'passes_timed': repeats}
 
 
+def bench_trackmap(frames=200, B=4, nq=300, nc=10, repeats=7):
+    """The track-mAP launches on bench_mot's sequence with a seeded score per row: the update launch per batch (alone, and as
+    TrackMapEvaluator.update runs it with the ground truth's upload), the HOTA update launch on the same batches as the yardstick (it
+    does the same steps 1 and 2 and pair-table work), the six end-of-sequence launches, the run's accumulation, and the host path on
+    the same rows: the batches' device-to-host copies plus engine.track_map_evaluate and track_map_summary."""
+    from tamtr_amd import engine, ops
+    from tamtr_amd.track import HotaEvaluator, TrackMapEvaluator, pack_track_rows
+    rng = np.random.default_rng(17)
+    scene = mot_scene(frames, nc=nc)
+    gts = [g for g, _ in scene]
+    trks = [np.concatenate([t, rng.uniform(0.05, 1.0, (len(t), 1)).astype(np.float32)], 1) for _, t in scene]
+    tracks_d, tc_d = pack_track_rows(trks, nq, 'cuda')
+    ev, hota = TrackMapEvaluator('cuda', nc, nq=nq, ng=300), HotaEvaluator('cuda', nc, nq=nq, ng=300)
+    pct = lambda v: [round(float(np.percentile(v, q)), 4) for q in (50, 10, 90)]   # noqa: E731
+    event = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
+    upd, end, full, hupd, acc = [], [], [], [], []
+    for rep in range(repeats + 1):
+        pairs, ends = [], []
+        for mode in ('hota', 'launch', 'upload'):      # a track-mAP pass comes last: its counts are read below
+            ev.reset(), hota.reset()
+            for i in range(0, frames, B):
+                if mode != 'upload':
+                    gt_d, gc_d = (hota if mode == 'hota' else ev).upload(gts[i:i + B])
+                e0, e1 = event(), event()
+                e0.record()
+                if mode == 'upload':
+                    ev.update(tracks_d[i:i + B], tc_d[i:i + B], gts[i:i + B])
+                elif mode == 'launch':
+                    ops.trackmap_update(tracks_d[i:i + B], tc_d[i:i + B], gt_d, gc_d, ev.state, nc, ev.caps, ev.iou, ev.workspace)
+                else:
+                    ops.hota_update(tracks_d[i:i + B], tc_d[i:i + B], gt_d, gc_d, hota.state, nc, hota.caps, hota.iou, hota.workspace)
+                e1.record()
+                pairs.append((mode, e0, e1))
+            if mode == 'hota':
+                continue
+            e2, e3, e4 = event(), event(), event()
+            e2.record()
+            ev.end_sequence()
+            e3.record()
+            ops.trackmap_accumulate(ev.state, nc, ev.caps, len(ev.thresholds))
+            e4.record()
+            ends.append((e2, e3, e4))
+        torch.cuda.synchronize()
+        if rep:      # the first pass is the warm-up
+            upd += [a.elapsed_time(b) for w, a, b in pairs if w == 'launch']
+            full += [a.elapsed_time(b) for w, a, b in pairs if w == 'upload']
+            hupd += [a.elapsed_time(b) for w, a, b in pairs if w == 'hota']
+            end += [a.elapsed_time(b) for a, b, _ in ends]
+            acc += [b.elapsed_time(c) for _, b, c in ends]
+    dev_counts, dev_res = ev.counts(), ev.results()      # the evaluator holds the last ended pass only: reset() came before it
+    hdr = ev.state['hdr'].cpu().tolist()
+
+    def host_pass():
+        rows = []
+        for i in range(0, frames, B):
+            t, c = tracks_d[i:i + B].cpu().numpy(), tc_d[i:i + B].cpu().numpy()      # the copy a host evaluation needs, per batch
+            rows += [t[b, :c[b]][:, [0, 1, 2, 3, 4, 6, 5]] for b in range(len(c))]
+        counts = engine.track_map_evaluate([list(zip(gts, rows))], nc)
+        return counts, engine.track_map_summary(counts)
+
+    host_pass()
+    t_host = []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        host_counts, host_res = host_pass()
+        t_host.append((time.perf_counter() - t0) * 1e3)
+    assert all(np.array_equal(dev_counts[k], host_counts[k]) for k in ('cls', 'bits', 'gt_tracks')), 'the two paths matched different things'
+    assert np.allclose(dev_counts['score'], host_counts['score'], rtol=1e-9, atol=0), 'the two paths scored different things'
+    assert np.allclose(dev_res['all']['AP_thr'], host_res['all']['AP_thr'], rtol=1e-9, atol=0), 'the two paths accumulated different things'
+    n_batches = frames / B
+    dev_seq = float(np.median(upd)) * n_batches + float(np.median(end))
+    return {'frames': frames, 'frames_per_launch': B, 'nq': nq, 'nc': nc, 'gt_rows_per_frame': round(float(np.mean([len(g) for g in gts])), 1),
+            'track_rows_per_frame': round(float(np.mean([len(t) for t in trks])), 1), 'tracks': dev_res['all']['tracks'],
+            'gt_tracks': dev_res['all']['gt_tracks'], 'AP': round(dev_res['all']['AP'], 4), 'AP_thr': [round(v, 4) for v in dev_res['all']['AP_thr']],
+            'header_after_the_run': hdr[:8],
+            'tmap_update_launch_ms_per_batch_p50_p10_p90': pct(upd), 'tmap_update_with_gt_upload_ms_per_batch_p50_p10_p90': pct(full),
+            'hota_update_launch_ms_per_batch_p50_p10_p90': pct(hupd), 'end_sequence_6_launches_ms_p50_p10_p90': pct(end),
+            'accumulate_ms_p50_p10_p90': pct(acc), 'tmap_update_launch_ms_per_frame': round(float(np.median(upd)) / B, 4),
+            'device_ms_per_sequence': round(dev_seq, 2),
+            'host_copy_plus_numpy_twin_ms_per_sequence_p50_min_max': [round(float(np.median(t_host)), 1), round(min(t_host), 1), round(max(t_host), 1)],
+            'host_ms_per_batch': round(float(np.median(t_host)) / n_batches, 3), 'passes_timed': repeats}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--images', type=int, default=64)
@@ -503,6 +589,8 @@ def main():
     ap.add_argument('--gmc', action='store_true', help="only (c'): BoT-SORT's camera-motion estimate and tracker launch on a 640 x 640 sequence")
     ap.add_argument('--mot', action='store_true', help='only (d): the MOT evaluation launches against copy + numpy twin')
     ap.add_argument('--hota', action='store_true', help='only (e): the HOTA launches against copy + numpy twin, on the sequence of --mot')
+    ap.add_argument('--track-map', action='store_true', help='only (f): the track-mAP launches against copy + numpy twin, on the sequence of --hota '
+                    'with scores added, next to the HOTA update launch')
     args = ap.parse_args()
     import tamtr_amd  # noqa: F401
     assert torch.cuda.is_available(), 'predict_bench needs an MI355X'
@@ -528,6 +616,11 @@ def main():
     if args.hota:
         print('(e) HOTA: update launch per batch of 4 frames and the end-of-sequence launches (device events) vs device-to-host copy + numpy twin (host clock)')
         print(json.dumps(bench_hota()))
+        return
+    if args.track_map:
+        print('(f) track-mAP: update launch per batch of 4 frames, the end-of-sequence launches and the accumulation (device events) vs device-to-host '
+              'copy + numpy twin (host clock)')
+        print(json.dumps(bench_trackmap()))
         return
     if args.kernel_only:
         print(json.dumps({'postprocess_kernel_only': bench_postprocess(True)}))

@@ -4,6 +4,8 @@ tracks with their ids; optional annotated copies, YOLO-format label files with t
 sequence, under an incremented --project/--name folder; one JSON line at the end.  With --gt the tracks are scored on the device
 as they are made (CLEAR-MOT and identity metrics, tam-tr_amd/csrc/mot.hip): a table per sequence and over all, and mot_metrics.json;
 --hota scores them by HOTA as well (tam-tr_amd/csrc/hota.hip): its tables next to the others and a `hota` key in mot_metrics.json.
+--track-map scores them by track-mAP, the score VisDrone-MOT ranks by (tam-tr_amd/csrc/trackmap.hip): AP over whole tracks at
+--track-map-iou (default 0.25 0.5 0.75), a table per sequence and over all, and a `track_map` key in mot_metrics.json.
 
     python tools/track.py --weights runs/train/TAMTR/best.pt --text-feats clip_vitb32.npz --data dataset.yaml \
         --source sequences/ [--tracker bytetrack.yaml | --tracker botsort.yaml [--gmc none] [--reid on]] --conf 0.1 --batch 4 --save-mot [--save --save-txt --save-conf] [--gt annotations/]
@@ -58,6 +60,8 @@ def parse_args(argv=None):
     ap.add_argument('--save-mot', action='store_true', help='write <sequence>.txt in the VisDrone-MOT result format')
     ap.add_argument('--gt', help='directory of VisDrone-MOT annotations <sequence>.txt: score the tracks (MOTA, MOTP, IDF1 ...)')
     ap.add_argument('--hota', action='store_true', help='with --gt: HOTA, DetA, AssA ... as well')
+    ap.add_argument('--track-map', action='store_true', help='with --gt: track-mAP (AP over whole tracks by spatio-temporal IoU) as well')
+    ap.add_argument('--track-map-iou', type=float, nargs='+', default=[0.25, 0.5, 0.75], help='the thresholds of --track-map (1 to 10)')
     ap.add_argument('--mot-iou', type=float, default=0.5, help='IoU a track needs with a ground truth to match it, with --gt')
     ap.add_argument('--project', default='runs/track')
     ap.add_argument('--name', default='TAMTR')
@@ -92,7 +96,7 @@ def main(argv=None):
     from tamtr_amd.model import RTDETRDetectionWorldModel
     from tamtr_amd.predict import Predictor, increment_path, is_image_file
     from tamtr_amd import engine
-    from tamtr_amd.track import ByteTracker, HotaEvaluator, MotEvaluator, read_mot, tracker_from_yaml, write_mot
+    from tamtr_amd.track import ByteTracker, HotaEvaluator, MotEvaluator, TrackMapEvaluator, read_mot, tracker_from_yaml, write_mot
     from predict import load_names
 
     dev = torch.device('cuda', 0)
@@ -111,7 +115,10 @@ def main(argv=None):
     saving = args.save or args.save_txt or args.save_mot or bool(args.gt)
     evaluator = MotEvaluator(dev, len(names), iou=args.mot_iou) if args.gt else None
     hota = HotaEvaluator(dev, len(names), iou=args.mot_iou) if args.gt and args.hota else None
+    tmap = TrackMapEvaluator(dev, len(names), thresholds=args.track_map_iou, iou=args.mot_iou) if args.gt and args.track_map else None
+    evaluators = [e for e in (evaluator, hota, tmap) if e is not None]
     scored, per_seq = engine.mot_new_counts(len(names)), {}
+    tscored, tper_seq = engine.track_map_new_counts(len(names), args.track_map_iou), {}
     hscored, hper_seq = engine.hota_new_counts(len(names)), {}
     class_names = list(names.values()) if isinstance(names, dict) else list(names)
     if saving:
@@ -123,7 +130,7 @@ def main(argv=None):
         frames, ids = [], set()
         gt_file = os.path.join(args.gt, name + '.txt') if args.gt else None
         gt = read_mot(gt_file) if gt_file and os.path.exists(gt_file) else None
-        for det in pred.track(folder, tracker=tracker, gt=gt, evaluator=(evaluator if hota is None else [evaluator, hota]) if gt is not None else None):     # persist=False: a fresh tracker
+        for det in pred.track(folder, tracker=tracker, gt=gt, evaluator=(evaluator if len(evaluators) == 1 else evaluators) if gt is not None else None):     # persist=False: a fresh tracker
             n_img += 1
             stem = os.path.splitext(os.path.basename(det.path))[0]
             if det.id is not None:
@@ -150,6 +157,11 @@ def main(argv=None):
                 hscored = engine.hota_add_counts(hscored, counts)
                 hper_seq[name] = engine.hota_summary(counts, class_names)
                 print(engine.hota_table(hper_seq[name], name))
+            if tmap is not None:
+                counts = engine.track_map_since(tmap.counts(), tscored)
+                tscored = engine.track_map_add_counts(tscored, counts)
+                tper_seq[name] = engine.track_map_summary(counts, class_names)
+                print(engine.track_map_table(tper_seq[name], name))
     wall = time.perf_counter() - t0
     sp = pred.speed()
     extra = {}
@@ -160,6 +172,9 @@ def main(argv=None):
         if hota is not None:
             metrics['hota'] = {'sequences': hper_seq, 'overall': engine.hota_summary(hscored, class_names)}
             print(engine.hota_table(metrics['hota']['overall'], 'OVERALL'))
+        if tmap is not None:      # the overall numbers are the evaluator's own accumulation, on the device
+            metrics['track_map'] = {'sequences': tper_seq, 'overall': tmap.results(class_names)}
+            print(engine.track_map_table(metrics['track_map']['overall'], 'OVERALL'))
         with open(save_dir / 'mot_metrics.json', 'w') as fh:
             json.dump(metrics, fh, indent=1)
         extra = {'mot': {k: overall['all'][k] for k in ('MOTA', 'MOTP', 'IDF1', 'IDSW', 'FP', 'FN')}, 'mot_ms_per_image': round(sp.get('mot', 0.0), 4),
@@ -167,6 +182,9 @@ def main(argv=None):
         if hota is not None:
             extra['hota'] = {k: metrics['hota']['overall']['all'][k] for k in ('HOTA', 'DetA', 'AssA', 'LocA')}
             extra['hota_ms_per_image'] = round(sp.get('hota', 0.0), 4)
+        if tmap is not None:
+            extra['track_map'] = {k: metrics['track_map']['overall']['all'][k] for k in ('AP', 'AP_thr', 'AR_thr')}
+            extra['tmap_ms_per_image'] = round(sp.get('tmap', 0.0), 4)
     print(json.dumps({**extra, 'sequences': len(seqs), 'images': n_img, 'track_rows': n_rows, 'ids': n_ids, 'save_dir': str(save_dir) if saving else None,
                       'ms_per_image': {'load': round(sp['load'], 3), 'forward': round(sp['h2d'] + sp['forward'], 3),
                                        'postprocess': round(sp['postprocess'], 3), 'track': round(sp['track'], 4), 'd2h': round(sp['d2h'], 3)},
