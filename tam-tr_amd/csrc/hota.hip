@@ -48,8 +48,9 @@
 //
 // DESIGN
 // Update: one workgroup of 256 threads walks the frames in order, as mot_update_kernel does, so every pot cell has one adder per frame
-// and the frames add in order: plain fp64 adds, no atomics, the same sum on every run.  (Steps 1 and 2 are restated here rather than
-// shared with mot_update_kernel; running both evaluators runs them twice.)  The frame's positive pairs go to the log with the slot of
+// and the frames add in order: plain fp64 adds, no atomics, the same sum on every run.  Steps 1 and 2 are mot_frame_filter
+// (mot_rule.h), as in mot_update_kernel; running both evaluators runs them twice.  The update's workspace is the filter's block
+// (mot_frame_ws_bytes), then rsum [ng] and csum [nq].  The frame's positive pairs go to the log with the slot of
 // their pair, so the second pass needs neither the boxes nor a table lookup; the log grows by the pairs present, not by nq x ng.
 // End of sequence, launch 1 (matching): `workgroups` workgroups stride over the logged frames - they are independent, unlike CLEAR's.
 // Each scatters the frame's pairs into a dense score matrix in its own slice of the workspace, takes out the isolated pairs and
@@ -62,7 +63,6 @@
 #define HOTA_THREADS 256
 #define HOTA_NA 19
 #define HOTA_LEVELS 20
-#define HOTA_MAX_PROBES 256
 
 enum { HH_FRAMES, HH_LOG, HH_OVER_GT, HH_OVER_TRK, HH_OVER_ROWS, HH_OVER_LOG, HH_OVER_FRAMES, HH_OVER_PAIRS };
 
@@ -89,23 +89,8 @@ struct HotaState {
   int nc, G, T, P, L, F;
 };
 
-static size_t hota_update_ws_bytes(size_t nq, size_t ng) { return 16 * ng * nq + 8 * (ng + nq) + 4 * (8 * ng + 6 * nq); }
+static size_t hota_update_ws_bytes(size_t nq, size_t ng) { return mot_frame_ws_bytes(nq, ng) + 8 * (ng + nq); }   // the frame's block, then rsum and csum
 static __host__ __device__ inline size_t hota_end_ws_per_group(size_t nq, size_t ng) { return (8 * ng * nq + 4 * (5 * ng + 3 * nq) + 15) & ~(size_t)15; }
-
-// the slot of pair (g, t), claimed if the pair is new; -1 when HOTA_MAX_PROBES slots from its home are all taken by others
-__device__ __forceinline__ int hota_slot(unsigned long long* keys, int P, int g, int t) {
-  const unsigned long long key = (((unsigned long long)(unsigned)g << 32) | (unsigned)t) + 1ull;
-  unsigned long long h = key * 0x9E3779B97F4A7C15ull;
-  h ^= h >> 29;
-  int s = (int)(h % (unsigned long long)P);
-  const int probes = min(P, HOTA_MAX_PROBES);
-  for (int q = 0; q < probes; ++q) {
-    const unsigned long long old = atomicCAS(&keys[s], 0ull, key);
-    if (old == 0ull || old == key) return s;
-    s = s + 1 == P ? 0 : s + 1;
-  }
-  return -1;
-}
 
 struct HotaUpdateParams {
   const float* tracks;
@@ -126,17 +111,11 @@ __global__ __launch_bounds__(HOTA_THREADS) void hota_update_kernel(HotaUpdatePar
   const HotaState& st = p.st;
   const int tid = threadIdx.x, nq = p.nq, ng = p.ng, nc = st.nc;
   const MotLsap w = mot_lsap_carve(lds, ng, nq + 1);
-  double* iouM = reinterpret_cast<double*>(p.ws);                  // [ngl, ntl]
-  double* S = iouM + (size_t)ng * nq;                              // step 2's cost matrix
-  double* rsum = S + (size_t)ng * nq;                              // [n3] the row sums of the class's similarity
-  double* csum = rsum + ng;                                        // [m3]
-  int* reg = reinterpret_cast<int*>(csum + nq);
-  int *gl = reg + ng, *g3 = gl + ng, *xs = g3 + ng;
-  int *tl = xs + ng, *t3 = tl + nq, *tdrop = t3 + nq;
-  MotSparse sq;
-  sq.rcnt = tdrop + nq; sq.rone = sq.rcnt + ng; sq.rl = sq.rone + ng; sq.xr = sq.rl + ng;
-  sq.ccnt = sq.xr + ng; sq.cone = sq.ccnt + nq; sq.cl = sq.cone + nq;
-  const double thr = p.thr;
+  const MotFrame f = mot_frame_carve(p.ws, nq, ng);
+  const double* iouM = f.iouM;
+  const int *gl = f.gl, *g3 = f.g3, *tl = f.tl, *t3 = f.t3;
+  double* rsum = reinterpret_cast<double*>(f.end);   // [n3] the row sums of the class's similarity; 8-byte aligned (mot_frame_ws_bytes)
+  double* csum = rsum + ng;                          // [m3]
   int fid = st.hdr[HH_FRAMES], used = st.hdr[HH_LOG];
 
   for (int b = 0; b < p.B; ++b) {
@@ -144,56 +123,13 @@ __global__ __launch_bounds__(HOTA_THREADS) void hota_update_kernel(HotaUpdatePar
       if (tid == 0) atomicAdd(&st.hdr[HH_OVER_FRAMES], 1);
       continue;
     }
-    const int graw = p.gcounts[b], traw = p.tcounts[b];
-    const int ngr = min(max(graw, 0), ng), ntr = min(max(traw, 0), nq);
-    if (tid == 0 && (graw > ng || traw > nq)) atomicAdd(&st.hdr[HH_OVER_ROWS], max(graw - ng, 0) + max(traw - nq, 0));
     const float* G = p.gt + (size_t)b * ng * 7;
     const float* Tr = p.tracks + (size_t)b * nq * 8;
-    // ---- the frame's lists and step 1, as in mot_update_kernel
-    const int nreg = mot_compact<HOTA_THREADS>(ngr, reg, wsum, [&](int i) { return mot_kind(G + (size_t)i * 7) == 2; });
-    const int ngl = mot_compact<HOTA_THREADS>(ngr, gl, wsum, [&](int i) {
-      const float* g = G + (size_t)i * 7;
-      const int k = mot_kind(g);
-      if (k == 1) return true;
-      if (k != 0 || !(g[5] >= 0.0f && g[5] < (float)nc)) return false;
-      if (!(g[4] >= 0.0f && g[4] < (float)st.G)) { atomicAdd(&st.hdr[HH_OVER_GT], 1); return false; }
-      return true;
-    });
-    const int ntl = mot_compact<HOTA_THREADS>(ntr, tl, wsum, [&](int j) {
-      const float* t = Tr + (size_t)j * 8;
-      if (!(t[6] >= 0.0f && t[6] < (float)nc)) return false;
-      if (!(t[4] >= 0.0f && t[4] < (float)st.T)) { atomicAdd(&st.hdr[HH_OVER_TRK], 1); return false; }
-      const MotBox tb = mot_box(t);
-      for (int r = 0; r < nreg; ++r)
-        if (mot_ioa(tb, mot_box(G + (size_t)reg[r] * 7)) > 0.5) return false;
-      return true;
-    });
-    for (int e = tid; e < ngl * ntl; e += HOTA_THREADS) {
-      const int i = e / ntl, j = e - i * ntl;
-      iouM[e] = mot_iou(mot_box(G + (size_t)gl[i] * 7), mot_box(Tr + (size_t)tl[j] * 8));
-    }
-    for (int j = tid; j < ntl; j += HOTA_THREADS) tdrop[j] = 0;
-    if (tid == 0) lcnt = 0;
-    __syncthreads();
-    // ---- step 2, distractors
-    const int ndis = mot_compact<HOTA_THREADS>(ngl, g3, wsum, [&](int i) { return mot_kind(G + (size_t)gl[i] * 7) == 1; });
-    if (ndis > 0 && ntl > 0) {
-      for (int e = tid; e < ngl * ntl; e += HOTA_THREADS) {
-        const int i = e / ntl, j = e - i * ntl;
-        const float* g = G + (size_t)gl[i] * 7;
-        const double v = iouM[e];
-        S[e] = (v >= thr && (g[6] == 1.0f || (int)g[5] == (int)Tr[(size_t)tl[j] * 8 + 6])) ? -v : 0.0;
-      }
-      __syncthreads();
-      mot_assign_sparse<HOTA_THREADS>(S, ngl, ntl, w, sq, xs, red, wsum);
-      for (int k = tid; k < ndis; k += HOTA_THREADS) {
-        const int i = g3[k], j = xs[i];
-        if (j >= 0 && S[(size_t)i * ntl + j] < 0.0) tdrop[j] = 1;
-      }
-      __syncthreads();
-    }
-    const int n3 = mot_compact<HOTA_THREADS>(ngl, g3, wsum, [&](int i) { return mot_kind(G + (size_t)gl[i] * 7) == 0; });
-    const int m3 = mot_compact<HOTA_THREADS>(ntl, t3, wsum, [&](int j) { return !tdrop[j]; });
+    if (tid == 0) lcnt = 0;   // the filter passes a barrier between this store and pass 1's atomicAdd
+    // ---- steps 1 and 2 of the MOT rule
+    const MotFrameSets fs = mot_frame_filter<HOTA_THREADS, true>(G, Tr, p.gcounts[b], p.tcounts[b], ng, nq, nc, st.G, st.T, p.thr,
+                                                                 &st.hdr[HH_OVER_GT], f, w, red, wsum, [](const float*) {}, [](const float*) {});
+    const int ntl = fs.ntl, n3 = fs.n3, m3 = fs.m3;
     auto gcls = [&](int a) { return (int)G[(size_t)gl[g3[a]] * 7 + 5]; };
     auto gidx = [&](int a) { return (int)G[(size_t)gl[g3[a]] * 7 + 4]; };
     auto tcls = [&](int c2) { return (int)Tr[(size_t)tl[t3[c2]] * 8 + 6]; };
@@ -225,7 +161,7 @@ __global__ __launch_bounds__(HOTA_THREADS) void hota_update_kernel(HotaUpdatePar
       const double v = sim(a, c2);
       if (!(v > 0.0) || gcls(a) != tcls(c2)) continue;
       const double den = (rsum[a] + csum[c2]) - v;
-      const int slot = hota_slot(st.pkey, st.P, gidx(a), tidx(c2));
+      const int slot = mot_pair_slot(st.pkey, st.P, gidx(a), tidx(c2));
       if (slot < 0) { atomicAdd(&st.hdr[HH_OVER_PAIRS], 1); continue; }
       st.ppot[slot] += den > p.eps ? v / den : 0.0;
       const int k = used + atomicAdd(&lcnt, 1);

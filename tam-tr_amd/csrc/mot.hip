@@ -51,7 +51,8 @@
 //
 // DESIGN
 // Update: one workgroup of 256 threads walks the frames in order (step 3 depends on the frame before; the whole update is one launch,
-// so the frames' independent parts are not split over workgroups - that would need a grid-wide barrier).  The frame's IoU matrix
+// so the frames' independent parts are not split over workgroups - that would need a grid-wide barrier).  Steps 1 and 2 are
+// mot_frame_filter (mot_rule.h), which hota.hip and trackmap.hip call too.  The frame's IoU matrix
 // (all gt rows x all surviving track rows, fp64) lives in the caller's workspace in global memory (300 x 300 f64 does not fit the
 // LDS), and next to it the cost matrix of the assignment being solved, written once per assignment by all threads so the solver's
 // serial steps read one value each.  Step 3 is solved as ONE assignment over all classes with score 0 on a class mismatch: the
@@ -89,7 +90,7 @@ struct MotParams {
   unsigned char* ws;
 };
 
-static size_t mot_update_ws_bytes(size_t nq, size_t ng) { return 16 * ng * nq + 4 * (8 * ng + 7 * nq); }
+static size_t mot_update_ws_bytes(size_t nq, size_t ng) { return mot_frame_ws_bytes(nq, ng) + 4 * nq; }   // the frame's block, then tm
 static size_t mot_end_ws_per_class(size_t G, size_t T) { return ((4 * (2 * G + T) + 15) & ~(size_t)15) + mot_lsap_bytes(G, T + 1); }
 
 __global__ __launch_bounds__(MOT_UPDATE_THREADS) void mot_update_kernel(MotParams p) {
@@ -98,73 +99,26 @@ __global__ __launch_bounds__(MOT_UPDATE_THREADS) void mot_update_kernel(MotParam
   __shared__ MotCand red[(MOT_UPDATE_THREADS / WAVE)];
   const int tid = threadIdx.x, nq = p.nq, ng = p.ng, nc = p.nc;
   const MotLsap w = mot_lsap_carve(lds, ng, nq + 1);
-  double* iouM = reinterpret_cast<double*>(p.ws);                  // [ngl, ntl]
-  double* S = iouM + (size_t)ng * nq;                              // the cost (- score) matrix of the assignment being solved
-  int* reg = reinterpret_cast<int*>(S + (size_t)ng * nq);          // rows of kind 2
-  int *gl = reg + ng, *g3 = gl + ng, *xs = g3 + ng;                // kind 0 / 1 rows; positions in gl of step 3's rows; the assignment
-  int *tl = xs + ng, *t3 = tl + nq, *tdrop = t3 + nq, *tm = tdrop + nq;   // track rows; positions in tl of step 3's; flags
-  MotSparse sq;
-  sq.rcnt = tm + nq; sq.rone = sq.rcnt + ng; sq.rl = sq.rone + ng; sq.xr = sq.rl + ng;
-  sq.ccnt = sq.xr + ng; sq.cone = sq.ccnt + nq; sq.cl = sq.cone + nq;
+  const MotFrame f = mot_frame_carve(p.ws, nq, ng);
+  double *iouM = f.iouM, *S = f.S;
+  int *gl = f.gl, *g3 = f.g3, *xs = f.xs, *tl = f.tl, *t3 = f.t3;
+  int* tm = reinterpret_cast<int*>(f.end);   // [m3] step 3's matched flags
   const double thr = p.thr;
   int fid = p.hdr[H_FRAME];
 
   for (int b = 0; b < p.B; ++b) {
     ++fid;
-    const int graw = p.gcounts[b], traw = p.tcounts[b];
-    const int ngr = min(max(graw, 0), ng), ntr = min(max(traw, 0), nq);
-    if (tid == 0 && (graw > ng || traw > nq)) atomicAdd(&p.hdr[H_OVER_ROWS], max(graw - ng, 0) + max(traw - nq, 0));
     const float* G = p.gt + (size_t)b * ng * 7;
     const float* Tr = p.tracks + (size_t)b * nq * 8;
-    // ---- the frame's lists: regions; kind-0 rows (class in range, id inside the table) and kind-1 rows; track rows that survive step 1
-    const int nreg = mot_compact<MOT_UPDATE_THREADS>(ngr, reg, wsum, [&](int i) { return mot_kind(G + (size_t)i * 7) == 2; });
-    const int ngl = mot_compact<MOT_UPDATE_THREADS>(ngr, gl, wsum, [&](int i) {
-      const float* g = G + (size_t)i * 7;
-      const int k = mot_kind(g);
-      if (k == 1) return true;
-      if (k != 0 || !(g[5] >= 0.0f && g[5] < (float)nc)) return false;
-      if (!(g[4] >= 0.0f && g[4] < (float)p.G)) { atomicAdd(&p.hdr[H_OVER_GT], 1); return false; }
-      return true;
-    });
-    const int ntl = mot_compact<MOT_UPDATE_THREADS>(ntr, tl, wsum, [&](int j) {
-      const float* t = Tr + (size_t)j * 8;
-      if (!(t[6] >= 0.0f && t[6] < (float)nc)) return false;
-      if (!(t[4] >= 0.0f && t[4] < (float)p.T)) { atomicAdd(&p.hdr[H_OVER_TRK], 1); return false; }
-      const MotBox tb = mot_box(t);
-      for (int r = 0; r < nreg; ++r)
-        if (mot_ioa(tb, mot_box(G + (size_t)reg[r] * 7)) > 0.5) { atomicAdd(&p.counts[(int)t[6] * 16 + K_DROP_REGION], 1); return false; }
-      return true;
-    });
-    // ---- the IoU matrix
-    for (int e = tid; e < ngl * ntl; e += MOT_UPDATE_THREADS) {
-      const int i = e / ntl, j = e - i * ntl;
-      iouM[e] = mot_iou(mot_box(G + (size_t)gl[i] * 7), mot_box(Tr + (size_t)tl[j] * 8));
-    }
-    for (int j = tid; j < ntl; j += MOT_UPDATE_THREADS) { tdrop[j] = 0; tm[j] = 0; }
-    __syncthreads();
-    // ---- 2. distractors
-    const int ndis = mot_compact<MOT_UPDATE_THREADS>(ngl, g3, wsum, [&](int i) { return mot_kind(G + (size_t)gl[i] * 7) == 1; });
-    if (ndis > 0 && ntl > 0) {
-      auto cost2 = [&](int i, int j) -> double {
-        const float* g = G + (size_t)gl[i] * 7;
-        const double v = iouM[(size_t)i * ntl + j];
-        return (v >= thr && (g[6] == 1.0f || (int)g[5] == (int)Tr[(size_t)tl[j] * 8 + 6])) ? -v : 0.0;
-      };
-      for (int e = tid; e < ngl * ntl; e += MOT_UPDATE_THREADS) S[e] = cost2(e / ntl, e % ntl);
-      __syncthreads();
-      mot_assign_sparse<MOT_UPDATE_THREADS>(S, ngl, ntl, w, sq, xs, red, wsum);
-      for (int k = tid; k < ndis; k += MOT_UPDATE_THREADS) {
-        const int i = g3[k], j = xs[i];
-        if (j >= 0 && S[(size_t)i * ntl + j] < 0.0) {
-          tdrop[j] = 1;
-          atomicAdd(&p.counts[(int)Tr[(size_t)tl[j] * 8 + 6] * 16 + K_DROP_DISTRACTOR], 1);
-        }
-      }
-      __syncthreads();
-    }
+    // ---- 1 and 2: regions and distractors; the drops are counted per class
+    const MotFrameSets fs = mot_frame_filter<MOT_UPDATE_THREADS, true>(
+        G, Tr, p.gcounts[b], p.tcounts[b], ng, nq, nc, p.G, p.T, thr, &p.hdr[H_OVER_GT], f, w, red, wsum,
+        [&](const float* t) { atomicAdd(&p.counts[(int)t[6] * 16 + K_DROP_REGION], 1); },
+        [&](const float* t) { atomicAdd(&p.counts[(int)t[6] * 16 + K_DROP_DISTRACTOR], 1); });
+    const int ntl = fs.ntl, n3 = fs.n3, m3 = fs.m3;
+    // either branch of step 3 passes a barrier between these stores and its writes to tm
+    for (int j = tid; j < m3; j += MOT_UPDATE_THREADS) tm[j] = 0;
     // ---- 3. CLEAR matching, all classes in one block-diagonal assignment
-    const int n3 = mot_compact<MOT_UPDATE_THREADS>(ngl, g3, wsum, [&](int i) { return mot_kind(G + (size_t)gl[i] * 7) == 0; });
-    const int m3 = mot_compact<MOT_UPDATE_THREADS>(ntl, t3, wsum, [&](int j) { return !tdrop[j]; });
     auto qualifies = [&](int a, int c2, double& v) -> bool {
       const int i = g3[a], j = t3[c2];
       v = iouM[(size_t)i * ntl + j];
@@ -179,7 +133,7 @@ __global__ __launch_bounds__(MOT_UPDATE_THREADS) void mot_update_kernel(MotParam
     if (n3 > 0 && m3 > 0) {
       for (int e = tid; e < n3 * m3; e += MOT_UPDATE_THREADS) S[e] = cost3(e / m3, e % m3);
       __syncthreads();
-      mot_assign_sparse<MOT_UPDATE_THREADS>(S, n3, m3, w, sq, xs, red, wsum);
+      mot_assign_sparse<MOT_UPDATE_THREADS>(S, n3, m3, w, f.sq, xs, red, wsum);
     } else {
       for (int a = tid; a < n3; a += MOT_UPDATE_THREADS) xs[a] = -1;
       __syncthreads();

@@ -43,7 +43,8 @@
 //
 // DESIGN
 // Update: one workgroup of 256 threads walks the frames in order, as hota_update_kernel does, so every sum has one adder per frame and
-// the frames add in order: plain fp64 adds, no atomics, the same bits on every run.  (Steps 1 and 2 are restated here as in hota.hip.)
+// the frames add in order: plain fp64 adds, no atomics, the same bits on every run.  Steps 1 and 2 are mot_frame_filter (mot_rule.h) without
+// the IoU matrix, which is filled only in a frame with a distractor; the update's workspace is the filter's block (mot_frame_ws_bytes).
 // End of sequence, all in global workspace so that no count has to fit a workgroup or its LDS:
 //   1 prep     mean scores (a NaN mean sorts as -inf), zeroed counters and `taken` bytes;
 //   2 rank     a track's place is the number of live tracks of its class that go before it, counted against LDS tiles of 256 (T / 256
@@ -61,7 +62,6 @@
 
 #define TM_THREADS 256
 #define TM_MAX_THR 10
-#define TM_MAX_PROBES 256
 
 enum { TH_ROWS, TH_SEQS, TH_OVER_GT, TH_OVER_TRK, TH_OVER_ROWS, TH_OVER_PAIRS, TH_OVER_RUN };
 
@@ -86,7 +86,7 @@ struct TmEndWs {
   unsigned char* taken;                                                // [nc, TM_MAX_THR, G]
 };
 
-static size_t tm_update_ws_bytes(size_t nq, size_t ng) { return 16 * ng * nq + 4 * (8 * ng + 6 * nq); }
+static size_t tm_update_ws_bytes(size_t nq, size_t ng) { return mot_frame_ws_bytes(nq, ng); }
 static size_t tm_end_ws_bytes(size_t nc, size_t G, size_t T, size_t P) {
   return (8 * (nc * T + P) + 4 * (2 * nc + 1 + 4 * nc * T + P) + nc * TM_MAX_THR * G + 15) & ~(size_t)15;
 }
@@ -103,21 +103,6 @@ static __host__ __device__ inline TmEndWs tm_end_carve(unsigned char* ws, size_t
   w.cand_g = w.cursor + nc * T;
   w.taken = reinterpret_cast<unsigned char*>(w.cand_g + P);
   return w;
-}
-
-// the slot of pair (g, t), claimed if the pair is new; -1 when TM_MAX_PROBES slots from its home are all taken by others (as hota_slot)
-__device__ __forceinline__ int tm_slot(unsigned long long* keys, int P, int g, int t) {
-  const unsigned long long key = (((unsigned long long)(unsigned)g << 32) | (unsigned)t) + 1ull;
-  unsigned long long h = key * 0x9E3779B97F4A7C15ull;
-  h ^= h >> 29;
-  int s = (int)(h % (unsigned long long)P);
-  const int probes = min(P, TM_MAX_PROBES);
-  for (int q = 0; q < probes; ++q) {
-    const unsigned long long old = atomicCAS(&keys[s], 0ull, key);
-    if (old == 0ull || old == key) return s;
-    s = s + 1 == P ? 0 : s + 1;
-  }
-  return -1;
 }
 
 __device__ __forceinline__ double tm_area(const float* r) { return ((double)r[2] - (double)r[0]) * ((double)r[3] - (double)r[1]); }
@@ -140,63 +125,16 @@ __global__ __launch_bounds__(TM_THREADS) void trackmap_update_kernel(TmUpdatePar
   const TmState& st = p.st;
   const int tid = threadIdx.x, nq = p.nq, ng = p.ng, nc = st.nc;
   const MotLsap w = mot_lsap_carve(lds, ng, nq + 1);
-  double* iouM = reinterpret_cast<double*>(p.ws);                  // [ngl, ntl]
-  double* S = iouM + (size_t)ng * nq;                              // step 2's cost matrix
-  int* reg = reinterpret_cast<int*>(S + (size_t)ng * nq);
-  int *gl = reg + ng, *g3 = gl + ng, *xs = g3 + ng;
-  int *tl = xs + ng, *t3 = tl + nq, *tdrop = t3 + nq;
-  MotSparse sq;
-  sq.rcnt = tdrop + nq; sq.rone = sq.rcnt + ng; sq.rl = sq.rone + ng; sq.xr = sq.rl + ng;
-  sq.ccnt = sq.xr + ng; sq.cone = sq.ccnt + nq; sq.cl = sq.cone + nq;
-  const double thr = p.thr;
+  const MotFrame f = mot_frame_carve(p.ws, nq, ng);
+  const int *gl = f.gl, *g3 = f.g3, *tl = f.tl, *t3 = f.t3;
 
   for (int b = 0; b < p.B; ++b) {
-    const int graw = p.gcounts[b], traw = p.tcounts[b];
-    const int ngr = min(max(graw, 0), ng), ntr = min(max(traw, 0), nq);
-    if (tid == 0 && (graw > ng || traw > nq)) atomicAdd(&st.hdr[TH_OVER_ROWS], max(graw - ng, 0) + max(traw - nq, 0));
     const float* G = p.gt + (size_t)b * ng * 7;
     const float* Tr = p.tracks + (size_t)b * nq * 8;
-    // ---- the frame's lists and step 1, as in mot_update_kernel
-    const int nreg = mot_compact<TM_THREADS>(ngr, reg, wsum, [&](int i) { return mot_kind(G + (size_t)i * 7) == 2; });
-    const int ngl = mot_compact<TM_THREADS>(ngr, gl, wsum, [&](int i) {
-      const float* g = G + (size_t)i * 7;
-      const int k = mot_kind(g);
-      if (k == 1) return true;
-      if (k != 0 || !(g[5] >= 0.0f && g[5] < (float)nc)) return false;
-      if (!(g[4] >= 0.0f && g[4] < (float)st.G)) { atomicAdd(&st.hdr[TH_OVER_GT], 1); return false; }
-      return true;
-    });
-    const int ntl = mot_compact<TM_THREADS>(ntr, tl, wsum, [&](int j) {
-      const float* t = Tr + (size_t)j * 8;
-      if (!(t[6] >= 0.0f && t[6] < (float)nc)) return false;
-      if (!(t[4] >= 0.0f && t[4] < (float)st.T)) { atomicAdd(&st.hdr[TH_OVER_TRK], 1); return false; }
-      const MotBox tb = mot_box(t);
-      for (int r = 0; r < nreg; ++r)
-        if (mot_ioa(tb, mot_box(G + (size_t)reg[r] * 7)) > 0.5) return false;
-      return true;
-    });
-    for (int j = tid; j < ntl; j += TM_THREADS) tdrop[j] = 0;
-    __syncthreads();
-    // ---- step 2, distractors
-    const int ndis = mot_compact<TM_THREADS>(ngl, g3, wsum, [&](int i) { return mot_kind(G + (size_t)gl[i] * 7) == 1; });
-    if (ndis > 0 && ntl > 0) {
-      for (int e = tid; e < ngl * ntl; e += TM_THREADS) {
-        const int i = e / ntl, j = e - i * ntl;
-        const float* g = G + (size_t)gl[i] * 7;
-        const double v = mot_iou(mot_box(g), mot_box(Tr + (size_t)tl[j] * 8));
-        iouM[e] = v;
-        S[e] = (v >= thr && (g[6] == 1.0f || (int)g[5] == (int)Tr[(size_t)tl[j] * 8 + 6])) ? -v : 0.0;
-      }
-      __syncthreads();
-      mot_assign_sparse<TM_THREADS>(S, ngl, ntl, w, sq, xs, red, wsum);
-      for (int k = tid; k < ndis; k += TM_THREADS) {
-        const int i = g3[k], j = xs[i];
-        if (j >= 0 && S[(size_t)i * ntl + j] < 0.0) tdrop[j] = 1;
-      }
-      __syncthreads();
-    }
-    const int n3 = mot_compact<TM_THREADS>(ngl, g3, wsum, [&](int i) { return mot_kind(G + (size_t)gl[i] * 7) == 0; });
-    const int m3 = mot_compact<TM_THREADS>(ntl, t3, wsum, [&](int j) { return !tdrop[j]; });
+    // ---- steps 1 and 2 of the MOT rule; the sums need no IoU
+    const MotFrameSets fs = mot_frame_filter<TM_THREADS, false>(G, Tr, p.gcounts[b], p.tcounts[b], ng, nq, nc, st.G, st.T, p.thr,
+                                                                &st.hdr[TH_OVER_GT], f, w, red, wsum, [](const float*) {}, [](const float*) {});
+    const int n3 = fs.n3, m3 = fs.m3;
     auto grow = [&](int a) { return G + (size_t)gl[g3[a]] * 7; };
     auto trow = [&](int c2) { return Tr + (size_t)tl[t3[c2]] * 8; };
     // ---- the sums: ids are unique within a frame, so every cell has one adder
@@ -220,7 +158,7 @@ __global__ __launch_bounds__(TM_THREADS) void trackmap_update_kernel(TmUpdatePar
       if ((int)g[5] != (int)t[6]) continue;
       const double v = mot_inter(mot_box(g), mot_box(t));
       if (!(v > 0.0)) continue;
-      const int slot = tm_slot(st.pkey, st.P, (int)g[4], (int)t[4]);
+      const int slot = mot_pair_slot(st.pkey, st.P, (int)g[4], (int)t[4]);
       if (slot < 0) { atomicAdd(&st.hdr[TH_OVER_PAIRS], 1); continue; }
       st.pinter[slot] += v;
     }

@@ -2148,10 +2148,12 @@ def _tracker_update(what, warps, out, counts, state, capacity, track_high_thresh
     return tracks, tcounts
 
 
-# the MOT evaluator's state (csrc/mot.hip states the columns): name, dtype, shape from (nc, G, T); all zero when fresh
-MOT_STATE_SPEC = (('gstate', torch.int32, lambda nc, G, T: (G, 8)), ('counts', torch.int32, lambda nc, G, T: (nc, 16)),
-                  ('iou_sum', torch.float64, lambda nc, G, T: (nc,)), ('pair', torch.int32, lambda nc, G, T: (G, T)),
-                  ('hdr', torch.int32, lambda nc, G, T: (8,)))
+# the MOT evaluator's state (csrc/mot.hip states the columns): name, dtype, shape from (nc, caps); caps = (gt identities, track ids);
+# all zero when fresh
+MOT_STATE_SPEC = (('gstate', torch.int32, lambda nc, c: (c[0], 8)), ('counts', torch.int32, lambda nc, c: (nc, 16)),
+                  ('iou_sum', torch.float64, lambda nc, c: (nc,)), ('pair', torch.int32, lambda nc, c: (c[0], c[1])),
+                  ('hdr', torch.int32, lambda nc, c: (8,)))
+MOT_CAPS = ('gt', 'tracks')
 
 
 def mot_workspace_bytes(nq, ng, nc, gt_capacity, track_capacity):
@@ -2163,17 +2165,39 @@ def mot_workspace_bytes(nq, ng, nc, gt_capacity, track_capacity):
     return n
 
 
-def _mot_state(what, state, nc, G, T):
-    for k, dt, shape in MOT_STATE_SPEC:
+def _mot_frames(what, tracks, tcounts, gt, gcounts, iou):
+    """The checks every tracking evaluator's update makes on a batch's rows -> B, nq, ng and the four tensors, contiguous."""
+    if tracks.dim() != 3 or tracks.shape[-1] != 8 or tracks.shape[0] < 1 or tracks.shape[1] < 1:
+        raise _lib.TamtrHipError(f'{what}: expected tracks [B, nq, 8], got {tuple(tracks.shape)}')
+    B, nq, _ = tracks.shape
+    if gt.dim() != 3 or gt.shape[0] != B or gt.shape[1] < 1 or gt.shape[2] != 7:
+        raise _lib.TamtrHipError(f'{what}: expected gt [B, ng, 7] with B = {B}, got {tuple(gt.shape)}')
+    if tuple(tcounts.shape) != (B,) or tuple(gcounts.shape) != (B,):
+        raise _lib.TamtrHipError(f'{what}: tcounts and gcounts must be [B] = [{B}], got {tuple(tcounts.shape)} and {tuple(gcounts.shape)}')
+    if tracks.dtype != torch.float32 or gt.dtype != torch.float32 or tcounts.dtype != torch.int32 or gcounts.dtype != torch.int32:
+        raise _lib.TamtrHipError(f'{what}: tracks and gt must be float32, tcounts and gcounts int32')
+    if not float(iou) > 0:
+        raise _lib.TamtrHipError(f'{what}: iou must be positive, got {iou}')
+    return B, nq, gt.shape[1], _c(tracks), _c(tcounts), _c(gt), _c(gcounts)
+
+
+def _eval_state(what, spec, cap_names, state, nc, caps):
+    """Check an evaluator's state against its spec -> (host array of its device pointers in the spec's order, host array of the
+    capacities)."""
+    caps = tuple(int(c) for c in caps)
+    if int(nc) < 1 or len(caps) != len(cap_names) or min(caps) < 1:
+        raise _lib.TamtrHipError(f'{what}: nc and the {len(cap_names)} capacities ({", ".join(cap_names)}) must be positive, got {nc} and {caps}')
+    for k, dt, shape in spec:
         t = state.get(k) if isinstance(state, dict) else None
-        want = shape(nc, G, T)
+        want = shape(int(nc), caps)
         if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
             got = None if t is None else (t.dtype, tuple(t.shape))
             raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want}, got {got}')
-    require_gpu(*(state[k] for k, _, _ in MOT_STATE_SPEC))
+    require_gpu(*(state[k] for k, _, _ in spec))
+    return (ctypes.c_void_p * len(spec))(*(state[k].data_ptr() for k, _, _ in spec)), (ctypes.c_int * len(caps))(*caps)
 
 
-def _mot_workspace(what, workspace, need, device):
+def _eval_workspace(what, workspace, need, device):
     if workspace is None:
         workspace = torch.empty(need, device=device, dtype=torch.uint8)
     require_gpu(workspace)
@@ -2188,23 +2212,11 @@ def mot_update(tracks, tcounts, gt, gcounts, state, nc, gt_capacity, track_capac
     (x1 y1 x2 y2 id cls kind, the id of a kind-0 row being its dense row in [0, gt_capacity)) and gcounts i32 [B] are on the GPU too.
     state: a dict of device tensors as MOT_STATE_SPEC lists them, updated in place.  Every check comes before the launch; no
     synchronisation."""
-    if tracks.dim() != 3 or tracks.shape[-1] != 8 or tracks.shape[0] < 1 or tracks.shape[1] < 1:
-        raise _lib.TamtrHipError(f'mot_update: expected tracks [B, nq, 8], got {tuple(tracks.shape)}')
-    B, nq, _ = tracks.shape
-    if gt.dim() != 3 or gt.shape[0] != B or gt.shape[1] < 1 or gt.shape[2] != 7:
-        raise _lib.TamtrHipError(f'mot_update: expected gt [B, ng, 7] with B = {B}, got {tuple(gt.shape)}')
-    ng = gt.shape[1]
-    if tuple(tcounts.shape) != (B,) or tuple(gcounts.shape) != (B,):
-        raise _lib.TamtrHipError(f'mot_update: tcounts and gcounts must be [B] = [{B}], got {tuple(tcounts.shape)} and {tuple(gcounts.shape)}')
-    if tracks.dtype != torch.float32 or gt.dtype != torch.float32 or tcounts.dtype != torch.int32 or gcounts.dtype != torch.int32:
-        raise _lib.TamtrHipError('mot_update: tracks and gt must be float32, tcounts and gcounts int32')
+    B, nq, ng, tracks, tcounts, gt, gcounts = _mot_frames('mot_update', tracks, tcounts, gt, gcounts, iou)
     nc, G, T = int(nc), int(gt_capacity), int(track_capacity)
-    if nc < 1 or G < 1 or T < 1 or not float(iou) > 0:
-        raise _lib.TamtrHipError(f'mot_update: nc, the capacities and iou must be positive, got {nc}, {G}, {T}, {iou}')
-    _mot_state('mot_update', state, nc, G, T)
+    _eval_state('mot_update', MOT_STATE_SPEC, MOT_CAPS, state, nc, (G, T))
     require_gpu(tracks, tcounts, gt, gcounts)
-    workspace = _mot_workspace('mot_update', workspace, mot_workspace_bytes(nq, ng, nc, G, T), tracks.device)
-    tracks, tcounts, gt, gcounts = _c(tracks), _c(tcounts), _c(gt), _c(gcounts)
+    workspace = _eval_workspace('mot_update', workspace, mot_workspace_bytes(nq, ng, nc, G, T), tracks.device)
     call('tamtr_mot_update', ptr(tracks), ptr(tcounts), ptr(gt), ptr(gcounts), B, nq, ng, nc, float(iou), ptr(state['gstate']),
          ptr(state['counts']), ptr(state['iou_sum']), ptr(state['pair']), ptr(state['hdr']), G, T, ptr(workspace), int(workspace.numel()),
          stream_ptr())
@@ -2214,10 +2226,10 @@ def mot_end_sequence(state, nc, gt_capacity, track_capacity, gt_used, workspace=
     """The per-sequence reduction of the MOT evaluation (MT / PT / ML / Frag and the identity assignment per class) in one launch; adds
     to state['counts'] and clears the per-sequence state.  gt_used: the number of dense gt rows the host handed out.  No synchronisation."""
     nc, G, T = int(nc), int(gt_capacity), int(track_capacity)
-    if nc < 1 or G < 1 or T < 1 or int(gt_used) < 0:
-        raise _lib.TamtrHipError(f'mot_end_sequence: nc and the capacities must be positive and gt_used >= 0, got {nc}, {G}, {T}, {gt_used}')
-    _mot_state('mot_end_sequence', state, nc, G, T)
-    workspace = _mot_workspace('mot_end_sequence', workspace, mot_workspace_bytes(1, 1, nc, G, T), state['hdr'].device)
+    if int(gt_used) < 0:
+        raise _lib.TamtrHipError(f'mot_end_sequence: gt_used must be >= 0, got {gt_used}')
+    _eval_state('mot_end_sequence', MOT_STATE_SPEC, MOT_CAPS, state, nc, (G, T))
+    workspace = _eval_workspace('mot_end_sequence', workspace, mot_workspace_bytes(1, 1, nc, G, T), state['hdr'].device)
     call('tamtr_mot_end_sequence', nc, ptr(state['gstate']), ptr(state['counts']), ptr(state['pair']), ptr(state['hdr']), G, T,
          min(int(gt_used), G), ptr(workspace), int(workspace.numel()), stream_ptr())
 
@@ -2230,6 +2242,7 @@ HOTA_STATE_SPEC = (('gstate', torch.int32, lambda nc, c: (c[0], 2)), ('tcount', 
                    ('log', torch.int32, lambda nc, c: (c[3], 4)), ('dets', torch.int32, lambda nc, c: (nc, 2)),
                    ('tp_lvl', torch.int32, lambda nc, c: (nc, 20)), ('loc_lvl', torch.float64, lambda nc, c: (nc, 20)),
                    ('ass', torch.float64, lambda nc, c: (3, nc, 19)), ('hdr', torch.int32, lambda nc, c: (16,)))
+HOTA_CAPS = ('gt', 'tracks', 'pairs', 'log', 'frames')
 HOTA_END_WORKGROUPS = 64     # workgroups of the matching launch: each strides over the logged frames and owns a slice of the workspace
 HOTA_EPS = 2.0 ** -52        # np.finfo(float).eps
 
@@ -2242,42 +2255,15 @@ def hota_workspace_bytes(nq, ng, workgroups=HOTA_END_WORKGROUPS):
     return n
 
 
-def _hota_state(what, state, nc, caps):
-    """Check the state against HOTA_STATE_SPEC -> (host array of its 12 device pointers, host array of the 5 capacities)."""
-    caps = tuple(int(c) for c in caps)
-    if int(nc) < 1 or len(caps) != 5 or min(caps) < 1:
-        raise _lib.TamtrHipError(f'{what}: nc and the 5 capacities (gt, tracks, pairs, log, frames) must be positive, got {nc} and {caps}')
-    for k, dt, shape in HOTA_STATE_SPEC:
-        t = state.get(k) if isinstance(state, dict) else None
-        want = shape(int(nc), caps)
-        if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
-            got = None if t is None else (t.dtype, tuple(t.shape))
-            raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want}, got {got}')
-    require_gpu(*(state[k] for k, _, _ in HOTA_STATE_SPEC))
-    return (ctypes.c_void_p * len(HOTA_STATE_SPEC))(*(state[k].data_ptr() for k, _, _ in HOTA_STATE_SPEC)), (ctypes.c_int * 5)(*caps)
-
-
 def hota_update(tracks, tcounts, gt, gcounts, state, nc, caps, iou=0.5, workspace=None):
     """Steps 1 and 2 of the MOT rule and pass 1 of HOTA (csrc/hota.hip; engine.hota_evaluate is its numpy statement) for the B frames of a
     batch, in order, in one launch.  tracks / tcounts / gt / gcounts as mot_update takes them.  state: a dict of device tensors as
     HOTA_STATE_SPEC lists them, updated in place; caps: (gt identities, track ids, pair slots, log entries, frames).  Every check
     comes before the launch; no synchronisation."""
-    if tracks.dim() != 3 or tracks.shape[-1] != 8 or tracks.shape[0] < 1 or tracks.shape[1] < 1:
-        raise _lib.TamtrHipError(f'hota_update: expected tracks [B, nq, 8], got {tuple(tracks.shape)}')
-    B, nq, _ = tracks.shape
-    if gt.dim() != 3 or gt.shape[0] != B or gt.shape[1] < 1 or gt.shape[2] != 7:
-        raise _lib.TamtrHipError(f'hota_update: expected gt [B, ng, 7] with B = {B}, got {tuple(gt.shape)}')
-    ng = gt.shape[1]
-    if tuple(tcounts.shape) != (B,) or tuple(gcounts.shape) != (B,):
-        raise _lib.TamtrHipError(f'hota_update: tcounts and gcounts must be [B] = [{B}], got {tuple(tcounts.shape)} and {tuple(gcounts.shape)}')
-    if tracks.dtype != torch.float32 or gt.dtype != torch.float32 or tcounts.dtype != torch.int32 or gcounts.dtype != torch.int32:
-        raise _lib.TamtrHipError('hota_update: tracks and gt must be float32, tcounts and gcounts int32')
-    if not float(iou) > 0:
-        raise _lib.TamtrHipError(f'hota_update: iou must be positive, got {iou}')
-    ptrs, ccaps = _hota_state('hota_update', state, nc, caps)
+    B, nq, ng, tracks, tcounts, gt, gcounts = _mot_frames('hota_update', tracks, tcounts, gt, gcounts, iou)
+    ptrs, ccaps = _eval_state('hota_update', HOTA_STATE_SPEC, HOTA_CAPS, state, nc, caps)
     require_gpu(tracks, tcounts, gt, gcounts)
-    workspace = _mot_workspace('hota_update', workspace, hota_workspace_bytes(nq, ng, 1), tracks.device)
-    tracks, tcounts, gt, gcounts = _c(tracks), _c(tcounts), _c(gt), _c(gcounts)
+    workspace = _eval_workspace('hota_update', workspace, hota_workspace_bytes(nq, ng, 1), tracks.device)
     call('tamtr_hota_update', ptr(tracks), ptr(tcounts), ptr(gt), ptr(gcounts), B, nq, ng, int(nc), float(iou), HOTA_EPS, ptrs, ccaps,
          ptr(workspace), int(workspace.numel()), stream_ptr())
 
@@ -2289,8 +2275,8 @@ def hota_end_sequence(state, nc, caps, nq, ng, workspace=None, workgroups=HOTA_E
     nq, ng, workgroups = int(nq), int(ng), int(workgroups)
     if nq < 1 or ng < 1 or workgroups < 1:
         raise _lib.TamtrHipError(f'hota_end_sequence: nq, ng and workgroups must be positive, got {nq}, {ng}, {workgroups}')
-    ptrs, ccaps = _hota_state('hota_end_sequence', state, nc, caps)
-    workspace = _mot_workspace('hota_end_sequence', workspace, hota_workspace_bytes(nq, ng, workgroups), state['hdr'].device)
+    ptrs, ccaps = _eval_state('hota_end_sequence', HOTA_STATE_SPEC, HOTA_CAPS, state, nc, caps)
+    workspace = _eval_workspace('hota_end_sequence', workspace, hota_workspace_bytes(nq, ng, workgroups), state['hdr'].device)
     import numpy as np
     alpha = (ctypes.c_double * 19)(*np.arange(0.05, 0.99, 0.05))   # the thresholds as TrackEval makes them, never k / 20
     call('tamtr_hota_end_sequence', alpha, HOTA_EPS, int(nc), nq, ng, workgroups, ptrs, ccaps, ptr(workspace), int(workspace.numel()),
@@ -2304,6 +2290,7 @@ TRACKMAP_STATE_SPEC = (('gstate', torch.int32, lambda nc, c: (c[0], 2)), ('garea
                        ('pkey', torch.int64, lambda nc, c: (c[2],)), ('pinter', torch.float64, lambda nc, c: (c[2],)),
                        ('rscore', torch.float64, lambda nc, c: (c[3],)), ('rmeta', torch.int32, lambda nc, c: (c[3], 2)),
                        ('gt_tracks', torch.int32, lambda nc, c: (nc,)), ('hdr', torch.int32, lambda nc, c: (16,)))
+TRACKMAP_CAPS = ('gt', 'tracks', 'pairs', 'rows')
 
 
 def trackmap_workspace_bytes(nq, ng, nc, caps):
@@ -2318,42 +2305,15 @@ def trackmap_workspace_bytes(nq, ng, nc, caps):
     return n
 
 
-def _trackmap_state(what, state, nc, caps):
-    """Check the state against TRACKMAP_STATE_SPEC -> (host array of its 10 device pointers, host array of the 4 capacities)."""
-    caps = tuple(int(c) for c in caps)
-    if int(nc) < 1 or len(caps) != 4 or min(caps) < 1:
-        raise _lib.TamtrHipError(f'{what}: nc and the 4 capacities (gt, tracks, pairs, rows) must be positive, got {nc} and {caps}')
-    for k, dt, shape in TRACKMAP_STATE_SPEC:
-        t = state.get(k) if isinstance(state, dict) else None
-        want = shape(int(nc), caps)
-        if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
-            got = None if t is None else (t.dtype, tuple(t.shape))
-            raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want}, got {got}')
-    require_gpu(*(state[k] for k, _, _ in TRACKMAP_STATE_SPEC))
-    return (ctypes.c_void_p * len(TRACKMAP_STATE_SPEC))(*(state[k].data_ptr() for k, _, _ in TRACKMAP_STATE_SPEC)), (ctypes.c_int * 4)(*caps)
-
-
 def trackmap_update(tracks, tcounts, gt, gcounts, state, nc, caps, iou=0.5, workspace=None):
     """Steps 1 and 2 of the MOT rule and the sums of track-mAP (csrc/trackmap.hip; engine.track_map_evaluate is its numpy statement) for
     the B frames of a batch, in order, in one launch.  tracks / tcounts / gt / gcounts as mot_update takes them; a track's score is
     column 5 of its row.  state: a dict of device tensors as TRACKMAP_STATE_SPEC lists them, updated in place; caps: (gt identities,
     track ids, pair slots, run rows).  Every check comes before the launch; no synchronisation."""
-    if tracks.dim() != 3 or tracks.shape[-1] != 8 or tracks.shape[0] < 1 or tracks.shape[1] < 1:
-        raise _lib.TamtrHipError(f'trackmap_update: expected tracks [B, nq, 8], got {tuple(tracks.shape)}')
-    B, nq, _ = tracks.shape
-    if gt.dim() != 3 or gt.shape[0] != B or gt.shape[1] < 1 or gt.shape[2] != 7:
-        raise _lib.TamtrHipError(f'trackmap_update: expected gt [B, ng, 7] with B = {B}, got {tuple(gt.shape)}')
-    ng = gt.shape[1]
-    if tuple(tcounts.shape) != (B,) or tuple(gcounts.shape) != (B,):
-        raise _lib.TamtrHipError(f'trackmap_update: tcounts and gcounts must be [B] = [{B}], got {tuple(tcounts.shape)} and {tuple(gcounts.shape)}')
-    if tracks.dtype != torch.float32 or gt.dtype != torch.float32 or tcounts.dtype != torch.int32 or gcounts.dtype != torch.int32:
-        raise _lib.TamtrHipError('trackmap_update: tracks and gt must be float32, tcounts and gcounts int32')
-    if not float(iou) > 0:
-        raise _lib.TamtrHipError(f'trackmap_update: iou must be positive, got {iou}')
-    ptrs, ccaps = _trackmap_state('trackmap_update', state, nc, caps)
+    B, nq, ng, tracks, tcounts, gt, gcounts = _mot_frames('trackmap_update', tracks, tcounts, gt, gcounts, iou)
+    ptrs, ccaps = _eval_state('trackmap_update', TRACKMAP_STATE_SPEC, TRACKMAP_CAPS, state, nc, caps)
     require_gpu(tracks, tcounts, gt, gcounts)
-    workspace = _mot_workspace('trackmap_update', workspace, trackmap_workspace_bytes(nq, ng, nc, caps), tracks.device)
-    tracks, tcounts, gt, gcounts = _c(tracks), _c(tcounts), _c(gt), _c(gcounts)
+    workspace = _eval_workspace('trackmap_update', workspace, trackmap_workspace_bytes(nq, ng, nc, caps), tracks.device)
     call('tamtr_trackmap_update', ptr(tracks), ptr(tcounts), ptr(gt), ptr(gcounts), B, nq, ng, int(nc), float(iou), ptrs, ccaps,
          ptr(workspace), int(workspace.numel()), stream_ptr())
 
@@ -2371,8 +2331,8 @@ def trackmap_end_sequence(state, nc, caps, thresholds, workspace=None):
     greedy matching at every threshold, the append to the run's table, the clearing of the sequence's state).  thresholds: 1 to 10
     fp64 values, handed over as they are.  No synchronisation."""
     thr = _trackmap_thresholds('trackmap_end_sequence', thresholds)
-    ptrs, ccaps = _trackmap_state('trackmap_end_sequence', state, nc, caps)
-    workspace = _mot_workspace('trackmap_end_sequence', workspace, trackmap_workspace_bytes(1, 1, nc, caps), state['hdr'].device)
+    ptrs, ccaps = _eval_state('trackmap_end_sequence', TRACKMAP_STATE_SPEC, TRACKMAP_CAPS, state, nc, caps)
+    workspace = _eval_workspace('trackmap_end_sequence', workspace, trackmap_workspace_bytes(1, 1, nc, caps), state['hdr'].device)
     call('tamtr_trackmap_end_sequence', (ctypes.c_double * len(thr))(*thr), len(thr), HOTA_EPS, int(nc), ptrs, ccaps, ptr(workspace),
          int(workspace.numel()), stream_ptr())
 
@@ -2386,7 +2346,7 @@ def trackmap_accumulate(state, nc, caps, n_thresholds):
     nt = int(n_thresholds)
     if not 1 <= nt <= 10:
         raise _lib.TamtrHipError(f'trackmap_accumulate: n_thresholds must be 1 .. 10, got {n_thresholds}')
-    _trackmap_state('trackmap_accumulate', state, nc, caps)
+    _eval_state('trackmap_accumulate', TRACKMAP_STATE_SPEC, TRACKMAP_CAPS, state, nc, caps)
     nc, R = int(nc), int(caps[3])
     dev = state['hdr'].device
     valid = torch.arange(R, device=dev, dtype=torch.int32) < state['hdr'][0]

@@ -317,28 +317,28 @@ MOT_HDR_FRAME, MOT_HDR_OVER_GT, MOT_HDR_OVER_TRK, MOT_HDR_OVER_ROWS = 0, 1, 2, 3
 VISDRONE_CATEGORIES = {0: (0, 2), **{c: (c - 1, 0) for c in range(1, 11)}, 11: (0, 1)}
 
 
-class MotEvaluator:
-    """CLEAR-MOT and identity counts of tracker rows against ground truth, kept on `device` (csrc/mot.hip states the rule and the
-    state).  gt_capacity: ground-truth identities (class, id) per sequence; track_capacity: track ids are used as they are and must
-    be below it; nq / ng: track / ground-truth rows per frame the workspace is sized for (a batch with wider track rows gets a larger
-    workspace on its first use; ground-truth rows beyond ng are counted as overflow)."""
-    times_key = 'mot'      # the key of Predictor.times this evaluator's launches go under
+HDR_OVER_FRAME = ('gt identities beyond gt_capacity', 'track ids beyond track_capacity', 'rows beyond ng / nq per frame')
 
-    def __init__(self, device, nc, iou=0.5, gt_capacity=1024, track_capacity=4096, nq=300, ng=300):
+
+class _SequenceEvaluator:
+    """What the tracking evaluators share: the state on `device`, the ground truth's way up, one update launch per batch and the
+    bookkeeping of the sequence in progress.  A subclass names its host path, its state spec and capacities in ops, the offset of its
+    overflow counters in hdr with what each counts and the exception they raise, and supplies _ws_bytes, _launch_update and
+    _launch_end."""
+    host = spec = cap_names = hdr_over = over = overflow = None
+
+    def __init__(self, device, nc, iou, caps, nq, ng):
         self.device = torch.device(device)
         if self.device.type != 'cuda':
-            raise ops._lib.TamtrHipError('MotEvaluator needs an MI355X; engine.mot_evaluate is the host path')
-        self.nc, self.iou = int(nc), float(iou)
-        self.gt_capacity, self.track_capacity, self.nq, self.ng = int(gt_capacity), int(track_capacity), int(nq), int(ng)
-        if min(self.nc, self.gt_capacity, self.track_capacity, self.nq, self.ng) < 1:
+            raise ops._lib.TamtrHipError(f'{type(self).__name__} needs an MI355X; engine.{self.host} is the host path')
+        self.nc, self.iou, self.nq, self.ng = int(nc), float(iou), int(nq), int(ng)
+        self.caps = tuple(int(c) for c in caps)
+        self.gt_capacity = self.caps[0]
+        if min(self.nc, self.nq, self.ng, *self.caps) < 1:
             raise ValueError('nc, the capacities, nq and ng must be positive')
         self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
-        self.state = {k: torch.zeros(shape(self.nc, self.gt_capacity, self.track_capacity), device=self.device, dtype=dt)
-                      for k, dt, shape in ops.MOT_STATE_SPEC}
+        self.state = {k: torch.zeros(shape(self.nc, self.caps), device=self.device, dtype=dt) for k, dt, shape in self.spec}
         self.rows, self.open = {}, False
-
-    def _ws_bytes(self):
-        return ops.mot_workspace_bytes(self.nq, self.ng, self.nc, self.gt_capacity, self.track_capacity)
 
     def reset(self):
         """Forget every count and the sequence in progress.  No synchronisation."""
@@ -372,27 +372,54 @@ class MotEvaluator:
             self.nq = int(tracks.shape[1])
             self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
         gt, gcounts = self.upload(gt_frames)
-        ops.mot_update(tracks, tcounts, gt, gcounts, self.state, self.nc, self.gt_capacity, self.track_capacity, self.iou, self.workspace)
+        self._launch_update(tracks, tcounts, gt, gcounts)
         self.open = True
 
     def end_sequence(self):
-        """Reduce the sequence in progress (one launch) and start a new one: ground-truth ids may be used again.  No synchronisation."""
-        ops.mot_end_sequence(self.state, self.nc, self.gt_capacity, self.track_capacity, len(self.rows), self.workspace)
+        """Reduce the sequence in progress (the class states the launches) and start a new one: ground-truth ids may be used again.
+        No synchronisation."""
+        self._launch_end()
         self.rows, self.open = {}, False
 
     def check_overflow(self, hdr):
         """Raise when the header (read by the caller, e.g. from the predictor's packed copy) counts anything beyond a capacity."""
-        g, t, r = (int(hdr[i]) for i in (MOT_HDR_OVER_GT, MOT_HDR_OVER_TRK, MOT_HDR_OVER_ROWS))
-        if g or t or r:
-            raise MotOverflow(f'{g} rows with a ground-truth identity beyond gt_capacity {self.gt_capacity}, {t} with a track id beyond '
-                              f'track_capacity {self.track_capacity}, {r} rows beyond ng {self.ng} / nq {self.nq} per frame were left out: '
-                              'build the evaluator with larger capacities')
+        over = [(int(hdr[self.hdr_over + i]), what) for i, what in enumerate(self.over)]
+        if any(n for n, _ in over):
+            raise self.overflow('; '.join(f'{n} {what}' for n, what in over if n) + f' were left out (capacities '
+                                f'{", ".join(self.cap_names)} = {self.caps}, ng {self.ng}, nq {self.nq}): build the evaluator with larger '
+                                'capacities')
+
+    def _ended(self):
+        if self.open:
+            raise RuntimeError('a sequence is in progress: call end_sequence() before reading the results')
+
+
+class MotEvaluator(_SequenceEvaluator):
+    """CLEAR-MOT and identity counts of tracker rows against ground truth, kept on `device` (csrc/mot.hip states the rule and the
+    state).  gt_capacity: ground-truth identities (class, id) per sequence; track_capacity: track ids are used as they are and must
+    be below it; nq / ng: track / ground-truth rows per frame the workspace is sized for (a batch with wider track rows gets a larger
+    workspace on its first use; ground-truth rows beyond ng are counted as overflow).  The end of a sequence is one launch."""
+    times_key = 'mot'      # the key of Predictor.times this evaluator's launches go under
+    host, spec, cap_names = 'mot_evaluate', ops.MOT_STATE_SPEC, ops.MOT_CAPS
+    hdr_over, over, overflow = MOT_HDR_OVER_GT, HDR_OVER_FRAME, MotOverflow
+
+    def __init__(self, device, nc, iou=0.5, gt_capacity=1024, track_capacity=4096, nq=300, ng=300):
+        super().__init__(device, nc, iou, (gt_capacity, track_capacity), nq, ng)
+        self.track_capacity = self.caps[1]
+
+    def _ws_bytes(self):
+        return ops.mot_workspace_bytes(self.nq, self.ng, self.nc, *self.caps)
+
+    def _launch_update(self, tracks, tcounts, gt, gcounts):
+        ops.mot_update(tracks, tcounts, gt, gcounts, self.state, self.nc, *self.caps, self.iou, self.workspace)
+
+    def _launch_end(self):
+        ops.mot_end_sequence(self.state, self.nc, *self.caps, len(self.rows), self.workspace)
 
     def counts(self):
         """The run's counts as engine.mot_evaluate returns them (synchronises; raises MotOverflow)."""
         from .engine import MOT_COUNT_KEYS
-        if self.open:
-            raise RuntimeError('a sequence is in progress: call end_sequence() before reading the results')
+        self._ended()
         c, s, hdr = (self.state[k].cpu().numpy() for k in ('counts', 'iou_sum', 'hdr'))
         self.check_overflow(hdr)
         out = {k: c[:, i].astype(np.int64) for i, k in enumerate(MOT_COUNT_KEYS)}
@@ -406,69 +433,37 @@ class MotEvaluator:
 
 
 # ------------------------------------------------------------------------------------------------ HOTA
-HOTA_HDR_OVER = ('gt identities beyond gt_capacity', 'track ids beyond track_capacity', 'rows beyond ng / nq per frame',
-                 'pairs beyond log_capacity', 'frames beyond frame_capacity', 'pairs that found no slot in pair_capacity')   # hdr[2:8]
+HOTA_HDR_OVER = HDR_OVER_FRAME + ('pairs beyond log_capacity', 'frames beyond frame_capacity',
+                                  'pairs that found no slot in pair_capacity')   # hdr[2:8]
 
 
-class HotaEvaluator:
+class HotaEvaluator(_SequenceEvaluator):
     """HOTA counts of tracker rows against ground truth, kept on `device` (csrc/hota.hip states the rule and the state).  The methods
     are MotEvaluator's.  gt_capacity / track_capacity / nq / ng as there; pair_capacity: slots of the sparse pair table (distinct
     (ground truth, track) pairs with a positive IoU in a sequence; the table fills badly beyond about half); log_capacity: positive
     pairs logged over the frames of a sequence; frame_capacity: frames of a sequence.  The defaults hold a 2 000-frame sequence of
-    100 rows a side several times over and take 85 MiB with the workspace."""
+    100 rows a side several times over and take 85 MiB with the workspace.  The end of a sequence is the second pass and the
+    reduction, three launches."""
     times_key = 'hota'
+    host, spec, cap_names = 'hota_evaluate', ops.HOTA_STATE_SPEC, ops.HOTA_CAPS
+    hdr_over, over, overflow = 2, HOTA_HDR_OVER, HotaOverflow
 
     def __init__(self, device, nc, iou=0.5, gt_capacity=1024, track_capacity=4096, pair_capacity=1 << 18, log_capacity=1 << 20,
                  frame_capacity=4096, nq=300, ng=300):
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise ops._lib.TamtrHipError('HotaEvaluator needs an MI355X; engine.hota_evaluate is the host path')
-        self.nc, self.iou, self.nq, self.ng = int(nc), float(iou), int(nq), int(ng)
-        self.caps = (int(gt_capacity), int(track_capacity), int(pair_capacity), int(log_capacity), int(frame_capacity))
-        self.gt_capacity = self.caps[0]
-        if min(self.nc, self.nq, self.ng, *self.caps) < 1:
-            raise ValueError('nc, the capacities, nq and ng must be positive')
-        self.workspace = torch.empty(ops.hota_workspace_bytes(self.nq, self.ng), device=self.device, dtype=torch.uint8)
-        self.state = {k: torch.zeros(shape(self.nc, self.caps), device=self.device, dtype=dt) for k, dt, shape in ops.HOTA_STATE_SPEC}
-        self.rows, self.open = {}, False
+        super().__init__(device, nc, iou, (gt_capacity, track_capacity, pair_capacity, log_capacity, frame_capacity), nq, ng)
 
-    upload = MotEvaluator.upload
+    def _ws_bytes(self):
+        return ops.hota_workspace_bytes(self.nq, self.ng)
 
-    def reset(self):
-        """Forget every count and the sequence in progress.  No synchronisation."""
-        for v in self.state.values():
-            v.zero_()
-        self.rows, self.open = {}, False
-
-    def update(self, tracks, tcounts, gt_frames):
-        """As MotEvaluator.update: the ground truth goes up in one copy, one launch follows; nothing synchronises."""
-        B = tracks.shape[0]
-        if len(gt_frames) != B:
-            raise ValueError(f'{len(gt_frames)} ground-truth frames for a batch of {B}')
-        if tracks.shape[1] > self.nq:
-            self.nq = int(tracks.shape[1])
-            self.workspace = torch.empty(ops.hota_workspace_bytes(self.nq, self.ng), device=self.device, dtype=torch.uint8)
-        gt, gcounts = self.upload(gt_frames)
+    def _launch_update(self, tracks, tcounts, gt, gcounts):
         ops.hota_update(tracks, tcounts, gt, gcounts, self.state, self.nc, self.caps, self.iou, self.workspace)
-        self.open = True
 
-    def end_sequence(self):
-        """The second pass and the reduction of the sequence in progress (three launches), then a new one starts: ground-truth ids may
-        be used again.  No synchronisation."""
+    def _launch_end(self):
         ops.hota_end_sequence(self.state, self.nc, self.caps, self.nq, self.ng, self.workspace)
-        self.rows, self.open = {}, False
-
-    def check_overflow(self, hdr):
-        """Raise when the header (read by the caller, e.g. from the predictor's packed copy) counts anything beyond a capacity."""
-        over = [(int(hdr[2 + i]), what) for i, what in enumerate(HOTA_HDR_OVER)]
-        if any(n for n, _ in over):
-            raise HotaOverflow('; '.join(f'{n} {what}' for n, what in over if n) + f' were left out (capacities gt, tracks, pairs, log, frames '
-                               f'= {self.caps}, ng {self.ng}, nq {self.nq}): build the evaluator with larger capacities')
 
     def counts(self):
         """The run's counts as engine.hota_evaluate returns them (synchronises; raises HotaOverflow)."""
-        if self.open:
-            raise RuntimeError('a sequence is in progress: call end_sequence() before reading the results')
+        self._ended()
         dets, tp, loc, ass, hdr = (self.state[k].cpu().numpy() for k in ('dets', 'tp_lvl', 'loc_lvl', 'ass', 'hdr'))
         self.check_overflow(hdr)
         above = lambda lvl: np.cumsum(lvl[:, ::-1], 1)[:, ::-1][:, 1:]   # noqa: E731  a pair at level k counts for every threshold a < k
@@ -484,73 +479,37 @@ class HotaEvaluator:
 
 
 # ------------------------------------------------------------------------------------------------ track-mAP
-TRACKMAP_HDR_OVER = ('gt identities beyond gt_capacity', 'track ids beyond track_capacity', 'rows beyond ng / nq per frame',
-                     'pairs that found no slot in pair_capacity', 'tracks beyond row_capacity')   # hdr[2:7]
+TRACKMAP_HDR_OVER = HDR_OVER_FRAME + ('pairs that found no slot in pair_capacity', 'tracks beyond row_capacity')   # hdr[2:7]
 
 
-class TrackMapEvaluator:
+class TrackMapEvaluator(_SequenceEvaluator):
     """Track-mAP of tracker rows against ground truth, kept on `device` (csrc/trackmap.hip states the rule and the state): average
     precision over whole tracks, ranked by mean score and matched by spatio-temporal IoU at `thresholds` (1 to 10 values; the default
     is VisDrone-MOT's, np.linspace(0.5, 0.95, 10) gives TrackEval's).  The methods are MotEvaluator's.  gt_capacity / track_capacity /
     nq / ng as there; pair_capacity: slots of the sparse pair table (distinct (ground truth, track) pairs that intersect in a sequence;
-    the table fills badly beyond about half); row_capacity: track identities of the whole run."""
+    the table fills badly beyond about half); row_capacity: track identities of the whole run.  The end of a sequence matches its
+    tracks and appends them to the run's table, six launches; track ids may be used again after it too."""
     times_key = 'tmap'
+    host, spec, cap_names = 'track_map_evaluate', ops.TRACKMAP_STATE_SPEC, ops.TRACKMAP_CAPS
+    hdr_over, over, overflow = 2, TRACKMAP_HDR_OVER, TrackMapOverflow
 
     def __init__(self, device, nc, thresholds=(0.25, 0.5, 0.75), iou=0.5, gt_capacity=1024, track_capacity=4096, pair_capacity=1 << 18,
                  row_capacity=1 << 16, nq=300, ng=300):
         from .engine import track_map_thresholds
-        self.device = torch.device(device)
-        if self.device.type != 'cuda':
-            raise ops._lib.TamtrHipError('TrackMapEvaluator needs an MI355X; engine.track_map_evaluate is the host path')
-        self.nc, self.iou, self.nq, self.ng = int(nc), float(iou), int(nq), int(ng)
+        super().__init__(device, nc, iou, (gt_capacity, track_capacity, pair_capacity, row_capacity), nq, ng)
         self.thresholds = track_map_thresholds(thresholds)
-        self.caps = (int(gt_capacity), int(track_capacity), int(pair_capacity), int(row_capacity))
-        self.gt_capacity = self.caps[0]
-        if min(self.nc, self.nq, self.ng, *self.caps) < 1:
-            raise ValueError('nc, the capacities, nq and ng must be positive')
-        self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
-        self.state = {k: torch.zeros(shape(self.nc, self.caps), device=self.device, dtype=dt) for k, dt, shape in ops.TRACKMAP_STATE_SPEC}
-        self.rows, self.open = {}, False
 
     def _ws_bytes(self):
         return ops.trackmap_workspace_bytes(self.nq, self.ng, self.nc, self.caps)
 
-    upload = MotEvaluator.upload
-
-    def reset(self):
-        """Forget every row and the sequence in progress.  No synchronisation."""
-        for v in self.state.values():
-            v.zero_()
-        self.rows, self.open = {}, False
-
-    def update(self, tracks, tcounts, gt_frames):
-        """As MotEvaluator.update: the ground truth goes up in one copy, one launch follows; nothing synchronises."""
-        B = tracks.shape[0]
-        if len(gt_frames) != B:
-            raise ValueError(f'{len(gt_frames)} ground-truth frames for a batch of {B}')
-        if tracks.shape[1] > self.nq:
-            self.nq = int(tracks.shape[1])
-            self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
-        gt, gcounts = self.upload(gt_frames)
+    def _launch_update(self, tracks, tcounts, gt, gcounts):
         ops.trackmap_update(tracks, tcounts, gt, gcounts, self.state, self.nc, self.caps, self.iou, self.workspace)
-        self.open = True
 
-    def end_sequence(self):
-        """Match the tracks of the sequence in progress and append them to the run's table (six launches), then a new one starts:
-        ground-truth and track ids may be used again.  No synchronisation."""
+    def _launch_end(self):
         ops.trackmap_end_sequence(self.state, self.nc, self.caps, self.thresholds, self.workspace)
-        self.rows, self.open = {}, False
-
-    def check_overflow(self, hdr):
-        """Raise when the header (read by the caller, e.g. from the predictor's packed copy) counts anything beyond a capacity."""
-        over = [(int(hdr[2 + i]), what) for i, what in enumerate(TRACKMAP_HDR_OVER)]
-        if any(n for n, _ in over):
-            raise TrackMapOverflow('; '.join(f'{n} {what}' for n, what in over if n) + f' were left out (capacities gt, tracks, pairs, rows '
-                                   f'= {self.caps}, ng {self.ng}, nq {self.nq}): build the evaluator with larger capacities')
 
     def _read(self, *keys):
-        if self.open:
-            raise RuntimeError('a sequence is in progress: call end_sequence() before reading the results')
+        self._ended()
         hdr = self.state['hdr'].cpu().numpy()
         self.check_overflow(hdr)
         n = int(hdr[0])

@@ -174,7 +174,7 @@ def test_overflow_is_counted_and_nothing_is_written_past_a_table():
     ev = evaluator(1, nq=12, ng=8, G=G_, Tcap=T_)
     big = {}
     for k, dt, shape in ops.MOT_STATE_SPEC:
-        sh = shape(1, G_, T_)
+        sh = shape(1, (G_, T_))
         big[k] = torch.full((sh[0] + pad,) + sh[1:], 77, dtype=dt, device='cuda')
         big[k][:sh[0]] = 0
         ev.state[k] = big[k][:sh[0]]
@@ -192,7 +192,7 @@ def test_overflow_is_counted_and_nothing_is_written_past_a_table():
     hdr = ev.state['hdr'].cpu().numpy()
     assert hdr.tolist() == [0, 4, 10, 2, 0, 0, 0, 0]      # per frame 2 gt identities beyond 4 and ids 8 .. 12; 2 rows beyond ng
     for k, dt, shape in ops.MOT_STATE_SPEC:
-        assert bool((big[k][shape(1, G_, T_)[0]:] == 77).all()), f'{k}: written past the table'
+        assert bool((big[k][shape(1, (G_, T_))[0]:] == 77).all()), f'{k}: written past the table'
     assert bool((ws[need:] == 77).all()), 'written past the workspace'
     with pytest.raises(MotOverflow):
         ev.results()

@@ -168,7 +168,7 @@ def test_cpu_tensors_are_refused():
     from tamtr_amd.track import MotEvaluator
     with pytest.raises(TamtrHipError):
         MotEvaluator('cpu', 2)
-    state = {k: torch.zeros(shape(2, 4, 8), dtype=dt) for k, dt, shape in ops.MOT_STATE_SPEC}
+    state = {k: torch.zeros(shape(2, (4, 8)), dtype=dt) for k, dt, shape in ops.MOT_STATE_SPEC}
     with pytest.raises(TamtrHipError):
         ops.mot_update(torch.zeros(1, 8, 8), torch.zeros(1, dtype=torch.int32), torch.zeros(1, 8, 7), torch.zeros(1, dtype=torch.int32), state, 2, 4, 8)
     with pytest.raises(TamtrHipError, match='tracks'):
