@@ -627,7 +627,27 @@ __global__ __launch_bounds__(BN_THREADS) void bncl_bwd_apply_kernel(const T* __r
 
 }  // namespace
 
-extern "C" int tamtr_bn_slices(int B, int HW) { return B * ((HW + BN_SLICE - 1) / BN_SLICE); }
+// ================================================================================================ host side
+// Every templated kernel is launched through bn_dispatch (NCHW: T) or bncl_dispatch (channels-last: T and V): `f` is a generic lambda,
+// called with a tag whose type carries the instantiation.
+template <typename T_, int V_ = 0>
+struct Tag { using T = T_; static constexpr int V = V_; };
+
+template <typename F>
+static void bn_dispatch(int dtype, F f) {
+  if (dtype == TAMTR_F32) f(Tag<float>{});
+  else f(Tag<bf16_t>{});
+}
+
+// every kernel runs workgroups of BN_THREADS and no dynamic LDS
+template <typename K, typename... A>
+static void launch(K kernel, dim3 grid, hipStream_t s, A... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(BN_THREADS), 0, s, args...);
+}
+
+// ---- NCHW entry points: x [B, C, HW]
+static int bn_slices_hw(int HW) { return (HW + BN_SLICE - 1) / BN_SLICE; }
+extern "C" int tamtr_bn_slices(int B, int HW) { return B * bn_slices_hw(HW); }
 
 static int bn_check(const void* a, const void* b, int B, int C, int HW, int dtype, int act) {
   if (!a || !b || B <= 0 || C <= 0 || HW <= 0) return TAMTR_EINVAL;
@@ -646,17 +666,14 @@ extern "C" int tamtr_bn_act_fwd(const void* x, const float* gamma, const float* 
   const int rc = bn_check(x, y, B, C, HW, dtype, act);
   if (rc) return rc;
   if (!gamma || !beta || !mean_rstd || !partials) return TAMTR_EINVAL;
-  const int sh = (HW + BN_SLICE - 1) / BN_SLICE, vec = bn_vec(x, y, HW, dtype);
-  const dim3 grid(sh, C, B);
+  const int vec = bn_vec(x, y, HW, dtype);
+  const dim3 grid(bn_slices_hw(HW), C, B);
   hipStream_t s = (hipStream_t)stream;
-  if (dtype == TAMTR_F32) hipLaunchKernelGGL(bn_stats_kernel<float>, grid, dim3(BN_THREADS), 0, s, (const float*)x, partials, C, HW, vec);
-  else hipLaunchKernelGGL(bn_stats_kernel<bf16_t>, grid, dim3(BN_THREADS), 0, s, (const bf16_t*)x, partials, C, HW, vec);
-  if (dtype == TAMTR_F32)
-    hipLaunchKernelGGL(bn_apply_kernel<float>, grid, dim3(BN_THREADS), 0, s, (const float*)x, partials, mean_rstd, running_mean, running_var,
-                       gamma, beta, (float*)y, C, HW, vec, act, eps, momentum);
-  else
-    hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, grid, dim3(BN_THREADS), 0, s, (const bf16_t*)x, partials, mean_rstd, running_mean,
-                       running_var, gamma, beta, (bf16_t*)y, C, HW, vec, act, eps, momentum);
+  bn_dispatch(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    launch(bn_stats_kernel<T>, grid, s, (const T*)x, partials, C, HW, vec);
+    launch(bn_apply_kernel<T>, grid, s, (const T*)x, partials, mean_rstd, running_mean, running_var, gamma, beta, (T*)y, C, HW, vec, act, eps, momentum);
+  });
   return tamtr_launch_status();
 }
 
@@ -665,36 +682,47 @@ extern "C" int tamtr_bn_act_bwd(const void* gy, const void* x, const float* gamm
   const int rc = bn_check(gy, x, B, C, HW, dtype, act);
   if (rc) return rc;
   if (!gamma || !beta || !mean_rstd || !gx || !ggamma || !gbeta || !partials) return TAMTR_EINVAL;
-  const int sh = (HW + BN_SLICE - 1) / BN_SLICE, vec = bn_vec(x, gy, HW, dtype) && bn_vec(gx, nullptr, HW, dtype);
-  const dim3 grid(sh, C, B);
+  const int vec = bn_vec(x, gy, HW, dtype) && bn_vec(gx, nullptr, HW, dtype);
+  const dim3 grid(bn_slices_hw(HW), C, B);
   hipStream_t s = (hipStream_t)stream;
   const float inv = 1.f / ((float)B * (float)HW);
-  if (dtype == TAMTR_F32) {
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<float>, grid, dim3(BN_THREADS), 0, s, (const float*)gy, (const float*)x, mean_rstd, gamma, beta,
-                       partials, C, HW, vec, act);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, grid, dim3(BN_THREADS), 0, s, (const float*)gy, (const float*)x, mean_rstd, gamma, beta,
-                       partials, (float*)gx, ggamma, gbeta, C, HW, vec, act, inv);
-  } else {
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<bf16_t>, grid, dim3(BN_THREADS), 0, s, (const bf16_t*)gy, (const bf16_t*)x, mean_rstd, gamma,
-                       beta, partials, C, HW, vec, act);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, grid, dim3(BN_THREADS), 0, s, (const bf16_t*)gy, (const bf16_t*)x, mean_rstd, gamma,
-                       beta, partials, (bf16_t*)gx, ggamma, gbeta, C, HW, vec, act, inv);
-  }
+  bn_dispatch(dtype, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    launch(bn_bwd_reduce_kernel<T>, grid, s, (const T*)gy, (const T*)x, mean_rstd, gamma, beta, partials, C, HW, vec, act);
+    launch(bn_bwd_apply_kernel<T>, grid, s, (const T*)gy, (const T*)x, mean_rstd, gamma, beta, partials, (T*)gx, ggamma, gbeta, C, HW, vec, act, inv);
+  });
   return tamtr_launch_status();
 }
 
 // ---- channels-last entry points: x [N, C], C contiguous
 static int bncl_vec(int C, int dtype) { return dtype == TAMTR_BF16 && C % 8 == 0 ? 8 : 4; }
-static int bncl_iters(long long N, int C, int dtype) {   // chunk length: about 1024 workgroups, 16 KB .. 256 KB each
-  const long long piece = (long long)BN_THREADS * bncl_vec(C, dtype), total = N * C;
+
+// How a call on an [N, C] map launches, the same for every channels-last kernel: S workgroups, each over `iters` pieces of 256 threads x V
+// elements (a chunk is about 1 / 1024 of the map, 16 KB .. 256 KB), on stream s
+struct ClPlan { int C, dtype, V, iters, S; size_t total; hipStream_t s; };
+static ClPlan bncl_plan(long long N, int C, int dtype, void* stream = nullptr) {
+  const int V = bncl_vec(C, dtype);
+  const long long piece = (long long)BN_THREADS * V, total = N * C;
   const long long it = (total / piece / 1024 + CL_UNROLL - 1) / CL_UNROLL * CL_UNROLL;
-  return (int)(it < 4 ? 4 : it > 64 ? 64 : it);
+  const long long iters = it < 4 ? 4 : it > 64 ? 64 : it;
+  return {C, dtype, V, (int)iters, (int)((total + iters * piece - 1) / (iters * piece)), (size_t)total, (hipStream_t)stream};
 }
-extern "C" int tamtr_bncl_blocks(long long N, int C, int dtype) {
-  if (N <= 0 || C <= 0) return 0;
-  const long long chunk = (long long)bncl_iters(N, C, dtype) * BN_THREADS * bncl_vec(C, dtype);
-  return (int)((N * C + chunk - 1) / chunk);
+extern "C" int tamtr_bncl_blocks(long long N, int C, int dtype) { return N <= 0 || C <= 0 ? 0 : bncl_plan(N, C, dtype).S; }
+
+template <typename F>
+static void bncl_dispatch(const ClPlan& p, F f) {
+  if (p.dtype == TAMTR_F32) f(Tag<float, 4>{});
+  else if (p.V == 8) f(Tag<bf16_t, 8>{});
+  else f(Tag<bf16_t, 4>{});
 }
+
+// partials = [C][S][per_chunk] floats that the S workgroups leave, then [C][tail] that the sum kernel leaves for the apply kernel
+// (ops.py sizes the buffers by the same figures)
+struct PartLayout { int per_chunk, tail; };
+constexpr PartLayout PART_FWD{3, 0};    // (count, mean, M2); the pair forward holds two such blocks
+constexpr PartLayout PART_BWD{2, 2};    // sums of dz and dz * xhat
+constexpr PartLayout PART_BWD2{3, 3};   // the pair: sums of dz, dz * xhat1, dz * xhat2
+static float* part_end(float* partials, const ClPlan& p, PartLayout l) { return partials + (size_t)p.C * p.S * l.per_chunk; }
 
 static int bncl_check(const void* a, const void* b, long long N, int C, int dtype, int act) {
   if (!a || !b || N <= 0 || C <= 0) return TAMTR_EINVAL;
@@ -705,27 +733,43 @@ static int bncl_check(const void* a, const void* b, long long N, int C, int dtyp
   if (((uintptr_t)a | (uintptr_t)b) % 16) return TAMTR_EUNSUP;
   return TAMTR_OK;
 }
+static bool pow2(int C) { return (C & (C - 1)) == 0; }
+static int cshift_of(int C) {   // log2 of a power-of-two C: the kernels split an element index into (row, column) by shift and mask
+  int cshift = 0;
+  while ((1 << cshift) < C) ++cshift;
+  return cshift;
+}
+// row pitch of gy in elements (C: packed); a pitch other than C needs the shift-and-mask split
+static bool ldgy_ok(long long ldgy, int C, int dtype) { return ldgy >= C && ldgy % bncl_vec(C, dtype) == 0 && pow2(C); }
+// image segments of a wider buffer: image b's seg_rows rows start b * seg_pitch elements after image 0's
+static bool seg_ok(long long seg_rows, long long seg_pitch, long long N, int C) {
+  return seg_rows > 0 && N % seg_rows == 0 && seg_pitch >= seg_rows * C && seg_pitch % 8 == 0 && seg_rows <= 0x7fffffffLL;
+}
+
+// batch statistics of x -> mean_rstd [C][2] and the running-statistics update, through `partials` [C][S][3]
+static void bncl_stats_finalize(const ClPlan& p, const void* x, float* partials, float* mean_rstd, float* running_mean, float* running_var,
+                                float eps, float momentum) {
+  bncl_dispatch(p, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    launch(bncl_stats_kernel<T, tag.V>, p.S, p.s, (const T*)x, partials, p.total, p.C, p.iters);
+  });
+  launch(bn_finalize_kernel, p.C, p.s, partials, mean_rstd, running_mean, running_var, p.S, eps, momentum);
+}
 
 static int bncl_act_fwd_impl(const void* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
                              const void* residual, void* y, float* mean_rstd, float* partials, long long N, int C, float eps,
-                             float momentum, int act, int dtype, void* stream, Seg ysg, int cshift) {
+                             float momentum, int act, int dtype, void* stream, Seg ysg) {
   const int rc = bncl_check(x, y, N, C, dtype, act);
   if (rc) return rc;
   if (!gamma || !beta || !mean_rstd || !partials) return TAMTR_EINVAL;
   if (residual && (uintptr_t)residual % 16) return TAMTR_EUNSUP;
-  const int S = tamtr_bncl_blocks(N, C, dtype), V = bncl_vec(C, dtype), iters = bncl_iters(N, C, dtype);
-  const size_t total = (size_t)N * C;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == TAMTR_F32) hipLaunchKernelGGL((bncl_stats_kernel<float, 4>), dim3(S), dim3(BN_THREADS), 0, s, (const float*)x, partials, total, C, iters);
-  else if (V == 8) hipLaunchKernelGGL((bncl_stats_kernel<bf16_t, 8>), dim3(S), dim3(BN_THREADS), 0, s, (const bf16_t*)x, partials, total, C, iters);
-  else hipLaunchKernelGGL((bncl_stats_kernel<bf16_t, 4>), dim3(S), dim3(BN_THREADS), 0, s, (const bf16_t*)x, partials, total, C, iters);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(BN_THREADS), 0, s, partials, mean_rstd, running_mean, running_var, S, eps, momentum);
-  if (dtype == TAMTR_F32)
-    hipLaunchKernelGGL((bncl_apply_kernel<float, 4>), dim3(S), dim3(BN_THREADS), 0, s, (const float*)x, mean_rstd, gamma, beta, (const float*)residual, (float*)y, total, C, iters, act, ysg, cshift);
-  else if (V == 8)
-    hipLaunchKernelGGL((bncl_apply_kernel<bf16_t, 8>), dim3(S), dim3(BN_THREADS), 0, s, (const bf16_t*)x, mean_rstd, gamma, beta, (const bf16_t*)residual, (bf16_t*)y, total, C, iters, act, ysg, cshift);
-  else
-    hipLaunchKernelGGL((bncl_apply_kernel<bf16_t, 4>), dim3(S), dim3(BN_THREADS), 0, s, (const bf16_t*)x, mean_rstd, gamma, beta, (const bf16_t*)residual, (bf16_t*)y, total, C, iters, act, ysg, cshift);
+  const ClPlan p = bncl_plan(N, C, dtype, stream);
+  const int cshift = ysg.rows ? cshift_of(C) : 0;
+  bncl_stats_finalize(p, x, partials, mean_rstd, running_mean, running_var, eps, momentum);
+  bncl_dispatch(p, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    launch(bncl_apply_kernel<T, tag.V>, p.S, p.s, (const T*)x, mean_rstd, gamma, beta, (const T*)residual, (T*)y, p.total, C, p.iters, act, ysg, cshift);
+  });
   return tamtr_launch_status();
 }
 
@@ -733,7 +777,7 @@ extern "C" int tamtr_bncl_act_fwd(const void* x, const float* gamma, const float
                                   const void* residual, void* y, float* mean_rstd, float* partials, long long N, int C, float eps,
                                   float momentum, int act, int dtype, void* stream) {
   return bncl_act_fwd_impl(x, gamma, beta, running_mean, running_var, residual, y, mean_rstd, partials, N, C, eps, momentum, act, dtype, stream,
-                           Seg{0, 0}, 0);
+                           Seg{0, 0});
 }
 
 /* the same with the OUTPUT written as image segments of a wider buffer: y points at the first row of image 0's segment, image b's rows
@@ -741,11 +785,9 @@ extern "C" int tamtr_bncl_act_fwd(const void* x, const float* gamma, const float
 extern "C" int tamtr_bncl_act_seg_fwd(const void* x, const float* gamma, const float* beta, float* running_mean, float* running_var, void* y,
                                       long long seg_rows, long long seg_pitch, float* mean_rstd, float* partials, long long N, int C, float eps,
                                       float momentum, int act, int dtype, void* stream) {
-  if (seg_rows <= 0 || N % seg_rows || seg_pitch < seg_rows * C || seg_pitch % 8 || (C & (C - 1)) || seg_rows > 0x7fffffffLL) return TAMTR_EUNSUP;
-  int cshift = 0;
-  while ((1 << cshift) < C) ++cshift;
+  if (!seg_ok(seg_rows, seg_pitch, N, C) || !pow2(C)) return TAMTR_EUNSUP;
   return bncl_act_fwd_impl(x, gamma, beta, running_mean, running_var, nullptr, y, mean_rstd, partials, N, C, eps, momentum, act, dtype, stream,
-                           Seg{(unsigned)seg_rows, (size_t)seg_pitch}, cshift);
+                           Seg{(unsigned)seg_rows, (size_t)seg_pitch});
 }
 
 static int bncl_act_bwd_impl(const void* gy, long long ldgy, const void* x, const float* gamma, const float* beta,
@@ -753,28 +795,20 @@ static int bncl_act_bwd_impl(const void* gy, long long ldgy, const void* x, cons
                              int dtype, void* stream, Seg gsg) {
   const int rc = bncl_check(gy, x, N, C, dtype, act);
   if (rc) return rc;
-  if (ldgy < C || ldgy % bncl_vec(C, dtype) || (C & (C - 1))) return TAMTR_EUNSUP;   // row pitch of gy in elements (C: packed)
-  int cshift = 0;
-  while ((1 << cshift) < C) ++cshift;
+  if (!ldgy_ok(ldgy, C, dtype)) return TAMTR_EUNSUP;
   if (!gamma || !beta || !mean_rstd || !gx || !ggamma || !gbeta || !partials || (uintptr_t)gx % 16) return TAMTR_EINVAL;
-  const int S = tamtr_bncl_blocks(N, C, dtype), V = bncl_vec(C, dtype), iters = bncl_iters(N, C, dtype);
-  const size_t total = (size_t)N * C;
-  hipStream_t s = (hipStream_t)stream;
-  float* sums = partials + (size_t)C * S * 2;  // [C][2] after the per-chunk partials
+  const ClPlan p = bncl_plan(N, C, dtype, stream);
+  const int cshift = cshift_of(C);
+  float* sums = part_end(partials, p, PART_BWD);
   const float inv = 1.f / (float)N;
-  if (dtype == TAMTR_F32)
-    hipLaunchKernelGGL((bncl_bwd_reduce_kernel<float, 4>), dim3(S), dim3(BN_THREADS), 0, s, (const float*)gy, (const float*)x, mean_rstd, gamma, beta, partials, total, C, iters, act, (size_t)ldgy, cshift, gsg);
-  else if (V == 8)
-    hipLaunchKernelGGL((bncl_bwd_reduce_kernel<bf16_t, 8>), dim3(S), dim3(BN_THREADS), 0, s, (const bf16_t*)gy, (const bf16_t*)x, mean_rstd, gamma, beta, partials, total, C, iters, act, (size_t)ldgy, cshift, gsg);
-  else
-    hipLaunchKernelGGL((bncl_bwd_reduce_kernel<bf16_t, 4>), dim3(S), dim3(BN_THREADS), 0, s, (const bf16_t*)gy, (const bf16_t*)x, mean_rstd, gamma, beta, partials, total, C, iters, act, (size_t)ldgy, cshift, gsg);
-  hipLaunchKernelGGL(bncl_sum_kernel, dim3(C), dim3(BN_THREADS), 0, s, partials, sums, ggamma, gbeta, S);
-  if (dtype == TAMTR_F32)
-    hipLaunchKernelGGL((bncl_bwd_apply_kernel<float, 4>), dim3(S), dim3(BN_THREADS), 0, s, (const float*)gy, (const float*)x, mean_rstd, gamma, beta, sums, (float*)gx, total, C, iters, act, inv, (size_t)ldgy, cshift, gsg);
-  else if (V == 8)
-    hipLaunchKernelGGL((bncl_bwd_apply_kernel<bf16_t, 8>), dim3(S), dim3(BN_THREADS), 0, s, (const bf16_t*)gy, (const bf16_t*)x, mean_rstd, gamma, beta, sums, (bf16_t*)gx, total, C, iters, act, inv, (size_t)ldgy, cshift, gsg);
-  else
-    hipLaunchKernelGGL((bncl_bwd_apply_kernel<bf16_t, 4>), dim3(S), dim3(BN_THREADS), 0, s, (const bf16_t*)gy, (const bf16_t*)x, mean_rstd, gamma, beta, sums, (bf16_t*)gx, total, C, iters, act, inv, (size_t)ldgy, cshift, gsg);
+  bncl_dispatch(p, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    launch(bncl_bwd_reduce_kernel<T, tag.V>, p.S, p.s, (const T*)gy, (const T*)x, mean_rstd, gamma, beta, partials, p.total, C, p.iters, act,
+           (size_t)ldgy, cshift, gsg);
+    launch(bncl_sum_kernel, C, p.s, partials, sums, ggamma, gbeta, p.S);
+    launch(bncl_bwd_apply_kernel<T, tag.V>, p.S, p.s, (const T*)gy, (const T*)x, mean_rstd, gamma, beta, sums, (T*)gx, p.total, C, p.iters, act, inv,
+           (size_t)ldgy, cshift, gsg);
+  });
   return tamtr_launch_status();
 }
 
@@ -788,7 +822,7 @@ extern "C" int tamtr_bncl_act_bwd(const void* gy, long long ldgy, const void* x,
 extern "C" int tamtr_bncl_act_seg_bwd(const void* gy, long long seg_rows, long long seg_pitch, const void* x, const float* gamma, const float* beta,
                                       const float* mean_rstd, void* gx, float* ggamma, float* gbeta, float* partials, long long N, int C, int act,
                                       int dtype, void* stream) {
-  if (seg_rows <= 0 || N % seg_rows || seg_pitch < seg_rows * C || seg_pitch % 8 || seg_rows > 0x7fffffffLL) return TAMTR_EUNSUP;
+  if (!seg_ok(seg_rows, seg_pitch, N, C)) return TAMTR_EUNSUP;
   return bncl_act_bwd_impl(gy, C, x, gamma, beta, mean_rstd, gx, ggamma, gbeta, partials, N, C, act, dtype, stream,
                            Seg{(unsigned)seg_rows, (size_t)seg_pitch});
 }
@@ -802,23 +836,16 @@ extern "C" int tamtr_bncl2_act_fwd(const void* x1, const float* gamma1, const fl
   if (!rc) rc = bncl_check(x2, y, N, C, dtype, act);
   if (rc) return rc;
   if (!gamma1 || !beta1 || !gamma2 || !beta2 || !mean_rstd || !partials) return TAMTR_EINVAL;
-  const int S = tamtr_bncl_blocks(N, C, dtype), V = bncl_vec(C, dtype), iters = bncl_iters(N, C, dtype);
-  const size_t total = (size_t)N * C;
-  hipStream_t s = (hipStream_t)stream;
-  float* mr2 = mean_rstd + 2 * (size_t)C;           // [2][C][2]
-  float* part2 = partials + (size_t)C * S * 3;      // [2][C][S][3]
-#define STATS(T, VV, X, P) hipLaunchKernelGGL((bncl_stats_kernel<T, VV>), dim3(S), dim3(BN_THREADS), 0, s, (const T*)X, P, total, C, iters)
-#define APPLY(T, VV)                                                                                                                   \
-  hipLaunchKernelGGL((bncl2_apply_kernel<T, VV>), dim3(S), dim3(BN_THREADS), 0, s, (const T*)x1, (const T*)x2, mean_rstd, mr2, gamma1, beta1, \
-                     gamma2, beta2, (T*)y, total, C, iters, act)
-  if (dtype == TAMTR_F32) { STATS(float, 4, x1, partials); STATS(float, 4, x2, part2); }
-  else if (V == 8) { STATS(bf16_t, 8, x1, partials); STATS(bf16_t, 8, x2, part2); }
-  else { STATS(bf16_t, 4, x1, partials); STATS(bf16_t, 4, x2, part2); }
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(BN_THREADS), 0, s, partials, mean_rstd, running_mean1, running_var1, S, eps, momentum);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(BN_THREADS), 0, s, part2, mr2, running_mean2, running_var2, S, eps, momentum);
-  if (dtype == TAMTR_F32) APPLY(float, 4); else if (V == 8) APPLY(bf16_t, 8); else APPLY(bf16_t, 4);
-#undef STATS
-#undef APPLY
+  const ClPlan p = bncl_plan(N, C, dtype, stream);
+  float* mr2 = mean_rstd + 2 * (size_t)C;                 // [2][C][2]
+  float* part2 = part_end(partials, p, PART_FWD);         // [2][C][S][3]
+  bncl_stats_finalize(p, x1, partials, mean_rstd, running_mean1, running_var1, eps, momentum);
+  bncl_stats_finalize(p, x2, part2, mr2, running_mean2, running_var2, eps, momentum);
+  bncl_dispatch(p, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    launch(bncl2_apply_kernel<T, tag.V>, p.S, p.s, (const T*)x1, (const T*)x2, mean_rstd, mr2, gamma1, beta1, gamma2, beta2, (T*)y, p.total, C, p.iters,
+           act);
+  });
   return tamtr_launch_status();
 }
 
@@ -832,26 +859,20 @@ extern "C" int tamtr_bncl2_act_bwd(const void* gy, long long ldgy, const void* x
   if (!gamma1 || !beta1 || !gamma2 || !beta2 || !mean_rstd || !gx2 || !ggamma1 || !gbeta1 || !ggamma2 || !gbeta2 || !partials ||
       (uintptr_t)gx2 % 16)
     return TAMTR_EINVAL;
-  if (ldgy < C || ldgy % bncl_vec(C, dtype) || (C & (C - 1))) return TAMTR_EUNSUP;
-  int cshift = 0;
-  while ((1 << cshift) < C) ++cshift;
-  const int S = tamtr_bncl_blocks(N, C, dtype), V = bncl_vec(C, dtype), iters = bncl_iters(N, C, dtype);
-  const size_t total = (size_t)N * C;
-  hipStream_t s = (hipStream_t)stream;
+  if (!ldgy_ok(ldgy, C, dtype)) return TAMTR_EUNSUP;
+  const ClPlan p = bncl_plan(N, C, dtype, stream);
+  const int cshift = cshift_of(C);
   const float* mr2 = mean_rstd + 2 * (size_t)C;
-  float* sums = partials + (size_t)C * S * 3;  // [C][3] after the per-chunk partials
+  float* sums = part_end(partials, p, PART_BWD2);
   const float inv = 1.f / (float)N;
-#define RED(T, VV)                                                                                                                       \
-  hipLaunchKernelGGL((bncl2_bwd_reduce_kernel<T, VV>), dim3(S), dim3(BN_THREADS), 0, s, (const T*)gy, (const T*)x1, (const T*)x2, mean_rstd, mr2, \
-                     gamma1, beta1, gamma2, beta2, partials, total, C, iters, act, (size_t)ldgy, cshift)
-#define APP(T, VV)                                                                                                                       \
-  hipLaunchKernelGGL((bncl2_bwd_apply_kernel<T, VV>), dim3(S), dim3(BN_THREADS), 0, s, (const T*)gy, (const T*)x1, (const T*)x2, mean_rstd, mr2,  \
-                     gamma1, beta1, gamma2, beta2, sums, (T*)gx1, (T*)gx2, total, C, iters, act, inv, (size_t)ldgy, cshift)
-  if (dtype == TAMTR_F32) RED(float, 4); else if (V == 8) RED(bf16_t, 8); else RED(bf16_t, 4);
-  hipLaunchKernelGGL(bncl2_sum_kernel, dim3(C), dim3(BN_THREADS), 0, s, partials, sums, ggamma1, gbeta1, ggamma2, gbeta2, S);
-  if (dtype == TAMTR_F32) APP(float, 4); else if (V == 8) APP(bf16_t, 8); else APP(bf16_t, 4);
-#undef RED
-#undef APP
+  bncl_dispatch(p, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    launch(bncl2_bwd_reduce_kernel<T, tag.V>, p.S, p.s, (const T*)gy, (const T*)x1, (const T*)x2, mean_rstd, mr2, gamma1, beta1, gamma2, beta2, partials,
+           p.total, C, p.iters, act, (size_t)ldgy, cshift);
+    launch(bncl2_sum_kernel, C, p.s, partials, sums, ggamma1, gbeta1, ggamma2, gbeta2, p.S);
+    launch(bncl2_bwd_apply_kernel<T, tag.V>, p.S, p.s, (const T*)gy, (const T*)x1, (const T*)x2, mean_rstd, mr2, gamma1, beta1, gamma2, beta2, sums,
+           (T*)gx1, (T*)gx2, p.total, C, p.iters, act, inv, (size_t)ldgy, cshift);
+  });
   return tamtr_launch_status();
 }
 
@@ -860,8 +881,7 @@ extern "C" int tamtr_bncl2_act_bwd(const void* gy, long long ldgy, const void* x
 extern "C" int tamtr_bn_finalize(const float* partials, float* mean_rstd, float* running_mean, float* running_var, int C, int S, float eps,
                                  float momentum, void* stream) {
   if (!partials || !mean_rstd || C <= 0 || S <= 0 || (!running_mean) != (!running_var)) return TAMTR_EINVAL;
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(BN_THREADS), 0, (hipStream_t)stream, partials, mean_rstd, running_mean, running_var, S, eps,
-                     momentum);
+  launch(bn_finalize_kernel, C, (hipStream_t)stream, partials, mean_rstd, running_mean, running_var, S, eps, momentum);
   return tamtr_launch_status();
 }
 
@@ -872,12 +892,6 @@ extern "C" int tamtr_bncl_stats(const void* x, float* running_mean, float* runni
   const int rc = bncl_check(x, mean_rstd, N, C, dtype, 0);
   if (rc) return rc;
   if (!partials) return TAMTR_EINVAL;
-  const int S = tamtr_bncl_blocks(N, C, dtype), V = bncl_vec(C, dtype), iters = bncl_iters(N, C, dtype);
-  const size_t total = (size_t)N * C;
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == TAMTR_F32) hipLaunchKernelGGL((bncl_stats_kernel<float, 4>), dim3(S), dim3(BN_THREADS), 0, s, (const float*)x, partials, total, C, iters);
-  else if (V == 8) hipLaunchKernelGGL((bncl_stats_kernel<bf16_t, 8>), dim3(S), dim3(BN_THREADS), 0, s, (const bf16_t*)x, partials, total, C, iters);
-  else hipLaunchKernelGGL((bncl_stats_kernel<bf16_t, 4>), dim3(S), dim3(BN_THREADS), 0, s, (const bf16_t*)x, partials, total, C, iters);
-  hipLaunchKernelGGL(bn_finalize_kernel, dim3(C), dim3(BN_THREADS), 0, s, partials, mean_rstd, running_mean, running_var, S, eps, momentum);
+  bncl_stats_finalize(bncl_plan(N, C, dtype, stream), x, partials, mean_rstd, running_mean, running_var, eps, momentum);
   return tamtr_launch_status();
 }

@@ -285,21 +285,6 @@ def gate_cl_ok(x, C, nh, T=None):
             and x.data_ptr() % 16 == 0)
 
 
-@torch.no_grad()
-def bn_stats_cl(x2d, bn):
-    """Batch statistics of a channels-last [N, C] map for a consumer that normalises in its own load: mean_rstd f32 [C, 2]; updates the
-    BatchNorm's running statistics and counter like a training-mode forward."""
-    require_gpu(x2d)
-    x2d = _c(x2d)
-    N, C = x2d.shape
-    mom = _bn_tick(bn)
-    mr = torch.empty(C, 2, device=x2d.device, dtype=torch.float32)
-    part = torch.empty(C * _lib.lib().tamtr_bncl_blocks(N, C, dtype_code(x2d)) * 3, device=x2d.device, dtype=torch.float32)
-    rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
-    call('tamtr_bncl_stats', ptr(x2d), ptr(rm), ptr(rv), ptr(mr), ptr(part), N, C, float(bn.eps), float(mom), dtype_code(x2d), stream_ptr())
-    return mr
-
-
 def conv3x3_cl_ok(x, conv):
     """What tamtr_conv3x3_cl_stats_fwd takes: a bf16 channels-last map (or a channel slice of one) into a plain 3x3 / stride 1 / pad 1
     convolution without bias, C1 % 32 == 0, C2 % 64 == 0.  TAMTR_PROJ_CONV=miopen keeps the library convolution (A/B switch)."""
@@ -325,10 +310,9 @@ def conv3x3_cl_stats(x, conv, bn):
     wpk = torch.empty(9 * C1 * C2, device=x.device, dtype=torch.bfloat16)
     call('tamtr_conv3x3_pack_weight', ptr(w), ptr(wpk), C1, C2, dtype_code(w), stream_ptr())
     y = torch.empty((B, C2, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-    mom = _bn_tick(bn)
+    rm, rv, mom = _bn_train_call(bn)
     mr = torch.empty(C2, 2, device=x.device, dtype=torch.float32)
     part = torch.empty(C2 * _lib.lib().tamtr_conv3x3_tiles(B, H, W) * 3, device=x.device, dtype=torch.float32)
-    rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
     call('tamtr_conv3x3_cl_stats_fwd', ptr(x), _cl_pitch(x), ptr(wpk), ptr(y), ptr(rm), ptr(rv), ptr(mr), ptr(part), B, H, W, C1, C2,
          float(bn.eps), float(mom), stream_ptr())
     return y, mr
@@ -2790,6 +2774,63 @@ def layer_norm_module(norm, x):
     return norm(x)
 
 
+# ------------------------------------------------------------------------------------------------ BatchNorm (csrc/bn.hip)
+# Every entry point is called from one place, which sizes its `partials` workspace (the PART_* layouts of csrc/bn.hip: floats per chunk, then
+# a per-channel tail).  The channels-last pair serves two autograd nodes and is a pair of launchers (_bncl_fwd, _bncl_bwd: allocate the outputs
+# and the workspace, launch, return the tensors); the NCHW and the two-BatchNorm entry points have one caller each, their autograd node.
+def _f32(dev, *shape):
+    return torch.empty(*shape, device=dev, dtype=torch.float32)
+
+
+def _bncl_blocks(x):
+    return _lib.lib().tamtr_bncl_blocks(x.shape[0], x.shape[1], dtype_code(x))
+
+
+def _bncl_stats_buffers(x):
+    """mean_rstd [C, 2] and the (count, mean, M2) partials of the statistics pass over rows x [N, C]."""
+    C = x.shape[1]
+    return _f32(x.device, C, 2), _f32(x.device, C * _bncl_blocks(x) * 3)
+
+
+def _bncl_fwd(x, gamma, beta, rm, rv, eps, mom, act, residual=None, seg=None):
+    """Channels-last rows x [N, C] -> y, the fp32 forms of gamma and beta, mean_rstd [C, 2].  seg = (destination pointer, seg_rows,
+    seg_pitch): the result is written as image segments of a wider buffer (include/tamtr_hip.h tamtr_bncl_act_seg_fwd) and y is None."""
+    N, C = x.shape
+    g32, b32 = _c(gamma.float()), _c(beta.float())
+    y = None if seg else torch.empty_like(x)
+    mr, part = _bncl_stats_buffers(x)
+    tail = (ptr(mr), ptr(part), N, C, float(eps), float(mom), act, dtype_code(x), stream_ptr())
+    if seg:
+        call('tamtr_bncl_act_seg_fwd', ptr(x), ptr(g32), ptr(b32), ptr(rm), ptr(rv), *seg, *tail)
+    else:
+        res = None if residual is None else _c(residual.to(x.dtype))
+        call('tamtr_bncl_act_fwd', ptr(x), ptr(g32), ptr(b32), ptr(rm), ptr(rv), ptr(res), ptr(y), *tail)
+    return y, g32, b32, mr
+
+
+def _bncl_bwd(gy, x, g32, b32, mr, act, seg=None):
+    """-> d(x), and d(gamma), d(beta) in fp32.  gy: rows as _gy_rows leaves them; or seg = (pointer, seg_rows, seg_pitch): the gradient is
+    read as image segments of a wider buffer (the gradient of _bncl_fwd's segmented result)."""
+    N, C = x.shape
+    gx = torch.empty_like(x)
+    gg, gb = _f32(x.device, C), _f32(x.device, C)
+    part = _f32(x.device, C * _bncl_blocks(x) * 2 + 2 * C)
+    src = seg if seg else (ptr(gy), gy.stride(0))
+    call('tamtr_bncl_act_seg_bwd' if seg else 'tamtr_bncl_act_bwd', *src, ptr(x), ptr(g32), ptr(b32), ptr(mr), ptr(gx), ptr(gg), ptr(gb), ptr(part),
+         N, C, act, dtype_code(x), stream_ptr())
+    return gx, gg, gb
+
+
+def _gy_rows(gy, x):
+    """gy as the kernels take it: x's dtype, unit column stride, 16-byte aligned rows (a channel slice of a wider map is fine)."""
+    C = x.shape[1]
+    gy = gy.to(x.dtype)
+    v = 8 if (x.dtype == torch.bfloat16 and C % 8 == 0) else 4
+    if not (gy.stride(1) == 1 and gy.stride(0) >= C and gy.stride(0) % v == 0 and gy.data_ptr() % 16 == 0 and (C & (C - 1)) == 0):
+        gy = gy.contiguous()
+    return gy
+
+
 class _BNAct(torch.autograd.Function):
     """Training-mode BatchNorm2d (+ SiLU) on an NCHW map - csrc/bn.hip.  running_mean / running_var are updated in place."""
 
@@ -2801,8 +2842,8 @@ class _BNAct(torch.autograd.Function):
         HW = x.numel() // (B * C)
         g32, b32 = _c(gamma.float()), _c(beta.float())
         y = torch.empty_like(x)
-        mr = torch.empty(C, 2, device=x.device, dtype=torch.float32)
-        part = torch.empty(C * _lib.lib().tamtr_bn_slices(B, HW) * 3, device=x.device, dtype=torch.float32)
+        mr = _f32(x.device, C, 2)
+        part = _f32(x.device, C * _lib.lib().tamtr_bn_slices(B, HW) * 3)
         call('tamtr_bn_act_fwd', ptr(x), ptr(g32), ptr(b32), ptr(running_mean), ptr(running_var), ptr(y), ptr(mr), ptr(part), B, C, HW,
              float(eps), float(momentum), int(bool(silu)), dtype_code(x), stream_ptr())
         ctx.save_for_backward(x, g32, b32, mr)
@@ -2817,8 +2858,8 @@ class _BNAct(torch.autograd.Function):
         HW = x.numel() // (B * C)
         gy = _c(gy.to(x.dtype))
         gx = torch.empty_like(x)
-        gg, gb = torch.empty(C, device=x.device, dtype=torch.float32), torch.empty(C, device=x.device, dtype=torch.float32)
-        part = torch.empty(C * _lib.lib().tamtr_bn_slices(B, HW) * 2, device=x.device, dtype=torch.float32)
+        gg, gb = _f32(x.device, C), _f32(x.device, C)
+        part = _f32(x.device, C * _lib.lib().tamtr_bn_slices(B, HW) * 2)
         call('tamtr_bn_act_bwd', ptr(gy), ptr(x), ptr(g32), ptr(b32), ptr(mr), ptr(gx), ptr(gg), ptr(gb), ptr(part), B, C, HW, act,
              dtype_code(x), stream_ptr())
         return gx, gg.to(g_dt), gb.to(b_dt), None, None, None, None, None
@@ -2831,15 +2872,8 @@ class _BNActCL(torch.autograd.Function):
     def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, silu, residual=None):
         require_gpu(x, gamma, beta)
         x = _c(x)
-        N, C = x.shape
-        g32, b32 = _c(gamma.float()), _c(beta.float())
-        y = torch.empty_like(x)
-        mr = torch.empty(C, 2, device=x.device, dtype=torch.float32)
-        part = torch.empty(C * _lib.lib().tamtr_bncl_blocks(N, C, dtype_code(x)) * 3, device=x.device, dtype=torch.float32)
-        res = None if residual is None else _c(residual.to(x.dtype))
-        call('tamtr_bncl_act_fwd', ptr(x), ptr(g32), ptr(b32), ptr(running_mean), ptr(running_var), ptr(res), ptr(y), ptr(mr), ptr(part), N, C,
-             float(eps), float(momentum), int(bool(silu)), dtype_code(x), stream_ptr())
-        ctx.save_for_backward(x, g32, b32, mr)
+        y, *saved = _bncl_fwd(x, gamma, beta, running_mean, running_var, eps, momentum, int(bool(silu)), residual)
+        ctx.save_for_backward(x, *saved)
         ctx.cfg = (int(bool(silu)), gamma.dtype, beta.dtype, None if residual is None else residual.dtype)
         return y
 
@@ -2847,25 +2881,10 @@ class _BNActCL(torch.autograd.Function):
     def backward(ctx, gy):
         x, g32, b32, mr = ctx.saved_tensors
         act, g_dt, b_dt, res_dt = ctx.cfg
-        N, C = x.shape
         g_res = None if res_dt is None else gy.to(res_dt)   # y = act(bn(x)) + residual: the shortcut's gradient is gy itself
-        gy = _gy_rows(gy, x)   # (a channel slice of a concatenation's gradient is read in place through its row pitch)
-        gx = torch.empty_like(x)
-        gg, gb = torch.empty(C, device=x.device, dtype=torch.float32), torch.empty(C, device=x.device, dtype=torch.float32)
-        part = torch.empty(C * _lib.lib().tamtr_bncl_blocks(N, C, dtype_code(x)) * 2 + 2 * C, device=x.device, dtype=torch.float32)
-        call('tamtr_bncl_act_bwd', ptr(gy), gy.stride(0), ptr(x), ptr(g32), ptr(b32), ptr(mr), ptr(gx), ptr(gg), ptr(gb), ptr(part), N, C, act,
-             dtype_code(x), stream_ptr())
+        # (a channel slice of a concatenation's gradient is read in place through its row pitch)
+        gx, gg, gb = _bncl_bwd(_gy_rows(gy, x), x, g32, b32, mr, act)
         return gx, gg.to(g_dt), gb.to(b_dt), None, None, None, None, None, g_res
-
-
-def _gy_rows(gy, x):
-    """gy as the kernels take it: x's dtype, unit column stride, 16-byte aligned rows (a channel slice of a wider map is fine)."""
-    C = x.shape[1]
-    gy = gy.to(x.dtype)
-    v = 8 if (x.dtype == torch.bfloat16 and C % 8 == 0) else 4
-    if not (gy.stride(1) == 1 and gy.stride(0) >= C and gy.stride(0) % v == 0 and gy.data_ptr() % 16 == 0 and (C & (C - 1)) == 0):
-        gy = gy.contiguous()
-    return gy
 
 
 class _BN2ActCL(torch.autograd.Function):
@@ -2879,8 +2898,8 @@ class _BN2ActCL(torch.autograd.Function):
         N, C = x1.shape
         p1 = [_c(t.float()) for t in (ga1, be1, ga2, be2)]
         y = torch.empty_like(x1)
-        mr = torch.empty(2, C, 2, device=x1.device, dtype=torch.float32)
-        part = torch.empty(2 * C * _lib.lib().tamtr_bncl_blocks(N, C, dtype_code(x1)) * 3, device=x1.device, dtype=torch.float32)
+        mr = _f32(x1.device, 2, C, 2)
+        part = _f32(x1.device, 2 * C * _bncl_blocks(x1) * 3)
         call('tamtr_bncl2_act_fwd', ptr(x1), ptr(p1[0]), ptr(p1[1]), ptr(rm1), ptr(rv1), ptr(x2), ptr(p1[2]), ptr(p1[3]), ptr(rm2), ptr(rv2),
              ptr(y), ptr(mr), ptr(part), N, C, float(eps), float(momentum), int(bool(silu)), dtype_code(x1), stream_ptr())
         ctx.save_for_backward(x1, x2, *p1, mr)
@@ -2894,11 +2913,17 @@ class _BN2ActCL(torch.autograd.Function):
         N, C = x1.shape
         gy = _gy_rows(gy, x1)
         gx1, gx2 = torch.empty_like(x1), torch.empty_like(x2)
-        gg = torch.empty(4, C, device=x1.device, dtype=torch.float32)
-        part = torch.empty(C * _lib.lib().tamtr_bncl_blocks(N, C, dtype_code(x1)) * 3 + 3 * C, device=x1.device, dtype=torch.float32)
+        gg = _f32(x1.device, 4, C)
+        part = _f32(x1.device, C * _bncl_blocks(x1) * 3 + 3 * C)
         call('tamtr_bncl2_act_bwd', ptr(gy), gy.stride(0), ptr(x1), ptr(x2), ptr(g1), ptr(b1), ptr(g2), ptr(b2), ptr(mr), ptr(gx1), ptr(gx2),
              gg[0].data_ptr(), gg[1].data_ptr(), gg[2].data_ptr(), gg[3].data_ptr(), ptr(part), N, C, act, dtype_code(x1), stream_ptr())
         return (gx1, gg[0].to(dt_g1), gg[1].to(dt_b1), None, None, gx2, gg[2].to(dt_g2), gg[3].to(dt_b2), None, None, None, None, None)
+
+
+def _cat_segments(t, Ls):
+    """The levels' segments of t [B, sum L_i, C] as the launchers take them: (pointer to image 0's rows, seg_rows, seg_pitch)."""
+    C = t.shape[2]
+    return [(t.data_ptr() + sum(Ls[:i]) * C * t.element_size(), L, sum(Ls) * C) for i, L in enumerate(Ls)]
 
 
 class _BNCatCL(torch.autograd.Function):
@@ -2912,20 +2937,11 @@ class _BNCatCL(torch.autograd.Function):
         ys, gammas, betas, rms, rvs = (args[k * n:(k + 1) * n] for k in range(5))
         require_gpu(*ys)
         ys = [_c(y) for y in ys]
-        C, dt = ys[0].shape[1], ys[0].dtype
         Ls = [y.shape[0] // B for y in ys]
-        Lt = sum(Ls)
-        feats = torch.empty(B, Lt, C, device=ys[0].device, dtype=dt)
-        saved, off = [], 0
-        for y, ga, be, rm, rv, mom, L in zip(ys, gammas, betas, rms, rvs, moms, Ls):
-            N = B * L
-            g32, b32 = _c(ga.float()), _c(be.float())
-            mr = torch.empty(C, 2, device=y.device, dtype=torch.float32)
-            part = torch.empty(C * _lib.lib().tamtr_bncl_blocks(N, C, dtype_code(y)) * 3, device=y.device, dtype=torch.float32)
-            call('tamtr_bncl_act_seg_fwd', ptr(y), ptr(g32), ptr(b32), ptr(rm), ptr(rv), feats.data_ptr() + off * C * feats.element_size(), L, Lt * C,
-                 ptr(mr), ptr(part), N, C, float(eps), float(mom), 0, dtype_code(y), stream_ptr())
-            saved += [y, g32, b32, mr]
-            off += L
+        feats = torch.empty(B, sum(Ls), ys[0].shape[1], device=ys[0].device, dtype=ys[0].dtype)
+        saved = []
+        for y, ga, be, rm, rv, mom, seg in zip(ys, gammas, betas, rms, rvs, moms, _cat_segments(feats, Ls)):
+            saved += [y, *_bncl_fwd(y, ga, be, rm, rv, eps, mom, 0, seg=seg)[1:]]
         ctx.save_for_backward(*saved)
         ctx.cfg = (B, n, Ls, [g.dtype for g in gammas], [b.dtype for b in betas])
         return feats
@@ -2934,37 +2950,12 @@ class _BNCatCL(torch.autograd.Function):
     def backward(ctx, gf):
         B, n, Ls, gdt, bdt = ctx.cfg
         saved = ctx.saved_tensors
-        Lt = sum(Ls)
-        C = saved[0].shape[1]
         gf = _c(gf.to(saved[0].dtype))
-        gxs, ggs, gbs, off = [], [], [], 0
-        for i, L in enumerate(Ls):
-            y, g32, b32, mr = saved[4 * i:4 * i + 4]
-            N = B * L
-            gx = torch.empty_like(y)
-            gg, gb = torch.empty(C, device=y.device, dtype=torch.float32), torch.empty(C, device=y.device, dtype=torch.float32)
-            part = torch.empty(C * _lib.lib().tamtr_bncl_blocks(N, C, dtype_code(y)) * 2 + 2 * C, device=y.device, dtype=torch.float32)
-            call('tamtr_bncl_act_seg_bwd', gf.data_ptr() + off * C * gf.element_size(), L, Lt * C, ptr(y), ptr(g32), ptr(b32), ptr(mr), ptr(gx), ptr(gg),
-                 ptr(gb), ptr(part), N, C, 0, dtype_code(y), stream_ptr())
+        gxs, ggs, gbs = [], [], []
+        for i, seg in enumerate(_cat_segments(gf, Ls)):
+            gx, gg, gb = _bncl_bwd(None, *saved[4 * i:4 * i + 4], 0, seg=seg)
             gxs.append(gx); ggs.append(gg.to(gdt[i])); gbs.append(gb.to(bdt[i]))
-            off += L
         return (None, None, None, None, *gxs, *ggs, *gbs, *([None] * (2 * n)))
-
-
-def bn_cat_cl(ys, bns, B):
-    """The token memory: per level y_i [B * L_i, C] -> BatchNorm_i (training mode, batch statistics, no activation) -> [B, sum L_i, C],
-    each level written into its segment directly.  All BatchNorms share eps; C a power of two."""
-    moms = [_bn_tick(bn) for bn in bns]
-    n = len(ys)
-    return _BNCatCL.apply(int(B), float(bns[0].eps), tuple(float(m) for m in moms), n, *ys, *[bn.weight for bn in bns], *[bn.bias for bn in bns],
-                          *[bn.running_mean for bn in bns], *[bn.running_var for bn in bns])
-
-
-def bn_cat_cl_ok(ys, bns):
-    C = ys[0].shape[1]
-    return (all(y.is_cuda and y.dim() == 2 and y.shape[1] == C and y.dtype == ys[0].dtype and y.dtype in (torch.float32, torch.bfloat16) for y in ys)
-            and C & (C - 1) == 0 and bn_cl_ok(C, ys[0].dtype) and all(bn.training and bn.track_running_stats and bn.affine and bn.eps == bns[0].eps for bn in bns)
-            and _os.environ.get('TAMTR_BN_CAT') != 'torch')
 
 
 _BN_COUNTERS = None
@@ -2984,27 +2975,28 @@ def end_bn_counter_batch():
         torch._foreach_add_(pending, 1)
 
 
+def _bn_train_call(bn):
+    """(running_mean, running_var, momentum) for one training-mode call of `bn`, the statistics None when it tracks none; counts the call:
+    num_batches_tracked += 1 (deferred to one multi-tensor kernel inside a counter batch)."""
+    if bn.track_running_stats:
+        if _BN_COUNTERS is not None and bn.momentum is not None:
+            _BN_COUNTERS.append(bn.num_batches_tracked)
+        else:
+            bn.num_batches_tracked += 1
+    mom = bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
+    return (bn.running_mean, bn.running_var, mom) if bn.track_running_stats else (None, None, mom)
+
+
 def bn_cl_ok(C, dtype):
     """Channel counts the channels-last BatchNorm kernels take (include/tamtr_hip.h: tamtr_bncl_act_fwd)."""
     v = 8 if dtype == torch.bfloat16 and C % 8 == 0 else 4
     return C % 4 == 0 and C <= 1024 and C // v <= 256 and 256 % (C // v) == 0
 
 
-def _bn_tick(bn):
-    """num_batches_tracked += 1 (deferred to one multi-tensor kernel inside a counter batch) and the momentum of this call."""
-    if bn.track_running_stats:
-        if _BN_COUNTERS is not None and bn.momentum is not None:
-            _BN_COUNTERS.append(bn.num_batches_tracked)
-        else:
-            bn.num_batches_tracked += 1
-    return bn.momentum if bn.momentum is not None else 1.0 / float(bn.num_batches_tracked)
-
-
 def bn_act(x, bn, silu, residual=None):
     """act(bn(x)) [+ residual] for an nn.BatchNorm2d in training mode (batch statistics; running stats and num_batches_tracked
     updated).  residual: only with the channels-last [N, C] form."""
-    mom = _bn_tick(bn)
-    rm, rv = (bn.running_mean, bn.running_var) if bn.track_running_stats else (None, None)
+    rm, rv, mom = _bn_train_call(bn)
     if x.dim() == 2:   # [N, C] token-major / channels-last map
         return _BNActCL.apply(x, bn.weight, bn.bias, rm, rv, bn.eps, mom, silu, residual)
     y = _BNAct.apply(x, bn.weight, bn.bias, rm, rv, bn.eps, mom, silu)
@@ -3015,7 +3007,34 @@ def bn2_act(x1, bn1, x2, bn2, silu):
     """act(bn1(x1) + bn2(x2)) on channels-last [N, C] maps, both BatchNorm2d in training mode with running statistics."""
     if bn1.eps != bn2.eps or bn1.momentum != bn2.momentum or not (bn1.track_running_stats and bn2.track_running_stats):
         raise _lib.TamtrHipError('bn2_act: the two BatchNorms must share eps / momentum and track running statistics')
-    mom = _bn_tick(bn1)
-    _bn_tick(bn2)
-    return _BN2ActCL.apply(x1, bn1.weight, bn1.bias, bn1.running_mean, bn1.running_var, x2, bn2.weight, bn2.bias, bn2.running_mean,
-                           bn2.running_var, bn1.eps, mom, silu)
+    rm1, rv1, mom = _bn_train_call(bn1)
+    rm2, rv2, _ = _bn_train_call(bn2)
+    return _BN2ActCL.apply(x1, bn1.weight, bn1.bias, rm1, rv1, x2, bn2.weight, bn2.bias, rm2, rv2, bn1.eps, mom, silu)
+
+
+def bn_cat_cl(ys, bns, B):
+    """The token memory: per level y_i [B * L_i, C] -> BatchNorm_i (training mode, batch statistics, no activation) -> [B, sum L_i, C],
+    each level written into its segment directly.  All BatchNorms share eps; C a power of two."""
+    rms, rvs, moms = zip(*[_bn_train_call(bn) for bn in bns])
+    return _BNCatCL.apply(int(B), float(bns[0].eps), tuple(float(m) for m in moms), len(ys), *ys, *[bn.weight for bn in bns],
+                          *[bn.bias for bn in bns], *rms, *rvs)
+
+
+def bn_cat_cl_ok(ys, bns):
+    C = ys[0].shape[1]
+    return (all(y.is_cuda and y.dim() == 2 and y.shape[1] == C and y.dtype == ys[0].dtype and y.dtype in (torch.float32, torch.bfloat16) for y in ys)
+            and C & (C - 1) == 0 and bn_cl_ok(C, ys[0].dtype) and all(bn.training and bn.track_running_stats and bn.affine and bn.eps == bns[0].eps for bn in bns))
+
+
+@torch.no_grad()
+def bn_stats_cl(x2d, bn):
+    """Batch statistics of a channels-last [N, C] map for a consumer that normalises in its own load: mean_rstd f32 [C, 2]; updates the
+    BatchNorm's running statistics and counter like a training-mode forward."""
+    require_gpu(x2d)
+    x2d = _c(x2d)
+    N, C = x2d.shape
+    rm, rv, mom = _bn_train_call(bn)
+    mr, part = _bncl_stats_buffers(x2d)
+    call('tamtr_bncl_stats', ptr(x2d), ptr(rm), ptr(rv), ptr(mr), ptr(part), N, C, float(bn.eps), float(mom), dtype_code(x2d), stream_ptr())
+    return mr
+

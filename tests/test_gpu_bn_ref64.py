@@ -277,7 +277,7 @@ def test_bn_finalize_takes_an_empty_partial_as_a_no_op(ops, S, empty):
     K.finalize_assert(f'bn_finalize[S={S},empty={empty}]', _finalize(ops, part, eps, mom, rm, rv), S, counts, data, eps, mom, rm, rv)
 
 
-# ------------------------------------------------------------------------------------------------ host branches of bn_act / _bn_tick
+# ------------------------------------------------------------------------------------------------ host branches of bn_act / _bn_train_call
 def test_bn_act_cumulative_average_second_call(ops):
     """momentum=None: the cumulative moving average, 1 / num_batches_tracked; the second call moves the running statistics by 1 / 2.  The
     reference of the second call starts from the running statistics the first one left on the device."""
