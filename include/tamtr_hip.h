@@ -38,7 +38,9 @@ extern "C" {
  * tamtr_text_pool_project), tamtr_val_confusion, tamtr_val_ap_curves / tamtr_val_ap_tile and tamtr_bytetrack_update / tamtr_botsort_update /
  * tamtr_bytetrack_workspace_bytes, tamtr_val_coco_match / tamtr_val_coco_workspace_bytes / tamtr_val_coco_accumulate and tamtr_mot_update /
  * tamtr_mot_end_sequence / tamtr_mot_workspace_bytes, tamtr_hota_update / tamtr_hota_end_sequence / tamtr_hota_workspace_bytes,
- * tamtr_trackmap_update / tamtr_trackmap_end_sequence / tamtr_trackmap_workspace_bytes and tamtr_dw_slices / tamtr_dw_bf16 are new symbols only: no existing signature changed, so the version stayed at 36 when they were added. */
+ * tamtr_trackmap_update / tamtr_trackmap_end_sequence / tamtr_trackmap_workspace_bytes, tamtr_dw_slices / tamtr_dw_bf16 and the stream forms
+ * tamtr_bytetrack_update_streams / tamtr_botsort_update_streams / tamtr_botsort_reid_update_streams / tamtr_gmc_estimate_streams with their
+ * workspace sizes are new symbols only: no existing signature changed, so the version stayed at 36 when they were added. */
 int tamtr_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -792,6 +794,44 @@ int tamtr_gmc_state_bytes(int H, int W);
 int tamtr_gmc_estimate(const uint8_t* frames, const int32_t* counts, const double* scale, int B, int H, int W, uint8_t* st_pyr,
                        int32_t* st_kp, int32_t* st_hdr, double* warps, int32_t* stats, void* workspace, int workspace_bytes,
                        int stages, void* stream);
+
+/*      Several streams at once: one tracker per stream, one launch.  Replaces trackers/track.py:33-53, where on_predict_start builds
+ *      predictor.trackers[i] for i in range(bs) and on_predict_postprocess_end walks the images of the batch on the host, image i to
+ *      tracker i.  A batch holds B = F * S images, frame-major: image f * S + s is the f-th frame of stream s (F = 1 is the live case).
+ *      The tables are stacked: mean f64 [S, T, 8], cov f64 [S, T, 8, 8], meta i32 [S, T, 8], sc f32 [S, T, 2], hdr i32 [S, 8]
+ *      [, tfeat f32 [S, T, D]]; out, counts, warps, feat, tracks and tcounts keep their shapes over the B images.  Workgroup s owns
+ *      tracker s and walks its images in order; the workgroups share nothing, so stream s gets what the single-tracker entry point
+ *      computes on its images and its slice of the tables, bit for bit - the single-tracker entry points are these with S = 1.  A stream
+ *      without a frame at some position (ended, or a dropped frame) keeps its image with counts = 0: it does not reach the tracker.
+ *      workspace: tamtr_bytetrack_streams_workspace_bytes(S, T, nq) (tamtr_botsort_reid_streams_workspace_bytes for the ReID entry)
+ *      bytes, 16-byte aligned: S times the single-tracker size rounded up to 16 (0 = unsupported).
+ *      TAMTR_EINVAL: as the single-tracker entry, and S < 1 or B % S != 0.  TAMTR_EUNSUP: as there (LDS is per workgroup).
+ *      (New symbols only: no existing signature changed, the ABI version stays 36.) */
+int tamtr_bytetrack_update_streams(const float* out, const int32_t* counts, int B, int S, int nq, double* mean, double* cov, int32_t* meta,
+                                   float* sc, int32_t* hdr, int T, float track_high_thresh, float track_low_thresh, float new_track_thresh,
+                                   double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts, void* workspace,
+                                   int workspace_bytes, void* stream);
+int tamtr_bytetrack_streams_workspace_bytes(int S, int T, int nq);
+int tamtr_botsort_update_streams(const float* out, const int32_t* counts, const double* warps, int B, int S, int nq, double* mean, double* cov,
+                                 int32_t* meta, float* sc, int32_t* hdr, int T, float track_high_thresh, float track_low_thresh,
+                                 float new_track_thresh, double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts,
+                                 void* workspace, int workspace_bytes, void* stream);
+int tamtr_botsort_reid_update_streams(const float* out, const int32_t* counts, const double* warps, const float* feat, int B, int S, int nq,
+                                      double* mean, double* cov, int32_t* meta, float* sc, int32_t* hdr, float* tfeat, int D, int T,
+                                      float track_high_thresh, float track_low_thresh, float new_track_thresh, double match_thresh,
+                                      int max_time_lost, float proximity_thresh, double appearance_thresh, float* tracks,
+                                      int32_t* tcounts, void* workspace, int workspace_bytes, void* stream);
+int tamtr_botsort_reid_streams_workspace_bytes(int S, int T, int nq);
+
+/*      tamtr_gmc_estimate_streams: tamtr_gmc_estimate for the same frame-major batch of S streams, with the state stacked: st_pyr u8
+ *      [S, tamtr_gmc_state_bytes(H, W)], st_kp i32 [S, 1024], st_hdr i32 [S, 4].  Frame i is paired with the nearest earlier frame
+ *      i - k S of its stream whose count is positive, else with stream i % S's state if that is valid, else with nothing; afterwards
+ *      stream s's state holds its last frame with a positive count and is untouched if it had none.  The same four launches for the
+ *      whole batch, the same workspace (tamtr_gmc_workspace_bytes(B, H, W)); S = 1 is tamtr_gmc_estimate.
+ *      TAMTR_EINVAL: as tamtr_gmc_estimate, and S < 1 or B % S != 0.  (New symbol only; the ABI version stays 36.) */
+int tamtr_gmc_estimate_streams(const uint8_t* frames, const int32_t* counts, const double* scale, int B, int S, int H, int W, uint8_t* st_pyr,
+                               int32_t* st_kp, int32_t* st_hdr, double* warps, int32_t* stats, void* workspace, int workspace_bytes,
+                               int stages, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * COCO-protocol bbox evaluation (AP / AR by object size) on the device.  Replaces the step the reference leaves to pycocotools:

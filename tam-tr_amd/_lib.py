@@ -119,6 +119,13 @@ _SIGS = {
     'tamtr_gmc_workspace_offset': [_I, _I, _I, _I],
     'tamtr_gmc_state_bytes': [_I, _I],
     'tamtr_gmc_estimate': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P],
+    'tamtr_bytetrack_update_streams': [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _F, _F, _F, _D, _I, _P, _P, _P, _I, _P],
+    'tamtr_bytetrack_streams_workspace_bytes': [_I, _I, _I],
+    'tamtr_botsort_update_streams': [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _I, _F, _F, _F, _D, _I, _P, _P, _P, _I, _P],
+    'tamtr_botsort_reid_update_streams': [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _F, _F, _F, _D, _I, _F, _D, _P, _P, _P, _I,
+                                          _P],
+    'tamtr_botsort_reid_streams_workspace_bytes': [_I, _I, _I],
+    'tamtr_gmc_estimate_streams': [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P],
     'tamtr_val_coco_match': [_P, _P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P],
     'tamtr_val_coco_workspace_bytes': [_I, _I, _I],
     'tamtr_val_coco_accumulate': [_P, _P, _P, _I, _I, _P, _P, _I, _P, _P, _P, _P, _P],

@@ -40,6 +40,13 @@
 //     tx sx; b sy / sx, a, ty sy].  (Fitting a similarity to points already scaled would be wrong by pixels where sx != sy: a
 //     rotation in network pixels is not one in original pixels.)
 //
+// Streams (tamtr_gmc_estimate_streams; trackers/track.py:33-53 keeps one tracker, and with it one estimator, per image of the batch):
+// a batch of B = F * S frames is frame-major, frame f * S + s being the f-th frame of stream s, and the state is stacked: pyr [S, P],
+// kp [S, 1024], hdr [S, 4].  The rule above holds per stream: frame i is paired with the nearest earlier frame i - k S whose count is
+// positive, else with stream i % S's state if it is valid, else with nothing; after the batch stream s's state holds its last frame
+// with a positive count, and is unchanged if it had none.  The launches are the same four for the whole batch.  S = 1 is
+// tamtr_gmc_estimate.
+//
 // Four launches on the caller's stream: pyramid + corner response, cells, LK, fit (+ the state copy in spare workgroups).  The object
 // is compiled with -ffp-contract=off so that every fp32 / fp64 operation rounds as the numpy statement's does.
 #include "common.h"
@@ -212,9 +219,10 @@ __global__ __launch_bounds__(256) void gmc_cells_kernel(const float* __restrict_
   if (lane == 0) kp[(long long)b * GMC_SLOTS + cell] = best ? (int32_t)(0xffffffffu - (unsigned)(best & 0xffffffffu)) : -1;
 }
 
-__device__ __forceinline__ int gmc_pair_of(const int32_t* counts, int b, int valid) {
+// frame b's pair among the frames of its stream (b - S, b - 2 S, ...), else the stream's state (-1) if `valid`, else nothing (-2)
+__device__ __forceinline__ int gmc_pair_of(const int32_t* counts, int b, int S, int valid) {
   if (counts[b] <= 0) return -2;
-  for (int q = b - 1; q >= 0; --q)
+  for (int q = b - S; q >= 0; q -= S)
     if (counts[q] > 0) return q;
   return valid ? -1 : -2;
 }
@@ -230,12 +238,15 @@ __device__ __forceinline__ float gmc_bil(const unsigned char* P, int w, int h, f
 }
 
 // launch 3: pyramidal LK, one wavefront per keypoint slot of the paired frame
-__global__ __launch_bounds__(256) void gmc_lk_kernel(const int32_t* __restrict__ counts, GmcGeo G, const unsigned char* __restrict__ pyr,
+__global__ __launch_bounds__(256) void gmc_lk_kernel(const int32_t* __restrict__ counts, int S, GmcGeo G, const unsigned char* __restrict__ pyr,
                                                     const int32_t* __restrict__ kp, const unsigned char* __restrict__ st_pyr,
                                                     const int32_t* __restrict__ st_kp, const int32_t* __restrict__ st_hdr,
                                                     float* __restrict__ pts, int32_t* __restrict__ status, int32_t* __restrict__ pair) {
   const int lane = threadIdx.x & 63, slot = blockIdx.x * 4 + (threadIdx.x >> 6), b = blockIdx.y;
-  const int pi = gmc_pair_of(counts, b, st_hdr[0]);
+  const int sid = b % S;      // the frame's stream: its slice of the stacked state
+  st_pyr += (long long)sid * G.P;
+  st_kp += sid * GMC_SLOTS;
+  const int pi = gmc_pair_of(counts, b, S, st_hdr[4 * sid]);
   if (slot == 0 && lane == 0) pair[b] = pi;
   const long long o = (long long)b * GMC_SLOTS + slot;
   const int k = pi == -2 ? -1 : (pi == -1 ? st_kp[slot] : kp[(long long)pi * GMC_SLOTS + slot]);
@@ -327,8 +338,9 @@ __device__ __forceinline__ bool gmc_inlier(const GmcSim& s, double x, double y, 
   return rx * rx + ry * ry <= 9.0;
 }
 
-// launch 4: workgroups 0 .. B-1 fit one frame each; the others copy the last tracked frame into the state
-__global__ __launch_bounds__(256) void gmc_fit_kernel(const int32_t* __restrict__ counts, const double* __restrict__ scale, int B, GmcGeo G,
+// launch 4: workgroups 0 .. B-1 fit one frame each; the others, GMC_COPY_BLOCKS per stream, copy the stream's last tracked frame into
+// its state
+__global__ __launch_bounds__(256) void gmc_fit_kernel(const int32_t* __restrict__ counts, const double* __restrict__ scale, int B, int S, GmcGeo G,
                                                      const unsigned char* __restrict__ pyr, const int32_t* __restrict__ kp,
                                                      const float* __restrict__ pts, const int32_t* __restrict__ status,
                                                      const int32_t* __restrict__ pair, int32_t* __restrict__ fit, unsigned char* st_pyr,
@@ -337,16 +349,17 @@ __global__ __launch_bounds__(256) void gmc_fit_kernel(const int32_t* __restrict_
   __shared__ int scan[256], hcnt[GMC_HYP], tot[2];
   const int t = threadIdx.x;
   if ((int)blockIdx.x >= B) {
+    const int sid = (blockIdx.x - B) / GMC_COPY_BLOCKS, cb = (blockIdx.x - B) % GMC_COPY_BLOCKS;
     int last = -1;
-    for (int q = 0; q < B; ++q)
+    for (int q = sid; q < B; q += S)
       if (counts[q] > 0) last = q;
     if (last < 0) return;
-    const int cb = blockIdx.x - B, nth = GMC_COPY_BLOCKS * 256, me = cb * 256 + t;
+    const int nth = GMC_COPY_BLOCKS * 256, me = cb * 256 + t;
     const uint4* src = reinterpret_cast<const uint4*>(pyr + (long long)last * G.P);
-    uint4* dst = reinterpret_cast<uint4*>(st_pyr);
+    uint4* dst = reinterpret_cast<uint4*>(st_pyr + (long long)sid * G.P);
     for (long long i = me; i < G.P / 16; i += nth) dst[i] = src[i];
-    for (int i = me; i < GMC_SLOTS; i += nth) st_kp[i] = kp[(long long)last * GMC_SLOTS + i];
-    if (me == 0) st_hdr[0] = 1;
+    for (int i = me; i < GMC_SLOTS; i += nth) st_kp[sid * GMC_SLOTS + i] = kp[(long long)last * GMC_SLOTS + i];
+    if (me == 0) st_hdr[4 * sid] = 1;
     return;
   }
   const int b = blockIdx.x;
@@ -454,10 +467,12 @@ extern "C" int tamtr_gmc_state_bytes(int H, int W) {
   return gmc_geo(H, W, &g) ? (int)g.P : -1;
 }
 
-extern "C" int tamtr_gmc_estimate(const uint8_t* frames, const int32_t* counts, const double* scale, int B, int H, int W, uint8_t* st_pyr,
-                                  int32_t* st_kp, int32_t* st_hdr, double* warps, int32_t* stats, void* workspace,
-                                  int workspace_bytes, int stages, void* stream) {
-  if (!frames || !counts || !scale || !st_pyr || !st_kp || !st_hdr || !warps || !stats || !workspace || B < 1 || B > 65535) return TAMTR_EINVAL;
+extern "C" int tamtr_gmc_estimate_streams(const uint8_t* frames, const int32_t* counts, const double* scale, int B, int S, int H, int W,
+                                          uint8_t* st_pyr, int32_t* st_kp, int32_t* st_hdr, double* warps, int32_t* stats, void* workspace,
+                                          int workspace_bytes, int stages, void* stream) {
+  if (!frames || !counts || !scale || !st_pyr || !st_kp || !st_hdr || !warps || !stats || !workspace || B < 1 || B > 65535 || S < 1 ||
+      B % S != 0)
+    return TAMTR_EINVAL;
   GmcGeo g;
   if (!gmc_geo(H, W, &g)) return TAMTR_EINVAL;
   if (gmc_section(g, B, 8) > 0x7fffffffll) return TAMTR_EUNSUP;
@@ -478,9 +493,16 @@ extern "C" int tamtr_gmc_estimate(const uint8_t* frames, const int32_t* counts, 
   if (stages & 1) hipLaunchKernelGGL(gmc_pyramid_kernel, dim3(g.ntx, g.nty, B), dim3(256), 0, s, frames, g, pyr, lam, tmax);
   if (stages & 2) hipLaunchKernelGGL(gmc_cells_kernel, dim3(GMC_SLOTS / 4, B), dim3(256), 0, s, lam, tmax, g, kp);
   if (stages & 4)
-    hipLaunchKernelGGL(gmc_lk_kernel, dim3(GMC_SLOTS / 4, B), dim3(256), 0, s, counts, g, pyr, kp, st_pyr, st_kp, st_hdr, pts, status, pair);
+    hipLaunchKernelGGL(gmc_lk_kernel, dim3(GMC_SLOTS / 4, B), dim3(256), 0, s, counts, S, g, pyr, kp, st_pyr, st_kp, st_hdr, pts, status, pair);
   if (stages & 8)
-    hipLaunchKernelGGL(gmc_fit_kernel, dim3(B + GMC_COPY_BLOCKS), dim3(256), 0, s, counts, scale, B, g, pyr, kp, pts, status, pair, fit, st_pyr,
-                       st_kp, st_hdr, warps, stats);
+    hipLaunchKernelGGL(gmc_fit_kernel, dim3(B + S * GMC_COPY_BLOCKS), dim3(256), 0, s, counts, scale, B, S, g, pyr, kp, pts, status, pair, fit,
+                       st_pyr, st_kp, st_hdr, warps, stats);
   return tamtr_launch_status();
+}
+
+extern "C" int tamtr_gmc_estimate(const uint8_t* frames, const int32_t* counts, const double* scale, int B, int H, int W, uint8_t* st_pyr,
+                                  int32_t* st_kp, int32_t* st_hdr, double* warps, int32_t* stats, void* workspace,
+                                  int workspace_bytes, int stages, void* stream) {
+  return tamtr_gmc_estimate_streams(frames, counts, scale, B, 1, H, W, st_pyr, st_kp, st_hdr, warps, stats, workspace, workspace_bytes, stages,
+                                    stream);
 }

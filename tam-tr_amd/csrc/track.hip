@@ -32,10 +32,16 @@
 // column of cost L with unlimited capacity: a path that reaches that column ends there, its dual stays 0, and the problem is
 // n x (m + 1).  Where the optimum is unique the matching is the reference's.
 //
-// Design: one workgroup of one wavefront per tracker (the grid dimension is kept for several trackers); the frames are a loop with
-// a barrier between the steps.  Lists (pool, unconfirmed, high / low detections ...) are built in index order with ballots, the cost
-// matrices and lists live in a workspace in global memory (L2-resident), the solver's duals and paths in LDS.  One lane runs one
-// track's filter.  The work is tiny and latency-bound.
+// Design: one workgroup of one wavefront per tracker; the frames are a loop with a barrier between the steps.  The grid dimension is
+// the stream dimension (tamtr_*_update_streams, which stand where trackers/track.py:33-53 keeps one tracker per image of the batch):
+// a batch of B = F * S images is frame-major, image f * S + s being the f-th frame of stream s; workgroup s owns tracker s - its
+// slice of the stacked tables mean / cov / meta / sc [/ tfeat] [S, T, ...], hdr [S, 8] and of the workspace - and walks the images
+// f * S + s, f = 0 .. F-1.  The workgroups share nothing and never synchronise with each other, so stream s computes what a launch
+// with S = 1 on its own images and tables computes, bit for bit; the single-tracker entry points ARE that launch.  A stream without
+// a frame at some position keeps its image with counts = 0: it does not reach the tracker.
+// Lists (pool, unconfirmed, high / low detections ...) are built in index order with ballots, the cost matrices and lists live in a
+// workspace in global memory (L2-resident), the solver's duals and paths in LDS.  One lane runs one track's filter.  The work is tiny
+// and latency-bound.
 //
 // BoT-SORT (tamtr_botsort_update): BOTSORT.update (trackers/bot_sort.py with byte_tracker.py:81-97 and utils/kalman_filter.py:222-368)
 // is the same kernel compiled with KF = KF_XYWH; the table, the lists, the costs and the assignment are the ones above.  It differs in:
@@ -395,6 +401,8 @@ struct TrkParams {
   int32_t* tcounts;
   unsigned char* ws;
   const double* warps;   // KF_XYWH only: [B, 2, 3] or null
+  int S;                 // streams: B = F * S images, frame-major; workgroup s owns tracker s
+  size_t ws_stride;      // bytes from one tracker's workspace to the next
   static constexpr bool reid = false;
   using cost_t = float;
 };
@@ -524,7 +532,15 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(P p) {
   constexpr bool REID = P::reid;
   using cost_t = typename P::cost_t;
   extern __shared__ __align__(16) unsigned char lds[];
-  const int lane = threadIdx.x, T = p.T, nq = p.nq;
+  const int lane = threadIdx.x, T = p.T, nq = p.nq, S = p.S, sid = blockIdx.x;
+  // this workgroup's tracker: its slice of the stacked tables and of the workspace
+  p.mean += (size_t)sid * T * 8;
+  p.cov += (size_t)sid * T * 64;
+  p.meta += (size_t)sid * T * 8;
+  p.sc += (size_t)sid * T * 2;
+  p.hdr += 8 * sid;
+  p.ws += (size_t)sid * p.ws_stride;
+  if constexpr (REID) p.tfeat += (size_t)sid * T * p.D;
   TrkLsap w;
   {
     const int R = T, Cn = nq + 1;
@@ -546,7 +562,7 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(P p) {
   int *hi = dup + T, *lo = hi + nq, *left = lo + nq, *newd = left + nq, *used = newd + nq;
 
   int fid = p.hdr[0], next_id = p.hdr[1], over = p.hdr[3];
-  for (int b = 0; b < p.B; ++b) {
+  for (int b = sid; b < p.B; b += S) {   // the stream's frames, in order
     const int nd = min(max(p.counts[b], 0), nq);
     const float* d = p.out + (size_t)b * nq * 6;
     float* trow = p.tracks + (size_t)b * nq * 8;
@@ -763,51 +779,103 @@ __global__ __launch_bounds__(WAVE) void bytetrack_kernel(P p) {
   if (lane == 0) { p.hdr[0] = fid; p.hdr[1] = next_id; p.hdr[2] = live; p.hdr[3] = over; }
 }
 
-extern "C" int tamtr_bytetrack_workspace_bytes(int T, int nq) {
-  if (T < 1 || nq < 1) return 0;
-  const size_t n = trk_ws_bytes(T, nq);
-  return n > 0x7fffffff ? 0 : (int)n;
+// the workspace of S trackers: the single-tracker byte count rounded up to 16 (trk_ws_bytes is only a multiple of 4, and the ReID cost
+// matrix at the head of a workspace is fp64), S times; as int, 0 = unsupported
+static size_t trk_ws_stride(size_t one) { return (one + 15) & ~(size_t)15; }
+static int trk_ws_int(size_t n) { return n > 0x7fffffff ? 0 : (int)n; }
+
+extern "C" int tamtr_bytetrack_workspace_bytes(int T, int nq) { return T < 1 || nq < 1 ? 0 : trk_ws_int(trk_ws_bytes(T, nq)); }
+
+extern "C" int tamtr_bytetrack_streams_workspace_bytes(int S, int T, int nq) {
+  return S < 1 || T < 1 || nq < 1 ? 0 : trk_ws_int((size_t)S * trk_ws_stride(trk_ws_bytes(T, nq)));
 }
 
-template <int KF>
-static int trk_launch(const float* out, const int32_t* counts, const double* warps, int B, int nq, double* mean, double* cov, int32_t* meta,
-                      float* sc, int32_t* hdr, int T, float track_high_thresh, float track_low_thresh, float new_track_thresh,
-                      double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts, void* workspace, int workspace_bytes,
-                      void* stream) {
-  if (!out || !counts || !mean || !cov || !meta || !sc || !hdr || !tracks || !tcounts || !workspace || B < 1 || nq < 1 || T < 1)
+#define REID_MAX_D 1024
+
+extern "C" int tamtr_botsort_reid_workspace_bytes(int T, int nq) { return T < 1 || nq < 1 ? 0 : trk_ws_int(trk_reid_ws_bytes(T, nq)); }
+
+extern "C" int tamtr_botsort_reid_streams_workspace_bytes(int S, int T, int nq) {
+  return S < 1 || T < 1 || nq < 1 ? 0 : trk_ws_int((size_t)S * trk_ws_stride(trk_reid_ws_bytes(T, nq)));
+}
+
+// The one launcher of all three instantiations (REID: feat and tfeat are read, the workspace holds an fp64 cost matrix); S = 1 is the
+// single-tracker entry points' call.  S trackers need (S - 1) strides and one tracker's bytes.
+template <int KF, bool REID>
+static int trk_launch(const float* out, const int32_t* counts, const double* warps, const float* feat, int B, int S, int nq, double* mean,
+                      double* cov, int32_t* meta, float* sc, int32_t* hdr, float* tfeat, int D, int T, float track_high_thresh,
+                      float track_low_thresh, float new_track_thresh, double match_thresh, int max_time_lost, float proximity_thresh,
+                      double appearance_thresh, float* tracks, int32_t* tcounts, void* workspace, int workspace_bytes, void* stream) {
+  if (!out || !counts || !mean || !cov || !meta || !sc || !hdr || !tracks || !tcounts || !workspace || B < 1 || nq < 1 || T < 1 || S < 1 ||
+      B % S != 0)
     return TAMTR_EINVAL;
-  if (tamtr_bytetrack_workspace_bytes(T, nq) == 0 || trk_lds_bytes(T, nq) > 64 * 1024) return TAMTR_EUNSUP;
-  if (workspace_bytes < tamtr_bytetrack_workspace_bytes(T, nq)) return TAMTR_EINVAL;
-  TrkParams p{out, counts, B, nq, T, mean, cov, meta, sc, hdr, track_high_thresh, track_low_thresh, new_track_thresh, match_thresh,
-              max_time_lost, tracks, tcounts, static_cast<unsigned char*>(workspace), warps};
-  hipLaunchKernelGGL((bytetrack_kernel<KF, TrkParams>), dim3(1), dim3(WAVE), trk_lds_bytes(T, nq), (hipStream_t)stream, p);
+  if (REID && (!feat || !tfeat || D < 1)) return TAMTR_EINVAL;
+  if (warps && (reinterpret_cast<uintptr_t>(warps) & 7)) return TAMTR_EINVAL;
+  if (REID && (reinterpret_cast<uintptr_t>(workspace) & 7)) return TAMTR_EINVAL;
+  const size_t one = REID ? trk_reid_ws_bytes(T, nq) : trk_ws_bytes(T, nq), stride = trk_ws_stride(one);
+  const size_t need = (size_t)(S - 1) * stride + one;
+  if ((REID && D > REID_MAX_D) || need > 0x7fffffff || trk_lds_bytes(T, nq) > 64 * 1024) return TAMTR_EUNSUP;
+  if (workspace_bytes < 0 || (size_t)workspace_bytes < need) return TAMTR_EINVAL;
+  const TrkParams base{out, counts, B, nq, T, mean, cov, meta, sc, hdr, track_high_thresh, track_low_thresh, new_track_thresh, match_thresh,
+                       max_time_lost, tracks, tcounts, static_cast<unsigned char*>(workspace), warps, S, stride};
+  if constexpr (REID) {
+    TrkReidParams p;
+    static_cast<TrkParams&>(p) = base;
+    p.feat = feat;
+    p.tfeat = tfeat;
+    p.D = D;
+    p.prox = proximity_thresh;
+    p.app = appearance_thresh;
+    hipLaunchKernelGGL((bytetrack_kernel<KF, TrkReidParams>), dim3(S), dim3(WAVE), trk_lds_bytes(T, nq), (hipStream_t)stream, p);
+  } else {
+    hipLaunchKernelGGL((bytetrack_kernel<KF, TrkParams>), dim3(S), dim3(WAVE), trk_lds_bytes(T, nq), (hipStream_t)stream, base);
+  }
   return tamtr_launch_status();
+}
+
+extern "C" int tamtr_bytetrack_update_streams(const float* out, const int32_t* counts, int B, int S, int nq, double* mean, double* cov,
+                                              int32_t* meta, float* sc, int32_t* hdr, int T, float track_high_thresh, float track_low_thresh,
+                                              float new_track_thresh, double match_thresh, int max_time_lost, float* tracks,
+                                              int32_t* tcounts, void* workspace, int workspace_bytes, void* stream) {
+  return trk_launch<KF_XYAH, false>(out, counts, nullptr, nullptr, B, S, nq, mean, cov, meta, sc, hdr, nullptr, 0, T, track_high_thresh,
+                                    track_low_thresh, new_track_thresh, match_thresh, max_time_lost, 0.0f, 0.0, tracks, tcounts, workspace,
+                                    workspace_bytes, stream);
 }
 
 extern "C" int tamtr_bytetrack_update(const float* out, const int32_t* counts, int B, int nq, double* mean, double* cov, int32_t* meta,
                                       float* sc, int32_t* hdr, int T, float track_high_thresh, float track_low_thresh,
                                       float new_track_thresh, double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts,
                                       void* workspace, int workspace_bytes, void* stream) {
-  return trk_launch<KF_XYAH>(out, counts, nullptr, B, nq, mean, cov, meta, sc, hdr, T, track_high_thresh, track_low_thresh, new_track_thresh,
-                             match_thresh, max_time_lost, tracks, tcounts, workspace, workspace_bytes, stream);
+  return tamtr_bytetrack_update_streams(out, counts, B, 1, nq, mean, cov, meta, sc, hdr, T, track_high_thresh, track_low_thresh,
+                                        new_track_thresh, match_thresh, max_time_lost, tracks, tcounts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tamtr_botsort_update_streams(const float* out, const int32_t* counts, const double* warps, int B, int S, int nq, double* mean,
+                                            double* cov, int32_t* meta, float* sc, int32_t* hdr, int T, float track_high_thresh,
+                                            float track_low_thresh, float new_track_thresh, double match_thresh, int max_time_lost,
+                                            float* tracks, int32_t* tcounts, void* workspace, int workspace_bytes, void* stream) {
+  return trk_launch<KF_XYWH, false>(out, counts, warps, nullptr, B, S, nq, mean, cov, meta, sc, hdr, nullptr, 0, T, track_high_thresh,
+                                    track_low_thresh, new_track_thresh, match_thresh, max_time_lost, 0.0f, 0.0, tracks, tcounts, workspace,
+                                    workspace_bytes, stream);
 }
 
 extern "C" int tamtr_botsort_update(const float* out, const int32_t* counts, const double* warps, int B, int nq, double* mean, double* cov,
                                     int32_t* meta, float* sc, int32_t* hdr, int T, float track_high_thresh, float track_low_thresh,
                                     float new_track_thresh, double match_thresh, int max_time_lost, float* tracks, int32_t* tcounts,
                                     void* workspace, int workspace_bytes, void* stream) {
-  if (warps && (reinterpret_cast<uintptr_t>(warps) & 7)) return TAMTR_EINVAL;
-  return trk_launch<KF_XYWH>(out, counts, warps, B, nq, mean, cov, meta, sc, hdr, T, track_high_thresh, track_low_thresh, new_track_thresh,
-                             match_thresh, max_time_lost, tracks, tcounts, workspace, workspace_bytes, stream);
+  return tamtr_botsort_update_streams(out, counts, warps, B, 1, nq, mean, cov, meta, sc, hdr, T, track_high_thresh, track_low_thresh,
+                                      new_track_thresh, match_thresh, max_time_lost, tracks, tcounts, workspace, workspace_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------- BoT-SORT with ReID
-#define REID_MAX_D 1024
-
-extern "C" int tamtr_botsort_reid_workspace_bytes(int T, int nq) {
-  if (T < 1 || nq < 1) return 0;
-  const size_t n = trk_reid_ws_bytes(T, nq);
-  return n > 0x7fffffff ? 0 : (int)n;
+extern "C" int tamtr_botsort_reid_update_streams(const float* out, const int32_t* counts, const double* warps, const float* feat, int B,
+                                                 int S, int nq, double* mean, double* cov, int32_t* meta, float* sc, int32_t* hdr,
+                                                 float* tfeat, int D, int T, float track_high_thresh, float track_low_thresh,
+                                                 float new_track_thresh, double match_thresh, int max_time_lost, float proximity_thresh,
+                                                 double appearance_thresh, float* tracks, int32_t* tcounts, void* workspace,
+                                                 int workspace_bytes, void* stream) {
+  return trk_launch<KF_XYWH, true>(out, counts, warps, feat, B, S, nq, mean, cov, meta, sc, hdr, tfeat, D, T, track_high_thresh,
+                                   track_low_thresh, new_track_thresh, match_thresh, max_time_lost, proximity_thresh, appearance_thresh,
+                                   tracks, tcounts, workspace, workspace_bytes, stream);
 }
 
 extern "C" int tamtr_botsort_reid_update(const float* out, const int32_t* counts, const double* warps, const float* feat, int B, int nq,
@@ -815,23 +883,9 @@ extern "C" int tamtr_botsort_reid_update(const float* out, const int32_t* counts
                                          float track_high_thresh, float track_low_thresh, float new_track_thresh, double match_thresh,
                                          int max_time_lost, float proximity_thresh, double appearance_thresh, float* tracks,
                                          int32_t* tcounts, void* workspace, int workspace_bytes, void* stream) {
-  if (!out || !counts || !feat || !mean || !cov || !meta || !sc || !hdr || !tfeat || !tracks || !tcounts || !workspace || B < 1 || nq < 1 ||
-      T < 1 || D < 1)
-    return TAMTR_EINVAL;
-  if ((warps && (reinterpret_cast<uintptr_t>(warps) & 7)) || (reinterpret_cast<uintptr_t>(workspace) & 7)) return TAMTR_EINVAL;
-  if (D > REID_MAX_D || tamtr_botsort_reid_workspace_bytes(T, nq) == 0 || trk_lds_bytes(T, nq) > 64 * 1024) return TAMTR_EUNSUP;
-  if (workspace_bytes < tamtr_botsort_reid_workspace_bytes(T, nq)) return TAMTR_EINVAL;
-  TrkReidParams p;
-  static_cast<TrkParams&>(p) = TrkParams{out, counts, B, nq, T, mean, cov, meta, sc, hdr, track_high_thresh, track_low_thresh,
-                                         new_track_thresh, match_thresh, max_time_lost, tracks, tcounts,
-                                         static_cast<unsigned char*>(workspace), warps};
-  p.feat = feat;
-  p.tfeat = tfeat;
-  p.D = D;
-  p.prox = proximity_thresh;
-  p.app = appearance_thresh;
-  hipLaunchKernelGGL((bytetrack_kernel<KF_XYWH, TrkReidParams>), dim3(1), dim3(WAVE), trk_lds_bytes(T, nq), (hipStream_t)stream, p);
-  return tamtr_launch_status();
+  return tamtr_botsort_reid_update_streams(out, counts, warps, feat, B, 1, nq, mean, cov, meta, sc, hdr, tfeat, D, T, track_high_thresh,
+                                           track_low_thresh, new_track_thresh, match_thresh, max_time_lost, proximity_thresh,
+                                           appearance_thresh, tracks, tcounts, workspace, workspace_bytes, stream);
 }
 
 // reid_rows: feat[b, j, :] = the row embed[b, keep[b, j], :] widened to fp32 and normalised twice, for j < counts[b]; zero after the

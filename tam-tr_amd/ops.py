@@ -1897,43 +1897,66 @@ def detect_postprocess(y, orig_hw, conf, iou, classes=None, single_cls=False, ma
 TRACK_STATE_SPEC = (('mean', torch.float64, (8,)), ('cov', torch.float64, (8, 8)), ('meta', torch.int32, (8,)), ('sc', torch.float32, (2,)))
 
 
-def bytetrack_workspace_bytes(capacity, nq):
-    """Bytes of device workspace tamtr_bytetrack_update needs for a table of `capacity` slots and nq rows per frame (no GPU call)."""
-    n = _lib.lib().tamtr_bytetrack_workspace_bytes(int(capacity), int(nq))
+def _check_streams(what, streams):
+    """streams=None: one tracker, today's shapes.  streams=S: S stacked trackers -> S as an int."""
+    if streams is None:
+        return None
+    if isinstance(streams, bool) or not isinstance(streams, int) or streams < 1:
+        raise _lib.TamtrHipError(f'{what}: streams must be None or a positive int, got {streams!r}')
+    return streams
+
+
+def bytetrack_workspace_bytes(capacity, nq, streams=None):
+    """Bytes of device workspace tamtr_bytetrack_update needs for a table of `capacity` slots and nq rows per frame (no GPU call);
+    streams=S: what tamtr_bytetrack_update_streams needs for S stacked tables."""
+    S = _check_streams('bytetrack', streams)
+    L = _lib.lib()
+    n = L.tamtr_bytetrack_workspace_bytes(int(capacity), int(nq)) if S is None else L.tamtr_bytetrack_streams_workspace_bytes(S, int(capacity), int(nq))
     if n <= 0:
-        raise _lib.TamtrHipError(f'bytetrack: capacity {capacity} with nq {nq} is outside what the kernel is built for')
+        raise _lib.TamtrHipError(f'bytetrack: capacity {capacity} with nq {nq}' + (f' and {S} streams' if S else '') +
+                                 ' is outside what the kernel is built for')
     return n
 
 
 def bytetrack_update(out, counts, state, capacity, track_high_thresh=0.5, track_low_thresh=0.1, new_track_thresh=0.6, match_thresh=0.8,
-                     max_time_lost=30, workspace=None):
+                     max_time_lost=30, workspace=None, streams=None):
     """BYTETracker.update (trackers/byte_tracker.py:238-351) for the B frames of a batch, in order, in one launch; the rule is stated
     in csrc/track.hip.  out f32 [B, nq, 6] and counts i32 [B] are detect_postprocess's outputs on the GPU; state: the tracker's table,
     a dict of device tensors mean f64 [T, 8], cov f64 [T, 8, 8], meta i32 [T, 8], sc f32 [T, 2], hdr i32 [8] with T = capacity,
     updated in place.  Returns device tensors tracks f32 [B, nq, 8] (x1 y1 x2 y2 id score cls idx, zero after the count) and
-    tcounts i32 [B].  hdr[3] counts the new tracks that found no free slot.  Every check comes before the launch; no synchronisation."""
+    tcounts i32 [B].  hdr[3] counts the new tracks that found no free slot.  Every check comes before the launch; no synchronisation.
+    streams=S: one tracker per stream, still one launch (trackers/track.py:33-53).  The B = F * S images are frame-major, image
+    f * S + s being the f-th frame of stream s; every state tensor carries a leading S (mean [S, T, 8] ... hdr [S, 8]) and the
+    workspace is bytetrack_workspace_bytes(T, nq, S).  Stream s gets what streams=None computes on its own images and state[k][s],
+    bit for bit.  A stream without a frame at some position keeps its image, with counts 0."""
     return _tracker_update('bytetrack_update', None, out, counts, state, capacity, track_high_thresh, track_low_thresh, new_track_thresh,
-                           match_thresh, max_time_lost, workspace)
+                           match_thresh, max_time_lost, workspace, streams=streams)
 
 
 def botsort_update(out, counts, state, capacity, warps=None, track_high_thresh=0.5, track_low_thresh=0.1, new_track_thresh=0.6,
-                   match_thresh=0.8, max_time_lost=30, workspace=None):
+                   match_thresh=0.8, max_time_lost=30, workspace=None, streams=None):
     """BOTSORT.update (trackers/bot_sort.py; with_reid off, as the reference runs it) for the B frames of a batch, in order, in one
     launch: bytetrack_update's operands, table layout, workspace and outputs, with the XYWH filter and the frames' warps; the rule is
     stated in csrc/track.hip.  warps f64 [B, 2, 3] on the GPU, in the pixels of `out` (gmc_estimate's output or the caller's own);
-    None = the identity for every frame.  Every check comes before the launch; no synchronisation."""
+    None = the identity for every frame.  Every check comes before the launch; no synchronisation.  streams=S as in bytetrack_update
+    (warps stay [B, 2, 3], one per image)."""
     return _tracker_update('botsort_update', warps, out, counts, state, capacity, track_high_thresh, track_low_thresh, new_track_thresh,
-                           match_thresh, max_time_lost, workspace)
+                           match_thresh, max_time_lost, workspace, streams=streams)
 
 
 REID_MAX_D = 1024
 
 
-def botsort_reid_workspace_bytes(capacity, nq):
-    """Bytes of device workspace tamtr_botsort_reid_update needs (its cost matrix is fp64; no GPU call)."""
-    n = _lib.lib().tamtr_botsort_reid_workspace_bytes(int(capacity), int(nq))
+def botsort_reid_workspace_bytes(capacity, nq, streams=None):
+    """Bytes of device workspace tamtr_botsort_reid_update needs (its cost matrix is fp64; no GPU call); streams=S: what
+    tamtr_botsort_reid_update_streams needs for S stacked tables."""
+    S = _check_streams('botsort_reid', streams)
+    L = _lib.lib()
+    n = L.tamtr_botsort_reid_workspace_bytes(int(capacity), int(nq)) if S is None else \
+        L.tamtr_botsort_reid_streams_workspace_bytes(S, int(capacity), int(nq))
     if n <= 0:
-        raise _lib.TamtrHipError(f'botsort_reid: capacity {capacity} with nq {nq} is outside what the kernel is built for')
+        raise _lib.TamtrHipError(f'botsort_reid: capacity {capacity} with nq {nq}' + (f' and {S} streams' if S else '') +
+                                 ' is outside what the kernel is built for')
     return n
 
 
@@ -1964,12 +1987,14 @@ def reid_rows(embed, keep, counts):
 
 
 def botsort_reid_update(out, counts, feat, state, capacity, warps=None, track_high_thresh=0.5, track_low_thresh=0.1, new_track_thresh=0.6,
-                        match_thresh=0.8, max_time_lost=30, proximity_thresh=0.5, appearance_thresh=0.25, workspace=None):
+                        match_thresh=0.8, max_time_lost=30, proximity_thresh=0.5, appearance_thresh=0.25, workspace=None, streams=None):
     """BOTSORT.update with with_reid on (trackers/bot_sort.py:55-64, 166-190 with utils/matching.py:84-105) for the B frames of a
     batch, in order, in one launch: botsort_update's operands and outputs plus feat f32 [B, nq, D], one feature row per row of `out`
     (reid_rows), and state['feat'] f32 [T, D], the tracks' smooth features, updated in place; the rule is stated in csrc/track.hip.
-    The workspace is botsort_reid_workspace_bytes(T, nq).  Every check comes before the launch; no synchronisation."""
+    The workspace is botsort_reid_workspace_bytes(T, nq).  Every check comes before the launch; no synchronisation.  streams=S as in
+    bytetrack_update, with state['feat'] [S, T, D] and the workspace botsort_reid_workspace_bytes(T, nq, S)."""
     what = 'botsort_reid_update'
+    S = _check_streams(what, streams)
     if not torch.is_tensor(feat) or feat.dim() != 3 or feat.dtype != torch.float32 or out.dim() != 3 or tuple(feat.shape[:2]) != tuple(out.shape[:2]) \
             or feat.shape[2] < 1:
         got = (feat.dtype, tuple(feat.shape)) if torch.is_tensor(feat) else type(feat).__name__
@@ -1978,11 +2003,13 @@ def botsort_reid_update(out, counts, feat, state, capacity, warps=None, track_hi
     if D > REID_MAX_D:
         raise _lib.TamtrHipError(f'{what}: D = {D} is above the {REID_MAX_D} the kernel is built for')
     tf = state.get('feat') if isinstance(state, dict) else None
-    if tf is None or tf.dtype != torch.float32 or tuple(tf.shape) != (int(capacity), D) or not tf.is_contiguous():
+    want = (() if S is None else (S,)) + (int(capacity), D)
+    if tf is None or tf.dtype != torch.float32 or tuple(tf.shape) != want or not tf.is_contiguous():
         got = None if tf is None else (tf.dtype, tuple(tf.shape))
-        raise _lib.TamtrHipError(f"{what}: state['feat'] must be a contiguous float32 tensor of shape {(int(capacity), D)}, got {got}")
+        raise _lib.TamtrHipError(f"{what}: state['feat'] must be a contiguous float32 tensor of shape {want}, got {got}")
     return _tracker_update(what, warps, out, counts, state, capacity, track_high_thresh, track_low_thresh, new_track_thresh,
-                           match_thresh, max_time_lost, workspace, reid=(feat, tf, D, float(proximity_thresh), float(appearance_thresh)))
+                           match_thresh, max_time_lost, workspace, reid=(feat, tf, D, float(proximity_thresh), float(appearance_thresh)),
+                           streams=S)
 
 
 # ------------------------------------------------------------------------------------------------ camera-motion estimate (csrc/gmc.hip)
@@ -2018,12 +2045,16 @@ def gmc_levels(H, W):
     return out
 
 
-def gmc_state(H, W, device):
-    """A fresh persistent state for frames of H x W: the pyramid and keypoint slots of the last tracked frame, hdr[0] = valid."""
+def gmc_state(H, W, device, streams=None):
+    """A fresh persistent state for frames of H x W: the pyramid and keypoint slots of the last tracked frame, hdr[0] = valid.
+    streams=S: one state per stream, stacked (pyr [S, P], kp [S, 1024], hdr [S, 4])."""
     _gmc_check_hw(int(H), int(W))
+    S = _check_streams('gmc_state', streams)
+    lead = () if S is None else (S,)
     n = _lib.lib().tamtr_gmc_state_bytes(int(H), int(W))
-    return {'pyr': torch.zeros(n, device=device, dtype=torch.uint8), 'kp': torch.full((GMC_SLOTS,), -1, device=device, dtype=torch.int32),
-            'hdr': torch.zeros(4, device=device, dtype=torch.int32)}
+    return {'pyr': torch.zeros(lead + (n,), device=device, dtype=torch.uint8),
+            'kp': torch.full(lead + (GMC_SLOTS,), -1, device=device, dtype=torch.int32),
+            'hdr': torch.zeros(lead + (4,), device=device, dtype=torch.int32)}
 
 
 def gmc_workspace_views(workspace, B, H, W):
@@ -2040,13 +2071,16 @@ def gmc_workspace_views(workspace, B, H, W):
     return out
 
 
-def gmc_estimate(frames, counts, scale, state, workspace=None, stages=15):
+def gmc_estimate(frames, counts, scale, state, workspace=None, stages=15, streams=None):
     """One 2x3 camera-motion warp per frame from the frames of a batch, on the device; the rule is written out in csrc/gmc.hip (it is
     the project's own, standing where the reference runs OpenCV's sparse optical flow on the host, trackers/utils/gmc.py:247-302).
     frames u8 [B, H, W, 3] RGB on the GPU (the network input as uploaded), counts i32 [B] on the GPU, scale [B, 2] = (w0 / W, h0 / H)
     (any array-like; a host one goes up in one copy), state: gmc_state(H, W), updated in place.  Returns device tensors warps f64
     [B, 2, 3] in original pixels, ready for botsort_update, and stats i32 [B, 4] (keypoints, tracked, inliers, used).  `stages` is for
-    tests (see the header).  At most four launches; every check comes before the first; no synchronisation."""
+    tests (see the header).  At most four launches; every check comes before the first; no synchronisation.
+    streams=S: the B = F * S frames are frame-major (frame f * S + s is the f-th of stream s), state is gmc_state(H, W, streams=S),
+    and pairing and the state's update run per stream; stream s gets what streams=None computes on its own frames and state[k][s]."""
+    S = _check_streams('gmc_estimate', streams)
     if not torch.is_tensor(frames) or frames.dim() != 4 or frames.shape[-1] != 3 or frames.shape[0] < 1:
         got = tuple(frames.shape) if torch.is_tensor(frames) else type(frames).__name__
         raise _lib.TamtrHipError(f'gmc_estimate: expected frames [B, H, W, 3], got {got}')
@@ -2054,6 +2088,9 @@ def gmc_estimate(frames, counts, scale, state, workspace=None, stages=15):
         raise _lib.TamtrHipError(f'gmc_estimate: frames must be uint8 (the network input as uploaded), got {frames.dtype}')
     B, H, W, _ = frames.shape
     _gmc_check_hw(H, W)
+    if S is not None and B % S:
+        raise _lib.TamtrHipError(f'gmc_estimate: a batch of {B} frames is no multiple of streams = {S}')
+    lead = () if S is None else (S,)
     if not torch.is_tensor(counts) or tuple(counts.shape) != (B,) or counts.dtype != torch.int32:
         got = (counts.dtype, tuple(counts.shape)) if torch.is_tensor(counts) else type(counts).__name__
         raise _lib.TamtrHipError(f'gmc_estimate: counts must be an int32 tensor [B] = [{B}], got {got}')
@@ -2064,9 +2101,10 @@ def gmc_estimate(frames, counts, scale, state, workspace=None, stages=15):
     need_st = _lib.lib().tamtr_gmc_state_bytes(H, W)
     for k, dt, shape in (('pyr', torch.uint8, (need_st,)), ('kp', torch.int32, (GMC_SLOTS,)), ('hdr', torch.int32, (4,))):
         t = state.get(k) if isinstance(state, dict) else None
-        if t is None or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+        if t is None or t.dtype != dt or tuple(t.shape) != lead + shape or not t.is_contiguous():
             got = None if t is None else (t.dtype, tuple(t.shape))
-            raise _lib.TamtrHipError(f'gmc_estimate: state[{k!r}] must be a contiguous {dt} tensor of shape {shape} (gmc_state({H}, {W})), got {got}')
+            made = f'gmc_state({H}, {W})' if S is None else f'gmc_state({H}, {W}, streams={S})'
+            raise _lib.TamtrHipError(f'gmc_estimate: state[{k!r}] must be a contiguous {dt} tensor of shape {lead + shape} ({made}), got {got}')
     if int(stages) < 1 or int(stages) > 15:
         raise _lib.TamtrHipError(f'gmc_estimate: stages must be a mask in 1 .. 15, got {stages}')
     require_gpu(frames, counts, state['pyr'], state['kp'], state['hdr'])
@@ -2081,18 +2119,23 @@ def gmc_estimate(frames, counts, scale, state, workspace=None, stages=15):
     frames, counts, scale = _c(frames), _c(counts), _c(scale)
     warps = torch.empty(B, 2, 3, device=frames.device, dtype=torch.float64)
     stats = torch.empty(B, 4, device=frames.device, dtype=torch.int32)
-    call('tamtr_gmc_estimate', ptr(frames), ptr(counts), ptr(scale), B, H, W, ptr(state['pyr']), ptr(state['kp']), ptr(state['hdr']),
-         ptr(warps), ptr(stats), ptr(workspace), workspace.numel(), int(stages), stream_ptr())
+    call('tamtr_gmc_estimate_streams', ptr(frames), ptr(counts), ptr(scale), B, S or 1, H, W, ptr(state['pyr']), ptr(state['kp']),
+         ptr(state['hdr']), ptr(warps), ptr(stats), ptr(workspace), workspace.numel(), int(stages), stream_ptr())
     return warps, stats
 
 
 def _tracker_update(what, warps, out, counts, state, capacity, track_high_thresh, track_low_thresh, new_track_thresh, match_thresh,
-                    max_time_lost, workspace, reid=None):
+                    max_time_lost, workspace, reid=None, streams=None):
+    """The one place the tracker kernel is launched from: tamtr_<what>_streams, of which the single-tracker entry is S = 1."""
+    S = _check_streams(what, streams)
     if out.dim() != 3 or out.shape[-1] != 6 or out.shape[0] < 1 or out.shape[1] < 1:
         raise _lib.TamtrHipError(f'{what}: expected out [B, nq, 6], got {tuple(out.shape)}')
     B, nq, _ = out.shape
     if tuple(counts.shape) != (B,):
         raise _lib.TamtrHipError(f'{what}: counts must be [B] = [{B}], got {tuple(counts.shape)}')
+    if S is not None and B % S:
+        raise _lib.TamtrHipError(f'{what}: a batch of {B} images is no multiple of streams = {S} (frame-major: image f * S + s)')
+    lead = () if S is None else (S,)
     if out.dtype != torch.float32 or counts.dtype != torch.int32:
         raise _lib.TamtrHipError(f'{what}: out must be float32 and counts int32, got {out.dtype} and {counts.dtype}')
     T = int(capacity)
@@ -2100,16 +2143,17 @@ def _tracker_update(what, warps, out, counts, state, capacity, track_high_thresh
         raise _lib.TamtrHipError(f'{what}: capacity must be positive, got {capacity}')
     for k, dt, tail in TRACK_STATE_SPEC + (('hdr', torch.int32, None),):
         t = state.get(k) if isinstance(state, dict) else None
-        want = (8,) if tail is None else (T,) + tail
+        want = lead + ((8,) if tail is None else (T,) + tail)
         if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
             got = None if t is None else (t.dtype, tuple(t.shape))
-            raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want} (capacity {T}), got {got}')
+            cap = f'capacity {T}' if S is None else f'capacity {T}, streams {S}'
+            raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want} ({cap}), got {got}')
     if warps is not None and (not torch.is_tensor(warps) or tuple(warps.shape) != (B, 2, 3) or warps.dtype != torch.float64):
         got = (warps.dtype, tuple(warps.shape)) if torch.is_tensor(warps) else type(warps).__name__
         raise _lib.TamtrHipError(f'{what}: warps must be a float64 tensor [B, 2, 3] = [{B}, 2, 3], got {got}')
     require_gpu(out, counts, warps, *(state[k] for k in ('mean', 'cov', 'meta', 'sc', 'hdr')), *(reid[:2] if reid else ()))
     warps = _c(warps) if warps is not None else None
-    need = botsort_reid_workspace_bytes(T, nq) if reid else bytetrack_workspace_bytes(T, nq)
+    need = botsort_reid_workspace_bytes(T, nq, S) if reid else bytetrack_workspace_bytes(T, nq, S)
     if workspace is None:
         workspace = torch.empty(need, device=out.device, dtype=torch.uint8)
     require_gpu(workspace)
@@ -2120,13 +2164,13 @@ def _tracker_update(what, warps, out, counts, state, capacity, track_high_thresh
     tcounts = torch.empty(B, device=out.device, dtype=torch.int32)
     if reid:
         feat, tf, D, prox, app = reid
-        call('tamtr_' + what, ptr(out), ptr(counts), ptr(warps) if warps is not None else None, ptr(_c(feat)), B, nq, ptr(state['mean']),
+        call(f'tamtr_{what}_streams', ptr(out), ptr(counts), ptr(warps) if warps is not None else None, ptr(_c(feat)), B, S or 1, nq, ptr(state['mean']),
              ptr(state['cov']), ptr(state['meta']), ptr(state['sc']), ptr(state['hdr']), ptr(tf), D, T, float(track_high_thresh),
              float(track_low_thresh), float(new_track_thresh), float(match_thresh), int(max_time_lost), prox, app, ptr(tracks), ptr(tcounts),
              ptr(workspace), int(workspace.numel()), stream_ptr())
         return tracks, tcounts
     args = (ptr(out), ptr(counts)) + ((ptr(warps) if warps is not None else None,) if what == 'botsort_update' else ())
-    call('tamtr_' + what, *args, B, nq, ptr(state['mean']), ptr(state['cov']), ptr(state['meta']), ptr(state['sc']),
+    call(f'tamtr_{what}_streams', *args, B, S or 1, nq, ptr(state['mean']), ptr(state['cov']), ptr(state['meta']), ptr(state['sc']),
          ptr(state['hdr']), T, float(track_high_thresh), float(track_low_thresh), float(new_track_thresh), float(match_thresh),
          int(max_time_lost), ptr(tracks), ptr(tcounts), ptr(workspace), int(workspace.numel()), stream_ptr())
     return tracks, tcounts

@@ -67,6 +67,26 @@ def load_image(path, imgsz):
     return im, letterbox_scalefill(im, imgsz)
 
 
+def stream_batches(files_per_stream, frames_per_stream=1):
+    """The batches of Predictor.track_streams: S file lists (one sequence each) -> [(paths [F * S], active [F * S])] with
+    F = frames_per_stream, frame-major: entry f * S + s of batch k is frame k * F + f of stream s.  A stream that has no such frame
+    (it ended, or it is empty) keeps its entry: active is False there and the path is the batch's first active one, an image that is
+    loaded anyway (padding; its result is dropped).  Batches run until the longest stream ends.  Pure: touches no file."""
+    files = [list(f) for f in files_per_stream]
+    S, F = len(files), int(frames_per_stream)
+    if S < 1:
+        raise ValueError('track_streams needs at least one source')
+    if F < 1:
+        raise ValueError(f'frames_per_stream must be positive, got {frames_per_stream!r}')
+    batches = []
+    for k in range(0, max(len(f) for f in files), F):
+        at = [(k + i // S, i % S) for i in range(F * S)]
+        active = [n < len(files[s]) for n, s in at]
+        pad = next(files[s][n] for (n, s), a in zip(at, active) if a)
+        batches.append(([files[s][n] if a else pad for (n, s), a in zip(at, active)], active))
+    return batches
+
+
 def to_model_input(ims_u8, device, keep_u8=False):
     """u8 [B, S, S, 3] host batch -> f32 [B, 3, S, S] / 255 on the device (engine/predictor.py:111-129: RGB, CHW, float, / 255).
     keep_u8: -> (that, the u8 batch as it was uploaded), which BoT-SORT's camera-motion estimate reads."""
@@ -187,13 +207,15 @@ class Predictor:
         self.last_img = self.last_y = None
 
     @torch.no_grad()
-    def run_batch(self, ims, tracker=None, gt_frames=None, evaluator=None):
+    def run_batch(self, ims, tracker=None, gt_frames=None, evaluator=None, active=None):
         """Network inputs u8 [B, S, S, 3] (host) + original (h, w) per image -> host (out [B, nq, 6], keep [B, nq], counts [B]).
         With a tracker (track.ByteTracker or track.BotSort) the batch's frames also go through one tracker launch, and its rows ride in the same copy:
         -> host (out, keep, counts, tracks [B, nq, 8], tcounts [B]).  With gt_frames (B host arrays [m, 7]) and an evaluator
         (track.MotEvaluator, track.HotaEvaluator or track.TrackMapEvaluator, or a list of them) as well, one more launch per evaluator
         scores the tracker's rows where they lie; each evaluator's header rides in the same copy and its time goes under its own key
-        of times ('mot', 'hota', 'tmap')."""
+        of times ('mot', 'hota', 'tmap').
+        active (track_streams; B host booleans): the images that are padding have their counts set to 0 on the device before the
+        estimator and the tracker see them - such an image reaches neither."""
         arr, hw = ims
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
         ev[0].record()
@@ -207,6 +229,8 @@ class Predictor:
         ev[2].record()
         out, keep, counts = ops.detect_postprocess(y, hw, self.conf, self.iou, self.classes, self.single_cls)
         ev[3].record()
+        if active is not None:      # the counts mask
+            counts = counts * torch.as_tensor(active, dtype=torch.int32).to(self.device, non_blocking=True)
         # one device-to-host copy for all the outputs
         B, nq = keep.shape
         parts = [out.view(-1), keep.view(torch.float32).view(-1), counts.view(torch.float32)]
@@ -223,7 +247,7 @@ class Predictor:
                 tracks, tcounts = tracker.update(out, counts, warps=warps, **self._reid_operands(reid, keep))
             else:
                 tracks, tcounts = tracker.update(out, counts, **self._reid_operands(reid, keep))
-            parts += [tracks.view(-1), tcounts.view(torch.float32), tracker.state['hdr'].view(torch.float32)]
+            parts += [tracks.view(-1), tcounts.view(torch.float32), tracker.state['hdr'].view(torch.float32).view(-1)]
             for e in evaluators if scoring else []:
                 ev_eval.append(torch.cuda.Event(enable_timing=True))
                 ev_eval[-1].record()
@@ -247,8 +271,9 @@ class Predictor:
         res = o.view(B, nq, 6), kp.view(torch.int32).view(B, nq), c.view(torch.int32)
         if tracker is None:
             return res
-        tr, tc, hdr, *ehdr = rest.split([B * nq * 8, B, 8] + [e.state['hdr'].numel() for e in evaluators if scoring])
-        tracker.check_overflow(hdr.view(torch.int32)[3])
+        n_hdr = tracker.state['hdr'].numel()      # 8 words, per stream of a stacked tracker
+        tr, tc, hdr, *ehdr = rest.split([B * nq * 8, B, n_hdr] + [e.state['hdr'].numel() for e in evaluators if scoring])
+        tracker.check_overflow(hdr.view(torch.int32).view(-1, 8)[:, 3])
         for e, h in zip(evaluators, ehdr):
             e.check_overflow(h.view(torch.int32))
         return res + (tr.view(B, nq, 8), tc.view(torch.int32))
@@ -296,6 +321,64 @@ class Predictor:
             yield from self._with_query_embed(self._track(files, gt, evaluator))
         else:
             yield from self._track(files, gt, evaluator)
+
+    def track_streams(self, sources, tracker=None, frames_per_stream=1, persist=False):
+        """S sequences at once, one tracker per sequence (the reference's model.track on a batch of streams, trackers/track.py:33-53):
+        `sources` is a list of S sources - each a directory, a list file or a list of paths, each a sequence of its own.  Every
+        batch holds `frames_per_stream` frames of every stream, frame-major (stream_batches), and gets one forward, one
+        detect_postprocess, the counts mask, at most four estimator launches, one tracker launch (one workgroup per stream) and one
+        device-to-host copy.  Yields (stream_index, Detections) as track() yields Detections, in frame order within a stream, until
+        the longest stream ends; a stream that has ended keeps its place in the batch as padding, which reaches neither the tracker
+        nor the estimator and is never yielded.  tracker: a yaml path, None for ByteTrack's defaults, or a track.ByteTracker /
+        track.BotSort built with streams=len(sources) (any other `streams` raises ValueError); persist as in track().  BoT-SORT's
+        camera-motion estimate and ReID work as in track(), per stream.  Evaluators are not taken here: each of them holds one
+        sequence's state (score the files of write_mot with tools/mot_eval.py).  The arguments are checked when this is called,
+        before the first frame is asked for."""
+        from .track import ByteTracker, tracker_from_yaml
+        sources = list(sources) if isinstance(sources, (list, tuple)) else None
+        if not sources:
+            raise ValueError('track_streams needs a non-empty list of sources, one per stream')
+        S = len(sources)
+        if isinstance(tracker, ByteTracker):
+            if tracker.streams != S:
+                raise ValueError(f'the tracker was built with streams={tracker.streams!r}, {S} sources need streams={S}')
+            self.tracker = tracker
+            if not persist:
+                tracker.reset()
+        elif not (persist and isinstance(self.tracker, ByteTracker) and self.tracker.streams == S):
+            head = self.model.model[-1]
+            self.tracker = tracker_from_yaml(tracker, self.device, reid_dim=head.hidden_dim, streams=S) if tracker else ByteTracker(self.device, streams=S)
+        batches = stream_batches([list_sources(src) for src in sources], frames_per_stream)
+        for k in ('mot', 'hota', 'tmap') + (('gmc',) if getattr(self.tracker, 'gmc_method', None) != 'sparseOptFlow' else ()):
+            self.times.pop(k, None)
+        frames = self._run_streams(batches, S)
+        return self._with_query_embed(frames) if getattr(self.tracker, 'with_reid', False) else frames
+
+    def _run_streams(self, batches, S):
+        with ThreadPoolExecutor(max_workers=self.workers) as pool:
+            def submit(paths):      # a padding entry shares its path's load
+                jobs = {f: pool.submit(load_image, f, self.imgsz) for f in dict.fromkeys(paths)}
+                return [jobs[f] for f in paths]
+            pending = submit(batches[0][0]) if batches else []
+            for k, (paths, active) in enumerate(batches):
+                t0 = time.perf_counter()
+                loaded = [f.result() for f in pending]
+                self.times['load'] += (time.perf_counter() - t0) * 1e3
+                pending = submit(batches[k + 1][0]) if k + 1 < len(batches) else []
+                origs = [o for o, _ in loaded]
+                hw = [o.shape[:2] for o in origs]
+                res = self.run_batch((np.stack([r for _, r in loaded]), hw), self.tracker, active=active)
+                out, counts = res[0], res[2]
+                self.seen += sum(active)
+                for i, path in enumerate(paths):
+                    if not active[i]:
+                        continue
+                    n, nt = int(counts[i]), int(res[4][i])
+                    if nt:
+                        rows = res[3][i, :nt]
+                        yield i % S, Detections(path, hw[i], self.names, rows[:, [0, 1, 2, 3, 5, 6]].clone(), orig_img=origs[i], id=rows[:, 4].long())
+                    else:
+                        yield i % S, Detections(path, hw[i], self.names, out[i, :n].clone(), orig_img=origs[i])
 
     def _with_query_embed(self, frames):
         head = self.model.model[-1]

@@ -23,6 +23,15 @@ encoder for it): every detection comes with a D-vector, either gathered from a p
     tracks, tcounts = tracker.update(out, counts, frames=u8, scale=s, embed=e, keep=keep)   # e f32 | bf16 [B, nqm, D]
     tracks, tcounts = tracker.update(out, counts, feats=f)                                   # f f32 [B, nq, D], rows aligned with out
 
+Several streams at once (the reference keeps one tracker per image of the batch, trackers/track.py:33-53): streams=S stacks S
+trackers' tables and still takes one launch per batch, one workgroup per stream.  A batch then holds F frames of every stream,
+frame-major (image f * S + s is the f-th frame of stream s); a stream without a frame at some position keeps its image with
+counts 0.  `Predictor.track_streams(sources)` drives it.
+
+    tracker = ByteTracker(device, streams=4)            # BotSort(device, streams=4), tracker_from_yaml(path, device, streams=4)
+    tracks, tcounts = tracker.update(out, counts)       # out [F * 4, nq, 6]
+    tracker.reset(stream=2)                             # stream 2 starts over; the others are untouched
+
 MOT evaluation next to it (CLEAR-MOT and identity metrics; the rule is written out in csrc/mot.hip, engine.mot_evaluate states it in
 numpy): one more launch per batch on the rows the tracker left on the device, one launch per sequence for the reduction.
 
@@ -74,12 +83,22 @@ def read_tracker_yaml(path):
     return {k: cfg[k] for k in YAML_KEYS if k in cfg}
 
 
+def check_streams(streams):
+    """streams=None (one tracker) or a positive int -> itself; anything else raises ValueError.  Touches no device."""
+    if streams is not None and (isinstance(streams, bool) or not isinstance(streams, int) or streams < 1):
+        raise ValueError(f'streams must be None (one tracker) or a positive int (one tracker per stream), got {streams!r}')
+    return streams
+
+
 class ByteTracker:
     """One tracker = one slot table of `capacity` tracks on `device` (ids start at 1).  nq is the number of rows per frame the
-    workspace is sized for; a batch with more rows gets a larger workspace on its first use."""
+    workspace is sized for; a batch with more rows gets a larger workspace on its first use.
+    streams=S: S trackers, one per stream, in one stacked table (every state tensor gains a leading S) and one launch; update()
+    then takes the frame-major batch (image f * S + s is the f-th frame of stream s) and every stream's ids start at 1."""
 
     def __init__(self, device, track_high_thresh=0.5, track_low_thresh=0.1, new_track_thresh=0.6, track_buffer=30, match_thresh=0.8,
-                 frame_rate=30, capacity=1024, nq=300):
+                 frame_rate=30, capacity=1024, nq=300, streams=None):
+        self.streams = check_streams(streams)
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise ops._lib.TamtrHipError('ByteTracker needs an MI355X; there is no CPU path')
@@ -90,9 +109,9 @@ class ByteTracker:
         self.capacity, self.nq = int(capacity), int(nq)
         if self.capacity < 1 or self.nq < 1:
             raise ValueError(f'capacity and nq must be positive, got {capacity} and {nq}')
-        self.workspace = torch.empty(ops.bytetrack_workspace_bytes(self.capacity, self.nq), device=self.device, dtype=torch.uint8)
-        self.state = {k: torch.zeros((self.capacity,) + tail, device=self.device, dtype=dt) for k, dt, tail in ops.TRACK_STATE_SPEC}
-        self.state['hdr'] = torch.zeros(8, device=self.device, dtype=torch.int32)
+        self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
+        self.state = {k: torch.zeros(self._lead + (self.capacity,) + tail, device=self.device, dtype=dt) for k, dt, tail in ops.TRACK_STATE_SPEC}
+        self.state['hdr'] = torch.zeros(self._lead + (8,), device=self.device, dtype=torch.int32)
         self._fresh_hdr = torch.tensor([0, 1, 0, 0, 0, 0, 0, 0], dtype=torch.int32).to(self.device)
         self.reset()
 
@@ -100,26 +119,59 @@ class ByteTracker:
     def from_yaml(cls, path, device, **kw):
         return cls(device, **{**read_tracker_yaml(path), **kw})
 
-    def reset(self):
-        """Forget every track; the next id is 1 again.  No synchronisation."""
-        self.state['meta'].zero_()
-        self.state['hdr'].copy_(self._fresh_hdr)
+    @property
+    def _lead(self):
+        """The leading dimension of every state tensor: none for one tracker, (S,) for a stack."""
+        return () if self.streams is None else (self.streams,)
+
+    def _stream(self, stream):
+        if self.streams is None or isinstance(stream, bool) or not isinstance(stream, int) or not 0 <= stream < self.streams:
+            raise ValueError(f'stream must be in 0 .. {self.streams - 1}, got {stream!r}' if self.streams else
+                             f'stream={stream!r} was given to a tracker built without streams')
+        return stream
+
+    def reset(self, stream=None):
+        """Forget every track; the next id is 1 again.  stream=s: of that stream's tracker alone.  No synchronisation."""
+        if stream is None:
+            self.state['meta'].zero_()
+            self.state['hdr'].copy_(self._fresh_hdr)
+        else:
+            s = self._stream(stream)
+            self.state['meta'][s].zero_()
+            self.state['hdr'][s].copy_(self._fresh_hdr)
+
+    def _ws_bytes(self):
+        return ops.bytetrack_workspace_bytes(self.capacity, self.nq, *self._lead)
 
     def _grow(self, out):
         """A batch with more rows per frame than the workspace was sized for gets a larger workspace."""
         if out.dim() == 3 and out.shape[1] > self.nq:
             self.nq = out.shape[1]
-            self.workspace = torch.empty(ops.bytetrack_workspace_bytes(self.capacity, self.nq), device=self.device, dtype=torch.uint8)
+            self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
+
+    def stream_state(self, s):
+        """Stream s's table as views state[k][s]: contiguous, so the single-tracker ops take them as they are."""
+        s = self._stream(s)
+        return {k: v[s] for k, v in self.state.items()}
 
     def update(self, out, counts):
         """out f32 [B, nq, 6], counts i32 [B] on the device (ops.detect_postprocess) -> tracks f32 [B, nq, 8] (x1 y1 x2 y2 id score
-        cls idx, zero after the count), tcounts i32 [B], on the device.  The B frames are consumed in order in one launch."""
+        cls idx, zero after the count), tcounts i32 [B], on the device.  The B frames are consumed in order in one launch; with
+        streams=S they are F frames of each stream, frame-major, and every stream's are consumed in order by its own tracker."""
         self._grow(out)
         return ops.bytetrack_update(out, counts, self.state, self.capacity, self.track_high_thresh, self.track_low_thresh,
-                                    self.new_track_thresh, self.match_thresh, self.max_time_lost, self.workspace)
+                                    self.new_track_thresh, self.match_thresh, self.max_time_lost, self.workspace, streams=self.streams)
 
     def check_overflow(self, overflow):
-        """Raise when the header's overflow count (read by the caller, e.g. from the predictor's packed copy) is not zero."""
+        """Raise when the header's overflow count (read by the caller, e.g. from the predictor's packed copy) is not zero.  With
+        streams=S it is the column hdr[:, 3], and the message names the streams that overflowed."""
+        if self.streams is not None:
+            over = np.asarray(overflow).reshape(-1).astype(np.int64)
+            if over.any():
+                which = ', '.join(f'stream {i}: {n}' for i, n in enumerate(over.tolist()) if n)
+                raise TrackerOverflow(f'new tracks found no free slot ({which}): each stream\'s table holds {self.capacity} tracks; '
+                                      'build the tracker with a larger capacity')
+            return
         if int(overflow):
             raise TrackerOverflow(f'{int(overflow)} new tracks found no free slot: the table holds {self.capacity} tracks; '
                                   'build the tracker with a larger capacity')
@@ -135,7 +187,7 @@ class ByteTracker:
             if a.shape != tuple(v.shape):
                 raise ValueError(f'state {k!r} has shape {a.shape}, this tracker (capacity {self.capacity}) needs {tuple(v.shape)}')
             v.copy_(torch.from_numpy(np.ascontiguousarray(a)).to(v.dtype))
-        self.check_overflow(np.asarray(sd['hdr'])[HDR_OVERFLOW])
+        self.check_overflow(np.asarray(sd['hdr'])[..., HDR_OVERFLOW])
 
 
 BOTSORT_YAML_KEYS = YAML_KEYS + ('gmc_method', 'proximity_thresh', 'appearance_thresh', 'with_reid')
@@ -163,7 +215,8 @@ class BotSort(ByteTracker):
     nothing here has been measured with trained weights.  A feature row of zero norm is outside the contract."""
 
     def __init__(self, device, gmc_method='sparseOptFlow', proximity_thresh=0.5, appearance_thresh=0.25, with_reid=False, reid_dim=None,
-                 **kw):
+                 streams=None, **kw):
+        self.streams = check_streams(streams)
         method = 'none' if gmc_method is None else str(gmc_method)
         if method not in GMC_BUILT:
             raise ValueError(f"gmc_method {gmc_method!r} is not built: 'sparseOptFlow' (estimated on the device) and 'none' are; the "
@@ -180,39 +233,34 @@ class BotSort(ByteTracker):
         self.proximity_thresh, self.appearance_thresh = float(proximity_thresh), float(appearance_thresh)
         self.last_warps = self.last_stats = None
         self.gmc, self.gmc_hw, self.gmc_workspace = None, None, None      # the estimator's state, made for the first frames' size
-        super().__init__(device, **kw)
+        super().__init__(device, **kw, **({} if streams is None else {'streams': streams}))
         if self.with_reid:
-            self.state['feat'] = torch.zeros(self.capacity, self.reid_dim, device=self.device, dtype=torch.float32)
-            self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
+            self.state['feat'] = torch.zeros(self._lead + (self.capacity, self.reid_dim), device=self.device, dtype=torch.float32)
 
     def _ws_bytes(self):
-        return (ops.botsort_reid_workspace_bytes if self.with_reid else ops.bytetrack_workspace_bytes)(self.capacity, self.nq)
+        return (ops.botsort_reid_workspace_bytes if self.with_reid else ops.bytetrack_workspace_bytes)(self.capacity, self.nq, *self._lead)
 
-    def _grow(self, out):
-        if out.dim() == 3 and out.shape[1] > self.nq:
-            self.nq = out.shape[1]
-            self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
-
-    def reset(self):
-        """Forget every track and the estimator's previous frame.  state['feat'] is left as it is: a slot's row is read only while
-        the slot holds a track, and a new track overwrites it.  No synchronisation."""
-        super().reset()
+    def reset(self, stream=None):
+        """Forget every track and the estimator's previous frame (stream=s: that stream's alone).  state['feat'] is left as it is: a
+        slot's row is read only while the slot holds a track, and a new track overwrites it.  No synchronisation."""
+        super().reset(stream)
         if self.gmc is not None:
-            self.gmc['hdr'].zero_()
+            (self.gmc['hdr'] if stream is None else self.gmc['hdr'][stream]).zero_()
 
     def estimate_warps(self, frames, counts, scale=None):
         """frames u8 [B, H, W, 3] on the device (the network input as uploaded), counts i32 [B], scale [B, 2] = (w0 / W, h0 / H) or
         None for ones -> warps f64 [B, 2, 3] on the device (ops.gmc_estimate); last_stats keeps i32 [B, 4] (keypoints, tracked,
-        inliers, used).  Frames of another size than the last start a new sequence for the estimator."""
+        inliers, used).  Frames of another size than the last start a new sequence for the estimator (with streams=S: for every
+        stream's, and pairing runs per stream over the frame-major batch)."""
         B, H, W = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
         if self.gmc_hw != (H, W):
-            self.gmc, self.gmc_hw = ops.gmc_state(H, W, self.device), (H, W)
+            self.gmc, self.gmc_hw = ops.gmc_state(H, W, self.device, self.streams), (H, W)
         need = ops.gmc_workspace_bytes(B, H, W)
         if self.gmc_workspace is None or self.gmc_workspace.numel() < need:
             self.gmc_workspace = torch.empty(need, device=self.device, dtype=torch.uint8)
         if scale is None:
             scale = np.ones((B, 2))
-        warps, self.last_stats = ops.gmc_estimate(frames, counts, scale, self.gmc, self.gmc_workspace)
+        warps, self.last_stats = ops.gmc_estimate(frames, counts, scale, self.gmc, self.gmc_workspace, streams=self.streams)
         return warps
 
     def update(self, out, counts, frames=None, scale=None, warps=None, embed=None, keep=None, feats=None):
@@ -248,9 +296,9 @@ class BotSort(ByteTracker):
             feat = ops.reid_rows(embed, keep, counts)
             return ops.botsort_reid_update(out, counts, feat, self.state, self.capacity, warps, self.track_high_thresh, self.track_low_thresh,
                                            self.new_track_thresh, self.match_thresh, self.max_time_lost, self.proximity_thresh,
-                                           self.appearance_thresh, self.workspace)
+                                           self.appearance_thresh, self.workspace, streams=self.streams)
         return ops.botsort_update(out, counts, self.state, self.capacity, warps, self.track_high_thresh, self.track_low_thresh,
-                                  self.new_track_thresh, self.match_thresh, self.max_time_lost, self.workspace)
+                                  self.new_track_thresh, self.match_thresh, self.max_time_lost, self.workspace, streams=self.streams)
 
     def state_dict(self):
         """ByteTracker's table (with ReID on it includes feat f32 [capacity, D]) plus the estimator's state (gmc_pyr, gmc_kp, gmc_hdr,
@@ -269,7 +317,7 @@ class BotSort(ByteTracker):
         self.gmc, self.gmc_hw = None, None
         if 'gmc_hw' in sd:
             H, W = (int(v) for v in np.asarray(sd['gmc_hw']))
-            self.gmc, self.gmc_hw = ops.gmc_state(H, W, self.device), (H, W)
+            self.gmc, self.gmc_hw = ops.gmc_state(H, W, self.device, self.streams), (H, W)
             for k, v in self.gmc.items():
                 a = np.asarray(sd['gmc_' + k])
                 if a.shape != tuple(v.shape):
@@ -279,8 +327,10 @@ class BotSort(ByteTracker):
 
 def tracker_from_yaml(path, device, **kw):
     """A tracker yaml with the reference's keys (cfg/trackers/bytetrack.yaml or botsort.yaml) -> ByteTracker or BotSort, by its
-    `tracker_type`; keyword arguments override the file (e.g. gmc_method='none', with_reid=True, reid_dim=256)."""
+    `tracker_type`; keyword arguments override the file (e.g. gmc_method='none', with_reid=True, reid_dim=256) or go to the
+    constructor as they are (streams=S: one tracker per stream)."""
     import yaml
+    check_streams(kw.get('streams'))
     with open(path) as f:
         cfg = yaml.safe_load(f) or {}
     kind = cfg.get('tracker_type', 'bytetrack')

@@ -13,6 +13,9 @@
       is numpy with scipy's assignment, NOT the reference's tracker with `lap`.  With --botsort as well: the same scene seen by a
       panning camera (tests/botsort_np.camera_path), the camera's warps on the device, one tamtr_botsort_update launch per batch
       against the twin tests/botsort_np.py.
+  (c*) --track --streams S [--botsort]: the scenes of (c) in S copies with different seeds, tracked by ONE stacked launch per batch
+      (one workgroup per stream, tamtr_*_update_streams) next to S single-tracker launches in sequence; ms per launch, and the two
+      paths' tables compared bit for bit.
   (c') --gmc: BoT-SORT with its camera-motion estimate on a seeded 640 x 640 sequence (tests/gmc_np.make_frames, 8 frames, batches of
       4, 60 boxes that sit in the scene): the estimate's launches (csrc/gmc.hip) and the tracker launch that reads their warps, device
       events around each, median and 10th / 90th percentile over repeated passes after a warm-up pass, per frame; against a host path
@@ -29,7 +32,7 @@
       HOTA update launch, the six end-of-sequence launches, the run's accumulation, and the host path (the batches' copies plus
       engine.track_map_evaluate).
 
-    python tools/predict_bench.py [--images 64] [--kernel-only] [--track [--botsort [--reid]]] [--gmc] [--mot] [--hota] [--track-map]
+    python tools/predict_bench.py [--images 64] [--kernel-only] [--track [--botsort [--reid]] [--streams S]] [--gmc] [--mot] [--hota] [--track-map]
 --kernel-only runs only the kernel loop of (a), for a `rocprofv3 --kernel-trace --stats` run of its own.
 """
 import argparse
@@ -205,6 +208,74 @@ def bench_track(n_obj, frames=240, B=4, nq=300, capacity=1024, botsort=False):
             'detections_per_frame': round(float(np.mean([len(f) for f in scene])), 1), 'track_rows': rows, 'ids': int(sd['hdr'][1]) - 1,
             'device_launch_ms_per_frame': round(t_dev / frames, 4), 'host_copy_plus_numpy_twin_ms_per_frame': round(t_host / frames, 3),
             'device_passes_timed': n_dev}
+
+
+def bench_track_streams(n_obj, S, frames=240, F=4, nq=300, capacity=1024, botsort=False, rounds=7):
+    """-> one row: ms per launch of ONE stacked launch for S streams (tamtr_*_update_streams, F frames of every stream, one workgroup
+    per stream) next to the S single-tracker launches that track the same streams one after another, on bench_track's scene in S
+    copies with different seeds.  Both are whole passes over the sequence between device events, taken in turn `rounds` times after a
+    warm-up pass of each: median and 10th / 90th percentile.  The two paths must leave the same tables, bit for bit."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'tests'))
+    import bytetrack_np as T
+    import botsort_np as BS
+    from tamtr_amd.track import BotSort, ByteTracker
+    out = np.zeros((frames, S, nq, 6), np.float32)
+    cnt = np.zeros((frames, S), np.int32)
+    warps = np.zeros((frames, S, 2, 3))
+    for s in range(S):
+        scene = T.make_scene(1 + s, n_obj=n_obj, frames=frames, fp_every=3, gaps=[(o, 20 + 7 * o, 5 + 10 * (o % 4)) for o in range(min(n_obj, 8))])
+        if botsort:
+            warps[:, s] = BS.camera_path(1 + s, frames, jumps={frames // 2: (40.0, 25.0)})
+            scene = BS.through_camera(scene, warps[:, s])
+        for i, f in enumerate(scene):
+            out[i, s, :len(f)] = f
+            cnt[i, s] = len(f)
+    out_d, cnt_d, warps_d = torch.from_numpy(out).cuda(), torch.from_numpy(cnt).cuda(), torch.from_numpy(warps).cuda()
+    # frame-major batches for the stack; one contiguous sequence per stream for the single trackers
+    so, sc, sw = (t.transpose(0, 1).contiguous() for t in (out_d, cnt_d, warps_d))
+    kind = BotSort if botsort else ByteTracker
+    kw = {'gmc_method': 'none'} if botsort else {}
+    stack = kind('cuda', capacity=capacity, nq=nq, streams=S, **kw)
+    singles = [kind('cuda', capacity=capacity, nq=nq, **kw) for _ in range(S)]
+
+    def upd(trk, o, c, w):
+        return trk.update(o, c, warps=w) if botsort else trk.update(o, c)
+
+    def stacked_pass():
+        stack.reset()
+        for i in range(0, frames, F):
+            upd(stack, out_d[i:i + F].flatten(0, 1), cnt_d[i:i + F].flatten(0, 1), warps_d[i:i + F].flatten(0, 1))
+
+    def sequential_pass():
+        for t in singles:
+            t.reset()
+        for i in range(0, frames, F):
+            for s, t in enumerate(singles):
+                upd(t, so[s, i:i + F], sc[s, i:i + F], sw[s, i:i + F])
+
+    def one(fn):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1)
+
+    one(stacked_pass), one(sequential_pass)
+    t_stack, t_seq = [], []
+    for _ in range(rounds):
+        t_stack.append(one(stacked_pass))
+        t_seq.append(one(sequential_pass))
+    sd = stack.state_dict()
+    stack.check_overflow(sd['hdr'][:, 3])
+    same = all(np.array_equal(sd[k][s], v) for s, t in enumerate(singles) for k, v in t.state_dict().items())
+    assert same, 'the stacked launch and the single-tracker launches left different tables'
+    n = -(-frames // F)
+    pct = lambda v: [round(float(x) / n, 4) for x in np.percentile(v, [50, 10, 90])]   # noqa: E731
+    return {'tracker': 'botsort' if botsort else 'bytetrack', 'objects': n_obj, 'streams': S, 'frames_per_stream_per_launch': F, 'frames': frames,
+            'nq': nq, 'capacity': capacity, 'ids_per_stream': (sd['hdr'][:, 1] - 1).tolist(), 'same_tables_bit_for_bit': same,
+            'stacked_launch_ms_p50_p10_p90': pct(t_stack), 'sequential_single_launches_ms_p50_p10_p90': pct(t_seq),
+            'stacked_ms_per_stream_frame': round(float(np.median(t_stack)) / (frames * S), 4), 'rounds': rounds}
 
 
 def bench_track_reid(n_obj, frames=240, B=4, nq=300, capacity=1024, dim=256, rounds=3):
@@ -584,6 +655,8 @@ def main():
     ap.add_argument('--kernel-only', action='store_true')
     ap.add_argument('--track', action='store_true', help='only (c): the tracker launch against copy + numpy twin')
     ap.add_argument('--botsort', action='store_true', help='with --track: the BoT-SORT form of the launch, with warps on the device')
+    ap.add_argument('--streams', type=int, help='with --track [--botsort]: S streams in one stacked launch (one workgroup per stream) next to S '
+                    'single-tracker launches in sequence, on S copies of the scenes with different seeds')
     ap.add_argument('--reid', action='store_true', help='with --track --botsort: the ReID launch and the feature gather next to the plain BoT-SORT '
                     'launch on the same scene, D = 256')
     ap.add_argument('--gmc', action='store_true', help="only (c'): BoT-SORT's camera-motion estimate and tracker launch on a 640 x 640 sequence")
@@ -595,6 +668,14 @@ def main():
     import tamtr_amd  # noqa: F401
     assert torch.cuda.is_available(), 'predict_bench needs an MI355X'
     print(torch.cuda.get_device_name(0), 'torch', torch.__version__)
+    if args.streams is not None and (not args.track or args.streams < 1 or args.reid):
+        ap.error('--streams S (S >= 1) goes with --track [--botsort]')
+    if args.track and args.streams:
+        print(f'(c*) {args.streams} streams: one stacked launch per 4 frames of every stream vs {args.streams} single-tracker launches in sequence '
+              '(device events around whole passes, taken in turn)')
+        for n_obj in (24, 100):
+            print(json.dumps(bench_track_streams(n_obj, args.streams, botsort=args.botsort)))
+        return
     if args.track:
         print('(c) tracker per frame: one launch per 4 frames (device events) vs device-to-host copy + numpy twin (host clock; numpy and scipy, not the reference with lap)')
         for n_obj in (24, 100):

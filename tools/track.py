@@ -20,6 +20,10 @@ the device as well: the tracker rule (XYWH filter, warped track states) in the t
 and compared on the device; how well those embeddings tell identities apart with trained weights has not been measured).
 --gt is a directory of VisDrone-MOT annotation files <sequence>.txt (track.read_mot states how categories become classes and kinds);
 a sequence without a file there is tracked but not scored.
+--streams S tracks the sequence directories S at a time, as S streams of one batch (Predictor.track_streams: one forward and one
+tracker launch, one workgroup per stream, for --batch frames of every stream); the files written are the same per-sequence ones.
+--gt does not go with it - every evaluator holds one sequence's state: write the tracks with --save-mot and score them with
+tools/mot_eval.py.
 """
 import argparse
 import json
@@ -49,7 +53,8 @@ def parse_args(argv=None):
                     "decoder's query embeddings, next to IoU; off = IoU only)")
     ap.add_argument('--capacity', type=int, default=1024, help='tracks the device table holds')
     ap.add_argument('--imgsz', type=int, default=640)
-    ap.add_argument('--batch', type=int, default=4)
+    ap.add_argument('--batch', type=int, default=4, help='frames per forward; with --streams: frames of every stream per forward')
+    ap.add_argument('--streams', type=int, help='track the sequence directories S at a time, one tracker per stream in one launch')
     ap.add_argument('--conf', type=float, default=0.1, help='keep it at or below track_low_thresh so the second association has input')
     ap.add_argument('--iou', type=float, default=0.7)
     ap.add_argument('--classes', type=int, nargs='+', default=None, help='keep only these class ids')
@@ -72,6 +77,11 @@ def parse_args(argv=None):
         ap.error('give either --text-feats, or --clip-weights together with --clip-vocab (not both, not neither)')
     if args.reid and not args.tracker:
         ap.error('--reid overrides a botsort.yaml: give --tracker')
+    if args.streams is not None and args.streams < 1:
+        ap.error('--streams must be positive')
+    if args.streams is not None and args.gt:
+        ap.error('--gt does not go with --streams (an evaluator holds one sequence\'s state): write the tracks with --save-mot and score '
+                 'them with tools/mot_eval.py')
     return args
 
 
@@ -106,11 +116,13 @@ def main(argv=None):
     model.load_state_dict(ck['model' if args.raw else 'ema'])
     pred = Predictor(model, names, D.TextFeatures.from_args(args.text_feats, args.clip_weights, args.clip_vocab, dev), imgsz=args.imgsz, conf=args.conf,
                      iou=args.iou, classes=args.classes, single_cls=args.single_cls, batch=args.batch, dtype=args.dtype)
-    if args.tracker:
-        over = {**({'gmc_method': args.gmc} if args.gmc else {}), **({'with_reid': args.reid == 'on'} if args.reid else {})}
-        tracker = tracker_from_yaml(args.tracker, dev, capacity=args.capacity, reid_dim=model.model[-1].hidden_dim, **over)
-    else:
-        tracker = ByteTracker(dev, capacity=args.capacity)
+    def make_tracker(streams=None):
+        if args.tracker:
+            over = {**({'gmc_method': args.gmc} if args.gmc else {}), **({'with_reid': args.reid == 'on'} if args.reid else {})}
+            return tracker_from_yaml(args.tracker, dev, capacity=args.capacity, reid_dim=model.model[-1].hidden_dim, streams=streams, **over)
+        return ByteTracker(dev, capacity=args.capacity, streams=streams)
+
+    tracker = make_tracker() if args.streams is None else None
     save_dir = increment_path(os.path.join(args.project, args.name), exist_ok=args.exist_ok)
     saving = args.save or args.save_txt or args.save_mot or bool(args.gt)
     evaluator = MotEvaluator(dev, len(names), iou=args.mot_iou) if args.gt else None
@@ -126,22 +138,39 @@ def main(argv=None):
     n_img = n_rows = n_ids = 0
     t0 = time.perf_counter()
     seqs = list_sequences(args.source, is_image_file)
-    for name, folder in seqs:
+
+    def keep(name, det, frames, ids):      # one frame's files and counts
+        nonlocal n_img, n_rows
+        n_img += 1
+        stem = os.path.splitext(os.path.basename(det.path))[0]
+        if det.id is not None:
+            n_rows += len(det)
+            ids.update(det.id.tolist())
+        if args.save_txt:
+            det.save_txt(save_dir / 'labels' / name / f'{stem}.txt', save_conf=args.save_conf)
+        if args.save:
+            det.save(save_dir / name / os.path.basename(det.path))
+        det.orig_img = None
+        frames.append(det)
+
+    groups = [seqs[g:g + args.streams] for g in range(0, len(seqs), args.streams)] if args.streams else []
+    trackers = {}      # --streams: one stacked tracker per group size (the last group may be smaller)
+    for group in groups:
+        frames, ids = [[] for _ in group], [set() for _ in group]
+        if len(group) not in trackers:
+            trackers[len(group)] = make_tracker(len(group))
+        for s, det in pred.track_streams([folder for _, folder in group], tracker=trackers[len(group)], frames_per_stream=args.batch):
+            keep(group[s][0], det, frames[s], ids[s])
+        n_ids += sum(len(i) for i in ids)
+        for (name, _), fr in zip(group, frames):
+            if args.save_mot:
+                write_mot(save_dir / f'{name}.txt', fr)
+    for name, folder in [] if args.streams else seqs:
         frames, ids = [], set()
         gt_file = os.path.join(args.gt, name + '.txt') if args.gt else None
         gt = read_mot(gt_file) if gt_file and os.path.exists(gt_file) else None
         for det in pred.track(folder, tracker=tracker, gt=gt, evaluator=(evaluator if len(evaluators) == 1 else evaluators) if gt is not None else None):     # persist=False: a fresh tracker
-            n_img += 1
-            stem = os.path.splitext(os.path.basename(det.path))[0]
-            if det.id is not None:
-                n_rows += len(det)
-                ids.update(det.id.tolist())
-            if args.save_txt:
-                det.save_txt(save_dir / 'labels' / name / f'{stem}.txt', save_conf=args.save_conf)
-            if args.save:
-                det.save(save_dir / name / os.path.basename(det.path))
-            det.orig_img = None
-            frames.append(det)
+            keep(name, det, frames, ids)
         n_ids += len(ids)
         if args.save_mot:
             write_mot(save_dir / f'{name}.txt', frames)
@@ -188,7 +217,8 @@ def main(argv=None):
     print(json.dumps({**extra, 'sequences': len(seqs), 'images': n_img, 'track_rows': n_rows, 'ids': n_ids, 'save_dir': str(save_dir) if saving else None,
                       'ms_per_image': {'load': round(sp['load'], 3), 'forward': round(sp['h2d'] + sp['forward'], 3),
                                        'postprocess': round(sp['postprocess'], 3), 'track': round(sp['track'], 4), 'd2h': round(sp['d2h'], 3)},
-                      'wall_s': round(wall, 3), 'dtype': args.dtype, 'imgsz': args.imgsz, 'batch': args.batch}))
+                      'wall_s': round(wall, 3), 'dtype': args.dtype, 'imgsz': args.imgsz, 'batch': args.batch,
+                      **({'streams': args.streams} if args.streams else {})}))
 
 
 if __name__ == '__main__':
