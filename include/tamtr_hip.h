@@ -39,8 +39,9 @@ extern "C" {
  * tamtr_bytetrack_workspace_bytes, tamtr_val_coco_match / tamtr_val_coco_workspace_bytes / tamtr_val_coco_accumulate and tamtr_mot_update /
  * tamtr_mot_end_sequence / tamtr_mot_workspace_bytes, tamtr_hota_update / tamtr_hota_end_sequence / tamtr_hota_workspace_bytes,
  * tamtr_trackmap_update / tamtr_trackmap_end_sequence / tamtr_trackmap_workspace_bytes, tamtr_dw_slices / tamtr_dw_bf16 and the stream forms
- * tamtr_bytetrack_update_streams / tamtr_botsort_update_streams / tamtr_botsort_reid_update_streams / tamtr_gmc_estimate_streams with their
- * workspace sizes are new symbols only: no existing signature changed, so the version stayed at 36 when they were added. */
+ * tamtr_bytetrack_update_streams / tamtr_botsort_update_streams / tamtr_botsort_reid_update_streams / tamtr_gmc_estimate_streams and
+ * tamtr_mot_update_streams / tamtr_mot_end_streams / tamtr_hota_update_streams / tamtr_hota_end_streams with their workspace sizes are new
+ * symbols only: no existing signature changed, so the version stayed at 36 when they were added. */
 int tamtr_abi_version(void);
 
 /* ---------------------------------------------------------------------------------------------------------------
@@ -928,6 +929,39 @@ int tamtr_hota_update(const float* tracks, const int32_t* tcounts, const float* 
 int tamtr_hota_end_sequence(const double* alpha, double eps, int nc, int nq, int ng, int workgroups, void* const* state, const int* caps,
                             void* workspace, int workspace_bytes, void* stream);
 int tamtr_hota_workspace_bytes(int nq, int ng, int workgroups); /* 0 = unsupported */
+
+/*      Several streams at once: one evaluator state per stream, scored next to tamtr_*_update_streams on the same frame-major batch
+ *      (image f * S + s is the f-th frame of stream s, B = F * S).  Every state tensor of either evaluator gains a leading S (MOT: gstate
+ *      [S, G, 8], counts [S, nc, 16], iou_sum [S, nc], pair [S, G, T], hdr [S, 8]; HOTA: all twelve likewise, the state array still holds
+ *      12 pointers), and slice s is a valid single-evaluator state: the single entries accept state[k][s] as it is.
+ *      tamtr_mot_update_streams / tamtr_hota_update_streams: one launch, grid = S; workgroup s walks images s, s + S, ... in order and
+ *       touches only slice s of the state and of the workspace, the run totals included: no atomic is shared between streams, so stream s
+ *       gets what the single entry computes on its images.  active i32 [B] on the device, NULL = every image counts: an image whose
+ *       word is 0 is no frame of its stream - it advances no frame counter, logs and counts nothing, and its rows are not read (a stream
+ *       that has ended keeps its place in the batch so, and a stream without ground truth stays unscored).
+ *      tamtr_mot_end_streams: one launch, grid (nc, S).  ending i32 [S] on the device, NULL = every stream ends: the workgroups of a
+ *       stream whose word is 0 return at once and leave slice s untouched; the others do what tamtr_mot_end_sequence does, on slice s,
+ *       with gt_used[s] (i32 [S] on the device) as its G_used.
+ *      tamtr_hota_end_streams: the three launches of tamtr_hota_end_sequence with the stream as the grid's second dimension and the same
+ *       `ending` mask; `workgroups` is per stream (ops: min(64, 1024 / S), at least 1), each with its own workspace slice.
+ *      workspace: tamtr_mot_streams_workspace_bytes(S, nq, ng, nc, G_cap, T_cap) / tamtr_hota_streams_workspace_bytes(S, nq, ng,
+ *       workgroups) bytes, 16-byte aligned: S times the single size rounded up to 16; 0 = a size the single entry does not support, or a
+ *       total beyond 2^31 - 1 bytes.  LDS use is per workgroup and unchanged.
+ *      TAMTR_EINVAL / TAMTR_EUNSUP: as the single entries, and TAMTR_EINVAL for S < 1, B % S != 0 or a NULL gt_used; TAMTR_EUNSUP for
+ *       S > 65535.  Every check comes before any GPU call; nothing is allocated, set or synchronised.  The single entries are these
+ *       with S = 1 and NULL masks.  (New symbols only: no existing signature changed, the ABI version stays 36.) */
+int tamtr_mot_update_streams(const float* tracks, const int32_t* tcounts, const float* gt, const int32_t* gcounts, int B, int S, int nq, int ng,
+                             int nc, double iou_thr, const int32_t* active, int32_t* gstate, int32_t* counts, double* iou_sum, int32_t* pair,
+                             int32_t* hdr, int G_cap, int T_cap, void* workspace, int workspace_bytes, void* stream);
+int tamtr_mot_end_streams(int nc, int S, const int32_t* ending, const int32_t* gt_used, int32_t* gstate, int32_t* counts, int32_t* pair,
+                          int32_t* hdr, int G_cap, int T_cap, void* workspace, int workspace_bytes, void* stream);
+int tamtr_mot_streams_workspace_bytes(int S, int nq, int ng, int nc, int G_cap, int T_cap); /* 0 = unsupported */
+int tamtr_hota_update_streams(const float* tracks, const int32_t* tcounts, const float* gt, const int32_t* gcounts, int B, int S, int nq, int ng,
+                              int nc, double iou_thr, double eps, const int32_t* active, void* const* state, const int* caps, void* workspace,
+                              int workspace_bytes, void* stream);
+int tamtr_hota_end_streams(const double* alpha, double eps, int nc, int S, const int32_t* ending, int nq, int ng, int workgroups,
+                           void* const* state, const int* caps, void* workspace, int workspace_bytes, void* stream);
+int tamtr_hota_streams_workspace_bytes(int S, int nq, int ng, int workgroups); /* 0 = unsupported */
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Track-mAP on the device, next to the MOT evaluation and HOTA: average precision over whole tracks, ranked by mean score and matched

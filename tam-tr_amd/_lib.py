@@ -135,6 +135,12 @@ _SIGS = {
     'tamtr_hota_update': [_P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P, _P, _I, _P],
     'tamtr_hota_end_sequence': [_P, _D, _I, _I, _I, _I, _P, _P, _P, _I, _P],
     'tamtr_hota_workspace_bytes': [_I, _I, _I],
+    'tamtr_mot_update_streams': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P],
+    'tamtr_mot_end_streams': [_I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _P],
+    'tamtr_mot_streams_workspace_bytes': [_I, _I, _I, _I, _I, _I],
+    'tamtr_hota_update_streams': [_P, _P, _P, _P, _I, _I, _I, _I, _I, _D, _D, _P, _P, _P, _P, _I, _P],
+    'tamtr_hota_end_streams': [_P, _D, _I, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P],
+    'tamtr_hota_streams_workspace_bytes': [_I, _I, _I, _I],
     'tamtr_trackmap_update': [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _I, _P],
     'tamtr_trackmap_end_sequence': [_P, _I, _D, _I, _P, _P, _P, _I, _P],
     'tamtr_trackmap_workspace_bytes': [_I, _I, _I, _I, _I, _I],

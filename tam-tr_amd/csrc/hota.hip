@@ -45,6 +45,9 @@
 // A pair matched at level k is a TP for every threshold a < k, so TP[c, a] = sum of tp_lvl[c, k] over k > a, loc_sum likewise, and the
 // 19 mc_a of a pair are a suffix sum over its 20-bin histogram.  There is no [19, G, T] table.  Whatever exceeds a capacity is counted
 // in hdr and left out: nothing is written past a table.
+// Several streams (tamtr_hota_update_streams, tamtr_hota_end_streams): each of the twelve tensors gains a leading S (gstate [S, G, 2],
+// ..., hdr [S, 16]; the state array still holds 12 pointers) and slice s is the state above for stream s, run totals included: the
+// single entries take state[k][s] as it is.
 //
 // DESIGN
 // Update: one workgroup of 256 threads walks the frames in order, as mot_update_kernel does, so every pot cell has one adder per frame
@@ -57,6 +60,12 @@
 // solves the rest (mot_assign_sparse), then bumps the level bins of the matched pairs (integer atomics; loc_lvl is an fp64 atomic
 // add, so its last bits depend on the order).  Launch 2 (reduction): one thread per pair slot forms the pair's 19 terms, adds them to
 // `ass` (fp64 atomics) and clears the slot.  Launch 3 clears gstate, tcount and the two counters of hdr.
+// Several streams: as in mot.hip.  Update: grid = S, workgroup s walks the images s, s + S, ... of the frame-major batch on slice s
+// (hota_stream) of the state and of the workspace; an image whose `active` word is 0 is no frame of its stream (nothing is logged, no
+// frame is used up).  End: the same three launches with the stream as the grid's second dimension; the workgroups of a stream whose
+// `ending` word is 0 return at once.  `workgroups` is per stream (the host picks min(64, 1024 / S), at least 1) and each has its own
+// workspace slice inside its stream's.  No atomic is shared between streams; ppot stays plain in-order adds.  The single entries are
+// the same launchers with S = 1 and no masks.
 #include "common.h"
 #include "mot_rule.h"
 
@@ -89,6 +98,24 @@ struct HotaState {
   int nc, G, T, P, L, F;
 };
 
+// slice s of a stacked state: every tensor of HOTA_STATE_SPEC has a leading S
+static __device__ inline HotaState hota_stream(HotaState st, int s) {
+  const size_t z = (size_t)s;
+  st.gstate += z * st.G * 2;
+  st.tcount += z * st.nc * st.T;
+  st.pkey += z * st.P;
+  st.ppot += z * st.P;
+  st.phist += z * st.P * HOTA_LEVELS;
+  st.fidx += z * st.F * 4;
+  st.log += z * st.L;
+  st.dets += z * st.nc * 2;
+  st.tp_lvl += z * st.nc * HOTA_LEVELS;
+  st.loc_lvl += z * st.nc * HOTA_LEVELS;
+  st.ass += z * 3 * st.nc * HOTA_NA;
+  st.hdr += z * 16;
+  return st;
+}
+
 static size_t hota_update_ws_bytes(size_t nq, size_t ng) { return mot_frame_ws_bytes(nq, ng) + 8 * (ng + nq); }   // the frame's block, then rsum and csum
 static __host__ __device__ inline size_t hota_end_ws_per_group(size_t nq, size_t ng) { return (8 * ng * nq + 4 * (5 * ng + 3 * nq) + 15) & ~(size_t)15; }
 
@@ -97,10 +124,12 @@ struct HotaUpdateParams {
   const int32_t* tcounts;
   const float* gt;
   const int32_t* gcounts;
-  int B, nq, ng;
+  const int32_t* active;   // [B] or NULL: an image whose word is 0 is no frame of its stream
+  int B, S, nq, ng;
   double thr, eps;
   HotaState st;
   unsigned char* ws;
+  size_t ws_slice;   // bytes between the workspaces of two streams
 };
 
 __global__ __launch_bounds__(HOTA_THREADS) void hota_update_kernel(HotaUpdateParams p) {
@@ -108,17 +137,20 @@ __global__ __launch_bounds__(HOTA_THREADS) void hota_update_kernel(HotaUpdatePar
   __shared__ int wsum[(HOTA_THREADS / WAVE)];
   __shared__ MotCand red[(HOTA_THREADS / WAVE)];
   __shared__ int lcnt;
-  const HotaState& st = p.st;
+  // workgroup s owns slice s of the state and of the workspace, and the images s, s + S, ... of the batch
+  const int s = blockIdx.x;
+  const HotaState st = hota_stream(p.st, s);
   const int tid = threadIdx.x, nq = p.nq, ng = p.ng, nc = st.nc;
   const MotLsap w = mot_lsap_carve(lds, ng, nq + 1);
-  const MotFrame f = mot_frame_carve(p.ws, nq, ng);
+  const MotFrame f = mot_frame_carve(p.ws + (size_t)s * p.ws_slice, nq, ng);
   const double* iouM = f.iouM;
   const int *gl = f.gl, *g3 = f.g3, *tl = f.tl, *t3 = f.t3;
   double* rsum = reinterpret_cast<double*>(f.end);   // [n3] the row sums of the class's similarity; 8-byte aligned (mot_frame_ws_bytes)
   double* csum = rsum + ng;                          // [m3]
   int fid = st.hdr[HH_FRAMES], used = st.hdr[HH_LOG];
 
-  for (int b = 0; b < p.B; ++b) {
+  for (int b = s; b < p.B; b += p.S) {
+    if (p.active && p.active[b] == 0) continue;   // uniform: not a frame of this stream
     if (fid >= st.F) {   // uniform: the frame is left out whole
       if (tid == 0) atomicAdd(&st.hdr[HH_OVER_FRAMES], 1);
       continue;
@@ -183,20 +215,24 @@ __global__ __launch_bounds__(HOTA_THREADS) void hota_update_kernel(HotaUpdatePar
 
 struct HotaMatchParams {
   HotaState st;
+  const int32_t* ending;   // [S] or NULL: the workgroups of a stream whose word is 0 return at once
   int nq, ng;
   double eps;
   double alpha[HOTA_NA];
   unsigned char* ws;
+  size_t ws_slice;
 };
 
 __global__ __launch_bounds__(HOTA_THREADS) void hota_match_kernel(HotaMatchParams p) {
   extern __shared__ __align__(16) unsigned char lds[];
   __shared__ int wsum[(HOTA_THREADS / WAVE)];
   __shared__ MotCand red[(HOTA_THREADS / WAVE)];
-  const HotaState& st = p.st;
+  const int s = blockIdx.y;
+  if (p.ending && p.ending[s] == 0) return;
+  const HotaState st = hota_stream(p.st, s);
   const int tid = threadIdx.x, nq = p.nq, ng = p.ng;
   const MotLsap w = mot_lsap_carve(lds, ng, nq + 1);
-  unsigned char* base = p.ws + (size_t)blockIdx.x * hota_end_ws_per_group(nq, ng);
+  unsigned char* base = p.ws + (size_t)s * p.ws_slice + (size_t)blockIdx.x * hota_end_ws_per_group(nq, ng);
   double* S = reinterpret_cast<double*>(base);                     // [n, m] minus the score
   int* x = reinterpret_cast<int*>(S + (size_t)ng * nq);
   MotSparse sq;
@@ -244,7 +280,9 @@ __global__ __launch_bounds__(HOTA_THREADS) void hota_match_kernel(HotaMatchParam
   }
 }
 
-__global__ __launch_bounds__(HOTA_THREADS) void hota_reduce_kernel(HotaState st) {
+__global__ __launch_bounds__(HOTA_THREADS) void hota_reduce_kernel(HotaState all, const int32_t* ending) {
+  if (ending && ending[blockIdx.y] == 0) return;
+  const HotaState st = hota_stream(all, blockIdx.y);
   const size_t plane = (size_t)st.nc * HOTA_NA;
   for (int s = blockIdx.x * HOTA_THREADS + threadIdx.x; s < st.P; s += gridDim.x * HOTA_THREADS) {
     const unsigned long long k1 = st.pkey[s];
@@ -273,7 +311,9 @@ __global__ __launch_bounds__(HOTA_THREADS) void hota_reduce_kernel(HotaState st)
   }
 }
 
-__global__ __launch_bounds__(HOTA_THREADS) void hota_clear_kernel(HotaState st) {
+__global__ __launch_bounds__(HOTA_THREADS) void hota_clear_kernel(HotaState all, const int32_t* ending) {
+  if (ending && ending[blockIdx.y] == 0) return;
+  const HotaState st = hota_stream(all, blockIdx.y);
   const size_t ng = (size_t)st.G * 2, nt = (size_t)st.nc * st.T;
   for (size_t e = (size_t)blockIdx.x * HOTA_THREADS + threadIdx.x; e < ng + nt; e += (size_t)gridDim.x * HOTA_THREADS) {
     if (e < ng) st.gstate[e] = 0;
@@ -308,34 +348,65 @@ static HotaState hota_state(void* const* state, int nc, const int* caps) {
                    (int32_t*)state[11], nc, caps[0], caps[1], caps[2], caps[3], caps[4]};
 }
 
+// S stacked evaluators: each stream's slice of the workspace is the single size rounded up to 16 bytes
+static size_t hota_ws_slice(int nq, int ng, int workgroups) { return ((size_t)tamtr_hota_workspace_bytes(nq, ng, workgroups) + 15) & ~(size_t)15; }
+
+extern "C" int tamtr_hota_streams_workspace_bytes(int S, int nq, int ng, int workgroups) {
+  if (S < 1 || tamtr_hota_workspace_bytes(nq, ng, workgroups) == 0) return 0;
+  const size_t slice = hota_ws_slice(nq, ng, workgroups);
+  return slice > (size_t)0x7fffffff / S ? 0 : (int)(S * slice);
+}
+
+static bool hota_streams_unsupported(int S, int nq, int ng, int workgroups, const HotaState& st) {
+  return hota_unsupported(nq, ng, workgroups, st) || S > 65535 || tamtr_hota_streams_workspace_bytes(S, nq, ng, workgroups) == 0;
+}
+
+// The one place hota_update_kernel is launched from; tamtr_hota_update is S = 1 without a mask.  The last stream's slice need not be
+// rounded up, so with S = 1 the workspace asked for is the single entry's.
+extern "C" int tamtr_hota_update_streams(const float* tracks, const int32_t* tcounts, const float* gt, const int32_t* gcounts, int B, int S, int nq,
+                                         int ng, int nc, double iou_thr, double eps, const int32_t* active, void* const* state, const int* caps,
+                                         void* workspace, int workspace_bytes, void* stream) {
+  const HotaState st = hota_state(state, nc, caps);
+  if (!tracks || !tcounts || !gt || !gcounts || hota_state_invalid(st) || !workspace || B < 1 || nq < 1 || ng < 1 || !(iou_thr > 0.0) ||
+      !(eps > 0.0) || ((uintptr_t)workspace & 15) || S < 1 || B % S != 0)
+    return TAMTR_EINVAL;
+  if (hota_streams_unsupported(S, nq, ng, 1, st)) return TAMTR_EUNSUP;
+  const size_t slice = hota_ws_slice(nq, ng, 1);
+  if (workspace_bytes < 0 || (size_t)workspace_bytes < (S - 1) * slice + hota_update_ws_bytes(nq, ng)) return TAMTR_EINVAL;
+  HotaUpdateParams p{tracks, tcounts, gt, gcounts, active, B, S, nq, ng, iou_thr, eps, st, static_cast<unsigned char*>(workspace), slice};
+  hipLaunchKernelGGL(hota_update_kernel, dim3(S), dim3(HOTA_THREADS), mot_lsap_bytes(ng, (size_t)nq + 1), (hipStream_t)stream, p);
+  return tamtr_launch_status();
+}
+
 extern "C" int tamtr_hota_update(const float* tracks, const int32_t* tcounts, const float* gt, const int32_t* gcounts, int B, int nq, int ng,
                                  int nc, double iou_thr, double eps, void* const* state, const int* caps, void* workspace,
                                  int workspace_bytes, void* stream) {
+  return tamtr_hota_update_streams(tracks, tcounts, gt, gcounts, B, 1, nq, ng, nc, iou_thr, eps, nullptr, state, caps, workspace, workspace_bytes,
+                                   stream);
+}
+
+// The one place the three launches of the end of a sequence are made from: the stream is the grid's second dimension, and the
+// workgroups of a stream that is not ending return at once.  tamtr_hota_end_sequence is S = 1 without a mask.
+extern "C" int tamtr_hota_end_streams(const double* alpha, double eps, int nc, int S, const int32_t* ending, int nq, int ng, int workgroups,
+                                      void* const* state, const int* caps, void* workspace, int workspace_bytes, void* stream) {
   const HotaState st = hota_state(state, nc, caps);
-  if (!tracks || !tcounts || !gt || !gcounts || hota_state_invalid(st) || !workspace || B < 1 || nq < 1 || ng < 1 || !(iou_thr > 0.0) ||
-      !(eps > 0.0) || ((uintptr_t)workspace & 15))
+  if (!alpha || hota_state_invalid(st) || !workspace || nq < 1 || ng < 1 || workgroups < 1 || !(eps > 0.0) || ((uintptr_t)workspace & 15) || S < 1)
     return TAMTR_EINVAL;
-  if (hota_unsupported(nq, ng, 1, st)) return TAMTR_EUNSUP;
-  if ((size_t)workspace_bytes < hota_update_ws_bytes(nq, ng)) return TAMTR_EINVAL;
-  HotaUpdateParams p{tracks, tcounts, gt, gcounts, B, nq, ng, iou_thr, eps, st, static_cast<unsigned char*>(workspace)};
-  hipLaunchKernelGGL(hota_update_kernel, dim3(1), dim3(HOTA_THREADS), mot_lsap_bytes(ng, (size_t)nq + 1), (hipStream_t)stream, p);
+  if (hota_streams_unsupported(S, nq, ng, workgroups, st)) return TAMTR_EUNSUP;
+  const size_t slice = hota_ws_slice(nq, ng, workgroups);
+  if (workspace_bytes < 0 || (size_t)workspace_bytes < (S - 1) * slice + (size_t)workgroups * hota_end_ws_per_group(nq, ng)) return TAMTR_EINVAL;
+  HotaMatchParams p{st, ending, nq, ng, eps, {}, static_cast<unsigned char*>(workspace), slice};
+  for (int a = 0; a < HOTA_NA; ++a) p.alpha[a] = alpha[a];   // host memory: the 19 values as numpy made them
+  hipLaunchKernelGGL(hota_match_kernel, dim3(workgroups, S), dim3(HOTA_THREADS), mot_lsap_bytes(ng, (size_t)nq + 1), (hipStream_t)stream, p);
+  const int blocks = (st.P + HOTA_THREADS - 1) / HOTA_THREADS;
+  hipLaunchKernelGGL(hota_reduce_kernel, dim3(blocks < 1024 ? blocks : 1024, S), dim3(HOTA_THREADS), 0, (hipStream_t)stream, st, ending);
+  const size_t cells = (size_t)st.G * 2 + (size_t)st.nc * st.T;
+  const size_t cb = (cells + HOTA_THREADS - 1) / HOTA_THREADS;
+  hipLaunchKernelGGL(hota_clear_kernel, dim3(cb < 1024 ? (int)cb : 1024, S), dim3(HOTA_THREADS), 0, (hipStream_t)stream, st, ending);
   return tamtr_launch_status();
 }
 
 extern "C" int tamtr_hota_end_sequence(const double* alpha, double eps, int nc, int nq, int ng, int workgroups, void* const* state,
                                        const int* caps, void* workspace, int workspace_bytes, void* stream) {
-  const HotaState st = hota_state(state, nc, caps);
-  if (!alpha || hota_state_invalid(st) || !workspace || nq < 1 || ng < 1 || workgroups < 1 || !(eps > 0.0) || ((uintptr_t)workspace & 15))
-    return TAMTR_EINVAL;
-  if (hota_unsupported(nq, ng, workgroups, st)) return TAMTR_EUNSUP;
-  if ((size_t)workspace_bytes < (size_t)workgroups * hota_end_ws_per_group(nq, ng)) return TAMTR_EINVAL;
-  HotaMatchParams p{st, nq, ng, eps, {}, static_cast<unsigned char*>(workspace)};
-  for (int a = 0; a < HOTA_NA; ++a) p.alpha[a] = alpha[a];   // host memory: the 19 values as numpy made them
-  hipLaunchKernelGGL(hota_match_kernel, dim3(workgroups), dim3(HOTA_THREADS), mot_lsap_bytes(ng, (size_t)nq + 1), (hipStream_t)stream, p);
-  const int blocks = (st.P + HOTA_THREADS - 1) / HOTA_THREADS;
-  hipLaunchKernelGGL(hota_reduce_kernel, dim3(blocks < 1024 ? blocks : 1024), dim3(HOTA_THREADS), 0, (hipStream_t)stream, st);
-  const size_t cells = (size_t)st.G * 2 + (size_t)st.nc * st.T;
-  const size_t cb = (cells + HOTA_THREADS - 1) / HOTA_THREADS;
-  hipLaunchKernelGGL(hota_clear_kernel, dim3(cb < 1024 ? (int)cb : 1024), dim3(HOTA_THREADS), 0, (hipStream_t)stream, st);
-  return tamtr_launch_status();
+  return tamtr_hota_end_streams(alpha, eps, nc, 1, nullptr, nq, ng, workgroups, state, caps, workspace, workspace_bytes, stream);
 }

@@ -48,6 +48,9 @@
 // axis; track ids are used as they are, [0, T).  An id or a per-frame row count beyond capacity is counted in hdr and the row is left
 // out: nothing is written past a table.  The CLEAR counts add straight into the run totals; Frag, MT / PT / ML, gt_ids and IDTP are
 // added by tamtr_mot_end_sequence, which then clears gstate, the rows of pair it used and the frame counter.
+// Several streams (tamtr_mot_update_streams, tamtr_mot_end_streams): every tensor gains a leading S - gstate [S, G, 8], counts
+// [S, nc, 16], iou_sum [S, nc], pair [S, G, T], hdr [S, 8] - and slice s is the state above for stream s, run totals included: the
+// single entries take state[k][s] as it is.  The host keeps one (class, id) -> dense row map per stream.
 //
 // DESIGN
 // Update: one workgroup of 256 threads walks the frames in order (step 3 depends on the frame before; the whole update is one launch,
@@ -63,6 +66,13 @@
 // End of sequence: one workgroup per class.  It lists the class's gt rows, reduces MT / PT / ML / Frag, drops the track ids whose
 // pair column is zero over those rows (a block-wide column scan), solves the identity assignment with the solver's state in the
 // workspace (global memory: 1024 x 4097 does not fit the LDS) and clears what it read.
+// Several streams: sequences are independent, so the stream is the grid.  Update: grid = S, and workgroup s walks the images s, s + S,
+// ... of a frame-major batch (image f * S + s is the f-th frame of stream s, the tracker's layout in track.hip) on slice s of the state
+// and of the workspace, the run totals included - no atomic is shared between streams, so stream s gets the single evaluator's
+// result.  An image whose `active` word is 0 is no frame of its stream: no frame counter moves and its rows are not read (a stream
+// that has ended keeps its place in the batch so; so does one without ground truth).  End: grid (nc, S), and the workgroups of a
+// stream whose `ending` word is 0 return at once.  The workspace is S slices of the single size, each rounded up to 16 bytes; the LDS
+// is per workgroup and unchanged.  The single entries are the same launchers with S = 1 and no masks.
 #include "common.h"
 #include "mot_rule.h"
 
@@ -80,7 +90,8 @@ struct MotParams {
   const int32_t* tcounts;
   const float* gt;
   const int32_t* gcounts;
-  int B, nq, ng, nc, G, T;
+  const int32_t* active;   // [B] or NULL: an image whose word is 0 is no frame of its stream
+  int B, S, nq, ng, nc, G, T;
   double thr;
   int32_t* gstate;
   int32_t* counts;
@@ -88,13 +99,23 @@ struct MotParams {
   int32_t* pair;
   int32_t* hdr;
   unsigned char* ws;
+  size_t ws_slice;   // bytes between the workspaces of two streams
 };
 
 static size_t mot_update_ws_bytes(size_t nq, size_t ng) { return mot_frame_ws_bytes(nq, ng) + 4 * nq; }   // the frame's block, then tm
 static size_t mot_end_ws_per_class(size_t G, size_t T) { return ((4 * (2 * G + T) + 15) & ~(size_t)15) + mot_lsap_bytes(G, T + 1); }
 
-__global__ __launch_bounds__(MOT_UPDATE_THREADS) void mot_update_kernel(MotParams p) {
+__global__ __launch_bounds__(MOT_UPDATE_THREADS) void mot_update_kernel(MotParams q) {
   extern __shared__ __align__(16) unsigned char lds[];
+  // workgroup s owns slice s of every state tensor and of the workspace, and the images s, s + S, ... of the batch
+  const int s = blockIdx.x;
+  MotParams p = q;
+  p.gstate += (size_t)s * p.G * 8;
+  p.counts += (size_t)s * p.nc * 16;
+  p.iou_sum += (size_t)s * p.nc;
+  p.pair += (size_t)s * p.G * p.T;
+  p.hdr += (size_t)s * 8;
+  p.ws += (size_t)s * p.ws_slice;
   __shared__ int wsum[(MOT_UPDATE_THREADS / WAVE)];
   __shared__ MotCand red[(MOT_UPDATE_THREADS / WAVE)];
   const int tid = threadIdx.x, nq = p.nq, ng = p.ng, nc = p.nc;
@@ -106,7 +127,8 @@ __global__ __launch_bounds__(MOT_UPDATE_THREADS) void mot_update_kernel(MotParam
   const double thr = p.thr;
   int fid = p.hdr[H_FRAME];
 
-  for (int b = 0; b < p.B; ++b) {
+  for (int b = s; b < p.B; b += p.S) {
+    if (p.active && p.active[b] == 0) continue;   // uniform: not a frame of this stream
     ++fid;
     const float* G = p.gt + (size_t)b * ng * 7;
     const float* Tr = p.tracks + (size_t)b * nq * 8;
@@ -183,19 +205,28 @@ __global__ __launch_bounds__(MOT_UPDATE_THREADS) void mot_update_kernel(MotParam
 
 struct MotEndParams {
   int nc, G, T, G_used;
+  const int32_t* ending;    // [S] or NULL: the workgroups of a stream whose word is 0 return at once
+  const int32_t* gt_used;   // [S] or NULL: G_used per stream
   int32_t* gstate;
   int32_t* counts;
   int32_t* pair;
   int32_t* hdr;
   unsigned char* ws;
-  size_t per_class;
+  size_t per_class, ws_slice;
 };
 
-__global__ __launch_bounds__(MOT_END_THREADS) void mot_end_kernel(MotEndParams p) {
+__global__ __launch_bounds__(MOT_END_THREADS) void mot_end_kernel(MotEndParams q) {
   __shared__ int wsum[(MOT_END_THREADS / WAVE)];
   __shared__ MotCand red[(MOT_END_THREADS / WAVE)];
-  const int tid = threadIdx.x, c = blockIdx.x, T = p.T;
-  unsigned char* base = p.ws + (size_t)c * p.per_class;
+  const int tid = threadIdx.x, c = blockIdx.x, s = blockIdx.y, T = q.T;
+  if (q.ending && q.ending[s] == 0) return;
+  MotEndParams p = q;
+  p.gstate += (size_t)s * p.G * 8;
+  p.counts += (size_t)s * p.nc * 16;
+  p.pair += (size_t)s * p.G * p.T;
+  p.hdr += (size_t)s * 8;
+  if (p.gt_used) p.G_used = max(p.gt_used[s], 0);
+  unsigned char* base = p.ws + (size_t)s * p.ws_slice + (size_t)c * p.per_class;
   int* rows = reinterpret_cast<int*>(base);
   int *x = rows + p.G, *cols = x + p.G;
   const MotLsap w = mot_lsap_carve(base + ((4 * (2 * (size_t)p.G + T) + 15) & ~(size_t)15), p.G, T + 1);
@@ -242,27 +273,64 @@ static bool mot_unsupported(int nq, int ng, int nc, int G, int T) {
          G > (1 << 24) || T > (1 << 24) || nc > (1 << 16);   // ids travel as fp32
 }
 
+// S stacked evaluators: each stream's slice of the workspace is the single size rounded up to 16 bytes
+static size_t mot_ws_slice(int nq, int ng, int nc, int G, int T) { return ((size_t)tamtr_mot_workspace_bytes(nq, ng, nc, G, T) + 15) & ~(size_t)15; }
+
+extern "C" int tamtr_mot_streams_workspace_bytes(int S, int nq, int ng, int nc, int G_cap, int T_cap) {
+  if (S < 1 || tamtr_mot_workspace_bytes(nq, ng, nc, G_cap, T_cap) == 0) return 0;
+  const size_t slice = mot_ws_slice(nq, ng, nc, G_cap, T_cap);
+  return slice > (size_t)0x7fffffff / S ? 0 : (int)(S * slice);
+}
+
+static bool mot_streams_unsupported(int S, int nq, int ng, int nc, int G, int T) {
+  return mot_unsupported(nq, ng, nc, G, T) || S > 65535 || tamtr_mot_streams_workspace_bytes(S, nq, ng, nc, G, T) == 0;
+}
+
+// The one place mot_update_kernel is launched from; tamtr_mot_update is S = 1 without a mask.  The last stream's slice need not be
+// rounded up, so with S = 1 the workspace asked for is the single entry's.
+extern "C" int tamtr_mot_update_streams(const float* tracks, const int32_t* tcounts, const float* gt, const int32_t* gcounts, int B, int S, int nq,
+                                        int ng, int nc, double iou_thr, const int32_t* active, int32_t* gstate, int32_t* counts, double* iou_sum,
+                                        int32_t* pair, int32_t* hdr, int G_cap, int T_cap, void* workspace, int workspace_bytes, void* stream) {
+  if (!tracks || !tcounts || !gt || !gcounts || !gstate || !counts || !iou_sum || !pair || !hdr || !workspace || B < 1 || nq < 1 || ng < 1 ||
+      nc < 1 || G_cap < 1 || T_cap < 1 || !(iou_thr > 0.0) || ((uintptr_t)workspace & 15) || S < 1 || B % S != 0)
+    return TAMTR_EINVAL;
+  if (mot_streams_unsupported(S, nq, ng, nc, G_cap, T_cap)) return TAMTR_EUNSUP;
+  const size_t slice = mot_ws_slice(nq, ng, nc, G_cap, T_cap);
+  if (workspace_bytes < 0 || (size_t)workspace_bytes < (S - 1) * slice + (size_t)tamtr_mot_workspace_bytes(nq, ng, nc, G_cap, T_cap)) return TAMTR_EINVAL;
+  MotParams p{tracks, tcounts, gt, gcounts, active, B, S, nq, ng, nc, G_cap, T_cap, iou_thr, gstate, counts, iou_sum, pair, hdr,
+              static_cast<unsigned char*>(workspace), slice};
+  hipLaunchKernelGGL(mot_update_kernel, dim3(S), dim3(MOT_UPDATE_THREADS), mot_lsap_bytes(ng, (size_t)nq + 1), (hipStream_t)stream, p);
+  return tamtr_launch_status();
+}
+
 extern "C" int tamtr_mot_update(const float* tracks, const int32_t* tcounts, const float* gt, const int32_t* gcounts, int B, int nq, int ng,
                                 int nc, double iou_thr, int32_t* gstate, int32_t* counts, double* iou_sum, int32_t* pair, int32_t* hdr,
                                 int G_cap, int T_cap, void* workspace, int workspace_bytes, void* stream) {
-  if (!tracks || !tcounts || !gt || !gcounts || !gstate || !counts || !iou_sum || !pair || !hdr || !workspace || B < 1 || nq < 1 || ng < 1 ||
-      nc < 1 || G_cap < 1 || T_cap < 1 || !(iou_thr > 0.0) || ((uintptr_t)workspace & 15))
+  return tamtr_mot_update_streams(tracks, tcounts, gt, gcounts, B, 1, nq, ng, nc, iou_thr, nullptr, gstate, counts, iou_sum, pair, hdr, G_cap, T_cap,
+                                  workspace, workspace_bytes, stream);
+}
+
+// The one place mot_end_kernel is launched from: grid (nc, S).  gt_used NULL: G_used for every stream (the single entry).
+static int mot_end_launch(int nc, int S, const int32_t* ending, const int32_t* gt_used, int G_used, int32_t* gstate, int32_t* counts, int32_t* pair,
+                          int32_t* hdr, int G_cap, int T_cap, void* workspace, int workspace_bytes, void* stream) {
+  if (!gstate || !counts || !pair || !hdr || !workspace || nc < 1 || G_cap < 1 || T_cap < 1 || G_used < 0 || ((uintptr_t)workspace & 15) || S < 1)
     return TAMTR_EINVAL;
-  if (mot_unsupported(nq, ng, nc, G_cap, T_cap)) return TAMTR_EUNSUP;
-  if (workspace_bytes < tamtr_mot_workspace_bytes(nq, ng, nc, G_cap, T_cap)) return TAMTR_EINVAL;
-  MotParams p{tracks, tcounts, gt, gcounts, B, nq, ng, nc, G_cap, T_cap, iou_thr, gstate, counts, iou_sum, pair, hdr,
-              static_cast<unsigned char*>(workspace)};
-  hipLaunchKernelGGL(mot_update_kernel, dim3(1), dim3(MOT_UPDATE_THREADS), mot_lsap_bytes(ng, (size_t)nq + 1), (hipStream_t)stream, p);
+  if (mot_streams_unsupported(S, 1, 1, nc, G_cap, T_cap)) return TAMTR_EUNSUP;
+  const size_t slice = mot_ws_slice(1, 1, nc, G_cap, T_cap);
+  if (workspace_bytes < 0 || (size_t)workspace_bytes < (S - 1) * slice + (size_t)nc * mot_end_ws_per_class(G_cap, T_cap)) return TAMTR_EINVAL;
+  MotEndParams p{nc, G_cap, T_cap, G_used, ending, gt_used, gstate, counts, pair, hdr, static_cast<unsigned char*>(workspace),
+                 mot_end_ws_per_class(G_cap, T_cap), slice};
+  hipLaunchKernelGGL(mot_end_kernel, dim3(nc, S), dim3(MOT_END_THREADS), 0, (hipStream_t)stream, p);
   return tamtr_launch_status();
 }
 
 extern "C" int tamtr_mot_end_sequence(int nc, int32_t* gstate, int32_t* counts, int32_t* pair, int32_t* hdr, int G_cap, int T_cap, int G_used,
                                       void* workspace, int workspace_bytes, void* stream) {
-  if (!gstate || !counts || !pair || !hdr || !workspace || nc < 1 || G_cap < 1 || T_cap < 1 || G_used < 0 || ((uintptr_t)workspace & 15))
-    return TAMTR_EINVAL;
-  if (mot_unsupported(1, 1, nc, G_cap, T_cap)) return TAMTR_EUNSUP;
-  if ((size_t)workspace_bytes < (size_t)nc * mot_end_ws_per_class(G_cap, T_cap)) return TAMTR_EINVAL;
-  MotEndParams p{nc, G_cap, T_cap, G_used, gstate, counts, pair, hdr, static_cast<unsigned char*>(workspace), mot_end_ws_per_class(G_cap, T_cap)};
-  hipLaunchKernelGGL(mot_end_kernel, dim3(nc), dim3(MOT_END_THREADS), 0, (hipStream_t)stream, p);
-  return tamtr_launch_status();
+  return mot_end_launch(nc, 1, nullptr, nullptr, G_used, gstate, counts, pair, hdr, G_cap, T_cap, workspace, workspace_bytes, stream);
+}
+
+extern "C" int tamtr_mot_end_streams(int nc, int S, const int32_t* ending, const int32_t* gt_used, int32_t* gstate, int32_t* counts, int32_t* pair,
+                                     int32_t* hdr, int G_cap, int T_cap, void* workspace, int workspace_bytes, void* stream) {
+  if (!gt_used) return TAMTR_EINVAL;
+  return mot_end_launch(nc, S, ending, gt_used, 0, gstate, counts, pair, hdr, G_cap, T_cap, workspace, workspace_bytes, stream);
 }

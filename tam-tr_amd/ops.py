@@ -2184,12 +2184,15 @@ MOT_STATE_SPEC = (('gstate', torch.int32, lambda nc, c: (c[0], 8)), ('counts', t
 MOT_CAPS = ('gt', 'tracks')
 
 
-def mot_workspace_bytes(nq, ng, nc, gt_capacity, track_capacity):
-    """Bytes of device workspace tamtr_mot_update and tamtr_mot_end_sequence need (no GPU call)."""
-    n = _lib.lib().tamtr_mot_workspace_bytes(int(nq), int(ng), int(nc), int(gt_capacity), int(track_capacity))
+def mot_workspace_bytes(nq, ng, nc, gt_capacity, track_capacity, streams=None):
+    """Bytes of device workspace tamtr_mot_update and tamtr_mot_end_sequence need (no GPU call); streams=S: what
+    tamtr_mot_update_streams and tamtr_mot_end_streams need for S stacked states (S slices, each rounded up to 16 bytes)."""
+    S = _check_streams('mot', streams)
+    sizes = (int(nq), int(ng), int(nc), int(gt_capacity), int(track_capacity))
+    n = _lib.lib().tamtr_mot_workspace_bytes(*sizes) if S is None else _lib.lib().tamtr_mot_streams_workspace_bytes(S, *sizes)
     if n <= 0:
-        raise _lib.TamtrHipError(f'mot: nq {nq}, ng {ng}, nc {nc} with capacities {gt_capacity} x {track_capacity} is outside what the '
-                                 'kernel is built for')
+        raise _lib.TamtrHipError(f'mot: nq {nq}, ng {ng}, nc {nc} with capacities {gt_capacity} x {track_capacity}' +
+                                 (f' and {S} streams' if S else '') + ' is outside what the kernel is built for')
     return n
 
 
@@ -2209,18 +2212,51 @@ def _mot_frames(what, tracks, tcounts, gt, gcounts, iou):
     return B, nq, gt.shape[1], _c(tracks), _c(tcounts), _c(gt), _c(gcounts)
 
 
-def _eval_state(what, spec, cap_names, state, nc, caps):
-    """Check an evaluator's state against its spec -> (host array of its device pointers in the spec's order, host array of the
-    capacities)."""
+def _eval_streams(what, B, streams, active):
+    """The stream dimension of a stacked evaluator's update: S or None, and the active words (i32 [B] on the device, or None for
+    "every image is a frame") as the kernel reads them."""
+    S = _check_streams(what, streams)
+    if S is not None and B % S:
+        raise _lib.TamtrHipError(f'{what}: a batch of {B} images is no multiple of streams = {S} (frame-major: image f * S + s)')
+    if active is None:
+        return S, None
+    if S is None:
+        raise _lib.TamtrHipError(f'{what}: active belongs to a stacked evaluator (streams=S)')
+    if not torch.is_tensor(active) or tuple(active.shape) != (B,) or active.dtype != torch.int32:
+        got = (active.dtype, tuple(active.shape)) if torch.is_tensor(active) else type(active).__name__
+        raise _lib.TamtrHipError(f'{what}: active must be an int32 tensor [B] = [{B}], got {got}')
+    require_gpu(active)
+    return S, _c(active)
+
+
+def _eval_masks(what, S, **masks):
+    """The per-stream words of a stacked evaluator's end of sequence (ending, gt_used): i32 [S] on the device, or None."""
+    out = []
+    for k, t in masks.items():
+        if t is not None:
+            if not torch.is_tensor(t) or tuple(t.shape) != (S,) or t.dtype != torch.int32:
+                got = (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__
+                raise _lib.TamtrHipError(f'{what}: {k} must be an int32 tensor [S] = [{S}], got {got}')
+            require_gpu(t)
+            t = _c(t)
+        out.append(t)
+    return out
+
+
+def _eval_state(what, spec, cap_names, state, nc, caps, streams=None):
+    """Check an evaluator's state against its spec (streams=S: every tensor with a leading S) -> (host array of its device pointers in
+    the spec's order, host array of the capacities)."""
+    lead = () if streams is None else (streams,)
     caps = tuple(int(c) for c in caps)
     if int(nc) < 1 or len(caps) != len(cap_names) or min(caps) < 1:
         raise _lib.TamtrHipError(f'{what}: nc and the {len(cap_names)} capacities ({", ".join(cap_names)}) must be positive, got {nc} and {caps}')
     for k, dt, shape in spec:
         t = state.get(k) if isinstance(state, dict) else None
-        want = shape(int(nc), caps)
+        want = lead + shape(int(nc), caps)
         if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
             got = None if t is None else (t.dtype, tuple(t.shape))
-            raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want}, got {got}')
+            stack = '' if streams is None else f' (streams {streams})'
+            raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want}{stack}, got {got}')
     require_gpu(*(state[k] for k, _, _ in spec))
     return (ctypes.c_void_p * len(spec))(*(state[k].data_ptr() for k, _, _ in spec)), (ctypes.c_int * len(caps))(*caps)
 
@@ -2234,32 +2270,51 @@ def _eval_workspace(what, workspace, need, device):
     return workspace
 
 
-def mot_update(tracks, tcounts, gt, gcounts, state, nc, gt_capacity, track_capacity, iou=0.5, workspace=None):
+def mot_update(tracks, tcounts, gt, gcounts, state, nc, gt_capacity, track_capacity, iou=0.5, workspace=None, streams=None, active=None):
     """Steps 1 to 4 of the MOT evaluation rule (csrc/mot.hip; engine.mot_evaluate is its numpy statement) for the B frames of a batch,
     in order, in one launch.  tracks f32 [B, nq, 8] and tcounts i32 [B] are bytetrack_update's outputs on the GPU; gt f32 [B, ng, 7]
     (x1 y1 x2 y2 id cls kind, the id of a kind-0 row being its dense row in [0, gt_capacity)) and gcounts i32 [B] are on the GPU too.
     state: a dict of device tensors as MOT_STATE_SPEC lists them, updated in place.  Every check comes before the launch; no
-    synchronisation."""
+    synchronisation.
+    streams=S: one evaluator state per stream, still one launch (one workgroup per stream).  The B = F * S images are frame-major,
+    image f * S + s is the f-th frame of stream s, as bytetrack_update(streams=S) leaves them; every state tensor has a leading S and
+    the workspace is mot_workspace_bytes(..., streams=S).  active i32 [B] on the GPU (None: every image counts): an image whose word
+    is 0 is no frame of its stream.  Stream s gets what streams=None computes on its own frames and state[k][s]."""
     B, nq, ng, tracks, tcounts, gt, gcounts = _mot_frames('mot_update', tracks, tcounts, gt, gcounts, iou)
+    S, active = _eval_streams('mot_update', B, streams, active)
     nc, G, T = int(nc), int(gt_capacity), int(track_capacity)
-    _eval_state('mot_update', MOT_STATE_SPEC, MOT_CAPS, state, nc, (G, T))
+    _eval_state('mot_update', MOT_STATE_SPEC, MOT_CAPS, state, nc, (G, T), S)
     require_gpu(tracks, tcounts, gt, gcounts)
-    workspace = _eval_workspace('mot_update', workspace, mot_workspace_bytes(nq, ng, nc, G, T), tracks.device)
-    call('tamtr_mot_update', ptr(tracks), ptr(tcounts), ptr(gt), ptr(gcounts), B, nq, ng, nc, float(iou), ptr(state['gstate']),
-         ptr(state['counts']), ptr(state['iou_sum']), ptr(state['pair']), ptr(state['hdr']), G, T, ptr(workspace), int(workspace.numel()),
-         stream_ptr())
+    workspace = _eval_workspace('mot_update', workspace, mot_workspace_bytes(nq, ng, nc, G, T, S), tracks.device)
+    call('tamtr_mot_update_streams', ptr(tracks), ptr(tcounts), ptr(gt), ptr(gcounts), B, S or 1, nq, ng, nc, float(iou), ptr(active),
+         ptr(state['gstate']), ptr(state['counts']), ptr(state['iou_sum']), ptr(state['pair']), ptr(state['hdr']), G, T, ptr(workspace),
+         int(workspace.numel()), stream_ptr())
 
 
-def mot_end_sequence(state, nc, gt_capacity, track_capacity, gt_used, workspace=None):
+def mot_end_sequence(state, nc, gt_capacity, track_capacity, gt_used, workspace=None, streams=None, ending=None):
     """The per-sequence reduction of the MOT evaluation (MT / PT / ML / Frag and the identity assignment per class) in one launch; adds
-    to state['counts'] and clears the per-sequence state.  gt_used: the number of dense gt rows the host handed out.  No synchronisation."""
+    to state['counts'] and clears the per-sequence state.  gt_used: the number of dense gt rows the host handed out.  No synchronisation.
+    streams=S: the same launch with the stream as a second grid dimension.  gt_used is then i32 [S] on the GPU, and ending i32 [S] on
+    the GPU (None: every stream ends) names the streams to reduce: slice s of a stream whose word is 0 is left untouched."""
+    S = _check_streams('mot_end_sequence', streams)
     nc, G, T = int(nc), int(gt_capacity), int(track_capacity)
-    if int(gt_used) < 0:
-        raise _lib.TamtrHipError(f'mot_end_sequence: gt_used must be >= 0, got {gt_used}')
-    _eval_state('mot_end_sequence', MOT_STATE_SPEC, MOT_CAPS, state, nc, (G, T))
-    workspace = _eval_workspace('mot_end_sequence', workspace, mot_workspace_bytes(1, 1, nc, G, T), state['hdr'].device)
-    call('tamtr_mot_end_sequence', nc, ptr(state['gstate']), ptr(state['counts']), ptr(state['pair']), ptr(state['hdr']), G, T,
-         min(int(gt_used), G), ptr(workspace), int(workspace.numel()), stream_ptr())
+    if S is None:
+        if ending is not None:
+            raise _lib.TamtrHipError('mot_end_sequence: ending belongs to a stacked evaluator (streams=S)')
+        if int(gt_used) < 0:
+            raise _lib.TamtrHipError(f'mot_end_sequence: gt_used must be >= 0, got {gt_used}')
+    else:
+        if gt_used is None:
+            raise _lib.TamtrHipError(f'mot_end_sequence: gt_used must be an int32 tensor [S] = [{S}], got None')
+        ending, gt_used = _eval_masks('mot_end_sequence', S, ending=ending, gt_used=gt_used)
+    _eval_state('mot_end_sequence', MOT_STATE_SPEC, MOT_CAPS, state, nc, (G, T), S)
+    workspace = _eval_workspace('mot_end_sequence', workspace, mot_workspace_bytes(1, 1, nc, G, T, S), state['hdr'].device)
+    if S is None:      # the host's scalar goes as it is: no upload
+        call('tamtr_mot_end_sequence', nc, ptr(state['gstate']), ptr(state['counts']), ptr(state['pair']), ptr(state['hdr']), G, T,
+             min(int(gt_used), G), ptr(workspace), int(workspace.numel()), stream_ptr())
+    else:
+        call('tamtr_mot_end_streams', nc, S, ptr(ending), ptr(gt_used), ptr(state['gstate']), ptr(state['counts']), ptr(state['pair']),
+             ptr(state['hdr']), G, T, ptr(workspace), int(workspace.numel()), stream_ptr())
 
 
 # the HOTA evaluator's state (csrc/hota.hip states it): name, dtype, shape from (nc, caps); caps = (gt identities, track ids, pair
@@ -2275,40 +2330,59 @@ HOTA_END_WORKGROUPS = 64     # workgroups of the matching launch: each strides o
 HOTA_EPS = 2.0 ** -52        # np.finfo(float).eps
 
 
-def hota_workspace_bytes(nq, ng, workgroups=HOTA_END_WORKGROUPS):
-    """Bytes of device workspace tamtr_hota_update and tamtr_hota_end_sequence need (no GPU call)."""
-    n = _lib.lib().tamtr_hota_workspace_bytes(int(nq), int(ng), int(workgroups))
+def hota_end_workgroups(streams=None):
+    """Workgroups per stream of the matching launch: HOTA_END_WORKGROUPS for one evaluator, min(64, 1024 / S), at least 1, for S."""
+    return HOTA_END_WORKGROUPS if streams is None else max(1, min(HOTA_END_WORKGROUPS, 1024 // streams))
+
+
+def hota_workspace_bytes(nq, ng, workgroups=None, streams=None):
+    """Bytes of device workspace tamtr_hota_update and tamtr_hota_end_sequence need (no GPU call); streams=S: what
+    tamtr_hota_update_streams and tamtr_hota_end_streams need for S stacked states (S slices, each rounded up to 16 bytes).
+    workgroups: per stream, hota_end_workgroups(streams) by default."""
+    S = _check_streams('hota', streams)
+    workgroups = hota_end_workgroups(S) if workgroups is None else int(workgroups)
+    L = _lib.lib()
+    n = L.tamtr_hota_workspace_bytes(int(nq), int(ng), workgroups) if S is None else L.tamtr_hota_streams_workspace_bytes(S, int(nq), int(ng), workgroups)
     if n <= 0:
-        raise _lib.TamtrHipError(f'hota: nq {nq}, ng {ng} with {workgroups} workgroups is outside what the kernel is built for')
+        raise _lib.TamtrHipError(f'hota: nq {nq}, ng {ng} with {workgroups} workgroups' + (f' and {S} streams' if S else '') +
+                                 ' is outside what the kernel is built for')
     return n
 
 
-def hota_update(tracks, tcounts, gt, gcounts, state, nc, caps, iou=0.5, workspace=None):
+def hota_update(tracks, tcounts, gt, gcounts, state, nc, caps, iou=0.5, workspace=None, streams=None, active=None):
     """Steps 1 and 2 of the MOT rule and pass 1 of HOTA (csrc/hota.hip; engine.hota_evaluate is its numpy statement) for the B frames of a
     batch, in order, in one launch.  tracks / tcounts / gt / gcounts as mot_update takes them.  state: a dict of device tensors as
     HOTA_STATE_SPEC lists them, updated in place; caps: (gt identities, track ids, pair slots, log entries, frames).  Every check
-    comes before the launch; no synchronisation."""
+    comes before the launch; no synchronisation.  streams=S and active as in mot_update: every state tensor has a leading S, the
+    workspace is hota_workspace_bytes(nq, ng, 1, streams=S), one workgroup per stream."""
     B, nq, ng, tracks, tcounts, gt, gcounts = _mot_frames('hota_update', tracks, tcounts, gt, gcounts, iou)
-    ptrs, ccaps = _eval_state('hota_update', HOTA_STATE_SPEC, HOTA_CAPS, state, nc, caps)
+    S, active = _eval_streams('hota_update', B, streams, active)
+    ptrs, ccaps = _eval_state('hota_update', HOTA_STATE_SPEC, HOTA_CAPS, state, nc, caps, S)
     require_gpu(tracks, tcounts, gt, gcounts)
-    workspace = _eval_workspace('hota_update', workspace, hota_workspace_bytes(nq, ng, 1), tracks.device)
-    call('tamtr_hota_update', ptr(tracks), ptr(tcounts), ptr(gt), ptr(gcounts), B, nq, ng, int(nc), float(iou), HOTA_EPS, ptrs, ccaps,
-         ptr(workspace), int(workspace.numel()), stream_ptr())
+    workspace = _eval_workspace('hota_update', workspace, hota_workspace_bytes(nq, ng, 1, S), tracks.device)
+    call('tamtr_hota_update_streams', ptr(tracks), ptr(tcounts), ptr(gt), ptr(gcounts), B, S or 1, nq, ng, int(nc), float(iou), HOTA_EPS,
+         ptr(active), ptrs, ccaps, ptr(workspace), int(workspace.numel()), stream_ptr())
 
 
-def hota_end_sequence(state, nc, caps, nq, ng, workspace=None, workgroups=HOTA_END_WORKGROUPS):
+def hota_end_sequence(state, nc, caps, nq, ng, workspace=None, workgroups=None, streams=None, ending=None):
     """Pass 2 of HOTA and the per-sequence reduction in three launches (matching over `workgroups` workgroups, the reduction over the
     pair table, the clearing of the sequence's state); adds to the run totals of `state`.  nq / ng: the widest rows any update of the
-    sequence was given.  No synchronisation."""
-    nq, ng, workgroups = int(nq), int(ng), int(workgroups)
+    sequence was given.  No synchronisation.  streams=S: the same three launches with the stream as a second grid dimension,
+    `workgroups` per stream (hota_end_workgroups(S) by default); ending i32 [S] on the GPU (None: every stream ends) names the streams
+    to reduce, and slice s of a stream whose word is 0 is left untouched."""
+    S = _check_streams('hota_end_sequence', streams)
+    nq, ng, workgroups = int(nq), int(ng), hota_end_workgroups(S) if workgroups is None else int(workgroups)
     if nq < 1 or ng < 1 or workgroups < 1:
         raise _lib.TamtrHipError(f'hota_end_sequence: nq, ng and workgroups must be positive, got {nq}, {ng}, {workgroups}')
-    ptrs, ccaps = _eval_state('hota_end_sequence', HOTA_STATE_SPEC, HOTA_CAPS, state, nc, caps)
-    workspace = _eval_workspace('hota_end_sequence', workspace, hota_workspace_bytes(nq, ng, workgroups), state['hdr'].device)
+    if ending is not None and S is None:
+        raise _lib.TamtrHipError('hota_end_sequence: ending belongs to a stacked evaluator (streams=S)')
+    ending, = _eval_masks('hota_end_sequence', S, ending=ending)
+    ptrs, ccaps = _eval_state('hota_end_sequence', HOTA_STATE_SPEC, HOTA_CAPS, state, nc, caps, S)
+    workspace = _eval_workspace('hota_end_sequence', workspace, hota_workspace_bytes(nq, ng, workgroups, S), state['hdr'].device)
     import numpy as np
     alpha = (ctypes.c_double * 19)(*np.arange(0.05, 0.99, 0.05))   # the thresholds as TrackEval makes them, never k / 20
-    call('tamtr_hota_end_sequence', alpha, HOTA_EPS, int(nc), nq, ng, workgroups, ptrs, ccaps, ptr(workspace), int(workspace.numel()),
-         stream_ptr())
+    call('tamtr_hota_end_streams', alpha, HOTA_EPS, int(nc), S or 1, ptr(ending), nq, ng, workgroups, ptrs, ccaps, ptr(workspace),
+         int(workspace.numel()), stream_ptr())
 
 
 # the track-mAP evaluator's state (csrc/trackmap.hip states it): name, dtype, shape from (nc, caps); caps = (gt identities, track ids,

@@ -215,7 +215,8 @@ class Predictor:
         scores the tracker's rows where they lie; each evaluator's header rides in the same copy and its time goes under its own key
         of times ('mot', 'hota', 'tmap').
         active (track_streams; B host booleans): the images that are padding have their counts set to 0 on the device before the
-        estimator and the tracker see them - such an image reaches neither."""
+        estimator and the tracker see them - such an image reaches neither.  There the evaluators are stacked ones (streams=S) and a
+        gt_frames[i] of None keeps image i out of the score."""
         arr, hw = ims
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
         ev[0].record()
@@ -252,7 +253,7 @@ class Predictor:
                 ev_eval.append(torch.cuda.Event(enable_timing=True))
                 ev_eval[-1].record()
                 e.update(tracks, tcounts, gt_frames)
-                parts.append(e.state['hdr'].view(torch.float32))
+                parts.append(e.state['hdr'].view(torch.float32).view(-1))
         ev[4].record()
         packed = torch.cat(parts)
         host = torch.empty(packed.shape, dtype=torch.float32, pin_memory=True)
@@ -322,7 +323,7 @@ class Predictor:
         else:
             yield from self._track(files, gt, evaluator)
 
-    def track_streams(self, sources, tracker=None, frames_per_stream=1, persist=False):
+    def track_streams(self, sources, tracker=None, frames_per_stream=1, persist=False, gt=None, evaluator=None):
         """S sequences at once, one tracker per sequence (the reference's model.track on a batch of streams, trackers/track.py:33-53):
         `sources` is a list of S sources - each a directory, a list file or a list of paths, each a sequence of its own.  Every
         batch holds `frames_per_stream` frames of every stream, frame-major (stream_batches), and gets one forward, one
@@ -331,14 +332,29 @@ class Predictor:
         the longest stream ends; a stream that has ended keeps its place in the batch as padding, which reaches neither the tracker
         nor the estimator and is never yielded.  tracker: a yaml path, None for ByteTrack's defaults, or a track.ByteTracker /
         track.BotSort built with streams=len(sources) (any other `streams` raises ValueError); persist as in track().  BoT-SORT's
-        camera-motion estimate and ReID work as in track(), per stream.  Evaluators are not taken here: each of them holds one
-        sequence's state (score the files of write_mot with tools/mot_eval.py).  The arguments are checked when this is called,
-        before the first frame is asked for."""
+        camera-motion estimate and ReID work as in track(), per stream.
+        gt + evaluator: `gt` is a list of S entries, each the sequence's per-frame arrays as track() takes them or None for "do not
+        score this stream"; `evaluator` is a track.MotEvaluator and / or track.HotaEvaluator built with streams=S, or a list of them
+        (anything else raises ValueError: another S, an evaluator without streams, a TrackMapEvaluator, which holds one sequence).
+        Every batch's rows are then scored on the device right after the tracker's launch, one launch per evaluator with one
+        workgroup per stream; the evaluators' headers ride in the batch's one device-to-host copy and speed() has an entry per
+        evaluator ('mot', 'hota').  A stream is ended right after the batch that holds its last frame, all streams ending there in
+        one call; stream_counts(s) and results() then hold the metrics.  Without both, nothing changes.
+        The arguments are checked when this is called, before the first frame is asked for."""
         from .track import ByteTracker, tracker_from_yaml
         sources = list(sources) if isinstance(sources, (list, tuple)) else None
         if not sources:
             raise ValueError('track_streams needs a non-empty list of sources, one per stream')
         S = len(sources)
+        evaluators = list(evaluator) if isinstance(evaluator, (list, tuple)) else [] if evaluator is None else [evaluator]
+        for e in evaluators:
+            if getattr(e, 'times_key', None) not in ('mot', 'hota') or getattr(e, 'streams', None) != S:
+                raise ValueError(f'track_streams scores {S} sources with a MotEvaluator / HotaEvaluator built with streams={S}, got '
+                                 f'{type(e).__name__} with streams={getattr(e, "streams", None)!r} (a TrackMapEvaluator holds one sequence)')
+        if gt is not None:
+            gt = list(gt) if isinstance(gt, (list, tuple)) else None
+            if gt is None or len(gt) != S:
+                raise ValueError(f'gt must be a list of {S} entries, one per source (per-frame arrays, or None for a stream that is not scored)')
         if isinstance(tracker, ByteTracker):
             if tracker.streams != S:
                 raise ValueError(f'the tracker was built with streams={tracker.streams!r}, {S} sources need streams={S}')
@@ -348,13 +364,21 @@ class Predictor:
         elif not (persist and isinstance(self.tracker, ByteTracker) and self.tracker.streams == S):
             head = self.model.model[-1]
             self.tracker = tracker_from_yaml(tracker, self.device, reid_dim=head.hidden_dim, streams=S) if tracker else ByteTracker(self.device, streams=S)
-        batches = stream_batches([list_sources(src) for src in sources], frames_per_stream)
-        for k in ('mot', 'hota', 'tmap') + (('gmc',) if getattr(self.tracker, 'gmc_method', None) != 'sparseOptFlow' else ()):
+        files = [list_sources(src) for src in sources]
+        batches = stream_batches(files, frames_per_stream)
+        scoring = gt is not None and bool(evaluators)
+        for k in {'mot', 'hota', 'tmap'} - ({e.times_key for e in evaluators} if scoring else set()):
             self.times.pop(k, None)
-        frames = self._run_streams(batches, S)
+        if getattr(self.tracker, 'gmc_method', None) != 'sparseOptFlow':
+            self.times.pop('gmc', None)
+        score = None
+        if scoring:      # per stream: its frames' ground truth (missing frames are empty), or None for a stream that is not scored
+            empty = np.zeros((0, 7), np.float32)
+            score = ([None if g is None else (list(g)[:len(f)] + [empty] * (len(f) - len(g))) for g, f in zip(gt, files)], evaluators)
+        frames = self._run_streams(batches, S, int(frames_per_stream), score)
         return self._with_query_embed(frames) if getattr(self.tracker, 'with_reid', False) else frames
 
-    def _run_streams(self, batches, S):
+    def _run_streams(self, batches, S, F=1, score=None):
         with ThreadPoolExecutor(max_workers=self.workers) as pool:
             def submit(paths):      # a padding entry shares its path's load
                 jobs = {f: pool.submit(load_image, f, self.imgsz) for f in dict.fromkeys(paths)}
@@ -367,7 +391,15 @@ class Predictor:
                 pending = submit(batches[k + 1][0]) if k + 1 < len(batches) else []
                 origs = [o for o, _ in loaded]
                 hw = [o.shape[:2] for o in origs]
-                res = self.run_batch((np.stack([r for _, r in loaded]), hw), self.tracker, active=active)
+                if score is None:
+                    res = self.run_batch((np.stack([r for _, r in loaded]), hw), self.tracker, active=active)
+                else:      # image f * S + s is frame k * F + f of stream s; padding and unscored streams are no frames to the evaluators
+                    gts, evaluators = score
+                    frames = [gts[i % S][k * F + i // S] if active[i] and gts[i % S] is not None else None for i in range(len(paths))]
+                    res = self.run_batch((np.stack([r for _, r in loaded]), hw), self.tracker, frames, evaluators, active=active)
+                    ending = [s for s, g in enumerate(gts) if g and (len(g) - 1) // F == k]
+                    for e in evaluators if ending else []:
+                        e.end_sequence(ending)
                 out, counts = res[0], res[2]
                 self.seen += sum(active)
                 for i, path in enumerate(paths):

@@ -42,6 +42,16 @@ numpy): one more launch per batch on the rows the tracker left on the device, on
 
 HotaEvaluator has the same methods and scores the same rows by HOTA (the rule is written out in csrc/hota.hip, engine.hota_evaluate
 states it in numpy): one launch per batch, three per sequence.  `Predictor.track(..., evaluator=[mot, hota])` feeds both.
+
+Several streams scored at once, next to the stacked trackers: streams=S keeps one evaluator state per stream in stacked tensors, and
+the update is still one launch per batch, one workgroup per stream, on the tracker's frame-major rows.
+
+    ev = MotEvaluator(device, nc, streams=4)            # HotaEvaluator(device, nc, streams=4)
+    ev.update(tracks, tcounts, gt_frames)               # gt_frames[f * 4 + s]: frame f of stream s, or None for "not a frame"
+    ev.end_sequence([1, 3])                             # streams 1 and 3 end, in one launch set; None ends every open stream
+    ev.stream_counts(1), ev.counts(), ev.results()      # one stream's totals; the run's totals over all streams
+
+`Predictor.track_streams(sources, gt=[...], evaluator=[mot, hota])` drives them; tools/mot_eval.py --streams S scores result files so.
 """
 import numpy as np
 import torch
@@ -370,14 +380,40 @@ VISDRONE_CATEGORIES = {0: (0, 2), **{c: (c - 1, 0) for c in range(1, 11)}, 11: (
 HDR_OVER_FRAME = ('gt identities beyond gt_capacity', 'track ids beyond track_capacity', 'rows beyond ng / nq per frame')
 
 
+def pack_gt(gt_frames, ng, nc, rows):
+    """The ground truth of a batch as one host buffer, pure numpy: B host arrays [m, 7] (or None) -> f32 [B * ng * 7 + 2 B]: the rows
+    gt [B, ng, 7], then the counts and the active words as i32 [B] each (view the tail as int32).  rows: one (class, id) -> dense row
+    map per stream, updated in place; image i belongs to stream i % len(rows) (frame-major), and the identities of its kind-0 rows are
+    replaced by their dense rows, handed out per stream in order of appearance.  None marks an image that is no frame of its stream:
+    active word 0, count 0, no row handed out.  Rows beyond ng are left out and the true count is kept (the device counts them)."""
+    B, S = len(gt_frames), len(rows)
+    n = B * ng * 7
+    buf = np.zeros(n + 2 * B, np.float32)
+    gt, cnt, act = buf[:n].reshape(B, ng, 7), buf[n:n + B].view(np.int32), buf[n + B:].view(np.int32)
+    for b, g in enumerate(gt_frames):
+        if g is None:
+            continue
+        g = np.array(g, np.float32).reshape(-1, 7)
+        table = rows[b % S]
+        for i in np.flatnonzero((g[:, 6] == 0) & (g[:, 5] >= 0) & (g[:, 5] < nc)):
+            g[i, 4] = table.setdefault((int(g[i, 5]), int(g[i, 4])), len(table))
+        cnt[b], act[b] = len(g), 1
+        gt[b, :min(len(g), ng)] = g[:ng]
+    return buf
+
+
 class _SequenceEvaluator:
     """What the tracking evaluators share: the state on `device`, the ground truth's way up, one update launch per batch and the
     bookkeeping of the sequence in progress.  A subclass names its host path, its state spec and capacities in ops, the offset of its
     overflow counters in hdr with what each counts and the exception they raise, and supplies _ws_bytes, _launch_update and
-    _launch_end."""
+    _launch_end.
+    streams=S (MotEvaluator and HotaEvaluator): one evaluator state per stream, stacked - every state tensor gains a leading S, `rows`
+    and `open` are lists with an entry per stream - and still one update launch per batch, one workgroup per stream.  update() then
+    takes the frame-major batch (image f * S + s is the f-th frame of stream s, as ByteTracker(streams=S) leaves it)."""
     host = spec = cap_names = hdr_over = over = overflow = None
 
-    def __init__(self, device, nc, iou, caps, nq, ng):
+    def __init__(self, device, nc, iou, caps, nq, ng, streams=None):
+        self.streams = check_streams(streams)
         self.device = torch.device(device)
         if self.device.type != 'cuda':
             raise ops._lib.TamtrHipError(f'{type(self).__name__} needs an MI355X; engine.{self.host} is the host path')
@@ -387,61 +423,144 @@ class _SequenceEvaluator:
         if min(self.nc, self.nq, self.ng, *self.caps) < 1:
             raise ValueError('nc, the capacities, nq and ng must be positive')
         self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
-        self.state = {k: torch.zeros(shape(self.nc, self.caps), device=self.device, dtype=dt) for k, dt, shape in self.spec}
-        self.rows, self.open = {}, False
+        self.state = {k: torch.zeros(self._lead + shape(self.nc, self.caps), device=self.device, dtype=dt) for k, dt, shape in self.spec}
+        self._fresh()
 
-    def reset(self):
-        """Forget every count and the sequence in progress.  No synchronisation."""
+    @property
+    def _lead(self):
+        """The leading dimension of every state tensor: none for one evaluator, (S,) for a stack."""
+        return () if self.streams is None else (self.streams,)
+
+    def _fresh(self):
+        self.rows, self.open = ({}, False) if self.streams is None else ([{} for _ in range(self.streams)], [False] * self.streams)
+
+    def _stream(self, stream):
+        if self.streams is None or isinstance(stream, bool) or not isinstance(stream, (int, np.integer)) or not 0 <= stream < self.streams:
+            raise ValueError(f'stream must be in 0 .. {self.streams - 1}, got {stream!r}' if self.streams else
+                             f'stream={stream!r} was given to an evaluator built without streams')
+        return int(stream)
+
+    def reset(self, stream=None):
+        """Forget every count and the sequence in progress (stream=s: stream s's alone).  No synchronisation."""
+        if stream is None:
+            for v in self.state.values():
+                v.zero_()
+            self._fresh()
+            return
+        s = self._stream(stream)
         for v in self.state.values():
-            v.zero_()
-        self.rows, self.open = {}, False
+            v[s].zero_()
+        self.rows[s], self.open[s] = {}, False
+
+    def stream_state(self, s):
+        """Stream s's state as views state[k][s]: contiguous, so the single-evaluator ops take them as they are."""
+        s = self._stream(s)
+        return {k: v[s] for k, v in self.state.items()}
 
     def upload(self, gt_frames):
-        """B host arrays [m, 7] -> gt f32 [B, ng, 7] and gcounts i32 [B] on the device, in one copy; the ground-truth identities
-        (class, id) of the kind-0 rows are replaced by their dense rows, handed out in order of appearance."""
+        """B host arrays [m, 7] -> gt f32 [B, ng, 7] and gcounts i32 [B] on the device, in one pinned copy (pack_gt makes the buffer);
+        the ground-truth identities (class, id) of the kind-0 rows are replaced by their dense rows, handed out in order of
+        appearance.  With streams=S the batch is frame-major, the rows are handed out per stream, None marks an image that is no
+        frame of its stream, and the active words i32 [B] come third."""
+        if self.streams is None and any(g is None for g in gt_frames):
+            raise ValueError('a ground-truth frame of None (not a frame) belongs to an evaluator built with streams=S')
         B, ng = len(gt_frames), self.ng
         n = B * ng * 7
-        buf = np.zeros(n + B, np.float32)
-        gt, cnt = buf[:n].reshape(B, ng, 7), buf[n:].view(np.int32)
-        for b, g in enumerate(gt_frames):
-            g = np.array(g, np.float32).reshape(-1, 7)
-            for i in np.flatnonzero((g[:, 6] == 0) & (g[:, 5] >= 0) & (g[:, 5] < self.nc)):
-                g[i, 4] = self.rows.setdefault((int(g[i, 5]), int(g[i, 4])), len(self.rows))
-            cnt[b] = len(g)
-            gt[b, :min(len(g), ng)] = g[:ng]
+        buf = pack_gt(gt_frames, ng, self.nc, [self.rows] if self.streams is None else self.rows)
         dev = torch.from_numpy(buf).pin_memory().to(self.device, non_blocking=True)
-        return dev[:n].view(B, ng, 7), dev[n:].view(torch.int32)
+        gt, words = dev[:n].view(B, ng, 7), dev[n:].view(torch.int32)
+        return (gt, words[:B]) if self.streams is None else (gt, words[:B], words[B:])
 
     def update(self, tracks, tcounts, gt_frames):
         """tracks f32 [B, nq, 8], tcounts i32 [B] on the device (ByteTracker.update); gt_frames: B host arrays [m, 7] x1 y1 x2 y2 id
-        cls kind.  The ground truth goes up in one copy (upload), one launch follows; nothing synchronises."""
+        cls kind.  The ground truth goes up in one copy (upload), one launch follows; nothing synchronises.  With streams=S the batch
+        is frame-major and a gt_frames[i] of None marks image i as no frame of its stream (padding after its end, or a stream that
+        is not scored): it counts nothing and its rows are not read."""
         B = tracks.shape[0]
         if len(gt_frames) != B:
             raise ValueError(f'{len(gt_frames)} ground-truth frames for a batch of {B}')
+        if self.streams is not None and B % self.streams:
+            raise ValueError(f'a batch of {B} images is no multiple of streams = {self.streams} (frame-major: image f * S + s)')
         if tracks.shape[1] > self.nq:
             self.nq = int(tracks.shape[1])
             self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
-        gt, gcounts = self.upload(gt_frames)
-        self._launch_update(tracks, tcounts, gt, gcounts)
-        self.open = True
+        self._launch_update(tracks, tcounts, *self.upload(gt_frames))
+        if self.streams is None:
+            self.open = True
+        else:
+            for i, g in enumerate(gt_frames):
+                if g is not None:
+                    self.open[i % self.streams] = True
 
-    def end_sequence(self):
+    def end_sequence(self, streams=None):
         """Reduce the sequence in progress (the class states the launches) and start a new one: ground-truth ids may be used again.
-        No synchronisation."""
-        self._launch_end()
-        self.rows, self.open = {}, False
+        No synchronisation.  With streams=S: None ends every open stream, an iterable of stream indices ends those - in one launch
+        set either way, the others' state is untouched - and the ground-truth ids of an ended stream may be used again."""
+        if self.streams is None:
+            if streams is not None:
+                raise ValueError(f'streams={streams!r} was given to an evaluator built without streams')
+            self._launch_end()
+            self.rows, self.open = {}, False
+            return
+        ending = [s for s in range(self.streams) if self.open[s]] if streams is None else sorted({self._stream(s) for s in streams})
+        if not ending:
+            return
+        words = np.zeros((2, self.streams), np.int32)      # ending, then the dense rows handed out
+        words[0, ending] = 1
+        words[1] = [len(r) for r in self.rows]
+        dev = torch.from_numpy(words).pin_memory().to(self.device, non_blocking=True)
+        self._launch_end(dev[0], dev[1])
+        for s in ending:
+            self.rows[s], self.open[s] = {}, False
 
-    def check_overflow(self, hdr):
-        """Raise when the header (read by the caller, e.g. from the predictor's packed copy) counts anything beyond a capacity."""
-        over = [(int(hdr[self.hdr_over + i]), what) for i, what in enumerate(self.over)]
-        if any(n for n, _ in over):
-            raise self.overflow('; '.join(f'{n} {what}' for n, what in over if n) + f' were left out (capacities '
-                                f'{", ".join(self.cap_names)} = {self.caps}, ng {self.ng}, nq {self.nq}): build the evaluator with larger '
-                                'capacities')
+    def check_overflow(self, hdr, stream=None):
+        """Raise when the header (read by the caller, e.g. from the predictor's packed copy) counts anything beyond a capacity.  With
+        streams=S it is the stacked header [S, n] (flat or not), or stream `stream`'s own row, and the message names the streams that
+        overflowed."""
+        hdr = np.asarray(hdr).reshape(1 if self.streams is None or stream is not None else self.streams, -1)
+        said = []
+        for s, h in enumerate(hdr, stream or 0):
+            over = [(int(h[self.hdr_over + i]), what) for i, what in enumerate(self.over)]
+            if any(n for n, _ in over):
+                said.append(('' if self.streams is None else f'stream {s}: ') + '; '.join(f'{n} {what}' for n, what in over if n))
+        if said:
+            raise self.overflow(' | '.join(said) + f' were left out (capacities {", ".join(self.cap_names)} = {self.caps}' +
+                                ('' if self.streams is None else ' per stream') + f', ng {self.ng}, nq {self.nq}): build the evaluator with '
+                                'larger capacities')
 
-    def _ended(self):
-        if self.open:
+    def _ended(self, stream=None):
+        if self.open if self.streams is None else (any(self.open) if stream is None else self.open[stream]):
             raise RuntimeError('a sequence is in progress: call end_sequence() before reading the results')
+
+    def _host_state(self, keys, stream=None):
+        """The named state tensors on the host as [S', ...] arrays (synchronises): every stream's, or stream `stream`'s alone (S' = 1)."""
+        if stream is not None:
+            stream = self._stream(stream)
+        self._ended(stream)
+        out = []
+        for k in keys:
+            a = self.state[k] if self.streams is None else self.state[k] if stream is None else self.state[k][stream]
+            out.append(a.cpu().numpy().reshape((-1,) + tuple(self.state[k].shape[len(self._lead):])))
+        return out
+
+    def _run_counts(self, stream=None):
+        """The totals as the host path's counts: per stream, then added in stream order (integers exactly, fp64 sums one add each)."""
+        arrays = self._host_state(self.count_keys, stream)
+        self.check_overflow(arrays[-1], stream)
+        per = [self._counts_of(*(a[s] for a in arrays[:-1])) for s in range(len(arrays[0]))]
+        out = per[0]
+        for c in per[1:]:
+            out = {k: out[k] + c[k] for k in out}
+        return out
+
+    def counts(self):
+        """The run's counts as the host path returns them (synchronises; raises on overflow); with streams=S the totals of all
+        streams."""
+        return self._run_counts()
+
+    def stream_counts(self, s):
+        """Stream s's totals in the form of counts() (synchronises); a caller gets per-sequence numbers by differencing."""
+        return self._run_counts(self._stream(s))
 
 
 class MotEvaluator(_SequenceEvaluator):
@@ -453,25 +572,25 @@ class MotEvaluator(_SequenceEvaluator):
     host, spec, cap_names = 'mot_evaluate', ops.MOT_STATE_SPEC, ops.MOT_CAPS
     hdr_over, over, overflow = MOT_HDR_OVER_GT, HDR_OVER_FRAME, MotOverflow
 
-    def __init__(self, device, nc, iou=0.5, gt_capacity=1024, track_capacity=4096, nq=300, ng=300):
-        super().__init__(device, nc, iou, (gt_capacity, track_capacity), nq, ng)
+    count_keys = ('counts', 'iou_sum', 'hdr')
+
+    def __init__(self, device, nc, iou=0.5, gt_capacity=1024, track_capacity=4096, nq=300, ng=300, streams=None):
+        super().__init__(device, nc, iou, (gt_capacity, track_capacity), nq, ng, streams)
         self.track_capacity = self.caps[1]
 
     def _ws_bytes(self):
-        return ops.mot_workspace_bytes(self.nq, self.ng, self.nc, *self.caps)
+        return ops.mot_workspace_bytes(self.nq, self.ng, self.nc, *self.caps, *self._lead)
 
-    def _launch_update(self, tracks, tcounts, gt, gcounts):
-        ops.mot_update(tracks, tcounts, gt, gcounts, self.state, self.nc, *self.caps, self.iou, self.workspace)
+    def _launch_update(self, tracks, tcounts, gt, gcounts, active=None):
+        ops.mot_update(tracks, tcounts, gt, gcounts, self.state, self.nc, *self.caps, self.iou, self.workspace, self.streams, active)
 
-    def _launch_end(self):
-        ops.mot_end_sequence(self.state, self.nc, *self.caps, len(self.rows), self.workspace)
+    def _launch_end(self, ending=None, gt_used=None):
+        ops.mot_end_sequence(self.state, self.nc, *self.caps, len(self.rows) if self.streams is None else gt_used, self.workspace,
+                             self.streams, ending)
 
-    def counts(self):
-        """The run's counts as engine.mot_evaluate returns them (synchronises; raises MotOverflow)."""
+    def _counts_of(self, c, s):
+        """One state's totals as engine.mot_evaluate returns them."""
         from .engine import MOT_COUNT_KEYS
-        self._ended()
-        c, s, hdr = (self.state[k].cpu().numpy() for k in ('counts', 'iou_sum', 'hdr'))
-        self.check_overflow(hdr)
         out = {k: c[:, i].astype(np.int64) for i, k in enumerate(MOT_COUNT_KEYS)}
         out['iou_sum'] = s.copy()
         return out
@@ -498,24 +617,23 @@ class HotaEvaluator(_SequenceEvaluator):
     host, spec, cap_names = 'hota_evaluate', ops.HOTA_STATE_SPEC, ops.HOTA_CAPS
     hdr_over, over, overflow = 2, HOTA_HDR_OVER, HotaOverflow
 
+    count_keys = ('dets', 'tp_lvl', 'loc_lvl', 'ass', 'hdr')
+
     def __init__(self, device, nc, iou=0.5, gt_capacity=1024, track_capacity=4096, pair_capacity=1 << 18, log_capacity=1 << 20,
-                 frame_capacity=4096, nq=300, ng=300):
-        super().__init__(device, nc, iou, (gt_capacity, track_capacity, pair_capacity, log_capacity, frame_capacity), nq, ng)
+                 frame_capacity=4096, nq=300, ng=300, streams=None):
+        super().__init__(device, nc, iou, (gt_capacity, track_capacity, pair_capacity, log_capacity, frame_capacity), nq, ng, streams)
 
     def _ws_bytes(self):
-        return ops.hota_workspace_bytes(self.nq, self.ng)
+        return ops.hota_workspace_bytes(self.nq, self.ng, streams=self.streams)
 
-    def _launch_update(self, tracks, tcounts, gt, gcounts):
-        ops.hota_update(tracks, tcounts, gt, gcounts, self.state, self.nc, self.caps, self.iou, self.workspace)
+    def _launch_update(self, tracks, tcounts, gt, gcounts, active=None):
+        ops.hota_update(tracks, tcounts, gt, gcounts, self.state, self.nc, self.caps, self.iou, self.workspace, self.streams, active)
 
-    def _launch_end(self):
-        ops.hota_end_sequence(self.state, self.nc, self.caps, self.nq, self.ng, self.workspace)
+    def _launch_end(self, ending=None, gt_used=None):
+        ops.hota_end_sequence(self.state, self.nc, self.caps, self.nq, self.ng, self.workspace, streams=self.streams, ending=ending)
 
-    def counts(self):
-        """The run's counts as engine.hota_evaluate returns them (synchronises; raises HotaOverflow)."""
-        self._ended()
-        dets, tp, loc, ass, hdr = (self.state[k].cpu().numpy() for k in ('dets', 'tp_lvl', 'loc_lvl', 'ass', 'hdr'))
-        self.check_overflow(hdr)
+    def _counts_of(self, dets, tp, loc, ass):
+        """One state's totals as engine.hota_evaluate returns them."""
         above = lambda lvl: np.cumsum(lvl[:, ::-1], 1)[:, ::-1][:, 1:]   # noqa: E731  a pair at level k counts for every threshold a < k
         out = {'TP': above(tp.astype(np.int64)), 'loc_sum': above(loc), 'ass_sum': ass[0].copy(), 'assre_sum': ass[1].copy(),
                'asspr_sum': ass[2].copy(), 'gt_dets': dets[:, 0].astype(np.int64), 'trk_dets': dets[:, 1].astype(np.int64)}

@@ -31,8 +31,13 @@
   (f) --track-map: the track-mAP launches on the same sequence with a seeded score per row: the update launch per batch next to the
       HOTA update launch, the six end-of-sequence launches, the run's accumulation, and the host path (the batches' copies plus
       engine.track_map_evaluate).
+  (d*) --mot --streams S / --hota --streams S: the sequence of (d) in S copies with different seeds, scored by ONE stacked update
+      launch per batch (one workgroup per stream, tamtr_mot_update_streams / tamtr_hota_update_streams) next to S single-evaluator
+      launches in sequence on the same rows, and the end of the S sequences likewise; ms per launch, and the two forms' counts
+      compared stream by stream.
 
-    python tools/predict_bench.py [--images 64] [--kernel-only] [--track [--botsort [--reid]] [--streams S]] [--gmc] [--mot] [--hota] [--track-map]
+    python tools/predict_bench.py [--images 64] [--kernel-only] [--track [--botsort [--reid]] [--streams S]] [--gmc] [--mot [--streams S]]
+                                  [--hota [--streams S]] [--track-map]
 --kernel-only runs only the kernel loop of (a), for a `rocprofv3 --kernel-trace --stats` run of its own.
 """
 import argparse
@@ -566,6 +571,78 @@ def bench_hota(frames=200, B=4, nq=300, nc=10, repeats=7):
             'host_ms_per_batch': round(float(np.median(t_host)) / n_batches, 3), 'passes_timed': repeats}
 
 
+def bench_eval_streams(kind, S, frames=200, F=4, nq=300, nc=10, rounds=7):
+    """-> one row: ONE stacked update launch for S streams (tamtr_<kind>_update_streams: F frames of every stream, one workgroup per
+    stream) next to the S single-evaluator launches that score the same streams one after another, on mot_scene in S copies with
+    different seeds; likewise the end of the S sequences (one launch set with the stream as a grid dimension next to S in sequence).
+    The ground truth is uploaded once, before anything is timed, so the rows are the same for both forms and every timed span holds
+    launches only.  A pass is all the update launches of the sequences between device events, then their end between two more; the
+    two forms take turns `rounds` times after a warm-up pass of each: median and 10th / 90th percentile, per launch.  The two forms
+    must count the same."""
+    from tamtr_amd import ops
+    from tamtr_amd.track import HotaEvaluator, MotEvaluator, pack_track_rows
+    make = MotEvaluator if kind == 'mot' else HotaEvaluator
+    scenes = [mot_scene(frames, nc=nc, seed=2 + s) for s in range(S)]
+    stack = make('cuda', nc, nq=nq, ng=300, streams=S)
+    singles = [make('cuda', nc, nq=nq, ng=300) for _ in range(S)]
+    starts = range(0, frames, F)
+    # frame-major batches for the stack, one contiguous sequence per stream for the single evaluators
+    fm = [pack_track_rows([scenes[s][f][1] for f in range(i, min(i + F, frames)) for s in range(S)], nq, 'cuda') + stack.upload(
+        [scenes[s][f][0] for f in range(i, min(i + F, frames)) for s in range(S)]) for i in starts]
+    per = [[pack_track_rows([t for _, t in scenes[s][i:i + F]], nq, 'cuda') + ev.upload([g for g, _ in scenes[s][i:i + F]]) for i in starts]
+           for s, ev in enumerate(singles)]
+    gt_used = torch.tensor([len(r) for r in stack.rows], dtype=torch.int32).cuda()
+    assert [len(r) for r in stack.rows] == [len(ev.rows) for ev in singles]
+
+    def update(ev, tracks, tc, gt, gc, active=None):
+        if kind == 'mot':
+            ops.mot_update(tracks, tc, gt, gc, ev.state, nc, *ev.caps, ev.iou, ev.workspace, ev.streams, active)
+        else:
+            ops.hota_update(tracks, tc, gt, gc, ev.state, nc, ev.caps, ev.iou, ev.workspace, ev.streams, active)
+
+    def end(ev):
+        used = gt_used if ev.streams else len(ev.rows)
+        if kind == 'mot':
+            ops.mot_end_sequence(ev.state, nc, *ev.caps, used, ev.workspace, ev.streams)
+        else:
+            ops.hota_end_sequence(ev.state, nc, ev.caps, ev.nq, ev.ng, ev.workspace, streams=ev.streams)
+
+    def one(evs, batches_of):
+        for ev in evs:
+            for v in ev.state.values():
+                v.zero_()
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record()
+        for k in range(len(starts)):
+            for j, ev in enumerate(evs):
+                update(ev, *batches_of[j][k])
+        e[1].record()
+        for ev in evs:
+            end(ev)
+        e[2].record()
+        e[2].synchronize()
+        return e[0].elapsed_time(e[1]) / len(starts), e[1].elapsed_time(e[2])
+
+    one([stack], [fm]), one(singles, per)
+    t_stack, t_seq = [], []
+    for _ in range(rounds):
+        t_stack.append(one([stack], [fm]))
+        t_seq.append(one(singles, per))
+    ints =[k for k, v in singles[0].counts().items() if v.dtype.kind == 'i']
+    for s, ev in enumerate(singles):
+        a, b = stack.stream_counts(s), ev.counts()
+        assert all(np.array_equal(a[k], b[k]) if k in ints else np.allclose(a[k], b[k], rtol=1e-9, atol=0) for k in b), f'stream {s} counted differently'
+    pct = lambda v: [round(float(x), 4) for x in np.percentile(v, [50, 10, 90])]   # noqa: E731
+    up_stack, up_seq = [u for u, _ in t_stack], [u for u, _ in t_seq]
+    return {'evaluator': kind, 'streams': S, 'frames_per_stream_per_launch': F, 'frames': frames, 'nq': nq, 'nc': nc,
+            'gt_rows_per_frame': round(float(np.mean([len(g) for sc in scenes for g, _ in sc])), 1),
+            'track_rows_per_frame': round(float(np.mean([len(t) for sc in scenes for _, t in sc])), 1), 'same_counts_per_stream': True,
+            'stacked_update_launch_ms_p50_p10_p90': pct(up_stack), 'sequential_single_update_launches_ms_p50_p10_p90': pct(up_seq),
+            'update_sequential_over_stacked': round(float(np.median(up_seq) / np.median(up_stack)), 2),
+            'stacked_end_ms_p50_p10_p90': pct([x for _, x in t_stack]), 'sequential_single_ends_ms_p50_p10_p90': pct([x for _, x in t_seq]),
+            'rounds': rounds}
+
+
 def bench_trackmap(frames=200, B=4, nq=300, nc=10, repeats=7):
     """The track-mAP launches on bench_mot's sequence with a seeded score per row: the update launch per batch (alone, and as
     TrackMapEvaluator.update runs it with the ground truth's upload), the HOTA update launch on the same batches as the yardstick (it
@@ -656,7 +733,8 @@ def main():
     ap.add_argument('--track', action='store_true', help='only (c): the tracker launch against copy + numpy twin')
     ap.add_argument('--botsort', action='store_true', help='with --track: the BoT-SORT form of the launch, with warps on the device')
     ap.add_argument('--streams', type=int, help='with --track [--botsort]: S streams in one stacked launch (one workgroup per stream) next to S '
-                    'single-tracker launches in sequence, on S copies of the scenes with different seeds')
+                    'single-tracker launches in sequence, on S copies of the scenes with different seeds; with --mot or --hota: the same for '
+                    'the stacked evaluator launches')
     ap.add_argument('--reid', action='store_true', help='with --track --botsort: the ReID launch and the feature gather next to the plain BoT-SORT '
                     'launch on the same scene, D = 256')
     ap.add_argument('--gmc', action='store_true', help="only (c'): BoT-SORT's camera-motion estimate and tracker launch on a 640 x 640 sequence")
@@ -668,8 +746,14 @@ def main():
     import tamtr_amd  # noqa: F401
     assert torch.cuda.is_available(), 'predict_bench needs an MI355X'
     print(torch.cuda.get_device_name(0), 'torch', torch.__version__)
-    if args.streams is not None and (not args.track or args.streams < 1 or args.reid):
-        ap.error('--streams S (S >= 1) goes with --track [--botsort]')
+    if args.streams is not None and (not (args.track or args.mot or args.hota) or args.streams < 1 or args.reid):
+        ap.error('--streams S (S >= 1) goes with --track [--botsort], --mot or --hota')
+    if (args.mot or args.hota) and args.streams:
+        kind = 'mot' if args.mot else 'hota'
+        print(f'(d*) {args.streams} streams: one stacked {kind} update launch per 4 frames of every stream vs {args.streams} single-evaluator launches '
+              'in sequence, and the end of the sequences likewise (device events around whole passes, taken in turn)')
+        print(json.dumps(bench_eval_streams(kind, args.streams)))
+        return
     if args.track and args.streams:
         print(f'(c*) {args.streams} streams: one stacked launch per 4 frames of every stream vs {args.streams} single-tracker launches in sequence '
               '(device events around whole passes, taken in turn)')

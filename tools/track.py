@@ -22,8 +22,8 @@ and compared on the device; how well those embeddings tell identities apart with
 a sequence without a file there is tracked but not scored.
 --streams S tracks the sequence directories S at a time, as S streams of one batch (Predictor.track_streams: one forward and one
 tracker launch, one workgroup per stream, for --batch frames of every stream); the files written are the same per-sequence ones.
---gt does not go with it - every evaluator holds one sequence's state: write the tracks with --save-mot and score them with
-tools/mot_eval.py.
+--gt does not go with it here: write the tracks with --save-mot and score them with tools/mot_eval.py --streams S, which stacks the
+evaluators the same way (Predictor.track_streams takes gt and stacked evaluators itself).
 """
 import argparse
 import json
@@ -80,8 +80,8 @@ def parse_args(argv=None):
     if args.streams is not None and args.streams < 1:
         ap.error('--streams must be positive')
     if args.streams is not None and args.gt:
-        ap.error('--gt does not go with --streams (an evaluator holds one sequence\'s state): write the tracks with --save-mot and score '
-                 'them with tools/mot_eval.py')
+        ap.error('--gt does not go with --streams here: write the tracks with --save-mot and score them S sequences at a time with '
+                 'tools/mot_eval.py --streams S')
     return args
 
 
