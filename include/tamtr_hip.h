@@ -410,6 +410,19 @@ int tamtr_bncl2_act_bwd(const void* gy, long long ldgy, const void* x1, const vo
                         float* ggamma2, float* gbeta2, float* partials, long long N, int C, int act, int dtype, void* stream);
 int tamtr_bncl_act_bwd(const void* gy, long long ldgy, const void* x, const float* gamma, const float* beta, const float* mean_rstd,
                        void* gx, float* ggamma, float* gbeta, float* partials, long long N, int C, int act, int dtype, void* stream);
+/*      tamtr_bncl_act_down2_*: y = act(bn(x))[:, ::2, ::2] - a Conv whose only consumer is a nearest x0.5 resample (TAMTR.yaml layers 13-14,
+ *      21-22, 29-30).  x, gx (T) [B, H, W, C] channels-last, H and W even; y, gy (T) [B, H/2, W/2, C] (gy with row pitch ldgy).  The batch
+ *      statistics, mean_rstd and the running update are those of tamtr_bncl_act_fwd over all N = B * H * W rows; the apply pass and the
+ *      backward reduction read the kept pixels only, and gx is written at every pixel.  The backward sums (hence ggamma, gbeta, gx) have the
+ *      bits tamtr_bncl_act_bwd gives for gy scattered into a zero full map.  partials: C * S * 3 floats forward, C * S * 2 + 2 * C floats
+ *      backward, S = tamtr_bncl_blocks(N, C, dtype).
+ */
+int tamtr_bncl_act_down2_fwd(const void* x, const float* gamma, const float* beta, float* running_mean, float* running_var, void* y,
+                             float* mean_rstd, float* partials, int B, int H, int W, int C, float eps, float momentum, int act, int dtype,
+                             void* stream);
+int tamtr_bncl_act_down2_bwd(const void* gy, long long ldgy, const void* x, const float* gamma, const float* beta, const float* mean_rstd,
+                             void* gx, float* ggamma, float* gbeta, float* partials, int B, int H, int W, int C, int act, int dtype,
+                             void* stream);
 
 /* ---- layout: NCHW <-> NHWC repacking of a feature map (tiled transpose through LDS).  The trunk runs channels-last around
  *      MIOpen's NHWC convolutions; the gate (a-1) and CPAM (next-3) kernels read NCHW planes.  Replaces torch's

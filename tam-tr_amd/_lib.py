@@ -94,6 +94,8 @@ _SIGS = {
     'tamtr_bncl2_act_fwd': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _F, _F, _I, _I, _P],
     'tamtr_bncl2_act_bwd': [_P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P],
     'tamtr_bncl_act_bwd': [_P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _LL, _I, _I, _I, _P],
+    'tamtr_bncl_act_down2_fwd': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _I, _I, _P],
+    'tamtr_bncl_act_down2_bwd': [_P, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     'tamtr_bn_act_fwd': [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _F, _I, _I, _P],
     'tamtr_bn_act_bwd': [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     'tamtr_layernorm_fwd': [_P, _P, _P, _P, _P, _LL, _I, _F, _I, _P],

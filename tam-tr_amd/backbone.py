@@ -59,10 +59,20 @@ class Conv(nn.Module):
         return ('bn' in self._modules and y.is_cuda and self.bn.training and self.bn.affine and type(self.act) in (nn.SiLU, nn.Identity)
                 and y.dtype in (torch.bfloat16, torch.float32))
 
-    def forward(self, x, residual=None):
+    def forward(self, x, residual=None, then=None):
         """residual: added to the block's output (the shortcut of a bottleneck); on the channels-last kernel path it joins inside the
-        BatchNorm apply pass."""
-        return self.post(_conv(self.conv, x), residual)
+        BatchNorm apply pass.  then: the Upsample(0.5) that is this block's only consumer (model.down2_pairs); the result is then(block(x)),
+        and where the kernels apply the BatchNorm output is made at the kept pixels only."""
+        y = _conv(self.conv, x)
+        if then is None:
+            return self.post(y, residual)
+        if residual is None and isinstance(then, Upsample) and then.scale_factor == 0.5 and then.mode == 'nearest' and self.fusable(y):
+            from . import ops
+            if ops.bn_down2_ok(y, self.bn):
+                B, C, H, W = y.shape   # BatchNorm statistics over the full map, apply + SiLU at pixels (2h, 2w): csrc/bn.hip bncl_down2_*
+                o = ops.bn_act_down2(y.permute(0, 2, 3, 1).reshape(B * H * W, C), self.bn, isinstance(self.act, nn.SiLU), B, H, W)
+                return o.view(B, H // 2, W // 2, C).permute(0, 3, 1, 2)
+        return then(self.post(y, residual))
 
     def post(self, y, residual=None):
         """Everything after the convolution: BatchNorm, activation, optional shortcut."""

@@ -625,6 +625,147 @@ __global__ __launch_bounds__(BN_THREADS) void bncl_bwd_apply_kernel(const T* __r
   }
 }
 
+// ---- BatchNorm + activation whose only consumer is a nearest x0.5 resample (y[:, ::2, ::2] of a 1x1 Conv, TAMTR.yaml layers 13-14, 21-22,
+// 29-30): the statistics need every pixel of x [B, H, W, C], everything after them only the kept ones.  The apply kernels below are chunked over
+// the QUARTER map q [B, H/2, W/2, C] (same pieces, same register-resident column constants); row r of q, with Wo = W / 2 and
+// t = r / Wo = b * (H / 2) + h, is pixel (2h, 2w) of image b: row 2 * (r + t * Wo) of x.  C is a power of two (bncl_check leaves nothing else).
+__device__ __forceinline__ size_t down2_src(size_t e, int C, int cshift, unsigned Wo) {
+  const unsigned r = (unsigned)(e >> cshift);
+  return ((2 * ((size_t)r + (size_t)(r / Wo) * Wo)) << cshift) + (e & (size_t)(C - 1));
+}
+
+// y (packed quarter map) = act(bn(x)) at the kept pixels; per-element arithmetic of bncl_apply_kernel
+template <typename T, int V>
+__global__ __launch_bounds__(BN_THREADS) void bncl_down2_apply_kernel(const T* __restrict__ x, const float* __restrict__ mean_rstd,
+                                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                       T* __restrict__ y, size_t total, int C, int iters, int act, int cshift,
+                                                                       unsigned Wo) {
+  const size_t piece = (size_t)BN_THREADS * V, start = (size_t)blockIdx.x * iters * piece, end = min(total, start + iters * piece);
+  const int c0 = (threadIdx.x % (C / V)) * V;
+  const size_t home = start + c0;   // first row of the chunk: where a load past the end is redirected
+  float mean[V], a[V], be[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) { mean[j] = mean_rstd[2 * (c0 + j)]; a[j] = mean_rstd[2 * (c0 + j) + 1] * gamma[c0 + j]; be[j] = beta[c0 + j]; }
+  const size_t e0 = start + (size_t)threadIdx.x * V;
+  for (int it = 0; it < iters; it += CL_UNROLL) {
+    float v[CL_UNROLL][V];
+#pragma unroll
+    for (int u = 0; u < CL_UNROLL; ++u) {
+      const size_t e = e0 + (size_t)(it + u) * piece;
+      Vec<T, V>::ld(x + down2_src(e < end ? e : home, C, cshift, Wo), v[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < CL_UNROLL; ++u) {
+      const size_t e = e0 + (size_t)(it + u) * piece;
+#pragma unroll
+      for (int j = 0; j < V; ++j) v[u][j] = act_fwd(fmaf(v[u][j] - mean[j], a[j], be[j]), act);
+      if (e < end) Vec<T, V>::st(y + e, v[u]);
+    }
+  }
+}
+
+// part[c][chunk][2] = sum dz, sum dz * xhat.  Chunked over the FULL map like bncl_bwd_reduce_kernel, and every thread adds its rows in that
+// kernel's order, so the sums have the bits that kernel leaves for a gradient map that is zero at the dropped pixels (a term of 0 changes no
+// sum); only a kept row (h and w even: with H and W even that is "r and r / W even") costs memory traffic: the loads of every other row go to
+// the chunk's home row and the head of gy, and their term is multiplied by 0.  Row r = q W + w of x is row (q / 2) (W / 2) + w / 2 of gy.
+template <typename T, int V>
+__global__ __launch_bounds__(BN_THREADS) void bncl_down2_bwd_reduce_kernel(const T* __restrict__ gy, const T* __restrict__ x,
+                                                                            const float* __restrict__ mean_rstd, const float* __restrict__ gamma,
+                                                                            const float* __restrict__ beta, float* __restrict__ part, size_t total,
+                                                                            int C, int iters, int act, size_t ldgy, int cshift, unsigned Wo) {
+  __shared__ float s_acc[BN_THREADS * 2 * V];
+  __shared__ float s_col[2 * 1024];
+  const size_t piece = (size_t)BN_THREADS * V, start = (size_t)blockIdx.x * iters * piece, end = min(total, start + iters * piece);
+  const int cg = C / V, c0 = (threadIdx.x % cg) * V, S = gridDim.x;
+  const size_t home = start + c0;
+  float mean[V], rstd[V], gm[V], be[V], acc[2 * V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    mean[j] = mean_rstd[2 * (c0 + j)]; rstd[j] = mean_rstd[2 * (c0 + j) + 1]; gm[j] = gamma[c0 + j]; be[j] = beta[c0 + j];
+    acc[j] = 0.f; acc[V + j] = 0.f;
+  }
+  const size_t e0 = start + (size_t)threadIdx.x * V;
+  for (int it = 0; it < iters; it += CL_UNROLL) {
+    float xv[CL_UNROLL][V], gv[CL_UNROLL][V], live[CL_UNROLL];
+#pragma unroll
+    for (int u = 0; u < CL_UNROLL; ++u) {
+      const size_t e = e0 + (size_t)(it + u) * piece;
+      const unsigned r = (unsigned)(e >> cshift), q = r / (2 * Wo);
+      const bool kept = e < end && !((r | q) & 1);
+      live[u] = kept ? 1.f : 0.f;
+      Vec<T, V>::ld(x + (kept ? e : home), xv[u]);
+      Vec<T, V>::ld(gy + (kept ? ((size_t)(q >> 1) * Wo + ((r - q * 2 * Wo) >> 1)) * ldgy : (size_t)0) + c0, gv[u]);   // gy may be a channel slice
+    }
+#pragma unroll
+    for (int u = 0; u < CL_UNROLL; ++u) {
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const float xh = (xv[u][j] - mean[j]) * rstd[j];
+        const float dz = live[u] * gv[u][j] * act_bwd(fmaf(xh, gm[j], be[j]), act);
+        acc[j] += dz; acc[V + j] = fmaf(dz, xh, acc[V + j]);
+      }
+    }
+  }
+  fold_row_lanes<2 * V>(acc, s_acc, s_col, cg);
+  for (int c = threadIdx.x; c < C; c += BN_THREADS) {
+    float* o = part + ((size_t)c * S + blockIdx.x) * 2;
+    o[0] = s_col[(c / V) * 2 * V + c % V]; o[1] = s_col[(c / V) * 2 * V + V + c % V];
+  }
+}
+
+// gx over the full map, one work item per 16 bytes of the quarter map: one gy load, the 2 x 2 pixels of x it stands for (the kept one first),
+// four gx stores.  dz is gy * act'(z) at the kept pixel and 0 at the other three; k1, k2 are means over the FULL map.
+template <typename T, int V>
+__global__ __launch_bounds__(BN_THREADS) void bncl_down2_bwd_apply_kernel(const T* __restrict__ gy, const T* __restrict__ x,
+                                                                           const float* __restrict__ mean_rstd, const float* __restrict__ gamma,
+                                                                           const float* __restrict__ beta, const float* __restrict__ sums,
+                                                                           T* __restrict__ gx, size_t total, int C, int iters, int act,
+                                                                           float inv_count, size_t ldgy, int cshift, unsigned Wo) {
+  const size_t piece = (size_t)BN_THREADS * V, start = (size_t)blockIdx.x * iters * piece, end = min(total, start + iters * piece);
+  const int c0 = (threadIdx.x % (C / V)) * V;
+  const size_t home = start + c0;
+  const size_t below = (size_t)2 * Wo << cshift;   // one image row of x further down
+  float mean[V], rstd[V], gm[V], be[V], k1[V], k2[V];
+#pragma unroll
+  for (int j = 0; j < V; ++j) {
+    mean[j] = mean_rstd[2 * (c0 + j)]; rstd[j] = mean_rstd[2 * (c0 + j) + 1]; gm[j] = gamma[c0 + j]; be[j] = beta[c0 + j];
+    k1[j] = sums[2 * (c0 + j)] * inv_count; k2[j] = sums[2 * (c0 + j) + 1] * inv_count;
+  }
+  const size_t e0 = start + (size_t)threadIdx.x * V;
+  for (int it = 0; it < iters; it += CL_UNROLL / 2) {   // five streams in, four out: half the unroll keeps the registers in bounds
+    float xv[CL_UNROLL / 2][4][V], gv[CL_UNROLL / 2][V];
+    size_t src[CL_UNROLL / 2];
+#pragma unroll
+    for (int u = 0; u < CL_UNROLL / 2; ++u) {
+      const size_t e = e0 + (size_t)(it + u) * piece, ee = e < end ? e : home;
+      src[u] = down2_src(ee, C, cshift, Wo);
+      Vec<T, V>::ld(x + src[u], xv[u][0]);
+      Vec<T, V>::ld(x + src[u] + C, xv[u][1]);
+      Vec<T, V>::ld(x + src[u] + below, xv[u][2]);
+      Vec<T, V>::ld(x + src[u] + below + C, xv[u][3]);
+      Vec<T, V>::ld(gy + (ee >> cshift) * ldgy + (ee & (size_t)(C - 1)), gv[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < CL_UNROLL / 2; ++u) {
+      const size_t e = e0 + (size_t)(it + u) * piece;
+#pragma unroll
+      for (int j = 0; j < V; ++j) {
+        const float xh = (xv[u][0][j] - mean[j]) * rstd[j], gr = gm[j] * rstd[j];
+        const float dz = gv[u][j] * act_bwd(fmaf(xh, gm[j], be[j]), act);
+        xv[u][0][j] = gr * (dz - k1[j] - xh * k2[j]);
+#pragma unroll
+        for (int q = 1; q < 4; ++q) xv[u][q][j] = gr * (0.f - k1[j] - (xv[u][q][j] - mean[j]) * rstd[j] * k2[j]);
+      }
+      if (e < end) {
+        Vec<T, V>::st(gx + src[u], xv[u][0]);
+        Vec<T, V>::st(gx + src[u] + C, xv[u][1]);
+        Vec<T, V>::st(gx + src[u] + below, xv[u][2]);
+        Vec<T, V>::st(gx + src[u] + below + C, xv[u][3]);
+      }
+    }
+  }
+}
+
 }  // namespace
 
 // ================================================================================================ host side
@@ -825,6 +966,58 @@ extern "C" int tamtr_bncl_act_seg_bwd(const void* gy, long long seg_rows, long l
   if (!seg_ok(seg_rows, seg_pitch, N, C)) return TAMTR_EUNSUP;
   return bncl_act_bwd_impl(gy, C, x, gamma, beta, mean_rstd, gx, ggamma, gbeta, partials, N, C, act, dtype, stream,
                            Seg{(unsigned)seg_rows, (size_t)seg_pitch});
+}
+
+// ---- act(bn(x))[:, ::2, ::2] of a channels-last map x [B, H, W, C]: statistics over the full map, apply over the quarter map
+// q [B, H/2, W/2, C], backward reduce in the full map's chunks but reading the kept rows only, backward apply over the full map in work items of
+// the quarter map (kernels: bncl_down2_*)
+static int down2_check(const void* a, const void* b, int B, int H, int W, int C, int dtype, int act) {
+  if (B <= 0 || H <= 0 || W <= 0) return TAMTR_EINVAL;
+  const long long hw = (long long)H * W;
+  if (hw > 2000000000LL || B > 2000000000LL / hw) return TAMTR_EUNSUP;
+  const int rc = bncl_check(a, b, B * hw, C, dtype, act);
+  if (rc) return rc;
+  return H % 2 || W % 2 ? TAMTR_EUNSUP : TAMTR_OK;
+}
+
+extern "C" int tamtr_bncl_act_down2_fwd(const void* x, const float* gamma, const float* beta, float* running_mean, float* running_var, void* y,
+                                        float* mean_rstd, float* partials, int B, int H, int W, int C, float eps, float momentum, int act,
+                                        int dtype, void* stream) {
+  if (!x || !y || !gamma || !beta || !mean_rstd || !partials) return TAMTR_EINVAL;
+  const int rc = down2_check(x, y, B, H, W, C, dtype, act);
+  if (rc) return rc;
+  const long long N = (long long)B * H * W;
+  const ClPlan p = bncl_plan(N, C, dtype, stream), q = bncl_plan(N / 4, C, dtype, stream);
+  bncl_stats_finalize(p, x, partials, mean_rstd, running_mean, running_var, eps, momentum);
+  bncl_dispatch(q, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    launch(bncl_down2_apply_kernel<T, tag.V>, q.S, q.s, (const T*)x, mean_rstd, gamma, beta, (T*)y, q.total, C, q.iters, act, cshift_of(C),
+           (unsigned)(W / 2));
+  });
+  return tamtr_launch_status();
+}
+
+extern "C" int tamtr_bncl_act_down2_bwd(const void* gy, long long ldgy, const void* x, const float* gamma, const float* beta,
+                                        const float* mean_rstd, void* gx, float* ggamma, float* gbeta, float* partials, int B, int H, int W,
+                                        int C, int act, int dtype, void* stream) {
+  if (!gy || !x || !gamma || !beta || !mean_rstd || !gx || !ggamma || !gbeta || !partials) return TAMTR_EINVAL;
+  const int rc = down2_check(gy, x, B, H, W, C, dtype, act);
+  if (rc) return rc;
+  if (!ldgy_ok(ldgy, C, dtype) || (uintptr_t)gx % 16) return TAMTR_EUNSUP;
+  const long long N = (long long)B * H * W;
+  const ClPlan p = bncl_plan(N, C, dtype, stream), q = bncl_plan(N / 4, C, dtype, stream);
+  const int cshift = cshift_of(C);
+  float* sums = part_end(partials, p, PART_BWD);
+  const float inv = 1.f / (float)N;   // the mean terms of the BatchNorm backward run over the full map
+  bncl_dispatch(q, [&](auto tag) {
+    using T = typename decltype(tag)::T;
+    launch(bncl_down2_bwd_reduce_kernel<T, tag.V>, p.S, p.s, (const T*)gy, (const T*)x, mean_rstd, gamma, beta, partials, p.total, C, p.iters, act,
+           (size_t)ldgy, cshift, (unsigned)(W / 2));
+    launch(bncl_sum_kernel, C, p.s, partials, sums, ggamma, gbeta, p.S);
+    launch(bncl_down2_bwd_apply_kernel<T, tag.V>, q.S, q.s, (const T*)gy, (const T*)x, mean_rstd, gamma, beta, sums, (T*)gx, q.total, C, q.iters, act,
+           inv, (size_t)ldgy, cshift, (unsigned)(W / 2));
+  });
+  return tamtr_launch_status();
 }
 
 // ---- y = act(bn1(x1) + bn2(x2)): both BatchNorms in training mode over the same [N, C] shape (RepConvN)

@@ -66,6 +66,14 @@ def build_graph(spec, ch=3, nc=10):
     return nn.Sequential(*layers), sorted(set(save))
 
 
+def down2_pairs(spec):
+    """Indices of the Conv rows of `spec` whose only consumer is the nearest x0.5 Upsample in the next row (TAMTR_SPEC: 13, 21, 29): the layer
+    loop runs such a pair as one call, Conv.forward(x, then=upsample), so that the BatchNorm output is made at the kept pixels only."""
+    saved = {x % i for i, (f, _, _) in enumerate(spec) for x in ([f] if isinstance(f, int) else f) if x != -1}
+    return {i for i, (row, nxt) in enumerate(zip(spec, spec[1:]))
+            if row[1] == 'Conv' and nxt[1] == 'Upsample' and nxt[0] == -1 and nxt[2][0] == 0.5 and i not in saved}
+
+
 import os
 # NHWC trunk on the GPU: MIOpen's bf16 convolutions are NHWC kernels and wrap every NCHW operand in a transpose (483 launches,
 # 7.75 ms of the 640 px / bs 16 step).  Channels-last activations + channels-last k x k weights take them as they are (needs
@@ -154,6 +162,7 @@ class RTDETRDetectionWorldModel(nn.Module):
         self.names = {i: f'{i}' for i in range(nc)}
         self.txt_feats = torch.randn(1, nc, 512)
         self.model, self.save = build_graph(cfg or TAMTR_SPEC, ch, nc)
+        self.down2 = down2_pairs(cfg or TAMTR_SPEC)   # Conv rows that run together with the Upsample(0.5) after them
         self.channels_last = False
         self.set_channels_last(_CHANNELS_LAST)
         self.stride = torch.Tensor([32])
@@ -223,19 +232,25 @@ class RTDETRDetectionWorldModel(nn.Module):
             counters = ops.begin_bn_counter_batch() if self.training else None
             y = []
             grouped_cast = self.autocast_dtype == torch.bfloat16 and x.is_cuda and torch.is_grad_enabled()
-            for m in self.model[:-1]:
+            layers, then = self.model[:-1], None
+            for m in layers:
+                if m is then:   # the Upsample(0.5) that ran inside the Conv before it
+                    y.append(x if m.i in self.save else None)
+                    continue
                 if m.f != -1:
                     x = y[m.f] if isinstance(m.f, int) else [x if j == -1 else y[j] for j in m.f]
                 args = (x, txt) if isinstance(m, TIAGELAN) else (x,)
+                then = layers[m.i + 1] if m.i in self.down2 else None
+                kwargs = {} if then is None else {'then': then}
                 names = _conv_weight_names(m) if grouped_cast else ()
                 if names:  # this layer's conv weights as bf16 copies from one kernel (see _CastGroup); same values autocast would use
                     masters = [m.get_parameter(n) for n in names]
                     w16 = _cast_group(masters)
                     for c, p in zip(w16, masters):   # ops.conv2d_module sends a 1x1 convolution's fp32 weight gradient straight to the master
                         c._tamtr_master = p
-                    x = torch.func.functional_call(m, dict(zip(names, w16)), args)
+                    x = torch.func.functional_call(m, dict(zip(names, w16)), args, kwargs)
                 else:
-                    x = m(*args)
+                    x = m(*args, **kwargs)
                 y.append(x if m.i in self.save else None)
             feats, shapes = head.encode([y[j] for j in head.f], drop_scales)
             if counters is not None:

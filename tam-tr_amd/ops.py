@@ -3005,6 +3005,51 @@ class _BNActCL(torch.autograd.Function):
         return gx, gg.to(g_dt), gb.to(b_dt), None, None, None, None, None, g_res
 
 
+def _bncl_down2_fwd(x, gamma, beta, rm, rv, eps, mom, act, B, H, W):
+    """Channels-last rows x [B * H * W, C] -> act(bn(x)) at the pixels (2h, 2w) as rows [B * H/2 * W/2, C], the fp32 forms of gamma and
+    beta, mean_rstd [C, 2]: the statistics pass of _bncl_fwd over the full map, the apply pass over the kept rows."""
+    N, C = x.shape
+    g32, b32 = _c(gamma.float()), _c(beta.float())
+    y = x.new_empty(N // 4, C)
+    mr, part = _bncl_stats_buffers(x)
+    call('tamtr_bncl_act_down2_fwd', ptr(x), ptr(g32), ptr(b32), ptr(rm), ptr(rv), ptr(y), ptr(mr), ptr(part), B, H, W, C, float(eps), float(mom),
+         act, dtype_code(x), stream_ptr())
+    return y, g32, b32, mr
+
+
+def _bncl_down2_bwd(gy, x, g32, b32, mr, act, B, H, W):
+    """-> d(x) over the full map, and d(gamma), d(beta) in fp32.  gy: the quarter map's rows as _gy_rows leaves them."""
+    C = x.shape[1]
+    gx = torch.empty_like(x)
+    gg, gb = _f32(x.device, C), _f32(x.device, C)
+    part = _f32(x.device, C * _bncl_blocks(x) * 2 + 2 * C)   # the reduce runs in the full map's chunks (the sums keep _bncl_bwd's bits)
+    call('tamtr_bncl_act_down2_bwd', ptr(gy), gy.stride(0), ptr(x), ptr(g32), ptr(b32), ptr(mr), ptr(gx), ptr(gg), ptr(gb), ptr(part), B, H, W, C,
+         act, dtype_code(x), stream_ptr())
+    return gx, gg, gb
+
+
+class _BNActDown2CL(torch.autograd.Function):
+    """act(bn(x))[:, ::2, ::2] on a channels-last map given as rows x [B * H * W, C]: a Conv whose only consumer is Upsample(0.5).  Three
+    quarters of the BatchNorm output are never made, and the backward never reads the zeros a resample backward would have filled in
+    (csrc/bn.hip tamtr_bncl_act_down2_*).  Returns rows [B * H/2 * W/2, C]."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, running_mean, running_var, eps, momentum, silu, B, H, W):
+        require_gpu(x, gamma, beta)
+        x = _c(x)
+        y, *saved = _bncl_down2_fwd(x, gamma, beta, running_mean, running_var, eps, momentum, int(bool(silu)), B, H, W)
+        ctx.save_for_backward(x, *saved)
+        ctx.cfg = (int(bool(silu)), gamma.dtype, beta.dtype, B, H, W)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, g32, b32, mr = ctx.saved_tensors
+        act, g_dt, b_dt, B, H, W = ctx.cfg
+        gx, gg, gb = _bncl_down2_bwd(_gy_rows(gy, x), x, g32, b32, mr, act, B, H, W)
+        return gx, gg.to(g_dt), gb.to(b_dt), None, None, None, None, None, None, None, None
+
+
 class _BN2ActCL(torch.autograd.Function):
     """y = act(bn1(x1) + bn2(x2)) on channels-last [N, C] maps, both BatchNorms in training mode: RepConvN's training form
     (extra_modules/block.py:66-69) in one apply pass and one backward pair (csrc/bn.hip tamtr_bncl2_act_*)."""
@@ -3119,6 +3164,23 @@ def bn_act(x, bn, silu, residual=None):
         return _BNActCL.apply(x, bn.weight, bn.bias, rm, rv, bn.eps, mom, silu, residual)
     y = _BNAct.apply(x, bn.weight, bn.bias, rm, rv, bn.eps, mom, silu)
     return y if residual is None else y + residual
+
+
+_BN_DOWN2 = _os.environ.get('TAMTR_BN_DOWN2') != '0'   # A/B switch: 0 = the full BatchNorm map, then the resample kernel, as before bn_act_down2
+
+
+def bn_down2_ok(y, bn):
+    """A convolution output y [B, C, H, W] whose BatchNorm (+ activation) can run together with a following nearest x0.5 resample:
+    channels-last on the GPU, a channel count the [N, C] kernels take, even H and W, training mode, affine, fp32 or bf16; TAMTR_BN_DOWN2 != 0."""
+    return (_BN_DOWN2 and y.is_cuda and y.dim() == 4 and y.dtype in (torch.float32, torch.bfloat16) and is_cl(y) and bn_cl_ok(y.shape[1], y.dtype)
+            and y.shape[2] % 2 == 0 and y.shape[3] % 2 == 0 and bn.training and bn.affine)
+
+
+def bn_act_down2(x_rows, bn, silu, B, H, W):
+    """act(bn(x))[:, ::2, ::2] for an nn.BatchNorm2d in training mode on the rows [B * H * W, C] of a channels-last map: rows
+    [B * H/2 * W/2, C].  Batch statistics over the full map; running stats and num_batches_tracked as bn_act."""
+    rm, rv, mom = _bn_train_call(bn)
+    return _BNActDown2CL.apply(x_rows, bn.weight, bn.bias, rm, rv, bn.eps, mom, silu, B, H, W)
 
 
 def bn2_act(x1, bn1, x2, bn2, silu):
