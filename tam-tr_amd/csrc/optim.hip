@@ -153,8 +153,10 @@ __global__ __launch_bounds__(OPT_THREADS) void opt_update_kernel(OptTable T, flo
   if (g) {
     g += off; m += off; v = T.v[ti] + off;
     const float step = T.step[ti] + 1.f;                           // every chunk of the tensor sees the old count; chunk 0 stores the new one below
-    step_size = S.lr[grp] / (1.f - powf(S.beta1, step));
-    bc2_sqrt = sqrtf(1.f - powf(S.beta2, step));
+    // the bias corrections in double, as torch forms them: 1 - beta2^t in fp32 is a cancellation at small t (at t = 2 it keeps 1e-5 relative;
+    // DESIGN.md "loss and optimizer against fp64").  Once per workgroup; the betas are the fp32 values passed in.
+    step_size = (float)((double)S.lr[grp] / (1.0 - pow((double)S.beta1, (double)step)));
+    bc2_sqrt = (float)sqrt(1.0 - pow((double)S.beta2, (double)step));
   }
   if (e) e += off;
   if (sh) sh += off;

@@ -1,7 +1,8 @@
 """fp64 references with an error model for the bf16 hot-path kernels (tests/test_gpu_bf16_kernels.py, tests/test_ref64_host.py) and for the
 text gate and CPAM kernels in fp32 and bf16 (tests/test_gpu_gates_ref64.py), and for the LayerNorm, cross-merge and depthwise SS2D kernels
 (tests/test_gpu_ss2d_ref64.py), and for the MFMA linear and x_proj kernels (tests/test_gpu_gemm_ref64.py), and for the BatchNorm kernels of
-csrc/bn.hip in both layouts, the pair, the segmented form and the statistics alone (tests/test_gpu_bn_ref64.py).
+csrc/bn.hip in both layouts, the pair, the segmented form and the statistics alone (tests/test_gpu_bn_ref64.py), and for the loss-term,
+matcher-cost and box-refinement kernels of csrc/detrloss.hip and the clip / AdamW / EMA kernels of csrc/optim.hip (tests/test_gpu_loss_ref64.py).
 
 Every reference takes the operands exactly as the kernel sees them (bf16 tensors, fp32 side inputs), promotes them to float64 and
 computes on the CPU.  Next to each value it returns a magnitude: the same computation on absolute values.  check() then asserts,
@@ -33,17 +34,26 @@ def _d(t):
     return t.detach().cpu().double()
 
 
-def check(what, got, ref, mag, a, b, log=True):
+def check(what, got, ref, mag, a, b, log=True, envelope=None, tiny=0.0):
     """Elementwise |got - ref| <= a 2^-8 |ref| + b mag.  NaN in ref must be NaN in got (and only there).  Returns the worst ratio.
-    log=False: one piece of a larger tensor (see report())."""
+    log=False: one piece of a larger tensor (see report()).
+    envelope = (lo, hi), lo <= ref <= hi elementwise: the reference is an interval (an operand that the operation rounds on purpose may
+    fall on either neighbour); the error is the distance of got from [lo, hi], 0 inside it, and the bound is unchanged.
+    tiny: the one absolute term a caller may ask for, and only as fp32's underflow threshold (FLT_MIN times the factors that follow the
+    underflow): a product below 2^-126 may be flushed to 0 or lose bits as a denormal.  Both default to the plain rule."""
     got, ref, mag = _d(got), _d(ref), _d(mag)
     assert got.shape == ref.shape == mag.shape, f'{what}: shapes {tuple(got.shape)} {tuple(ref.shape)} {tuple(mag.shape)}'
     nan = torch.isnan(ref)
     assert torch.equal(torch.isnan(got), nan), f'{what}: NaN pattern differs ({int(torch.isnan(got).sum())} vs {int(nan.sum())})'
     live = ~nan
     assert bool(torch.isfinite(got[live]).all()), f'{what}: non-finite output'
-    err = (got - ref).abs()[live]
-    bound = (a * U8 * ref.abs() + b * mag)[live]
+    if envelope is None:
+        err = (got - ref).abs()[live]
+    else:
+        lo, hi = _d(envelope[0]), _d(envelope[1])
+        assert lo.shape == hi.shape == ref.shape and bool(((lo <= ref) & (ref <= hi))[live].all()), f'{what}: the envelope does not hold the reference'
+        err = torch.maximum(lo - got, got - hi).clamp_min(0)[live]
+    bound = (a * U8 * ref.abs() + b * mag + tiny)[live]
     zero = bound == 0
     assert bool((err[zero] == 0).all()), f'{what}: {int((err[zero] != 0).sum())} elements must be exactly 0 and are not'
     ratio = torch.zeros_like(err)
@@ -1013,3 +1023,292 @@ def bn_bounds(layout, plan, bf16, act, zmax=None, residual=False):
     for n in ('dx', 'dgamma', 'dbeta', 'mean', 'rstd', 'running_mean', 'running_var'):
         two[n + '1'] = two[n + '2'] = one[n]
     return two
+
+
+# ------------------------------------------------------------------------------------------------ loss terms, matcher cost, box refinement (csrc/detrloss.hip)
+def f32(x):
+    """A Python number as the fp32 value a `float` parameter of the C ABI (or an `f` literal of the source) holds, as a Python float."""
+    return float(torch.tensor(float(x), dtype=torch.float32))
+
+
+DL_EPS = f32(1e-7)                    # DL_EPS of csrc/detrloss.hip
+DL_ONE_EPS = f32(1.0 + 1e-7)          # its 1.f + DL_EPS, formed in fp32: 1 + 2^-23
+FOCAL_EPS = f32(1e-8)                 # the matcher's 1e-8f
+REF_EPS = f32(1e-5)                   # inverse_sigmoid's eps
+FLT_MIN = 2.0 ** -126                 # fp32's smallest normal number: what check()'s `tiny` is a small multiple of
+
+
+def riou_parts(a, b, eps=DL_EPS, one_eps=DL_ONE_EPS, mut=()):
+    """1 - RIOU (ultralytics/utils/metrics.py:91-130) of predictions a against boxes b (xywh, fp64, broadcastable [..., 4]) and its
+    gradient by a, written out as plain formulas; csrc/detrloss.hip riou_xywh / riou_loss_grad state the same ones in fp32.
+
+    The rules: the IoU's intersection clamp passes its gradient where its argument is >= 0; a tie of min / max / maximum gives each side
+    half; RIOU's alpha is a constant; coincident centres give d sqrt(rho2) = inf * 0 = NaN in all four components.
+    Magnitudes: the same formulas on absolute values with the cancelling terms added: the union a + b - inter as a + b + inter (its
+    relative conditioning `ku` multiplies everything that divides by it), the aspect term atan(.) - atan(.) as the sum of the two, the
+    denominator of alpha as v + iou + 1, and the three contributions of the gradient (d iou, the distance term, alpha dv) as a sum.
+    mut: deliberate mistakes for the host tests ('tie0' | 'tie1': a tie's half as 0 | 1; 'cx_gt': the clamp gate of x as > 0; 'dm1_swap').
+    Returns a dict: iou, ku, loss, m_loss, l1, grad [..., 4], m_grad [..., 4]."""
+    a, b = torch.broadcast_tensors(a, b)
+    ax, ay, aw, ah = a.unbind(-1)
+    bx, by, bw, bh = b.unbind(-1)
+    ax1, ax2, ay1, ay2 = ax - aw / 2, ax + aw / 2, ay - ah / 2, ay + ah / 2
+    bx1, bx2, by1, by2 = bx - bw / 2, bx + bw / 2, by - bh / 2, by + bh / 2
+    one, z = torch.ones_like(ax), torch.zeros_like(ax)
+    half = 0.0 if 'tie0' in mut else 1.0 if 'tie1' in mut else 0.5
+
+    def step(gt, eq):
+        return torch.where(gt, one, torch.where(eq, half * one, z))
+    ixr, iyr = torch.minimum(ax2, bx2) - torch.maximum(ax1, bx1), torch.minimum(ay2, by2) - torch.maximum(ay1, by1)
+    iw, ih = ixr.clamp(min=0), iyr.clamp(min=0)
+    cx, cy = ((ixr > 0) if 'cx_gt' in mut else (ixr >= 0)).double(), (iyr >= 0).double()
+    d_ax2, d_ax1 = step(ax2 < bx2, ax2 == bx2) * cx, -step(ax1 > bx1, ax1 == bx1) * cx
+    d_ay2, d_ay1 = step(ay2 < by2, ay2 == by2) * cy, -step(ay1 > by1, ay1 == by1) * cy
+    diw = [d_ax1 + d_ax2, z, 0.5 * (d_ax2 - d_ax1), z]
+    dih = [z, d_ay1 + d_ay2, z, 0.5 * (d_ay2 - d_ay1)]
+    inter, areas = iw * ih, aw * ah + bw * bh
+    uni = areas - inter + eps
+    iou, ku = inter / uni, (areas + inter + eps) / uni
+    sx, sy = bx1 + bx2 - ax1 - ax2, by1 + by2 - ay1 - ay2
+    rho2 = (sx * sx + sy * sy) / 4
+    s = rho2.sqrt()
+    cs = torch.maximum(aw, ah) + torch.maximum(bw, bh) + s + eps
+    c2 = cs * cs
+    r1 = aw / ah
+    tb, ta = torch.atan(bw / bh), torch.atan(r1)
+    da, m_da = tb - ta, tb + ta
+    kv = 4 / math.pi ** 2
+    v, m_v = kv * da * da, 2 * kv * da.abs() * m_da
+    den = v - iou + one_eps
+    alpha = v / den
+    m_alpha = m_v / den + alpha * (m_v + iou * ku + one_eps) / den
+    loss = 1 - (iou - (rho2 / c2 + v * alpha))
+    m_loss = 1 + iou * ku + rho2 / c2 + m_v * m_alpha
+    drho2 = [-sx, -sy, z, z]
+    wide, tall = step(aw > ah, aw == ah), step(ah > aw, aw == ah)
+    dm1 = [z, z, tall, wide] if 'dm1_swap' in mut else [z, z, wide, tall]
+    inv = 1 / (ah * (1 + r1 * r1))
+    dat = [z, z, inv, -r1 * inv]
+    dwh = [z, z, ah, aw]
+    g, m_g = [], []
+    for k in range(4):
+        dinter, m_dinter = diw[k] * ih + iw * dih[k], diw[k].abs() * ih + iw * dih[k].abs()
+        diou = (dinter * uni - inter * (dwh[k] - dinter)) / (uni * uni)
+        m_diou = ku * (m_dinter * uni + inter * (dwh[k] + m_dinter)) / (uni * uni)
+        ds = 0.5 / s * drho2[k]                                  # inf * 0 = NaN where the centres coincide
+        dcs = dm1[k] + ds
+        dterm = (drho2[k] * c2 - rho2 * 2 * cs * dcs) / (c2 * c2)
+        m_dterm = (drho2[k].abs() * c2 + rho2 * 2 * cs * (dm1[k] + ds.abs())) / (c2 * c2)
+        dv, m_dv = 2 * kv * da * (-dat[k]), 2 * kv * m_da * dat[k].abs()
+        g.append(-(diou - dterm - alpha * dv))
+        m_g.append(m_diou + m_dterm + m_alpha * m_dv)
+    return {'iou': iou, 'ku': ku, 'loss': loss, 'm_loss': m_loss, 'l1': (a - b).abs().sum(-1), 'grad': torch.stack(g, -1), 'm_grad': torch.stack(m_g, -1)}
+
+
+def detr_terms(pb, ps, gtb, gtc, li, bi, si, gi, n, gains, up, mut=()):
+    """csrc/detrloss.hip tamtr_detr_layers_fwd / _bwd (ops.detr_layer_losses): the (class, bbox, giou) terms [Lr] of the stacked decoder
+    layers and d/d(pb), d/d(ps) for the upstream gradient up [3, Lr].
+
+    pb [Lr,B,nq,4], ps [Lr,B,nq,nc] fp32; gtb [G,4], gtc [G]; the matched pairs (li, bi, si) <-> gi as flat lists, n per layer,
+    layer-major; gains = (class, bbox, giou).  class = gains[0] / max(n, 1) * sum over every logit of BCE(x, t) w with, on the matched
+    class of a matched row, t = w = IoU(pred, box) (a constant: detached), elsewhere t = 0 and w = 0.75 sigmoid(x)^2; bbox = gains[1] / n
+    * sum |pred - box|; giou = gains[2] / n * sum (1 - RIOU).  Rounding points: none on purpose.
+    Magnitudes.  The three terms: the sum of their absolute summands, BCE as |x| (1 + t) + log1p(exp(-|x|)), the IoU with its
+    conditioning ku (riou_parts).  (BCE: the kernel adds max(x, 0) - x t, the torch form of tam-tr_amd/loss.py (1 - t) x + max(-x, 0), which
+    cancels for x < 0; |x| (1 + t) covers the summands of both, so both are held to one bound.)  d/d(ps) = u (w (p - t) + BCE dw), dw = 1.5 p^2 (1 - p): |u| (w (p + t) + BCE dw) with 1 - p taken as
+    1 + p (the kernel subtracts a rounded p from 1).  A row of d/d(pb): |u_bbox| |sign| + |u_giou| times riou_parts' magnitude.
+    mut: riou_parts' mistakes, and 'dw075' (the factor of dw halved).
+    Returns {name: (value, magnitude)} for class, bbox, giou [Lr], dpb [Lr,B,nq,4], dps [Lr,B,nq,nc]."""
+    pbd, x, gb_, upd = _d(pb), _d(ps), _d(gtb), _d(up)
+    Lr, B, nq, nc = x.shape
+    gc, gbx, gg = (f32(v) for v in gains)
+    li, bi, si, gi, cls = (t.detach().cpu().long() for t in (li, bi, si, gi, gtc))
+    a, b = pbd[li, bi, si], gb_[gi]
+    rp = riou_parts(a, b, mut=mut)
+    tgt = torch.full((Lr, B, nq), nc, dtype=torch.long)
+    score, kk = torch.zeros(Lr, B, nq, dtype=torch.float64), torch.ones(Lr, B, nq, dtype=torch.float64)
+    tgt[li, bi, si], score[li, bi, si], kk[li, bi, si] = cls[gi], rp['iou'], rp['ku']
+    pos = torch.nn.functional.one_hot(tgt, nc + 1)[..., :nc].bool()
+    sc, k = score.unsqueeze(-1), kk.unsqueeze(-1)
+    p = torch.sigmoid(x)
+    t, m_t = torch.where(pos, sc, torch.zeros_like(x)), torch.where(pos, sc * k, torch.zeros_like(x))
+    w = torch.where(pos, sc.expand_as(x), 0.75 * p * p)
+    m_w = torch.where(pos, (sc * k).expand_as(x), w)
+    soft = torch.log1p(torch.exp(-x.abs()))
+    bce, m_bce = x.clamp(min=0) - x * t + soft, x.abs() * (1 + m_t) + soft
+    dn = float(max(n, 1))
+    res = {'class': ((bce * w).sum((1, 2, 3)) / dn * gc, (m_bce * m_w).sum((1, 2, 3)) / dn * gc),
+           'bbox': (rp['l1'].view(Lr, n).sum(1) / n * gbx,) * 2,
+           'giou': (rp['loss'].view(Lr, n).sum(1) / n * gg, rp['m_loss'].view(Lr, n).sum(1) / n * gg)}
+    u = (upd[0] * (gc / n)).view(Lr, 1, 1, 1)
+    f = 0.75 if 'dw075' in mut else 1.5
+    dw, m_dw = torch.where(pos, torch.zeros_like(x), f * p * p * (1 - p)), torch.where(pos, torch.zeros_like(x), 1.5 * p * p * (1 + p))
+    res['dps'] = (u * (w * (p - t) + bce * dw), u.abs() * (m_w * (p + m_t) + m_bce * m_dw))
+    ub, ui = (upd[1] * (gbx / n))[li].unsqueeze(-1), (upd[2] * (gg / n))[li].unsqueeze(-1)
+    sgn = torch.sign(a - b)
+    dpb, m_dpb = torch.zeros_like(pbd), torch.zeros_like(pbd)
+    dpb[li, bi, si], m_dpb[li, bi, si] = ub * sgn + ui * rp['grad'], ub.abs() * sgn.abs() + ui.abs() * rp['m_grad']
+    res['dpb'] = (dpb, m_dpb)
+    return res
+
+
+# Roundings along the kernels' chains; a math function counts its documented error in ulp: expf 1, logf 1, log1pf 2, atanf 2, powf 1 (ROCm's
+# OCML device library; doubled here, since the figures are stated and not proven), the division and sqrtf are correctly rounded (1).
+DL_IOU_N = 8          # a.w a.h, b.w b.h, their sum, - inter, + eps (4 + inter's product 1), the division (1), the two edge differences (2)
+DL_P_N = 4            # p = 1 / (1 + expf(-x)): expf (2), the sum, the division
+DL_BCE_N = 8          # x t (1), max - . (1), expf (2), log1pf (4: 2 ulp, doubled) -> 7, the last sum (1)
+DL_RIOU_N = 44        # iou (8), rho2 (3), sqrtf (1), cs (3), c2 (1), rho2 / c2 with c2's error twice (3), two atanf of a quotient (10), da (1),
+#                       v (2), alpha's denominator (2) and division (1) with v twice (4), v alpha (1), the three outer differences (3), +1 spare
+DL_RIOU_GRAD_N = 72   # the forward chain's intermediates (44 - 4) and, per component: dinter (3), d iou (6), ds (2), dcs (1), the distance
+#                       term (7), inv and dat (5), dv (3), alpha dv (1), the two differences and the sign (3) = 31, +1 spare
+
+
+def detr_bounds(B, nq, nc, n):
+    """{name: b} (a = 0: everything is fp32) for detr_terms' outputs.
+    class: per logit p (DL_P_N) twice in w = 0.75 p p (+2), or the IoU (DL_IOU_N); BCE (DL_BCE_N, with the IoU inside t: counted by ku in
+    the magnitude, DL_IOU_N); the product (1).  Then a thread adds its nc logits in sequence (nc), block_sum256 (6 + 4), the reduce
+    kernel's strided loop over the row blocks (ceil(nblk / 256)), block_sum256 again (10), / n and * gain (2).
+    bbox: four differences and absolute values summed (7), ceil(n / 256) + 10, the gain, the division (2).  giou: DL_RIOU_N and the same sum.
+    dps: p (4), w (10), t and p - t (DL_IOU_N + 1), the product (1), BCE (DL_BCE_N + DL_IOU_N), dw = 1.5 p p (1 - p) with p three
+    times (12 + 4), the product and the sum (2), u = up * scale with scale = gain / n, and the last product (3).
+    dpb: DL_RIOU_GRAD_N, the two upstream scalings (4), the product and the sum (2)."""
+    nblk = -(-B * nq // 256)
+    cls_elem = 2 * DL_P_N + 2 + DL_BCE_N + DL_IOU_N + 1
+    return {'class': fp32_b(cls_elem + nc + 10 + -(-nblk // 256) + 10 + 2), 'bbox': fp32_b(7 + -(-n // 256) + 10 + 2),
+            'giou': fp32_b(DL_RIOU_N + -(-n // 256) + 10 + 2),
+            'dps': fp32_b(DL_P_N + 10 + DL_IOU_N + 2 + DL_BCE_N + DL_IOU_N + 16 + 2 + 3), 'dpb': fp32_b(DL_RIOU_GRAD_N + 6)}
+
+
+def detr_match_cost(ps, pb, gtb, gtc, gains, alpha, gamma):
+    """csrc/detrloss.hip tamtr_detr_match_cost (ops.detr_match_cost): C [Lr,B,nq,G] = g_class (pos - neg) + g_bbox |pred - box|_1 +
+    g_giou (1 - RIOU), pos = alpha (1 - p)^gamma (-log(p + 1e-8)), neg = (1 - alpha) p^gamma (-log(1 - p + 1e-8)), p = sigmoid of the
+    logit of the box's class; a non-finite entry is 0 (models/utils/ops.py:84-112).
+
+    The rounding the operation has on purpose: p is an fp32 number.  Past logit 16.6 the quantised 1 - p decides neg (up to 1.4 in
+    absolute cost between fp32 and fp64), so p = sigmoid(x) is formed in fp64 and rounded to fp32, and the focal part is evaluated at that
+    p and at its two fp32 neighbours (inside [0, 1]): the device's expf may put p on either.  The envelope (lo, hi) of the three is what
+    check(envelope=) takes; the value is the middle one.  1 - p is then exact (p >= 1/2) or one rounding, like p + 1e-8: the argument of
+    each logarithm carries a relative 2^-24, the logarithm an absolute one: its magnitude is |log| + 1.
+    An entry that is not finite (a NaN or a 0 / 0 aspect in a diverged prediction) has value, envelope and magnitude 0: check() then
+    demands an exact 0 there.  Returns (value, magnitude, lo, hi)."""
+    x = _d(ps)[..., gtc.detach().cpu().long()]                       # [Lr,B,nq,G]
+    gc, gbx, gg, al, ga = (f32(v) for v in (*gains, alpha, gamma))
+    p32 = torch.sigmoid(x).float()
+    cand = [p32, torch.nextafter(p32, torch.zeros_like(p32)), torch.nextafter(p32, torch.ones_like(p32))]
+
+    def focal(p):
+        qp, qn = p + FOCAL_EPS, 1 - p + FOCAL_EPS
+        pos, neg = al * (1 - p) ** ga * (-torch.log(qp)), (1 - al) * p ** ga * (-torch.log(qn))
+        m = al * (1 - p) ** ga * (torch.log(qp).abs() + 1) + (1 - al) * p ** ga * (torch.log(qn).abs() + 1)
+        return gc * (pos - neg), gc * m
+    fs = [focal(p.double()) for p in cand]
+    vals = torch.stack([f[0] for f in fs])
+    rp = riou_parts(_d(pb).unsqueeze(-2), _d(gtb))
+    rest = gbx * rp['l1'] + gg * rp['loss']
+    val, lo, hi = fs[0][0] + rest, vals.amin(0) + rest, vals.amax(0) + rest
+    mag = torch.stack([f[1] for f in fs]).amax(0) + gbx * rp['l1'] + gg * rp['m_loss']
+    bad = ~torch.isfinite(val)
+    zero = torch.zeros_like(val)
+    return tuple(torch.where(bad, zero, t) for t in (val, mag, lo, hi))
+
+
+# the focal part: p (DL_P_N), 1 - p and + 1e-8 twice (3), two logf (4), two powf of arguments that carry p's error gamma = 2 times (4 + 2 DL_P_N),
+# four products per side (8), the difference and the gain (2); L1 (7) and its gain (1); RIOU (DL_RIOU_N), its gain (1); the two sums (2)
+DL_COST_N = DL_P_N + 3 + 4 + 4 + 2 * DL_P_N + 8 + 2 + 8 + DL_RIOU_N + 1 + 2
+
+
+def box_refine(delta, ref, cot):
+    """csrc/detrloss.hip tamtr_box_refine_fwd / _bwd (ops.box_refine): y = sigmoid(delta + log(max(x, eps) / max(1 - x, eps))),
+    x = clamp(ref, 0, 1), eps = 1e-5f, and d/d(delta), d/d(ref) for the cotangent cot, with torch's clamp gradients: each clamp passes
+    where its bound holds, the bound included.
+
+    delta as the kernel reads it (fp32, or bf16 widened), ref fp32.  Magnitudes: the logit is |delta| + |log| + 1 (the logarithm's
+    argument carries relative roundings), the sigmoid sig_mag of that; 1 - y in the backward is taken as 1 + (magnitude of y), the kernel
+    forms it from the stored y.  Returns {name: (value, magnitude)} for y, gd, gr."""
+    d, r, g = _d(delta), _d(ref), _d(cot)
+    x = r.clamp(0, 1)
+    om = 1 - x
+    lg = torch.log(x.clamp(min=REF_EPS) / om.clamp(min=REF_EPS))
+    z, m_z = d + lg, d.abs() + lg.abs() + 1
+    y = torch.sigmoid(z)
+    m_y = sig_mag(y, m_z)
+    gd, m_gd = g * y * (1 - y), g.abs() * m_y * (1 + m_y)
+    di = torch.where(x >= REF_EPS, 1 / x, torch.zeros_like(x)) + torch.where(om.float().double() >= REF_EPS, 1 / om, torch.zeros_like(x))
+    inside = ((r >= 0) & (r <= 1)).double()
+    return {'y': (y, m_y), 'gd': (gd, m_gd), 'gr': (gd * di * inside, m_gd * di * inside)}
+
+
+# y: two clamps exact, 1 - x (1), the division (1), logf (2), the sum (1), expf (2), 1 + e and the division (2) = 9, +1 spare.
+# gd: y's chain twice (y and 1 - y) and three roundings; gr: the two reciprocals, their sum and the product (4) more.
+BOX_REFINE_B = {'y': fp32_b(10), 'gd': fp32_b(2 * 10 + 3), 'gr': fp32_b(2 * 10 + 7)}
+
+
+# ------------------------------------------------------------------------------------------------ clip + AdamW + EMA (csrc/optim.hip)
+OPT_CHUNK = 8192       # elements per workgroup of csrc/optim.hip (tamtr_optim_chunk)
+OPT_NORM_N = OPT_CHUNK // 256 + 6 + 4 + 2     # a thread's 32 squares added in sequence, block_sum (6 + 4); the chunks are added in double;
+#                                               sqrt in double and its rounding to fp32 (1), one spare
+
+
+def optim_step(p, g, m, v, e, step, lr, wd, beta1, beta2, eps, max_norm, ema_decay, mut=()):
+    """csrc/optim.hip tamtr_optim_step (engine.FusedOptimStep.step): clip_grad_norm_(max_norm), AdamW, the EMA of the new value; one step
+    from a given state.
+
+    p, g, m, v, e, step, lr, wd: one entry per tensor (lr / wd: those of the tensor's parameter group).  g[i] None: no gradient this
+    step (no Adam step, the count stays; the EMA still moves); m[i] None: an EMA-only entry; e[i] None: no EMA.  beta1, beta2, eps,
+    lr wd and the EMA decay are the fp32 values the C ABI receives (lr wd: the fp32 product of the two fp32 values, as the kernel
+    forms it); the bias corrections 1 - beta^t and everything after them are fp64.
+    norm = sqrt(sum g^2) over every gradient; coef = min(1, max_norm / (norm + 1e-6)), 1 where max_norm <= 0; gc = coef g;
+    m' = m + (1 - beta1)(gc - m); v' = beta2 v + (1 - beta2) gc^2; update = -(lr / (1 - beta1^t)) m' / (sqrt(v') / sqrt(1 - beta2^t) +
+    eps); p' = (1 - lr wd) p + update; e' = d e + (1 - d) p'.
+    Magnitudes: the same sums on absolute values; p' is |p| + |update|, so a parameter at 0 is held to the accuracy of its update, and
+    `update` (what a test forms as p' - (1 - lr wd) p from the stored p') has the same one: the store of p' rounds relative to |p'|.
+    mut: 'no_wd' (the decay dropped).
+    Returns {'norm', 'coef': (value, magnitude)} and per tensor lists 'gc', 'm', 'v', 'update', 'p', 'e' of (value, magnitude) or None, and
+    'step' (the new counts)."""
+    b1, b2, ep, d = f32(beta1), f32(beta2), f32(eps), f32(ema_decay)
+    sq = sum(float((_d(t) ** 2).sum()) for t in g if t is not None)
+    norm = math.sqrt(sq)
+    coef = min(1.0, f32(max_norm) / (norm + f32(1e-6))) if max_norm > 0 else 1.0
+    res = {'norm': (torch.tensor(norm, dtype=torch.float64),) * 2, 'coef': (torch.tensor(coef, dtype=torch.float64),) * 2,
+           'gc': [], 'm': [], 'v': [], 'update': [], 'p': [], 'e': [], 'step': []}
+    for i, pt in enumerate(p):
+        pd = _d(pt)
+        new_p, m_p = pd, pd.abs()
+        if m[i] is not None and g[i] is not None:
+            lw = 0.0 if 'no_wd' in mut else f32(f32(lr[i]) * f32(wd[i]))
+            t = float(step[i]) + 1
+            gc = _d(g[i]) * coef
+            md, vd = _d(m[i]), _d(v[i])
+            mn, m_mn = md + (1 - b1) * (gc - md), md.abs() + (1 - b1) * (gc.abs() + md.abs())
+            vn = b2 * vd + (1 - b2) * gc * gc
+            step_size, bc2_sqrt = f32(lr[i]) / (1 - b1 ** t), math.sqrt(1 - b2 ** t)
+            den = vn.sqrt() / bc2_sqrt + ep
+            upd, m_upd = -step_size * mn / den, step_size * m_mn / den
+            new_p, m_p = pd - lw * pd + upd, pd.abs() + m_upd
+            res['gc'].append((gc, gc.abs())); res['m'].append((mn, m_mn)); res['v'].append((vn, vn))
+            res['update'].append((upd, m_p)); res['p'].append((new_p, m_p)); res['step'].append(t)
+        else:
+            for k in ('gc', 'm', 'v', 'update'):
+                res[k].append(None)
+            res['p'].append((pd, torch.zeros_like(pd)))          # untouched: bit for bit
+            res['step'].append(float(step[i]))
+        if e[i] is not None:
+            ed = _d(e[i])
+            res['e'].append((d * ed + (1 - d) * new_p, d * ed.abs() + (1 - d) * m_p))
+        else:
+            res['e'].append(None)
+    return res
+
+
+def optim_bounds(clipped):
+    """{name: b} (a = 0) for optim_step's outputs.  norm: OPT_NORM_N on the sum of squares, halved by the root: counted whole.  coef:
+    the norm, + 1e-6, the division (2).  A gradient that is not clipped is left bit for bit (coef is an exact 1): the norm drops out of
+    everything below.  gc: coef and the product (1).  m': gc, the difference, the product, the sum (3), one spare.  v': gc twice, the square,
+    two products, the sum (4), one spare.  update: m', half of v' and sqrtf (1), bc2_sqrt rounded to fp32 and the division (2), + eps (1), step_size
+    rounded (1), the product and the division (2).  p': the update, lr wd (1), its product with p (1), the two differences (2).
+    e': p', 1 - d (1), two products, the sum (3)."""
+    n_gc = OPT_NORM_N + 3 if clipped else 0
+    n_m, n_v = n_gc + 4, 2 * n_gc + 5
+    n_u = n_m + (n_v + 1) // 2 + 7
+    return {'norm': fp32_b(OPT_NORM_N), 'coef': fp32_b(OPT_NORM_N + 2), 'gc': fp32_b(n_gc), 'm': fp32_b(n_m), 'v': fp32_b(n_v),
+            'update': fp32_b(n_u + 4), 'p': fp32_b(n_u + 4), 'e': fp32_b(n_u + 8)}

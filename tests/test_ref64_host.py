@@ -1404,3 +1404,215 @@ def test_bn_mutants_fail():
         MUTANT_TABLE.append(('bn', f'segment b at b * seg_rows * C [{dt_},C={C_}]', False, new))      # (the old test compares bits with ops.bn_act)
         assert not new
     _report_mutants('bn')
+
+
+# ------------------------------------------------------------------------------------------------ loss terms, matcher cost, box refinement, optimizer
+import loss_cases as LC
+
+HOST_LIMIT = 0.5      # the fp32 torch form alone may use half of every bound: the rest is for the device's math functions
+
+
+def _grid(t):
+    return torch.tensor(t, dtype=torch.float64) * LC.U
+
+
+def _all_family_pairs():
+    """Every pair of every family in its four mirrorings (family_pair's layers 0 .. 3), fp64."""
+    fams, a, b = zip(*[LC.family_pair(j, l) for j in range(len(LC.PAIRS)) for l in range(4)])
+    return fams, _grid(a), _grid(b)
+
+
+def test_riou_reference_is_float64_autograd_of_bbox_iou_on_every_family():
+    """ref64.riou_parts - the plain formulas that csrc/detrloss.hip also states - against float64 autograd of tam-tr_amd/loss.py bbox_iou,
+    which the CPU suite pins on the reference project's fixtures: values, and the gradient with its tie, clamp and NaN rules, on every
+    family and mirroring.  (bbox_iou's constants in double: eps = 1e-7, 1 + eps.)"""
+    import tamtr_amd.loss as LS
+    fams, a, b = _all_family_pairs()
+    ar = a.clone().requires_grad_()
+    loss = 1 - LS.bbox_iou(ar, b, xywh=True, RIOU=True).squeeze(-1)
+    loss.sum().backward()
+    rp = R.riou_parts(a, b, eps=1e-7, one_eps=1 + 1e-7)
+    assert torch.allclose(rp['loss'], loss.detach(), rtol=1e-13, atol=0)
+    assert torch.allclose(rp['iou'], LS.bbox_iou(a, b, xywh=True).squeeze(-1), rtol=1e-13, atol=0)
+    nan = torch.isnan(ar.grad)
+    same = torch.tensor([f == 'same_centre' for f in fams])
+    assert torch.equal(nan, same.unsqueeze(-1).expand(-1, 4)), 'coincident centres, and only they, give four NaN components'
+    assert torch.equal(torch.isnan(rp['grad']), nan)
+    err = (rp['grad'] - ar.grad).abs()[~nan]
+    assert bool((err <= 1e-12 * rp['m_grad'][~nan]).all()), float((err / rp['m_grad'][~nan]).max())
+    assert bool((rp['m_grad'][~nan] >= rp['grad'][~nan].abs() * (1 - 1e-12)).all()), 'a magnitude is at least the value'
+    # the families have what their names say
+    ax1, ax2 = a[:, 0] - a[:, 2] / 2, a[:, 0] + a[:, 2] / 2
+    bx1, bx2 = b[:, 0] - b[:, 2] / 2, b[:, 0] + b[:, 2] / 2
+    ixr = torch.minimum(ax2, bx2) - torch.maximum(ax1, bx1)
+    iyr = torch.minimum(a[:, 1] + a[:, 3] / 2, b[:, 1] + b[:, 3] / 2) - torch.maximum(a[:, 1] - a[:, 3] / 2, b[:, 1] - b[:, 3] / 2)
+    for i, f in enumerate(fams):
+        if f in ('disjoint_x', 'disjoint_xy'):
+            assert ixr[i] < 0
+        if f in ('disjoint_y', 'disjoint_xy'):
+            assert iyr[i] < 0
+        if f == 'touching':
+            assert (ixr[i] == 0) != (iyr[i] == 0) and rp['iou'][i] == 0
+        if f in ('tie_left', 'tie_right'):
+            assert (ax1[i] == bx1[i]) != (ax2[i] == bx2[i]) and a[i, 1] != b[i, 1]
+        if f == 'identical_shape_shifted':
+            assert torch.equal(a[i, 2:], b[i, 2:])
+    assert any((ixr[i] == 0) for i, f in enumerate(fams) if f == 'touching') and any((iyr[i] == 0) for i, f in enumerate(fams) if f == 'touching')
+
+
+@pytest.mark.parametrize('c', LC.CASES, ids=LC.case_id)
+def test_loss_torch_form_meets_every_bound_at_half(c):
+    """The fp32 torch form of tam-tr_amd/loss.py on the CPU - the three terms and both gradients, and the matcher's cost with three diverged
+    predictions - against detr_terms / detr_match_cost on the very inputs of tests/test_gpu_loss_ref64.py: no ratio above 0.5, on every
+    family, the NaN rows checked as NaN rows."""
+    case, _ = LC.terms_ref(c)
+    got = LC.terms_of(LC.torch_form, case)
+    LC.assert_terms('host', c, got, limit=HOST_LIMIT)
+    for nonfinite in (False, True):
+        cc = LC.cost_case(c, nonfinite)
+        C = LC.cost_torch_form(cc)
+        LC.assert_cost('host' + (' nonfinite' if nonfinite else ''), c, cc, C, limit=HOST_LIMIT)
+        if nonfinite:
+            assert bool((C[0, 0, [1, 3, 4]] == 0).all()) and int((C == 0).sum()) == 3 * C.shape[-1]
+
+
+def test_loss_references_on_the_generic_families_in_float64():
+    """detr_terms against a float64 restatement of DETRLoss._layers' torch form (the same expressions without its .float() casts) on the
+    generic families: the wiring of the reference - pair lists, tables, the three sums, the upstream gradients - apart from the box
+    formulas, which the bbox_iou test holds."""
+    import torch.nn.functional as F
+    import tamtr_amd.loss as LS
+    c = (4, 3, 171, 80, [40, 0, 25], False)
+    case = LC.make_case(*c, only=LC.GENERIC)
+    Lr, B, nq, nc = case['shape']
+    n = case['n']
+    pb, ps = case['pb'].double().requires_grad_(), case['ps'].double().requires_grad_()
+    gtb, li, bi, si, gi = case['gtb'].double(), case['li'], case['bi'], case['si'], case['gi']
+    p_sel, g_sel = pb[li, bi, si], gtb[gi]
+    tg = torch.full((Lr, B, nq), nc)
+    tg[li, bi, si] = case['gtc'][gi]
+    sc = torch.zeros(Lr, B, nq, dtype=torch.float64)
+    sc[li, bi, si] = LS.bbox_iou(p_sel.detach(), g_sel, eps=R.DL_EPS).squeeze(-1)
+    one_hot = F.one_hot(tg, nc + 1)[..., :-1]
+    score = sc.unsqueeze(-1) * one_hot
+    w = 0.75 * ps.sigmoid().pow(2.0) * (1 - one_hot) + score * one_hot
+    l_cls = (F.binary_cross_entropy_with_logits(ps, score, reduction='none') * w).mean(2).sum((1, 2)) / (n / nq) * LC.GAINS_LOSS[0]
+    l_box = LC.GAINS_LOSS[1] * (p_sel - g_sel).abs().view(Lr, n, 4).sum((1, 2)) / n
+    rp = R.riou_parts(p_sel, g_sel)
+    l_iou = LC.GAINS_LOSS[2] * rp['loss'].view(Lr, n).sum(1) / n
+    gpb_cls_box, gps = torch.autograd.grad((torch.stack([l_cls, l_box]) * case['up'][:2].double()).sum(), [pb, ps])
+    gpb = gpb_cls_box.clone()
+    gpb[li, bi, si] += (case['up'][2].double() * LC.GAINS_LOSS[2] / n)[li].unsqueeze(-1) * rp['grad']
+    ref = R.detr_terms(case['pb'], case['ps'], case['gtb'], case['gtc'], li, bi, si, gi, n, LC.GAINS_LOSS, case['up'])
+    for k, t in (('class', l_cls), ('bbox', l_box), ('giou', l_iou), ('dpb', gpb), ('dps', gps)):
+        R.check(f'fp64 {k}', t.detach(), ref[k][0], ref[k][1], 0, 1e-12, log=False)
+
+
+@pytest.mark.parametrize('ddt', [torch.float32, torch.bfloat16])
+def test_box_refine_torch_formula_meets_every_bound_at_half(ddt):
+    ref, delta, cot = LC.refine_inputs(ddt)
+    d, r = delta.float().clone().requires_grad_(), ref.clone().requires_grad_()
+    y = LC.refine_torch_form(d, r)
+    (y * cot).sum().backward()
+    w = LC.assert_refine('host', ddt, ref, delta, cot, y.detach(), d.grad.to(ddt), r.grad)
+    assert w['y'] <= HOST_LIMIT and w['gr'] <= HOST_LIMIT and (w['gd'] <= HOST_LIMIT or ddt == torch.bfloat16)     # (bf16: the one rounding of the store is the bound)
+    # float64 autograd of the same formula is the reference
+    d64, r64 = delta.double().requires_grad_(), ref.double().requires_grad_()
+    x = r64.clamp(min=0, max=1)
+    y64 = torch.sigmoid(d64 + torch.log(x.clamp(min=R.REF_EPS) / (1 - x).clamp(min=R.REF_EPS)))
+    (y64 * cot.double()).sum().backward()
+    want = R.box_refine(delta, ref, cot)
+    for k, t in (('y', y64.detach()), ('gd', d64.grad), ('gr', r64.grad)):
+        R.check(f'fp64 {k}', t, want[k][0], want[k][1], 0, 1e-12, log=False)
+
+
+@pytest.mark.parametrize('c', LC.OPT_CASES, ids=LC.opt_case_id)
+def test_optim_torch_form_meets_every_bound_at_half(c):
+    """clip_grad_norm_ + torch.optim.AdamW + ModelEMA in fp32 on the CPU, from the fp32 constants the C ABI receives, against optim_step:
+    one step of every case of tests/test_gpu_loss_ref64.py, no ratio above 0.5."""
+    tensors, before, got, _ = LC.optim_run(c, LC.torch_stepper, abi_consts=True)
+    LC.assert_optim('host', c, tensors, before, got, limit=HOST_LIMIT)
+
+
+def test_optim_reference_follows_a_float64_twin_over_three_steps():
+    """optim_step chained over three steps against torch.optim.AdamW + clip_grad_norm_ + ModelEMA on a float64 twin, with constants that
+    are exact in fp32 and in double alike, so that torch's double scalars are the reference's: 1e-11 of the magnitudes."""
+    from tamtr_amd.engine import ModelEMA
+    c = (9, 'clipped', 100, False)
+    groups = ((2.0 ** -7, 0.0), (2.0 ** -9, 2.0 ** -3), (2.0 ** -11, 2.0 ** -4))
+    betas, eps, max_norm = (R.f32(0.9), R.f32(0.999)), R.f32(1e-8), R.f32(0.1)
+    tensors = LC.opt_tensors(c[0], c[1])
+    names = list(tensors)
+    net = LC.opt_module(tensors, 'cpu', torch.float64)
+    opt = LC.opt_optimizer(net, tensors, c[0], groups, betas, eps)
+    ema = ModelEMA(net, updates=99)
+    ema.decay = lambda x: R.f32(LC.ema_decay(x))
+    lr = [groups[tensors[n][0]][0] if tensors[n][0] is not None else 0.0 for n in names]
+    wd = [groups[tensors[n][0]][1] if tensors[n][0] is not None else 0.0 for n in names]
+    state = {n: [t[1].double(), t[3], t[4], t[1].double(), float(c[0])] for n, t in tensors.items()}      # p, m, v, e, step
+    g = torch.Generator().manual_seed(3)
+    for it in range(3):
+        grads = {n: (None if t[2] is None or (n == 'w3' and it == 1) else torch.randn(t[1].shape, generator=g, dtype=torch.float64) * (0.01 if it == 2 else 1.0))
+                 for n, t in tensors.items()}
+        for n in names:
+            if tensors[n][0] is not None:
+                getattr(net, n).grad = None if grads[n] is None else grads[n].clone()
+        LC.torch_stepper(net, opt, ema, max_norm)
+        ref = R.optim_step([state[n][0] for n in names], [grads[n] for n in names], [state[n][1] for n in names], [state[n][2] for n in names],
+                           [state[n][3] for n in names], [state[n][4] for n in names], lr, wd, *betas, eps, max_norm, LC.ema_decay(100 + it))
+        esd = ema.ema.state_dict()
+        for i, n in enumerate(names):
+            q = getattr(net, n)
+            R.check(f'step {it} p {n}', q.detach(), ref['p'][i][0], ref['p'][i][1] + ref['p'][i][0].abs(), 0, 1e-11, log=False)
+            R.check(f'step {it} e {n}', esd[n], ref['e'][i][0], ref['e'][i][1], 0, 1e-11, log=False)
+            state[n][0], state[n][3], state[n][4] = ref['p'][i][0], ref['e'][i][0], ref['step'][i]
+            if ref['m'][i] is not None:
+                st = opt.state[q]
+                R.check(f'step {it} m {n}', st['exp_avg'], ref['m'][i][0], ref['m'][i][1], 0, 1e-11, log=False)
+                R.check(f'step {it} v {n}', st['exp_avg_sq'], ref['v'][i][0], ref['v'][i][1], 0, 1e-11, log=False)
+                R.check(f'step {it} clipped gradient {n}', q.grad, ref['gc'][i][0], ref['gc'][i][1], 0, 1e-11, log=False)
+                assert float(st['step']) == ref['step'][i]
+                state[n][1], state[n][2] = ref['m'][i][0], ref['v'][i][0]
+    assert state['w3'][4] == c[0] + 2 and state['nograd'][4] == c[0] and state['w1'][4] == c[0] + 3
+
+
+def _fails(fn):
+    try:
+        fn()
+    except AssertionError:
+        return True
+    return False
+
+
+def test_loss_and_optimizer_mistakes_miss_their_bounds():
+    """Each mistake that the kernels could hold - stated in the reference formulas, whose output then stands in for the kernel's - misses a
+    bound on the inputs of tests/test_gpu_loss_ref64.py; the same inputs pass unmutated (the tests above).  Which check catches which
+    mistake is listed in profiles/loss_optim_ref64.txt."""
+    c = LC.CASES[1]                                       # Lr 1, 255 pairs: every family
+    case, _ = LC.terms_ref(c)
+    caught = {}
+    for mut in ('tie0', 'tie1', 'cx_gt', 'dm1_swap', 'dw075'):
+        _, bad = LC.terms_ref(c, (mut,))
+        got = {k: v[0] for k, v in bad.items()}
+        hit = [k for k in ('class', 'bbox', 'giou', 'dpb', 'dps') if _fails(lambda: R.check(k, got[k], LC.terms_ref(c)[1][k][0], LC.terms_ref(c)[1][k][1], 0,
+                                                                                               R.detr_bounds(1, 256, 7, 255)[k], log=False))]
+        caught[mut] = hit
+        assert hit == (['dps'] if mut == 'dw075' else ['dpb']), (mut, hit)
+        assert _fails(lambda: LC.assert_terms('mutant', c, got))
+    # which families see which mistake: the rows of d/d(pb) that move
+    ref = LC.terms_ref(c)[1]['dpb'][0]
+    for mut, fams in (('tie0', {'tie_left', 'tie_right', 'tie_top', 'tie_bottom', 'tie_all_but_centre', 'square_pred', 'tiny'}), ('cx_gt', {'touching'})):
+        moved = (torch.nan_to_num(LC.terms_ref(c, (mut,))[1]['dpb'][0] - ref).abs().sum(-1) > 0)[case['li'], case['bi'], case['si']]
+        assert {f for f, m in zip(case['families'], moved.tolist()) if m} == fams, mut
+    # the optimizer: the decay dropped; the scalar tail after the last quad skipped (those elements keep their old values)
+    oc = LC.OPT_CASES[1]
+    tensors, before, got, _ = LC.optim_run(oc, LC.torch_stepper, abi_consts=True)
+    LC.assert_optim('host', oc, tensors, before, got)
+    assert _fails(lambda: LC.assert_optim('mutant', oc, tensors, before, got, mut=('no_wd',))), 'a reference without the decay must not accept a step with it'
+    for name in ('w3', 'w8193', 'w1'):
+        n4 = tensors[name][1].numel() // 4 * 4
+        bad = {k: (dict(v) if isinstance(v, dict) else v) for k, v in got.items()}
+        p = got[name]['p'].clone()
+        p[n4:] = tensors[name][1][n4:]
+        bad[name]['p'] = p
+        assert _fails(lambda: LC.assert_optim('mutant', oc, tensors, before, bad)), name
