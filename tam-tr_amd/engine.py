@@ -1202,6 +1202,16 @@ class Validator:
 _EMPTY = {'precision': 0.0, 'recall': 0.0, 'mAP50': 0.0, 'mAP50-95': 0.0}
 
 
+def _cat(xs, shape, dt):
+    return np.concatenate(xs) if xs else np.zeros(shape, dt)
+
+
+def _batch_labels(lab_cls, lab_off, B, first):
+    """One batch's labels grouped by image - host arrays, or the host copy of device ones, where lab_off[0] .. lab_off[B] may be a
+    slice of a larger upload - with `first` the run's index of its first image -> target_cls [m], target_image [m]."""
+    return lab_cls[lab_off[0]:lab_off[B]], first + np.repeat(np.arange(B), np.diff(lab_off[:B + 1]))
+
+
 class DeviceValidator:
     """Validator with the per-image work on the device: update() is ops.val_postprocess_match (one launch per batch, csrc/valmatch.hip)
     plus list appends - no synchronisation; results() does one concatenation and one device-to-host copy for the whole run and feeds
@@ -1262,68 +1272,63 @@ class DeviceValidator:
         self._reduced = self._reduced_dev = None
 
     def _coco_parts(self):
-        """coco: what the run's one device-to-host copy carries for it - the head of ops.val_coco_accumulate's packed buffer (ap_tkam and
-        recall; the precision array stays behind) and the ground-truth count table - as flat uint8 device tensors."""
+        """coco: what the run's one device-to-host copy carries for it, as named parts - ap_tkam and recall as ops.val_coco_accumulate
+        returns them (views of the head of its packed buffer; the precision array stays behind) and the ground-truth count table."""
         if not self.coco or not self._coco_batches:
-            return []
+            return {}
         from . import ops
-        packed = ops.val_coco_accumulate([(b[0], c[0], c[1]) for b, c in zip(self.batches, self._coco_batches)], self._npig, self.nc,
-                                         self.coco_max_dets, return_packed=True)[-1]
-        return [packed[:80 * self.nc * len(self.coco_max_dets)].view(torch.uint8), self._npig.reshape(-1).view(torch.uint8)]
-
-    def _coco_take(self, flat):
-        """The tail of the copy that _coco_parts() put there -> self._coco_host, by the lines the host path ends in."""
-        from . import ops
-        nc, n_m = self.nc, len(self.coco_max_dets)
-        tail = flat[len(flat) - (640 * nc * n_m + 16 * nc):]
-        ap_tkam, recall, _ = ops.val_coco_split(tail[:640 * nc * n_m].view(np.float64), nc, n_m)
-        self._coco_host = coco_summary(ap_tkam, recall, self.coco_max_dets, tail[640 * nc * n_m:].view(np.int32).reshape(nc, 4))
+        ap_tkam, recall, _ = ops.val_coco_accumulate([(b[0], c[0], c[1]) for b, c in zip(self.batches, self._coco_batches)], self._npig,
+                                                     self.nc, self.coco_max_dets)
+        return {'coco_ap': ap_tkam, 'coco_recall': recall, 'npig': self._npig}
 
     def _coco_empty(self):
         nc = self.nc or 0
         return coco_summary(-np.ones((10, nc, 4, len(self.coco_max_dets))), -np.ones((10, nc, 4, len(self.coco_max_dets))), self.coco_max_dets)
 
+    def _take_riders(self, host):
+        """What rides in either reduction's copy besides its own rows: the confusion matrix and the coco parts, by the lines the host
+        path ends in."""
+        if 'matrix' in host:
+            self._matrix_host = host['matrix'].copy()
+        if 'npig' in host:
+            self._coco_host = coco_summary(host['coco_ap'], host['coco_recall'], self.coco_max_dets, host['npig'])
+
+    def _device_labels(self):
+        """The named parts of the batches whose labels live on the device."""
+        return {(k, i): t for i, b in enumerate(self.batches) if isinstance(b[3], torch.Tensor) for k, t in (('lab_cls', b[3]), ('lab_off', b[4]))}
+
+    def _labels(self, host):
+        """-> the run's target_cls [m] and target_image [m]: every batch's host labels, or the copy's views of its device labels."""
+        tcls, timage, first = [], [], 0
+        for i, (predn, _, _, lab_cls, lab_off) in enumerate(self.batches):
+            B = predn.shape[0]
+            c, im = _batch_labels(host.get(('lab_cls', i), lab_cls), host.get(('lab_off', i), lab_off), B, first)
+            tcls.append(c)
+            timage.append(im)
+            first += B
+        return _cat(tcls, (0,), np.float32), _cat(timage, (0,), np.int64)
+
     def _reduce(self):
         """-> (predn [n, 6], correct [n, 10] bool, image [n], target_cls [m], target_image [m]) as numpy, rows in image order."""
         if self._reduced is None:
-            outs = self.batches
-            dev_parts = []
-            for predn, correct, counts, lab_cls, lab_off in outs:
-                parts = [predn, correct, counts] + ([lab_cls, lab_off] if isinstance(lab_cls, torch.Tensor) else [])
-                dev_parts += [p.reshape(-1).view(torch.uint8) for p in parts]
+            from ._lib import to_host
+            parts = {(k, i): t for i, b in enumerate(self.batches) for k, t in zip(('predn', 'correct', 'counts'), b)}
+            parts.update(self._device_labels())
             if self._matrix is not None:
-                dev_parts.append(self._matrix.reshape(-1).view(torch.uint8))
-            coco_parts = self._coco_parts() if not self.device_metrics else []      # (device_metrics: _reduce_device()'s copy carries them)
-            dev_parts += coco_parts
-            flat = torch.cat(dev_parts).cpu().numpy() if dev_parts else np.zeros(0, np.uint8)   # the run's one device-to-host copy
-            if coco_parts:
-                self._coco_take(flat)
-            pos, rows, hits, image, tcls, timage, first = 0, [], [], [], [], [], 0
-
-            def take(n, dtype):
-                nonlocal pos
-                a = flat[pos:pos + n * np.dtype(dtype).itemsize].view(dtype)
-                pos += a.nbytes
-                return a
-
-            for predn, _, counts, lab_cls, lab_off in outs:
-                B, nq = predn.shape[:2]
-                pn, co, cn = take(B * nq * 6, np.float32).reshape(B, nq, 6), take(B * nq * 10, np.uint8).reshape(B, nq, 10), take(B, np.int32)
-                if isinstance(lab_cls, torch.Tensor):
-                    lab_cls, lab_off = take(lab_cls.numel(), np.float32), take(B + 1, np.int32)
-                    lab_cls, lab_off = lab_cls[lab_off[0]:lab_off[B]], lab_off - lab_off[0]
-                live = np.arange(nq)[None, :] < cn[:, None]
+                parts['matrix'] = self._matrix
+            if not self.device_metrics:      # (device_metrics: _reduce_device()'s copy carries them)
+                parts.update(self._coco_parts())
+            host = to_host(parts)            # the run's one device-to-host copy
+            self._take_riders(host)
+            rows, hits, image, first = [], [], [], 0
+            for i in range(len(self.batches)):
+                pn, co, cn = host['predn', i], host['correct', i], host['counts', i]
+                live = np.arange(pn.shape[1])[None, :] < cn[:, None]
                 rows.append(pn[live])
                 hits.append(co[live].astype(bool))
                 image.append(first + np.nonzero(live)[0])
-                tcls.append(lab_cls)
-                timage.append(first + np.repeat(np.arange(B), np.diff(lab_off)))
-                first += B
-            if self._matrix is not None:
-                self._matrix_host = take(self._matrix.numel(), np.int32).reshape(tuple(self._matrix.shape)).copy()
-            cat = lambda xs, shape, dt: np.concatenate(xs) if xs else np.zeros(shape, dt)   # noqa: E731
-            self._reduced = (cat(rows, (0, 6), np.float32), cat(hits, (0, 10), bool), cat(image, (0,), np.int64),
-                             cat(tcls, (0,), np.float32), cat(timage, (0,), np.int64))
+                first += len(cn)
+            self._reduced = (_cat(rows, (0, 6), np.float32), _cat(hits, (0, 10), bool), _cat(image, (0,), np.int64), *self._labels(host))
         return self._reduced
 
     def _reduce_device(self):
@@ -1331,39 +1336,22 @@ class DeviceValidator:
         copy: the packed result, the confusion matrix, and the labels of the batches whose labels live on the device."""
         if self._reduced_dev is None:
             from . import ops
-            nc, labs, dev_labs = self._ncls, [], []
+            from ._lib import to_host
+            nc, labs = self._ncls, []
             for _, _, _, lab_cls, lab_off in self.batches:
                 if isinstance(lab_cls, torch.Tensor):     # rows outside lab_off[0] .. lab_off[B] belong to no image: class -1, counted nowhere
                     i = torch.arange(lab_cls.numel(), device=lab_cls.device)
-                    labs.append(torch.where((i >= lab_off[0]) & (i < lab_off[-1]), lab_cls, -1.0))
-                    dev_labs += [lab_cls, lab_off]
-                else:
-                    labs.append(lab_cls)
-            packed = ops.val_ap_curves([b[:3] for b in self.batches], labs, nc, return_packed=True)[-1]
-            parts = [packed] + (dev_labs if not self.save_json else []) + ([self._matrix] if self._matrix is not None and not self.save_json else [])
-            coco_parts = self._coco_parts()
-            flat = torch.cat([p.reshape(-1).view(torch.uint8) for p in parts] + coco_parts).cpu().numpy()   # the run's one device-to-host copy
-            if coco_parts:
-                self._coco_take(flat)
-            out = ops.val_ap_split(flat[:packed.numel() * 8].view(np.float64), nc)
-            if self.save_json:                            # the records need the rows: today's copy, which also brings labels and matrix
-                tcls, timage = self._reduce()[3:]
-            else:
-                pos, tcls, timage, first = packed.numel() * 8, [], [], 0
-                for predn, _, _, lab_cls, lab_off in self.batches:
-                    B = predn.shape[0]
-                    if isinstance(lab_cls, torch.Tensor):
-                        n = lab_cls.numel()
-                        lab_cls, lab_off = flat[pos:pos + 4 * n].view(np.float32), flat[pos + 4 * n:pos + 4 * (n + B + 1)].view(np.int32)
-                        pos += 4 * (n + B + 1)
-                        lab_cls, lab_off = lab_cls[lab_off[0]:lab_off[B]], lab_off - lab_off[0]
-                    tcls.append(lab_cls)
-                    timage.append(first + np.repeat(np.arange(B), np.diff(lab_off)))
-                    first += B
+                    lab_cls = torch.where((i >= lab_off[0]) & (i < lab_off[-1]), lab_cls, -1.0)
+                labs.append(lab_cls)
+            parts = {'ap': ops.val_ap_curves([b[:3] for b in self.batches], labs, nc, return_packed=True)[-1]}
+            if not self.save_json:                        # (the records need the rows: _reduce()'s copy, which also brings labels and matrix)
+                parts.update(self._device_labels())
                 if self._matrix is not None:
-                    self._matrix_host = flat[pos:pos + 4 * self._matrix.numel()].view(np.int32).reshape(tuple(self._matrix.shape)).copy()
-                tcls, timage = np.concatenate(tcls), np.concatenate(timage)
-            self._reduced_dev = (*out, tcls, timage)
+                    parts['matrix'] = self._matrix
+            parts.update(self._coco_parts())
+            host = to_host(parts)                         # the run's one device-to-host copy
+            self._take_riders(host)
+            self._reduced_dev = (*ops.val_ap_split(host['ap'], nc), *(self._reduce()[3:] if self.save_json else self._labels(host)))
         return self._reduced_dev
 
     def _table(self, classes, p, r, ap, tcls, timage):
@@ -1379,43 +1367,38 @@ class DeviceValidator:
     def results(self, curves=False):
         """curves: the dict also carries 'curves' (ap_per_class's curves as nested lists, plus 'classes'; {} when there is nothing to reduce)."""
         extra = {'curves': {}} if curves else {}
-        if self.device_metrics:
-            if not self.batches:
-                return {**_EMPTY, 'seen': self.seen, 'per_class': [], **({'confusion_matrix': []} if self.confusion else {}),
-                        **({'coco': self._coco_empty()} if self.coco else {}), **extra}
+        stats = None      # (classes, p, r, ap, tcls, timage), unless there is nothing to reduce
+        if not self.device_metrics:
+            predn, correct, _, tcls, timage = self._reduce()
+            if (len(predn) or len(tcls)) and correct.any():
+                _, _, p, r, _, ap, classes, *cv = ap_per_class(correct, predn[:, 4], predn[:, 5], tcls, curves=curves)
+                stats = classes, p, r, ap, tcls, timage
+                if curves:
+                    extra['curves'] = curves_as_lists(cv[0], classes)
+        elif self.batches:
             ap, p_curve, r_curve, pr_curve, n_gt, n_pred, tcls, timage = self._reduce_device()
-            if self.coco:
-                extra['coco'] = self._coco_host
-            if self.save_json:
-                predn, _, image = self._reduce()[:3]
-                self.jdict = self._records(predn, image)
-            if self.confusion:
-                extra['confusion_matrix'] = self._matrix_host.tolist() if self._matrix_host is not None else []
             # `no row and no label, or no hit at all` of the host path: a hit makes the precision envelope positive at recall 0, and with
             # it the class's AP; without a hit every AP is zero
-            if not ap.any():
-                return {**_EMPTY, 'seen': self.seen, 'per_class': [], **extra}
-            has = n_gt > 0
-            classes, ap = np.nonzero(has)[0], ap[has]
-            _, _, p, r, _, f1_curve = operating_point(p_curve[has], r_curve[has], n_gt[has])
-            if curves:
-                extra['curves'] = curves_as_lists({'px': np.linspace(0, 1, 1000), 'p': p_curve[has], 'r': r_curve[has], 'f1': f1_curve,
-                                                   'pr': pr_curve[has], 'valid': n_pred[has] > 0}, classes)
-        else:
-            predn, correct, image, tcls, timage = self._reduce()
-            if self.coco:
-                extra['coco'] = self._coco_host if self._coco_host is not None else self._coco_empty()
-            if self.save_json:
-                self.jdict = self._records(predn, image)
-            if self.confusion:
-                extra['confusion_matrix'] = self._matrix_host.tolist() if self._matrix_host is not None else []
-            if (len(predn) == 0 and len(tcls) == 0) or not correct.any():
-                return {**_EMPTY, 'seen': self.seen, 'per_class': [], **extra}
-            _, _, p, r, _, ap, classes, *cv = ap_per_class(correct, predn[:, 4], predn[:, 5], tcls, curves=curves)
-            if curves:
-                extra['curves'] = curves_as_lists(cv[0], classes)
+            if ap.any():
+                has = n_gt > 0
+                classes = np.nonzero(has)[0]
+                _, _, p, r, _, f1_curve = operating_point(p_curve[has], r_curve[has], n_gt[has])
+                stats = classes, p, r, ap[has], tcls, timage
+                if curves:
+                    extra['curves'] = curves_as_lists({'px': np.linspace(0, 1, 1000), 'p': p_curve[has], 'r': r_curve[has], 'f1': f1_curve,
+                                                       'pr': pr_curve[has], 'valid': n_pred[has] > 0}, classes)
+        if self.coco:
+            extra['coco'] = self._coco_host if self._coco_host is not None else self._coco_empty()
+        if self.save_json:
+            predn, _, image = self._reduce()[:3]
+            self.jdict = self._records(predn, image)
+        if self.confusion:
+            extra['confusion_matrix'] = self._matrix_host.tolist() if self._matrix_host is not None else []
+        if stats is None:
+            return {**_EMPTY, 'seen': self.seen, 'per_class': [], **extra}
+        _, p, r, ap = stats[:4]
         return {'precision': float(p.mean()), 'recall': float(r.mean()), 'mAP50': float(ap[:, 0].mean()), 'mAP50-95': float(ap.mean()),
-                'seen': self.seen, 'per_class': self._table(classes, p, r, ap, tcls, timage), **extra}
+                'seen': self.seen, 'per_class': self._table(*stats), **extra}
 
     def _records(self, predn, image):
         """pred_to_json: image_id = the file stem; bbox = top-left x, y, w, h rounded to 3; score rounded to 5."""

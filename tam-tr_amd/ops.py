@@ -1906,6 +1906,33 @@ def _check_streams(what, streams):
     return streams
 
 
+def _check_state(what, state, wanted, note=''):
+    """Every (key, dtype, full shape) of `wanted` must be a contiguous tensor of that dtype and shape in the dict `state`; `note`
+    says in the message what fixed the shapes."""
+    for k, dt, want in wanted:
+        t = state.get(k) if isinstance(state, dict) else None
+        if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
+            got = None if t is None else (t.dtype, tuple(t.shape))
+            raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want}{note and f" ({note})"}, got {got}')
+
+
+def _check_counts(what, counts, B, name='counts'):
+    if not torch.is_tensor(counts) or tuple(counts.shape) != (B,) or counts.dtype != torch.int32:
+        got = (counts.dtype, tuple(counts.shape)) if torch.is_tensor(counts) else type(counts).__name__
+        raise _lib.TamtrHipError(f'{what}: {name} must be an int32 tensor [B] = [{B}], got {got}')
+
+
+def _workspace(what, workspace, need, device, align=None):
+    """The caller's workspace, checked (align: the pointer must be a multiple of it), or a new one of `need` bytes."""
+    if workspace is None:
+        workspace = torch.empty(need, device=device, dtype=torch.uint8)
+    require_gpu(workspace)
+    if workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous() or (align and workspace.data_ptr() % align):
+        aligned = f', {align}-byte aligned' if align else ''
+        raise _lib.TamtrHipError(f'{what}: workspace must be a contiguous{aligned} uint8 tensor of at least {need} bytes')
+    return workspace
+
+
 def bytetrack_workspace_bytes(capacity, nq, streams=None):
     """Bytes of device workspace tamtr_bytetrack_update needs for a table of `capacity` slots and nq rows per frame (no GPU call);
     streams=S: what tamtr_bytetrack_update_streams needs for S stacked tables."""
@@ -1974,9 +2001,7 @@ def reid_rows(embed, keep, counts):
     if not torch.is_tensor(keep) or keep.dim() != 2 or keep.shape[0] != B or keep.shape[1] < 1 or keep.dtype != torch.int32:
         got = (keep.dtype, tuple(keep.shape)) if torch.is_tensor(keep) else type(keep).__name__
         raise _lib.TamtrHipError(f'reid_rows: keep must be an int32 tensor [B, nq] with B = {B}, got {got}')
-    if not torch.is_tensor(counts) or tuple(counts.shape) != (B,) or counts.dtype != torch.int32:
-        got = (counts.dtype, tuple(counts.shape)) if torch.is_tensor(counts) else type(counts).__name__
-        raise _lib.TamtrHipError(f'reid_rows: counts must be an int32 tensor [B] = [{B}], got {got}')
+    _check_counts('reid_rows', counts, B)
     code = dtype_code(embed)
     require_gpu(embed, keep, counts)
     embed, keep, counts = _c(embed), _c(keep), _c(counts)
@@ -2002,13 +2027,9 @@ def botsort_reid_update(out, counts, feat, state, capacity, warps=None, track_hi
     D = int(feat.shape[2])
     if D > REID_MAX_D:
         raise _lib.TamtrHipError(f'{what}: D = {D} is above the {REID_MAX_D} the kernel is built for')
-    tf = state.get('feat') if isinstance(state, dict) else None
-    want = (() if S is None else (S,)) + (int(capacity), D)
-    if tf is None or tf.dtype != torch.float32 or tuple(tf.shape) != want or not tf.is_contiguous():
-        got = None if tf is None else (tf.dtype, tuple(tf.shape))
-        raise _lib.TamtrHipError(f"{what}: state['feat'] must be a contiguous float32 tensor of shape {want}, got {got}")
+    _check_state(what, state, [('feat', torch.float32, (() if S is None else (S,)) + (int(capacity), D))])
     return _tracker_update(what, warps, out, counts, state, capacity, track_high_thresh, track_low_thresh, new_track_thresh,
-                           match_thresh, max_time_lost, workspace, reid=(feat, tf, D, float(proximity_thresh), float(appearance_thresh)),
+                           match_thresh, max_time_lost, workspace, reid=(feat, state['feat'], D, float(proximity_thresh), float(appearance_thresh)),
                            streams=S)
 
 
@@ -2091,31 +2112,20 @@ def gmc_estimate(frames, counts, scale, state, workspace=None, stages=15, stream
     if S is not None and B % S:
         raise _lib.TamtrHipError(f'gmc_estimate: a batch of {B} frames is no multiple of streams = {S}')
     lead = () if S is None else (S,)
-    if not torch.is_tensor(counts) or tuple(counts.shape) != (B,) or counts.dtype != torch.int32:
-        got = (counts.dtype, tuple(counts.shape)) if torch.is_tensor(counts) else type(counts).__name__
-        raise _lib.TamtrHipError(f'gmc_estimate: counts must be an int32 tensor [B] = [{B}], got {got}')
+    _check_counts('gmc_estimate', counts, B)
     if not torch.is_tensor(scale):
         scale = torch.as_tensor(scale, dtype=torch.float64)
     if tuple(scale.shape) != (B, 2) or scale.dtype != torch.float64:
         raise _lib.TamtrHipError(f'gmc_estimate: scale must be float64 [B, 2] = [{B}, 2], got {scale.dtype} {tuple(scale.shape)}')
     need_st = _lib.lib().tamtr_gmc_state_bytes(H, W)
-    for k, dt, shape in (('pyr', torch.uint8, (need_st,)), ('kp', torch.int32, (GMC_SLOTS,)), ('hdr', torch.int32, (4,))):
-        t = state.get(k) if isinstance(state, dict) else None
-        if t is None or t.dtype != dt or tuple(t.shape) != lead + shape or not t.is_contiguous():
-            got = None if t is None else (t.dtype, tuple(t.shape))
-            made = f'gmc_state({H}, {W})' if S is None else f'gmc_state({H}, {W}, streams={S})'
-            raise _lib.TamtrHipError(f'gmc_estimate: state[{k!r}] must be a contiguous {dt} tensor of shape {lead + shape} ({made}), got {got}')
+    _check_state('gmc_estimate', state, (('pyr', torch.uint8, lead + (need_st,)), ('kp', torch.int32, lead + (GMC_SLOTS,)), ('hdr', torch.int32, lead + (4,))),
+                 f'gmc_state({H}, {W})' if S is None else f'gmc_state({H}, {W}, streams={S})')
     if int(stages) < 1 or int(stages) > 15:
         raise _lib.TamtrHipError(f'gmc_estimate: stages must be a mask in 1 .. 15, got {stages}')
     require_gpu(frames, counts, state['pyr'], state['kp'], state['hdr'])
     if not scale.is_cuda:
         scale = scale.to(frames.device, non_blocking=True)
-    need = gmc_workspace_bytes(B, H, W)
-    if workspace is None:
-        workspace = torch.empty(need, device=frames.device, dtype=torch.uint8)
-    require_gpu(workspace)
-    if workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
-        raise _lib.TamtrHipError(f'gmc_estimate: workspace must be a contiguous uint8 tensor of at least {need} bytes')
+    workspace = _workspace('gmc_estimate', workspace, gmc_workspace_bytes(B, H, W), frames.device)
     frames, counts, scale = _c(frames), _c(counts), _c(scale)
     warps = torch.empty(B, 2, 3, device=frames.device, dtype=torch.float64)
     stats = torch.empty(B, 4, device=frames.device, dtype=torch.int32)
@@ -2141,24 +2151,14 @@ def _tracker_update(what, warps, out, counts, state, capacity, track_high_thresh
     T = int(capacity)
     if T < 1:
         raise _lib.TamtrHipError(f'{what}: capacity must be positive, got {capacity}')
-    for k, dt, tail in TRACK_STATE_SPEC + (('hdr', torch.int32, None),):
-        t = state.get(k) if isinstance(state, dict) else None
-        want = lead + ((8,) if tail is None else (T,) + tail)
-        if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
-            got = None if t is None else (t.dtype, tuple(t.shape))
-            cap = f'capacity {T}' if S is None else f'capacity {T}, streams {S}'
-            raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want} ({cap}), got {got}')
+    _check_state(what, state, [(k, dt, lead + (T,) + tail) for k, dt, tail in TRACK_STATE_SPEC] + [('hdr', torch.int32, lead + (8,))],
+                 f'capacity {T}' if S is None else f'capacity {T}, streams {S}')
     if warps is not None and (not torch.is_tensor(warps) or tuple(warps.shape) != (B, 2, 3) or warps.dtype != torch.float64):
         got = (warps.dtype, tuple(warps.shape)) if torch.is_tensor(warps) else type(warps).__name__
         raise _lib.TamtrHipError(f'{what}: warps must be a float64 tensor [B, 2, 3] = [{B}, 2, 3], got {got}')
     require_gpu(out, counts, warps, *(state[k] for k in ('mean', 'cov', 'meta', 'sc', 'hdr')), *(reid[:2] if reid else ()))
     warps = _c(warps) if warps is not None else None
-    need = botsort_reid_workspace_bytes(T, nq, S) if reid else bytetrack_workspace_bytes(T, nq, S)
-    if workspace is None:
-        workspace = torch.empty(need, device=out.device, dtype=torch.uint8)
-    require_gpu(workspace)
-    if workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
-        raise _lib.TamtrHipError(f'{what}: workspace must be a contiguous uint8 tensor of at least {need} bytes')
+    workspace = _workspace(what, workspace, botsort_reid_workspace_bytes(T, nq, S) if reid else bytetrack_workspace_bytes(T, nq, S), out.device)
     out, counts = _c(out), _c(counts)
     tracks = torch.empty(B, nq, 8, device=out.device, dtype=torch.float32)
     tcounts = torch.empty(B, device=out.device, dtype=torch.int32)
@@ -2222,9 +2222,7 @@ def _eval_streams(what, B, streams, active):
         return S, None
     if S is None:
         raise _lib.TamtrHipError(f'{what}: active belongs to a stacked evaluator (streams=S)')
-    if not torch.is_tensor(active) or tuple(active.shape) != (B,) or active.dtype != torch.int32:
-        got = (active.dtype, tuple(active.shape)) if torch.is_tensor(active) else type(active).__name__
-        raise _lib.TamtrHipError(f'{what}: active must be an int32 tensor [B] = [{B}], got {got}')
+    _check_counts(what, active, B, 'active')
     require_gpu(active)
     return S, _c(active)
 
@@ -2250,24 +2248,9 @@ def _eval_state(what, spec, cap_names, state, nc, caps, streams=None):
     caps = tuple(int(c) for c in caps)
     if int(nc) < 1 or len(caps) != len(cap_names) or min(caps) < 1:
         raise _lib.TamtrHipError(f'{what}: nc and the {len(cap_names)} capacities ({", ".join(cap_names)}) must be positive, got {nc} and {caps}')
-    for k, dt, shape in spec:
-        t = state.get(k) if isinstance(state, dict) else None
-        want = lead + shape(int(nc), caps)
-        if t is None or t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
-            got = None if t is None else (t.dtype, tuple(t.shape))
-            stack = '' if streams is None else f' (streams {streams})'
-            raise _lib.TamtrHipError(f'{what}: state[{k!r}] must be a contiguous {dt} tensor of shape {want}{stack}, got {got}')
+    _check_state(what, state, [(k, dt, lead + shape(int(nc), caps)) for k, dt, shape in spec], '' if streams is None else f'streams {streams}')
     require_gpu(*(state[k] for k, _, _ in spec))
     return (ctypes.c_void_p * len(spec))(*(state[k].data_ptr() for k, _, _ in spec)), (ctypes.c_int * len(caps))(*caps)
-
-
-def _eval_workspace(what, workspace, need, device):
-    if workspace is None:
-        workspace = torch.empty(need, device=device, dtype=torch.uint8)
-    require_gpu(workspace)
-    if workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous() or workspace.data_ptr() % 16:
-        raise _lib.TamtrHipError(f'{what}: workspace must be a contiguous, 16-byte aligned uint8 tensor of at least {need} bytes')
-    return workspace
 
 
 def mot_update(tracks, tcounts, gt, gcounts, state, nc, gt_capacity, track_capacity, iou=0.5, workspace=None, streams=None, active=None):
@@ -2285,7 +2268,7 @@ def mot_update(tracks, tcounts, gt, gcounts, state, nc, gt_capacity, track_capac
     nc, G, T = int(nc), int(gt_capacity), int(track_capacity)
     _eval_state('mot_update', MOT_STATE_SPEC, MOT_CAPS, state, nc, (G, T), S)
     require_gpu(tracks, tcounts, gt, gcounts)
-    workspace = _eval_workspace('mot_update', workspace, mot_workspace_bytes(nq, ng, nc, G, T, S), tracks.device)
+    workspace = _workspace('mot_update', workspace, mot_workspace_bytes(nq, ng, nc, G, T, S), tracks.device, align=16)
     call('tamtr_mot_update_streams', ptr(tracks), ptr(tcounts), ptr(gt), ptr(gcounts), B, S or 1, nq, ng, nc, float(iou), ptr(active),
          ptr(state['gstate']), ptr(state['counts']), ptr(state['iou_sum']), ptr(state['pair']), ptr(state['hdr']), G, T, ptr(workspace),
          int(workspace.numel()), stream_ptr())
@@ -2308,7 +2291,7 @@ def mot_end_sequence(state, nc, gt_capacity, track_capacity, gt_used, workspace=
             raise _lib.TamtrHipError(f'mot_end_sequence: gt_used must be an int32 tensor [S] = [{S}], got None')
         ending, gt_used = _eval_masks('mot_end_sequence', S, ending=ending, gt_used=gt_used)
     _eval_state('mot_end_sequence', MOT_STATE_SPEC, MOT_CAPS, state, nc, (G, T), S)
-    workspace = _eval_workspace('mot_end_sequence', workspace, mot_workspace_bytes(1, 1, nc, G, T, S), state['hdr'].device)
+    workspace = _workspace('mot_end_sequence', workspace, mot_workspace_bytes(1, 1, nc, G, T, S), state['hdr'].device, align=16)
     if S is None:      # the host's scalar goes as it is: no upload
         call('tamtr_mot_end_sequence', nc, ptr(state['gstate']), ptr(state['counts']), ptr(state['pair']), ptr(state['hdr']), G, T,
              min(int(gt_used), G), ptr(workspace), int(workspace.numel()), stream_ptr())
@@ -2359,7 +2342,7 @@ def hota_update(tracks, tcounts, gt, gcounts, state, nc, caps, iou=0.5, workspac
     S, active = _eval_streams('hota_update', B, streams, active)
     ptrs, ccaps = _eval_state('hota_update', HOTA_STATE_SPEC, HOTA_CAPS, state, nc, caps, S)
     require_gpu(tracks, tcounts, gt, gcounts)
-    workspace = _eval_workspace('hota_update', workspace, hota_workspace_bytes(nq, ng, 1, S), tracks.device)
+    workspace = _workspace('hota_update', workspace, hota_workspace_bytes(nq, ng, 1, S), tracks.device, align=16)
     call('tamtr_hota_update_streams', ptr(tracks), ptr(tcounts), ptr(gt), ptr(gcounts), B, S or 1, nq, ng, int(nc), float(iou), HOTA_EPS,
          ptr(active), ptrs, ccaps, ptr(workspace), int(workspace.numel()), stream_ptr())
 
@@ -2378,7 +2361,7 @@ def hota_end_sequence(state, nc, caps, nq, ng, workspace=None, workgroups=None, 
         raise _lib.TamtrHipError('hota_end_sequence: ending belongs to a stacked evaluator (streams=S)')
     ending, = _eval_masks('hota_end_sequence', S, ending=ending)
     ptrs, ccaps = _eval_state('hota_end_sequence', HOTA_STATE_SPEC, HOTA_CAPS, state, nc, caps, S)
-    workspace = _eval_workspace('hota_end_sequence', workspace, hota_workspace_bytes(nq, ng, workgroups, S), state['hdr'].device)
+    workspace = _workspace('hota_end_sequence', workspace, hota_workspace_bytes(nq, ng, workgroups, S), state['hdr'].device, align=16)
     import numpy as np
     alpha = (ctypes.c_double * 19)(*np.arange(0.05, 0.99, 0.05))   # the thresholds as TrackEval makes them, never k / 20
     call('tamtr_hota_end_streams', alpha, HOTA_EPS, int(nc), S or 1, ptr(ending), nq, ng, workgroups, ptrs, ccaps, ptr(workspace),
@@ -2415,7 +2398,7 @@ def trackmap_update(tracks, tcounts, gt, gcounts, state, nc, caps, iou=0.5, work
     B, nq, ng, tracks, tcounts, gt, gcounts = _mot_frames('trackmap_update', tracks, tcounts, gt, gcounts, iou)
     ptrs, ccaps = _eval_state('trackmap_update', TRACKMAP_STATE_SPEC, TRACKMAP_CAPS, state, nc, caps)
     require_gpu(tracks, tcounts, gt, gcounts)
-    workspace = _eval_workspace('trackmap_update', workspace, trackmap_workspace_bytes(nq, ng, nc, caps), tracks.device)
+    workspace = _workspace('trackmap_update', workspace, trackmap_workspace_bytes(nq, ng, nc, caps), tracks.device, align=16)
     call('tamtr_trackmap_update', ptr(tracks), ptr(tcounts), ptr(gt), ptr(gcounts), B, nq, ng, int(nc), float(iou), ptrs, ccaps,
          ptr(workspace), int(workspace.numel()), stream_ptr())
 
@@ -2434,7 +2417,7 @@ def trackmap_end_sequence(state, nc, caps, thresholds, workspace=None):
     fp64 values, handed over as they are.  No synchronisation."""
     thr = _trackmap_thresholds('trackmap_end_sequence', thresholds)
     ptrs, ccaps = _eval_state('trackmap_end_sequence', TRACKMAP_STATE_SPEC, TRACKMAP_CAPS, state, nc, caps)
-    workspace = _eval_workspace('trackmap_end_sequence', workspace, trackmap_workspace_bytes(1, 1, nc, caps), state['hdr'].device)
+    workspace = _workspace('trackmap_end_sequence', workspace, trackmap_workspace_bytes(1, 1, nc, caps), state['hdr'].device, align=16)
     call('tamtr_trackmap_end_sequence', (ctypes.c_double * len(thr))(*thr), len(thr), HOTA_EPS, int(nc), ptrs, ccaps, ptr(workspace),
          int(workspace.numel()), stream_ptr())
 
@@ -2677,12 +2660,7 @@ def val_coco_match(predn, counts, device_labels, nc, max_det, npig, workspace=No
             or d_off.numel() != B + 1 or d_scale.numel() != 4 * B or d_box.numel() != 4 * M
             or any(t.dtype != torch.float32 for t in (d_cls, d_box, d_scale))):
         raise _lib.TamtrHipError(f'val_coco_match: npig must be contiguous i32 [{nc}, 4] and the labels those of val_postprocess_match')
-    need = val_coco_workspace_bytes(B, nq, M)
-    if workspace is None:
-        workspace = torch.empty(need, device=predn.device, dtype=torch.uint8)
-    require_gpu(workspace)
-    if workspace.dtype != torch.uint8 or workspace.numel() < need or not workspace.is_contiguous():
-        raise _lib.TamtrHipError(f'val_coco_match: workspace must be a contiguous uint8 tensor of at least {need} bytes')
+    workspace = _workspace('val_coco_match', workspace, val_coco_workspace_bytes(B, nq, M), predn.device)
     predn, counts, d_cls, d_box, d_off, d_scale = _c(predn), _c(counts), _c(d_cls), _c(d_box), _c(d_off), _c(d_scale)
     bits = torch.empty(B, nq, 4, device=predn.device, dtype=torch.int32)
     rank = torch.empty(B, nq, device=predn.device, dtype=torch.int32)

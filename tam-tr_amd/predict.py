@@ -87,6 +87,42 @@ def stream_batches(files_per_stream, frames_per_stream=1):
     return batches
 
 
+def _as_list(evaluator):
+    """One evaluator, a list / tuple of them or None -> a list."""
+    return list(evaluator) if isinstance(evaluator, (list, tuple)) else [] if evaluator is None else [evaluator]
+
+
+def _pad_gt(gt, n):
+    """A sequence's per-frame ground truth for n frames: cut to them, missing frames empty."""
+    gt = list(gt)[:n]
+    return gt + [np.zeros((0, 7), np.float32)] * (n - len(gt))
+
+
+def sequence_records(files, batch, gt=None):
+    """What Predictor's batch loop runs on for ONE sequence: [(paths, active, gt_frames, ending)] per batch, plain chunks of `batch`
+    files - no padding (active is None) and the last chunk may be short.  gt_frames: the chunk's slice of `gt` (_pad_gt), or None
+    without gt; ending is empty: track() ends the sequence after the last frame.  Pure: touches no file."""
+    gt = None if gt is None else _pad_gt(gt, len(files))
+    return [(files[i:i + batch], None, None if gt is None else gt[i:i + batch], []) for i in range(0, len(files), batch)]
+
+
+def stream_records(files_per_stream, frames_per_stream=1, gt=None):
+    """The same for S sequences at once, over stream_batches: active is its mask; gt_frames (gt: S entries, a sequence's frames or
+    None for a stream that is not scored) holds None for padding and for unscored streams, which are no frames to the evaluators;
+    ending: the scored streams whose last frame lies in this batch."""
+    files = [list(f) for f in files_per_stream]
+    S, F = len(files), int(frames_per_stream)
+    gts = None if gt is None else [None if g is None else _pad_gt(g, len(f)) for g, f in zip(gt, files)]
+    records = []
+    for k, (paths, active) in enumerate(stream_batches(files, frames_per_stream)):
+        frames, ending = None, []
+        if gts is not None:      # image f * S + s is frame k * F + f of stream s
+            frames = [gts[i % S][k * F + i // S] if active[i] and gts[i % S] is not None else None for i in range(len(paths))]
+            ending = [s for s, g in enumerate(gts) if g and (len(g) - 1) // F == k]
+        records.append((paths, active, frames, ending))
+    return records
+
+
 def to_model_input(ims_u8, device, keep_u8=False):
     """u8 [B, S, S, 3] host batch -> f32 [B, 3, S, S] / 255 on the device (engine/predictor.py:111-129: RGB, CHW, float, / 255).
     keep_u8: -> (that, the u8 batch as it was uploaded), which BoT-SORT's camera-motion estimate reads."""
@@ -233,10 +269,8 @@ class Predictor:
         if active is not None:      # the counts mask
             counts = counts * torch.as_tensor(active, dtype=torch.int32).to(self.device, non_blocking=True)
         # one device-to-host copy for all the outputs
-        B, nq = keep.shape
-        parts = [out.view(-1), keep.view(torch.float32).view(-1), counts.view(torch.float32)]
-        evaluators = list(evaluator) if isinstance(evaluator, (list, tuple)) else [] if evaluator is None else [evaluator]
-        scoring = tracker is not None and bool(evaluators) and gt_frames is not None
+        parts = {'out': out, 'keep': keep, 'counts': counts}
+        evaluators = _as_list(evaluator) if tracker is not None and gt_frames is not None else []
         ev_eval = []
         ev_gmc = None
         if tracker is not None:
@@ -248,36 +282,30 @@ class Predictor:
                 tracks, tcounts = tracker.update(out, counts, warps=warps, **self._reid_operands(reid, keep))
             else:
                 tracks, tcounts = tracker.update(out, counts, **self._reid_operands(reid, keep))
-            parts += [tracks.view(-1), tcounts.view(torch.float32), tracker.state['hdr'].view(torch.float32).view(-1)]
-            for e in evaluators if scoring else []:
+            parts.update(tracks=tracks, tcounts=tcounts, hdr=tracker.state['hdr'])      # hdr: 8 words, per stream of a stacked tracker
+            for i, e in enumerate(evaluators):
                 ev_eval.append(torch.cuda.Event(enable_timing=True))
                 ev_eval[-1].record()
                 e.update(tracks, tcounts, gt_frames)
-                parts.append(e.state['hdr'].view(torch.float32).view(-1))
+                parts['ehdr', i] = e.state['hdr']
         ev[4].record()
-        packed = torch.cat(parts)
-        host = torch.empty(packed.shape, dtype=torch.float32, pin_memory=True)
-        host.copy_(packed, non_blocking=True)
-        ev[5].record()
+        host = {k: torch.from_numpy(a) for k, a in ops._lib.to_host(parts, pinned=True, record=ev[5]).items()}
         ev[5].synchronize()
         spans = [('h2d', ev[0], ev[1]), ('forward', ev[1], ev[2]), ('postprocess', ev[2], ev[3]), ('track', ev_gmc or ev[3], (ev_eval + [ev[4]])[0]),
                  ('d2h', ev[4], ev[5])] + ([('gmc', ev[3], ev_gmc)] if ev_gmc is not None else [])
-        for i, e in enumerate(evaluators if scoring else []):
+        for i, e in enumerate(evaluators):
             spans.append((e.times_key, ev_eval[i], (ev_eval + [ev[4]])[i + 1]))
         for k, a, b in spans:
             self.times[k] = self.times.get(k, 0.0) + a.elapsed_time(b)
         if self.keep_raw:
             self.last_img, self.last_y = img, y
-        o, kp, c, rest = host.split([B * nq * 6, B * nq, B, host.numel() - B * nq * 7 - B])
-        res = o.view(B, nq, 6), kp.view(torch.int32).view(B, nq), c.view(torch.int32)
+        res = host['out'], host['keep'], host['counts']
         if tracker is None:
             return res
-        n_hdr = tracker.state['hdr'].numel()      # 8 words, per stream of a stacked tracker
-        tr, tc, hdr, *ehdr = rest.split([B * nq * 8, B, n_hdr] + [e.state['hdr'].numel() for e in evaluators if scoring])
-        tracker.check_overflow(hdr.view(torch.int32).view(-1, 8)[:, 3])
-        for e, h in zip(evaluators, ehdr):
-            e.check_overflow(h.view(torch.int32))
-        return res + (tr.view(B, nq, 8), tc.view(torch.int32))
+        tracker.check_overflow(host['hdr'].view(-1, 8)[:, 3])
+        for i, e in enumerate(evaluators):
+            e.check_overflow(host['ehdr', i].view(-1))
+        return res + (host['tracks'], host['tcounts'])
 
     def _reid_operands(self, reid, keep):
         """For a BotSort with ReID: the decoder's per-query hidden state of this forward (head.keep_query_embed) and the source query
@@ -291,7 +319,8 @@ class Predictor:
 
     def predict(self, source):
         """Yields one Detections per image, in the sorted order of list_sources(source)."""
-        yield from self._run(list_sources(source), None)
+        for _, det in self._run(sequence_records(list_sources(source), self.batch)):
+            yield det
 
     def track(self, source, tracker=None, persist=False, gt=None, evaluator=None):
         """The sorted files of `source` as ONE sequence (the reference's model.track): the batches of predict, then one tracker launch
@@ -309,14 +338,7 @@ class Predictor:
         every batch's rows are scored on the device right after the tracker's launch, by each evaluator in turn (a frame without track
         rows is an empty track set, as write_mot has it), the sequence is ended after the last frame, and speed() has an entry per
         evaluator ('mot', 'hota', 'tmap'); each evaluator's results() then holds the metrics.  Without both, nothing changes."""
-        from .track import ByteTracker, tracker_from_yaml
-        if isinstance(tracker, ByteTracker):
-            self.tracker = tracker
-            if not persist:
-                tracker.reset()
-        elif self.tracker is None or not persist:
-            head = self.model.model[-1]
-            self.tracker = tracker_from_yaml(tracker, self.device, reid_dim=head.hidden_dim) if tracker else ByteTracker(self.device)
+        self._install_tracker(tracker, persist)
         files = list_sources(source)
         if getattr(self.tracker, 'with_reid', False):
             yield from self._with_query_embed(self._track(files, gt, evaluator))
@@ -341,12 +363,11 @@ class Predictor:
         evaluator ('mot', 'hota').  A stream is ended right after the batch that holds its last frame, all streams ending there in
         one call; stream_counts(s) and results() then hold the metrics.  Without both, nothing changes.
         The arguments are checked when this is called, before the first frame is asked for."""
-        from .track import ByteTracker, tracker_from_yaml
         sources = list(sources) if isinstance(sources, (list, tuple)) else None
         if not sources:
             raise ValueError('track_streams needs a non-empty list of sources, one per stream')
         S = len(sources)
-        evaluators = list(evaluator) if isinstance(evaluator, (list, tuple)) else [] if evaluator is None else [evaluator]
+        evaluators = _as_list(evaluator)
         for e in evaluators:
             if getattr(e, 'times_key', None) not in ('mot', 'hota') or getattr(e, 'streams', None) != S:
                 raise ValueError(f'track_streams scores {S} sources with a MotEvaluator / HotaEvaluator built with streams={S}, got '
@@ -355,62 +376,34 @@ class Predictor:
             gt = list(gt) if isinstance(gt, (list, tuple)) else None
             if gt is None or len(gt) != S:
                 raise ValueError(f'gt must be a list of {S} entries, one per source (per-frame arrays, or None for a stream that is not scored)')
+        self._install_tracker(tracker, persist, streams=S)
+        evaluators = evaluators if gt is not None else []
+        records = stream_records([list_sources(src) for src in sources], frames_per_stream, gt if evaluators else None)
+        self._prune_times(evaluators)
+        frames = self._run(records, self.tracker, evaluators, S)
+        return self._with_query_embed(frames) if getattr(self.tracker, 'with_reid', False) else frames
+
+    def _install_tracker(self, tracker, persist, streams=None):
+        """self.tracker for a run of track() (streams=None) or track_streams() (streams=S): the given instance, reset unless persist;
+        else the previous call's with persist, when it has these streams; else a new one from the yaml path or ByteTrack's defaults."""
+        from .track import ByteTracker, tracker_from_yaml
         if isinstance(tracker, ByteTracker):
-            if tracker.streams != S:
-                raise ValueError(f'the tracker was built with streams={tracker.streams!r}, {S} sources need streams={S}')
+            if streams is not None and tracker.streams != streams:
+                raise ValueError(f'the tracker was built with streams={tracker.streams!r}, {streams} sources need streams={streams}')
             self.tracker = tracker
             if not persist:
                 tracker.reset()
-        elif not (persist and isinstance(self.tracker, ByteTracker) and self.tracker.streams == S):
+        elif not persist or (self.tracker is None if streams is None else getattr(self.tracker, 'streams', None) != streams):
+            kw = {} if streams is None else {'streams': streams}
             head = self.model.model[-1]
-            self.tracker = tracker_from_yaml(tracker, self.device, reid_dim=head.hidden_dim, streams=S) if tracker else ByteTracker(self.device, streams=S)
-        files = [list_sources(src) for src in sources]
-        batches = stream_batches(files, frames_per_stream)
-        scoring = gt is not None and bool(evaluators)
-        for k in {'mot', 'hota', 'tmap'} - ({e.times_key for e in evaluators} if scoring else set()):
+            self.tracker = tracker_from_yaml(tracker, self.device, reid_dim=head.hidden_dim, **kw) if tracker else ByteTracker(self.device, **kw)
+
+    def _prune_times(self, evaluators):
+        """An evaluator's key of times exists only while a run is scored by it, the estimator's only while a BotSort run is in progress."""
+        for k in {'mot', 'hota', 'tmap'} - {e.times_key for e in evaluators}:
             self.times.pop(k, None)
         if getattr(self.tracker, 'gmc_method', None) != 'sparseOptFlow':
             self.times.pop('gmc', None)
-        score = None
-        if scoring:      # per stream: its frames' ground truth (missing frames are empty), or None for a stream that is not scored
-            empty = np.zeros((0, 7), np.float32)
-            score = ([None if g is None else (list(g)[:len(f)] + [empty] * (len(f) - len(g))) for g, f in zip(gt, files)], evaluators)
-        frames = self._run_streams(batches, S, int(frames_per_stream), score)
-        return self._with_query_embed(frames) if getattr(self.tracker, 'with_reid', False) else frames
-
-    def _run_streams(self, batches, S, F=1, score=None):
-        with ThreadPoolExecutor(max_workers=self.workers) as pool:
-            def submit(paths):      # a padding entry shares its path's load
-                jobs = {f: pool.submit(load_image, f, self.imgsz) for f in dict.fromkeys(paths)}
-                return [jobs[f] for f in paths]
-            pending = submit(batches[0][0]) if batches else []
-            for k, (paths, active) in enumerate(batches):
-                t0 = time.perf_counter()
-                loaded = [f.result() for f in pending]
-                self.times['load'] += (time.perf_counter() - t0) * 1e3
-                pending = submit(batches[k + 1][0]) if k + 1 < len(batches) else []
-                origs = [o for o, _ in loaded]
-                hw = [o.shape[:2] for o in origs]
-                if score is None:
-                    res = self.run_batch((np.stack([r for _, r in loaded]), hw), self.tracker, active=active)
-                else:      # image f * S + s is frame k * F + f of stream s; padding and unscored streams are no frames to the evaluators
-                    gts, evaluators = score
-                    frames = [gts[i % S][k * F + i // S] if active[i] and gts[i % S] is not None else None for i in range(len(paths))]
-                    res = self.run_batch((np.stack([r for _, r in loaded]), hw), self.tracker, frames, evaluators, active=active)
-                    ending = [s for s, g in enumerate(gts) if g and (len(g) - 1) // F == k]
-                    for e in evaluators if ending else []:
-                        e.end_sequence(ending)
-                out, counts = res[0], res[2]
-                self.seen += sum(active)
-                for i, path in enumerate(paths):
-                    if not active[i]:
-                        continue
-                    n, nt = int(counts[i]), int(res[4][i])
-                    if nt:
-                        rows = res[3][i, :nt]
-                        yield i % S, Detections(path, hw[i], self.names, rows[:, [0, 1, 2, 3, 5, 6]].clone(), orig_img=origs[i], id=rows[:, 4].long())
-                    else:
-                        yield i % S, Detections(path, hw[i], self.names, out[i, :n].clone(), orig_img=origs[i])
 
     def _with_query_embed(self, frames):
         head = self.model.model[-1]
@@ -423,46 +416,46 @@ class Predictor:
             head.keep_query_embed = was
 
     def _track(self, files, gt, evaluator):
-        evaluators = list(evaluator) if isinstance(evaluator, (list, tuple)) else [] if evaluator is None else [evaluator]
-        for k in {'mot', 'hota', 'tmap'} - ({e.times_key for e in evaluators} if gt is not None else set()):
-            self.times.pop(k, None)          # an evaluator's key exists only while a run is scored by it
-        if getattr(self.tracker, 'gmc_method', None) != 'sparseOptFlow':
-            self.times.pop('gmc', None)      # and the estimator's only while a BotSort run is in progress
-        if gt is None or not evaluators:
-            yield from self._run(files, self.tracker)
-            return
-        gt = list(gt)[:len(files)]
-        gt += [np.zeros((0, 7), np.float32)] * (len(files) - len(gt))
-        yield from self._run(files, self.tracker, gt, evaluators)
+        evaluators = _as_list(evaluator) if gt is not None else []
+        self._prune_times(evaluators)
+        for _, det in self._run(sequence_records(files, self.batch, gt if evaluators else None), self.tracker, evaluators):
+            yield det
         for e in evaluators:
             e.end_sequence()
 
-    def _run(self, files, tracker, gt=None, evaluator=None):
+    def _run(self, records, tracker=None, evaluators=(), S=1):
+        """The batch loop of predict, track and track_streams over sequence_records / stream_records: yields (stream index, Detections)
+        for every image that is not padding.  The next batch decodes while this one runs on the GPU."""
         with ThreadPoolExecutor(max_workers=self.workers) as pool:
-            chunks = [files[i:i + self.batch] for i in range(0, len(files), self.batch)]
-            pending = [pool.submit(load_image, f, self.imgsz) for f in chunks[0]] if chunks else []
-            for k, chunk in enumerate(chunks):
+            def submit(k):      # a padding entry shares its path's load
+                paths = records[k][0] if k < len(records) else []
+                jobs = {f: pool.submit(load_image, f, self.imgsz) for f in dict.fromkeys(paths)}
+                return [jobs[f] for f in paths]
+            pending = submit(0)
+            for k, (paths, active, gt_frames, ending) in enumerate(records):
                 t0 = time.perf_counter()
                 loaded = [f.result() for f in pending]
                 self.times['load'] += (time.perf_counter() - t0) * 1e3
-                # the next batch decodes while this one runs on the GPU
-                pending = [pool.submit(load_image, f, self.imgsz) for f in chunks[k + 1]] if k + 1 < len(chunks) else []
+                pending = submit(k + 1)
                 origs = [o for o, _ in loaded]
                 hw = [o.shape[:2] for o in origs]
                 ims = (np.stack([r for _, r in loaded]), hw)
-                if evaluator is None:
-                    res = self.run_batch(ims, tracker)
-                else:
-                    res = self.run_batch(ims, tracker, gt[k * self.batch:k * self.batch + len(chunk)], evaluator)
+                more = {} if active is None else {'active': active}
+                res = self.run_batch(ims, tracker, **more) if gt_frames is None else self.run_batch(ims, tracker, gt_frames, evaluators, **more)
+                for e in evaluators if ending else []:
+                    e.end_sequence(ending)
                 out, counts = res[0], res[2]
-                self.seen += len(chunk)
-                for i, path in enumerate(chunk):
+                live = [True] * len(paths) if active is None else active
+                self.seen += sum(live)
+                for i, path in enumerate(paths):
+                    if not live[i]:
+                        continue
                     n, nt = int(counts[i]), int(res[4][i]) if tracker is not None else 0
                     if nt:
                         rows = res[3][i, :nt]
-                        yield Detections(path, hw[i], self.names, rows[:, [0, 1, 2, 3, 5, 6]].clone(), orig_img=origs[i], id=rows[:, 4].long())
+                        yield i % S, Detections(path, hw[i], self.names, rows[:, [0, 1, 2, 3, 5, 6]].clone(), orig_img=origs[i], id=rows[:, 4].long())
                     else:
-                        yield Detections(path, hw[i], self.names, out[i, :n].clone(), orig_img=origs[i])
+                        yield i % S, Detections(path, hw[i], self.names, out[i, :n].clone(), orig_img=origs[i])
 
     def __call__(self, source):
         return list(self.predict(source))

@@ -100,11 +100,33 @@ def check_streams(streams):
     return streams
 
 
-class ByteTracker:
+class _Stacked:
+    """What a tracker and an evaluator built with streams=S share: `state`, a dict of device tensors that each gain a leading S."""
+    _noun = streams = None
+
+    @property
+    def _lead(self):
+        """The leading dimension of every state tensor: none without streams, (S,) for a stack."""
+        return () if self.streams is None else (self.streams,)
+
+    def _stream(self, stream):
+        if self.streams is None or isinstance(stream, bool) or not isinstance(stream, (int, np.integer)) or not 0 <= stream < self.streams:
+            raise ValueError(f'stream must be in 0 .. {self.streams - 1}, got {stream!r}' if self.streams else
+                             f'stream={stream!r} was given to {self._noun} built without streams')
+        return int(stream)
+
+    def stream_state(self, s):
+        """Stream s's state as views state[k][s]: contiguous, so the ops without streams take them as they are."""
+        s = self._stream(s)
+        return {k: v[s] for k, v in self.state.items()}
+
+
+class ByteTracker(_Stacked):
     """One tracker = one slot table of `capacity` tracks on `device` (ids start at 1).  nq is the number of rows per frame the
     workspace is sized for; a batch with more rows gets a larger workspace on its first use.
     streams=S: S trackers, one per stream, in one stacked table (every state tensor gains a leading S) and one launch; update()
     then takes the frame-major batch (image f * S + s is the f-th frame of stream s) and every stream's ids start at 1."""
+    _noun = 'a tracker'
 
     def __init__(self, device, track_high_thresh=0.5, track_low_thresh=0.1, new_track_thresh=0.6, track_buffer=30, match_thresh=0.8,
                  frame_rate=30, capacity=1024, nq=300, streams=None):
@@ -129,17 +151,6 @@ class ByteTracker:
     def from_yaml(cls, path, device, **kw):
         return cls(device, **{**read_tracker_yaml(path), **kw})
 
-    @property
-    def _lead(self):
-        """The leading dimension of every state tensor: none for one tracker, (S,) for a stack."""
-        return () if self.streams is None else (self.streams,)
-
-    def _stream(self, stream):
-        if self.streams is None or isinstance(stream, bool) or not isinstance(stream, int) or not 0 <= stream < self.streams:
-            raise ValueError(f'stream must be in 0 .. {self.streams - 1}, got {stream!r}' if self.streams else
-                             f'stream={stream!r} was given to a tracker built without streams')
-        return stream
-
     def reset(self, stream=None):
         """Forget every track; the next id is 1 again.  stream=s: of that stream's tracker alone.  No synchronisation."""
         if stream is None:
@@ -158,11 +169,6 @@ class ByteTracker:
         if out.dim() == 3 and out.shape[1] > self.nq:
             self.nq = out.shape[1]
             self.workspace = torch.empty(self._ws_bytes(), device=self.device, dtype=torch.uint8)
-
-    def stream_state(self, s):
-        """Stream s's table as views state[k][s]: contiguous, so the single-tracker ops take them as they are."""
-        s = self._stream(s)
-        return {k: v[s] for k, v in self.state.items()}
 
     def update(self, out, counts):
         """out f32 [B, nq, 6], counts i32 [B] on the device (ops.detect_postprocess) -> tracks f32 [B, nq, 8] (x1 y1 x2 y2 id score
@@ -226,7 +232,6 @@ class BotSort(ByteTracker):
 
     def __init__(self, device, gmc_method='sparseOptFlow', proximity_thresh=0.5, appearance_thresh=0.25, with_reid=False, reid_dim=None,
                  streams=None, **kw):
-        self.streams = check_streams(streams)
         method = 'none' if gmc_method is None else str(gmc_method)
         if method not in GMC_BUILT:
             raise ValueError(f"gmc_method {gmc_method!r} is not built: 'sparseOptFlow' (estimated on the device) and 'none' are; the "
@@ -402,7 +407,7 @@ def pack_gt(gt_frames, ng, nc, rows):
     return buf
 
 
-class _SequenceEvaluator:
+class _SequenceEvaluator(_Stacked):
     """What the tracking evaluators share: the state on `device`, the ground truth's way up, one update launch per batch and the
     bookkeeping of the sequence in progress.  A subclass names its host path, its state spec and capacities in ops, the offset of its
     overflow counters in hdr with what each counts and the exception they raise, and supplies _ws_bytes, _launch_update and
@@ -411,6 +416,7 @@ class _SequenceEvaluator:
     and `open` are lists with an entry per stream - and still one update launch per batch, one workgroup per stream.  update() then
     takes the frame-major batch (image f * S + s is the f-th frame of stream s, as ByteTracker(streams=S) leaves it)."""
     host = spec = cap_names = hdr_over = over = overflow = None
+    _noun = 'an evaluator'
 
     def __init__(self, device, nc, iou, caps, nq, ng, streams=None):
         self.streams = check_streams(streams)
@@ -426,19 +432,8 @@ class _SequenceEvaluator:
         self.state = {k: torch.zeros(self._lead + shape(self.nc, self.caps), device=self.device, dtype=dt) for k, dt, shape in self.spec}
         self._fresh()
 
-    @property
-    def _lead(self):
-        """The leading dimension of every state tensor: none for one evaluator, (S,) for a stack."""
-        return () if self.streams is None else (self.streams,)
-
     def _fresh(self):
         self.rows, self.open = ({}, False) if self.streams is None else ([{} for _ in range(self.streams)], [False] * self.streams)
-
-    def _stream(self, stream):
-        if self.streams is None or isinstance(stream, bool) or not isinstance(stream, (int, np.integer)) or not 0 <= stream < self.streams:
-            raise ValueError(f'stream must be in 0 .. {self.streams - 1}, got {stream!r}' if self.streams else
-                             f'stream={stream!r} was given to an evaluator built without streams')
-        return int(stream)
 
     def reset(self, stream=None):
         """Forget every count and the sequence in progress (stream=s: stream s's alone).  No synchronisation."""
@@ -451,11 +446,6 @@ class _SequenceEvaluator:
         for v in self.state.values():
             v[s].zero_()
         self.rows[s], self.open[s] = {}, False
-
-    def stream_state(self, s):
-        """Stream s's state as views state[k][s]: contiguous, so the single-evaluator ops take them as they are."""
-        s = self._stream(s)
-        return {k: v[s] for k, v in self.state.items()}
 
     def upload(self, gt_frames):
         """B host arrays [m, 7] -> gt f32 [B, ng, 7] and gcounts i32 [B] on the device, in one pinned copy (pack_gt makes the buffer);

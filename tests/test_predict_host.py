@@ -171,6 +171,61 @@ def test_predict_cli_help_runs_without_a_gpu():
         assert flag in r.stdout
 
 
+# ------------------------------------------------------------------------------------------------ the packed copy and the batch records
+def test_to_host_makes_one_cat_and_returns_aligned_views_of_every_part(monkeypatch):
+    """The uint8 part is 60 bytes long: without padding everything after it would start at an odd multiple of 4."""
+    from tamtr_amd._lib import to_host
+    g = torch.Generator().manual_seed(0)
+    parts = {'out': torch.randn(2, 3, 6, generator=g), 'hits': torch.randint(0, 256, (2, 3, 10), generator=g, dtype=torch.uint8),
+             'counts': torch.tensor([3, -7], dtype=torch.int32), 'curve': torch.randn(5, generator=g, dtype=torch.float64),
+             'keys': torch.tensor([2 ** 40, -1, 5]), 'none': torch.zeros(0, 6)}
+    assert [t.dtype for t in parts.values()] == [torch.float32, torch.uint8, torch.int32, torch.float64, torch.int64, torch.float32]
+    want = {k: t.clone() for k, t in parts.items()}
+    cats, cat = [], torch.cat
+    monkeypatch.setattr(torch, 'cat', lambda *a, **kw: cats.append(1) or cat(*a, **kw))
+    host = to_host(parts)
+    monkeypatch.undo()
+    assert len(cats) == 1 and list(host) == list(parts)
+    for k, t in want.items():
+        a = host[k]
+        assert isinstance(a, np.ndarray) and a.dtype == t.numpy().dtype and a.shape == tuple(t.shape), k
+        assert np.array_equal(a, t.numpy()) and a.ctypes.data % 8 == 0, k
+    assert to_host({}) == {}
+
+
+def test_batch_records_of_a_sequence_are_plain_chunks():
+    from tamtr_amd.predict import sequence_records
+    files = [f'{i}.png' for i in range(5)]
+    gt = [np.full((1, 7), i, np.float32) for i in range(4)]      # the fifth frame's is missing: empty
+    plain = sequence_records(files, 2)
+    assert [r[0] for r in plain] == [files[0:2], files[2:4], files[4:5]]
+    assert all(r[1:] == (None, None, []) for r in plain)
+    scored = sequence_records(files, 2, gt)
+    assert [(r[0], r[1], r[3]) for r in scored] == [(r[0], None, []) for r in plain]
+    for r, (a, b) in zip(scored, ((0, 2), (2, 4), (4, 5))):
+        assert len(r[2]) == b - a and all(g is w for g, w in zip(r[2], gt[a:b]))
+    assert scored[2][2][0].shape == (0, 7) and scored[2][2][0].dtype == np.float32
+    assert sequence_records([], 2) == [] and len(sequence_records(files, 2, gt + gt)[2][2]) == 1      # surplus ground truth is cut
+
+
+def test_batch_records_of_streams_follow_stream_batches():
+    from tamtr_amd.predict import stream_batches, stream_records
+    files = [['a0', 'a1', 'a2'], ['b0']]
+    gt = [[np.full((1, 7), i, np.float32) for i in range(3)], [np.full((2, 7), 9, np.float32)]]
+    batches = stream_batches(files, 2)
+    assert [a for _, a in batches] == [[True, True, True, False], [True, False, False, False]]
+    plain = stream_records(files, 2)
+    assert [(r[0], r[1]) for r in plain] == batches and all(r[2:] == (None, []) for r in plain)
+    scored = stream_records(files, 2, gt)
+    assert [(r[0], r[1]) for r in scored] == batches
+    (f0, e0), (f1, e1) = [r[2:] for r in scored]
+    assert f0[0] is gt[0][0] and f0[1] is gt[1][0] and f0[2] is gt[0][1] and f0[3] is None and e0 == [1]
+    assert f1[0] is gt[0][2] and f1[1:] == [None, None, None] and e1 == [0]
+    half = stream_records(files, 2, [gt[0], None])      # a stream that is not scored is no frame to the evaluators and never ends
+    assert [[g is not None for g in r[2]] for r in half] == [[True, False, True, False], [True, False, False, False]]
+    assert [r[3] for r in half] == [[], [0]]
+
+
 # ------------------------------------------------------------------------------------------------ the C ABI without a GPU
 def _lib():
     import tamtr_amd

@@ -372,6 +372,37 @@ def test_device_validator_reduce_equals_validator():
         assert np.mean([r[key] for r in per_class]) == pytest.approx(want[key], rel=1e-12, abs=1e-15)
 
 
+def test_device_validator_reduces_device_style_labels_and_the_matrix():
+    """A batch whose labels are tensors - a slice lab_off[0] .. lab_off[B] of a larger upload, as the device path returns them - rides in
+    the one copy with a confusion matrix set by hand, next to batches with host labels."""
+    dv, hv = _fed_validators()
+    B = 3
+    y, cls, boxes, bidx = make_case(B, 64, 10, (5, 0, 12), 31)
+    hw = orig_shapes(B, 31)
+    predn, correct, counts = val_rule(y, cls, boxes, bidx, hw, 160, 0.001, 0.7)
+    lab_cls, _, lab_off = group_labels(cls, boxes, bidx, B)
+    big = np.concatenate([np.array([7, 7], F), lab_cls, np.array([3], F)])      # rows outside the slice belong to no image
+    dv.batches.insert(1, (torch.from_numpy(predn), torch.from_numpy(correct), torch.from_numpy(counts), torch.from_numpy(big),
+                          torch.from_numpy(lab_off + 2)))
+    dv.seen += B
+    hv.stats, hv.seen = [], 0
+    for k, Bk in ((0, 3), (None, B), (1, 3), (2, 2)):      # the host validator sees the same batches in the same order
+        if k is None:
+            hv.update(torch.from_numpy(y), {'cls': cls, 'bboxes': boxes, 'batch_idx': bidx, 'ori_shape': hw})
+        else:
+            yk, ck, bk, ik = make_case(Bk, 64, 10, (0, 1, 37), 20 + k)
+            hv.update(torch.from_numpy(yk), {'cls': ck, 'bboxes': bk, 'batch_idx': ik, 'ori_shape': orig_shapes(Bk, k)})
+    matrix = torch.arange(121, dtype=torch.int32).reshape(11, 11)
+    dv.confusion, dv._matrix = True, matrix.clone()
+    got, want = dv.results(), hv.results()
+    per_class = got.pop('per_class')
+    assert got.pop('confusion_matrix') == matrix.tolist()
+    assert got == want and want['mAP50'] > 0 and want['seen'] == 11
+    tcls, timage = dv._reduce()[3:]
+    assert len(tcls) == len(timage) == sum(r['instances'] for r in per_class) == 3 * 38 - 37 + 17
+    assert np.array_equal(tcls[38:55], lab_cls) and np.array_equal(timage[38:55], 3 + np.repeat(np.arange(B), np.diff(lab_off)))
+
+
 def test_device_validator_without_detections_or_labels():
     from tamtr_amd import engine as E
     dv = E.DeviceValidator(160)
