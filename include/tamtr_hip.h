@@ -1012,6 +1012,39 @@ int tamtr_trackmap_end_sequence(const double* thresholds, int n_thresholds, doub
                                 void* workspace, int workspace_bytes, void* stream);
 int tamtr_trackmap_workspace_bytes(int nq, int ng, int nc, int G_cap, int T_cap, int P_cap); /* 0 = unsupported */
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Test-time augmentation.  Replaces DetectionModel._predict_augment, ultralytics/nn/tasks.py:272-295, with scale_img
+ * (utils/torch_utils.py:316-327) and _descale_pred (tasks.py:286-295), as `augment` reaches them from the predictor and the validator
+ * (engine/predictor.py:135, engine/validator.py:109,169).  _clip_augmented (tasks.py:297-306) is anchor-layer specific and has no
+ * counterpart for a query decoder.  (New symbols only; the ABI version stays 36.)
+ *
+ * tamtr_tta_view: scale_img(x.flip(3) if flip else x, ratio, gs) (torch_utils.py:316-327) for a batch in one launch.
+ *      x   f32 [B, 3, H, W]    the model input (already / 255)
+ *      out f32 [B, 3, Hp, Wp]  the view
+ *  The caller computes the sizes in double: content (sh, sw) = (int(H ratio), int(W ratio)), canvas (Hp, Wp) = (ceil(H ratio / gs) gs,
+ *  ceil(W ratio / gs) gs).  Inside the content rectangle: torch's bilinear align_corners=False sample of x (of x mirrored left-right
+ *  when flip = 1), coordinates in fp32 (csrc/tta.hip states them); outside: 0.447f.  (sh, sw) = (H, W) is a copy, bit for bit.
+ *  TAMTR_EINVAL: a NULL operand, B, H, W, sh or sw < 1, Hp < sh, Wp < sw, flip not 0 / 1.  TAMTR_EUNSUP: B or Hp > 65535.
+ *
+ * tamtr_tta_merge: the views' de-augmented rows concatenated along the query axis (tasks.py:281-284) and merged by the ordinary NMS
+ * (models/rtdetrworld/predict.py:34-78), for a batch in one launch, one workgroup per image.
+ *      ys      HOST array of V device pointers, each (dtype) [B, nq, 4 + nc]: cx cy w h in 0..1 of the view's canvas, class scores
+ *      views   f32 [V, 4]       kx, ky, flip (0 / 1), 0 per view: cx' = cx kx, then 1 - cx' when flip; cy' = cy ky; w' = w kx; h' = h ky
+ *      classes i32 [n_classes] or NULL (no class filter)
+ *      ym      f32 [B, max_out, 4 + nc]  the first max_out NMS survivors in order: cx' cy' w' h', the source row's scores; zero rows after
+ *      src     i32 [B, max_out]  the candidate i = v nq + q a row came from, -1 after counts[b]
+ *      counts  i32 [B]           rows written
+ *      dropped i32 [B]           survivors that did not fit into max_out rows
+ *  Bit-exact in fp32, every operation rounded on its own: score / class / filter / order / NMS as tamtr_detect_postprocess on the
+ *  de-augmented candidates (equal scores: ascending i; IoU > iou compared in fp32).  Nothing is written past a table; nothing is
+ *  allocated, set or synchronised, so the call can be captured.
+ *  TAMTR_EINVAL: a NULL operand or view pointer, V, B, nq or max_out < 1, nd < 5, n_classes < 0, dtype not F32 / BF16.
+ *  TAMTR_EUNSUP: V nq > 2048, V > 16, max_out > 512. */
+int tamtr_tta_view(const float* x, float* out, int B, int H, int W, int sh, int sw, int Hp, int Wp, int flip, void* stream);
+int tamtr_tta_merge(const void* const* ys, int V, int dtype, int B, int nq, int nd, const float* views, float conf, float iou,
+                    int single_cls, float max_wh, const int32_t* classes, int n_classes, int max_out, float* ym, int32_t* src,
+                    int32_t* counts, int32_t* dropped, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

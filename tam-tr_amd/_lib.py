@@ -146,6 +146,8 @@ _SIGS = {
     'tamtr_trackmap_update': [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _I, _P],
     'tamtr_trackmap_end_sequence': [_P, _I, _D, _I, _P, _P, _P, _I, _P],
     'tamtr_trackmap_workspace_bytes': [_I, _I, _I, _I, _I, _I],
+    'tamtr_tta_view': [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    'tamtr_tta_merge': [_P, _I, _I, _I, _I, _I, _P, _F, _F, _I, _F, _P, _I, _I, _P, _P, _P, _P, _P],
 }
 EXPORTS = tuple(_SIGS)
 _lib = None

@@ -1429,7 +1429,7 @@ class DeviceValidator:
 
 @torch.no_grad()
 def validate(model, batches, imgsz=640, conf=0.001, iou=0.7, autocast_dtype=None, on_device=False, save_json=None, names=None,
-             confusion=False, device_metrics=False, curves=False, coco=False, coco_max_dets=(1, 10, 100)):
+             confusion=False, device_metrics=False, curves=False, coco=False, coco_max_dets=(1, 10, 100), augment=False, tta_views=None):
     """model in eval mode over an iterable of batches -> metric dict (valTAMTR.py's flow without the dataset plumbing).
     on_device: postprocess and label matching in one HIP launch per batch (DeviceValidator; the dict then also carries 'per_class');
     save_json (a file or folder path, needs on_device): also write the reference's predictions.json there.
@@ -1437,7 +1437,11 @@ def validate(model, batches, imgsz=640, conf=0.001, iou=0.7, autocast_dtype=None
     device_metrics (needs on_device): AP and the curves are reduced on the device too (DeviceValidator(device_metrics=True)).
     curves: the dict also carries 'curves' (the reference's P / R / F1 / PR curves; see ap_per_class).
     coco: the dict also carries 'coco', the COCO-protocol AP / AR by object size with the cuts coco_max_dets (coco_evaluate on the host
-    path, csrc/cocoeval.hip with on_device); it needs nothing beyond the path it selects."""
+    path, csrc/cocoeval.hip with on_device); it needs nothing beyond the path it selects.
+    augment: test-time augmentation (the reference's `augment`, engine/validator.py:109,169; tta.py): every batch's predictions become
+    tta.tta_forward's merged tensor over tta_views (default tta.DEFAULT_VIEWS) before either validator sees them, so the confusion
+    matrix, COCO and save_json ride along unchanged; the dict then carries 'tta_dropped', the merged rows beyond 512 per image (read
+    once, after the last batch)."""
     if save_json and not on_device:
         raise ValueError('validate(save_json=...) needs on_device=True: the records come from the device path')
     if device_metrics and not on_device:
@@ -1447,13 +1451,22 @@ def validate(model, batches, imgsz=640, conf=0.001, iou=0.7, autocast_dtype=None
     v = (DeviceValidator(imgsz, conf, iou, save_json=bool(save_json), names=names, confusion=confusion, device_metrics=device_metrics,
                          coco=coco, coco_max_dets=coco_max_dets) if on_device
          else Validator(imgsz, conf, iou, confusion=confusion, coco=coco, coco_max_dets=coco_max_dets))
+    if augment:
+        from . import tta
+        views, dropped = tta.check_views(tta.DEFAULT_VIEWS if tta_views is None else tta_views), []
     for batch in batches:
         img = batch['img']
-        with torch.autocast(img.device.type, dtype=autocast_dtype or torch.bfloat16, enabled=autocast_dtype is not None):
-            preds = model(img, txt_feats=batch.get('txt_feats'))
+        if augment:
+            preds, _, _, drop = tta.tta_forward(model, img, batch.get('txt_feats'), views, conf, iou, autocast_dtype=autocast_dtype)
+            dropped.append(drop)
+        else:
+            with torch.autocast(img.device.type, dtype=autocast_dtype or torch.bfloat16, enabled=autocast_dtype is not None):
+                preds = model(img, txt_feats=batch.get('txt_feats'))
         v.update(preds, batch)
     model.train(was_training)
     res = v.results(curves=True) if curves else v.results()
+    if augment:
+        res['tta_dropped'] = int(torch.cat(dropped).sum()) if dropped else 0
     if save_json:
         res['json'] = v.write_json(save_json)
     return res

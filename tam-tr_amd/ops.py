@@ -1894,7 +1894,106 @@ def detect_postprocess(y, orig_hw, conf, iou, classes=None, single_cls=False, ma
     return out, keep, counts
 
 
-TRACK_STATE_SPEC = (('mean', torch.float64, (8,)), ('cov', torch.float64, (8, 8)), ('meta', torch.int32, (8,)), ('sc', torch.float32, (2,)))
+def tta_view_sizes(H, W, ratio, gs=64):
+    """scale_img's sizes (utils/torch_utils.py:322-326), in Python double: content (sh, sw) = (int(H ratio), int(W ratio)) and canvas
+    (Hp, Wp) = (ceil(H ratio / gs) gs, ceil(W ratio / gs) gs)."""
+    import math
+    ratio, gs = float(ratio), int(gs)
+    if not (ratio > 0 and math.isfinite(ratio)) or gs < 1 or H < 1 or W < 1:
+        raise _lib.TamtrHipError(f'tta view: ratio must be positive and finite, gs and the input size at least 1; got ratio {ratio!r}, gs {gs}, '
+                                 f'size {(H, W)}')
+    sh, sw = int(H * ratio), int(W * ratio)
+    if sh < 1 or sw < 1:
+        raise _lib.TamtrHipError(f'tta view: ratio {ratio} leaves nothing of a {H} x {W} input')
+    return (sh, sw), (math.ceil(H * ratio / gs) * gs, math.ceil(W * ratio / gs) * gs)
+
+
+def tta_view_factors(views, size, gs=64):
+    """[(ratio, flip)] and the input size (H, W) -> [(kx, ky, flip)]: what a view's normalised cx / w (kx) and cy / h (ky) are
+    multiplied by to land in the input's normalised frame: canvas pixels (Wp), / ratio as _descale_pred divides (nn/tasks.py:289),
+    / W.  Computed in double, rounded to fp32: ratio 1 on a size that is a multiple of gs gives exactly 1.0."""
+    import numpy as np
+    H, W = (int(s) for s in size)
+    out = []
+    for ratio, flip in views:
+        _, (Hp, Wp) = tta_view_sizes(H, W, ratio, gs)
+        out.append((float(np.float32(Wp / (float(ratio) * W))), float(np.float32(Hp / (float(ratio) * H))), bool(flip)))
+    return out
+
+
+@torch.no_grad()
+def tta_view(x, ratio, flip, gs=64):
+    """One test-time-augmentation view of a batch in one launch (csrc/tta.hip): scale_img(x.flip(3) if flip else x, ratio, gs)
+    (utils/torch_utils.py:316-327) - bilinear align_corners=False to (int(H ratio), int(W ratio)), padded with 0.447 to the next
+    multiples of gs.  x f32 [B, 3, H, W] on the GPU -> f32 [B, 3, Hp, Wp].  ratio 1 is a copy (mirrored when flip), bit for bit.
+    No synchronisation."""
+    require_gpu(x)
+    if x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32:
+        raise _lib.TamtrHipError(f'tta_view: expected x f32 [B, 3, H, W], got {x.dtype} {tuple(x.shape)}')
+    B, _, H, W = x.shape
+    (sh, sw), (Hp, Wp) = tta_view_sizes(H, W, ratio, gs)
+    x = _c(x)
+    out = torch.empty(B, 3, Hp, Wp, device=x.device, dtype=torch.float32)
+    call('tamtr_tta_view', ptr(x), ptr(out), B, H, W, sh, sw, Hp, Wp, int(bool(flip)), stream_ptr())
+    return out
+
+
+@torch.no_grad()
+def tta_merge(ys, views, conf, iou, classes=None, single_cls=False, max_wh=7680., max_out=512, size=None, gs=64):
+    """The views' raw eval outputs of a batch -> one ordinary prediction tensor, in one launch (csrc/tta.hip): every row de-augmented
+    as _descale_pred does (nn/tasks.py:286-295: descale, then de-flip), the views concatenated along the query axis (tasks.py:284) and
+    merged by the predictor's NMS rule (class max, `score > conf`, the class filter, class-aware torchvision NMS; detect_postprocess
+    states it).  ys: V tensors (all f32 or all bf16) [B, nq, 4 + nc] on the GPU, V * nq <= 2048 and V <= 16; views: V entries
+    (ratio, flip) with `size` = the input's (H, W) and the views' gs (tta_view_factors), or V ready (kx, ky, flip) with size=None;
+    classes: a tensor or a list.  Returns device tensors ym f32 [B, max_out, 4 + nc] (the first max_out survivors in NMS order:
+    de-augmented cx cy w h and the source row's scores; zero rows after the count), src i32 [B, max_out] (candidate v * nq + q, -1
+    after the count), counts i32 [B], dropped i32 [B] (survivors beyond max_out).  ym goes to detect_postprocess,
+    val_postprocess_match and the rest unchanged, with the same conf / iou / classes / single_cls: they keep what the same rule keeps
+    of the concatenation.  With identity views ((1, False) each) the op is the NMS merge of the reference's Ensemble (nn/tasks.py
+    Ensemble.forward: torch.cat(y, 1) of several models' outputs).  No synchronisation (views and classes go up in one copy)."""
+    ys = list(ys)
+    if not ys:
+        raise _lib.TamtrHipError('tta_merge: needs at least one view output')
+    require_gpu(*ys)
+    y0 = ys[0]
+    if y0.dim() != 3 or any(y.shape != y0.shape or y.dtype != y0.dtype or y.device != y0.device for y in ys):
+        raise _lib.TamtrHipError(f'tta_merge: expected V tensors of one shape [B, nq, 4 + nc], dtype and device, got '
+                                 f'{[(y.dtype, tuple(y.shape)) for y in ys]}')
+    if y0.dtype not in (torch.float32, torch.bfloat16):
+        ys = [y.float() for y in ys]
+    ys = [_c(y) for y in ys]
+    V, (B, nq, nd), dev = len(ys), ys[0].shape, ys[0].device
+    views = list(views)
+    table = tta_view_factors(views, size, gs) if size is not None else [(float(kx), float(ky), bool(f)) for kx, ky, f in views]
+    if len(table) != V:
+        raise _lib.TamtrHipError(f'tta_merge: {V} outputs need {V} views, got {len(table)}')
+    max_out = int(max_out)
+    vt = torch.tensor([[kx, ky, float(f), 0.0] for kx, ky, f in table], dtype=torch.float32).reshape(-1)
+    # an empty filter keeps nothing and still needs a non-NULL pointer, as in detect_postprocess
+    cl = None if classes is None else torch.as_tensor(classes, dtype=torch.int32).reshape(-1)
+    n_cl = 0 if cl is None else cl.numel()
+    if cl is None:
+        vt = vt.to(dev, non_blocking=True)
+    else:      # host operands go up in one copy (the table travels as its bits)
+        cl = cl if n_cl else torch.zeros(1, dtype=torch.int32, device=cl.device)
+        if cl.is_cuda:
+            vt = vt.to(dev, non_blocking=True)
+        else:
+            up = torch.cat([vt.view(torch.int32), cl]).to(dev, non_blocking=True)
+            vt, cl = up[:vt.numel()].view(torch.float32), up[vt.numel():]
+        cl = _c(cl)
+    ym = torch.empty(B, max(max_out, 0), nd, device=dev, dtype=torch.float32)
+    src = torch.empty(B, max(max_out, 0), device=dev, dtype=torch.int32)
+    counts = torch.empty(B, device=dev, dtype=torch.int32)
+    dropped = torch.empty(B, device=dev, dtype=torch.int32)
+    pv = (ctypes.c_void_p * V)(*[y.data_ptr() for y in ys])
+    call('tamtr_tta_merge', ctypes.cast(pv, ctypes.c_void_p), V, dtype_code(ys[0]), B, nq, nd, ptr(vt), float(conf), _f32_at_most(float(iou)),
+         int(bool(single_cls)), float(max_wh), ptr(cl) if cl is not None else None, n_cl, max_out, ptr(ym), ptr(src), ptr(counts),
+         ptr(dropped), stream_ptr())
+    return ym, src, counts, dropped
+
+
+TRACK_STATE_SPEC =(('mean', torch.float64, (8,)), ('cov', torch.float64, (8, 8)), ('meta', torch.int32, (8,)), ('sc', torch.float32, (2,)))
 
 
 def _check_streams(what, streams):

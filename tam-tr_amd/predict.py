@@ -213,10 +213,16 @@ _COLORS = [(255, 56, 56), (255, 157, 151), (255, 112, 31), (255, 178, 29), (207,
 class Predictor:
     """model: RTDETRDetectionWorldModel on the GPU; names: {id: name} or a list; text_features: data.TextFeatures (encodes the
     names, first synonym of a 'a/b' entry) or a ready [nc, d] tensor.  Defaults are the reference's (cfg/default.yaml:47-49,68).
-    keep_raw=True keeps the last batch's model input (`last_img`) and raw eval output (`last_y`) for inspection."""
+    keep_raw=True keeps the last batch's model input (`last_img`) and raw eval output (`last_y`) for inspection.
+    augment=True: test-time augmentation (the reference's `augment`, cfg/default.yaml:66; tta.py): the forward runs on tta_views
+    (default tta.DEFAULT_VIEWS: the reference's three scales and flips) and ops.tta_merge leaves one prediction tensor of at most
+    tta_max_out rows per image, which the postprocess takes as it takes the model's.  `tta_dropped` sums the merged rows that did not
+    fit (it rides in the batch's one device-to-host copy), times gains 'tta' (the view launches and the merge, taken out of
+    'forward'), and keep_raw then keeps the merged tensor as `last_y` and the per-view inputs / raw outputs as `last_views` /
+    `last_ys`.  track() and track_streams() refuse it: a merged row is no single decoder query."""
 
     def __init__(self, model, names, text_features, imgsz=640, conf=0.25, iou=0.7, classes=None, single_cls=False, batch=4, dtype='bf16',
-                 keep_raw=False, workers=None):
+                 keep_raw=False, workers=None, augment=False, tta_views=None, tta_max_out=512):
         if dtype not in ('bf16', 'fp32'):
             raise ValueError(f"dtype must be 'bf16' or 'fp32', got {dtype!r}")
         self.names = names if isinstance(names, dict) else dict(enumerate(names))
@@ -241,6 +247,12 @@ class Predictor:
         self.seen = 0
         self.tracker = None
         self.last_img = self.last_y = None
+        self.augment, self.tta_max_out, self.tta_dropped = bool(augment), int(tta_max_out), 0
+        self.last_views = self.last_ys = None
+        if self.augment:
+            from . import tta
+            self.tta_views = tta.check_views(tta.DEFAULT_VIEWS if tta_views is None else tta_views)
+            self.times['tta'] = 0.0
 
     @torch.no_grad()
     def run_batch(self, ims, tracker=None, gt_frames=None, evaluator=None, active=None):
@@ -260,9 +272,15 @@ class Predictor:
         reid = bool(getattr(tracker, 'with_reid', False))                  # a track.BotSort that takes the decoder's query embeddings
         img, u8 = to_model_input(arr, self.device, keep_u8=True)
         ev[1].record()
-        with torch.autocast('cuda', dtype=self.autocast_dtype or torch.bfloat16, enabled=self.autocast_dtype is not None):
-            preds = self.model(img)
-        y = preds[0] if isinstance(preds, (list, tuple)) else preds
+        ev_tta = []
+        if self.augment:      # views, one forward per canvas size, one merge launch: y is the merged tensor
+            from . import tta
+            y, _, _, dropped, views, ys = tta.tta_forward(self.model, img, None, self.tta_views, self.conf, self.iou, self.classes, self.single_cls,
+                                                          self.tta_max_out, self.autocast_dtype, keep=True, events=ev_tta)
+        else:
+            with torch.autocast('cuda', dtype=self.autocast_dtype or torch.bfloat16, enabled=self.autocast_dtype is not None):
+                preds = self.model(img)
+            y = preds[0] if isinstance(preds, (list, tuple)) else preds
         ev[2].record()
         out, keep, counts = ops.detect_postprocess(y, hw, self.conf, self.iou, self.classes, self.single_cls)
         ev[3].record()
@@ -270,6 +288,8 @@ class Predictor:
             counts = counts * torch.as_tensor(active, dtype=torch.int32).to(self.device, non_blocking=True)
         # one device-to-host copy for all the outputs
         parts = {'out': out, 'keep': keep, 'counts': counts}
+        if self.augment:
+            parts['dropped'] = dropped
         evaluators = _as_list(evaluator) if tracker is not None and gt_frames is not None else []
         ev_eval = []
         ev_gmc = None
@@ -295,10 +315,16 @@ class Predictor:
                  ('d2h', ev[4], ev[5])] + ([('gmc', ev[3], ev_gmc)] if ev_gmc is not None else [])
         for i, e in enumerate(evaluators):
             spans.append((e.times_key, ev_eval[i], (ev_eval + [ev[4]])[i + 1]))
+        if self.augment:
+            spans[1] = ('forward', ev_tta[1], ev_tta[2])
+            spans += [('tta', ev[1], ev_tta[1]), ('tta', ev_tta[2], ev[2])]
+            self.tta_dropped += int(host['dropped'].sum())
         for k, a, b in spans:
             self.times[k] = self.times.get(k, 0.0) + a.elapsed_time(b)
         if self.keep_raw:
             self.last_img, self.last_y = img, y
+            if self.augment:
+                self.last_views, self.last_ys = views, ys
         res = host['out'], host['keep'], host['counts']
         if tracker is None:
             return res
@@ -338,6 +364,10 @@ class Predictor:
         every batch's rows are scored on the device right after the tracker's launch, by each evaluator in turn (a frame without track
         rows is an empty track set, as write_mot has it), the sequence is ended after the last frame, and speed() has an entry per
         evaluator ('mot', 'hota', 'tmap'); each evaluator's results() then holds the metrics.  Without both, nothing changes."""
+        self._refuse_augment('track')      # when track() is called, not at the first frame
+        return self._track_source(source, tracker, persist, gt, evaluator)
+
+    def _track_source(self, source, tracker, persist, gt, evaluator):
         self._install_tracker(tracker, persist)
         files = list_sources(source)
         if getattr(self.tracker, 'with_reid', False):
@@ -363,6 +393,7 @@ class Predictor:
         evaluator ('mot', 'hota').  A stream is ended right after the batch that holds its last frame, all streams ending there in
         one call; stream_counts(s) and results() then hold the metrics.  Without both, nothing changes.
         The arguments are checked when this is called, before the first frame is asked for."""
+        self._refuse_augment('track_streams')
         sources = list(sources) if isinstance(sources, (list, tuple)) else None
         if not sources:
             raise ValueError('track_streams needs a non-empty list of sources, one per stream')
@@ -382,6 +413,11 @@ class Predictor:
         self._prune_times(evaluators)
         frames = self._run(records, self.tracker, evaluators, S)
         return self._with_query_embed(frames) if getattr(self.tracker, 'with_reid', False) else frames
+
+    def _refuse_augment(self, what):
+        if getattr(self, 'augment', False):      # (an object that never ran __init__ has no augment: the argument checks still work on it)
+            raise ValueError(f'{what}() does not take a predictor with augment=True: a merged row is no single decoder query, so the tracker\'s '
+                             'row-to-query identity (ReID) would not hold; build a Predictor without augment for tracking')
 
     def _install_tracker(self, tracker, persist, streams=None):
         """self.tracker for a run of track() (streams=None) or track_streams() (streams=S): the given instance, reset unless persist;

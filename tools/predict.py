@@ -7,6 +7,8 @@ label files under an incremented --project/--name folder; one JSON line at the e
 
 Instead of --text-feats, --clip-weights ViT-B-32.pt --clip-vocab bpe_simple_vocab_16e6.txt.gz encodes the class names with the package's
 own CLIP text tower (tamtr_amd.text), so any name works, not only those of a table.
+--augment predicts with test-time augmentation (tamtr_amd.tta): the reference's three views (scales 1 0.83 0.67, the second mirrored), or
+--tta-scales / --tta-flips, merged on the device; the JSON line then carries 'tta' under ms_per_image and 'tta_dropped'.
 """
 import argparse
 import json
@@ -41,7 +43,12 @@ def parse_args(argv=None):
     ap.add_argument('--name', default='TAMTR')
     ap.add_argument('--exist-ok', action='store_true', help='reuse --project/--name instead of incrementing it')
     ap.add_argument('--dtype', default='bf16', choices=['bf16', 'fp32'])
+    ap.add_argument('--augment', action='store_true', help='test-time augmentation: scaled / mirrored views merged on the device')
+    ap.add_argument('--tta-scales', type=float, nargs='+', default=None, help='with --augment: one scale per view (default 1 0.83 0.67)')
+    ap.add_argument('--tta-flips', type=int, nargs='+', default=None, choices=[0, 1], help='with --augment: 1 mirrors a view left-right (default 0 1 0)')
     args = ap.parse_args(argv)
+    if (args.tta_scales or args.tta_flips) and not args.augment:
+        ap.error('--tta-scales / --tta-flips need --augment')
     if (args.text_feats is None) == (args.clip_weights is None and args.clip_vocab is None) or (args.clip_weights is None) != (args.clip_vocab is None):
         ap.error('give either --text-feats, or --clip-weights together with --clip-vocab (not both, not neither)')
     return args
@@ -63,6 +70,7 @@ def main(argv=None):
     from tamtr_amd import data as D
     from tamtr_amd.model import RTDETRDetectionWorldModel
     from tamtr_amd.predict import Predictor, increment_path
+    from tamtr_amd.tta import views_from_cli
 
     dev = torch.device('cuda', 0)
     names = load_names(args)
@@ -70,7 +78,8 @@ def main(argv=None):
     ck = torch.load(args.weights, map_location=dev)
     model.load_state_dict(ck['model' if args.raw else 'ema'])
     pred = Predictor(model, names, D.TextFeatures.from_args(args.text_feats, args.clip_weights, args.clip_vocab, dev), imgsz=args.imgsz, conf=args.conf, iou=args.iou,
-                     classes=args.classes, single_cls=args.single_cls, batch=args.batch, dtype=args.dtype)
+                     classes=args.classes, single_cls=args.single_cls, batch=args.batch, dtype=args.dtype, augment=args.augment,
+                     tta_views=views_from_cli(args.tta_scales, args.tta_flips))
     save_dir = increment_path(os.path.join(args.project, args.name), exist_ok=args.exist_ok)
     if args.save or args.save_txt:
         (save_dir / 'labels' if args.save_txt else save_dir).mkdir(parents=True, exist_ok=True)
@@ -86,9 +95,11 @@ def main(argv=None):
             det.save(save_dir / os.path.basename(det.path))
     wall = time.perf_counter() - t0
     sp = pred.speed()
+    tta = {'tta': round(sp['tta'], 3)} if args.augment else {}
     print(json.dumps({'images': n_img, 'detections': n_det, 'save_dir': str(save_dir) if (args.save or args.save_txt) else None,
-                      'ms_per_image': {'load': round(sp['load'], 3), 'forward': round(sp['h2d'] + sp['forward'], 3),
+                      'ms_per_image': {'load': round(sp['load'], 3), 'forward': round(sp['h2d'] + sp['forward'], 3), **tta,
                                        'postprocess': round(sp['postprocess'] + sp['d2h'], 3)},
+                      **({'augment': True, 'tta_dropped': pred.tta_dropped} if args.augment else {}),
                       'wall_s': round(wall, 3), 'dtype': args.dtype, 'imgsz': args.imgsz, 'batch': args.batch}))
 
 

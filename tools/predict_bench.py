@@ -36,8 +36,14 @@
       launches in sequence on the same rows, and the end of the S sequences likewise; ms per launch, and the two forms' counts
       compared stream by stream.
 
+  (g) --tta: test-time augmentation at 640 x 640, B = 4, the reference's three views (canvases 640, 576 and 448 at gs 64), nq = 300,
+      nc = 10 and 80, in one run (device events, >= 1 s window after warm-up): the three ops.tta_view launches next to their torch
+      composition (flip / F.interpolate / F.pad on the device); the ops.tta_merge launch on 900 candidates per image followed by
+      ops.detect_postprocess on its 512 rows, next to the torch composition (de-augment, torch.cat, then the per-image host loop of
+      (a) with engine.nms), and next to the existing ops.detect_postprocess on one view's 300 rows.
+
     python tools/predict_bench.py [--images 64] [--kernel-only] [--track [--botsort [--reid]] [--streams S]] [--gmc] [--mot [--streams S]]
-                                  [--hota [--streams S]] [--track-map]
+                                  [--hota [--streams S]] [--track-map] [--tta]
 --kernel-only runs only the kernel loop of (a), for a `rocprofv3 --kernel-trace --stats` run of its own.
 """
 import argparse
@@ -726,6 +732,66 @@ def bench_trackmap(frames=200, B=4, nq=300, nc=10, repeats=7):
             'host_ms_per_batch': round(float(np.median(t_host)) / n_batches, 3), 'passes_timed': repeats}
 
 
+def bench_tta(B=4, S=640, nq=300, conf=0.25, iou=0.7):
+    import torch.nn.functional as F
+    from tamtr_amd import ops, tta
+    views = tta.DEFAULT_VIEWS
+    x = torch.rand(B, 3, S, S, generator=torch.Generator().manual_seed(0)).cuda()
+    canvases = [ops.tta_view_sizes(S, S, r, tta.GS) for r, _ in views]
+
+    def view_kernels():
+        return [ops.tta_view(x, r, f, tta.GS) for r, f in views]
+
+    def view_torch():
+        out = []
+        for (r, f), ((sh, sw), (hp, wp)) in zip(views, canvases):
+            v = x.flip(3) if f else x
+            v = v if r == 1.0 else F.interpolate(v, size=(sh, sw), mode='bilinear', align_corners=False)
+            out.append(F.pad(v, [0, wp - sw, 0, hp - sh], value=0.447))
+        return out
+
+    t_vk, n_vk = timed(view_kernels)
+    t_vt, n_vt = timed(view_torch)
+    bytes_moved = 4 * B * 3 * sum(S * S + hp * wp for _, (hp, wp) in canvases)      # every view reads the input once and writes its canvas
+    rows = [{'what': 'views', 'B': B, 'size': S, 'canvases': [c[1] for c in canvases], 'kernels_ms': round(t_vk, 4), 'torch_ms': round(t_vt, 4),
+             'speedup_vs_torch': round(t_vt / t_vk, 2), 'kernels_GB_per_s': round(bytes_moved / t_vk / 1e6, 1), 'iters': [n_vk, n_vt]}]
+    hw = [(540 + 20 * i, 960 - 10 * i) for i in range(B)]
+    hw_dev = torch.tensor(hw, dtype=torch.int32, device='cuda')
+    table = ops.tta_view_factors(views, (S, S), tta.GS)
+    for nc in (10, 80):
+        ys = [synthetic_preds(B, nq, nc, seed=v).cuda() for v in range(len(views))]
+
+        def merge():
+            return ops.tta_merge(ys, views, conf, iou, size=(S, S), gs=tta.GS)
+
+        def merge_and_postprocess():
+            return ops.detect_postprocess(merge()[0], hw_dev, conf, iou)
+
+        def merge_postprocess_copy():   # what the predictor does: both launches plus one device-to-host copy of the outputs
+            o, k, c = merge_and_postprocess()
+            return torch.cat([o.view(-1), k.view(torch.float32).view(-1), c.view(torch.float32)]).cpu()
+
+        def torch_composition():        # de-augment and concatenate on the device, then the per-image host loop of (a)
+            parts = []
+            for y, (kx, ky, f) in zip(ys, table):
+                cx = y[..., 0:1] * kx
+                parts.append(torch.cat([1 - cx if f else cx, y[..., 1:2] * ky, y[..., 2:3] * kx, y[..., 3:4] * ky, y[..., 4:]], -1))
+            return host_loop(torch.cat(parts, 1), hw, conf, iou)
+
+        t_m, n_m = timed(merge)
+        t_mp, _ = timed(merge_and_postprocess)
+        t_mpc, _ = timed(merge_postprocess_copy)
+        t_one, _ = timed(lambda: ops.detect_postprocess(ys[0], hw_dev, conf, iou))
+        t_h, n_h = timed(torch_composition)
+        _, _, counts, dropped = merge()
+        rows.append({'what': 'merge', 'B': B, 'V': len(views), 'nq': nq, 'nc': nc, 'conf': conf, 'iou': iou,
+                     'merged_per_image': round(float(counts.float().mean()), 1), 'dropped': int(dropped.sum()), 'merge_ms': round(t_m, 4),
+                     'merge_plus_postprocess_ms': round(t_mp, 4), 'merge_postprocess_d2h_ms': round(t_mpc, 4),
+                     'detect_postprocess_nq300_ms': round(t_one, 4), 'torch_cat_host_loop_ms': round(t_h, 3),
+                     'speedup_vs_torch': round(t_h / t_mpc, 1), 'iters': [n_m, n_h]})
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--images', type=int, default=64)
@@ -742,6 +808,7 @@ def main():
     ap.add_argument('--hota', action='store_true', help='only (e): the HOTA launches against copy + numpy twin, on the sequence of --mot')
     ap.add_argument('--track-map', action='store_true', help='only (f): the track-mAP launches against copy + numpy twin, on the sequence of --hota '
                     'with scores added, next to the HOTA update launch')
+    ap.add_argument('--tta', action='store_true', help='only (g): the test-time-augmentation view and merge launches against their torch compositions')
     args = ap.parse_args()
     import tamtr_amd  # noqa: F401
     assert torch.cuda.is_available(), 'predict_bench needs an MI355X'
@@ -786,6 +853,11 @@ def main():
         print('(f) track-mAP: update launch per batch of 4 frames, the end-of-sequence launches and the accumulation (device events) vs device-to-host '
               'copy + numpy twin (host clock)')
         print(json.dumps(bench_trackmap()))
+        return
+    if args.tta:
+        print('(g) test-time augmentation, one batch of 4 at 640 x 640, three views (device events, >= 1 s window after 5 warm-up calls)')
+        for r in bench_tta():
+            print(json.dumps(r))
         return
     if args.kernel_only:
         print(json.dumps({'postprocess_kernel_only': bench_postprocess(True)}))

@@ -17,6 +17,8 @@ step the reference leaves to save_json + dataset/yolo2coco.py + pycocotools.  On
 (csrc/cocoeval.hip), engine.coco_evaluate with --host-postprocess; the twelve lines are printed in pycocotools' wording (to stderr; the
 JSON result line stays the last line of stdout) and coco_metrics.json is written into the run folder.  Every image of the split is
 evaluated, also one without labels.
+--augment validates with test-time augmentation (tamtr_amd.tta: the reference's three scaled / mirrored views, or --tta-scales / --tta-flips,
+merged on the device into one prediction tensor per image before the validator sees it); everything above rides along unchanged.
 """
 import argparse
 import csv
@@ -55,7 +57,12 @@ def main():
     ap.add_argument('--coco-max-dets', type=int, nargs='+', default=[1, 10, 100], help='ascending cuts, at most 4 (VisDrone: 1 10 100 500)')
     ap.add_argument('--project', default='runs/val')
     ap.add_argument('--name', default='TAMTR')
+    ap.add_argument('--augment', action='store_true', help='test-time augmentation: scaled / mirrored views merged on the device')
+    ap.add_argument('--tta-scales', type=float, nargs='+', default=None, help='with --augment: one scale per view (default 1 0.83 0.67)')
+    ap.add_argument('--tta-flips', type=int, nargs='+', default=None, choices=[0, 1], help='with --augment: 1 mirrors a view left-right (default 0 1 0)')
     args = ap.parse_args()
+    if (args.tta_scales or args.tta_flips) and not args.augment:
+        ap.error('--tta-scales / --tta-flips need --augment')
     if (args.text_feats is None) == (args.clip_weights is None and args.clip_vocab is None) or (args.clip_weights is None) != (args.clip_vocab is None):
         ap.error('give either --text-feats, or --clip-weights together with --clip-vocab (not both, not neither)')
     if args.save_json and args.host_postprocess:
@@ -69,6 +76,7 @@ def main():
     import tamtr_amd  # noqa: F401
     from tamtr_amd import data as D, engine as E
     from tamtr_amd.model import RTDETRDetectionWorldModel
+    from tamtr_amd.tta import views_from_cli
     dev = torch.device('cuda', 0)
     with open(args.data) as f:
         spec = yaml.safe_load(f)
@@ -93,7 +101,8 @@ def main():
     res = E.validate(model, (D.preprocess_batch(b, None, dev) for b in loader), imgsz=args.imgsz, conf=args.conf, iou=args.iou,
                      autocast_dtype=torch.bfloat16 if args.dtype == 'bf16' else None, on_device=not args.host_postprocess,
                      save_json=save_dir if args.save_json else None, names=short, confusion=args.confusion,
-                     device_metrics=args.device_metrics, curves=args.curves, coco=args.coco, coco_max_dets=tuple(args.coco_max_dets))
+                     device_metrics=args.device_metrics, curves=args.curves, coco=args.coco, coco_max_dets=tuple(args.coco_max_dets),
+                     augment=args.augment, tta_views=views_from_cli(args.tta_scales, args.tta_flips))
     if save_dir is not None:
         res['save_dir'] = save_dir
     if args.confusion:
