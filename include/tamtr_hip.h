@@ -1045,6 +1045,48 @@ int tamtr_tta_merge(const void* const* ys, int V, int dtype, int B, int nq, int 
                     int single_cls, float max_wh, const int32_t* classes, int n_classes, int max_out, float* ym, int32_t* src,
                     int32_t* counts, int32_t* dropped, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------------
+ * Sliced prediction for large frames.  Replaces nothing of the reference, whose predictor stretches the whole frame to imgsz
+ * (LetterBox(scaleFill=True), models/rtdetrworld/predict.py:80-92); it replaces the host loop of sliced inference around a detector:
+ * crop overlapping windows, resize each to imgsz, forward, shift the boxes back, merge with the whole-frame view's.  The two rules are
+ * stated in tam-tr_amd/slicing.py (views_host, merge_host).  (New symbols only; the ABI version stays 36.)
+ *
+ * tamtr_slice_views: the windows of ONE original frame as network inputs, in one launch.
+ *      src     u8  [h, w, 3]     the original RGB frame on the device
+ *      windows HOST i32 [V, 4]   x0 y0 x1 y1 in pixels, 0 <= x0 < x1 <= w and 0 <= y0 < y1 <= h (checked here, passed by value)
+ *      out     f32 [V, 3, S, S]  out[v] = CHW(float(resize_linear_u8(src[y0:y1, x0:x1], S, S)) * float(1.0 / 255.0))
+ *  resize_linear_u8 is tamtr_resize_linear_u8 (tamtr_host.h) bit for bit, all three branches: a window already S x S is a copy, a
+ *  window exactly 2S x 2S takes the 2 x 2 mean, everything else the 11-bit fixed-point two-pass rule (tap positions in double, not
+ *  contracted; csrc/slice.hip states it).  The product by float(1.0 / 255.0) is what `.float() / 255` gives on the device, so the view
+ *  of the window (0, 0, w, h) has the bits of the plain predictor's input.
+ *  TAMTR_EINVAL: a NULL operand, h, w, V or S < 1, a window that is empty or leaves the frame.  TAMTR_EUNSUP: V > 64 (the windows
+ *  travel as a kernel argument), S > 65535 (grid y).
+ *
+ * tamtr_slice_merge: every view's rows mapped to its frame and merged by tamtr_tta_merge's rule, for a batch in one launch, one
+ * workgroup per frame.
+ *      y        (dtype) [N, nq, 4 + nc]  the eval outputs of all views of the batch: cx cy w h in 0..1 of the view, class scores
+ *      view_off HOST i32 [B + 1]  frame b owns views view_off[b] .. view_off[b + 1] - 1; view_off[0] = 0, view_off[B] = N, every frame
+ *                                 owns at least one view (checked here, passed by value)
+ *      views    f32 [N, 4]        ox oy kx ky per view: cx' = cx kx + ox; cy' = cy ky + oy; w' = w kx; h' = h ky.  The caller computes
+ *                                 them in double and rounds once: ox = x0 / w, kx = (x1 - x0) / w, likewise for y; (0, 0, 1, 1) is the identity
+ *      match    0: IoU, torchvision's arithmetic; 1: IoS = inter / min(area_a, area_b); both suppress on `> iou` in fp32, NaN never does
+ *      classes  i32 [n_classes] or NULL (no class filter)
+ *      ym       f32 [B, max_out, 4 + nc]  the first max_out NMS survivors in order: cx' cy' w' h', the source row's scores; zero rows after
+ *      src      i32 [B, max_out]  the candidate i = v_local nq + q a row came from, -1 after counts[b]
+ *      counts   i32 [B]           rows written
+ *      dropped  i32 [B]           survivors that did not fit into max_out rows
+ *      overflow i32 [B]           candidates that passed the filter beyond the table of 4096 (the highest i), left out of the merge
+ *  Bit-exact in fp32, every operation rounded on its own: class max, `score > conf`, the class filter, the passing candidates compacted
+ *  in ascending i into a table of 4096, order by descending score (equal scores: ascending i), greedy class-aware NMS (shift
+ *  cls * max_wh unless single_cls).  Nothing is written past a table; nothing is allocated, set or synchronised, so the call can be captured.
+ *  TAMTR_EINVAL: a NULL operand, N, B, nq or max_out < 1, nd < 5, n_classes < 0, dtype not F32 / BF16, match not 0 / 1, a view_off
+ *  that does not start at 0, end at N or gives a frame no view.  TAMTR_EUNSUP: B > 255, a frame with more than 64 views, nq > 512,
+ *  max_out > 512. */
+int tamtr_slice_views(const uint8_t* src, int h, int w, const int32_t* windows, int V, int S, float* out, void* stream);
+int tamtr_slice_merge(const void* y, int dtype, int N, int B, int nq, int nd, const int32_t* view_off, const float* views, int match,
+                      float conf, float iou, int single_cls, float max_wh, const int32_t* classes, int n_classes, int max_out, float* ym,
+                      int32_t* src, int32_t* counts, int32_t* dropped, int32_t* overflow, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

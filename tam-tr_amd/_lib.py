@@ -148,6 +148,8 @@ _SIGS = {
     'tamtr_trackmap_workspace_bytes': [_I, _I, _I, _I, _I, _I],
     'tamtr_tta_view': [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     'tamtr_tta_merge': [_P, _I, _I, _I, _I, _I, _P, _F, _F, _I, _F, _P, _I, _I, _P, _P, _P, _P, _P],
+    'tamtr_slice_views': [_P, _I, _I, _P, _I, _I, _P, _P],
+    'tamtr_slice_merge': [_P, _I, _I, _I, _I, _I, _P, _P, _I, _F, _F, _I, _F, _P, _I, _I, _P, _P, _P, _P, _P, _P],
 }
 EXPORTS = tuple(_SIGS)
 _lib = None

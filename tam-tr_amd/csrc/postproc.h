@@ -1,5 +1,6 @@
 // postproc.h - device helpers shared by the two detection postprocess kernels: predict.hip (the predictor's rule) and
-// valmatch.hip (the validator's rule).  Both are compiled with -ffp-contract=off; every float operation here rounds on its own.
+// valmatch.hip (the validator's rule), and by the two merges that feed them, tta.hip and slice.hip (pp_overlap, pp_greedy_tiles).  All
+// are compiled with -ffp-contract=off; every float operation here rounds on its own.
 #pragma once
 #include "common.h"
 
@@ -97,6 +98,87 @@ __device__ __forceinline__ int pp_greedy(const uint64_t (*mask)[PP_WORDS], int* 
       if (lane == 0) kept[cnt] = i;
       ++cnt;
       if (lane < nw) rem |= mask[i][lane];
+    }
+  }
+  return cnt;
+}
+
+// Overlap of two shifted corner boxes with torchvision's nms_kernel.cpp arithmetic (operand order included), as pp_nms_mask has it; `a`
+// is the earlier (kept) row.  MATCH 0: IoU = inter / ((area_a + area_b) - inter).  MATCH 1: IoS = inter / min(area_a, area_b), the
+// intersection over the smaller box.  0 / 0 is NaN, which no `> thr` passes.
+template <int MATCH>
+__device__ __forceinline__ float pp_overlap(const float* a, float area_a, const float* b) {
+  const float xx1 = pp_max(a[0], b[0]), yy1 = pp_max(a[1], b[1]);
+  const float xx2 = pp_min(a[2], b[2]), yy2 = pp_min(a[3], b[3]);
+  const float ww = pp_max(0.0f, xx2 - xx1), hh = pp_max(0.0f, yy2 - yy1);
+  const float inter = ww * hh;
+  const float area_b = (b[2] - b[0]) * (b[3] - b[1]);
+  if (MATCH == 1) return inter / pp_min(area_a, area_b);
+  return inter / ((area_a + area_b) - inter);
+}
+
+__device__ __forceinline__ uint64_t pp_uniform(uint64_t v) {
+  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+  return ((uint64_t)hi << 32) | lo;  // (the builtins return int: no sign extension of the low word)
+}
+
+// Greedy NMS over n boxes in NMS order without an n x n mask, by a workgroup of WAVES waves, over tiles of 64 rows with one barrier per
+// tile: the waves build the tile's 64 x 64 mask with ballots (tmask, double buffered); every wave resolves it by itself from registers
+// (lane r holds row r's word, 64 readlanes) starting from the tile's removed word; then the tile's kept rows strike all later rows in
+// parallel - a wave owns the removed words it writes.  rem: one removed bit per row, ceil(n / 64) words, zero on entry (and a barrier
+// behind the zeroing and the boxes).  kept[] receives the positions of the first max_out kept rows in order; returns the number of
+// kept rows (the same value in every thread).  The caller puts a barrier after it.
+template <int WAVES, int MATCH>
+__device__ __forceinline__ int pp_greedy_tiles(const float (*sbox)[4], uint64_t* rem, uint64_t (*tmask)[64], int* kept, int n, float thr,
+                                               int max_out, int wave, int lane) {
+  const int nw = (n + WAVE - 1) / WAVE;
+  int cnt = 0;
+  for (int t = 0; t < nw; ++t) {
+    const int base = t * WAVE;
+    uint64_t* tm = tmask[t & 1];
+    // the tile's mask: word r bit l = overlap(base + r, base + l) > thr for l > r
+    for (int r = wave; r < WAVE; r += WAVES) {
+      bool sup = false;
+      const int i = base + r, j = base + lane;
+      if (i < n && j < n && lane > r) {
+        const float* bi = sbox[i];
+        sup = pp_overlap<MATCH>(bi, (bi[2] - bi[0]) * (bi[3] - bi[1]), sbox[j]) > thr;
+      }
+      const uint64_t word = __ballot(sup);
+      if (lane == 0) tm[r] = word;
+    }
+    __syncthreads();  // also orders the previous tile's strikes before this tile's read of rem[t]
+    // resolve, by every wave for itself: lane r holds row r's word
+    const uint64_t mine = tm[lane];
+    uint64_t cur = pp_uniform(rem[t]);
+    if (n - base < WAVE) cur |= ~0ull << (n - base);  // positions past n are no rows
+    uint64_t keptw = 0;
+    for (int r = 0; r < WAVE; ++r) {
+      if (!((cur >> r) & 1ull)) {
+        keptw |= 1ull << r;
+        const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)mine, r), hi = __builtin_amdgcn_readlane((uint32_t)(mine >> 32), r);
+        cur |= ((uint64_t)hi << 32) | lo;
+      }
+    }
+    if (wave == 0 && ((keptw >> lane) & 1ull)) {
+      const int pos = cnt + __popcll(keptw & ((1ull << lane) - 1ull));
+      if (pos < max_out) kept[pos] = base + lane;
+    }
+    cnt += __popcll(keptw);
+    // the tile's kept rows strike the later rows: wave w owns removed word t + 1 + w, t + 1 + w + WAVES, ...
+    for (int w = t + 1 + wave; w < nw; w += WAVES) {
+      const int j = w * WAVE + lane;
+      const uint64_t had = rem[w];
+      bool sup = false;
+      if (j < n && !((had >> lane) & 1ull)) {
+        const float bj[4] = {sbox[j][0], sbox[j][1], sbox[j][2], sbox[j][3]};
+        for (uint64_t m = keptw; m && !sup; m &= m - 1) {
+          const float* bi = sbox[base + __builtin_ctzll(m)];
+          sup = pp_overlap<MATCH>(bi, (bi[2] - bi[0]) * (bi[3] - bi[1]), bj) > thr;
+        }
+      }
+      const uint64_t word = __ballot(sup);
+      if (lane == 0 && word) rem[w] = had | word;
     }
   }
   return cnt;

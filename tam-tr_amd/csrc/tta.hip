@@ -123,21 +123,6 @@ __device__ __forceinline__ void tta_box(const T* r, const float* __restrict__ vw
   o[3] = Elt<T>::ld(r + 3) * ky;
 }
 
-// torchvision's nms_kernel.cpp arithmetic on two shifted boxes (operand order included), as pp_nms_mask has it
-__device__ __forceinline__ float tta_iou(const float* a, float area_a, const float* b) {
-  const float xx1 = pp_max(a[0], b[0]), yy1 = pp_max(a[1], b[1]);
-  const float xx2 = pp_min(a[2], b[2]), yy2 = pp_min(a[3], b[3]);
-  const float ww = pp_max(0.0f, xx2 - xx1), hh = pp_max(0.0f, yy2 - yy1);
-  const float inter = ww * hh;
-  const float area_b = (b[2] - b[0]) * (b[3] - b[1]);
-  return inter / ((area_a + area_b) - inter);
-}
-
-__device__ __forceinline__ uint64_t tta_uniform(uint64_t v) {
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-  return ((uint64_t)hi << 32) | lo;  // (the builtins return int: no sign extension of the low word)
-}
-
 template <typename T, int GW>
 __global__ __launch_bounds__(TTA_THREADS) void tta_merge_kernel(TtaViews ys, int V, int nq, int nd, const float* __restrict__ views,
                                                                 float conf, float thr, int single_cls, float max_wh,
@@ -208,57 +193,8 @@ __global__ __launch_bounds__(TTA_THREADS) void tta_merge_kernel(TtaViews ys, int
   }
   __syncthreads();
 
-  // ---- 4. greedy pass over tiles of 64 rows; `cnt` is the same in every thread
-  const int nw = (n + WAVE - 1) / WAVE;
-  int cnt = 0;
-  for (int t = 0; t < nw; ++t) {
-    const int base = t * WAVE;
-    uint64_t* tm = s.tmask[t & 1];
-    // the tile's mask: word r bit l = iou(base + r, base + l) > thr for l > r
-    for (int r = wave; r < WAVE; r += TTA_WAVES) {
-      bool sup = false;
-      const int i = base + r, j = base + lane;
-      if (i < n && j < n && lane > r) {
-        const float* bi = s.sbox[i];
-        sup = tta_iou(bi, (bi[2] - bi[0]) * (bi[3] - bi[1]), s.sbox[j]) > thr;
-      }
-      const uint64_t word = __ballot(sup);
-      if (lane == 0) tm[r] = word;
-    }
-    __syncthreads();  // also orders the previous tile's strikes before this tile's read of rem[t]
-    // resolve, by every wave for itself: lane r holds row r's word
-    const uint64_t mine = tm[lane];
-    uint64_t cur = tta_uniform(s.rem[t]);
-    if (n - base < WAVE) cur |= ~0ull << (n - base);  // positions past n are no rows
-    uint64_t keptw = 0;
-    for (int r = 0; r < WAVE; ++r) {
-      if (!((cur >> r) & 1ull)) {
-        keptw |= 1ull << r;
-        const uint32_t lo = __builtin_amdgcn_readlane((uint32_t)mine, r), hi = __builtin_amdgcn_readlane((uint32_t)(mine >> 32), r);
-        cur |= ((uint64_t)hi << 32) | lo;
-      }
-    }
-    if (wave == 0 && ((keptw >> lane) & 1ull)) {
-      const int pos = cnt + __popcll(keptw & ((1ull << lane) - 1ull));
-      if (pos < max_out) s.kept[pos] = base + lane;
-    }
-    cnt += __popcll(keptw);
-    // the tile's kept rows strike the later rows: wave w owns removed word t + 1 + w, t + 1 + w + 16, ...
-    for (int w = t + 1 + wave; w < nw; w += TTA_WAVES) {
-      const int j = w * WAVE + lane;
-      const uint64_t had = s.rem[w];
-      bool sup = false;
-      if (j < n && !((had >> lane) & 1ull)) {
-        const float bj[4] = {s.sbox[j][0], s.sbox[j][1], s.sbox[j][2], s.sbox[j][3]};
-        for (uint64_t m = keptw; m && !sup; m &= m - 1) {
-          const float* bi = s.sbox[base + __builtin_ctzll(m)];
-          sup = tta_iou(bi, (bi[2] - bi[0]) * (bi[3] - bi[1]), bj) > thr;
-        }
-      }
-      const uint64_t word = __ballot(sup);
-      if (lane == 0 && word) s.rem[w] = had | word;
-    }
-  }
+  // ---- 4. greedy pass over tiles of 64 rows (postproc.h); `cnt` is the same in every thread
+  const int cnt = pp_greedy_tiles<TTA_WAVES, 0>(s.sbox, s.rem, s.tmask, s.kept, n, thr, max_out, wave, lane);
   __syncthreads();
 
   // ---- 5. outputs: the first max_out survivors, then zero / -1 padding

@@ -1993,6 +1993,107 @@ def tta_merge(ys, views, conf, iou, classes=None, single_cls=False, max_wh=7680.
     return ym, src, counts, dropped
 
 
+SLICE_MAX_VIEWS, SLICE_MAX_CAND = 64, 4096      # csrc/slice.hip: views per frame, candidates that may pass the filter per frame
+SLICE_MATCH = {'iou': 0, 'ios': 1}
+
+
+def _slice_windows_array(what, windows):
+    import numpy as np
+    win = np.ascontiguousarray(np.asarray(windows, dtype=np.int64).reshape(-1, 4).astype(np.int32))
+    if not len(win):
+        raise _lib.TamtrHipError(f'{what}: needs at least one window')
+    return win
+
+
+def slice_view_factors(windows, view_off, hws):
+    """Windows i32 [N, 4] (x0 y0 x1 y1 in pixels), the frames' view ranges view_off [B + 1] and sizes hws [B] (h, w) -> f32 numpy
+    [N, 4] = ox oy kx ky, what maps a view's normalised box to its frame's: ox = x0 / w, oy = y0 / h, kx = (x1 - x0) / w,
+    ky = (y1 - y0) / h, each computed in double and rounded once.  The whole frame gives exactly (0, 0, 1, 1)."""
+    import numpy as np
+    win = _slice_windows_array('slice_view_factors', windows)
+    off = [int(o) for o in view_off]
+    hws = [(int(h), int(w)) for h, w in hws]
+    if len(off) != len(hws) + 1 or off[0] != 0 or off[-1] != len(win) or any(b <= a for a, b in zip(off, off[1:])):
+        raise _lib.TamtrHipError(f'slice: view_off {off} must run from 0 to the {len(win)} views in {len(hws)} non-empty steps')
+    out = np.empty((len(win), 4), np.float32)
+    for b, (h, w) in enumerate(hws):
+        for v in range(off[b], off[b + 1]):
+            x0, y0, x1, y1 = (int(t) for t in win[v])
+            out[v] = (x0 / w, y0 / h, (x1 - x0) / w, (y1 - y0) / h)
+    return out
+
+
+@torch.no_grad()
+def slice_views(src, windows, S, out=None):
+    """The windows of one original frame as network inputs, in one launch (csrc/slice.hip): src u8 [h, w, 3] on the GPU (RGB, as
+    data.decode_image returns it), windows i32 [V, 4] on the host (x0 y0 x1 y1 in pixels inside the frame, V <= 64) -> f32
+    [V, 3, S, S], out[v] = data.resize_linear_u8 of the crop (a copy at S x S, the 2 x 2 mean at 2S x 2S, else the fixed-point
+    two-pass rule), CHW, * float(1 / 255) - what predict.letterbox_scalefill and to_model_input make of the crop, bit for bit.
+    out: a contiguous f32 [V, 3, S, S] tensor (e.g. a slice of a larger batch) to write into.  No synchronisation."""
+    require_gpu(src)
+    if src.dim() != 3 or src.shape[2] != 3 or src.dtype != torch.uint8:
+        raise _lib.TamtrHipError(f'slice_views: expected src u8 [h, w, 3], got {src.dtype} {tuple(src.shape)}')
+    win = _slice_windows_array('slice_views', windows)
+    V, S = len(win), int(S)
+    src = _c(src)
+    if out is None:
+        out = torch.empty(V, 3, max(S, 0), max(S, 0), device=src.device, dtype=torch.float32)
+    elif tuple(out.shape) != (V, 3, S, S) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != src.device:
+        raise _lib.TamtrHipError(f'slice_views: out must be a contiguous f32 [{V}, 3, {S}, {S}] on {src.device}, got {out.dtype} {tuple(out.shape)}')
+    call('tamtr_slice_views', ptr(src), src.shape[0], src.shape[1], win.ctypes.data_as(ctypes.c_void_p), V, S, ptr(out), stream_ptr())
+    return out
+
+
+@torch.no_grad()
+def slice_merge(y, view_off, windows, hws, conf, iou, classes=None, single_cls=False, match='iou', max_wh=7680., max_out=512):
+    """The raw eval outputs of all views of a batch -> one ordinary prediction tensor, in one launch (csrc/slice.hip), one workgroup
+    per frame.  y (f32 / bf16) [N, nq, 4 + nc] on the GPU; frame b owns views view_off[b] .. view_off[b + 1] - 1 (host ints [B + 1], at
+    most 64 views per frame, nq <= 512); windows i32 [N, 4] and hws [B] (h, w) on the host give every view's place in its frame
+    (slice_view_factors).  Every row is mapped to its frame (cx' = cx kx + ox ...) and the frame's candidates are merged by
+    tta_merge's rule: class max, `score > conf`, the class filter, class-aware greedy NMS on `match`: 'iou' (torchvision's) or 'ios'
+    (intersection over the smaller box), both `> iou`.  The candidates that pass the filter are compacted in ascending order into a
+    table of 4096; those beyond it are left out and counted.  Returns device tensors ym f32 [B, max_out, 4 + nc], src i32 [B, max_out]
+    (candidate v_local * nq + q, -1 after the count), counts, dropped (survivors beyond max_out), overflow (passing candidates beyond
+    the table) i32 [B].  ym goes to detect_postprocess unchanged with the same conf / iou / classes / single_cls.  No synchronisation
+    (the factors and classes go up in one copy)."""
+    require_gpu(y)
+    if y.dim() != 3:
+        raise _lib.TamtrHipError(f'slice_merge: expected y [N, nq, 4 + nc], got {tuple(y.shape)}')
+    if match not in SLICE_MATCH:
+        raise _lib.TamtrHipError(f"slice_merge: match must be 'iou' or 'ios', got {match!r}")
+    y = _c(y if y.dtype in (torch.float32, torch.bfloat16) else y.float())
+    N, nq, nd = y.shape
+    dev = y.device
+    off = [int(o) for o in view_off]
+    B = len(off) - 1
+    fac = slice_view_factors(windows, off, hws)
+    if len(fac) != N:
+        raise _lib.TamtrHipError(f'slice_merge: {N} view outputs need {N} windows, got {len(fac)}')
+    max_out = int(max_out)
+    vt = torch.from_numpy(fac).reshape(-1)
+    # an empty filter keeps nothing and still needs a non-NULL pointer, as in detect_postprocess
+    cl = None if classes is None else torch.as_tensor(classes, dtype=torch.int32).reshape(-1)
+    n_cl = 0 if cl is None else cl.numel()
+    if cl is None:
+        vt = vt.to(dev, non_blocking=True)
+    else:      # host operands go up in one copy (the table travels as its bits)
+        cl = cl if n_cl else torch.zeros(1, dtype=torch.int32, device=cl.device)
+        if cl.is_cuda:
+            vt = vt.to(dev, non_blocking=True)
+        else:
+            up = torch.cat([vt.view(torch.int32), cl]).to(dev, non_blocking=True)
+            vt, cl = up[:vt.numel()].view(torch.float32), up[vt.numel():]
+        cl = _c(cl)
+    ym = torch.empty(B, max(max_out, 0), nd, device=dev, dtype=torch.float32)
+    src = torch.empty(B, max(max_out, 0), device=dev, dtype=torch.int32)
+    counts, dropped, overflow = (torch.empty(B, device=dev, dtype=torch.int32) for _ in range(3))
+    offs = (ctypes.c_int32 * (B + 1))(*off)
+    call('tamtr_slice_merge', ptr(y), dtype_code(y), N, B, nq, nd, ctypes.cast(offs, ctypes.c_void_p), ptr(vt), SLICE_MATCH[match], float(conf),
+         _f32_at_most(float(iou)), int(bool(single_cls)), float(max_wh), ptr(cl) if cl is not None else None, n_cl, max_out, ptr(ym), ptr(src),
+         ptr(counts), ptr(dropped), ptr(overflow), stream_ptr())
+    return ym, src, counts, dropped, overflow
+
+
 TRACK_STATE_SPEC =(('mean', torch.float64, (8,)), ('cov', torch.float64, (8, 8)), ('meta', torch.int32, (8,)), ('sc', torch.float32, (2,)))
 
 

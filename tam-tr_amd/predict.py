@@ -67,6 +67,11 @@ def load_image(path, imgsz):
     return im, letterbox_scalefill(im, imgsz)
 
 
+def load_original(path, imgsz=None):
+    """-> (original RGB u8 [h, w, 3], None): the loader of sliced prediction, whose network inputs are cut on the device."""
+    return D.decode_image(path), None
+
+
 def stream_batches(files_per_stream, frames_per_stream=1):
     """The batches of Predictor.track_streams: S file lists (one sequence each) -> [(paths [F * S], active [F * S])] with
     F = frames_per_stream, frame-major: entry f * S + s of batch k is frame k * F + f of stream s.  A stream that has no such frame
@@ -131,6 +136,13 @@ def to_model_input(ims_u8, device, keep_u8=False):
         t = t.pin_memory().to(device, non_blocking=True)
     x = t.permute(0, 3, 1, 2).contiguous().float() / 255
     return (x, t) if keep_u8 else x
+
+
+def _pinned_copy(a):
+    """A host u8 array -> a pinned tensor holding its values (one copy; the array may be read-only, as a decoded image is)."""
+    t = torch.empty(a.shape, dtype=torch.uint8, pin_memory=True)
+    t.numpy()[...] = a
+    return t
 
 
 # ------------------------------------------------------------------------------------------------ results
@@ -219,10 +231,19 @@ class Predictor:
     tta_max_out rows per image, which the postprocess takes as it takes the model's.  `tta_dropped` sums the merged rows that did not
     fit (it rides in the batch's one device-to-host copy), times gains 'tta' (the view launches and the merge, taken out of
     'forward'), and keep_raw then keeps the merged tensor as `last_y` and the per-view inputs / raw outputs as `last_views` /
-    `last_ys`.  track() and track_streams() refuse it: a merged row is no single decoder query."""
+    `last_ys`.  track() and track_streams() refuse it: a merged row is no single decoder query.
+    slice=int | (h, w): sliced prediction for large frames (slicing.py): the loader hands over the original frame only, the frames are
+    uploaded as they are, overlapping windows of `slice` pixels (slicing.slice_windows with slice_overlap; slice_full adds the whole
+    frame as view 0) are cut and resized to imgsz on the device, the model runs on all views in chunks of `batch`, and ops.slice_merge
+    (slice_match 'iou' or 'ios', the predictor's conf / iou / classes / single_cls) leaves one prediction tensor of at most
+    slice_max_out rows per frame, which the postprocess takes as it takes the model's.  `slice_dropped` sums the merged rows that did
+    not fit; candidates beyond the merge's table raise slicing.SliceOverflow; times gains 'slice' (the view launches and the merge,
+    taken out of 'forward'); keep_raw keeps the merged tensor as `last_y` and all views / their raw outputs as `last_views` /
+    `last_ys`.  track() and track_streams() refuse it for augment's reason, and slice together with augment is refused."""
 
     def __init__(self, model, names, text_features, imgsz=640, conf=0.25, iou=0.7, classes=None, single_cls=False, batch=4, dtype='bf16',
-                 keep_raw=False, workers=None, augment=False, tta_views=None, tta_max_out=512):
+                 keep_raw=False, workers=None, augment=False, tta_views=None, tta_max_out=512, slice=None, slice_overlap=0.2, slice_full=True,
+                 slice_match='iou', slice_max_out=512):
         if dtype not in ('bf16', 'fp32'):
             raise ValueError(f"dtype must be 'bf16' or 'fp32', got {dtype!r}")
         self.names = names if isinstance(names, dict) else dict(enumerate(names))
@@ -253,10 +274,22 @@ class Predictor:
             from . import tta
             self.tta_views = tta.check_views(tta.DEFAULT_VIEWS if tta_views is None else tta_views)
             self.times['tta'] = 0.0
+        self.slice, self.slice_dropped = None, 0
+        if slice is not None:
+            from . import slicing
+            if self.augment:
+                raise ValueError('slice and augment cannot be combined: each replaces the forward by views and a merge of its own')
+            if slice_match not in ops.SLICE_MATCH:
+                raise ValueError(f"slice_match must be 'iou' or 'ios', got {slice_match!r}")
+            self.slice = slicing.check_slice(slice)
+            self.slice_overlap, self.slice_full, self.slice_match, self.slice_max_out = float(slice_overlap), bool(slice_full), slice_match, int(slice_max_out)
+            slicing.slice_windows(self.slice[0], self.slice[1], self.slice, self.slice_overlap, self.slice_full)      # checks the overlap now
+            self.times['slice'] = 0.0
 
     @torch.no_grad()
     def run_batch(self, ims, tracker=None, gt_frames=None, evaluator=None, active=None):
         """Network inputs u8 [B, S, S, 3] (host) + original (h, w) per image -> host (out [B, nq, 6], keep [B, nq], counts [B]).
+        With slice set, the first entry is instead the list of the B original frames u8 [h, w, 3] (host), and nq is slice_max_out.
         With a tracker (track.ByteTracker or track.BotSort) the batch's frames also go through one tracker launch, and its rows ride in the same copy:
         -> host (out, keep, counts, tracks [B, nq, 8], tcounts [B]).  With gt_frames (B host arrays [m, 7]) and an evaluator
         (track.MotEvaluator, track.HotaEvaluator or track.TrackMapEvaluator, or a list of them) as well, one more launch per evaluator
@@ -270,17 +303,27 @@ class Predictor:
         ev[0].record()
         gmc = getattr(tracker, 'gmc_method', None) == 'sparseOptFlow'      # a track.BotSort that estimates its warps from the frames
         reid = bool(getattr(tracker, 'with_reid', False))                  # a track.BotSort that takes the decoder's query embeddings
-        img, u8 = to_model_input(arr, self.device, keep_u8=True)
-        ev[1].record()
         ev_tta = []
-        if self.augment:      # views, one forward per canvas size, one merge launch: y is the merged tensor
-            from . import tta
-            y, _, _, dropped, views, ys = tta.tta_forward(self.model, img, None, self.tta_views, self.conf, self.iou, self.classes, self.single_cls,
-                                                          self.tta_max_out, self.autocast_dtype, keep=True, events=ev_tta)
+        if self.slice:      # the original frames go up as they are; views, forwards in chunks of `batch`, one merge launch
+            from . import slicing
+            origs = [_pinned_copy(o).to(self.device, non_blocking=True) for o in arr]
+            ev[1].record()
+            wins = [slicing.slice_windows(h0, w0, self.slice, self.slice_overlap, self.slice_full) for h0, w0 in hw]
+            y, _, _, dropped, overflow, views, ys = slicing.sliced_forward(self.model, origs, wins, self.imgsz, self.batch, None, self.conf, self.iou,
+                                                                           self.classes, self.single_cls, self.slice_match, self.slice_max_out,
+                                                                           self.autocast_dtype, keep=True, events=ev_tta)
+            img = u8 = None      # there is no one network input; a tracker, which would read u8, is refused
         else:
-            with torch.autocast('cuda', dtype=self.autocast_dtype or torch.bfloat16, enabled=self.autocast_dtype is not None):
-                preds = self.model(img)
-            y = preds[0] if isinstance(preds, (list, tuple)) else preds
+            img, u8 = to_model_input(arr, self.device, keep_u8=True)
+            ev[1].record()
+            if self.augment:      # views, one forward per canvas size, one merge launch: y is the merged tensor
+                from . import tta
+                y, _, _, dropped, views, ys = tta.tta_forward(self.model, img, None, self.tta_views, self.conf, self.iou, self.classes,
+                                                              self.single_cls, self.tta_max_out, self.autocast_dtype, keep=True, events=ev_tta)
+            else:
+                with torch.autocast('cuda', dtype=self.autocast_dtype or torch.bfloat16, enabled=self.autocast_dtype is not None):
+                    preds = self.model(img)
+                y = preds[0] if isinstance(preds, (list, tuple)) else preds
         ev[2].record()
         out, keep, counts = ops.detect_postprocess(y, hw, self.conf, self.iou, self.classes, self.single_cls)
         ev[3].record()
@@ -290,6 +333,8 @@ class Predictor:
         parts = {'out': out, 'keep': keep, 'counts': counts}
         if self.augment:
             parts['dropped'] = dropped
+        if self.slice:
+            parts.update(dropped=dropped, overflow=overflow)
         evaluators = _as_list(evaluator) if tracker is not None and gt_frames is not None else []
         ev_eval = []
         ev_gmc = None
@@ -319,12 +364,19 @@ class Predictor:
             spans[1] = ('forward', ev_tta[1], ev_tta[2])
             spans += [('tta', ev[1], ev_tta[1]), ('tta', ev_tta[2], ev[2])]
             self.tta_dropped += int(host['dropped'].sum())
+        if self.slice:
+            spans[1] = ('forward', ev_tta[1], ev_tta[2])
+            spans += [('slice', ev[1], ev_tta[1]), ('slice', ev_tta[2], ev[2])]
+            self.slice_dropped += int(host['dropped'].sum())
         for k, a, b in spans:
             self.times[k] = self.times.get(k, 0.0) + a.elapsed_time(b)
         if self.keep_raw:
             self.last_img, self.last_y = img, y
-            if self.augment:
+            if self.augment or self.slice:
                 self.last_views, self.last_ys = views, ys
+        if self.slice:
+            from .slicing import check_overflow
+            check_overflow(host['overflow'], self.conf)
         res = host['out'], host['keep'], host['counts']
         if tracker is None:
             return res
@@ -415,6 +467,9 @@ class Predictor:
         return self._with_query_embed(frames) if getattr(self.tracker, 'with_reid', False) else frames
 
     def _refuse_augment(self, what):
+        if getattr(self, 'slice', None):
+            raise ValueError(f'{what}() does not take a predictor with slice set: a merged row is no single decoder query of one forward, so the '
+                             'tracker\'s row-to-query identity (ReID) would not hold; build a Predictor without slice for tracking')
         if getattr(self, 'augment', False):      # (an object that never ran __init__ has no augment: the argument checks still work on it)
             raise ValueError(f'{what}() does not take a predictor with augment=True: a merged row is no single decoder query, so the tracker\'s '
                              'row-to-query identity (ReID) would not hold; build a Predictor without augment for tracking')
@@ -462,10 +517,11 @@ class Predictor:
     def _run(self, records, tracker=None, evaluators=(), S=1):
         """The batch loop of predict, track and track_streams over sequence_records / stream_records: yields (stream index, Detections)
         for every image that is not padding.  The next batch decodes while this one runs on the GPU."""
+        load = load_original if self.slice else load_image      # sliced prediction: the host makes no stretched network input
         with ThreadPoolExecutor(max_workers=self.workers) as pool:
             def submit(k):      # a padding entry shares its path's load
                 paths = records[k][0] if k < len(records) else []
-                jobs = {f: pool.submit(load_image, f, self.imgsz) for f in dict.fromkeys(paths)}
+                jobs = {f: pool.submit(load, f, self.imgsz) for f in dict.fromkeys(paths)}
                 return [jobs[f] for f in paths]
             pending = submit(0)
             for k, (paths, active, gt_frames, ending) in enumerate(records):
@@ -475,7 +531,7 @@ class Predictor:
                 pending = submit(k + 1)
                 origs = [o for o, _ in loaded]
                 hw = [o.shape[:2] for o in origs]
-                ims = (np.stack([r for _, r in loaded]), hw)
+                ims = (origs if self.slice else np.stack([r for _, r in loaded]), hw)
                 more = {} if active is None else {'active': active}
                 res = self.run_batch(ims, tracker, **more) if gt_frames is None else self.run_batch(ims, tracker, gt_frames, evaluators, **more)
                 for e in evaluators if ending else []:

@@ -42,8 +42,14 @@
       ops.detect_postprocess on its 512 rows, next to the torch composition (de-augment, torch.cat, then the per-image host loop of
       (a) with engine.nms), and next to the existing ops.detect_postprocess on one view's 300 rows.
 
+  (h) --slice: sliced prediction of ONE frame of 1500 x 2000 (13 views) and of 2160 x 3840 (33 views) at 640-pixel slices, overlap 0.2,
+      imgsz 640, nq = 300, nc = 10: the ops.slice_views launch (device events) next to the same views made on the host
+      (data.resize_linear_u8 per window on the predictor's worker threads, host clock) plus the upload of the V stretched inputs
+      (to_model_input); the upload of the original frame next to that upload; the ops.slice_merge launch on V * 300 candidates next
+      to a torch composition (map and concatenate on the device, then the per-image host loop of (a) with engine.nms).
+
     python tools/predict_bench.py [--images 64] [--kernel-only] [--track [--botsort [--reid]] [--streams S]] [--gmc] [--mot [--streams S]]
-                                  [--hota [--streams S]] [--track-map] [--tta]
+                                  [--hota [--streams S]] [--track-map] [--tta] [--slice]
 --kernel-only runs only the kernel loop of (a), for a `rocprofv3 --kernel-trace --stats` run of its own.
 """
 import argparse
@@ -792,6 +798,84 @@ def bench_tta(B=4, S=640, nq=300, conf=0.25, iou=0.7):
     return rows
 
 
+def host_timed(fn, min_s=1.0, warmup=2):
+    """Median ms per call on the host clock (the call synchronises itself where it uses the device), until >= min_s has passed."""
+    for _ in range(warmup):
+        fn()
+    ts, t0 = [], time.perf_counter()
+    while time.perf_counter() - t0 < min_s or len(ts) < 3:
+        t = time.perf_counter()
+        fn()
+        ts.append((time.perf_counter() - t) * 1e3)
+    return float(np.median(ts)), len(ts)
+
+
+def bench_slice(S=640, sl=640, overlap=0.2, nq=300, nc=10, conf=0.25, iou=0.7):
+    from concurrent.futures import ThreadPoolExecutor
+    from tamtr_amd import data as D, ops, slicing
+    from tamtr_amd.predict import _pinned_copy, allowed_cpus, letterbox_scalefill, to_model_input
+    dev = torch.device('cuda', 0)
+    rows = []
+    for h, w in ((1500, 2000), (2160, 3840)):
+        im = np.random.default_rng(h).integers(0, 256, (h, w, 3), dtype=np.uint8)
+        wins = slicing.slice_windows(h, w, sl, overlap)
+        V = len(wins)
+        src = torch.from_numpy(im).cuda()
+        out = torch.empty(V, 3, S, S, device='cuda')
+        t_views, n_views = timed(lambda: ops.slice_views(src, wins, S, out=out))
+        crop_bytes = 3 * sum((x1 - x0) * (y1 - y0) for x0, y0, x1, y1 in wins.tolist())
+
+        def upload_orig():
+            t = _pinned_copy(im).to(dev, non_blocking=True)
+            torch.cuda.synchronize()
+            return t
+
+        with ThreadPoolExecutor(max_workers=allowed_cpus()) as pool:
+            def host_views():
+                return np.stack(list(pool.map(lambda q: letterbox_scalefill(np.ascontiguousarray(im[q[1]:q[3], q[0]:q[2]]), S), wins.tolist())))
+
+            t_hv, _ = host_timed(host_views)
+            stretched = host_views()
+
+        def upload_views():
+            x = to_model_input(stretched, dev)
+            torch.cuda.synchronize()
+            return x
+
+        t_uo, _ = host_timed(upload_orig)
+        t_uv, _ = host_timed(upload_views)
+        assert torch.equal(upload_views(), ops.slice_views(src, wins, S))      # the two paths make the same network inputs
+        y = synthetic_preds(V, nq, nc, seed=h).cuda()
+        off, hws = [0, V], [(h, w)]
+        fac = torch.from_numpy(ops.slice_view_factors(wins, off, hws)).cuda()[:, None, :]
+
+        def merge():
+            return ops.slice_merge(y, off, wins, hws, conf, iou)
+
+        def merge_postprocess_copy():   # what the predictor does: both launches plus one device-to-host copy of the outputs
+            o, k, c = ops.detect_postprocess(merge()[0], hws, conf, iou)
+            return torch.cat([o.view(-1), k.view(torch.float32).view(-1), c.view(torch.float32)]).cpu()
+
+        def torch_composition():        # map and concatenate on the device, then the per-image host loop of (a)
+            m = torch.cat([y[..., 0:1] * fac[..., 2:3] + fac[..., 0:1], y[..., 1:2] * fac[..., 3:4] + fac[..., 1:2], y[..., 2:3] * fac[..., 2:3],
+                           y[..., 3:4] * fac[..., 3:4], y[..., 4:]], -1)
+            return host_loop(m.reshape(1, V * nq, 4 + nc), hws, conf, iou)
+
+        t_m, n_m = timed(merge)
+        t_mpc, _ = timed(merge_postprocess_copy)
+        t_h, n_h = timed(torch_composition)
+        _, _, counts, dropped, overflow = merge()
+        passing = int((y[..., 4:].max(-1).values > conf).sum())
+        rows.append({'frame': [h, w], 'slice': sl, 'overlap': overlap, 'imgsz': S, 'views': V, 'nq': nq, 'nc': nc,
+                     'slice_views_ms': round(t_views, 4), 'slice_views_GB_per_s': round((crop_bytes + 4 * V * 3 * S * S) / t_views / 1e6, 1),
+                     'host_views_ms': round(t_hv, 2), 'host_workers': allowed_cpus(), 'upload_original_ms': round(t_uo, 3),
+                     'upload_V_inputs_ms': round(t_uv, 3), 'device_path_ms': round(t_uo + t_views, 3), 'host_path_ms': round(t_hv + t_uv, 3),
+                     'candidates': V * nq, 'passing': passing, 'merged': int(counts[0]), 'dropped': int(dropped[0]), 'overflow': int(overflow[0]),
+                     'slice_merge_ms': round(t_m, 4), 'merge_postprocess_d2h_ms': round(t_mpc, 4), 'torch_map_cat_host_loop_ms': round(t_h, 3),
+                     'speedup_vs_torch': round(t_h / t_mpc, 1), 'iters': [n_views, n_m, n_h]})
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--images', type=int, default=64)
@@ -809,6 +893,7 @@ def main():
     ap.add_argument('--track-map', action='store_true', help='only (f): the track-mAP launches against copy + numpy twin, on the sequence of --hota '
                     'with scores added, next to the HOTA update launch')
     ap.add_argument('--tta', action='store_true', help='only (g): the test-time-augmentation view and merge launches against their torch compositions')
+    ap.add_argument('--slice', action='store_true', help='only (h): the sliced-prediction view and merge launches against the host views and a torch composition')
     args = ap.parse_args()
     import tamtr_amd  # noqa: F401
     assert torch.cuda.is_available(), 'predict_bench needs an MI355X'
@@ -857,6 +942,12 @@ def main():
     if args.tta:
         print('(g) test-time augmentation, one batch of 4 at 640 x 640, three views (device events, >= 1 s window after 5 warm-up calls)')
         for r in bench_tta():
+            print(json.dumps(r))
+        return
+    if args.slice:
+        print('(h) sliced prediction of one frame, 640-pixel slices at overlap 0.2 plus the whole frame, imgsz 640 (device events, >= 1 s window after '
+              '5 warm-up calls; host paths on the host clock, median)')
+        for r in bench_slice():
             print(json.dumps(r))
         return
     if args.kernel_only:
