@@ -1,6 +1,8 @@
 // postproc.h - device helpers shared by the two detection postprocess kernels: predict.hip (the predictor's rule) and
-// valmatch.hip (the validator's rule), and by the two merges that feed them, tta.hip and slice.hip (pp_overlap, pp_greedy_tiles).  All
-// are compiled with -ffp-contract=off; every float operation here rounds on its own.
+// valmatch.hip (the validator's rule), and by the two merges that feed them, tta.hip and slice.hip: the filter and the GW launch
+// switch serve all four; the pair sort, the shifted boxes, the tile-wise greedy pass and the output stage (pp_merge_*) are the merges'
+// common body, which sees a kernel's candidates through its row source.  All are compiled with -ffp-contract=off; every float
+// operation here rounds on its own.
 #pragma once
 #include "common.h"
 
@@ -44,12 +46,51 @@ __device__ __forceinline__ void pp_row_max(const T* r, int nc, int sub, bool row
   }
 }
 
-// Bitonic sort of P <= PP_THREADS keys in LDS, ascending (P a power of two); called by the whole workgroup, ends on a barrier.
+// The filter: a row needs score > conf (a NaN score fails) and, with a class filter, its class among classes[0 .. n_classes).
+__device__ __forceinline__ bool pp_passes(float bv, int bi, float conf, const int32_t* __restrict__ classes, int n_classes) {
+  bool ok = bv > conf;
+  if (ok && classes) {
+    bool in = false;
+    for (int k = 0; k < n_classes; ++k) in |= classes[k] == bi;
+    ok = in;
+  }
+  return ok;
+}
+
+// The class-max group width GW from the class count nc: 4 lanes per row up to 8 classes, 16 up to 32, else a whole wave.  LAUNCH(GW) is
+// the caller's launch statement.
+#define PP_LAUNCH_GW(nc, LAUNCH)         \
+  do {                                   \
+    if ((nc) <= 8) { LAUNCH(4); }        \
+    else if ((nc) <= 32) { LAUNCH(16); } \
+    else { LAUNCH(64); }                 \
+  } while (0)
+
+// Bitonic sort of P <= PP_THREADS keys in LDS, ascending (P a power of two), one key per thread; called by the whole workgroup, ends on a
+// barrier.  predict.hip's and valmatch.hip's: measured against pp_bitonic_sort_pairs at P = 512 it saves the pair index arithmetic of 45
+// latency-bound steps, about 1.5 us of a 95 us launch (profiles/merge_shared_stages.txt).
 __device__ __forceinline__ void pp_bitonic_sort(uint64_t* key, int P, int tid) {
   for (int k = 2; k <= P; k <<= 1) {
     for (int j = k >> 1; j > 0; j >>= 1) {
       const int i = tid, l = i ^ j;
       if (i < P && l > i) {
+        const uint64_t a = key[i], c = key[l];
+        if ((a > c) == ((i & k) == 0)) { key[i] = c; key[l] = a; }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// The same sort for any P, by a workgroup of THREADS: thread t takes pairs t, t + THREADS, ... of every step, one barrier per step; ends
+// on a barrier.  The merges' (P up to 4096 on 1024 threads).  The keys are unique apart from the ~0ull fillers, so the sorted array does
+// not depend on which of the two networks produced it.
+template <int THREADS>
+__device__ __forceinline__ void pp_bitonic_sort_pairs(uint64_t* key, int P, int tid) {
+  for (int k = 2; k <= P; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < P / 2; t += THREADS) {
+        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
         const uint64_t a = key[i], c = key[l];
         if ((a > c) == ((i & k) == 0)) { key[i] = c; key[l] = a; }
       }
@@ -182,4 +223,62 @@ __device__ __forceinline__ int pp_greedy_tiles(const float (*sbox)[4], uint64_t*
     }
   }
   return cnt;
+}
+
+// ---- the merges' common body (tta.hip, slice.hip).  A kernel hands its candidates over as a row source `rows`, a small struct passed by
+// value: cand(key) = the candidate of a sort key, cls_of(key) = its class, row(i) = candidate i's source row, box(i, o) = its box
+// cx' cy' w' h' in the merged frame.
+
+// cx cy w h -> the corner box shifted by cls * max_wh (not at all when single_cls), as the NMS sees it
+__device__ __forceinline__ void pp_shifted_box(const float (&c)[4], int cls, int single_cls, float max_wh, float* out) {
+  const float dw = c[2] / 2.0f, dh = c[3] / 2.0f;
+  const float sh = (float)cls * (single_cls ? 0.0f : max_wh);
+  out[0] = (c[0] - dw) + sh;
+  out[1] = (c[1] - dh) + sh;
+  out[2] = (c[0] + dw) + sh;
+  out[3] = (c[1] + dh) + sh;
+}
+
+// Shifted corner boxes of the n sorted candidates, in NMS order (the four box numbers are read again from global memory: 16 bytes per
+// row, no LDS copy); ends on a barrier.
+template <int THREADS, typename Rows>
+__device__ __forceinline__ void pp_merge_sbox(const Rows rows, const uint64_t* key, int n, int single_cls, float max_wh, float (*sbox)[4],
+                                              int tid) {
+  for (int p = tid; p < n; p += THREADS) {
+    float c[4];
+    rows.box(rows.cand(key[p]), c);
+    pp_shifted_box(c, rows.cls_of(key[p]), single_cls, max_wh, sbox[p]);
+  }
+  __syncthreads();
+}
+
+// Outputs of image b from the greedy pass's kept[] and cnt: the first max_out survivors in order - the box recomputed, the source row's
+// scores widened exactly - then zero rows; src = the candidate, -1 after them; counts = rows written, dropped = survivors that did not
+// fit.  Coalesced over ym.
+template <typename T, int THREADS, typename Rows>
+__device__ __forceinline__ void pp_merge_write(const Rows rows, const uint64_t* key, const int* kept, int cnt, int max_out, int nd, int b,
+                                               int tid, float* __restrict__ ym, int32_t* __restrict__ src, int32_t* __restrict__ counts,
+                                               int32_t* __restrict__ dropped) {
+  const int n_rows = cnt < max_out ? cnt : max_out;
+  float* ob = ym + (size_t)b * max_out * nd;
+  for (int e = tid; e < max_out * nd; e += THREADS) {
+    const int r = e / nd, c = e - r * nd;
+    float val = 0.0f;
+    if (r < n_rows) {
+      const int i = rows.cand(key[kept[r]]);
+      if (c < 4) {
+        float bx[4];
+        rows.box(i, bx);
+        val = bx[c];
+      } else {
+        val = Elt<T>::ld(rows.row(i) + c);
+      }
+    }
+    ob[e] = val;
+  }
+  for (int r = tid; r < max_out; r += THREADS) src[(size_t)b * max_out + r] = r < n_rows ? rows.cand(key[kept[r]]) : -1;
+  if (tid == 0) {
+    counts[b] = n_rows;
+    dropped[b] = cnt - n_rows;
+  }
 }

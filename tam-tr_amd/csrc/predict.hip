@@ -77,12 +77,7 @@ __global__ __launch_bounds__(PP_THREADS) void detect_postprocess_kernel(const T*
       s.box[q][3] = bx[1] + dh;
       s.score[q] = bv;
       s.cls[q] = bi;
-      bool ok = bv > conf;
-      if (ok && classes) {
-        bool in = false;
-        for (int k = 0; k < n_classes; ++k) in |= classes[k] == bi;
-        ok = in;
-      }
+      const bool ok = pp_passes(bv, bi, conf, classes, n_classes);
       s.key[q] = ok ? ((uint64_t)~pp_ordered(bv) << 32) | (uint32_t)q : ~0ull;
       n_local += ok;
     }
@@ -138,17 +133,12 @@ __global__ __launch_bounds__(PP_THREADS) void detect_postprocess_kernel(const T*
 template <typename T>
 static void pp_launch(const void* preds, int B, int nq, int nd, const int32_t* orig_hw, float conf, float iou, int single_cls, float max_wh,
                       const int32_t* classes, int n_classes, float* out, int32_t* keep, int32_t* counts, hipStream_t st) {
-  const int nc = nd - 4;
   const T* p = static_cast<const T*>(preds);
-  if (nc <= 8)
-    hipLaunchKernelGGL((detect_postprocess_kernel<T, 4>), dim3(B), dim3(PP_THREADS), 0, st, p, nq, nd, orig_hw, conf, iou, single_cls,
-                       max_wh, classes, n_classes, out, keep, counts);
-  else if (nc <= 32)
-    hipLaunchKernelGGL((detect_postprocess_kernel<T, 16>), dim3(B), dim3(PP_THREADS), 0, st, p, nq, nd, orig_hw, conf, iou, single_cls,
-                       max_wh, classes, n_classes, out, keep, counts);
-  else
-    hipLaunchKernelGGL((detect_postprocess_kernel<T, 64>), dim3(B), dim3(PP_THREADS), 0, st, p, nq, nd, orig_hw, conf, iou, single_cls,
-                       max_wh, classes, n_classes, out, keep, counts);
+#define PP_LAUNCH(GW)                                                                                                                  \
+  hipLaunchKernelGGL((detect_postprocess_kernel<T, GW>), dim3(B), dim3(PP_THREADS), 0, st, p, nq, nd, orig_hw, conf, iou, single_cls, \
+                     max_wh, classes, n_classes, out, keep, counts)
+  PP_LAUNCH_GW(nd - 4, PP_LAUNCH);
+#undef PP_LAUNCH
 }
 
 extern "C" int tamtr_detect_postprocess(const void* preds, int dtype, int B, int nq, int nd, const int32_t* orig_hw, float conf, float iou,

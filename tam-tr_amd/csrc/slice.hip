@@ -40,8 +40,9 @@
 //      of candidate i is its word's offset + the set bits below it - ascending i, no counter that threads race for.
 //   3. the compacted table: candidate index per position; class max again for the <= SL_MAX_C rows that go on (16 to 320 bytes each,
 //      cheaper than an LDS copy of 32768 scores), sort key (~ordered(score) << 32 | position: positions ascend with i).
-//   4. bitonic sort over the next power of two of the table, shifted corner boxes in NMS order, the tile-wise greedy pass of
-//      postproc.h (pp_greedy_tiles, shared with tta.hip), coalesced write of ym / src and the three counters.
+//   4. the stages of postproc.h, shared with tta.hip, which reach the candidates through SlRows: bitonic sort over the next power of
+//      two of the table (pp_bitonic_sort_pairs), shifted corner boxes in NMS order (pp_merge_sbox), the tile-wise greedy pass
+//      (pp_greedy_tiles), coalesced write of ym / src and two counters (pp_merge_write); overflow is written here.
 // LDS: key 32 KB + cand 16 KB + cls 16 KB + sbox 64 KB + candidate mask 4 KB + word offsets 2 KB + rem 0.5 KB + tile masks 1 KB +
 // kept 2 KB = about 138 KB of the CU's 160 KB; one workgroup per CU, which 16 waves fill to half its wave slots anyway.
 #include "postproc.h"
@@ -155,6 +156,20 @@ __device__ __forceinline__ void sl_box(const T* r, const float* __restrict__ vw,
   o[3] = Elt<T>::ld(r + 3) * ky;
 }
 
+// The merge's row source: the frame's rows are contiguous, candidate i is row i; a sort key's low word is a compacted position, which
+// indexes cand[] and cls[]
+template <typename T>
+struct SlRows {
+  const T* yb;
+  const float* vb;
+  const int *cands, *cls;  // by compacted position
+  int nq, nd;
+  __device__ __forceinline__ int cand(uint64_t key) const { return cands[key & 0xffffffffu]; }
+  __device__ __forceinline__ int cls_of(uint64_t key) const { return cls[key & 0xffffffffu]; }
+  __device__ __forceinline__ const T* row(int i) const { return yb + (size_t)i * nd; }
+  __device__ __forceinline__ void box(int i, float (&o)[4]) const { sl_box<T>(row(i), vb + 4 * (i / nq), o); }
+};
+
 template <typename T, int GW, int MATCH>
 __global__ __launch_bounds__(SL_THREADS) void slice_merge_kernel(const T* __restrict__ y, SlOffsets offs, int nq, int nd,
                                                                  const float* __restrict__ views, float conf, float thr, int single_cls,
@@ -166,7 +181,7 @@ __global__ __launch_bounds__(SL_THREADS) void slice_merge_kernel(const T* __rest
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
   const int nc = nd - 4, v0 = offs.off[b], N = (offs.off[b + 1] - v0) * nq;  // N <= SL_MAX_N: checked by the host
   const T* yb = y + (size_t)v0 * nq * nd;                                     // the frame's rows are contiguous: candidate i is row i
-  const float* vb = views + (size_t)v0 * 4;
+  const SlRows<T> rows = {yb, views + (size_t)v0 * 4, s.cand, s.cls, nq, nd};
   const uint64_t* mask64 = reinterpret_cast<const uint64_t*>(s.mask);
   for (int w = tid; w < 2 * SL_WORDS; w += SL_THREADS) s.mask[w] = 0;
   for (int w = tid; w < SL_MAX_C / 64; w += SL_THREADS) s.rem[w] = 0;
@@ -179,16 +194,8 @@ __global__ __launch_bounds__(SL_THREADS) void slice_merge_kernel(const T* __rest
     const bool row = i < N;  // uniform inside the group
     float bv;
     int bi;
-    pp_row_max<T, GW>(yb + (size_t)(row ? i : 0) * nd, nc, sub, row, bv, bi);
-    if (row && sub == 0) {
-      bool ok = bv > conf;
-      if (ok && classes) {
-        bool in = false;
-        for (int k = 0; k < n_classes; ++k) in |= classes[k] == bi;
-        ok = in;
-      }
-      if (ok) atomicOr(&s.mask[i >> 5], 1u << (i & 31));
-    }
+    pp_row_max<T, GW>(rows.row(row ? i : 0), nc, sub, row, bv, bi);
+    if (row && sub == 0 && pp_passes(bv, bi, conf, classes, n_classes)) atomicOr(&s.mask[i >> 5], 1u << (i & 31));
   }
   __syncthreads();
 
@@ -226,7 +233,7 @@ __global__ __launch_bounds__(SL_THREADS) void slice_merge_kernel(const T* __rest
     const bool row = p < n;
     float bv;
     int bi;
-    pp_row_max<T, GW>(yb + (size_t)(row ? s.cand[p] : 0) * nd, nc, sub, row, bv, bi);
+    pp_row_max<T, GW>(rows.row(row ? s.cand[p] : 0), nc, sub, row, bv, bi);
     if (row && sub == 0) {
       s.cls[p] = bi;
       s.key[p] = ((uint64_t)~pp_ordered(bv) << 32) | (uint32_t)p;
@@ -237,76 +244,26 @@ __global__ __launch_bounds__(SL_THREADS) void slice_merge_kernel(const T* __rest
   for (int p = n + tid; p < P; p += SL_THREADS) s.key[p] = ~0ull;
   __syncthreads();
 
-  // ---- 4. bitonic sort of P <= SL_MAX_C keys, ascending (= NMS order): thread t takes pairs t, t + SL_THREADS, ... of every step
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < P / 2; t += SL_THREADS) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-        const uint64_t a = s.key[i], c = s.key[l];
-        if ((a > c) == ((i & k) == 0)) { s.key[i] = c; s.key[l] = a; }
-      }
-      __syncthreads();
-    }
-  }
-  // shifted corner boxes in NMS order (the four box numbers are read again from global memory)
-  for (int p = tid; p < n; p += SL_THREADS) {
-    const int cp = (int)(s.key[p] & 0xffffffffu), i = s.cand[cp];
-    float c[4];
-    sl_box<T>(yb + (size_t)i * nd, vb + 4 * (i / nq), c);
-    const float dw = c[2] / 2.0f, dh = c[3] / 2.0f;
-    const float sh = (float)s.cls[cp] * (single_cls ? 0.0f : max_wh);
-    s.sbox[p][0] = (c[0] - dw) + sh;
-    s.sbox[p][1] = (c[1] - dh) + sh;
-    s.sbox[p][2] = (c[0] + dw) + sh;
-    s.sbox[p][3] = (c[1] + dh) + sh;
-  }
-  __syncthreads();
+  // ---- 4. (postproc.h) sort of P <= SL_MAX_C keys (= NMS order), shifted boxes, greedy pass, outputs
+  pp_bitonic_sort_pairs<SL_THREADS>(s.key, P, tid);
+  pp_merge_sbox<SL_THREADS>(rows, s.key, n, single_cls, max_wh, s.sbox, tid);
   const int cnt = pp_greedy_tiles<SL_WAVES, MATCH>(s.sbox, s.rem, s.tmask, s.kept, n, thr, max_out, wave, lane);
   __syncthreads();
-
-  // ---- 5. outputs: the first max_out survivors, then zero / -1 padding
-  const int rows = cnt < max_out ? cnt : max_out;
-  float* ob = ym + (size_t)b * max_out * nd;
-  for (int e = tid; e < max_out * nd; e += SL_THREADS) {
-    const int r = e / nd, c = e - r * nd;
-    float val = 0.0f;
-    if (r < rows) {
-      const int i = s.cand[s.key[s.kept[r]] & 0xffffffffu];
-      const T* row = yb + (size_t)i * nd;
-      if (c < 4) {
-        float bx[4];
-        sl_box<T>(row, vb + 4 * (i / nq), bx);
-        val = bx[c];
-      } else {
-        val = Elt<T>::ld(row + c);
-      }
-    }
-    ob[e] = val;
-  }
-  for (int r = tid; r < max_out; r += SL_THREADS)
-    src[(size_t)b * max_out + r] = r < rows ? s.cand[s.key[s.kept[r]] & 0xffffffffu] : -1;
-  if (tid == 0) {
-    counts[b] = rows;
-    dropped[b] = cnt - rows;
-    overflow[b] = n_pass - n;
-  }
+  pp_merge_write<T, SL_THREADS>(rows, s.key, s.kept, cnt, max_out, nd, b, tid, ym, src, counts, dropped);
+  if (tid == 0) overflow[b] = n_pass - n;
 }
 
-#define SL_LAUNCH(T, GW, M)                                                                                                              \
-  hipLaunchKernelGGL((slice_merge_kernel<T, GW, M>), dim3(B), dim3(SL_THREADS), 0, st, static_cast<const T*>(y), offs, nq, nd, views, conf, \
-                     thr, single_cls, max_wh, classes, n_classes, max_out, ym, src, counts, dropped, overflow)
-
-template <typename T, int M>
-static void sl_launch(const void* y, const SlOffsets& offs, int B, int nq, int nd, const float* views, float conf, float thr,
+template <typename T>
+static void sl_launch(const void* y, const SlOffsets& offs, int B, int nq, int nd, const float* views, int match, float conf, float thr,
                       int single_cls, float max_wh, const int32_t* classes, int n_classes, int max_out, float* ym, int32_t* src,
                       int32_t* counts, int32_t* dropped, int32_t* overflow, hipStream_t st) {
-  const int nc = nd - 4;
-  if (nc <= 8)
-    SL_LAUNCH(T, 4, M);
-  else if (nc <= 32)
-    SL_LAUNCH(T, 16, M);
-  else
-    SL_LAUNCH(T, 64, M);
+#define SL_LAUNCH_M(GW, M)                                                                                                                  \
+  hipLaunchKernelGGL((slice_merge_kernel<T, GW, M>), dim3(B), dim3(SL_THREADS), 0, st, static_cast<const T*>(y), offs, nq, nd, views, conf, \
+                     thr, single_cls, max_wh, classes, n_classes, max_out, ym, src, counts, dropped, overflow)
+#define SL_LAUNCH(GW) if (match == 0) SL_LAUNCH_M(GW, 0); else SL_LAUNCH_M(GW, 1)
+  PP_LAUNCH_GW(nd - 4, SL_LAUNCH);
+#undef SL_LAUNCH
+#undef SL_LAUNCH_M
 }
 
 extern "C" int tamtr_slice_merge(const void* y, int dtype, int N, int B, int nq, int nd, const int32_t* view_off, const float* views,
@@ -330,21 +287,11 @@ extern "C" int tamtr_slice_merge(const void* y, int dtype, int N, int B, int nq,
   offs.off[B] = N;
   if (wide || nq > SL_MAX_NQ || max_out > PP_MAX_Q) return TAMTR_EUNSUP;
   hipStream_t st = (hipStream_t)stream;
-  const float thr = iou;
-  if (dtype == TAMTR_F32) {
-    if (match == 0)
-      sl_launch<float, 0>(y, offs, B, nq, nd, views, conf, thr, single_cls, max_wh, classes, n_classes, max_out, ym, src, counts, dropped,
-                          overflow, st);
-    else
-      sl_launch<float, 1>(y, offs, B, nq, nd, views, conf, thr, single_cls, max_wh, classes, n_classes, max_out, ym, src, counts, dropped,
-                          overflow, st);
-  } else {
-    if (match == 0)
-      sl_launch<bf16_t, 0>(y, offs, B, nq, nd, views, conf, thr, single_cls, max_wh, classes, n_classes, max_out, ym, src, counts,
-                           dropped, overflow, st);
-    else
-      sl_launch<bf16_t, 1>(y, offs, B, nq, nd, views, conf, thr, single_cls, max_wh, classes, n_classes, max_out, ym, src, counts,
-                           dropped, overflow, st);
-  }
+  if (dtype == TAMTR_F32)
+    sl_launch<float>(y, offs, B, nq, nd, views, match, conf, iou, single_cls, max_wh, classes, n_classes, max_out, ym, src, counts, dropped,
+                     overflow, st);
+  else
+    sl_launch<bf16_t>(y, offs, B, nq, nd, views, match, conf, iou, single_cls, max_wh, classes, n_classes, max_out, ym, src, counts, dropped,
+                      overflow, st);
   return tamtr_launch_status();
 }

@@ -30,13 +30,12 @@
 //
 // Design: one workgroup of 16 waves per image, N = V nq <= 2048 candidates, about 59 KB of LDS.  A full N x N suppression mask would
 // take 512 KB, so predict.hip's mask-then-greedy pass does not carry over:
-//   1. class max per row by groups of GW lanes, filter, 64-bit key (~ordered(score) << 32 | i), all ones for rows that fail.
-//   2. bitonic sort over the next power of two: survivors first, in NMS order.
-//   3. shifted corner boxes in NMS order (the four box numbers are read again from global memory: 16 bytes per row, no LDS copy).
-//   4. greedy pass over tiles of 64 rows, one barrier per tile: the waves build the tile's 64 x 64 mask with ballots (double
-//      buffered); every wave resolves it by itself from registers (lane r holds row r's word, 64 readlanes) starting from the tile's
-//      removed word; then the tile's kept rows strike all later rows in parallel - a wave owns the removed words it writes.
-//   5. coalesced write of ym / src (zero / -1 padding) and the two counters.
+//   1. class max per row by groups of GW lanes, filter (pp_passes), 64-bit key (~ordered(score) << 32 | i), all ones for rows that fail.
+//   2. bitonic sort over the next power of two: survivors first, in NMS order (pp_bitonic_sort_pairs).
+//   3. shifted corner boxes in NMS order (pp_merge_sbox).
+//   4. greedy pass over tiles of 64 rows, one barrier per tile (pp_greedy_tiles).
+//   5. coalesced write of ym / src (zero / -1 padding) and the two counters (pp_merge_write).
+// Stages 2 to 5 are postproc.h's, shared with slice.hip; they reach the candidates through TtaRows.
 #include "postproc.h"
 
 #define TTA_MAX_N 2048
@@ -123,6 +122,23 @@ __device__ __forceinline__ void tta_box(const T* r, const float* __restrict__ vw
   o[3] = Elt<T>::ld(r + 3) * ky;
 }
 
+// The merge's row source: candidate i = v nq + q is row q of view v; a sort key's low word is the candidate, which also indexes cls[]
+template <typename T>
+struct TtaRows {
+  const TtaViews& ys;
+  const float* views;
+  const int* cls;  // by candidate
+  size_t img;
+  int nq, nd;
+  __device__ __forceinline__ int cand(uint64_t key) const { return (int)(key & 0xffffffffu); }
+  __device__ __forceinline__ int cls_of(uint64_t key) const { return cls[cand(key)]; }
+  __device__ __forceinline__ const T* row(int i) const {
+    const int v = i / nq;
+    return static_cast<const T*>(ys.y[v]) + img + (size_t)(i - v * nq) * nd;
+  }
+  __device__ __forceinline__ void box(int i, float (&o)[4]) const { tta_box<T>(row(i), views + 4 * (i / nq), o); }
+};
+
 template <typename T, int GW>
 __global__ __launch_bounds__(TTA_THREADS) void tta_merge_kernel(TtaViews ys, int V, int nq, int nd, const float* __restrict__ views,
                                                                 float conf, float thr, int single_cls, float max_wh,
@@ -132,7 +148,7 @@ __global__ __launch_bounds__(TTA_THREADS) void tta_merge_kernel(TtaViews ys, int
   __shared__ TtaShared s;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
   const int nc = nd - 4, N = V * nq;
-  const size_t img = (size_t)b * nq * nd;
+  const TtaRows<T> rows = {ys, views, s.cls, (size_t)b * nq * nd, nq, nd};
   if (tid == 0) s.n = 0;
   for (int w = tid; w < TTA_MAX_N / 64; w += TTA_THREADS) s.rem[w] = 0;
   __syncthreads();
@@ -144,18 +160,12 @@ __global__ __launch_bounds__(TTA_THREADS) void tta_merge_kernel(TtaViews ys, int
     const int i = i0 + tid / GW;
     const bool row = i < N;  // uniform inside the group
     const int v = row ? i / nq : 0, q = row ? i - v * nq : 0;
-    const T* r = static_cast<const T*>(ys.y[v]) + img + (size_t)q * nd;
     float bv;
     int bi;
-    pp_row_max<T, GW>(r, nc, sub, row, bv, bi);
+    pp_row_max<T, GW>(static_cast<const T*>(ys.y[v]) + rows.img + (size_t)q * nd, nc, sub, row, bv, bi);
     if (row && sub == 0) {
       s.cls[i] = bi;
-      bool ok = bv > conf;
-      if (ok && classes) {
-        bool in = false;
-        for (int k = 0; k < n_classes; ++k) in |= classes[k] == bi;
-        ok = in;
-      }
+      const bool ok = pp_passes(bv, bi, conf, classes, n_classes);
       s.key[i] = ok ? ((uint64_t)~pp_ordered(bv) << 32) | (uint32_t)i : ~0ull;
       n_local += ok;
     }
@@ -167,77 +177,23 @@ __global__ __launch_bounds__(TTA_THREADS) void tta_merge_kernel(TtaViews ys, int
   __syncthreads();
   const int n = s.n;
 
-  // ---- 2. bitonic sort of P <= 2048 keys, ascending (= NMS order; failed rows last): thread t takes pair t of every step
-  for (int k = 2; k <= P; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int t = tid; t < P / 2; t += TTA_THREADS) {
-        const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), l = i | j;
-        const uint64_t a = s.key[i], c = s.key[l];
-        if ((a > c) == ((i & k) == 0)) { s.key[i] = c; s.key[l] = a; }
-      }
-      __syncthreads();
-    }
-  }
-
-  // ---- 3. shifted corner boxes in NMS order
-  for (int p = tid; p < n; p += TTA_THREADS) {
-    const int i = (int)(s.key[p] & 0xffffffffu), v = i / nq, q = i - v * nq;
-    float c[4];
-    tta_box<T>(static_cast<const T*>(ys.y[v]) + img + (size_t)q * nd, views + 4 * v, c);
-    const float dw = c[2] / 2.0f, dh = c[3] / 2.0f;
-    const float sh = (float)s.cls[i] * (single_cls ? 0.0f : max_wh);
-    s.sbox[p][0] = (c[0] - dw) + sh;
-    s.sbox[p][1] = (c[1] - dh) + sh;
-    s.sbox[p][2] = (c[0] + dw) + sh;
-    s.sbox[p][3] = (c[1] + dh) + sh;
-  }
+  // ---- 2 - 5 (postproc.h): sort of P <= 2048 keys (= NMS order; failed rows last), shifted boxes, greedy pass, outputs
+  pp_bitonic_sort_pairs<TTA_THREADS>(s.key, P, tid);
+  pp_merge_sbox<TTA_THREADS>(rows, s.key, n, single_cls, max_wh, s.sbox, tid);
+  const int cnt = pp_greedy_tiles<TTA_WAVES, 0>(s.sbox, s.rem, s.tmask, s.kept, n, thr, max_out, wave, lane);  // the same in every thread
   __syncthreads();
-
-  // ---- 4. greedy pass over tiles of 64 rows (postproc.h); `cnt` is the same in every thread
-  const int cnt = pp_greedy_tiles<TTA_WAVES, 0>(s.sbox, s.rem, s.tmask, s.kept, n, thr, max_out, wave, lane);
-  __syncthreads();
-
-  // ---- 5. outputs: the first max_out survivors, then zero / -1 padding
-  const int rows = cnt < max_out ? cnt : max_out;
-  float* ob = ym + (size_t)b * max_out * nd;
-  for (int e = tid; e < max_out * nd; e += TTA_THREADS) {
-    const int r = e / nd, c = e - r * nd;
-    float val = 0.0f;
-    if (r < rows) {
-      const int i = (int)(s.key[s.kept[r]] & 0xffffffffu), v = i / nq, q = i - v * nq;
-      const T* row = static_cast<const T*>(ys.y[v]) + img + (size_t)q * nd;
-      if (c < 4) {
-        float bx[4];
-        tta_box<T>(row, views + 4 * v, bx);
-        val = bx[c];
-      } else {
-        val = Elt<T>::ld(row + c);
-      }
-    }
-    ob[e] = val;
-  }
-  for (int r = tid; r < max_out; r += TTA_THREADS)
-    src[(size_t)b * max_out + r] = r < rows ? (int)(s.key[s.kept[r]] & 0xffffffffu) : -1;
-  if (tid == 0) {
-    counts[b] = rows;
-    dropped[b] = cnt - rows;
-  }
+  pp_merge_write<T, TTA_THREADS>(rows, s.key, s.kept, cnt, max_out, nd, b, tid, ym, src, counts, dropped);
 }
 
 template <typename T>
 static void tta_launch(const TtaViews& ys, int V, int B, int nq, int nd, const float* views, float conf, float iou, int single_cls,
                        float max_wh, const int32_t* classes, int n_classes, int max_out, float* ym, int32_t* src, int32_t* counts,
                        int32_t* dropped, hipStream_t st) {
-  const int nc = nd - 4;
-  if (nc <= 8)
-    hipLaunchKernelGGL((tta_merge_kernel<T, 4>), dim3(B), dim3(TTA_THREADS), 0, st, ys, V, nq, nd, views, conf, iou, single_cls, max_wh,
-                       classes, n_classes, max_out, ym, src, counts, dropped);
-  else if (nc <= 32)
-    hipLaunchKernelGGL((tta_merge_kernel<T, 16>), dim3(B), dim3(TTA_THREADS), 0, st, ys, V, nq, nd, views, conf, iou, single_cls, max_wh,
-                       classes, n_classes, max_out, ym, src, counts, dropped);
-  else
-    hipLaunchKernelGGL((tta_merge_kernel<T, 64>), dim3(B), dim3(TTA_THREADS), 0, st, ys, V, nq, nd, views, conf, iou, single_cls, max_wh,
-                       classes, n_classes, max_out, ym, src, counts, dropped);
+#define TTA_LAUNCH(GW)                                                                                                                  \
+  hipLaunchKernelGGL((tta_merge_kernel<T, GW>), dim3(B), dim3(TTA_THREADS), 0, st, ys, V, nq, nd, views, conf, iou, single_cls, max_wh, \
+                     classes, n_classes, max_out, ym, src, counts, dropped)
+  PP_LAUNCH_GW(nd - 4, TTA_LAUNCH);
+#undef TTA_LAUNCH
 }
 
 extern "C" int tamtr_tta_merge(const void* const* ys, int V, int dtype, int B, int nq, int nd, const float* views, float conf, float iou,

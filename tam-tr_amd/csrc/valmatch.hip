@@ -214,17 +214,12 @@ template <typename T>
 static void vm_launch(const void* preds, int B, int nq, int nd, float imgsz, float conf, float iou, int single_cls, float max_wh,
                       const float* lab_cls, const float* lab_box, const int32_t* lab_off, int M, const float* scale, float* predn,
                       uint8_t* correct, int32_t* counts, hipStream_t st) {
-  const int nc = nd - 4;
   const T* p = static_cast<const T*>(preds);
-  if (nc <= 8)
-    hipLaunchKernelGGL((val_postprocess_match_kernel<T, 4>), dim3(B), dim3(PP_THREADS), 0, st, p, nq, nd, imgsz, conf, iou, single_cls, max_wh,
-                       lab_cls, lab_box, lab_off, M, scale, predn, correct, counts);
-  else if (nc <= 32)
-    hipLaunchKernelGGL((val_postprocess_match_kernel<T, 16>), dim3(B), dim3(PP_THREADS), 0, st, p, nq, nd, imgsz, conf, iou, single_cls, max_wh,
-                       lab_cls, lab_box, lab_off, M, scale, predn, correct, counts);
-  else
-    hipLaunchKernelGGL((val_postprocess_match_kernel<T, 64>), dim3(B), dim3(PP_THREADS), 0, st, p, nq, nd, imgsz, conf, iou, single_cls, max_wh,
-                       lab_cls, lab_box, lab_off, M, scale, predn, correct, counts);
+#define VM_LAUNCH(GW)                                                                                                                        \
+  hipLaunchKernelGGL((val_postprocess_match_kernel<T, GW>), dim3(B), dim3(PP_THREADS), 0, st, p, nq, nd, imgsz, conf, iou, single_cls, max_wh, \
+                     lab_cls, lab_box, lab_off, M, scale, predn, correct, counts)
+  PP_LAUNCH_GW(nd - 4, VM_LAUNCH);
+#undef VM_LAUNCH
 }
 
 extern "C" int tamtr_val_postprocess_match(const void* preds, int dtype, int B, int nq, int nd, float imgsz, float conf, float iou,

@@ -1863,6 +1863,33 @@ def _f32_nearest(x):
     return float(np.float32(x))
 
 
+def _class_filter(classes):
+    """classes: None, a tensor or a list -> (i32 tensor or None, n_classes).  An empty filter keeps nothing (the reference's `.any(1)`
+    over no classes) and still needs a non-NULL pointer: it travels as one zero with n_classes = 0."""
+    if classes is None:
+        return None, 0
+    cl = torch.as_tensor(classes, dtype=torch.int32).reshape(-1)
+    return (cl if cl.numel() else torch.zeros(1, dtype=torch.int32, device=cl.device)), cl.numel()
+
+
+def _upload(dev, *parts):
+    """Flat i32 / f32 operands (None passes through) -> the same, contiguous, those on the host now on dev: they go up in ONE copy (a
+    float operand travels as its bits), without synchronisation."""
+    host = [p for p in parts if p is not None and not p.is_cuda]
+    up = iter(torch.cat([p.view(torch.int32) for p in host]).to(dev, non_blocking=True).split([p.numel() for p in host])) if host else None
+    return [None if p is None else _c(p if p.is_cuda else next(up).view(p.dtype)) for p in parts]
+
+
+def _merge_operands(vt_host, classes, dev, B, max_out, nd, n_counters):
+    """What tta_merge and slice_merge share: the view table f32 (host) and the class filter on dev in one copy, and the outputs
+    -> (vt, cl, n_classes, ym f32 [B, max_out, nd], src i32 [B, max_out], n_counters counters i32 [B])."""
+    cl, n_cl = _class_filter(classes)
+    vt, cl = _upload(dev, vt_host.reshape(-1), cl)
+    ym = torch.empty(B, max(max_out, 0), nd, device=dev, dtype=torch.float32)
+    src = torch.empty(B, max(max_out, 0), device=dev, dtype=torch.int32)
+    return vt, cl, n_cl, ym, src, tuple(torch.empty(B, device=dev, dtype=torch.int32) for _ in range(n_counters))
+
+
 @torch.no_grad()
 def detect_postprocess(y, orig_hw, conf, iou, classes=None, single_cls=False, max_wh=7680.):
     """RTDETRPredictor.postprocess (models/rtdetrworld/predict.py:34-78) for the whole batch in one launch: class max,
@@ -1879,13 +1906,8 @@ def detect_postprocess(y, orig_hw, conf, iou, classes=None, single_cls=False, ma
     hw = torch.as_tensor(orig_hw, dtype=torch.int32)
     if tuple(hw.shape) != (B, 2):
         raise _lib.TamtrHipError(f'detect_postprocess: orig_hw must be [B, 2] = [{B}, 2], got {tuple(hw.shape)}')
-    # an empty filter keeps nothing (the reference's `.any(1)` over no classes) and still needs a non-NULL pointer
-    cl = None if classes is None else torch.as_tensor(classes, dtype=torch.int32).reshape(-1)
-    n_cl = 0 if cl is None else cl.numel()
-    parts = [hw.reshape(-1)] + ([] if cl is None else [cl if n_cl else torch.zeros(1, dtype=torch.int32, device=hw.device)])
-    if not all(p.is_cuda for p in parts):   # host operands go up in one copy
-        parts = list(torch.cat([p.cpu() for p in parts]).to(dev, non_blocking=True).split([p.numel() for p in parts]))
-    hw, cl = _c(parts[0]), (_c(parts[1]) if cl is not None else None)
+    cl, n_cl = _class_filter(classes)
+    hw, cl = _upload(dev, hw.reshape(-1), cl)      # host operands go up in one copy
     out = torch.empty(B, nq, 6, device=dev, dtype=torch.float32)
     keep = torch.empty(B, nq, device=dev, dtype=torch.int32)
     counts = torch.empty(B, device=dev, dtype=torch.int32)
@@ -1968,24 +1990,8 @@ def tta_merge(ys, views, conf, iou, classes=None, single_cls=False, max_wh=7680.
     if len(table) != V:
         raise _lib.TamtrHipError(f'tta_merge: {V} outputs need {V} views, got {len(table)}')
     max_out = int(max_out)
-    vt = torch.tensor([[kx, ky, float(f), 0.0] for kx, ky, f in table], dtype=torch.float32).reshape(-1)
-    # an empty filter keeps nothing and still needs a non-NULL pointer, as in detect_postprocess
-    cl = None if classes is None else torch.as_tensor(classes, dtype=torch.int32).reshape(-1)
-    n_cl = 0 if cl is None else cl.numel()
-    if cl is None:
-        vt = vt.to(dev, non_blocking=True)
-    else:      # host operands go up in one copy (the table travels as its bits)
-        cl = cl if n_cl else torch.zeros(1, dtype=torch.int32, device=cl.device)
-        if cl.is_cuda:
-            vt = vt.to(dev, non_blocking=True)
-        else:
-            up = torch.cat([vt.view(torch.int32), cl]).to(dev, non_blocking=True)
-            vt, cl = up[:vt.numel()].view(torch.float32), up[vt.numel():]
-        cl = _c(cl)
-    ym = torch.empty(B, max(max_out, 0), nd, device=dev, dtype=torch.float32)
-    src = torch.empty(B, max(max_out, 0), device=dev, dtype=torch.int32)
-    counts = torch.empty(B, device=dev, dtype=torch.int32)
-    dropped = torch.empty(B, device=dev, dtype=torch.int32)
+    vt = torch.tensor([[kx, ky, float(f), 0.0] for kx, ky, f in table], dtype=torch.float32)
+    vt, cl, n_cl, ym, src, (counts, dropped) = _merge_operands(vt, classes, dev, B, max_out, nd, 2)
     pv = (ctypes.c_void_p * V)(*[y.data_ptr() for y in ys])
     call('tamtr_tta_merge', ctypes.cast(pv, ctypes.c_void_p), V, dtype_code(ys[0]), B, nq, nd, ptr(vt), float(conf), _f32_at_most(float(iou)),
          int(bool(single_cls)), float(max_wh), ptr(cl) if cl is not None else None, n_cl, max_out, ptr(ym), ptr(src), ptr(counts),
@@ -2070,23 +2076,7 @@ def slice_merge(y, view_off, windows, hws, conf, iou, classes=None, single_cls=F
     if len(fac) != N:
         raise _lib.TamtrHipError(f'slice_merge: {N} view outputs need {N} windows, got {len(fac)}')
     max_out = int(max_out)
-    vt = torch.from_numpy(fac).reshape(-1)
-    # an empty filter keeps nothing and still needs a non-NULL pointer, as in detect_postprocess
-    cl = None if classes is None else torch.as_tensor(classes, dtype=torch.int32).reshape(-1)
-    n_cl = 0 if cl is None else cl.numel()
-    if cl is None:
-        vt = vt.to(dev, non_blocking=True)
-    else:      # host operands go up in one copy (the table travels as its bits)
-        cl = cl if n_cl else torch.zeros(1, dtype=torch.int32, device=cl.device)
-        if cl.is_cuda:
-            vt = vt.to(dev, non_blocking=True)
-        else:
-            up = torch.cat([vt.view(torch.int32), cl]).to(dev, non_blocking=True)
-            vt, cl = up[:vt.numel()].view(torch.float32), up[vt.numel():]
-        cl = _c(cl)
-    ym = torch.empty(B, max(max_out, 0), nd, device=dev, dtype=torch.float32)
-    src = torch.empty(B, max(max_out, 0), device=dev, dtype=torch.int32)
-    counts, dropped, overflow = (torch.empty(B, device=dev, dtype=torch.int32) for _ in range(3))
+    vt, cl, n_cl, ym, src, (counts, dropped, overflow) = _merge_operands(torch.from_numpy(fac), classes, dev, B, max_out, nd, 3)
     offs = (ctypes.c_int32 * (B + 1))(*off)
     call('tamtr_slice_merge', ptr(y), dtype_code(y), N, B, nq, nd, ctypes.cast(offs, ctypes.c_void_p), ptr(vt), SLICE_MATCH[match], float(conf),
          _f32_at_most(float(iou)), int(bool(single_cls)), float(max_wh), ptr(cl) if cl is not None else None, n_cl, max_out, ptr(ym), ptr(src),

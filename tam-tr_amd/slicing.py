@@ -13,7 +13,7 @@ import torch
 
 from . import ops
 from .ops import SLICE_MAX_CAND, SLICE_MAX_VIEWS, slice_view_factors
-from .tta import _nms_host as _nms_iou_host
+from .tta import _eval_forward, _event_marker, merge_images_host
 
 
 # ------------------------------------------------------------------------------------------------ the grid
@@ -87,70 +87,20 @@ def map_host(y, view_off, windows, hws):
     return y
 
 
-def _nms_host(boxes, scores, thr, match):
-    """tta._nms_host (torchvision's CPU NMS: fp32, no eps, the fp32 overlap compared with the double threshold, scores sorted
-    descending and stable) with the overlap of `match`: 'iou', or 'ios' = inter / min(area_i, area_j).  -> indices in keep order."""
-    if match == 'iou':
-        return _nms_iou_host(boxes, scores, thr)
-    order = scores.sort(descending=True, stable=True).indices
-    x1, y1, x2, y2 = boxes[order].unbind(1)
-    areas = (x2 - x1) * (y2 - y1)
-    n = len(order)
-    later = torch.arange(n)
-    suppressed = torch.zeros(n, dtype=torch.bool)
-    zero = torch.zeros((), dtype=torch.float32)
-    keep = []
-    for i in range(n):
-        if suppressed[i]:
-            continue
-        keep.append(i)
-        xx1 = torch.where(x1[i] < x1, x1, x1[i])      # std::max(ix1, x1[j])
-        yy1 = torch.where(y1[i] < y1, y1, y1[i])
-        xx2 = torch.where(x2 < x2[i], x2, x2[i])      # std::min(ix2, x2[j])
-        yy2 = torch.where(y2 < y2[i], y2, y2[i])
-        dx, dy = xx2 - xx1, yy2 - yy1
-        inter = torch.where(zero < dx, dx, zero) * torch.where(zero < dy, dy, zero)
-        ovr = inter / torch.where(areas < areas[i], areas, areas[i])      # std::min(area_i, area_j)
-        suppressed |= (ovr.double() > thr) & (later > i)
-    return order[torch.as_tensor(keep, dtype=torch.long)]
-
-
 def merge_host(y, view_off, windows, hws, conf, iou, classes=None, single_cls=False, match='iou', max_out=512, max_cand=SLICE_MAX_CAND,
                max_wh=7680.):
     """The rule of ops.slice_merge on the CPU in fp32, with its arguments: frame b's candidates are the mapped rows of its views
     view_off[b] .. view_off[b + 1] - 1 in order (candidate i = v_local * nq + q); class max, `score > conf`, the class filter; the
     first max_cand passing candidates in ascending i go on and the others are counted in overflow; class-aware greedy NMS on `match`
-    (equal scores: the lower candidate first), the first max_out survivors.
+    (equal scores: the lower candidate first), the first max_out survivors: map_host, then tta.merge_rows_host per frame.
     -> (ym [B, max_out, 4 + nc], src i32 [B, max_out], counts, dropped, overflow i32 [B])."""
     if match not in ops.SLICE_MATCH:
         raise ValueError(f"match must be 'iou' or 'ios', got {match!r}")
     y = torch.cat(list(y)) if isinstance(y, (list, tuple)) else y
     rows = map_host(y, view_off, windows, hws)
-    off = [int(o) for o in view_off]
-    B, nd = len(off) - 1, rows.shape[2]
-    ym = torch.zeros(B, max_out, nd)
-    src = torch.full((B, max_out), -1, dtype=torch.int32)
-    counts, dropped, overflow = (torch.zeros(B, dtype=torch.int32) for _ in range(3))
-    for b in range(B):
-        cat = rows[off[b]:off[b + 1]].reshape(-1, nd)
-        bbox, scores = cat[:, :4], cat[:, 4:]
-        dw, dh = bbox[:, 2] / 2, bbox[:, 3] / 2
-        xyxy = torch.stack([bbox[:, 0] - dw, bbox[:, 1] - dh, bbox[:, 0] + dw, bbox[:, 1] + dh], 1)
-        score, cls = scores.max(-1)
-        ok = score > conf
-        if classes is not None:
-            ok = (cls[:, None] == torch.as_tensor(classes, dtype=torch.long).reshape(-1)).any(1) & ok
-        cand = ok.nonzero().view(-1)
-        overflow[b] = max(len(cand) - max_cand, 0)
-        cand = cand[:max_cand]
-        shifted = xyxy[cand] + cls[cand, None].float() * (0 if single_cls else max_wh)
-        kept = cand[_nms_host(shifted, score[cand], iou, match)]
-        n = min(len(kept), max_out)
-        ym[b, :n] = cat[kept[:n]]
-        src[b, :n] = kept[:n].to(torch.int32)
-        counts[b] = n
-        dropped[b] = len(kept) - n
-    return ym, src, counts, dropped, overflow
+    off, nd = [int(o) for o in view_off], rows.shape[2]
+    return merge_images_host([rows[a:b].reshape(-1, nd) for a, b in zip(off, off[1:])], nd, conf, iou, classes, single_cls, match, max_out,
+                             max_cand, max_wh)
 
 
 def check_overflow(overflow, conf):
@@ -184,12 +134,7 @@ def sliced_forward(model, origs_dev, windows_per_frame, imgsz, batch, txt_feats=
                          f'{len(origs_dev)} frames (use larger slices or less overlap)')
     off = np.concatenate([[0], np.cumsum([len(w) for w in wins])]).tolist()
     N, batch = off[-1], max(int(batch), 1)
-
-    def mark():
-        if events is not None:
-            events.append(torch.cuda.Event(enable_timing=True))
-            events[-1].record()
-
+    mark = _event_marker(events)
     mark()
     x = torch.empty(N, 3, imgsz, imgsz, device=origs_dev[0].device, dtype=torch.float32)
     for b, (o, w) in enumerate(zip(origs_dev, wins)):
@@ -198,9 +143,7 @@ def sliced_forward(model, origs_dev, windows_per_frame, imgsz, batch, txt_feats=
     ys = []
     for k in range(0, N, batch):
         xc = x[k:k + batch]
-        with torch.autocast('cuda', dtype=autocast_dtype or torch.bfloat16, enabled=autocast_dtype is not None):
-            preds = model(xc) if txt_feats is None else model(xc, txt_feats=txt_feats.expand(len(xc), -1, -1))
-        ys.append(preds[0] if isinstance(preds, (list, tuple)) else preds)
+        ys.append(_eval_forward(model, xc, None if txt_feats is None else txt_feats.expand(len(xc), -1, -1), autocast_dtype))
     y = ys[0] if len(ys) == 1 else torch.cat(ys)
     mark()
     merged = ops.slice_merge(y, off, np.concatenate(wins), [tuple(o.shape[:2]) for o in origs_dev], conf, iou, classes, single_cls, match,

@@ -64,9 +64,10 @@ def deaugment_host(ys, table):
     return torch.cat(rows, 1)
 
 
-def _nms_host(boxes, scores, iou):
-    """torchvision.ops.nms as its CPU kernel computes it (fp32, no eps, the fp32 IoU compared with the double threshold), the scores
-    sorted descending and stable -> indices into boxes, in keep order."""
+def nms_host(boxes, scores, thr, match='iou'):
+    """torchvision.ops.nms as its CPU kernel computes it (fp32, no eps, the fp32 overlap compared with the double threshold), the scores
+    sorted descending and stable, with the overlap of `match`: 'iou', or 'ios' = inter / min(area_i, area_j) -> indices into boxes, in
+    keep order."""
     order = scores.sort(descending=True, stable=True).indices
     x1, y1, x2, y2 = boxes[order].unbind(1)
     areas = (x2 - x1) * (y2 - y1)
@@ -85,43 +86,78 @@ def _nms_host(boxes, scores, iou):
         yy2 = torch.where(y2 < y2[i], y2, y2[i])
         dx, dy = xx2 - xx1, yy2 - yy1
         inter = torch.where(zero < dx, dx, zero) * torch.where(zero < dy, dy, zero)
-        ovr = inter / ((areas[i] + areas) - inter)
-        suppressed |= (ovr.double() > iou) & (later > i)
+        if match == 'iou':
+            ovr = inter / ((areas[i] + areas) - inter)
+        else:
+            ovr = inter / torch.where(areas < areas[i], areas, areas[i])      # std::min(area_i, area_j)
+        suppressed |= (ovr.double() > thr) & (later > i)
     return order[torch.as_tensor(keep, dtype=torch.long)]
 
 
+_nms_host = nms_host
+
+
+def merge_rows_host(cat, conf, iou, classes, single_cls, match, max_out, max_cand, max_wh):
+    """The merge rule of ops.tta_merge and ops.slice_merge for ONE image: cat [N, 4 + nc], its candidates' de-augmented / mapped rows in
+    fp32 -> class max, `score > conf`, the class filter; the first max_cand passing candidates in ascending order go on (None: all);
+    class-aware greedy NMS on `match` (equal scores: the lower candidate first); the first max_out survivors.
+    -> (their rows, their candidates i32, their number, the survivors that did not fit, the passing candidates beyond max_cand)."""
+    bbox, scores = cat[:, :4], cat[:, 4:]
+    dw, dh = bbox[:, 2] / 2, bbox[:, 3] / 2
+    xyxy = torch.stack([bbox[:, 0] - dw, bbox[:, 1] - dh, bbox[:, 0] + dw, bbox[:, 1] + dh], 1)
+    score, cls = scores.max(-1)
+    ok = score > conf
+    if classes is not None:
+        ok = (cls[:, None] == torch.as_tensor(classes, dtype=torch.long).reshape(-1)).any(1) & ok
+    cand = ok.nonzero().view(-1)
+    overflow = 0 if max_cand is None else max(len(cand) - max_cand, 0)
+    cand = cand[:max_cand]
+    shifted = xyxy[cand] + cls[cand, None].float() * (0 if single_cls else max_wh)
+    kept = cand[nms_host(shifted, score[cand], iou, match)]
+    n = min(len(kept), max_out)
+    return cat[kept[:n]], kept[:n].to(torch.int32), n, len(kept) - n, overflow
+
+
+def merge_images_host(images, nd, conf, iou, classes, single_cls, match, max_out, max_cand, max_wh):
+    """merge_rows_host over the images' rows [N_b, nd], padded as the kernels pad: -> (ym [B, max_out, nd] with zero rows after the
+    count, src i32 [B, max_out] with -1 after it, counts, dropped, overflow i32 [B])."""
+    B = len(images)
+    ym = torch.zeros(B, max_out, nd)
+    src = torch.full((B, max_out), -1, dtype=torch.int32)
+    counts, dropped, overflow = (torch.zeros(B, dtype=torch.int32) for _ in range(3))
+    for b, cat in enumerate(images):
+        rows, cand, n, dropped[b], overflow[b] = merge_rows_host(cat, conf, iou, classes, single_cls, match, max_out, max_cand, max_wh)
+        ym[b, :n], src[b, :n], counts[b] = rows, cand, n
+    return ym, src, counts, dropped, overflow
+
+
 def merge_host(ys, views, conf, iou, classes=None, single_cls=False, max_wh=7680., max_out=512, size=None, gs=GS):
-    """The rule of ops.tta_merge on the CPU in fp32, with its arguments: the concatenation of the de-augmented rows, class max,
-    `score > conf`, the class filter, class-aware NMS (equal scores: the lower candidate first), the first max_out survivors.
+    """The rule of ops.tta_merge on the CPU in fp32, with its arguments: the concatenation of the de-augmented rows, then merge_rows_host
+    per image (IoU, no candidate limit).
     -> (ym [B, max_out, 4 + nc], src i32 [B, max_out], counts i32 [B], dropped i32 [B])."""
     views = list(views)
     table = tta_view_factors(views, size, gs) if size is not None else [(float(kx), float(ky), bool(f)) for kx, ky, f in views]
     cat = deaugment_host(ys, table)
-    B, N, nd = cat.shape
-    ym = torch.zeros(B, max_out, nd)
-    src = torch.full((B, max_out), -1, dtype=torch.int32)
-    counts = torch.zeros(B, dtype=torch.int32)
-    dropped = torch.zeros(B, dtype=torch.int32)
-    for b in range(B):
-        bbox, scores = cat[b, :, :4], cat[b, :, 4:]
-        dw, dh = bbox[:, 2] / 2, bbox[:, 3] / 2
-        xyxy = torch.stack([bbox[:, 0] - dw, bbox[:, 1] - dh, bbox[:, 0] + dw, bbox[:, 1] + dh], 1)
-        score, cls = scores.max(-1)
-        ok = score > conf
-        if classes is not None:
-            ok = (cls[:, None] == torch.as_tensor(classes, dtype=torch.long).reshape(-1)).any(1) & ok
-        cand = ok.nonzero().view(-1)
-        shifted = xyxy[cand] + cls[cand, None].float() * (0 if single_cls else max_wh)
-        kept = cand[_nms_host(shifted, score[cand], iou)]
-        n = min(len(kept), max_out)
-        ym[b, :n] = cat[b, kept[:n]]
-        src[b, :n] = kept[:n].to(torch.int32)
-        counts[b] = n
-        dropped[b] = len(kept) - n
-    return ym, src, counts, dropped
+    return merge_images_host(cat, cat.shape[2], conf, iou, classes, single_cls, 'iou', max_out, None, max_wh)[:4]
 
 
 # ------------------------------------------------------------------------------------------------ the forward
+def _event_marker(events):
+    """-> mark(): appends a recorded CUDA timing event to `events` (a list, or None: nothing happens)."""
+    def mark():
+        if events is not None:
+            events.append(torch.cuda.Event(enable_timing=True))
+            events[-1].record()
+    return mark
+
+
+def _eval_forward(model, x, txt_feats, autocast_dtype):
+    """The model's eval output [len(x), nq, 4 + nc] on x (and txt_feats, when given), under autocast when autocast_dtype is set."""
+    with torch.autocast('cuda', dtype=autocast_dtype or torch.bfloat16, enabled=autocast_dtype is not None):
+        preds = model(x) if txt_feats is None else model(x, txt_feats=txt_feats)
+    return preds[0] if isinstance(preds, (list, tuple)) else preds
+
+
 @torch.no_grad()
 def tta_forward(model, img, txt_feats=None, views=DEFAULT_VIEWS, conf=0.25, iou=0.7, classes=None, single_cls=False, max_out=512,
                 autocast_dtype=None, keep=False, events=None):
@@ -133,12 +169,7 @@ def tta_forward(model, img, txt_feats=None, views=DEFAULT_VIEWS, conf=0.25, iou=
     Nothing synchronises."""
     views = check_views(views)
     B, _, H, W = img.shape
-
-    def mark():
-        if events is not None:
-            events.append(torch.cuda.Event(enable_timing=True))
-            events[-1].record()
-
+    mark = _event_marker(events)
     mark()
     xs = [ops.tta_view(img, r, f, GS) for r, f in views]
     mark()
@@ -148,12 +179,7 @@ def tta_forward(model, img, txt_feats=None, views=DEFAULT_VIEWS, conf=0.25, iou=
     ys = [None] * len(views)
     for ks in groups.values():
         x = xs[ks[0]] if len(ks) == 1 else torch.cat([xs[k] for k in ks])
-        with torch.autocast('cuda', dtype=autocast_dtype or torch.bfloat16, enabled=autocast_dtype is not None):
-            if txt_feats is None:
-                preds = model(x)
-            else:
-                preds = model(x, txt_feats=txt_feats if len(ks) == 1 else txt_feats.repeat(len(ks), 1, 1))
-        y = preds[0] if isinstance(preds, (list, tuple)) else preds
+        y = _eval_forward(model, x, txt_feats if txt_feats is None or len(ks) == 1 else txt_feats.repeat(len(ks), 1, 1), autocast_dtype)
         for k, part in zip(ks, y.split(B)):
             ys[k] = part
     mark()
